@@ -117,6 +117,24 @@ int pcabo_gp_condition_end(pcabo_ctx* ctx);
 int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq,
                                 double* val);
 
+/* Opt-in GP hyperparameter fit (not in the reference, which never trains its SingleTaskGP; DESIGN.md "GP hyperparameter fit").
+ * theta = {noise s2, mean constant c, raw lengthscale rho}, lengthscale = softplus(rho); the model's initial values are
+ * {exp(-5), 0, 0}.  loss = -[log N(y_s; c 1, K + s2 I) + log LogNormal(s2; -4, 1)] / n, what botorch's fit_gpytorch_mll minimises
+ * for SingleTaskGP(MaternKernel(2.5), Standardize, Normalize).  Matern-5/2 only (PCABO_KERNEL_RBF: PCABO_ERR_ARG); exact
+ * Cholesky with the jitter retries of pcabo_gp_condition at every n.  The other arguments as in pcabo_gp_condition.
+ * Loss and gradient at theta; leaves the context conditioned at theta (acquisition calls may follow). */
+int pcabo_gp_mll(pcabo_ctx* ctx, const double* Z /* NULL: Z of the last wPCA */, const double* y, int n, int k,
+                 const double* norm_bounds, int kernel, const double* theta /*3*/, double* loss, double* grad /*3*/);
+/* The whole fit from theta_inout: host L-BFGS-B with scipy's defaults (m 10, factr 1e7, pgtol 1e-5, maxls 20, maxiter = maxfun
+ * = 15000, the published summation order), bound s2 >= 1e-4, one attempt.  On return theta_inout holds the fitted theta, *loss
+ * its loss, and the context is conditioned there (acquisition calls follow directly).
+ * info[4] = {iterations, evaluations, warnflag (scipy's: 0 converged, 1 limit, 2 abnormal), task (LBFGSB_* code of the
+ * optimiser, or PCABO_FIT_TASK_NOT_PD when a trial theta could not be factored even with jitter)}.  A fit that ends abnormally
+ * keeps the last accepted iterate (or the start) and still returns PCABO_OK: the caller reads warnflag. */
+#define PCABO_FIT_TASK_NOT_PD (-2)
+int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
+                 double* theta_inout /*3*/, double* loss, int* info /*4*/);
+
 /* Rows A-H as ONE enqueue: pcabo_wpca immediately followed by pcabo_gp_condition_begin(Z = NULL,
  * norm_bounds = NULL), i.e. PCA_BO._transform_points_to_reduced_space + _initialize_model of one iteration
  * (PCA_BO.py:343-408 and :502-545) without the host round trip between them: the conditioning launches are queued

@@ -50,6 +50,16 @@ NOISE = 0.006737946999085467         # exp(-5), mode of the LogNormal(-4, 1) noi
 OOB_PENALTY = 1000
 
 
+def fit_gp_hyperparameters(ctx, y, Z=None, norm_bounds=None) -> dict:
+    """fit_gpytorch_mll(ExactMarginalLogLikelihood(...)) of a freshly built model, on the device (Context.gp_fit); like botorch,
+    a fit that does not converge keeps its last iterate and warns."""
+    hp = ctx.gp_fit(y, Z=Z, norm_bounds=norm_bounds, kernel=_native.KERNEL_MATERN52)
+    if hp["warnflag"] != 0:
+        warnings.warn(f"GP hyperparameter fit did not converge (warnflag {hp['warnflag']}, task {hp['task']}); keeping the last "
+                      "accepted iterate", RuntimeWarning)
+    return hp
+
+
 class AnalyticAcquisitionFunction:
     """Descriptor of the acquisition the device kernels evaluate (stands in for botorch's class)."""
     acq_code = _native.ACQ_LOG_EI
@@ -132,6 +142,11 @@ class PCA_BO(AbstractBayesianOptimizer):
         self.__fused = bool(kwargs.pop("fused_enqueue", True))
         self.__early_scoring = bool(kwargs.pop("early_scoring", True))
         self.__speculate_engine = bool(kwargs.pop("engine_guess", True))
+        # fit_gp=True (not in the reference, which never trains its GP): every iteration fits (noise, mean constant, lengthscale)
+        # by the marginal likelihood from the model's initial values before the acquisition (Context.gp_fit, DESIGN.md "GP
+        # hyperparameter fit"); takes the unfused wPCA -> fit path.  False keeps the reference's fixed hyperparameters.
+        self.__fit_gp = bool(kwargs.pop("fit_gp", False))
+        self.gp_hyperparameters = None     # fit_gp=True: the last fit's result (Context.gp_fit), None otherwise
         self.__gc_entered = False
         super().__init__(budget, n_DoE, **kwargs)
         self.random_seed = random_seed
@@ -347,7 +362,7 @@ class PCA_BO(AbstractBayesianOptimizer):
         ranks = self._calculate_ranks()
         noise = self._take_noise(X.shape)                      # same draw, same global RNG as the reference
         start = perf_counter()
-        if self.__fused:
+        if self.__fused and not self.__fit_gp:
             # rows A-H in one enqueue: the GP conditioning is queued right behind the projection and runs while the
             # wPCA results travel back (`_initialize_model` then has nothing left to launch)
             self.__ctx.wpca_gp_condition(
@@ -394,6 +409,10 @@ class PCA_BO(AbstractBayesianOptimizer):
             return
         start = perf_counter()
         if self.__gp_pending:              # already enqueued together with the wPCA
+            self.timing_logs["SingleTaskGP"].append(perf_counter() - start)
+            return
+        if self.__fit_gp:                  # the fit leaves the context conditioned at the fitted hyperparameters
+            self.gp_hyperparameters = fit_gp_hyperparameters(self.__ctx, np.array(self.f_evals, dtype=np.float64))
             self.timing_logs["SingleTaskGP"].append(perf_counter() - start)
             return
         # enqueue only: the device conditions the GP while the host prepares the Sobol engine (gp_wait below)

@@ -24,7 +24,7 @@ from pcabo import initializers as _init
 from .AbstractBayesianOptimizer import AbstractBayesianOptimizer
 from .PCA_BO import (ALLOWED_ACQUISITION_FUNCTION_STRINGS, ALLOWED_SHORTHAND_ACQUISITION_FUNCTION_STRINGS,
                      AnalyticAcquisitionFunction, LogExpectedImprovement, ProbabilityOfImprovement,
-                     UpperConfidenceBound, LENGTHSCALE, NOISE)
+                     UpperConfidenceBound, LENGTHSCALE, NOISE, fit_gp_hyperparameters)
 
 
 class Vanilla_BO(AbstractBayesianOptimizer):
@@ -39,6 +39,8 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         self.__gc_freeze = bool(kwargs.pop("gc_freeze", True))      # see pcabo/gcguard.py
         self.__gc_entered = False
         self.__resident = bool(kwargs.pop("resident", True))         # see PCA_BO: False = one launch per evaluation
+        self.__fit_gp = bool(kwargs.pop("fit_gp", False))             # see PCA_BO: marginal-likelihood fit every iteration
+        self.gp_hyperparameters = None
         super().__init__(budget, n_DoE, **kwargs)
         self.random_seed = random_seed
         smoke_test = os.environ.get("SMOKE_TEST")
@@ -138,6 +140,10 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         X = np.array(self.x_evals, dtype=np.float64).reshape((-1, self.dimension))
         y = np.array(self.f_evals, dtype=np.float64)
         start = perf_counter()
+        if self.__fit_gp:
+            self.gp_hyperparameters = fit_gp_hyperparameters(self.__ctx, y, Z=X, norm_bounds=self.__identity)
+            self.timing_logs["SingleTaskGP"].append(perf_counter() - start)
+            return
         self.__ctx.gp_condition(y, Z=X, norm_bounds=self.__identity, lengthscale=LENGTHSCALE, noise=NOISE,
                                 kernel=_native.KERNEL_MATERN52, wait=False)
         self.timing_logs["SingleTaskGP"].append(perf_counter() - start)
@@ -147,9 +153,11 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         start = perf_counter()
         engine = _init.scrambled_sobol_engine(self.dimension)      # built and drawn while the device conditions the GP
         raw = _init.draw_sobol(self.__box, cfg["RAW_SAMPLES"], engine)
-        t0 = perf_counter()                # the raw samples are scored right behind the conditioning: one wait for both
-        raw_vals = ctx.gp_wait_eval(raw, acq.best_f, acq.maximize, acq.acq_code)
-        self.phase_breakdown["raw_eval"] = self.phase_breakdown.get("raw_eval", 0.0) + perf_counter() - t0
+        raw_vals = None                    # (fit_gp: the GP is conditioned already, the optimiser scores the raw samples)
+        if not self.__fit_gp:
+            t0 = perf_counter()            # the raw samples are scored right behind the conditioning: one wait for both
+            raw_vals = ctx.gp_wait_eval(raw, acq.best_f, acq.maximize, acq.acq_code)
+            self.phase_breakdown["raw_eval"] = self.phase_breakdown.get("raw_eval", 0.0) + perf_counter() - t0
         new_x, cand, vals, info = _acqopt.optimize_acqf(
             ctx, self.__box, acq.best_f, acq.maximize, acq.acq_code, cfg["NUM_RESTARTS"], cfg["RAW_SAMPLES"], 5, 200,
             raw=raw, raw_vals=raw_vals, breakdown=self.phase_breakdown,

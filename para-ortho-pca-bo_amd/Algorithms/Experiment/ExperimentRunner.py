@@ -124,7 +124,14 @@ class ExperimentRunner:
                  budget_factor: int = 10, doe_factor: float = 3.0, root_dir: str = os.getcwd(),
                  experiment_name: str = "experiment", acquisition_function: str = "expected_improvement",
                  pca_components: Optional[int] = None, var_threshold: float = 0.95, verbose: bool = False,
-                 progress: bool = True, batched: int = 0, side_by_side: int = 2, batch_acq_kernel: str = "group"):
+                 progress: bool = True, batched: int = 0, side_by_side: int = 2, batch_acq_kernel: str = "group",
+                 fit_gp: bool = False):
+        # fit_gp (not in the reference): every run fits its GP's hyperparameters by the marginal likelihood each iteration
+        # (PCA_BO / Vanilla_BO fit_gp=True).  The lock-step batches do not fit: the two options exclude each other.
+        self.fit_gp = bool(fit_gp)
+        if self.fit_gp and int(batched) > 1:
+            raise ValueError("fit_gp=True runs one run after the other (batched=0, Algorithms.PCA_BO / Vanilla_BO); the "
+                             "lock-step batches (batched > 1) have no GP fit")
         self.algorithms = algorithms
         self.dimensions = dimensions
         self.problem_ids = problem_ids
@@ -319,6 +326,8 @@ class ExperimentRunner:
                 # (the reference sets the first three, then REPLACES them by the PCA pair for "pca" - ExperimentRunner.py:105-117,
                 # kept; `arithmetic_mode` is this package's: which summation order produced the rows of each dimension)
                 provenance = {"arithmetic_mode": ",".join(f"d{dim}={self.arithmetic_modes[dim]}" for dim in self.dimensions)}
+                if self.fit_gp:
+                    provenance["gp_fit"] = "map"         # hyperparameters fitted by the marginal likelihood (+ noise prior)
                 logger.set_experiment_attributes({
                     "budget_factor": f"{self.budget_factor}",
                     "doe_factor": f"{self.doe_factor}",
@@ -364,6 +373,8 @@ class ExperimentRunner:
                                       random_seed=random_seed, maximization=maximization, verbose=self.verbose,
                                       DoE_parameters=self.doe_params, pbar=pbar if self.progress else None,
                                       device=self.device)
+                        if self.fit_gp:
+                            common["fit_gp"] = True
                         if algorithm == "vanilla":
                             optimizer = Vanilla_BO(**common)
                         else:

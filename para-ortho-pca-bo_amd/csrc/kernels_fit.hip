@@ -1,0 +1,136 @@
+// Marginal-likelihood gradient of the exact GP on gfx950 (opt-in hyperparameter fit, DESIGN.md "GP hyperparameter fit").
+//
+// At a conditioned state (L = chol(K), R = L^-1, alpha = K^-1 y_s, all from kernels_gp.hip) the fit needs, besides the scalar
+// pieces of the loss, the two contractions
+//   tr K^-1                       and   S = sum_ij W_ij dK_ij/dlog l,   W = alpha alpha^T - K^-1,
+// where dK/dlog l = (5/3) r^2 (1 + sqrt5 r) exp(-sqrt5 r) for Matern-5/2 (0 on the diagonal).  K^-1 = R^T R is formed tile by
+// tile on f64 MFMA and consumed in the epilogue: it never goes to memory.
+//
+// Storage as in kernels_gp.hip: R is NP x NP row-major (leading dimension ld), lower triangular, identity on the padding.
+#include "pcabo_internal.h"
+
+#define BS PCABO_BS
+
+// One work-group per 64 x 64 lower tile (I >= J) of K^-1, wave w owns rows 16w .. 16w+15 of the tile:
+//   K^-1[I][J] = sum_{P >= I} R[P][I]^T R[P][J]   (R[P][I] = 0 for P < I),
+// i.e. (K^-1)_ij = sum_p R_pi R_pj over the rows p >= 64 I.  A lane's MFMA operands are 16 consecutive columns of one row of R
+// (A[i][kk] = R[p0+kk][i], B[kk][j] = R[p0+kk][j]): 128-byte row segments, coalesced.  The epilogue rebuilds the tile's scaled
+// distances from AT / nrm with k_gram's MFMA form (the same bits as the Gram the factorisation saw), then reduces
+//   W_ij dK_ij  (i, j < n)   and, on the diagonal tiles, (K^-1)_ii  (i < n)
+// in a fixed order (per thread, then the wave, then the four waves).  Off-diagonal tiles count twice (W and dK are symmetric).
+// partial[2 t], partial[2 t + 1]: tile t's two sums; k_mll_finish adds them in tile order.
+__global__ __launch_bounds__(256) void k_mll_grad(const double* __restrict__ R, const double* __restrict__ AT,
+                                                  const double* __restrict__ nrm, const double* __restrict__ alpha, int n,
+                                                  int NP, int KP, int ld, double* __restrict__ partial) {
+  __shared__ double s_red[2][4];
+  const int t = blockIdx.x;
+  int I = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);           // t = I (I + 1) / 2 + J, 0 <= J <= I
+  while ((I + 1) * (I + 2) / 2 <= t) ++I;
+  while (I * (I + 1) / 2 > t) --I;
+  const int J = t - I * (I + 1) / 2;
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int ci = I * BS + 16 * w, cj = J * BS;                 // first column of this wave's A rows / of the tile's B columns
+  double4_t acc[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) acc[q] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  // K^-1 tile: rows p = 64 I .. NP - 1 of R (a multiple of 64 rows), 16 rows per trip: 20 loads in flight per lane
+  for (int p0 = I * BS; p0 < NP; p0 += 16) {
+    double a[4], b[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double* row = R + (size_t)(p0 + 4 * u + (l >> 4)) * ld;
+      a[u] = row[ci + (l & 15)];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) b[u][q] = row[cj + 16 * q + (l & 15)];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u][q], acc[q], 0, 0, 0);
+  }
+  // scaled distances of the tile, exactly as k_gram forms them
+  double4_t dd[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) dd[q] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  for (int kk = 0; kk < KP; kk += 4) {
+    const double* row = AT + (size_t)(kk + (l >> 4)) * ld;
+    const double a = row[ci + (l & 15)];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const double b = row[cj + 16 * q + (l & 15)];
+      dd[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, dd[q], 0, 0, 0);
+    }
+  }
+  const double s5 = 2.23606797749979;   // sqrt(5)
+  double sw = 0.0, st = 0.0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int j = cj + 16 * q + (l & 15);                      // f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 reg
+    const bool jn = j < n;
+    const double nj = jn ? nrm[j] : 0.0, aj = jn ? alpha[j] : 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = ci + (l >> 4) + 4 * r;
+      if (i >= n || !jn) continue;
+      const double kinv = acc[q][r];
+      if (i == j) {
+        st += kinv;                                            // dK_ii = 0: the diagonal adds to the trace only
+        continue;
+      }
+      double sq = (nrm[i] + nj) - 2.0 * dd[q][r];
+      sq = fmax(sq, 0.0);
+      const double dist = sqrt(fmax(sq, 1e-30));
+      const double dk = (5.0 / 3.0) * (dist * dist) * (1.0 + s5 * dist) * exp(-s5 * dist);
+      sw += (alpha[i] * aj - kinv) * dk;
+    }
+  }
+  sw = wave_sum(sw);
+  st = wave_sum(st);
+  if (l == 0) { s_red[0][w] = sw; s_red[1][w] = st; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double f = (I == J) ? 1.0 : 2.0;
+    partial[2 * t] = f * (((s_red[0][0] + s_red[0][1]) + s_red[0][2]) + s_red[0][3]);
+    partial[2 * t + 1] = ((s_red[1][0] + s_red[1][1]) + s_red[1][2]) + s_red[1][3];
+  }
+}
+
+// The scalar pieces, one work-group, fixed order (strided per thread, then the waves in order):
+//   out[0] = sum_i log L_ii,  out[1] = y_s^T alpha,  out[2] = sum_i alpha_i,  out[3] = alpha^T alpha,
+//   out[4] = tr K^-1,         out[5] = S             (the tile partials of k_mll_grad in tile order)
+#define MLL_FIN_THREADS 256
+__global__ __launch_bounds__(MLL_FIN_THREADS) void k_mll_finish(const double* __restrict__ L, const double* __restrict__ ys,
+                                                               const double* __restrict__ alpha, int n, int ld,
+                                                               const double* __restrict__ partial, int tiles,
+                                                               double* __restrict__ out) {
+  __shared__ double s_red[6][MLL_FIN_THREADS / 64];
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < n; i += MLL_FIN_THREADS) {
+    const double a = alpha[i];
+    v[0] += log(L[(size_t)i * ld + i]);
+    v[1] += ys[i] * a;
+    v[2] += a;
+    v[3] += a * a;
+  }
+  for (int t = tid; t < tiles; t += MLL_FIN_THREADS) { v[5] += partial[2 * t]; v[4] += partial[2 * t + 1]; }
+#pragma unroll
+  for (int u = 0; u < 6; ++u) {
+    const double s = wave_sum(v[u]);
+    if (l == 0) s_red[u][w] = s;
+  }
+  __syncthreads();
+  if (tid < 6) {
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < MLL_FIN_THREADS / 64; ++u) s += s_red[tid][u];
+    out[tid] = s;
+  }
+}
+
+void launch_mll_grad(hipStream_t s, const double* R, const double* AT, const double* nrm, const double* alpha, const double* L,
+                     const double* ys, int n, int NP, int KP, int ld, double* partial, double* out) {
+  const int nb = NP / BS, tiles = nb * (nb + 1) / 2;
+  hipLaunchKernelGGL(k_mll_grad, dim3(tiles), dim3(256), 0, s, R, AT, nrm, alpha, n, NP, KP, ld, partial);
+  hipLaunchKernelGGL(k_mll_finish, dim3(1), dim3(MLL_FIN_THREADS), 0, s, L, ys, alpha, n, ld, partial, tiles, out);
+}

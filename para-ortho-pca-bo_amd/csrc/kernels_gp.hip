@@ -407,7 +407,7 @@ void launch_gram(hipStream_t s, const double* AT, const double* nrm, int n, int 
 void launch_add_jitter(hipStream_t s, double* K, int n, int ld, double jitter) {
   hipLaunchKernelGGL(k_add_jitter, dim3((n + 255) / 256), dim3(256), 0, s, K, n, ld, jitter);
 }
-void launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb) {
+int launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb) {
   const int nblk = NP / BS;
   // Two forms of the same left-looking factorisation, bit-identical (tests/golden/gp_factor_hashes.json):
   //  * k_chol_step (kernels_gpw.hip): ONE launch per panel - final update + panel of column J beside the look-ahead of
@@ -419,7 +419,7 @@ void launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double
   //  * round 4, the oversubscribed case in groups of NC = 4 block columns (k_chol_lookn): one look-back over all earlier panels
   //    for the four columns together (the row tiles L[I][p] read once instead of four times), then per panel of the group the
   //    panel launch and one single-step update of the group's remaining columns - the same number of launches, the same bits.
-  if (zb.B * nblk <= 256) { launch_chol_steps(s, L, NP, ld, info, diag_scratch, zb); return; }
+  if (zb.B * nblk <= 256) return launch_chol_steps(s, L, NP, ld, info, diag_scratch, zb);
   if (zb.B * nblk > 1024) {
     // several waves of work-groups per launch: two independent 4-wave groups per CU overlap one's loads with the other's MFMAs
     // better than one 8-wave group in lock-step (measured round 4, us: 120 runs at n = 1050: 2 468 against 2 602 grouped; the
@@ -429,17 +429,17 @@ void launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double
         hipLaunchKernelGGL(k_chol_lookback, dim3(nblk - p + 1, 1, zb.B), dim3(256), 0, s, L, p, nblk, ld, diag_scratch, zb.zs);
       launch_chol_panel(s, L, p, nblk - p, ld, info, diag_scratch, zb);
     }
-    return;
+    return 0;
   }
   constexpr int NC = CHOL_LOOKN_NC;
   {
     static std::mutex attr_mu;
     static bool attr_done[64] = {false};
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
     std::lock_guard<std::mutex> lk(attr_mu);
     if (!attr_done[dev]) {
-      if (hipFuncSetAttribute((const void*)k_chol_lookn<NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHOL_LOOKN_LDS) != hipSuccess) return;
+      if (hipFuncSetAttribute((const void*)k_chol_lookn<NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHOL_LOOKN_LDS) != hipSuccess) return -1;
       attr_done[dev] = true;
     }
   }
@@ -462,6 +462,7 @@ void launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double
       }
     }
   }
+  return 0;
 }
 void launch_trinv(hipStream_t s, const double* L, int NP, int ld, double* R, ZB zb) {
   const int nblk = NP / BS;

@@ -525,15 +525,15 @@ void launch_chol_panel(hipStream_t s, double* L, int p, int nblocks, int ld, int
   hipLaunchKernelGGL(k_chol_panel_m, dim3(nblocks, 1, zb.B), dim3(128), 0, s, L, p, ld, info, diag_scratch, zb.zs);
 }
 // diag_scratch: TWO 64 x 64 tiles
-void launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb) {
+int launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb) {
   static std::mutex attr_mu;
   static bool attr_done[64] = {false};
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;   // (nothing factored: the caller reports it)
   {
     std::lock_guard<std::mutex> lk(attr_mu);
     if (!attr_done[dev]) {
-      if (hipFuncSetAttribute((const void*)k_chol_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHOL_STEP_LDS) != hipSuccess) return;
+      if (hipFuncSetAttribute((const void*)k_chol_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHOL_STEP_LDS) != hipSuccess) return -1;
       attr_done[dev] = true;
     }
   }
@@ -542,6 +542,7 @@ void launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, doub
     const int groups = (nblk - J) + (J >= 1 ? nblk - J - 1 : 0) + (J >= 1 ? 1 : 0);
     hipLaunchKernelGGL(k_chol_step, dim3(groups, 1, zb.B), dim3(256), CHOL_STEP_LDS, s, L, J, nblk, ld, info, diag_scratch, zb.zs);
   }
+  return 0;
 }
 void launch_trinv_diag_w(hipStream_t s, const double* L, int nblk, int ld, double* R, ZB zb) {
   hipLaunchKernelGGL(k_trinv_diag_w, dim3(nblk, 1, zb.B), dim3(64), 0, s, L, ld, R, zb.zs);

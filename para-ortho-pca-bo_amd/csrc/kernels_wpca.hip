@@ -507,7 +507,7 @@ __global__ __launch_bounds__(WP_THREADS) void k_zstats(const double* __restrict_
                                                        double* __restrict__ bounds4, double* __restrict__ zn_mean,
                                                        double* __restrict__ ystats, double* __restrict__ ys,
                                                        HostMirror* hm, const int* __restrict__ k_dev, size_t zs,
-                                                       size_t hzs) {
+                                                       size_t hzs, double mean_c) {
   ZRUN(Z); ZRUN(y); ZRUN(user_nb); ZRUN(bounds4); ZRUN(zn_mean); ZRUN(ystats); ZRUN(ys); ZRUN(k_dev);
   hm = zrun(hm, hzs, blockIdx.z);
   if (k_dev) k = *k_dev;          // enqueued behind the wPCA: the reduced dimension is not on the host yet
@@ -562,8 +562,11 @@ __global__ __launch_bounds__(WP_THREADS) void k_zstats(const double* __restrict_
   double var = block_sum_1024(loc, s_red) / (double)(n > 1 ? n - 1 : 1);
   double sd = sqrt(var);
   if (!(sd >= 1e-8)) sd = 1.0;
-  for (int i = tid; i < n; i += WP_THREADS) ys[i] = (y[i] - ym) / sd;
-  if (tid == 0) { ystats[0] = ym; ystats[1] = sd; hm->y_mean = ym; hm->y_std = sd; }
+  // constant mean c of a fitted GP (pcabo_gp_mll): the posterior with mean c is the one with mean 0 and the shift m' = m + s c,
+  // so y_s and the statistics the acquisition kernels read carry m' (c = 0, every other caller: m itself, the same bits)
+  const double ym2 = (mean_c == 0.0) ? ym : ym + sd * mean_c;
+  for (int i = tid; i < n; i += WP_THREADS) ys[i] = (y[i] - ym2) / sd;
+  if (tid == 0) { ystats[0] = ym2; ystats[1] = sd; hm->y_mean = ym2; hm->y_std = sd; }
 }
 
 // Row E: Normalize the training inputs and lay them out for the Gram / acquisition kernels:
@@ -673,9 +676,10 @@ void launch_project(hipStream_t s, const double* X, const double* data_mean, con
                      zb.zs);
 }
 void launch_zstats(hipStream_t s, const double* Z, const double* y, int n, int k, const double* user_norm_bounds,
-                   double* bounds4, double* zn_mean, double* ystats, double* ys, HostMirror* hm, const int* k_dev, ZB zb) {
+                   double* bounds4, double* zn_mean, double* ystats, double* ys, HostMirror* hm, const int* k_dev, ZB zb,
+                   double mean_c) {
   hipLaunchKernelGGL(k_zstats, dim3(1, 1, zb.B), dim3(WP_THREADS), 0, s, Z, y, n, k, user_norm_bounds, bounds4, zn_mean,
-                     ystats, ys, hm, k_dev, zb.zs, zb.hzs);
+                     ystats, ys, hm, k_dev, zb.zs, zb.hzs, mean_c);
 }
 void launch_znorm(hipStream_t s, const double* Z, int n, int k, int NP, int KP, int ld, const double* bounds4,
                   const double* zn_mean, double inv_ls, double* ZnT, double* AT, double* nrm, const int* k_dev, ZB zb) {

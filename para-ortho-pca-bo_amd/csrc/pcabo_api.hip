@@ -26,7 +26,7 @@
 #include <unistd.h>
 #include <emmintrin.h>
 
-#define PCABO_ABI_VERSION 1
+#define PCABO_ABI_VERSION 2
 #define PROF_GROUPS 6
 #define PROF_POOL 4096
 
@@ -107,6 +107,7 @@ struct pcabo_ctx {
   int cnt_S = 0; bool cnt_dirty = true;  // slab-group count the tickets are consistent with / a launch may have died
   double* dKS = nullptr;                 // q x ld kernel vectors of the GEMM scoring path
   double* dBestF = nullptr;              // best_f of this run for the batched acquisition launches (set by the batch)
+  double* dMll = nullptr;                // GP fit: 2 partial sums per lower 64 x 64 tile of K^-1, then the 6 results (k_mll_finish)
   char *dRegion = nullptr, *hRegion = nullptr;   // the two allocations everything above / below is carved from
   size_t region_bytes = 0, hregion_bytes = 0;
   bool in_batch = false; int batch_index = 0;
@@ -114,6 +115,7 @@ struct pcabo_ctx {
   // pinned host
   HostMirror* hm = nullptr;
   double *hXq = nullptr, *hVal = nullptr, *hGrad = nullptr, *hSmall = nullptr, *hBestF = nullptr;
+  double* hMll = nullptr;                // GP fit: the 6 results of one evaluation
   MailPair* dMail = nullptr;             // mailbox of the resident acquisition kernel, in device memory
   bool mail_bar = false;                 // the host can write dMail itself through the PCIe BAR (the resident mode needs it)
   MailPair* dPairs = nullptr;            // its partial records as (value, tag) pairs: 32 queries x 32 slabs
@@ -372,6 +374,8 @@ static size_t carve_device(pcabo_ctx* ctx, char* base) {
   ctx->dBestF = c.take<double>(2);
   ctx->dKS = c.take<double>(Q * N);        // kernel vectors of a large value-only batch (GEMM scoring)
   ctx->dCounters = c.take<unsigned int>(PCABO_CNT_DONE + 1);
+  const size_t nb = N / PCABO_BS;
+  ctx->dMll = c.take<double>(nb * (nb + 1) + 8);
   return (c.off + 4095) & ~(size_t)4095;
 }
 static size_t carve_host(pcabo_ctx* ctx, char* base) {
@@ -385,6 +389,7 @@ static size_t carve_host(pcabo_ctx* ctx, char* base) {
   ctx->hSmall = c.take<double>(d * d + 8 * d + 64);
   ctx->hIn = c.take<double>(n * (2 * d + 2));
   ctx->hBestF = c.take<double>(2);
+  ctx->hMll = c.take<double>(8);
   return (c.off + 4095) & ~(size_t)4095;
 }
 
@@ -633,7 +638,11 @@ static int launch_factorisation(pcabo_ctx* ctx, double jitter) {
                 ctx->dL, ctx->dInfo);
     launch_add_jitter(s, ctx->dL, ctx->n, ctx->ld, jitter);
   }
-  { ProfScope ps(ctx, 2, 16.0 * ctx->n * ctx->n, (double)ctx->n * ctx->n * ctx->n / 3.0); launch_cholesky(s, ctx->dL, ctx->NP, ctx->ld, ctx->dInfo, ctx->dDiag); }
+  {
+    ProfScope ps(ctx, 2, 16.0 * ctx->n * ctx->n, (double)ctx->n * ctx->n * ctx->n / 3.0);
+    if (launch_cholesky(s, ctx->dL, ctx->NP, ctx->ld, ctx->dInfo, ctx->dDiag) != 0)
+      return set_err(ctx, PCABO_ERR_HIP, "the Cholesky launches could not be set up (device or kernel attribute)%s", "");
+  }
   {
     ProfScope ps(ctx, 3, 16.0 * ctx->n * ctx->n, (double)ctx->n * ctx->n * ctx->n / 3.0 + 2.0 * ctx->n * ctx->n);
     launch_trinv(s, ctx->dL, ctx->NP, ctx->ld, ctx->dR);
@@ -646,7 +655,7 @@ static int launch_factorisation(pcabo_ctx* ctx, double jitter) {
 // Rows D-H on the stream, inputs on the device.  k < 0: the reduced dimension is still on its way (the launches sit
 // right behind the wPCA) - the three kernels that need it read it from ctx->dK.
 static int enqueue_condition(pcabo_ctx* ctx, const double* y_dev, int n, int k, const double* unb, double lengthscale,
-                             double noise, int kernel) {
+                             double noise, int kernel, double mean_c = 0.0) {
   hipStream_t s = ctx->stream;
   const int* k_dev = k < 0 ? ctx->dK : nullptr;
   const int kk = k < 0 ? ctx->max_d : k;              // work model only
@@ -664,7 +673,7 @@ static int enqueue_condition(pcabo_ctx* ctx, const double* y_dev, int n, int k, 
   }
   {
     ProfScope ps(ctx, 1, 8.0 * n * kk + 4.0 * n * (n + 1.0), 2.0 * n * n * kk + 12.0 * n * n);
-    launch_zstats(s, ctx->dZ, y_dev, n, k, unb, ctx->dBounds4, ctx->dZnMean, ctx->dYstats, ctx->dYs, ctx->hm, k_dev);
+    launch_zstats(s, ctx->dZ, y_dev, n, k, unb, ctx->dBounds4, ctx->dZnMean, ctx->dYstats, ctx->dYs, ctx->hm, k_dev, ZB(), mean_c);
     HIPCHK(hipEventRecord(ctx->evBounds, s));
     launch_znorm(s, ctx->dZ, n, k, ctx->NP, ctx->KP, ctx->ld, ctx->dBounds4, ctx->dZnMean, 1.0 / lengthscale, ctx->dZnT,
                  ctx->dAT, ctx->dNrm, k_dev);
@@ -768,6 +777,148 @@ int pcabo_gp_condition(pcabo_ctx* ctx, const double* Z, const double* y, int n, 
   int rc = pcabo_gp_condition_begin(ctx, Z, y, n, k, norm_bounds, lengthscale, noise, kernel);
   if (rc != PCABO_OK) return rc;
   return pcabo_gp_condition_end(ctx);
+}
+
+// ---- opt-in GP hyperparameter fit (DESIGN.md "GP hyperparameter fit") -------------------------------------------
+// theta = {noise s2, mean constant c, raw lengthscale rho}; lengthscale = softplus(rho) as torch computes it (threshold 20).
+static double softplus_host(double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); }
+
+// Inputs of a fit staged like pcabo_gp_condition_begin's; *unb = the device copy of the user's Normalize bounds or NULL.
+static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, const double* Z, const double* y, int n, int k,
+                            const double* norm_bounds, int kernel, const double** unb) {
+  if (!y || k < 1 || k > ctx->max_d || n < 2 || n > ctx->max_n)
+    return set_err(ctx, PCABO_ERR_ARG, "%s: bad argument or size beyond context capacity", who);
+  if (kernel != PCABO_KERNEL_MATERN52)
+    return set_err(ctx, PCABO_ERR_ARG, "%s: the fit is restated for the Matern-5/2 kernel only", who);
+  if (ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "%s: a conditioning is in flight, call pcabo_gp_condition_end first", who);
+  if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
+  if (!Z && (!ctx->have_wpca || ctx->n != n || ctx->k != k))
+    return set_err(ctx, PCABO_ERR_ARG, "%s: Z == NULL needs a matching pcabo_wpca call first", who);
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  if (Z) STAGE_IN(ctx->dZ, Z, (size_t)n * k, double);
+  STAGE_IN(ctx->dY, y, n, double);
+  *unb = nullptr;
+  if (norm_bounds) {
+    HIPCHK(hipMemcpyAsync(ctx->dUserNB, norm_bounds, (size_t)2 * k * sizeof(double), hipMemcpyHostToDevice, s));
+    *unb = ctx->dUserNB;
+  }
+  return PCABO_OK;
+}
+
+// One evaluation: the conditioning at theta (k_zstats with the mean constant -> k_znorm -> k_gram -> Cholesky -> root inverse
+// -> alpha, the jitter retries of pcabo_gp_condition_end), k_mll_grad + k_mll_finish, one 48-byte copy and one wait per attempt.
+// Loss and gradient are assembled here: the prior on s2 and the chain rule through softplus are host arithmetic.
+static int mll_eval(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta, double* loss, double* grad) {
+  const double s2 = theta[0], c = theta[1], rho = theta[2];
+  const double ls = softplus_host(rho);
+  if (!(s2 > 0.0) || !std::isfinite(s2) || !std::isfinite(c) || !(ls > 0.0) || !std::isfinite(ls))
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
+  hipStream_t s = ctx->stream;
+  int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, ls, s2, PCABO_KERNEL_MATERN52, c);
+  if (rc != PCABO_OK) return rc;
+  ctx->gp_pending = false;
+  const int nb = ctx->NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
+  double* out = ctx->dMll + 2 * (size_t)tiles;
+  double jitter = 0.0;
+  for (int attempt = 0;; ++attempt) {                    // psd_safe_cholesky: 0, 1e-8, 1e-7, 1e-6
+    launch_mll_grad(s, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
+    HOST_OUT(ctx->hMll, out, 6, double);
+    HIPCHK(wait_stream(s));
+    HIPCHK(hipGetLastError());
+    if (ctx->hm->chol_info == 0) break;
+    if (attempt == 3)
+      return set_err(ctx, PCABO_ERR_NOT_PD, "K + s2 I not positive definite after jitter retries (pivot %s%d)", "", ctx->hm->chol_info);
+    jitter = (attempt == 0) ? 1e-8 : jitter * 10.0;
+    rc = launch_factorisation(ctx, jitter);
+    if (rc != PCABO_OK) return rc;
+  }
+  ctx->have_gp = true;
+  const double* h = ctx->hMll;   // sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, sum W dK/dlog l
+  const double LOG2PI = 1.8378770664093453;
+  const double lnz = std::log(s2), u = lnz + 4.0;
+  const double log_n = -0.5 * h[1] - h[0] - 0.5 * n * LOG2PI;
+  const double log_prior = -lnz - 0.5 * LOG2PI - 0.5 * u * u;              // LogNormal(-4, 1) at s2
+  *loss = -(log_n + log_prior) / n;
+  if (grad) {
+    const double sig = 1.0 / (1.0 + std::exp(-rho));                       // d softplus / d rho
+    grad[0] = -((0.5 * (h[3] - h[4])) + (-1.0 - u) / s2) / n;
+    grad[1] = -h[2] / n;
+    grad[2] = -(0.5 * h[5] * sig / ls) / n;
+  }
+  return PCABO_OK;
+}
+
+int pcabo_gp_mll(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
+                 const double* theta, double* loss, double* grad) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (!theta || !loss) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta and loss are required%s", "");
+  const double* unb = nullptr;
+  int rc = stage_fit_inputs(ctx, "pcabo_gp_mll", Z, y, n, k, norm_bounds, kernel, &unb);
+  if (rc != PCABO_OK) return rc;
+  return mll_eval(ctx, n, k, unb, theta, loss, grad);
+}
+
+// scipy.optimize.minimize(method="L-BFGS-B") with its defaults around mll_eval (the driver of pcabo_lbfgsb_minimize: x0 clipped
+// into the box, scipy's memoisation of the last point, its iteration / evaluation limits).
+int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
+                 double* theta_inout, double* loss, int* info) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (!theta_inout) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_fit: theta_inout is required%s", "");
+  const double* unb = nullptr;
+  int rc = stage_fit_inputs(ctx, "pcabo_gp_fit", Z, y, n, k, norm_bounds, kernel, &unb);
+  if (rc != PCABO_OK) return rc;
+  const int NV = 3, maxiter = 15000, maxfun = 15000;
+  const double lower[3] = {1e-4, -INFINITY, -INFINITY}, upper[3] = {INFINITY, INFINITY, INFINITY};
+  Lbfgsb opt;
+  opt.init(NV, 10, lower, upper, 1e7, 1e-5, 20);
+  opt.set_sum_order(0);                                  // the published order, whatever the process-wide default
+  double x[3], g[3] = {0.0, 0.0, 0.0}, f = 0.0;
+  for (int i = 0; i < NV; ++i) x[i] = theta_inout[i] < lower[i] ? lower[i] : (theta_inout[i] > upper[i] ? upper[i] : theta_inout[i]);
+  double xc[3], gc[3], fc = 0.0, xacc[3];               // last evaluated point (the context is conditioned there) / last accepted
+  bool have_c = false, not_pd = false;
+  memcpy(xacc, x, sizeof(x));
+  int iters = 0, evals = 0;
+  while (true) {
+    const int task = opt.step(x, &f, g);
+    if (task == LBFGSB_FG) {
+      if (have_c && memcmp(x, xc, sizeof(x)) == 0) { f = fc; memcpy(g, gc, sizeof(g)); continue; }
+      rc = mll_eval(ctx, n, k, unb, x, &f, g);
+      if (rc == PCABO_ERR_NOT_PD) {                      // a trial theta the factorisation cannot take: stop, keep the last iterate
+        if (!have_c) return rc;                          // (not even the start)
+        not_pd = true;
+        break;
+      }
+      if (rc != PCABO_OK) return rc;
+      ++evals;
+      memcpy(xc, x, sizeof(x)); memcpy(gc, g, sizeof(g)); fc = f; have_c = true;
+      continue;
+    }
+    if (task == LBFGSB_NEW_X) {
+      ++iters;
+      memcpy(xacc, x, sizeof(x));
+      if (iters >= maxiter) opt.stop(LBFGSB_STOP_ITER);
+      else if (evals > maxfun) opt.stop(LBFGSB_STOP_FUN);
+      continue;
+    }
+    break;
+  }
+  if (!not_pd) memcpy(xacc, x, sizeof(x));               // where the optimiser ended (it restores the last iterate itself)
+  // leave the context conditioned at the result (and report the loss there)
+  double fr = fc;
+  if (!have_c || memcmp(xacc, xc, sizeof(xacc)) != 0) {
+    double gr[3];
+    rc = mll_eval(ctx, n, k, unb, xacc, &fr, gr);
+    if (rc != PCABO_OK) return rc;
+  }
+  memcpy(theta_inout, xacc, sizeof(xacc));
+  if (loss) *loss = fr;
+  if (info) {
+    info[0] = iters; info[1] = evals;
+    info[2] = not_pd ? 2 : opt.warnflag();
+    info[3] = not_pd ? PCABO_FIT_TASK_NOT_PD : opt.task();
+  }
+  return PCABO_OK;
 }
 
 int pcabo_acq_bounds(pcabo_ctx* ctx, double* bounds) {

@@ -194,7 +194,8 @@ void launch_project(hipStream_t s, const double* X, const double* data_mean, con
                     const double* comps, const int* k_dev, int n, int d, double* Z, ZB zb = ZB());
 void launch_zstats(hipStream_t s, const double* Z, const double* y, int n, int k, const double* user_norm_bounds,
                    double* bounds4 /*norm_lo,norm_hi,acq_lo,acq_hi each MAXD*/, double* zn_mean, double* ystats,
-                   double* ys, HostMirror* hm, const int* k_dev = nullptr, ZB zb = ZB());
+                   double* ys, HostMirror* hm, const int* k_dev = nullptr, ZB zb = ZB(),
+                   double mean_c = 0.0);   // mean_c: constant mean of a fitted GP (y_s and the statistics carry m + s c)
 void launch_znorm(hipStream_t s, const double* Z, int n, int k, int NP, int KP, int ld, const double* bounds4,
                   const double* zn_mean, double inv_ls, double* ZnT, double* AT, double* nrm,
                   const int* k_dev = nullptr, ZB zb = ZB());   // k_dev != NULL: k (and KP) are read on the device, the arguments ignored
@@ -202,13 +203,18 @@ void launch_gram(hipStream_t s, const double* AT, const double* nrm, int n, int 
                  int kernel, double* K, const int* k_dev = nullptr, double* K2 = nullptr, int* info_reset = nullptr,
                  ZB zb = ZB());
 void launch_add_jitter(hipStream_t s, double* K, int n, int ld, double jitter);
-void launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb = ZB());
+// 0, or -1 when nothing was factored (the device or a kernel attribute could not be set up)
+int launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb = ZB());
 void launch_trinv(hipStream_t s, const double* L, int NP, int ld, double* R, ZB zb = ZB());
 void launch_chol_panel(hipStream_t s, double* L, int p, int nblocks, int ld, int* info, double* diag_scratch, ZB zb = ZB());
-void launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch /* two tiles */, ZB zb = ZB());
+int launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch /* two tiles */, ZB zb = ZB());
 void launch_trinv_diag_w(hipStream_t s, const double* L, int nblk, int ld, double* R, ZB zb = ZB());
 void launch_alpha(hipStream_t s, const double* R, const double* ys, int n, int NP, int ld, double* tmp, double* alpha,
                   ZB zb = ZB());
+// marginal-likelihood pieces of a conditioned state (kernels_fit.hip, Matern-5/2): partial = 2 doubles per lower 64 x 64 tile,
+// out[6] = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, sum_ij W_ij dK_ij/dlog l}
+void launch_mll_grad(hipStream_t s, const double* R, const double* AT, const double* nrm, const double* alpha, const double* L,
+                     const double* ys, int n, int NP, int KP, int ld, double* partial, double* out);
 void launch_acq(hipStream_t s, const QueryArgs* qa, const double* Xq, int q, int n, int k, int NP, int ld,
                 const double* ZnT, const double* R, const double* alpha, const double* bounds4, const double* ystats,
                 AcqParams p, double* partial, unsigned int* counters, double* val,

@@ -13,7 +13,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # read by the HIP runtime at 
 from Algorithms import ExperimentRunner
 
 
-def parse_arguments():
+def parse_arguments(argv=None):
     p = argparse.ArgumentParser(description="Run Bayesian Optimization comparison experiments on MI355X.")
     p.add_argument("--dimensions", type=int, nargs="+", default=[10, 20, 40])
     p.add_argument("--problems", type=int, nargs="+", default=[15, 16, 17])
@@ -34,7 +34,10 @@ def parse_arguments():
                    help="'device': every restart group's L-BFGS-B inside one kernel launch, the batches interleaved on one host "
                         "thread - for many runs per GPU (e.g. --batched 75 --side_by_side 4); 'auto': 'device' for a dimension "
                         "20 <= d <= 40 with 30 or more runs on this GPU, 'group' otherwise")
-    return p.parse_args()
+    p.add_argument("--fit_gp", action="store_true",
+                   help="fit the GP's noise, mean constant and lengthscale by the marginal likelihood every iteration (not in the "
+                        "reference, which keeps them fixed; not with --batched)")
+    return p.parse_args(argv)
 
 
 def main():
@@ -46,7 +49,8 @@ def main():
         algorithms=a.algorithms, dimensions=a.dimensions, problem_ids=a.problems, num_runs=a.runs,
         budget_factor=a.budget_factor, doe_factor=a.doe_factor, root_dir=os.getcwd(), experiment_name=a.experiment_dir,
         acquisition_function=a.acquisition, pca_components=0, var_threshold=a.var_threshold, verbose=a.verbose,
-        progress=(rank == 0), batched=a.batched, side_by_side=a.side_by_side, batch_acq_kernel=a.batch_acq_kernel)
+        progress=(rank == 0), batched=a.batched, side_by_side=a.side_by_side, batch_acq_kernel=a.batch_acq_kernel,
+        fit_gp=a.fit_gp)
     t0 = time.time()
     experiment.run_experiment()
     dt = time.time() - t0

@@ -7,16 +7,19 @@ library is missing the import of this module fails loudly - there is no CPU fall
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
 import numpy as np
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 KERNEL_MATERN52, KERNEL_RBF = 0, 1
 ACQ_LOG_EI, ACQ_PI = 0, 1
 PTR_HOST, PTR_DEVICE = 0, 1
 OPT_RESIDENT, OPT_BESTF_F32, OPT_GROUP_ACQ, OPT_DEVICE_LBFGSB, OPT_LBFGSB_CUS = 0, 1, 2, 3, 4
+FIT_THETA0 = (0.006737946999085467, 0.0, 0.0)   # GP fit: (noise, mean constant, raw lengthscale) of a freshly built model
+FIT_TASK_NOT_PD = -2                            # gp_fit's `task` when a trial theta could not be factored even with jitter
 PROFILE_GROUPS = ("wpca", "gram", "cholesky", "root_inverse_alpha", "acq_partial", "acq_large_batches")
 
 # Hardware queues.  A Batch drives the GPU from several worker threads on separate HIP streams (its gangs): the runtime's
@@ -46,6 +49,7 @@ EXPORTS = [
     "pcabo_abi_version", "pcabo_device_count", "pcabo_ctx_create", "pcabo_ctx_destroy",
     "pcabo_set_pointer_mode", "pcabo_set_option", "pcabo_last_error", "pcabo_wpca", "pcabo_gp_condition", "pcabo_gp_condition_begin",
     "pcabo_gp_condition_end", "pcabo_gp_condition_end_eval", "pcabo_wpca_gp_condition_begin", "pcabo_wpca_results",
+    "pcabo_gp_mll", "pcabo_gp_fit",
     "pcabo_acq_bounds",
     "pcabo_acq_eval", "pcabo_logei", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
     "pcabo_get_gram", "pcabo_lbfgsb_minimize", "pcabo_lbfgsb_set_vector_kernels", "pcabo_lbfgsb_set_sum_order", "pcabo_sobol_scramble", "pcabo_sobol_draw", "pcabo_sobol_draw_rows", "pcabo_torch_randint2", "pcabo_torch_multinomial_rows", "pcabo_boltzmann_pick_rows", "pcabo_set_profiling",
@@ -96,6 +100,8 @@ def _load() -> C.CDLL:
     lib.pcabo_gp_condition.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int]
     lib.pcabo_gp_condition_begin.argtypes = lib.pcabo_gp_condition.argtypes
     lib.pcabo_gp_condition_end.argtypes = [vp]
+    lib.pcabo_gp_mll.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, dp, vp]
+    lib.pcabo_gp_fit.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, dp, vp]
     lib.pcabo_wpca_results.argtypes = [vp, vp, vp, vp, vp, ip]
     lib.pcabo_gp_condition_end_eval.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp]
     lib.pcabo_wpca_gp_condition_begin.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp,
@@ -297,6 +303,44 @@ class Context:
         fn = LIB.pcabo_gp_condition if wait else LIB.pcabo_gp_condition_begin
         self._chk(fn(self._h, _ptr(Z), _ptr(y), n, k, _ptr(nb), float(lengthscale), float(noise), int(kernel)))
         self.n, self.k = n, k
+
+    # ---- opt-in GP hyperparameter fit (pcabo_gp_mll / pcabo_gp_fit) ----------------------------
+    def _fit_args(self, y, Z, norm_bounds):
+        y = _f64(y).reshape(-1)
+        Z = None if Z is None else _f64(Z)
+        k = self.k if Z is None else Z.shape[1]
+        nb = None if norm_bounds is None else _f64(norm_bounds, (2, k))
+        return y, Z, k, nb
+
+    @staticmethod
+    def _fit_result(theta, loss):
+        rho = float(theta[2])                           # softplus as torch (and the library) compute it
+        return {"lengthscale": math.log1p(math.exp(rho)) if rho <= 20.0 else rho,
+                "noise": float(theta[0]), "mean_constant": float(theta[1]), "loss": float(loss), "theta": theta.copy()}
+
+    def gp_mll(self, y, theta=FIT_THETA0, Z=None, norm_bounds=None, kernel=KERNEL_MATERN52):
+        """Loss of the GP fit and its gradient at theta = (noise, mean constant, raw lengthscale); the context is left
+        conditioned at theta.  Returns the fit's dict (`lengthscale`, `noise`, `mean_constant`, `loss`) with `grad` (3,)."""
+        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
+        th = _f64(theta, (3,))
+        loss, g = C.c_double(0.0), np.empty(3)
+        self._chk(LIB.pcabo_gp_mll(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th), C.byref(loss),
+                                   _ptr(g)))
+        self.n, self.k = y.shape[0], k
+        return {**self._fit_result(th, loss.value), "grad": g}
+
+    def gp_fit(self, y, theta0=FIT_THETA0, Z=None, norm_bounds=None, kernel=KERNEL_MATERN52):
+        """Fit (noise, mean constant, raw lengthscale) by the marginal likelihood from theta0 (default: the model's initial
+        values); the context is left conditioned at the fit.  Returns `lengthscale`, `noise`, `mean_constant`, `loss`,
+        `iterations`, `evaluations`, `warnflag` (scipy's), `task` and `theta`."""
+        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
+        th = _f64(theta0, (3,)).copy()
+        loss, info = C.c_double(0.0), np.zeros(4, dtype=np.int32)
+        self._chk(LIB.pcabo_gp_fit(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th), C.byref(loss),
+                                   _ptr(info)))
+        self.n, self.k = y.shape[0], k
+        return {**self._fit_result(th, loss.value), "iterations": int(info[0]), "evaluations": int(info[1]),
+                "warnflag": int(info[2]), "task": int(info[3])}
 
     def gp_wait(self) -> None:
         self._chk(LIB.pcabo_gp_condition_end(self._h))
