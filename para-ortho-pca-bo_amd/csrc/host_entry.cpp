@@ -6,6 +6,7 @@
 #include "lbfgsb.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -13,42 +14,25 @@
 
 extern "C" {
 
+namespace { std::atomic<int> g_minimize_sum_order{0}; }       // pcabo_lbfgsb_set_sum_order: read by pcabo_lbfgsb_minimize alone
+
 int pcabo_lbfgsb_minimize(int nvar, double* x, const double* lower, const double* upper, pcabo_fg_callback fg,
                           void* user, int m, double factr, double pgtol, int maxiter, int maxfun, int maxls,
                           double* f_out, int* nit, int* nfev, int* task_out) {
   if (nvar < 1 || !x || !fg || m < 1) return PCABO_ERR_ARG;
-  Lbfgsb opt;
-  opt.init(nvar, m, lower, upper, factr, pgtol, maxls);
-  if (lower && upper)
-    for (int i = 0; i < nvar; ++i) x[i] = x[i] < lower[i] ? lower[i] : (x[i] > upper[i] ? upper[i] : x[i]);
-  std::vector<double> g(nvar, 0.0), xc, gc;
-  double f = 0.0, fc = 0.0;
-  int iters = 0, evals = 0;
-  while (true) {
-    int task = opt.step(x, &f, g.data());
-    if (task == LBFGSB_FG) {
-      if (!xc.empty() && memcmp(x, xc.data(), nvar * sizeof(double)) == 0) { f = fc; g = gc; continue; }   // scipy's memoisation
-      f = fg(x, g.data(), user); ++evals;
-      xc.assign(x, x + nvar); gc = g; fc = f;
-      continue;
-    }
-    if (task == LBFGSB_NEW_X) {
-      ++iters;
-      if (iters >= maxiter) opt.stop(LBFGSB_STOP_ITER);
-      else if (evals > maxfun) opt.stop(LBFGSB_STOP_FUN);
-      continue;
-    }
-    break;
-  }
-  if (f_out) *f_out = f;
-  if (nit) *nit = iters;
-  if (nfev) *nfev = evals;
-  if (task_out) *task_out = opt.task();
-  return opt.warnflag();
+  LbfgsbDriver run;
+  run.init(nvar, x, lower, upper, g_minimize_sum_order.load(), maxiter, maxfun, m, factr, pgtol, maxls);
+  while (run.advance()) run.absorb(fg(run.x.data(), run.g.data(), user));
+  std::copy(run.x.begin(), run.x.end(), x);
+  if (f_out) *f_out = run.f;
+  if (nit) *nit = run.niter;
+  if (nfev) *nfev = run.nfev;
+  if (task_out) *task_out = run.opt.task();
+  return run.opt.warnflag();
 }
 
 int pcabo_lbfgsb_set_vector_kernels(int enabled) { return lbfgsb_set_vector_kernels(enabled); }
-int pcabo_lbfgsb_set_sum_order(int order) { return lbfgsb_set_default_sum_order(order); }
+int pcabo_lbfgsb_set_sum_order(int order) { return g_minimize_sum_order.exchange(order ? 1 : 0); }
 
 int pcabo_sobol_scramble(int64_t* state, const int64_t* ltm, int k) {
   if (!state || !ltm || k < 1) return PCABO_ERR_ARG;

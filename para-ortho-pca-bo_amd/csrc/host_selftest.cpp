@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 namespace {
@@ -196,32 +197,93 @@ void test_plan() {
   }
 }
 
+// One RestartGroup driven to its end on the CPU objective (each restart's point its own copy of the objective, the acquisition's
+// signs: values -f, gradients -g); the points it evaluated, one after the other, into trail.
+void drive_group(RestartGroup& rg, Objective& o, std::vector<double>* trail) {
+  std::vector<double> hVal(rg.q0 + rg.nq), hGrad((size_t)(rg.q0 + rg.nq) * rg.k);
+  while (rg.advance()) {
+    if (trail) trail->insert(trail->end(), rg.x.begin(), rg.x.end());
+    for (int j = 0; j < rg.nq; ++j) {
+      double* gj = hGrad.data() + (size_t)(rg.q0 + j) * rg.k;
+      hVal[rg.q0 + j] = -fg_objective(rg.x.data() + (size_t)j * rg.k, gj, &o);
+      for (int c = 0; c < rg.k; ++c) gj[c] = -gj[c];
+    }
+    CHECK(rg.absorb(hVal.data(), hGrad.data(), rg.q0), "NaN gradient");
+  }
+}
+
+// the joint problem of nq restarts: the sum of the restarts' objectives, in restart order
+struct Joint { Objective* o; int nq, k; };
+double fg_joint(const double* x, double* g, void* user) {
+  const Joint* J = static_cast<const Joint*>(user);
+  double f = 0.0;
+  for (int j = 0; j < J->nq; ++j) f += fg_objective(x + (size_t)j * J->k, g + (size_t)j * J->k, J->o);
+  return f;
+}
+
+void test_restart_group() {
+  const int k = 9, nq = 4, q0 = 3, restarts = q0 + nq;
+  Lcg r(31);
+  Objective o; o.c.resize(k);
+  for (auto& v : o.c) v = 2.0 * r.uni() - 1.0;
+  std::vector<double> ics((size_t)restarts * k), bounds(2 * k);
+  for (auto& v : ics) v = 4.0 * r.uni() - 2.0;
+  for (int c = 0; c < k; ++c) { bounds[c] = -1.0 - 0.1 * c; bounds[k + c] = 1.25 + 0.05 * c; }
+  // (a) the group is scipy's L-BFGS-B on the summed joint problem: negation and a sum in restart order are exact, so the
+  // group and pcabo_lbfgsb_minimize take the same iterates and end on the same bits
+  RestartGroup rg;
+  rg.init(ics.data(), bounds.data(), q0, nq, k, 200);
+  drive_group(rg, o, nullptr);
+  std::vector<double> x(ics.begin() + (size_t)q0 * k, ics.end()), lo(nq * k), hi(nq * k);
+  for (int t = 0; t < nq * k; ++t) { lo[t] = bounds[t % k]; hi[t] = bounds[k + t % k]; }
+  Joint J{&o, nq, k};
+  double f = 0.0; int nit = 0, nfev = 0, task = 0;
+  const int wf = pcabo_lbfgsb_minimize(nq * k, x.data(), lo.data(), hi.data(), fg_joint, &J, 10, 1e7, 1e-5, 200, 15000, 20, &f, &nit, &nfev, &task);
+  CHECK(std::memcmp(x.data(), rg.x.data(), x.size() * sizeof(double)) == 0, "group and joint minimize end on different points");
+  CHECK(f == rg.f && nit == rg.niter && nfev == rg.nfev && wf == rg.opt.warnflag() && task == rg.opt.task(),
+        "group f %.17g nit %d nfev %d, joint minimize f %.17g nit %d nfev %d", rg.f, rg.niter, rg.nfev, f, nit, nfev);
+  CHECK(rg.niter > 2, "too short a run to compare: %d iterations", rg.niter);
+  // (b) the order a group steps in is the one it was given: pcabo_lbfgsb_set_sum_order concerns pcabo_lbfgsb_minimize alone
+  std::vector<double> trail0, trail1;
+  RestartGroup g0, g1;
+  g0.init(ics.data(), bounds.data(), q0, nq, k, 200, 0);
+  drive_group(g0, o, &trail0);
+  const int was = pcabo_lbfgsb_set_sum_order(1);
+  g1.init(ics.data(), bounds.data(), q0, nq, k, 200, 0);
+  drive_group(g1, o, &trail1);
+  pcabo_lbfgsb_set_sum_order(was);
+  CHECK(trail0.size() == trail1.size() && std::memcmp(trail0.data(), trail1.data(), trail0.size() * sizeof(double)) == 0,
+        "a group of order 0 strays from its iterates while the process-wide order is 1 (%zu / %zu coordinates)",
+        trail0.size(), trail1.size());
+}
+
 // RestartGroups of several "runs" stepped by the pool's workers, each worker with its own launch table on its stack (the
 // product's shape: run << 16 | first query << 8 | count), values and gradients written into per-run blocks and absorbed.
 void test_gang_pool(int workers, int runs) {
   const int k = 7, nq = 5, ngroups = 2, restarts = nq * ngroups;
   std::vector<std::vector<RestartGroup>> groups(runs);
   std::vector<Objective> obj(runs);
-  std::vector<std::vector<double>> hXq(runs), hVal(runs), hGrad(runs);
+  std::vector<std::vector<double>> ics(runs), bounds(runs), hXq(runs), hVal(runs), hGrad(runs);
+  // every second run steps in the device optimiser's order (the twin's setting)
+  auto init_groups = [&](int b) {
+    for (int gi = 0; gi < ngroups; ++gi) groups[b][gi].init(ics[b].data(), bounds[b].data(), gi * nq, nq, k, 200, b & 1);
+  };
   for (int b = 0; b < runs; ++b) {
     Lcg r(100 + b);
     obj[b].c.resize(k);
     for (auto& v : obj[b].c) v = 2.0 * r.uni() - 1.0;
-    std::vector<double> ics((size_t)restarts * k), bounds(2 * k);
-    for (auto& v : ics) v = 4.0 * r.uni() - 2.0;
-    for (int c = 0; c < k; ++c) { bounds[c] = -1.25; bounds[k + c] = 1.5; }
+    ics[b].resize((size_t)restarts * k); bounds[b].resize(2 * k);
+    for (auto& v : ics[b]) v = 4.0 * r.uni() - 2.0;
+    for (int c = 0; c < k; ++c) { bounds[b][c] = -1.25; bounds[b][k + c] = 1.5; }
     groups[b].resize(ngroups);
-    for (int gi = 0; gi < ngroups; ++gi) {
-      groups[b][gi].init(ics.data(), bounds.data(), gi * nq, nq, k, 200);
-      groups[b][gi].opt.set_sum_order(b & 1);          // every second run steps in the device optimiser's order (the twin's setting)
-    }
+    init_groups(b);
     hXq[b].assign((size_t)restarts * k, 0.0); hVal[b].assign(restarts, 0.0); hGrad[b].assign((size_t)restarts * k, 0.0);
   }
   GangPool pool;
   pool.start(workers);
   std::atomic<int> rounds{0}, bad{0};
   for (int call = 0; call < 3; ++call) {              // the pool is reused across calls, as a batch does per BO iteration
-    if (call > 0) for (int b = 0; b < runs; ++b) for (auto& rg : groups[b]) { rg.active = true; rg.niter = 0; rg.have_cache = false; rg.opt.init(nq * k, 10, rg.lo.data(), rg.hi.data(), 1e7, 1e-5, 20); }
+    if (call > 0) for (int b = 0; b < runs; ++b) init_groups(b);
     pool.run([&](int t) {
       unsigned table[64];                              // the worker's own launch table
       struct Pending { int b, gi; };
@@ -249,7 +311,10 @@ void test_gang_pool(int workers, int runs) {
             for (int c = 0; c < k; ++c) hGrad[b][(size_t)(q0 + j) * k + c] = -g[c];
           }
         }
-        for (const Pending& pe : pend) if (!groups[pe.b][pe.gi].absorb(hVal[pe.b].data(), hGrad[pe.b].data())) bad.fetch_add(1);
+        for (const Pending& pe : pend) {
+          RestartGroup& rg = groups[pe.b][pe.gi];
+          if (!rg.absorb(hVal[pe.b].data(), hGrad[pe.b].data(), rg.q0)) bad.fetch_add(1);
+        }
         rounds.fetch_add(1);
       }
     });
@@ -274,6 +339,7 @@ int main(int argc, char** argv) {
   test_sobol_rows();
   test_torch_rng();
   test_plan();
+  test_restart_group();
   test_gang_pool(1, 3);
   test_gang_pool(workers, 11);
   if (g_fail) { std::fprintf(stderr, "host selftest: %d check(s) failed\n", g_fail); return 1; }

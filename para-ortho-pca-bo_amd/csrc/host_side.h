@@ -1,5 +1,5 @@
-// Host-side pieces of the batch path that need no HIP: the restart group's state machine around csrc/lbfgsb.cpp and the worker
-// pool of a batch.  Included by pcabo_api.hip (the product) and by host_selftest.cpp (the sanitizer builds of the Makefile:
+// Host-side pieces of the optimisers that need no HIP: the restart group (a joint problem on LbfgsbDriver, csrc/lbfgsb.h) and
+// the worker pool of a batch.  Included by pcabo_api.hip (the product) and by host_selftest.cpp (the sanitizer builds of the Makefile:
 // `make asan ubsan tsan` compile this header, lbfgsb.cpp and host_entry.cpp with g++ and run them without a GPU).
 #pragma once
 #include "lbfgsb.h"
@@ -11,58 +11,47 @@
 #include <thread>
 #include <vector>
 
-// One restart group of one run: scipy's L-BFGS-B state machine plus the memoisation of scipy's ScalarFunction (same
-// logic as in pcabo_optimize_acqf, which keeps its own copy for the resident-kernel path).
-struct RestartGroup {
-  Lbfgsb opt;
-  int q0 = 0, nq = 0, k = 0, maxiter = 200;
-  std::vector<double> x, g, lo, hi, xc, gc, vc;
-  double fval = 0.0, fc = 0.0;
-  bool have_cache = false, active = true;
-  int niter = 0, nfev = 0;
-  void init(const double* ics, const double* bounds, int q0_, int nq_, int k_, int maxiter_) {
-    q0 = q0_; nq = nq_; k = k_; maxiter = maxiter_;
-    const int nv = nq * k;
-    x.resize(nv); g.assign(nv, 0.0); lo.resize(nv); hi.resize(nv);
+// One restart group of one run: the joint L-BFGS-B problem of restarts q0 .. q0 + nq - 1 (nq k variables) on the negated
+// acquisition, and botorch's end of it (the values at the clamped end points).
+struct RestartGroup : LbfgsbDriver {
+  int q0 = 0, nq = 0, k = 0;
+  std::vector<double> lo, hi, vc;      // the box per variable; the per-restart values of the cached evaluation
+  void init(const double* ics, const double* bounds, int q0_, int nq_, int k_, int maxiter, int sum_order = 0) {
+    q0 = q0_; nq = nq_; k = k_;
+    lo.resize(nq * k); hi.resize(nq * k);
     for (int j = 0; j < nq; ++j)
-      for (int c = 0; c < k; ++c) {
-        const double l = bounds[c], h = bounds[k + c], v = ics[(size_t)(q0 + j) * k + c];
-        lo[j * k + c] = l; hi[j * k + c] = h;
-        x[j * k + c] = v < l ? l : (v > h ? h : v);              // columnwise_clamp / np.clip
-      }
-    opt.init(nv, 10, lo.data(), hi.data(), 1e7, 1e-5, 20);
+      for (int c = 0; c < k; ++c) { lo[j * k + c] = bounds[c]; hi[j * k + c] = bounds[k + c]; }
+    LbfgsbDriver::init(nq * k, ics + (size_t)q0 * k, lo.data(), hi.data(), sum_order, maxiter);   // (columnwise_clamp)
   }
-  void advance() {                    // until the group needs f, g at x (or stops)
-    while (active) {
-      const int task = opt.step(x.data(), &fval, g.data());
-      if (task == LBFGSB_FG) {
-        if (have_cache && memcmp(x.data(), xc.data(), x.size() * sizeof(double)) == 0) { fval = fc; g = gc; continue; }
-        return;
-      }
-      if (task == LBFGSB_NEW_X) {
-        niter += 1;
-        if (niter >= maxiter) opt.stop(LBFGSB_STOP_ITER);
-        else if (nfev > 15000) opt.stop(LBFGSB_STOP_FUN);
-        continue;
-      }
-      active = false;
-    }
-  }
-  bool absorb(const double* hVal, const double* hGrad) {      // false: NaN in the gradient
+  // the evaluation at x: values hVal[row .. row + nq), gradients behind hGrad + row k (of the acquisition, maximised); false: a NaN
+  // in the gradient (nothing recorded)
+  bool absorb(const double* hVal, const double* hGrad, int row) {
     double fs = 0.0;
     bool nan = false;
-    for (int j = 0; j < nq; ++j) fs += hVal[q0 + j];
+    for (int j = 0; j < nq; ++j) fs += hVal[row + j];
     for (int t = 0; t < nq * k; ++t) {
-      const double gv = -hGrad[(size_t)q0 * k + t];
+      const double gv = -hGrad[(size_t)row * k + t];
       if (gv != gv) nan = true;
       g[t] = gv;
     }
     if (nan) return false;
-    fval = -fs;
-    nfev += 1;
-    xc = x; gc = g; fc = fval; have_cache = true;
-    vc.assign(hVal + q0, hVal + q0 + nq);
+    LbfgsbDriver::absorb(-fs);
+    vc.assign(hVal + row, hVal + row + nq);
     return true;
+  }
+  // the end point clamped into the box, into the rows q0 .. q0 + nq - 1 of cand
+  void end_point(double* cand) const {
+    for (int t = 0; t < nq * k; ++t) cand[(size_t)q0 * k + t] = x[t] < lo[t] ? lo[t] : (x[t] > hi[t] ? hi[t] : x[t]);
+  }
+  // the clamped end point in cand is the last evaluated point: its values vc are the ones a launch there would give
+  bool ends_on_cache(const double* cand) const {
+    return have_cache && memcmp(cand + (size_t)q0 * k, xc.data(), (size_t)nq * k * sizeof(double)) == 0;
+  }
+  // niter, nfev, warnflag, task into info[4 slot .. 4 slot + 3] (info may be null); true: the group failed (warnflag 2)
+  bool report(int* info, size_t slot) const {
+    const int wf = opt.warnflag();
+    if (info) { int* o = info + 4 * slot; o[0] = niter; o[1] = nfev; o[2] = wf; o[3] = opt.task(); }
+    return wf == 2;
   }
 };
 

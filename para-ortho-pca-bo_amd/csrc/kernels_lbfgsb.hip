@@ -12,7 +12,7 @@
 //    per lane; the sums over the variables (d'd, g'd, r'r, the 2m accumulations W'd, f1 of the Cauchy search) are formed in
 //    the 64-LANE TREE ORDER - lane l adds the terms l, l + 64, ..., the lane sums meet in a balanced tree of adjacent pairs
 //    (DPP row operations; several sums at once through an LDS tile) - which csrc/lbfgsb.cpp implements behind
-//    Lbfgsb::set_sum_order(1): the host class in that order is this kernel's twin.  The short ordered sums over the <= 2m
+//    sum order 1 of Lbfgsb::init: the host class in that order is this kernel's twin.  The short ordered sums over the <= 2m
 //    history columns and the small dense pieces (10 x 10 and 20 x 20 factorisations and triangular solves) keep the
 //    published order: a column or a right-hand side per lane, pivots broadcast with v_readlane.  Every number goes
 //    through the same operations in the same order as in the twin (this file is compiled with -ffp-contract=off; IEEE
@@ -1405,7 +1405,7 @@ __device__ void lb_helper(const LbLds L, int lane, int& last) {
   }
 }
 
-// RestartGroup::advance (pcabo_api.hip): step until the group needs f, g at x (I_TASK == FG on return) or has stopped (I_ACTIVE == 0)
+// LbfgsbDriver::advance (lbfgsb.cpp): step until the group needs f, g at x (I_TASK == FG on return) or has stopped (I_ACTIVE == 0)
 __device__ void lb_advance(const LbLds L, int maxiter, int lane) {
   while (ISR(I_ACTIVE)) {
     const int task = lb_step(L, lane);

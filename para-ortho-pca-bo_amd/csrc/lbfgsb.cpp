@@ -128,7 +128,7 @@ inline double ddot(int n, const double* x, const double* y) {
   return s;
 }
 
-// ---- the second summation order ("tree", Lbfgsb::set_sum_order(1)) ---------------------------------------------------
+// ---- the second summation order ("tree", sum_order 1 of Lbfgsb::init) ---------------------------------------------------
 // The sums over the VARIABLES (the inner products d'd, g'd, r'r, the 2m accumulations W'd of cauchy / formk / subsm / matupd,
 // f1 of the Cauchy search, the descent test of subsm) in the order a 64-lane wavefront forms them without a serial chain:
 // lane l adds the terms l, l + 64, l + 128, ... in that order, then the 64 lane sums meet in a balanced tree of adjacent
@@ -212,7 +212,7 @@ int dtrsl(const double* t, int ldt, int nn, double* b, int job) {
 }
 
 // dtrsl with the pivots' reciprocals formed first (r_j = 1 / t_jj, one division each) and multiplied in: the form of the tree /
-// wave order (set_sum_order(1)) - on a wavefront the pivots' reciprocals are formed side by side, and the solve's chain of nn
+// wave order (sum_order 1) - on a wavefront the pivots' reciprocals are formed side by side, and the solve's chain of nn
 // dependent divisions becomes a chain of multiplications.  One more rounding per pivot than the published division.
 int dtrsl_recip(const double* t, int ldt, int nn, double* b, int job) {
   double r[2 * LBFGSB_MAXM];
@@ -240,19 +240,16 @@ int dtrsl_recip(const double* t, int ldt, int nn, double* b, int job) {
 
 }  // namespace
 
-namespace { std::atomic<int> g_default_sum_order{0}; }
-int lbfgsb_set_default_sum_order(int order) { return g_default_sum_order.exchange(order ? 1 : 0); }
-
 int lbfgsb_set_vector_kernels(int enabled) {
   const bool was = &vec_kernels() != &g_scalar_kernels;
   g_kernels.store(enabled ? default_kernels() : &g_scalar_kernels, std::memory_order_release);
   return was ? 1 : 0;
 }
 
-void Lbfgsb::init(int n, int m, const double* lower, const double* upper, double factr, double pgtol, int maxls) {
+void Lbfgsb::init(int n, int m, const double* lower, const double* upper, double factr, double pgtol, int maxls, int sum_order) {
   if (m > LBFGSB_MAXM) m = LBFGSB_MAXM;
   n_ = n; m_ = m; factr_ = factr; pgtol_ = pgtol; maxls_ = maxls;
-  sum_order_ = g_default_sum_order.load();
+  sum_order_ = sum_order ? 1 : 0;
   l_.assign(n, 0.0); u_.assign(n, 0.0); nbd_.assign(n, 0);
   for (int i = 0; i < n; ++i) {
     double lo = lower ? lower[i] : -INFINITY, hi = upper ? upper[i] : INFINITY;
@@ -1220,4 +1217,43 @@ int Lbfgsb::step(double* x, double* fp, double* g) {
     task_ = LBFGSB_NEW_X;
     return task_;
   }
+}
+
+void LbfgsbDriver::init(int n, const double* x0, const double* lower, const double* upper, int sum_order, int maxiter_,
+                        int maxfun_, int m, double factr, double pgtol, int maxls) {
+  x.assign(x0, x0 + n);
+  if (lower && upper)
+    for (int i = 0; i < n; ++i) x[i] = x[i] < lower[i] ? lower[i] : (x[i] > upper[i] ? upper[i] : x[i]);     // np.clip
+  g.assign(n, 0.0);
+  xc.clear(); gc.clear();
+  if (keep_accepted) xacc = x;
+  f = fc = 0.0;
+  niter = nfev = 0; maxiter = maxiter_; maxfun = maxfun_;
+  have_cache = false; active = true;
+  opt.init(n, m, lower, upper, factr, pgtol, maxls, sum_order);
+}
+
+bool LbfgsbDriver::advance() {
+  while (active) {
+    const int task = opt.step(x.data(), &f, g.data());
+    if (task == LBFGSB_FG) {
+      if (have_cache && memcmp(x.data(), xc.data(), x.size() * sizeof(double)) == 0) { f = fc; g = gc; continue; }
+      return true;
+    }
+    if (task == LBFGSB_NEW_X) {
+      niter += 1;
+      if (keep_accepted) xacc = x;
+      if (niter >= maxiter) opt.stop(LBFGSB_STOP_ITER);
+      else if (nfev > maxfun) opt.stop(LBFGSB_STOP_FUN);
+      continue;
+    }
+    active = false;
+  }
+  return false;
+}
+
+void LbfgsbDriver::absorb(double fx) {
+  f = fx;
+  nfev += 1;
+  xc = x; gc = g; fc = f; have_cache = true;
 }

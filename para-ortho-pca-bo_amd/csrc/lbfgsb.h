@@ -26,14 +26,13 @@ enum {
 
 // 0: scalar O(m n) loops, 1: the default (AVX2 where available); same iterates either way.  Returns the previous setting.
 int lbfgsb_set_vector_kernels(int enabled);
-// Summation order of the sums over the variables for optimisers initialised from now on: 0 the published order (scipy's iterates),
-// 1 the 64-lane tree order the device-resident optimiser steps in (see lbfgsb.cpp).  Returns the previous default.
-int lbfgsb_set_default_sum_order(int order);
 
 class Lbfgsb {
  public:
-  // lower/upper may be null (unbounded); +-inf entries mean "no bound on that side".
-  void init(int n, int m, const double* lower, const double* upper, double factr, double pgtol, int maxls);
+  // lower/upper may be null (unbounded); +-inf entries mean "no bound on that side".  sum_order: the order of the sums over the
+  // variables - 0 the published order (scipy's iterates), 1 the 64-lane tree order the device-resident optimiser steps in
+  // (see lbfgsb.cpp).
+  void init(int n, int m, const double* lower, const double* upper, double factr, double pgtol, int maxls, int sum_order);
   int step(double* x, double* f, double* g);
   void stop(int code) { task_ = code; }
   int task() const { return task_; }
@@ -44,8 +43,6 @@ class Lbfgsb {
     return 2;
   }
   int iterations() const { return iter_; }
-  void set_sum_order(int order) { sum_order_ = order ? 1 : 0; }      // (after init, before the first step)
-  int sum_order() const { return sum_order_; }
 
  private:
   // problem
@@ -95,4 +92,23 @@ class Lbfgsb {
                      double stpmax, Dcsrch& s);
   static void dcstep(double* stx, double* fx, double* dx, double* sty, double* fy, double* dy, double* stp, double fp,
                      double dp, bool* brackt, double stpmin, double stpmax);
+};
+
+// scipy.optimize.minimize(method="L-BFGS-B") around Lbfgsb: what scipy's _minimize_lbfgsb does around setulb.  The start is
+// clipped into the box (when both sides are given); ScalarFunction memoises the last evaluated point, so a trial point that
+// repeats it (a line-search step that underflowed) is neither evaluated nor counted; an iteration ends in NEW_X; the run stops
+// after maxiter iterations or once more than maxfun evaluations were made.  Use:
+//   while (run.advance()) { evaluate f and the gradient at run.x, the gradient into run.g; run.absorb(f); }
+struct LbfgsbDriver {
+  Lbfgsb opt;
+  std::vector<double> x, g;            // the point and the gradient there
+  std::vector<double> xc, gc, xacc;    // the last evaluated point and its gradient; the last accepted iterate (keep_accepted)
+  double f = 0.0, fc = 0.0;
+  int niter = 0, nfev = 0, maxiter = 15000, maxfun = 15000;
+  bool have_cache = false, active = true;
+  bool keep_accepted = false;          // (set before init) track xacc: the clipped start, then x at every NEW_X
+  void init(int n, const double* x0, const double* lower, const double* upper, int sum_order = 0, int maxiter = 15000,
+            int maxfun = 15000, int m = 10, double factr = 1e7, double pgtol = 1e-5, int maxls = 20);
+  bool advance();                      // step until f, g are needed at x (true) or the run has stopped (false)
+  void absorb(double fx);              // one evaluation at x: fx, and the gradient the caller wrote into g
 };

@@ -859,8 +859,8 @@ int pcabo_gp_mll(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k,
   return mll_eval(ctx, n, k, unb, theta, loss, grad);
 }
 
-// scipy.optimize.minimize(method="L-BFGS-B") with its defaults around mll_eval (the driver of pcabo_lbfgsb_minimize: x0 clipped
-// into the box, scipy's memoisation of the last point, its iteration / evaluation limits).
+// scipy.optimize.minimize(method="L-BFGS-B") with its defaults around mll_eval (LbfgsbDriver, as pcabo_lbfgsb_minimize: x0
+// clipped into the box, scipy's memoisation of the last point, its iteration / evaluation limits).
 int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
                  double* theta_inout, double* loss, int* info) {
   if (!ctx) return PCABO_ERR_ARG;
@@ -868,55 +868,37 @@ int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k,
   const double* unb = nullptr;
   int rc = stage_fit_inputs(ctx, "pcabo_gp_fit", Z, y, n, k, norm_bounds, kernel, &unb);
   if (rc != PCABO_OK) return rc;
-  const int NV = 3, maxiter = 15000, maxfun = 15000;
   const double lower[3] = {1e-4, -INFINITY, -INFINITY}, upper[3] = {INFINITY, INFINITY, INFINITY};
-  Lbfgsb opt;
-  opt.init(NV, 10, lower, upper, 1e7, 1e-5, 20);
-  opt.set_sum_order(0);                                  // the published order, whatever the process-wide default
-  double x[3], g[3] = {0.0, 0.0, 0.0}, f = 0.0;
-  for (int i = 0; i < NV; ++i) x[i] = theta_inout[i] < lower[i] ? lower[i] : (theta_inout[i] > upper[i] ? upper[i] : theta_inout[i]);
-  double xc[3], gc[3], fc = 0.0, xacc[3];               // last evaluated point (the context is conditioned there) / last accepted
-  bool have_c = false, not_pd = false;
-  memcpy(xacc, x, sizeof(x));
-  int iters = 0, evals = 0;
-  while (true) {
-    const int task = opt.step(x, &f, g);
-    if (task == LBFGSB_FG) {
-      if (have_c && memcmp(x, xc, sizeof(x)) == 0) { f = fc; memcpy(g, gc, sizeof(g)); continue; }
-      rc = mll_eval(ctx, n, k, unb, x, &f, g);
-      if (rc == PCABO_ERR_NOT_PD) {                      // a trial theta the factorisation cannot take: stop, keep the last iterate
-        if (!have_c) return rc;                          // (not even the start)
-        not_pd = true;
-        break;
-      }
-      if (rc != PCABO_OK) return rc;
-      ++evals;
-      memcpy(xc, x, sizeof(x)); memcpy(gc, g, sizeof(g)); fc = f; have_c = true;
-      continue;
+  LbfgsbDriver fit;                                      // scipy's defaults and limits, the published order
+  fit.keep_accepted = true;
+  fit.init(3, theta_inout, lower, upper);
+  bool not_pd = false;
+  while (fit.advance()) {
+    double f = 0.0;
+    rc = mll_eval(ctx, n, k, unb, fit.x.data(), &f, fit.g.data());
+    if (rc == PCABO_ERR_NOT_PD) {                        // a trial theta the factorisation cannot take: stop, keep the last iterate
+      if (!fit.have_cache) return rc;                    // (not even the start)
+      not_pd = true;
+      break;
     }
-    if (task == LBFGSB_NEW_X) {
-      ++iters;
-      memcpy(xacc, x, sizeof(x));
-      if (iters >= maxiter) opt.stop(LBFGSB_STOP_ITER);
-      else if (evals > maxfun) opt.stop(LBFGSB_STOP_FUN);
-      continue;
-    }
-    break;
+    if (rc != PCABO_OK) return rc;
+    fit.absorb(f);
   }
-  if (!not_pd) memcpy(xacc, x, sizeof(x));               // where the optimiser ended (it restores the last iterate itself)
-  // leave the context conditioned at the result (and report the loss there)
-  double fr = fc;
-  if (!have_c || memcmp(xacc, xc, sizeof(xacc)) != 0) {
+  // the result: where the optimiser ended (it restores the last iterate itself), after a NOT_PD stop the last accepted iterate.
+  // Leave the context conditioned there (it is conditioned at the last evaluated point) and report the loss there.
+  const double* xr = not_pd ? fit.xacc.data() : fit.x.data();
+  double fr = fit.fc;
+  if (!fit.have_cache || memcmp(xr, fit.xc.data(), 3 * sizeof(double)) != 0) {
     double gr[3];
-    rc = mll_eval(ctx, n, k, unb, xacc, &fr, gr);
+    rc = mll_eval(ctx, n, k, unb, xr, &fr, gr);
     if (rc != PCABO_OK) return rc;
   }
-  memcpy(theta_inout, xacc, sizeof(xacc));
+  memcpy(theta_inout, xr, 3 * sizeof(double));
   if (loss) *loss = fr;
   if (info) {
-    info[0] = iters; info[1] = evals;
-    info[2] = not_pd ? 2 : opt.warnflag();
-    info[3] = not_pd ? PCABO_FIT_TASK_NOT_PD : opt.task();
+    info[0] = fit.niter; info[1] = fit.nfev;
+    info[2] = not_pd ? 2 : fit.opt.warnflag();
+    info[3] = not_pd ? PCABO_FIT_TASK_NOT_PD : fit.opt.task();
   }
   return PCABO_OK;
 }
@@ -1156,58 +1138,17 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
   HIPCHK(hipSetDevice(ctx->device));
   const int k = ctx->k;
   const int ngroups = (num_restarts + batch_limit - 1) / batch_limit;
-  std::vector<Lbfgsb> opt(ngroups);
-  std::vector<int> gstart(ngroups), gsize(ngroups), niter(ngroups, 0), nfev(ngroups, 0);
-  std::vector<char> active(ngroups, 1);     // char, not vector<bool>: groups are touched from two threads
-  std::vector<std::vector<double>> x(ngroups), g(ngroups), lo(ngroups), hi(ngroups);
-  std::vector<double> fval(ngroups, 0.0), fc(ngroups, 0.0);
-  std::vector<std::vector<double>> xc(ngroups), gc(ngroups), vc(ngroups);   // vc: per-restart values of the cached evaluation
-  std::vector<char> have_cache(ngroups, 0);
-  for (int gi = 0; gi < ngroups; ++gi) {
-    gstart[gi] = gi * batch_limit;
-    gsize[gi] = std::min(batch_limit, num_restarts - gstart[gi]);
-    const int nv = gsize[gi] * k;
-    x[gi].resize(nv); g[gi].assign(nv, 0.0); lo[gi].resize(nv); hi[gi].resize(nv);
-    for (int j = 0; j < gsize[gi]; ++j)
-      for (int c = 0; c < k; ++c) {
-        double l = bounds[c], h = bounds[k + c];
-        double v = ics[(size_t)(gstart[gi] + j) * k + c];
-        lo[gi][j * k + c] = l; hi[gi][j * k + c] = h;
-        x[gi][j * k + c] = v < l ? l : (v > h ? h : v);          // columnwise_clamp / np.clip
-      }
-    opt[gi].init(nv, 10, lo[gi].data(), hi[gi].data(), 1e7, 1e-5, 20);
-  }
+  std::vector<RestartGroup> grp(ngroups);
+  for (int gi = 0; gi < ngroups; ++gi)
+    grp[gi].init(ics, bounds, gi * batch_limit, std::min(batch_limit, num_restarts - gi * batch_limit), k, maxiter);
   AcqParams p = make_params(ctx, best_f, maximize, acq, 1);
-  const int maxfun = 15000;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  int any_failed = 0;
-  // advance one group's state machine until it needs f,g at x[gi] (or stops)
-  // scipy wraps the objective in a ScalarFunction that memoises the last evaluated point: when a shrinking
-  // line-search step underflows and the trial point repeats, the function is neither called nor counted.
-  // Same here (xc/fc/gc = last evaluated point of the group and its value/gradient).
-  std::vector<char> pending(ngroups, 0);    // x[gi] waits for its evaluation (left so by the free-running mode below)
+  // advance one group until it needs f, g at its x (or stops); a group the free-running mode below left waiting for its
+  // evaluation (pending: char, not vector<bool> - groups are touched from two threads) is not stepped again
+  std::vector<char> pending(ngroups, 0);
   auto advance = [&](int gi) {
-    if (!active[gi]) return;
-    if (pending[gi]) { pending[gi] = 0; return; }
-    while (true) {
-      int task = opt[gi].step(x[gi].data(), &fval[gi], g[gi].data());
-      if (task == LBFGSB_FG) {
-        if (have_cache[gi] && memcmp(x[gi].data(), xc[gi].data(), x[gi].size() * sizeof(double)) == 0) {
-          fval[gi] = fc[gi];
-          g[gi] = gc[gi];
-          continue;
-        }
-        return;
-      }
-      if (task == LBFGSB_NEW_X) {
-        niter[gi] += 1;
-        if (niter[gi] >= maxiter) opt[gi].stop(LBFGSB_STOP_ITER);
-        else if (nfev[gi] > maxfun) opt[gi].stop(LBFGSB_STOP_FUN);
-        continue;
-      }
-      active[gi] = false;
-      return;
-    }
+    if (pending[gi]) pending[gi] = 0;
+    else grp[gi].advance();
   };
   // The groups are independent between evaluations: odd-numbered groups advance on the context's helper thread
   // while the calling thread advances the even ones (hand-off through two monotonic round counters, spin-waiting).
@@ -1251,10 +1192,10 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
     int nq = 0;
     for (int gi = 0; gi < ngroups; ++gi) {
       qoff[gi] = -1;
-      if (!active[gi]) continue;
+      if (!grp[gi].active) continue;
       qoff[gi] = nq;
-      memcpy(ctx->hXq + (size_t)nq * k, x[gi].data(), (size_t)gsize[gi] * k * sizeof(double));
-      nq += gsize[gi];
+      memcpy(ctx->hXq + (size_t)nq * k, grp[gi].x.data(), grp[gi].x.size() * sizeof(double));
+      nq += grp[gi].nq;
     }
     if (nq == 0) break;
     int rc;
@@ -1270,7 +1211,7 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
                  ctx->dBounds4, ctx->dYstats, p, ctx->dPartial, ctx->dCounters, ctx->dVal, ctx->dGrad, ctx->hVal, ctx->hGrad,
                  ctx->hm, ctx->seq + 1, ctx->dMail, ctx->dPairs);
       HIPCHK(hipGetLastError());
-      if (ngroups == 2 && active[0] && active[1] && nq == num_restarts) {
+      if (ngroups == 2 && grp[0].active && grp[1].active && nq == num_restarts) {
         // ---- the two restart groups free of each other ------------------------------------------------------------
         // Each group has its own slots, control pairs and round counter in the mailbox, so each host thread drives its
         // own group (post - wait - L-BFGS-B step) without meeting the other: a round no longer waits for the slower of
@@ -1282,12 +1223,13 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
         int timed_out[2] = {0, 0}, got_nan[2] = {0, 0}, left[2] = {0, 0}, slow_first[2] = {0, 0};
         unsigned long long used[2] = {0, 0};
         auto free_loop = [&](int gi) {
-          const int q0 = gstart[gi], nqg = gsize[gi];
+          RestartGroup& rg = grp[gi];
+          const int q0 = rg.q0, nqg = rg.nq;
           unsigned long long r = 0;
           for (;;) {
             if (abort_flag.load(std::memory_order_relaxed)) { pending[gi] = 1; break; }
             const unsigned long long tag = seq0 + (++r);
-            for (int t = 0; t < nqg * k; ++t) put_mail_pair(m + 1 + q0 * k + t, x[gi][t], tag);
+            for (int t = 0; t < nqg * k; ++t) put_mail_pair(m + 1 + q0 * k + t, rg.x[t], tag);
             for (int j = 0; j < nqg; ++j) put_mail_pair(m + 1 + cap * k + q0 + j, 1.0, tag);
             _mm_sfence();
             const auto t0 = std::chrono::steady_clock::now();
@@ -1305,21 +1247,8 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
             }
             if (!ok) { pending[gi] = 1; break; }
             if (r == 1 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(1)) slow_first[gi] = 1;
-            double fs = 0.0;
-            bool nan = false;
-            for (int j = 0; j < nqg; ++j) fs += ctx->hVal[q0 + j];
-            for (int t = 0; t < nqg * k; ++t) {
-              const double gv = -ctx->hGrad[(size_t)q0 * k + t];
-              if (gv != gv) nan = true;
-              g[gi][t] = gv;
-            }
-            if (nan) { got_nan[gi] = 1; abort_flag.store(1, std::memory_order_relaxed); break; }
-            fval[gi] = -fs;
-            nfev[gi] += 1;
-            xc[gi] = x[gi]; gc[gi] = g[gi]; fc[gi] = fval[gi]; have_cache[gi] = 1;
-            vc[gi].assign(ctx->hVal + q0, ctx->hVal + q0 + nqg);
-            advance(gi);
-            if (!active[gi]) break;
+            if (!rg.absorb(ctx->hVal, ctx->hGrad, q0)) { got_nan[gi] = 1; abort_flag.store(1, std::memory_order_relaxed); break; }
+            if (!rg.advance()) break;
           }
           // this group's slab and finishing groups may go (they wait for round r + 1 of their own count)
           const unsigned long long bye = seq0 + r + 1;
@@ -1340,7 +1269,7 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
         if (got_nan[0] || got_nan[1]) return set_err(ctx, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
         if (timed_out[0] || timed_out[1]) ctx->srv_penalty = 1000;      // plain launches from here on (see below)
         else if (slow_first[0] || slow_first[1]) ctx->srv_penalty = 40;
-        if (!active[0] && !active[1]) break;            // the normal end: both groups ran to their stop
+        if (!grp[0].active && !grp[1].active) break;    // the normal end: both groups ran to their stop
         continue;                                       // a wait failed: the lock-step loop below finishes the call
       }
     }
@@ -1361,56 +1290,34 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
       }
     } else if (group_mode(ctx, nq, 1) && batch_limit <= PCABO_GROUP_Q && ngroups <= 8) {
       int g0[8], gn[8], ng = 0;
-      for (int gi = 0; gi < ngroups; ++gi) if (qoff[gi] >= 0) { g0[ng] = qoff[gi]; gn[ng] = gsize[gi]; ++ng; }
+      for (int gi = 0; gi < ngroups; ++gi) if (qoff[gi] >= 0) { g0[ng] = qoff[gi]; gn[ng] = grp[gi].nq; ++ng; }
       rc = eval_staged_groups(ctx, g0, gn, ng, p);
     } else {
       rc = eval_staged(ctx, nq, p);
     }
     if (rc != PCABO_OK) return rc;
-    for (int gi = 0; gi < ngroups; ++gi) {
-      if (qoff[gi] < 0) continue;
-      double fs = 0.0;
-      bool nan = false;
-      for (int j = 0; j < gsize[gi]; ++j) fs += ctx->hVal[qoff[gi] + j];
-      for (int t = 0; t < gsize[gi] * k; ++t) {
-        double gv = -ctx->hGrad[(size_t)qoff[gi] * k + t];
-        if (gv != gv) nan = true;
-        g[gi][t] = gv;
-      }
-      if (nan) return set_err(ctx, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
-      fval[gi] = -fs;
-      nfev[gi] += 1;
-      xc[gi] = x[gi]; gc[gi] = g[gi]; fc[gi] = fval[gi]; have_cache[gi] = 1;
-      vc[gi].assign(ctx->hVal + qoff[gi], ctx->hVal + qoff[gi] + gsize[gi]);
-    }
+    for (int gi = 0; gi < ngroups; ++gi)
+      if (qoff[gi] >= 0 && !grp[gi].absorb(ctx->hVal, ctx->hGrad, qoff[gi]))
+        return set_err(ctx, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
   }
   server_stop.stop();
-  // final clamp and acquisition values at the candidates (no gradient)
-  for (int gi = 0; gi < ngroups; ++gi) {
-    for (int t = 0; t < gsize[gi] * k; ++t) {
-      double v = x[gi][t];
-      v = v < lo[gi][t] ? lo[gi][t] : (v > hi[gi][t] ? hi[gi][t] : v);
-      cand[(size_t)gstart[gi] * k + t] = v;
-      ctx->hXq[(size_t)gstart[gi] * k + t] = v;
-    }
-    int wf = opt[gi].warnflag();
-    if (info) { info[4 * gi] = niter[gi]; info[4 * gi + 1] = nfev[gi]; info[4 * gi + 2] = wf; info[4 * gi + 3] = opt[gi].task(); }
-    if (wf == 2) any_failed = 1;
-  }
   // botorch evaluates the acquisition once more at the clamped end points.  An L-BFGS-B run normally ends ON the last point
   // it had evaluated (the accepted trial of its last line search), whose per-restart values are still here - the same
   // kernel arithmetic, so the same bits; only a run that ended elsewhere (abnormal line search) needs the launch.
+  int any_failed = 0;
   bool reuse = true;
-  for (int gi = 0; gi < ngroups && reuse; ++gi)
-    reuse = have_cache[gi] && (int)vc[gi].size() == gsize[gi] &&
-            memcmp(cand + (size_t)gstart[gi] * k, xc[gi].data(), (size_t)gsize[gi] * k * sizeof(double)) == 0;
+  for (int gi = 0; gi < ngroups; ++gi) {
+    grp[gi].end_point(cand);
+    reuse = reuse && grp[gi].ends_on_cache(cand);
+    if (grp[gi].report(info, gi)) any_failed = 1;
+  }
   if (reuse) {
-    for (int gi = 0; gi < ngroups; ++gi)
-      for (int j = 0; j < gsize[gi]; ++j) vals[gstart[gi] + j] = vc[gi][j];
+    for (const RestartGroup& rg : grp) std::copy(rg.vc.begin(), rg.vc.end(), vals + rg.q0);
   } else {
     AcqParams pv = make_params(ctx, best_f, maximize, acq, 0);
     // (through the slab kernels whatever the number of restarts: the values of a restart must not depend on how many
     // restarts share the call)
+    memcpy(ctx->hXq, cand, (size_t)num_restarts * k * sizeof(double));
     int rc = eval_staged(ctx, num_restarts, pv, false);
     if (rc != PCABO_OK) return rc;
     for (int j = 0; j < num_restarts; ++j) vals[j] = ctx->hVal[j];
@@ -2208,8 +2115,8 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
     groups[b].resize(ngroups);
     for (int gi = 0; gi < ngroups; ++gi) {
       const int q0 = gi * batch_limit, nq = std::min(batch_limit, num_restarts - q0);
-      groups[b][gi].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, q0, nq, batch->ctx[b]->k, maxiter);
-      groups[b][gi].opt.set_sum_order(1);              // the device steps in the 64-lane tree order (lbfgsb.cpp): so does its twin
+      // (the device steps in the 64-lane tree order of lbfgsb.cpp: so does its twin)
+      groups[b][gi].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, q0, nq, batch->ctx[b]->k, maxiter, 1);
     }
   }
   struct Pending { int b, gi; };
@@ -2235,7 +2142,8 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
     if (rc != PCABO_OK) return rc;
     for (const Pending& pe : pend) {
       pcabo_ctx* c = batch->ctx[pe.b];
-      if (!groups[pe.b][pe.gi].absorb(c->hVal, c->hGrad)) {
+      RestartGroup& rg = groups[pe.b][pe.gi];
+      if (!rg.absorb(c->hVal, c->hGrad, rg.q0)) {
         run_status[pe.b] = PCABO_ERR_NAN;
         set_err(c, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
       }
@@ -2250,15 +2158,9 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
       const int k = c->k;
       double* cb = cand + (size_t)b * num_restarts * MD;
       for (int gi = 0; gi < ngroups; ++gi) {
-        RestartGroup& rg = groups[b][gi];
-        for (int t = 0; t < rg.nq * k; ++t) {
-          double v = rg.x[t];
-          v = v < rg.lo[t] ? rg.lo[t] : (v > rg.hi[t] ? rg.hi[t] : v);
-          cb[(size_t)rg.q0 * k + t] = v;
-        }
-        const bool reuse = rg.have_cache && (int)rg.vc.size() == rg.nq &&
-                           memcmp(cb + (size_t)rg.q0 * k, rg.xc.data(), (size_t)rg.nq * k * sizeof(double)) == 0;
-        if (reuse) { for (int j = 0; j < rg.nq; ++j) vals[(size_t)b * num_restarts + rg.q0 + j] = rg.vc[j]; }
+        const RestartGroup& rg = groups[b][gi];
+        rg.end_point(cb);
+        if (rg.ends_on_cache(cb)) std::copy(rg.vc.begin(), rg.vc.end(), vals + (size_t)b * num_restarts + rg.q0);
         else {
           memcpy(c->hXq + (size_t)rg.q0 * k, cb + (size_t)rg.q0 * k, (size_t)rg.nq * k * sizeof(double));
           batch->hOptTab[nent++] = ((unsigned)b << 16) | ((unsigned)rg.q0 << 8) | (unsigned)rg.nq;
@@ -2277,12 +2179,8 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
   }
   for (int b = 0; b < B; ++b) {
     int any_failed = 0;
-    for (int gi = 0; gi < (int)groups[b].size(); ++gi) {
-      const RestartGroup& rg = groups[b][gi];
-      const int wf = rg.opt.warnflag();
-      if (info) { int* o = info + ((size_t)b * ngroups + gi) * 4; o[0] = rg.niter; o[1] = rg.nfev; o[2] = wf; o[3] = rg.opt.task(); }
-      if (wf == 2) any_failed = 1;
-    }
+    for (int gi = 0; gi < (int)groups[b].size(); ++gi)
+      if (groups[b][gi].report(info, (size_t)b * ngroups + gi)) any_failed = 1;
     if (failed) failed[b] = any_failed;
   }
   fill_status(run_status);
@@ -2390,7 +2288,8 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
       }
       for (const Pending& pe : pend) {
         pcabo_ctx* c = batch->ctx[pe.b];
-        if (!groups[pe.b][pe.gi].absorb(c->hVal, c->hGrad)) {
+        RestartGroup& rg = groups[pe.b][pe.gi];
+        if (!rg.absorb(c->hVal, c->hGrad, rg.q0)) {
           run_status[pe.b] = PCABO_ERR_NAN;
           set_err(c, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
         }
@@ -2423,19 +2322,12 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
       const int k = c->k;
       double* cb = cand + (size_t)b * num_restarts * MD;
       bool reuse = true;
-      for (int gi = 0; gi < ngroups; ++gi) {
-        RestartGroup& rg = groups[b][gi];
-        for (int t = 0; t < rg.nq * k; ++t) {
-          double v = rg.x[t];
-          v = v < rg.lo[t] ? rg.lo[t] : (v > rg.hi[t] ? rg.hi[t] : v);
-          cb[(size_t)rg.q0 * k + t] = v;
-        }
-        reuse = reuse && rg.have_cache && (int)rg.vc.size() == rg.nq &&
-                memcmp(cb + (size_t)rg.q0 * k, rg.xc.data(), (size_t)rg.nq * k * sizeof(double)) == 0;
+      for (const RestartGroup& rg : groups[b]) {
+        rg.end_point(cb);
+        reuse = reuse && rg.ends_on_cache(cb);
       }
       if (reuse) {
-        for (int gi = 0; gi < ngroups; ++gi)
-          for (int j = 0; j < groups[b][gi].nq; ++j) vals[(size_t)b * num_restarts + groups[b][gi].q0 + j] = groups[b][gi].vc[j];
+        for (const RestartGroup& rg : groups[b]) std::copy(rg.vc.begin(), rg.vc.end(), vals + (size_t)b * num_restarts + rg.q0);
       } else {
         memcpy(c->hXq, cb, (size_t)num_restarts * k * sizeof(double));
         for (int j = 0; j < num_restarts; ++j) ent[nent++] = ((unsigned)b << 16) | (unsigned)j;
@@ -2457,15 +2349,8 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
   }
   for (int b = 0; b < B; ++b) {
     int any_failed = 0;
-    for (int gi = 0; gi < (int)groups[b].size(); ++gi) {
-      const RestartGroup& rg = groups[b][gi];
-      const int wf = rg.opt.warnflag();
-      if (info) {
-        int* o = info + ((size_t)b * ngroups + gi) * 4;
-        o[0] = rg.niter; o[1] = rg.nfev; o[2] = wf; o[3] = rg.opt.task();
-      }
-      if (wf == 2) any_failed = 1;
-    }
+    for (int gi = 0; gi < (int)groups[b].size(); ++gi)
+      if (groups[b][gi].report(info, (size_t)b * ngroups + gi)) any_failed = 1;
     if (failed) failed[b] = any_failed;
     if (status) status[b] = run_status[b];
   }

@@ -123,7 +123,7 @@ def test_vector_kernels_take_the_scalar_iterates(native):
 
 def test_tree_order_of_the_device_optimiser_keeps_scipys_counts(native):
     """The summation order in which the device-resident optimiser steps (64-lane tree over the variables, reciprocal pivots in the
-    small triangular solves; Lbfgsb::set_sum_order(1), the device's bit-for-bit twin - tests/test_gpu_device_lbfgsb.py) on the same
+    small triangular solves; sum order 1 of Lbfgsb::init, the device's bit-for-bit twin - tests/test_gpu_device_lbfgsb.py) on the same
     35 bounded problems and the joint 5-restart acquisition problem: iteration and evaluation counts are scipy's on every one of
     them, end points within the same tolerance (the gate for a second arithmetic order)."""
     was = native.lbfgsb_set_sum_order(1)
