@@ -1,8 +1,8 @@
 // Sanitizer driver for the host side of libpcabo (Makefile targets asan / ubsan / tsan; tests/test_host_sanitizers.py runs them).
 // Everything here is CPU code of the product compiled by g++ with -fsanitize=...: csrc/lbfgsb.cpp, csrc/host_entry.cpp (the
-// L-BFGS-B driver and the Sobol helpers), csrc/host_side.h (RestartGroup, GangPool) and csrc/lb_plan.h (the work plan of the device
-// optimiser's passes).  The launcher is a stub: where the product launches an acquisition kernel and polls its flags, the
-// workers here evaluate a bounded test objective on the CPU - same table packing, same per-thread tables, same pool protocol.
+// L-BFGS-B driver and the Sobol helpers), csrc/host_side.h (RestartGroup, RunRestarts, run_rounds, GangPool) and csrc/lb_plan.h (the
+// work plan of the device optimiser's passes).  The batch's round loop is the product's run_rounds with a stub evaluator: where the
+// product launches an acquisition kernel and polls its flags, the workers here evaluate a bounded test objective on the CPU.
 // Exit code 0 and "host selftest ok" = every check passed; a sanitizer report aborts the process (halt_on_error).
 #include "../../include/pcabo.h"
 #include "host_side.h"
@@ -257,17 +257,14 @@ void test_restart_group() {
         trail0.size(), trail1.size());
 }
 
-// RestartGroups of several "runs" stepped by the pool's workers, each worker with its own launch table on its stack (the
-// product's shape: run << 16 | first query << 8 | count), values and gradients written into per-run blocks and absorbed.
+// The product's round loop (run_rounds, host_side.h) over several "runs", stepped by the pool's workers: each worker drives its
+// own runs with its own launch table on its stack; the stub evaluator does what the kernel would do with the table (the CPU
+// objective, written into each run's host block).  Then the end points as the product takes them.
 void test_gang_pool(int workers, int runs) {
   const int k = 7, nq = 5, ngroups = 2, restarts = nq * ngroups;
-  std::vector<std::vector<RestartGroup>> groups(runs);
+  std::vector<RunRestarts> run(runs);
   std::vector<Objective> obj(runs);
-  std::vector<std::vector<double>> ics(runs), bounds(runs), hXq(runs), hVal(runs), hGrad(runs);
-  // every second run steps in the device optimiser's order (the twin's setting)
-  auto init_groups = [&](int b) {
-    for (int gi = 0; gi < ngroups; ++gi) groups[b][gi].init(ics[b].data(), bounds[b].data(), gi * nq, nq, k, 200, b & 1);
-  };
+  std::vector<std::vector<double>> ics(runs), bounds(runs), hXq(runs), hVal(runs), hGrad(runs), cand(runs), vals(runs);
   for (int b = 0; b < runs; ++b) {
     Lcg r(100 + b);
     obj[b].c.resize(k);
@@ -275,58 +272,53 @@ void test_gang_pool(int workers, int runs) {
     ics[b].resize((size_t)restarts * k); bounds[b].resize(2 * k);
     for (auto& v : ics[b]) v = 4.0 * r.uni() - 2.0;
     for (int c = 0; c < k; ++c) { bounds[b][c] = -1.25; bounds[b][k + c] = 1.5; }
-    groups[b].resize(ngroups);
-    init_groups(b);
     hXq[b].assign((size_t)restarts * k, 0.0); hVal[b].assign(restarts, 0.0); hGrad[b].assign((size_t)restarts * k, 0.0);
+    cand[b].assign((size_t)restarts * k, 0.0); vals[b].assign(restarts, 0.0);
+    run[b].bind(hXq[b].data(), hVal[b].data(), hGrad[b].data());
   }
   GangPool pool;
   pool.start(workers);
-  std::atomic<int> rounds{0}, bad{0};
+  std::atomic<int> rounds{0};
   for (int call = 0; call < 3; ++call) {              // the pool is reused across calls, as a batch does per BO iteration
-    if (call > 0) for (int b = 0; b < runs; ++b) init_groups(b);
+    // every second run steps in the device optimiser's order (the twin's setting)
+    for (int b = 0; b < runs; ++b) run[b].init(ics[b].data(), bounds[b].data(), restarts, nq, k, 200, b & 1);
     pool.run([&](int t) {
+      std::vector<int> mine;
+      for (int b = t; b < runs; b += workers) mine.push_back(b);
       unsigned table[64];                              // the worker's own launch table
-      struct Pending { int b, gi; };
-      std::vector<Pending> pend;
-      for (;;) {
-        pend.clear();
-        int nent = 0;
-        for (int b = t; b < runs; b += workers)
-          for (int gi = 0; gi < ngroups; ++gi) {
-            RestartGroup& rg = groups[b][gi];
-            if (!rg.active) continue;
-            rg.advance();
-            if (!rg.active) continue;
-            std::memcpy(hXq[b].data() + (size_t)rg.q0 * k, rg.x.data(), (size_t)rg.nq * k * sizeof(double));
-            if (nent < 64) table[nent++] = ((unsigned)b << 16) | ((unsigned)rg.q0 << 8) | (unsigned)rg.nq;
-            pend.push_back({b, gi});
-          }
-        if (nent == 0) break;
-        for (int e = 0; e < nent; ++e) {               // the stub launcher: what the kernel would do with the table entry
+      int nent = 0;
+      auto stage = [&](int b, const RestartGroup& rg) { if (nent < 64) table[nent++] = group_entry(b, rg.q0, rg.nq); };
+      auto eval = [&] {                                // the stub evaluator: what the kernel would do with the table
+        for (int e = 0; e < nent; ++e) {
           const int b = (int)(table[e] >> 16), q0 = (int)((table[e] >> 8) & 0xffu), cnt = (int)(table[e] & 0xffu);
           for (int j = 0; j < cnt; ++j) {
-            std::vector<double> g(k);
-            const double f = fg_objective(hXq[b].data() + (size_t)(q0 + j) * k, g.data(), &obj[b]);
-            hVal[b][q0 + j] = -f;                      // (the acquisition is maximised: RestartGroup::absorb negates)
-            for (int c = 0; c < k; ++c) hGrad[b][(size_t)(q0 + j) * k + c] = -g[c];
+            double* g = hGrad[b].data() + (size_t)(q0 + j) * k;
+            hVal[b][q0 + j] = -fg_objective(hXq[b].data() + (size_t)(q0 + j) * k, g, &obj[b]);
+            for (int c = 0; c < k; ++c) g[c] = -g[c];  // (the acquisition is maximised: RestartGroup::absorb negates)
           }
         }
-        for (const Pending& pe : pend) {
-          RestartGroup& rg = groups[pe.b][pe.gi];
-          if (!rg.absorb(hVal[pe.b].data(), hGrad[pe.b].data(), rg.q0)) bad.fetch_add(1);
-        }
+        nent = 0;
         rounds.fetch_add(1);
-      }
+        return PCABO_OK;
+      };
+      CHECK(run_rounds(run.data(), mine, stage, eval) == PCABO_OK, "run_rounds failed");
+      for (int b : mine) run[b].end_points(cand[b].data(), vals[b].data());
     });
-    for (int b = 0; b < runs; ++b)
-      for (auto& rg : groups[b]) {
+    for (int b = 0; b < runs; ++b) {
+      CHECK(run[b].status == PCABO_OK, "run %d: status %d", b, run[b].status);
+      int info[4 * ngroups];
+      run[b].report(info, 0);
+      for (int gi = 0; gi < ngroups; ++gi) {
+        const RestartGroup& rg = run[b].grp[gi];
         CHECK(!rg.active, "a group is still active after the call");
+        CHECK(info[4 * gi] == rg.niter && info[4 * gi + 1] == rg.nfev && info[4 * gi + 2] == rg.opt.warnflag(), "report of group %d", gi);
         CHECK(rg.opt.warnflag() >= 0 && rg.opt.warnflag() <= 2, "warnflag");
         for (size_t i = 0; i < rg.x.size(); ++i) CHECK(rg.x[i] >= rg.lo[i] && rg.x[i] <= rg.hi[i], "end point outside the box");
+        CHECK(std::memcmp(cand[b].data() + (size_t)rg.q0 * k, rg.x.data(), rg.x.size() * sizeof(double)) == 0, "end point of group %d", gi);
       }
+    }
   }
   pool.shutdown();
-  CHECK(bad.load() == 0, "NaN gradients: %d", bad.load());
   CHECK(rounds.load() > 0, "no rounds");
 }
 

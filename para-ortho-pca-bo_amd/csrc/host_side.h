@@ -1,14 +1,18 @@
-// Host-side pieces of the optimisers that need no HIP: the restart group (a joint problem on LbfgsbDriver, csrc/lbfgsb.h) and
-// the worker pool of a batch.  Included by pcabo_api.hip (the product) and by host_selftest.cpp (the sanitizer builds of the Makefile:
-// `make asan ubsan tsan` compile this header, lbfgsb.cpp and host_entry.cpp with g++ and run them without a GPU).
+// Host-side pieces of the optimisers that need no HIP: the restart group (a joint problem on LbfgsbDriver, csrc/lbfgsb.h), the
+// restart groups of one run and the round loop over several runs, and the worker pool of a batch.  Included by pcabo_api.hip (the
+// product) and by host_selftest.cpp (the sanitizer builds of the Makefile: `make asan ubsan tsan` compile this header, lbfgsb.cpp
+// and host_entry.cpp with g++ and run them without a GPU).
 #pragma once
+#include "../../include/pcabo.h"
 #include "lbfgsb.h"
 
+#include <algorithm>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
 // One restart group of one run: the joint L-BFGS-B problem of restarts q0 .. q0 + nq - 1 (nq k variables) on the negated
@@ -39,21 +43,86 @@ struct RestartGroup : LbfgsbDriver {
     vc.assign(hVal + row, hVal + row + nq);
     return true;
   }
-  // the end point clamped into the box, into the rows q0 .. q0 + nq - 1 of cand
-  void end_point(double* cand) const {
-    for (int t = 0; t < nq * k; ++t) cand[(size_t)q0 * k + t] = x[t] < lo[t] ? lo[t] : (x[t] > hi[t] ? hi[t] : x[t]);
+};
+
+// The restart groups of one run in one optimise call: restarts q0 .. q0 + batch_limit - 1 per group, and the run's host block
+// (xq: the points the device reads, val / grad: the values and gradients it writes back; row q = restart q).
+struct RunRestarts {
+  std::vector<RestartGroup> grp;
+  int status = PCABO_OK;               // PCABO_ERR_NAN once a gradient had a NaN (run_rounds then leaves the run alone)
+  double* xq = nullptr;
+  const double *val = nullptr, *grad = nullptr;
+  void init(const double* ics, const double* bounds, int num_restarts, int batch_limit, int k, int maxiter, int sum_order = 0) {
+    grp.resize((num_restarts + batch_limit - 1) / batch_limit);
+    for (size_t gi = 0; gi < grp.size(); ++gi) {
+      const int q0 = (int)gi * batch_limit;
+      grp[gi].init(ics, bounds, q0, std::min(batch_limit, num_restarts - q0), k, maxiter, sum_order);
+    }
+    status = PCABO_OK;
   }
-  // the clamped end point in cand is the last evaluated point: its values vc are the ones a launch there would give
-  bool ends_on_cache(const double* cand) const {
-    return have_cache && memcmp(cand + (size_t)q0 * k, xc.data(), (size_t)nq * k * sizeof(double)) == 0;
+  void bind(double* xq_, const double* val_, const double* grad_) { xq = xq_; val = val_; grad = grad_; }
+  // botorch's end: the end points clamped into the box, into cand.  A group whose clamped end point is its last evaluated point
+  // copies that evaluation's values (the ones a launch there would give) into vals; any other is handed to redo(group), which must
+  // evaluate it there.  Returns the number of groups handed on.
+  template <class Redo> int end_points(double* cand, double* vals, Redo&& redo) const {
+    int n = 0;
+    for (const RestartGroup& rg : grp) {
+      double* c = cand + (size_t)rg.q0 * rg.k;
+      for (size_t t = 0; t < rg.x.size(); ++t) c[t] = rg.x[t] < rg.lo[t] ? rg.lo[t] : (rg.x[t] > rg.hi[t] ? rg.hi[t] : rg.x[t]);
+      if (rg.have_cache && memcmp(c, rg.xc.data(), rg.x.size() * sizeof(double)) == 0) std::copy(rg.vc.begin(), rg.vc.end(), vals + rg.q0);
+      else { redo(rg); ++n; }
+    }
+    return n;
   }
-  // niter, nfev, warnflag, task into info[4 slot .. 4 slot + 3] (info may be null); true: the group failed (warnflag 2)
-  bool report(int* info, size_t slot) const {
-    const int wf = opt.warnflag();
-    if (info) { int* o = info + 4 * slot; o[0] = niter; o[1] = nfev; o[2] = wf; o[3] = opt.task(); }
-    return wf == 2;
+  int end_points(double* cand, double* vals) const { return end_points(cand, vals, [](const RestartGroup&) {}); }
+  // niter, nfev, warnflag, task of group gi into info[4 (slot0 + gi) .. + 3] (info may be null); true: some group failed
+  // (warnflag 2)
+  bool report(int* info, size_t slot0) const {
+    bool any = false;
+    for (size_t gi = 0; gi < grp.size(); ++gi) {
+      const RestartGroup& rg = grp[gi];
+      const int wf = rg.opt.warnflag();
+      if (info) { int* o = info + 4 * (slot0 + gi); o[0] = rg.niter; o[1] = rg.nfev; o[2] = wf; o[3] = rg.opt.task(); }
+      if (wf == 2) any = true;
+    }
+    return any;
   }
 };
+
+// Launch-table entries as the acquisition kernels read them: a restart group, or one query
+inline unsigned group_entry(int run, int q0, int nq) { return ((unsigned)run << 16) | ((unsigned)q0 << 8) | (unsigned)nq; }
+inline unsigned query_entry(int run, int q) { return ((unsigned)run << 16) | (unsigned)q; }
+
+// The restart rounds of the runs order[..] (indices into runs) until no group wants an evaluation.  A round advances every
+// active group of every run whose status is PCABO_OK (runs in the given order, groups by index), copies its point into its
+// run's xq and hands it to stage(run, group); eval() then evaluates what was staged since its last call and returns PCABO_OK or
+// an error, which ends the rounds and is returned.  Each staged group absorbs its run's val / grad; a NaN in a gradient sets
+// the run's status to PCABO_ERR_NAN.  Only the runs listed are touched: workers may drive disjoint lists of one runs array.
+template <class Stage, class Eval>
+int run_rounds(RunRestarts* runs, const std::vector<int>& order, Stage&& stage, Eval&& eval) {
+  std::vector<std::pair<RunRestarts*, RestartGroup*>> pend;
+  size_t ng = 0;
+  for (int b : order) ng += runs[b].grp.size();
+  pend.reserve(ng);
+  for (;;) {
+    pend.clear();
+    for (int b : order) {
+      RunRestarts& run = runs[b];
+      if (run.status != PCABO_OK) continue;
+      for (RestartGroup& rg : run.grp) {
+        if (!rg.advance()) continue;
+        std::memcpy(run.xq + (size_t)rg.q0 * rg.k, rg.x.data(), rg.x.size() * sizeof(double));
+        stage(b, rg);
+        pend.push_back({&run, &rg});
+      }
+    }
+    if (pend.empty()) return PCABO_OK;
+    const int rc = eval();
+    if (rc != PCABO_OK) return rc;
+    for (auto& pe : pend)
+      if (!pe.second->absorb(pe.first->val, pe.first->grad, pe.second->q0)) pe.first->status = PCABO_ERR_NAN;
+  }
+}
 
 // Worker pool of a batch: the calling thread is worker 0, n - 1 persistent threads are workers 1..n-1 (sleeping between
 // calls, woken per call).  With one worker nothing leaves the calling thread (PCABO_BATCH_THREADS=1: profiler runs).

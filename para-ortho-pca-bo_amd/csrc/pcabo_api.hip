@@ -226,6 +226,26 @@ static hipError_t wait_event(hipEvent_t ev) {
   }
   return hipEventSynchronize(ev);
 }
+// Spin until the host mirror's qflag[q0 .. q0 + nq) all carry seq (the launch that writes them has published its results) or the
+// deadline passes; given a stream, also stop once that stream has finished while a flag is still missing.
+enum FlagWait { FLAGS_SET, FLAGS_LATE, FLAGS_UNPUBLISHED };
+static FlagWait wait_flags(const HostMirror* hm, int q0, int nq, unsigned long long seq,
+                           std::chrono::steady_clock::time_point deadline, const hipStream_t* s = nullptr) {
+  unsigned long spins = 0;
+  for (int q = q0; q < q0 + nq; ++q)
+    while (__atomic_load_n(&hm->qflag[q], __ATOMIC_ACQUIRE) != seq) {
+      if ((++spins & 0xFFFF) != 0) continue;
+      if (s && hipStreamQuery(*s) == hipSuccess) {              // the launch is over: the flag must be there
+        if (__atomic_load_n(&hm->qflag[q], __ATOMIC_ACQUIRE) == seq) break;
+        return FLAGS_UNPUBLISHED;
+      }
+      if (std::chrono::steady_clock::now() > deadline) return FLAGS_LATE;
+    }
+  return FLAGS_SET;
+}
+static std::chrono::steady_clock::time_point deadline_in(int seconds) {
+  return std::chrono::steady_clock::now() + std::chrono::seconds(seconds);
+}
 
 // ---- the resident kernel's mailbox, written by the host straight into device memory --------------------------------
 // With a large PCIe BAR the CPU can address device memory.  The host then stores the round's (value, tag) pairs into the
@@ -929,6 +949,16 @@ static AcqParams make_params(pcabo_ctx* ctx, double best_f, int maximize, int ac
   return p;
 }
 
+// The outcome of waiting for an acquisition launch's flags
+static int acq_published(pcabo_ctx* ctx, FlagWait w) {
+  if (w == FLAGS_UNPUBLISHED) {
+    HIPCHK(hipGetLastError());
+    return set_err(ctx, PCABO_ERR_TIMEOUT, "acquisition kernel finished without publishing its results%s", "");
+  }
+  if (w == FLAGS_LATE) return set_err(ctx, PCABO_ERR_TIMEOUT, "device did not publish acquisition results%s", "");
+  return PCABO_OK;
+}
+
 // One evaluation of the acquisition at the nq points staged in ctx->hXq (pinned): a single fused launch
 // whose results land in ctx->hVal / ctx->hGrad; the host spins on the sequence flag.
 static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = true) {
@@ -966,22 +996,7 @@ static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = t
     HIPCHK(hipGetLastError());
     return PCABO_OK;
   }
-  const auto t0 = std::chrono::steady_clock::now();
-  unsigned long spins = 0;
-  for (int qi = 0; qi < nq; ++qi) {
-    while (__atomic_load_n(&ctx->hm->qflag[qi], __ATOMIC_ACQUIRE) != seq) {
-      if ((++spins & 0xFFFF) == 0) {
-        if (hipStreamQuery(s) == hipSuccess) {              // kernel done: the flag must be there
-          if (__atomic_load_n(&ctx->hm->qflag[qi], __ATOMIC_ACQUIRE) == seq) break;
-          HIPCHK(hipGetLastError());
-          return set_err(ctx, PCABO_ERR_TIMEOUT, "acquisition kernel finished without publishing its results%s", "");
-        }
-        double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (el > 20.0) return set_err(ctx, PCABO_ERR_TIMEOUT, "device did not publish acquisition results%s", "");
-      }
-    }
-  }
-  return PCABO_OK;
+  return acq_published(ctx, wait_flags(ctx->hm, 0, nq, seq, deadline_in(20), &s));
 }
 
 // The same for restart groups through the throughput kernel (PCABO_OPT_GROUP_ACQ): group g = the gn[g] <= 5 points staged
@@ -1002,23 +1017,10 @@ static int eval_staged_groups(pcabo_ctx* ctx, const int* g0, const int* gn, int 
       return set_err(ctx, PCABO_ERR_HIP, "the restart-group acquisition kernel could not be launched%s", "");
   }
   HIPCHK(hipGetLastError());
-  const auto t0 = std::chrono::steady_clock::now();
-  unsigned long spins = 0;
-  for (int g = 0; g < ng; ++g)
-    for (int j = 0; j < gn[g]; ++j) {
-      while (__atomic_load_n(&ctx->hm->qflag[g0[g] + j], __ATOMIC_ACQUIRE) != seq) {
-        if ((++spins & 0xFFFF) == 0) {
-          if (hipStreamQuery(s) == hipSuccess) {
-            if (__atomic_load_n(&ctx->hm->qflag[g0[g] + j], __ATOMIC_ACQUIRE) == seq) break;
-            HIPCHK(hipGetLastError());
-            return set_err(ctx, PCABO_ERR_TIMEOUT, "acquisition kernel finished without publishing its results%s", "");
-          }
-          if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 20.0)
-            return set_err(ctx, PCABO_ERR_TIMEOUT, "device did not publish acquisition results%s", "");
-        }
-      }
-    }
-  return PCABO_OK;
+  const auto deadline = deadline_in(20);
+  FlagWait w = FLAGS_SET;
+  for (int g = 0; g < ng && w == FLAGS_SET; ++g) w = wait_flags(ctx->hm, g0[g], gn[g], seq, deadline, &s);
+  return acq_published(ctx, w);
 }
 static bool group_mode(const pcabo_ctx* ctx, int q, int want_grad) {
   return ctx->opt_group_acq && want_grad && q <= PCABO_INLAUNCH_MAXQ && acq_group_possible(ctx->NP, ctx->k);
@@ -1110,16 +1112,8 @@ static void server_post(pcabo_ctx* ctx, int cap, int nq, int k, unsigned long lo
   _mm_sfence();                                                // flush the write-combining buffers now
 }
 static int server_wait(pcabo_ctx* ctx, int nq, unsigned long long tag) {
-  const auto t0 = std::chrono::steady_clock::now();
-  unsigned long spins = 0;
-  for (int qi = 0; qi < nq; ++qi) {
-    while (__atomic_load_n(&ctx->hm->qflag[qi], __ATOMIC_ACQUIRE) != tag) {
-      if ((++spins & 0xFFFF) == 0) {
-        double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (el > 3.0) return set_err(ctx, PCABO_ERR_TIMEOUT, "resident acquisition kernel did not answer%s", "");
-      }
-    }
-  }
+  if (wait_flags(ctx->hm, 0, nq, tag, deadline_in(3)) != FLAGS_SET)
+    return set_err(ctx, PCABO_ERR_TIMEOUT, "resident acquisition kernel did not answer%s", "");
   return PCABO_OK;
 }
 
@@ -1137,10 +1131,10 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
   if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: call pcabo_gp_condition first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
   const int k = ctx->k;
-  const int ngroups = (num_restarts + batch_limit - 1) / batch_limit;
-  std::vector<RestartGroup> grp(ngroups);
-  for (int gi = 0; gi < ngroups; ++gi)
-    grp[gi].init(ics, bounds, gi * batch_limit, std::min(batch_limit, num_restarts - gi * batch_limit), k, maxiter);
+  RunRestarts run;
+  run.init(ics, bounds, num_restarts, batch_limit, k, maxiter);
+  std::vector<RestartGroup>& grp = run.grp;
+  const int ngroups = (int)grp.size();
   AcqParams p = make_params(ctx, best_f, maximize, acq, 1);
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   // advance one group until it needs f, g at its x (or stops); a group the free-running mode below left waiting for its
@@ -1304,16 +1298,9 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
   // botorch evaluates the acquisition once more at the clamped end points.  An L-BFGS-B run normally ends ON the last point
   // it had evaluated (the accepted trial of its last line search), whose per-restart values are still here - the same
   // kernel arithmetic, so the same bits; only a run that ended elsewhere (abnormal line search) needs the launch.
-  int any_failed = 0;
-  bool reuse = true;
-  for (int gi = 0; gi < ngroups; ++gi) {
-    grp[gi].end_point(cand);
-    reuse = reuse && grp[gi].ends_on_cache(cand);
-    if (grp[gi].report(info, gi)) any_failed = 1;
-  }
-  if (reuse) {
-    for (const RestartGroup& rg : grp) std::copy(rg.vc.begin(), rg.vc.end(), vals + rg.q0);
-  } else {
+  const bool redo = run.end_points(cand, vals) > 0;
+  const bool any_failed = run.report(info, 0);
+  if (redo) {
     AcqParams pv = make_params(ctx, best_f, maximize, acq, 0);
     // (through the slab kernels whatever the number of restarts: the values of a restart must not depend on how many
     // restarts share the call)
@@ -1340,18 +1327,12 @@ int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x) {
   launch_inverse_map(s, ctx->hXq, ctx->dComps, ctx->dDataMean, ctx->dPcaMean, ctx->k, ctx->d, ctx->dXout, nullptr, ZB(),
                      hx, ctx->hm, seq);
   HIPCHK(hipGetLastError());
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned long spins = 1; __atomic_load_n(&ctx->hm->qflag[0], __ATOMIC_ACQUIRE) != seq; ++spins) {
-    if ((spins & 0xFFFF) == 0) {
-      if (hipStreamQuery(s) == hipSuccess) {
-        if (__atomic_load_n(&ctx->hm->qflag[0], __ATOMIC_ACQUIRE) == seq) break;
-        HIPCHK(hipGetLastError());
-        return set_err(ctx, PCABO_ERR_TIMEOUT, "inverse-map kernel finished without publishing its result%s", "");
-      }
-      if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 20.0)
-        return set_err(ctx, PCABO_ERR_TIMEOUT, "device did not publish the inverse map%s", "");
-    }
+  const FlagWait w = wait_flags(ctx->hm, 0, 1, seq, deadline_in(20), &s);
+  if (w == FLAGS_UNPUBLISHED) {
+    HIPCHK(hipGetLastError());
+    return set_err(ctx, PCABO_ERR_TIMEOUT, "inverse-map kernel finished without publishing its result%s", "");
   }
+  if (w == FLAGS_LATE) return set_err(ctx, PCABO_ERR_TIMEOUT, "device did not publish the inverse map%s", "");
   memcpy(x, hx, (size_t)ctx->d * sizeof(double));
   return PCABO_OK;
 }
@@ -1975,6 +1956,11 @@ int pcabo_batch_gp_condition_end_eval_end(pcabo_batch* batch, const double* Xq, 
   return batch_score_impl(batch, Xq, q, best_f, maximize, acq, val, status, 2);
 }
 
+// a run's status at the start of an optimise call: parked by the caller, without a GP, or taking part
+static int batch_run_status(const pcabo_batch* batch, int b) {
+  return !batch->active[b] ? PCABO_ERR_ARG : !batch->ctx[b]->have_gp ? PCABO_ERR_NOT_PD : PCABO_OK;
+}
+
 // pcabo_batch_optimize_acqf with PCABO_OPT_DEVICE_LBFGSB: every restart group's L-BFGS-B inside one launch of k_lbfgsb_group
 // (value 1), or the host's L-BFGS-B over the same kernel's evaluation-only mode, one launch per round (value 2: the twin the
 // device stepping is compared with).  Returns PCABO_OK / an error, or 1 when the call is not eligible (the caller then takes
@@ -2010,14 +1996,6 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
     pcabo_ctx* c = batch->ctx[b];
     if (c->rt_stale) { launch_rt_build(s, c->dR, c->n, c->NP, c->ld, c->dGram); c->rt_stale = false; }
   }
-  auto fill_status = [&](const std::vector<int>& run_status) {
-    for (int b = 0; b < B; ++b) {
-      const pcabo_ctx* c = batch->ctx[b];
-      int st = run_status[b];
-      if (!batch->active[b]) st = PCABO_ERR_ARG; else if (!c->have_gp) st = PCABO_ERR_NOT_PD;
-      if (status) status[b] = st;
-    }
-  };
   const size_t xq_doubles = (size_t)(num_restarts + 2) * kmax;
   const double inv_ls = 1.0 / batch->lengthscale;
   // PCABO_OPT_LBFGSB_CUS: the optimiser's work-groups take a whole CU each for milliseconds; confined to a part of the chip they
@@ -2064,16 +2042,17 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
     BHIPCHK(hipGetLastError());
     return PCABO_OK;
   };
-  std::vector<int> run_status(B, PCABO_OK);
   if (batch->dev_lbfgsb == 1) {
+    std::vector<int> run_status(B);
+    for (int b = 0; b < B; ++b) run_status[b] = batch_run_status(batch, b);
     // ---- everything on the device
     int nent = 0;
     if (phase != 2) {
     for (size_t blk = 0; blk < act.size(); blk += 8)          // both groups of a run on one XCD (work-groups go round the 8 XCDs)
       for (int gi = 0; gi < ngroups; ++gi)
         for (size_t r = blk; r < std::min(act.size(), blk + 8); ++r) {
-          const int q0 = gi * batch_limit, nq = std::min(batch_limit, num_restarts - q0);
-          batch->hOptTab[nent++] = ((unsigned)act[r] << 16) | ((unsigned)q0 << 8) | (unsigned)nq;
+          const int q0 = gi * batch_limit;
+          batch->hOptTab[nent++] = group_entry(act[r], q0, std::min(batch_limit, num_restarts - q0));
         }
     for (int b : act) {
       pcabo_ctx* c = batch->ctx[b];
@@ -2104,86 +2083,51 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
       memcpy(vals + (size_t)b * num_restarts, c->hVal, (size_t)num_restarts * sizeof(double));
       if (failed) failed[b] = any_failed;
     }
-    for (int b = 0; b < B; ++b) if (failed && (!batch->active[b] || !batch->ctx[b]->have_gp)) failed[b] = 0;
-    fill_status(run_status);
+    for (int b = 0; b < B; ++b) {
+      if (failed && batch_run_status(batch, b) != PCABO_OK) failed[b] = 0;
+      if (status) status[b] = run_status[b];
+    }
     return PCABO_OK;
   }
   if (phase != 0) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin / _end need PCABO_OPT_DEVICE_LBFGSB = 1%s", "");
   // ---- the twin: host L-BFGS-B (csrc/lbfgsb.cpp), evaluations through mode 0 of the same kernel, one launch per round
-  std::vector<std::vector<RestartGroup>> groups(B);
+  std::vector<RunRestarts> runs(B);
+  for (int b = 0; b < B; ++b) runs[b].status = batch_run_status(batch, b);
   for (int b : act) {
-    groups[b].resize(ngroups);
-    for (int gi = 0; gi < ngroups; ++gi) {
-      const int q0 = gi * batch_limit, nq = std::min(batch_limit, num_restarts - q0);
-      // (the device steps in the 64-lane tree order of lbfgsb.cpp: so does its twin)
-      groups[b][gi].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, q0, nq, batch->ctx[b]->k, maxiter, 1);
-    }
+    pcabo_ctx* c = batch->ctx[b];
+    // (the device steps in the 64-lane tree order of lbfgsb.cpp: so does its twin)
+    runs[b].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, num_restarts, batch_limit, c->k, maxiter, 1);
+    runs[b].bind(c->hXq, c->hVal, c->hGrad);
   }
-  struct Pending { int b, gi; };
-  std::vector<Pending> pend;
-  for (;;) {
-    pend.clear();
-    int nent = 0;
-    for (int b : act) {
-      if (run_status[b] != PCABO_OK) continue;
-      pcabo_ctx* c = batch->ctx[b];
-      for (int gi = 0; gi < ngroups; ++gi) {
-        RestartGroup& rg = groups[b][gi];
-        if (!rg.active) continue;
-        rg.advance();
-        if (!rg.active) continue;
-        memcpy(c->hXq + (size_t)rg.q0 * c->k, rg.x.data(), (size_t)rg.nq * c->k * sizeof(double));
-        batch->hOptTab[nent++] = ((unsigned)b << 16) | ((unsigned)rg.q0 << 8) | (unsigned)rg.nq;
-        pend.push_back({b, gi});
-      }
-    }
-    if (nent == 0) break;
-    const int rc = launch(nent, 0);
+  int nent = 0;
+  auto stage = [&](int b, const RestartGroup& rg) { batch->hOptTab[nent++] = group_entry(b, rg.q0, rg.nq); };
+  auto eval = [&] { const int n = nent; nent = 0; return launch(n, 0); };
+  int rc = run_rounds(runs.data(), act, stage, eval);
+  for (int b : act) if (runs[b].status == PCABO_ERR_NAN) set_err(batch->ctx[b], PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
+  if (rc != PCABO_OK) return rc;
+  // end points: the groups that did not end on their last evaluated point are evaluated there (mode 0 again)
+  std::vector<std::pair<int, const RestartGroup*>> redo;
+  for (int b : act) {
+    if (runs[b].status != PCABO_OK) continue;
+    const int k = batch->ctx[b]->k;
+    double* cb = cand + (size_t)b * num_restarts * MD;
+    runs[b].end_points(cb, vals + (size_t)b * num_restarts, [&](const RestartGroup& rg) {
+      memcpy(runs[b].xq + (size_t)rg.q0 * k, cb + (size_t)rg.q0 * k, (size_t)rg.nq * k * sizeof(double));
+      stage(b, rg);
+      redo.push_back({b, &rg});
+    });
+  }
+  if (nent > 0) {
+    rc = eval();
     if (rc != PCABO_OK) return rc;
-    for (const Pending& pe : pend) {
-      pcabo_ctx* c = batch->ctx[pe.b];
-      RestartGroup& rg = groups[pe.b][pe.gi];
-      if (!rg.absorb(c->hVal, c->hGrad, rg.q0)) {
-        run_status[pe.b] = PCABO_ERR_NAN;
-        set_err(c, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
-      }
-    }
-  }
-  {
-    int nent = 0;
-    std::vector<Pending> redo;
-    for (int b : act) {
-      if (run_status[b] != PCABO_OK) continue;
-      pcabo_ctx* c = batch->ctx[b];
-      const int k = c->k;
-      double* cb = cand + (size_t)b * num_restarts * MD;
-      for (int gi = 0; gi < ngroups; ++gi) {
-        const RestartGroup& rg = groups[b][gi];
-        rg.end_point(cb);
-        if (rg.ends_on_cache(cb)) std::copy(rg.vc.begin(), rg.vc.end(), vals + (size_t)b * num_restarts + rg.q0);
-        else {
-          memcpy(c->hXq + (size_t)rg.q0 * k, cb + (size_t)rg.q0 * k, (size_t)rg.nq * k * sizeof(double));
-          batch->hOptTab[nent++] = ((unsigned)b << 16) | ((unsigned)rg.q0 << 8) | (unsigned)rg.nq;
-          redo.push_back({b, gi});
-        }
-      }
-    }
-    if (nent > 0) {
-      const int rc = launch(nent, 0);
-      if (rc != PCABO_OK) return rc;
-      for (const Pending& pe : redo) {
-        const RestartGroup& rg = groups[pe.b][pe.gi];
-        for (int j = 0; j < rg.nq; ++j) vals[(size_t)pe.b * num_restarts + rg.q0 + j] = batch->ctx[pe.b]->hVal[rg.q0 + j];
-      }
-    }
+    for (const auto& [b, rg] : redo)
+      std::copy(runs[b].val + rg->q0, runs[b].val + rg->q0 + rg->nq, vals + (size_t)b * num_restarts + rg->q0);
   }
   for (int b = 0; b < B; ++b) {
-    int any_failed = 0;
-    for (int gi = 0; gi < (int)groups[b].size(); ++gi)
-      if (groups[b][gi].report(info, (size_t)b * ngroups + gi)) any_failed = 1;
+    const bool any_failed = runs[b].report(info, (size_t)b * ngroups);
     if (failed) failed[b] = any_failed;
+    if (status) status[b] = runs[b].status;
   }
-  fill_status(run_status);
   return PCABO_OK;
 }
 
@@ -2210,17 +2154,13 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
   AcqParams pg = make_params(c0, 0.0, maximize, acq, 1);
   pg.inv_ls = 1.0 / batch->lengthscale; pg.kernel = batch->kernel;
   AcqParams pv = pg; pv.want_grad = 0;
-  std::vector<std::vector<RestartGroup>> groups(B);
-  std::vector<int> run_status(B, PCABO_OK);
+  std::vector<RunRestarts> runs(B);
   for (int b = 0; b < B; ++b) {
-    const pcabo_ctx* c = batch->ctx[b];
-    if (!batch->active[b]) { groups[b].clear(); run_status[b] = PCABO_ERR_ARG; continue; }      // parked by the caller
-    groups[b].resize(c->have_gp ? ngroups : 0);
-    if (!c->have_gp) { run_status[b] = PCABO_ERR_NOT_PD; continue; }
-    for (int gi = 0; gi < ngroups; ++gi) {
-      const int q0 = gi * batch_limit, nq = std::min(batch_limit, num_restarts - q0);
-      groups[b][gi].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, q0, nq, c->k, maxiter);
-    }
+    pcabo_ctx* c = batch->ctx[b];
+    runs[b].status = batch_run_status(batch, b);
+    if (runs[b].status != PCABO_OK) continue;
+    runs[b].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, num_restarts, batch_limit, c->k, maxiter);
+    runs[b].bind(c->hXq, c->hVal, c->hGrad);
   }
   std::atomic<int> hip_failed{0};
   const int table_cap = PCABO_QA_MAX * 2;          // 32-bit entries in the QueryArgs slot
@@ -2231,114 +2171,58 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
   auto gang = [&](int g) {
     if (hipSetDevice(batch->device) != hipSuccess) { hip_failed.store(1); return; }
     std::vector<int> mine;
-    for (int b = g; b < B; b += G) if (run_status[b] == PCABO_OK) mine.push_back(b);
-    struct Pending { int b, gi; };
+    for (int b = g; b < B; b += G) mine.push_back(b);
     const bool use_group = batch->group_acq && batch_limit <= PCABO_GROUP_Q && acq_group_possible(batch->NP, kmax);
     hipStream_t st = batch->gstream[g];
-    QueryArgs tab;                                   // the round's launch table (travels in the kernel arguments)
+    QueryArgs tab;                                   // the launch table (travels in the kernel arguments)
     unsigned* ent = reinterpret_cast<unsigned*>(tab.x);
-    std::vector<Pending> pend;
-    auto flags_ready = [&](int nent, unsigned long long seq) -> bool {
-      for (int e = 0; e < nent; ++e) {
-        const pcabo_ctx* c = batch->ctx[ent[e] >> 16];
-        if (use_group) {
-          const int q0 = (int)((ent[e] >> 8) & 0xffu), nqe = (int)(ent[e] & 0xffu);
-          for (int j = 0; j < nqe; ++j) if (__atomic_load_n(&c->hm->qflag[q0 + j], __ATOMIC_ACQUIRE) != seq) return false;
-        } else if (__atomic_load_n(&c->hm->qflag[ent[e] & 0xffffu], __ATOMIC_ACQUIRE) != seq) return false;
-      }
-      return true;
-    };
-    for (;;) {
-      // step every active restart group of the gang to its next evaluation point
-      pend.clear();
-      int nent = 0;
-      for (int b : mine) {
-        if (run_status[b] != PCABO_OK) continue;
-        pcabo_ctx* c = batch->ctx[b];
-        for (int gi = 0; gi < ngroups; ++gi) {
-          RestartGroup& rg = groups[b][gi];
-          if (!rg.active) continue;
-          rg.advance();
-          if (!rg.active) continue;
-          memcpy(c->hXq + (size_t)rg.q0 * c->k, rg.x.data(), (size_t)rg.nq * c->k * sizeof(double));
-          if (use_group) ent[nent++] = ((unsigned)b << 16) | ((unsigned)rg.q0 << 8) | (unsigned)rg.nq;
-          else for (int j = 0; j < rg.nq; ++j) ent[nent++] = ((unsigned)b << 16) | (unsigned)(rg.q0 + j);
-          pend.push_back({b, gi});
-        }
-      }
-      if (nent == 0) break;
+    int nent = 0;
+    // one launch of the table's entries (restart groups, or single queries) and the wait for their flags; empties the table
+    auto launch = [&](const AcqParams& p, bool groups) -> bool {
       const unsigned long long seq = batch->seq.fetch_add(1) + 1;
-      if (use_group) {
-        if (launch_acq_group(st, &tab, nent, c0->hXq, batch->n, kmax, batch->NP, c0->ld, c0->dZnT, c0->dR, c0->dAlpha,
-                             c0->dBounds4, c0->dYstats, pg, c0->dPartial, c0->dCounters + PCABO_GROUP_CNT_OFFSET, c0->dVal,
-                             c0->dGrad, c0->hVal, c0->hGrad, c0->hm, seq, batch_ab(batch, 1, 1)) != 0) {
-          hip_failed.store(1); return;                       // nothing was launched: no flags to wait for
-        }
+      const int n = nent;
+      nent = 0;
+      if (groups) {
+        if (launch_acq_group(st, &tab, n, c0->hXq, batch->n, kmax, batch->NP, c0->ld, c0->dZnT, c0->dR, c0->dAlpha,
+                             c0->dBounds4, c0->dYstats, p, c0->dPartial, c0->dCounters + PCABO_GROUP_CNT_OFFSET, c0->dVal,
+                             c0->dGrad, c0->hVal, c0->hGrad, c0->hm, seq, batch_ab(batch, 1, 1)) != 0)
+          return false;                              // nothing was launched: no flags to wait for
       } else {
         launch_acq(st, &tab, c0->hXq, PCABO_INLAUNCH_MAXQ, batch->n, kmax, batch->NP, c0->ld, c0->dZnT, c0->dR,
-                   c0->dAlpha, c0->dBounds4, c0->dYstats, pg, c0->dPartial, c0->dCounters, c0->dVal, c0->dGrad, c0->hVal,
-                   c0->hGrad, c0->hm, seq, nullptr, nullptr, batch_ab(batch, 1, 1), B, nent);
+                   c0->dAlpha, c0->dBounds4, c0->dYstats, p, c0->dPartial, c0->dCounters, c0->dVal, c0->dGrad, c0->hVal,
+                   c0->hGrad, c0->hm, seq, nullptr, nullptr, batch_ab(batch, 1, 1), B, n);
       }
-      if (hipGetLastError() != hipSuccess) { hip_failed.store(1); return; }
-      const auto t0 = std::chrono::steady_clock::now();
-      for (unsigned long spins = 1; !flags_ready(nent, seq); ++spins) {
-        if ((spins & 0xFFFF) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 20.0) {
-          hip_failed.store(1); return;                       // the launch did not publish its results
-        }
-      }
-      for (const Pending& pe : pend) {
-        pcabo_ctx* c = batch->ctx[pe.b];
-        RestartGroup& rg = groups[pe.b][pe.gi];
-        if (!rg.absorb(c->hVal, c->hGrad, rg.q0)) {
-          run_status[pe.b] = PCABO_ERR_NAN;
-          set_err(c, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
-        }
-      }
-    }
-    auto launch_and_wait = [&](int nent, const AcqParams& p, unsigned long long seq) -> bool {
-      launch_acq(st, &tab, c0->hXq, PCABO_INLAUNCH_MAXQ, batch->n, kmax, batch->NP, c0->ld, c0->dZnT, c0->dR, c0->dAlpha,
-                 c0->dBounds4, c0->dYstats, p, c0->dPartial, c0->dCounters, c0->dVal, c0->dGrad, c0->hVal, c0->hGrad, c0->hm,
-                 seq, nullptr, nullptr, batch_ab(batch, 1, 1), B, nent);
       if (hipGetLastError() != hipSuccess) return false;
-      const auto t0 = std::chrono::steady_clock::now();
-      unsigned long spins = 0;
-      for (int e = 0; e < nent; ++e) {
-        const pcabo_ctx* c = batch->ctx[ent[e] >> 16];
-        const int q = (int)(ent[e] & 0xffffu);
-        while (__atomic_load_n(&c->hm->qflag[q], __ATOMIC_ACQUIRE) != seq) {
-          if ((++spins & 0xFFFF) == 0 &&
-              std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 20.0) return false;
-        }
+      const auto deadline = deadline_in(20);
+      for (int e = 0; e < n; ++e) {
+        const unsigned u = ent[e];
+        const int q0 = groups ? (int)((u >> 8) & 0xffu) : (int)(u & 0xffffu), nq = groups ? (int)(u & 0xffu) : 1;
+        if (wait_flags(batch->ctx[u >> 16]->hm, q0, nq, seq, deadline) != FLAGS_SET) return false;
       }
       return true;
     };
+    auto stage = [&](int b, const RestartGroup& rg) {
+      if (use_group) ent[nent++] = group_entry(b, rg.q0, rg.nq);
+      else for (int j = 0; j < rg.nq; ++j) ent[nent++] = query_entry(b, rg.q0 + j);
+    };
+    const int rc = run_rounds(runs.data(), mine, stage, [&] { return launch(pg, use_group) ? PCABO_OK : PCABO_ERR_HIP; });
+    for (int b : mine) if (runs[b].status == PCABO_ERR_NAN) set_err(batch->ctx[b], PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
+    if (rc != PCABO_OK) { hip_failed.store(1); return; }
     // end points, values there (botorch evaluates once more at the clamped end points; normally that is the last point
     // the run evaluated - same kernel arithmetic, same bits - otherwise one value-only launch for the gang's leftovers)
-    int nent = 0;
     std::vector<int> redo;
     for (int b : mine) {
-      if (run_status[b] != PCABO_OK) continue;
-      pcabo_ctx* c = batch->ctx[b];
-      const int k = c->k;
+      RunRestarts& run = runs[b];
+      if (run.status != PCABO_OK) continue;
       double* cb = cand + (size_t)b * num_restarts * MD;
-      bool reuse = true;
-      for (const RestartGroup& rg : groups[b]) {
-        rg.end_point(cb);
-        reuse = reuse && rg.ends_on_cache(cb);
-      }
-      if (reuse) {
-        for (const RestartGroup& rg : groups[b]) std::copy(rg.vc.begin(), rg.vc.end(), vals + (size_t)b * num_restarts + rg.q0);
-      } else {
-        memcpy(c->hXq, cb, (size_t)num_restarts * k * sizeof(double));
-        for (int j = 0; j < num_restarts; ++j) ent[nent++] = ((unsigned)b << 16) | (unsigned)j;
-        redo.push_back(b);
-      }
+      if (run.end_points(cb, vals + (size_t)b * num_restarts) == 0) continue;
+      memcpy(run.xq, cb, (size_t)num_restarts * batch->ctx[b]->k * sizeof(double));
+      for (int j = 0; j < num_restarts; ++j) ent[nent++] = query_entry(b, j);
+      redo.push_back(b);
     }
     if (nent > 0) {
-      const unsigned long long seq = batch->seq.fetch_add(1) + 1;
-      if (!launch_and_wait(nent, pv, seq)) { hip_failed.store(1); return; }
-      for (int b : redo)
-        for (int j = 0; j < num_restarts; ++j) vals[(size_t)b * num_restarts + j] = batch->ctx[b]->hVal[j];
+      if (!launch(pv, false)) { hip_failed.store(1); return; }
+      for (int b : redo) std::copy(runs[b].val, runs[b].val + num_restarts, vals + (size_t)b * num_restarts);
     }
   };
   batch->pool.run(gang);
@@ -2348,11 +2232,9 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
     return bset_err(batch, PCABO_ERR_HIP, "an acquisition launch of the batch failed or did not answer%s", "");
   }
   for (int b = 0; b < B; ++b) {
-    int any_failed = 0;
-    for (int gi = 0; gi < (int)groups[b].size(); ++gi)
-      if (groups[b][gi].report(info, (size_t)b * ngroups + gi)) any_failed = 1;
+    const bool any_failed = runs[b].report(info, (size_t)b * ngroups);
     if (failed) failed[b] = any_failed;
-    if (status) status[b] = run_status[b];
+    if (status) status[b] = runs[b].status;
   }
   return PCABO_OK;
 }
