@@ -358,9 +358,10 @@ __device__ inline bool acq_server_finisher(const MailPair* rec, int S, int k, in
       if (__any(wall_clock64() - t0 > PCABO_SERVER_TIMEOUT_TICKS)) { if (l == 0) *s_srv = 1; break; }
       __builtin_amdgcn_s_sleep(1);
     }
-    double vv = l < S ? pair_value(o[0]) : 0.0, mus = l < S ? pair_value(o[1]) : 0.0;
-    vv = wave_sum(vv);
-    mus = wave_sum(mus);
+    double vm[2] = {l < S ? pair_value(o[0]) : 0.0, l < S ? pair_value(o[1]) : 0.0};
+    wave_sum_multi<2>(vm, l);
+    constexpr int lane_vv = wave_multi_lane(2, 0), lane_mus = wave_multi_lane(2, 1);
+    const double vv = read_lane(vm[0], lane_vv), mus = read_lane(vm[0], lane_mus);
     acq_scalar_core(vv, mus, q, ym, ysd, prm, val, host_val, s_coef, l);
   } else if (prm.want_grad) {
     const int first = w - 1;
@@ -458,6 +459,25 @@ __device__ __noinline__ void acq_server_finish_main(double* s_mem, MailPair* dev
 // number of slab groups per query that launch_acq uses for this size
 #define ACQ_SLAB32_NP 448          // 16 rows per work-group below this padded size, 32 from it on (see launch_acq)
 int acq_slabs(int NP) { return NP / (NP >= ACQ_SLAB32_NP ? 32 : 16); }
+
+// Gradient pairs of k_acq_fast: the wave sums of gs[u], gm[u] for its first NU components (those >= k are not
+// published), one lane per sum.  pout != nullptr: resident mode, (value, tag) pairs; otherwise write-through partials.
+template <int NU, int CU>
+__device__ inline void publish_grad(const double (&gs)[CU], const double (&gm)[CU], int w, int k, int l, MailPair* pout,
+                                    double* out, unsigned long long seq) {
+  static_assert(NU <= CU, "components per wave");
+  double v[2 * NU];
+#pragma unroll
+  for (int u = 0; u < NU; ++u) { v[2 * u] = gs[u]; v[2 * u + 1] = gm[u]; }
+  wave_sum_multi<2 * NU>(v, l);
+  const int i = wave_multi_owner<2 * NU>(l);
+  const int c = w + 4 * (i >> 1);
+  if (i >= 0 && c < k) {
+    const int off = 2 + (i & 1) * PCABO_MAXD + c;
+    if (pout) st_pair_sys(pout + off, make_pair(v[0], seq));
+    else st_wt(out + off, v[0]);
+  }
+}
 
 // ---- fast path: NP = 64 NB <= 512 and k <= 40, everything static ---------------------------------------------
 // The generic kernel above re-reads its operands (ZnT for ks and again for the gradient contraction, the R slab
@@ -643,12 +663,9 @@ __global__ __launch_bounds__(256) void k_acq_fast(
 #pragma unroll
       for (int u = 0; u < RW; ++u) acc[u] += r[u][b] * kj;
     }
-#pragma unroll
-    for (int u = 0; u < RW; ++u) acc[u] = wave_sum(acc[u]);
-    if (l == 0) {
-#pragma unroll
-      for (int u = 0; u < RW; ++u) s_v[w + 4 * u] = acc[u];
-    }
+    wave_sum_multi<RW>(acc, l);           // the RW row sums land in RW different lanes: one LDS store
+    const int u = wave_multi_owner<RW>(l);
+    if (u >= 0) s_v[w + 4 * u] = acc[0];
   }
   __syncthreads();
   STAMP(3);
@@ -661,11 +678,12 @@ __global__ __launch_bounds__(256) void k_acq_fast(
       vv = vi * vi;
       if (i < n) mu = alpha[i] * s_ks[i];
     }
-    vv = wave_sum(vv);
-    mu = wave_sum(mu);
-    if (l == 0) {
-      if (server) { st_pair_sys(pout + 0, make_pair(vv, cur_seq)); st_pair_sys(pout + 1, make_pair(mu, cur_seq)); }
-      else { st_wt(out + 0, vv); st_wt(out + 1, mu); }
+    double vm[2] = {vv, mu};
+    wave_sum_multi<2>(vm, l);
+    const int i = wave_multi_owner<2>(l);   // lane 0: |v|^2, lane 1: mu_s
+    if (i >= 0) {
+      if (server) st_pair_sys(pout + i, make_pair(vm[0], cur_seq));
+      else st_wt(out + i, vm[0]);
     }
   }
   if (want_grad) {
@@ -712,17 +730,11 @@ __global__ __launch_bounds__(256) void k_acq_fast(
         gm[u] += tm * dlt;
       }
     }
-#pragma unroll
-    for (int u = 0; u < CU; ++u) {
-      const int c = w + 4 * u;
-      if (c < k) {                          // wave-uniform
-        const double a = wave_sum(gs[u]), b2 = wave_sum(gm[u]);
-        if (l == 0) {
-          if (server) { st_pair_sys(pout + 2 + c, make_pair(a, cur_seq)); st_pair_sys(pout + 2 + PCABO_MAXD + c, make_pair(b2, cur_seq)); }
-          else { st_wt(out + 2 + c, a); st_wt(out + 2 + PCABO_MAXD + c, b2); }
-        }
-      }
-    }
+    // the wave's components c = w + 4u < k: nu of them (wave-uniform); their 2 nu sums in one multi-value reduction
+    const int nu = k > w ? (k - w + 3) / 4 : 0;
+    if (nu > 5) publish_grad<10>(gs, gm, w, k, l, pout, out, cur_seq);
+    else if (nu > 2) publish_grad<5>(gs, gm, w, k, l, pout, out, cur_seq);
+    else if (nu > 0) publish_grad<2>(gs, gm, w, k, l, pout, out, cur_seq);
   }
   }  // want_grad
   }   // queries of this group
@@ -1520,4 +1532,49 @@ void launch_acq(hipStream_t st, const QueryArgs* qa, const double* Xq, int q, in
   if (!combine)
     hipLaunchKernelGGL(k_acq_combine, dim3((q + 3) / 4, 1, gz), dim3(256), 0, st, partial, q, S, k, bounds4, ystats, p, val,
                        grad, ab);
+}
+
+// ---- self-test of the multi-value wave reduction (tests/test_gpu_acq_fast_bits.py) ---------------------------------
+// One wave: in[i * 64 + lane] is value i of a lane.  ref[i] = wave_sum(value i); multi[i] = what the owner lane of value i
+// holds after wave_sum_multi<N>; uni[i] = the same sum read back into every lane (lane 0's copy), and mism[i] counts lanes
+// that also hold value i (wave_multi_index) with other bits than the owner.
+template <int N>
+__global__ __launch_bounds__(64) void k_debug_wave_sum_multi(const double* __restrict__ in, double* ref, double* multi,
+                                                             double* uni, int* mism) {
+  const int l = threadIdx.x;
+  double v[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = in[i * 64 + l];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { const double r = wave_sum(v[i]); if (l == 0) ref[i] = r; }
+  wave_sum_multi<N>(v, l);
+  const int own = wave_multi_owner<N>(l), idx = wave_multi_index<N>(l);
+  if (own >= 0) multi[own] = v[0];
+  __syncthreads();
+  if (__double_as_longlong(multi[idx]) != __double_as_longlong(v[0])) atomicAdd(&mism[idx], 1);
+#pragma unroll
+  for (int i = 0; i < N; ++i) { const double r = read_lane(v[0], __builtin_amdgcn_readfirstlane(wave_multi_lane(N, i))); if (l == 0) uni[i] = r; }
+}
+
+// 0, -1: N not instantiated, -3: HIP error.  Host arrays: in [N][64], ref / multi / uni [N], mism [N].
+extern "C" int pcabo_debug_wave_sum_multi(const double* in, int N, double* ref, double* multi, double* uni, int* mism) {
+  double* d = nullptr;
+  if (hipMalloc(&d, (size_t)N * (64 + 3) * sizeof(double) + (size_t)N * sizeof(int)) != hipSuccess) return -3;
+  double *dref = d + N * 64, *dmul = dref + N, *duni = dmul + N;
+  int* dmis = reinterpret_cast<int*>(duni + N);
+  int rc = hipMemcpy(d, in, (size_t)N * 64 * sizeof(double), hipMemcpyHostToDevice) == hipSuccess ? 0 : -3;
+  if (rc == 0 && hipMemset(dref, 0, (size_t)N * 3 * sizeof(double) + (size_t)N * sizeof(int)) != hipSuccess) rc = -3;
+#define DBG_WSM(NV) case NV: hipLaunchKernelGGL(k_debug_wave_sum_multi<NV>, dim3(1), dim3(64), 0, 0, d, dref, dmul, duni, dmis); break;
+  if (rc == 0) {
+    switch (N) { DBG_WSM(1) DBG_WSM(2) DBG_WSM(3) DBG_WSM(4) DBG_WSM(5) DBG_WSM(7) DBG_WSM(8) DBG_WSM(10) DBG_WSM(13)
+                 DBG_WSM(20) DBG_WSM(33) DBG_WSM(64) default: rc = -1; }
+  }
+#undef DBG_WSM
+  if (rc == 0 && hipGetLastError() != hipSuccess) rc = -3;
+  if (rc == 0 && (hipMemcpy(ref, dref, N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+                  hipMemcpy(multi, dmul, N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+                  hipMemcpy(uni, duni, N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+                  hipMemcpy(mism, dmis, N * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) rc = -3;
+  (void)hipFree(d);
+  return rc;
 }

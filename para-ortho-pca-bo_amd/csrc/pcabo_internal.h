@@ -178,6 +178,99 @@ __device__ inline double wave_sum(double v) {         // uniform result: sum ove
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63),
                           __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
+
+// ---- N sums at once, bit for bit those of N wave_sum calls ----------------------------------------------------------
+// wave_sum adds the lanes as a balanced binary tree in lane order: level t adds the sums of lane blocks that differ in
+// lane bit t (f64 addition is commutative, so which of the two lanes holds which operand does not change a bit).  The
+// multi-value form builds the same tree for every value but transposes the work, like a reduce-scatter: at level t the
+// live values of a lane are taken in pairs; lanes with bit t clear keep the first of a pair, lanes with bit t set the
+// second, and each lane adds its partner's (lane ^ 2^t) partial of the value it keeps.  The number of live values halves
+// per level (an odd one out is added symmetrically), so N values cost ~7 N wave instructions instead of ~20 N, and the
+// N sums end up in N different lanes (wave_multi_owner), ready for one store instruction.
+template <int T>
+__device__ inline double lane_xor(double v) {           // v of lane l ^ 2^T, T < 4 (DPP, inside a row of 16)
+  if (T == 0) return dpp_get<0xB1, 0xf>(v);             // quad_perm [1,0,3,2]
+  if (T == 1) return dpp_get<0x4E, 0xf>(v);             // quad_perm [2,3,0,1]
+  if (T == 2) return dpp_get<0x141, 0xf>(dpp_get<0x1B, 0xf>(v));   // quad_perm [3,2,1,0], then row_half_mirror: l ^ 4
+  return dpp_get<0x128, 0xf>(v);                        // row_ror 8: l ^ 8
+}
+// v_permlane16_swap (T = 4) / v_permlane32_swap (T = 5): the lanes with bit T set of a trade places with the lanes with
+// bit T clear of b, so a + b afterwards is a's level-T sum where bit T is clear and b's where it is set.  No select.
+template <int T>
+__device__ inline double swap_add(double a, double b) {
+  unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
+  unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
+  if (T == 4) {
+    const auto lo = __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
+    alo = lo[0]; blo = lo[1]; ahi = hi[0]; bhi = hi[1];
+  } else {
+    const auto lo = __builtin_amdgcn_permlane32_swap(alo, blo, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
+    alo = lo[0]; blo = lo[1]; ahi = hi[0]; bhi = hi[1];
+  }
+  return __hiloint2double((int)ahi, (int)alo) + __hiloint2double((int)bhi, (int)blo);
+}
+template <int T>
+__device__ inline double pair_level(double a, double b, int lane) {   // bit T clear: a's level-T sum; set: b's
+  if (T >= 4) return swap_add<T>(a, b);
+  const bool hi = (lane >> T) & 1;
+  return (hi ? b : a) + lane_xor<T>(hi ? a : b);
+}
+template <int T>
+__device__ inline double single_level(double v) {       // every lane: its level-T sum of v
+  if (T >= 4) return swap_add<T>(v, v);
+  return v + lane_xor<T>(v);
+}
+__host__ __device__ constexpr int wave_multi_live(int n, int t) { return (n + (1 << t) - 1) >> t; }   // values before level t: ceil(n / 2^t)
+template <int T, int N>
+__device__ inline void wave_multi_level(double* v, int lane) {
+  constexpr int M = wave_multi_live(N, T);
+#pragma unroll
+  for (int i = 0; i < M / 2; ++i) v[i] = pair_level<T>(v[2 * i], v[2 * i + 1], lane);
+  if (M & 1) v[M / 2] = single_level<T>(v[M - 1]);
+}
+// v[0 .. N) per lane -> v[0] = the wave sum of value wave_multi_index<N>(lane) (N <= 64; v[1 ..] are left undefined)
+template <int N>
+__device__ inline void wave_sum_multi(double* v, int lane) {
+  static_assert(N >= 1 && N <= 64, "one value per lane at the end");
+  wave_multi_level<0, N>(v, lane); wave_multi_level<1, N>(v, lane); wave_multi_level<2, N>(v, lane);
+  wave_multi_level<3, N>(v, lane); wave_multi_level<4, N>(v, lane); wave_multi_level<5, N>(v, lane);
+}
+// which value's sum this lane holds after wave_sum_multi<N> ...
+template <int N>
+__device__ inline int wave_multi_index(int lane) {
+  int slot = 0;
+#pragma unroll
+  for (int t = 5; t >= 0; --t) {
+    const int m = wave_multi_live(N, t);
+    slot = slot < m / 2 ? 2 * slot + ((lane >> t) & 1) : m - 1;
+  }
+  return slot;
+}
+// ... and whether it is the one lane that publishes it (values added symmetrically at some level sit in several lanes)
+template <int N>
+__device__ inline int wave_multi_owner(int lane) {
+  int slot = 0;
+  bool first = true;
+#pragma unroll
+  for (int t = 5; t >= 0; --t) {
+    const int m = wave_multi_live(N, t);
+    if (slot < m / 2) slot = 2 * slot + ((lane >> t) & 1);
+    else { slot = m - 1; first = first && !((lane >> t) & 1); }
+  }
+  return first ? slot : -1;
+}
+// the lane that owns value i, for a uniform copy through readlane (use it in a constant expression)
+__host__ __device__ constexpr int wave_multi_lane(int n, int i, int t = 0) {
+  return t == 6 ? 0
+       : (i < wave_multi_live(n, t) / 2 * 2 ? ((i & 1) << t) + wave_multi_lane(n, i / 2, t + 1)
+                                            : wave_multi_lane(n, wave_multi_live(n, t) / 2, t + 1));
+}
+__device__ inline double read_lane(double v, int lane) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
+                          __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
 #endif
 
 void launch_rank(hipStream_t s, const double* f, int n, int maximize, long long* ranks);
