@@ -129,9 +129,11 @@ int pcabo_gp_mll(pcabo_ctx* ctx, const double* Z /* NULL: Z of the last wPCA */,
  * = 15000, the published summation order), bound s2 >= 1e-4, one attempt.  On return theta_inout holds the fitted theta, *loss
  * its loss, and the context is conditioned there (acquisition calls follow directly).
  * info[4] = {iterations, evaluations, warnflag (scipy's: 0 converged, 1 limit, 2 abnormal), task (LBFGSB_* code of the
- * optimiser, or PCABO_FIT_TASK_NOT_PD when a trial theta could not be factored even with jitter)}.  A fit that ends abnormally
- * keeps the last accepted iterate (or the start) and still returns PCABO_OK: the caller reads warnflag. */
+ * optimiser, or PCABO_FIT_TASK_NOT_PD when a trial theta could not be factored even with jitter, PCABO_FIT_TASK_DOMAIN when a
+ * trial theta left the model's domain: a step so long that softplus(rho) underflows to 0, a non-finite value)}.  A fit that ends
+ * abnormally keeps the last accepted iterate (or the start) and still returns PCABO_OK: the caller reads warnflag. */
 #define PCABO_FIT_TASK_NOT_PD (-2)
+#define PCABO_FIT_TASK_DOMAIN (-3)
 int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
                  double* theta_inout /*3*/, double* loss, int* info /*4*/);
 
@@ -359,6 +361,22 @@ int pcabo_batch_inverse_map(pcabo_batch* batch, const double* z, double* x);
  * For diagnostics and parity tests: pcabo_batch_optimize_acqf evaluates inside its own launch. */
 int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq,
                                 double* val, double* grad);
+/* The opt-in GP hyperparameter fit (pcabo_gp_mll / pcabo_gp_fit) for the B runs of a batch in lock-step.  Both work on the inputs
+ * of the last pcabo_batch_wpca_gp_condition_begin / pcabo_batch_gp_condition_begin (their Z, y and Normalize bounds are still on
+ * the device; the lengthscale and noise given there are the model of the runs that do not take part).  Every run has its own
+ * theta = {s2, c, rho}; one round is ONE launch sequence for all runs (conditioning + likelihood kernels, one wait), and every
+ * run takes bit for bit the evaluations - and so the fit - it takes alone through pcabo_gp_mll / pcabo_gp_fit on the same Z, y.
+ * theta[B][3], loss[B], grad[B][3] (or NULL), info[B][4] and the status codes as in pcabo_gp_fit; status[B]: PCABO_OK,
+ * PCABO_ERR_ARG for a run parked by pcabo_batch_set_active (it is skipped) or a theta outside the model's domain,
+ * PCABO_ERR_NOT_PD for a run that could not be factored even with the jitter retries (done for that run alone; a trial theta of
+ * a fit that fails so ends that run's fit with warnflag 2 at its last accepted iterate, the other runs go on).  Matern-5/2 only.
+ * On return every run's context is conditioned at its own theta (for pcabo_batch_gp_fit: its result; a run that has finished
+ * rests there while the others step), the batched acquisition launches and the single-context calls on pcabo_batch_ctx(b) use
+ * that model, and pcabo_batch_gp_condition_end_eval* scores it (the wait it would have done is over already).  The next
+ * conditioning call returns the batch to the shared model.  pcabo_batch_gp_fit_rounds: launch sequences of the last call. */
+int pcabo_batch_gp_mll(pcabo_batch* batch, const double* theta /*B*3*/, double* loss /*B*/, double* grad /*B*3*/, int* status /*B*/);
+int pcabo_batch_gp_fit(pcabo_batch* batch, double* theta_inout /*B*3*/, double* loss /*B*/, int* info /*B*4*/, int* status /*B*/);
+int pcabo_batch_gp_fit_rounds(pcabo_batch* batch);
 
 /* ---- BBOB f15-f24 objectives on the device, for runs that advance in lock-step ---------------------------------------
  * The reference evaluates `problem(x)` on the host, one candidate per BO iteration (PCA_BO.py:263; the problems come from

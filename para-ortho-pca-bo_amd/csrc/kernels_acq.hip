@@ -184,6 +184,7 @@ __device__ inline void acq_tail(int combine, double* s_v, double* partial, unsig
     host_val = zrun(host_val, ab.hzs, run_); host_grad = zrun(host_grad, ab.hzs, run_); hm = zrun(hm, ab.hzs, run_); \
     if (ab.k_dev) k = *zrun(ab.k_dev, ab.zs, run_);                                                              \
     if (ab.bestf) prm.best_f = *zrun(ab.bestf, ab.zs, run_);                                                     \
+    if (ab.hyp) prm.inv_ls = zrun(ab.hyp, ab.zs, run_)[PCABO_HYP_INV_LS];                                        \
   }                                                                                                              \
   (void)qsel_;
 
@@ -913,6 +914,7 @@ __global__ __launch_bounds__(256) void k_acq_group(
     host_val = zrun(host_val, ab.hzs, run_); host_grad = zrun(host_grad, ab.hzs, run_); hm = zrun(hm, ab.hzs, run_);
     if (ab.k_dev) k = *zrun(ab.k_dev, ab.zs, run_);
     if (ab.bestf) prm.best_f = *zrun(ab.bestf, ab.zs, run_);
+    if (ab.hyp) prm.inv_ls = zrun(ab.hyp, ab.zs, run_)[PCABO_HYP_INV_LS];
   }
   const int tid = threadIdx.x, l = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1336,6 +1338,7 @@ __global__ __launch_bounds__(256) void k_score_ks(const double* __restrict__ Xq,
     Xq = zrun(Xq, ab.zs, run_); ZnT = zrun(ZnT, ab.zs, run_); alpha = zrun(alpha, ab.zs, run_);
     bounds4 = zrun(bounds4, ab.zs, run_); KS = zrun(KS, ab.zs, run_); partial = zrun(partial, ab.zs, run_);
     if (ab.k_dev) k = *zrun(ab.k_dev, ab.zs, run_);
+    if (ab.hyp) prm.inv_ls = zrun(ab.hyp, ab.zs, run_)[PCABO_HYP_INV_LS];
   }
   __shared__ double s_xn[SC_QB][PCABO_MAXD];
   __shared__ double s_mu[4][SC_QB];

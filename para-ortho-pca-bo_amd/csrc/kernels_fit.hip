@@ -19,9 +19,14 @@
 //   W_ij dK_ij  (i, j < n)   and, on the diagonal tiles, (K^-1)_ii  (i < n)
 // in a fixed order (per thread, then the wave, then the four waves).  Off-diagonal tiles count twice (W and dK are symmetric).
 // partial[2 t], partial[2 t + 1]: tile t's two sums; k_mll_finish adds them in tile order.
+// Batched (pcabo_batch_gp_mll / pcabo_batch_gp_fit): blockIdx.z = run, every operand zs bytes further per run, KP from the run's
+// own k (the runs of a PCA batch differ in k); n and NP are common.  No sum crosses a run, so a run's bits are the single launch's.
 __global__ __launch_bounds__(256) void k_mll_grad(const double* __restrict__ R, const double* __restrict__ AT,
                                                   const double* __restrict__ nrm, const double* __restrict__ alpha, int n,
-                                                  int NP, int KP, int ld, double* __restrict__ partial) {
+                                                  int NP, int KP, int ld, double* __restrict__ partial,
+                                                  const int* __restrict__ k_dev, size_t zs) {
+  ZRUN(R); ZRUN(AT); ZRUN(nrm); ZRUN(alpha); ZRUN(partial); ZRUN(k_dev);
+  if (k_dev) KP = (*k_dev + 3) & ~3;
   __shared__ double s_red[2][4];
   const int t = blockIdx.x;
   int I = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);           // t = I (I + 1) / 2 + J, 0 <= J <= I
@@ -102,7 +107,8 @@ __global__ __launch_bounds__(256) void k_mll_grad(const double* __restrict__ R, 
 __global__ __launch_bounds__(MLL_FIN_THREADS) void k_mll_finish(const double* __restrict__ L, const double* __restrict__ ys,
                                                                const double* __restrict__ alpha, int n, int ld,
                                                                const double* __restrict__ partial, int tiles,
-                                                               double* __restrict__ out) {
+                                                               double* __restrict__ out, size_t zs) {
+  ZRUN(L); ZRUN(ys); ZRUN(alpha); ZRUN(partial); ZRUN(out);
   __shared__ double s_red[6][MLL_FIN_THREADS / 64];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
   double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -129,8 +135,8 @@ __global__ __launch_bounds__(MLL_FIN_THREADS) void k_mll_finish(const double* __
 }
 
 void launch_mll_grad(hipStream_t s, const double* R, const double* AT, const double* nrm, const double* alpha, const double* L,
-                     const double* ys, int n, int NP, int KP, int ld, double* partial, double* out) {
+                     const double* ys, int n, int NP, int KP, int ld, double* partial, double* out, const int* k_dev, ZB zb) {
   const int nb = NP / BS, tiles = nb * (nb + 1) / 2;
-  hipLaunchKernelGGL(k_mll_grad, dim3(tiles), dim3(256), 0, s, R, AT, nrm, alpha, n, NP, KP, ld, partial);
-  hipLaunchKernelGGL(k_mll_finish, dim3(1), dim3(MLL_FIN_THREADS), 0, s, L, ys, alpha, n, ld, partial, tiles, out);
+  hipLaunchKernelGGL(k_mll_grad, dim3(tiles, 1, zb.B), dim3(256), 0, s, R, AT, nrm, alpha, n, NP, KP, ld, partial, k_dev, zb.zs);
+  hipLaunchKernelGGL(k_mll_finish, dim3(1, 1, zb.B), dim3(MLL_FIN_THREADS), 0, s, L, ys, alpha, n, ld, partial, tiles, out, zb.zs);
 }

@@ -24,9 +24,10 @@
 __global__ __launch_bounds__(256) void k_gram(const double* __restrict__ AT, const double* __restrict__ nrm, int n,
                                               int KP, int ld, double noise, int kernel, double* __restrict__ K,
                                               const int* __restrict__ k_dev, double* __restrict__ K2,
-                                              int* __restrict__ info_reset, size_t zs) {
+                                              int* __restrict__ info_reset, size_t zs, const double* __restrict__ hyp) {
   const XcdTile xt_ = xcd_tile();                    // (the tiles of a run read the same rows of AT: one XCD)
-  ZRUNX(AT); ZRUNX(nrm); ZRUNX(K); ZRUNX(k_dev); ZRUNX(K2); ZRUNX(info_reset);
+  ZRUNX(AT); ZRUNX(nrm); ZRUNX(K); ZRUNX(k_dev); ZRUNX(K2); ZRUNX(info_reset); ZRUNX(hyp);
+  if (hyp) noise = hyp[PCABO_HYP_NOISE];
   const int ti = (int)xt_.x, tj = (int)xt_.y;
   // K2: the copy the factorisation works on in place; info_reset: its failure flag (saves a copy and a fill launch).
   // K itself is written only when somebody asks for it (pcabo_get_gram): a second full-size store doubled the kernel's
@@ -402,7 +403,7 @@ void launch_gram(hipStream_t s, const double* AT, const double* nrm, int n, int 
                  int kernel, double* K, const int* k_dev, double* K2, int* info_reset, ZB zb) {
   int nb = NP / BS;
   hipLaunchKernelGGL(k_gram, dim3(nb, nb, zb.B), dim3(256), 0, s, AT, nrm, n, KP, ld, noise, kernel, K, k_dev, K2, info_reset,
-                     zb.zs);
+                     zb.zs, zb.hyp);
 }
 void launch_add_jitter(hipStream_t s, double* K, int n, int ld, double jitter) {
   hipLaunchKernelGGL(k_add_jitter, dim3((n + 255) / 256), dim3(256), 0, s, K, n, ld, jitter);

@@ -1855,7 +1855,7 @@ __global__ __launch_bounds__(LB_THREADS) void k_lbfgsb_group(
     const double* __restrict__ Xq, const double* __restrict__ ZnT, const double* __restrict__ R, const double* __restrict__ RT,
     const double* __restrict__ alpha, const double* __restrict__ bounds4, const double* __restrict__ ystats,
     const double* __restrict__ bestf, const int* __restrict__ k_dev, double inv_ls, int maximize, int acq, int kernel,
-    double* __restrict__ out_x, double* __restrict__ out_v, size_t zs) {
+    double* __restrict__ out_x, double* __restrict__ out_v, size_t zs, const double* __restrict__ hyp) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
   const unsigned ent = table[blockIdx.x];
   const unsigned run_ = ent >> 16;
@@ -1871,7 +1871,7 @@ __global__ __launch_bounds__(LB_THREADS) void k_lbfgsb_group(
   LbEval E;
   E.ZnT = (gcd*)ZnT; E.R = (gcd*)R; E.RT = (gcd*)RT; E.alpha = (gcd*)alpha; E.nlo = (gcd*)bounds4; E.nhi = (gcd*)(bounds4 + PCABO_MAXD);
   E.n = n; E.k = k; E.NP = NP; E.ld = ld; E.S = NP / 64;
-  E.best_f = *bestf; E.ym = ystats[0]; E.ysd = ystats[1]; E.inv_ls = inv_ls; E.maximize = maximize; E.acq = acq; E.kernel = kernel;
+  E.best_f = *bestf; E.ym = ystats[0]; E.ysd = ystats[1]; E.inv_ls = hyp ? zrun(hyp, zs, run_)[PCABO_HYP_INV_LS] : inv_ls; E.maximize = maximize; E.acq = acq; E.kernel = kernel;
   // ---- initial state
   for (int i = tid; i < nv; i += LB_THREADS) {
     const int q = i / k, c = i - q * k;
@@ -2006,7 +2006,7 @@ bool lbfgsb_device_possible(int NP, int kmax, int batch_limit) {
 int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int mode, int num_restarts, int maxiter, int n, int NP,
                         int ld, const double* Xq, const double* ZnT, const double* R, const double* RT, const double* alpha,
                         const double* bounds4, const double* ystats, const double* bestf, const int* k_dev, double inv_ls,
-                        int maximize, int acq, int kernel, double* out_x, double* out_v, size_t zs) {
+                        int maximize, int acq, int kernel, double* out_x, double* out_v, size_t zs, const double* hyp) {
   const size_t lds = lb_lds_doubles(NP) * sizeof(double);
   if (lds > 150 * 1024) return -1;
   if (lb_lds_doubles(NP) < (size_t)OFF_KS + 2 * LB_TILE) return -1;      // the step's two transposition tiles lie in the evaluation's arrays
@@ -2022,6 +2022,6 @@ int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int 
     }
   }
   hipLaunchKernelGGL(k_lbfgsb_group, dim3(entries), dim3(LB_THREADS), lds, st, table, mode, num_restarts, maxiter, n, NP, ld, Xq,
-                     ZnT, R, RT, alpha, bounds4, ystats, bestf, k_dev, inv_ls, maximize, acq, kernel, out_x, out_v, zs);
+                     ZnT, R, RT, alpha, bounds4, ystats, bestf, k_dev, inv_ls, maximize, acq, kernel, out_x, out_v, zs, hyp);
   return 0;
 }

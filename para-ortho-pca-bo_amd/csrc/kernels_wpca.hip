@@ -507,8 +507,9 @@ __global__ __launch_bounds__(WP_THREADS) void k_zstats(const double* __restrict_
                                                        double* __restrict__ bounds4, double* __restrict__ zn_mean,
                                                        double* __restrict__ ystats, double* __restrict__ ys,
                                                        HostMirror* hm, const int* __restrict__ k_dev, size_t zs,
-                                                       size_t hzs, double mean_c) {
-  ZRUN(Z); ZRUN(y); ZRUN(user_nb); ZRUN(bounds4); ZRUN(zn_mean); ZRUN(ystats); ZRUN(ys); ZRUN(k_dev);
+                                                       size_t hzs, double mean_c, const double* __restrict__ hyp) {
+  ZRUN(Z); ZRUN(y); ZRUN(user_nb); ZRUN(bounds4); ZRUN(zn_mean); ZRUN(ystats); ZRUN(ys); ZRUN(k_dev); ZRUN(hyp);
+  if (hyp) mean_c = hyp[PCABO_HYP_MEAN_C];      // a batch whose runs carry their own fitted model
   hm = zrun(hm, hzs, blockIdx.z);
   if (k_dev) k = *k_dev;          // enqueued behind the wPCA: the reduced dimension is not on the host yet
   __shared__ double s_red[WP_THREADS];
@@ -577,8 +578,10 @@ __global__ __launch_bounds__(WP_THREADS) void k_zstats(const double* __restrict_
 __global__ __launch_bounds__(256) void k_znorm(const double* __restrict__ Z, int n, int k, int NP, int KP, int ld,
                                                const double* __restrict__ bounds4, const double* __restrict__ zn_mean,
                                                double inv_ls, double* __restrict__ ZnT, double* __restrict__ AT,
-                                               double* __restrict__ nrm, const int* __restrict__ k_dev, size_t zs) {
-  ZRUN(Z); ZRUN(bounds4); ZRUN(zn_mean); ZRUN(ZnT); ZRUN(AT); ZRUN(nrm); ZRUN(k_dev);
+                                               double* __restrict__ nrm, const int* __restrict__ k_dev, size_t zs,
+                                               const double* __restrict__ hyp) {
+  ZRUN(Z); ZRUN(bounds4); ZRUN(zn_mean); ZRUN(ZnT); ZRUN(AT); ZRUN(nrm); ZRUN(k_dev); ZRUN(hyp);
+  if (hyp) inv_ls = hyp[PCABO_HYP_INV_LS];
   if (k_dev) { k = *k_dev; KP = (k + 3) & ~3; }
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= NP) return;
@@ -679,12 +682,12 @@ void launch_zstats(hipStream_t s, const double* Z, const double* y, int n, int k
                    double* bounds4, double* zn_mean, double* ystats, double* ys, HostMirror* hm, const int* k_dev, ZB zb,
                    double mean_c) {
   hipLaunchKernelGGL(k_zstats, dim3(1, 1, zb.B), dim3(WP_THREADS), 0, s, Z, y, n, k, user_norm_bounds, bounds4, zn_mean,
-                     ystats, ys, hm, k_dev, zb.zs, zb.hzs, mean_c);
+                     ystats, ys, hm, k_dev, zb.zs, zb.hzs, mean_c, zb.hyp);
 }
 void launch_znorm(hipStream_t s, const double* Z, int n, int k, int NP, int KP, int ld, const double* bounds4,
                   const double* zn_mean, double inv_ls, double* ZnT, double* AT, double* nrm, const int* k_dev, ZB zb) {
   hipLaunchKernelGGL(k_znorm, dim3((NP + 255) / 256, 1, zb.B), dim3(256), 0, s, Z, n, k, NP, KP, ld, bounds4, zn_mean, inv_ls,
-                     ZnT, AT, nrm, k_dev, zb.zs);
+                     ZnT, AT, nrm, k_dev, zb.zs, zb.hyp);
 }
 void launch_inverse_map(hipStream_t s, const double* z, const double* comps, const double* data_mean,
                         const double* pca_mean, int k, int d, double* x, const int* k_dev, ZB zb, double* host_x,

@@ -108,6 +108,7 @@ struct pcabo_ctx {
   double* dKS = nullptr;                 // q x ld kernel vectors of the GEMM scoring path
   double* dBestF = nullptr;              // best_f of this run for the batched acquisition launches (set by the batch)
   double* dMll = nullptr;                // GP fit: 2 partial sums per lower 64 x 64 tile of K^-1, then the 6 results (k_mll_finish)
+  double* dHyp = nullptr;                // lock-step fit of a batch: this run's {1 / lengthscale, noise, mean constant} (PCABO_HYP_*)
   char *dRegion = nullptr, *hRegion = nullptr;   // the two allocations everything above / below is carved from
   size_t region_bytes = 0, hregion_bytes = 0;
   bool in_batch = false; int batch_index = 0;
@@ -116,6 +117,7 @@ struct pcabo_ctx {
   HostMirror* hm = nullptr;
   double *hXq = nullptr, *hVal = nullptr, *hGrad = nullptr, *hSmall = nullptr, *hBestF = nullptr;
   double* hMll = nullptr;                // GP fit: the 6 results of one evaluation
+  double* hHyp = nullptr;                // lock-step fit of a batch: the host copy of dHyp
   MailPair* dMail = nullptr;             // mailbox of the resident acquisition kernel, in device memory
   bool mail_bar = false;                 // the host can write dMail itself through the PCIe BAR (the resident mode needs it)
   MailPair* dPairs = nullptr;            // its partial records as (value, tag) pairs: 32 queries x 32 slabs
@@ -396,6 +398,7 @@ static size_t carve_device(pcabo_ctx* ctx, char* base) {
   ctx->dCounters = c.take<unsigned int>(PCABO_CNT_DONE + 1);
   const size_t nb = N / PCABO_BS;
   ctx->dMll = c.take<double>(nb * (nb + 1) + 8);
+  ctx->dHyp = c.take<double>(PCABO_HYP_WORDS);
   return (c.off + 4095) & ~(size_t)4095;
 }
 static size_t carve_host(pcabo_ctx* ctx, char* base) {
@@ -410,6 +413,7 @@ static size_t carve_host(pcabo_ctx* ctx, char* base) {
   ctx->hIn = c.take<double>(n * (2 * d + 2));
   ctx->hBestF = c.take<double>(2);
   ctx->hMll = c.take<double>(8);
+  ctx->hHyp = c.take<double>(PCABO_HYP_WORDS);
   return (c.off + 4095) & ~(size_t)4095;
 }
 
@@ -828,33 +832,44 @@ static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, const double* Z, co
 
 // One evaluation: the conditioning at theta (k_zstats with the mean constant -> k_znorm -> k_gram -> Cholesky -> root inverse
 // -> alpha, the jitter retries of pcabo_gp_condition_end), k_mll_grad + k_mll_finish, one 48-byte copy and one wait per attempt.
-// Loss and gradient are assembled here: the prior on s2 and the chain rule through softplus are host arithmetic.
-static int mll_eval(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta, double* loss, double* grad) {
-  const double s2 = theta[0], c = theta[1], rho = theta[2];
-  const double ls = softplus_host(rho);
-  if (!(s2 > 0.0) || !std::isfinite(s2) || !std::isfinite(c) || !(ls > 0.0) || !std::isfinite(ls))
-    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
+// Loss and gradient are assembled on the host: the prior on s2 and the chain rule through softplus are host arithmetic.
+// The three pieces below are shared by the single context (mll_eval) and the lock-step fit of a batch (batch_mll_round).
+static bool mll_theta_ok(const double* theta) {
+  const double s2 = theta[0], c = theta[1], ls = softplus_host(theta[2]);
+  return s2 > 0.0 && std::isfinite(s2) && std::isfinite(c) && ls > 0.0 && std::isfinite(ls);
+}
+
+// The attempts of one evaluation from `attempt` on (psd_safe_cholesky: 0, 1e-8, 1e-7, 1e-6).  Attempt 0 finds its
+// factorisation already on the stream; a later one redoes it with that attempt's jitter.  Each attempt: the likelihood
+// kernels, the copy of their 6 results, one wait.  A run of a batch whose lock-step round failed enters at attempt 1.
+static int mll_attempts(pcabo_ctx* ctx, int attempt) {
   hipStream_t s = ctx->stream;
-  int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, ls, s2, PCABO_KERNEL_MATERN52, c);
-  if (rc != PCABO_OK) return rc;
-  ctx->gp_pending = false;
   const int nb = ctx->NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
   double* out = ctx->dMll + 2 * (size_t)tiles;
-  double jitter = 0.0;
-  for (int attempt = 0;; ++attempt) {                    // psd_safe_cholesky: 0, 1e-8, 1e-7, 1e-6
-    launch_mll_grad(s, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
+  double jitter = 1e-8;
+  for (int a = 2; a <= attempt; ++a) jitter *= 10.0;
+  for (;; ++attempt) {
+    if (attempt > 0) {
+      const int rc = launch_factorisation(ctx, jitter);
+      if (rc != PCABO_OK) return rc;
+      jitter *= 10.0;
+    }
+    launch_mll_grad(s, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
     HOST_OUT(ctx->hMll, out, 6, double);
     HIPCHK(wait_stream(s));
     HIPCHK(hipGetLastError());
     if (ctx->hm->chol_info == 0) break;
     if (attempt == 3)
       return set_err(ctx, PCABO_ERR_NOT_PD, "K + s2 I not positive definite after jitter retries (pivot %s%d)", "", ctx->hm->chol_info);
-    jitter = (attempt == 0) ? 1e-8 : jitter * 10.0;
-    rc = launch_factorisation(ctx, jitter);
-    if (rc != PCABO_OK) return rc;
   }
   ctx->have_gp = true;
-  const double* h = ctx->hMll;   // sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, sum W dK/dlog l
+  return PCABO_OK;
+}
+
+// h = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, sum W dK/dlog l} of a state conditioned at theta
+static void mll_assemble(const double* h, int n, const double* theta, double* loss, double* grad) {
+  const double s2 = theta[0], rho = theta[2];
+  const double ls = softplus_host(rho);
   const double LOG2PI = 1.8378770664093453;
   const double lnz = std::log(s2), u = lnz + 4.0;
   const double log_n = -0.5 * h[1] - h[0] - 0.5 * n * LOG2PI;
@@ -866,6 +881,17 @@ static int mll_eval(pcabo_ctx* ctx, int n, int k, const double* unb, const doubl
     grad[1] = -h[2] / n;
     grad[2] = -(0.5 * h[5] * sig / ls) / n;
   }
+}
+
+static int mll_eval(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta, double* loss, double* grad) {
+  if (!mll_theta_ok(theta))
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
+  int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, softplus_host(theta[2]), theta[0], PCABO_KERNEL_MATERN52, theta[1]);
+  if (rc != PCABO_OK) return rc;
+  ctx->gp_pending = false;
+  rc = mll_attempts(ctx, 0);
+  if (rc != PCABO_OK) return rc;
+  mll_assemble(ctx->hMll, n, theta, loss, grad);
   return PCABO_OK;
 }
 
@@ -892,23 +918,28 @@ int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k,
   LbfgsbDriver fit;                                      // scipy's defaults and limits, the published order
   fit.keep_accepted = true;
   fit.init(3, theta_inout, lower, upper);
-  bool not_pd = false;
+  int stop_task = 0;                                     // PCABO_FIT_TASK_*: a trial theta ended the fit (abnormal, warnflag 2)
   while (fit.advance()) {
     double f = 0.0;
+    // a trial theta outside the model's domain (a line-search step so long that softplus(rho) underflows to 0, a non-finite
+    // value): like one the factorisation cannot take it ends the fit abnormally at the last accepted iterate
+    if (fit.have_cache && !mll_theta_ok(fit.x.data())) { stop_task = PCABO_FIT_TASK_DOMAIN; break; }
     rc = mll_eval(ctx, n, k, unb, fit.x.data(), &f, fit.g.data());
     if (rc == PCABO_ERR_NOT_PD) {                        // a trial theta the factorisation cannot take: stop, keep the last iterate
       if (!fit.have_cache) return rc;                    // (not even the start)
-      not_pd = true;
+      stop_task = PCABO_FIT_TASK_NOT_PD;
       break;
     }
     if (rc != PCABO_OK) return rc;
     fit.absorb(f);
   }
+  const bool not_pd = stop_task != 0;
   // the result: where the optimiser ended (it restores the last iterate itself), after a NOT_PD stop the last accepted iterate.
   // Leave the context conditioned there (it is conditioned at the last evaluated point) and report the loss there.
   const double* xr = not_pd ? fit.xacc.data() : fit.x.data();
   double fr = fit.fc;
-  if (!fit.have_cache || memcmp(xr, fit.xc.data(), 3 * sizeof(double)) != 0) {
+  // (after a NOT_PD stop the context holds the trial theta's failed factorisation: it is conditioned again in any case)
+  if (stop_task == PCABO_FIT_TASK_NOT_PD || !fit.have_cache || memcmp(xr, fit.xc.data(), 3 * sizeof(double)) != 0) {
     double gr[3];
     rc = mll_eval(ctx, n, k, unb, xr, &fr, gr);
     if (rc != PCABO_OK) return rc;
@@ -918,7 +949,7 @@ int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k,
   if (info) {
     info[0] = fit.niter; info[1] = fit.nfev;
     info[2] = not_pd ? 2 : fit.opt.warnflag();
-    info[3] = not_pd ? PCABO_FIT_TASK_NOT_PD : fit.opt.task();
+    info[3] = not_pd ? stop_task : fit.opt.task();
   }
   return PCABO_OK;
 }
@@ -1449,6 +1480,11 @@ struct pcabo_batch {
   bool wpca_uncollected = false, gp_pending = false, have_gp = false;
   double lengthscale = 0.0, noise = 0.0;
   int kernel = 0;
+  // lock-step fit (pcabo_batch_gp_mll / pcabo_batch_gp_fit): where the last conditioning's inputs lie on the device (run 0), and
+  // whether the runs now carry their own model - then every batched launch reads 1 / lengthscale from the runs' dHyp blocks
+  const double *fitZ = nullptr, *fitY = nullptr, *fitUnb = nullptr;
+  bool fitted = false;
+  int fit_rounds = 0;
   int gcur = 0, vprev_d = 0;             // eigenvector ping-pong of ALL runs (they advance together)
   int cnt_S = 0; bool cnt_dirty = true;
   bool prof = false; hipEvent_t pev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // phase marks of the last conditioning
@@ -1480,6 +1516,8 @@ static int bset_err(pcabo_batch* b, int code, const char* fmt, const char* a = "
   } while (0)
 
 static ZB batch_zb(const pcabo_batch* b) { ZB z; z.B = b->B; z.zs = b->zs; z.hzs = b->hzs; return z; }
+// per-run hyperparameter blocks for the batched acquisition launches: only after a lock-step fit (null: the shared scalar)
+static const double* batch_hyp(const pcabo_batch* b) { return b->fitted ? b->ctx[0]->dHyp : nullptr; }
 
 static void batch_free(pcabo_batch* batch) {
   (void)hipSetDevice(batch->device);
@@ -1726,6 +1764,7 @@ int pcabo_batch_wpca_gp_condition_begin(pcabo_batch* batch, const double* X, con
   batch->n = n; batch->d = d; batch->NP = NP;
   batch->lengthscale = lengthscale; batch->noise = gp_noise; batch->kernel = kernel;
   batch->wpca_uncollected = true; batch->gp_pending = true; batch->have_gp = false;
+  batch->fitZ = c0->dZ; batch->fitY = inY; batch->fitUnb = nullptr; batch->fitted = false;
   for (int b = 0; b < B; ++b) {          // the per-run contexts see the same state (single-context calls keep working)
     pcabo_ctx* c = batch->ctx[b];
     c->n = n; c->d = d; c->NP = NP; c->lengthscale = lengthscale; c->noise = gp_noise; c->kernel = kernel;
@@ -1793,6 +1832,7 @@ int pcabo_batch_gp_condition_begin(pcabo_batch* batch, const double* Z, const do
   batch->n = n; batch->d = k; batch->NP = NP;
   batch->lengthscale = lengthscale; batch->noise = gp_noise; batch->kernel = kernel;
   batch->wpca_uncollected = false; batch->gp_pending = true; batch->have_gp = false;
+  batch->fitZ = inZ; batch->fitY = inY; batch->fitUnb = norm_bounds ? c0->dUserNB : nullptr; batch->fitted = false;
   for (int b = 0; b < B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
     c->n = n; c->d = k; c->k = k; c->KP = round_up(k, 4); c->NP = NP; c->lengthscale = lengthscale; c->noise = gp_noise; c->kernel = kernel;
@@ -1850,7 +1890,7 @@ static int batch_max_k(const pcabo_batch* batch) {
 static AcqBatch batch_ab(const pcabo_batch* batch, int table, int xq_host) {
   AcqBatch ab;
   ab.zs = batch->zs; ab.hzs = batch->hzs; ab.k_dev = batch->ctx[0]->dK; ab.bestf = batch->ctx[0]->dBestF;
-  ab.table = table; ab.xq_host = xq_host;
+  ab.table = table; ab.xq_host = xq_host; ab.hyp = batch_hyp(batch);
   return ab;
 }
 
@@ -1864,6 +1904,218 @@ static int batch_put_best_f(pcabo_batch* batch, const double* best_f) {
   BHIPCHK(hipMemcpy2DAsync(c0->dBestF, batch->zs, c0->hBestF, batch->hzs, sizeof(double), batch->B, hipMemcpyHostToDevice, batch->stream));
   return PCABO_OK;
 }
+
+}  // extern "C"
+
+// ---- lock-step GP hyperparameter fit of a batch (DESIGN.md "GP hyperparameter fit", the batched form) -------------------
+// One round = ONE launch sequence for all B runs (blockIdx.z = run): every run is conditioned at its own theta, read by k_zstats,
+// k_znorm and k_gram from the runs' dHyp blocks, then k_mll_grad + k_mll_finish, one strided copy of B x 6 doubles and one wait.
+// hyp_theta[b]: the theta run b is conditioned at, or NULL for a run that rests at the batch's shared model (parked runs).
+// A run whose Cholesky failed in the round is redone alone on its own context (mll_attempts from the first jitter on), as
+// batch_score_impl does; st[b] is PCABO_OK, PCABO_ERR_NOT_PD or a HIP error for every run with a theta, untouched otherwise.
+static int batch_mll_round(pcabo_batch* batch, const std::vector<const double*>& hyp_theta, int* st) {
+  const int B = batch->B, n = batch->n, NP = batch->NP;
+  pcabo_ctx* c0 = batch->ctx[0];
+  hipStream_t s = batch->stream;
+  for (int b = 0; b < B; ++b) {
+    pcabo_ctx* c = batch->ctx[b];
+    const double* th = hyp_theta[b];
+    // the very doubles the single-context path passes by value: 1.0 / softplus(rho), the noise, the mean constant
+    const double ls = th ? softplus_host(th[2]) : batch->lengthscale;
+    c->hHyp[PCABO_HYP_INV_LS] = 1.0 / ls;
+    c->hHyp[PCABO_HYP_NOISE] = th ? th[0] : batch->noise;
+    c->hHyp[PCABO_HYP_MEAN_C] = th ? th[1] : 0.0;
+    c->hHyp[3] = 0.0;
+    c->lengthscale = ls; c->noise = c->hHyp[PCABO_HYP_NOISE]; c->kernel = batch->kernel;   // single-context calls on a member see its model
+    c->have_gp = false;
+  }
+  BHIPCHK(hipMemcpy2DAsync(c0->dHyp, batch->zs, c0->hHyp, batch->hzs, PCABO_HYP_WORDS * sizeof(double), B, hipMemcpyHostToDevice, s));
+  ZB zb = batch_zb(batch);
+  zb.hyp = c0->dHyp;
+  launch_zstats(s, batch->fitZ, batch->fitY, n, -1, batch->fitUnb, c0->dBounds4, c0->dZnMean, c0->dYstats, c0->dYs, c0->hm, c0->dK, zb);
+  launch_znorm(s, batch->fitZ, n, -1, NP, 0, c0->ld, c0->dBounds4, c0->dZnMean, 0.0, c0->dZnT, c0->dAT, c0->dNrm, c0->dK, zb);
+  launch_gram(s, c0->dAT, c0->dNrm, n, NP, 0, c0->ld, 0.0, batch->kernel, nullptr, c0->dK, c0->dL, c0->dInfo, zb);
+  if (launch_cholesky(s, c0->dL, NP, c0->ld, c0->dInfo, c0->dDiag, zb) != 0)
+    return bset_err(batch, PCABO_ERR_HIP, "the Cholesky launches could not be set up (device or kernel attribute)%s", "");
+  launch_trinv(s, c0->dL, NP, c0->ld, c0->dR, zb);
+  launch_alpha(s, c0->dR, c0->dYs, n, NP, c0->ld, c0->dTmp, c0->dAlpha, zb);
+  const int nb = NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
+  double* out = c0->dMll + 2 * (size_t)tiles;
+  launch_mll_grad(s, c0->dR, c0->dAT, c0->dNrm, c0->dAlpha, c0->dL, c0->dYs, n, NP, 0, c0->ld, c0->dMll, out, c0->dK, zb);
+  BHIPCHK(hipMemcpy2DAsync(c0->hMll, batch->hzs, out, batch->zs, 6 * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  BHIPCHK(hipMemcpy2DAsync((void*)&c0->hm->chol_info, batch->hzs, c0->dInfo, batch->zs, sizeof(int), B, hipMemcpyDeviceToHost, s));
+  BHIPCHK(wait_stream(s));
+  BHIPCHK(hipGetLastError());
+  ++batch->fit_rounds;
+  for (int b = 0; b < B; ++b) {
+    pcabo_ctx* c = batch->ctx[b];
+    if (c->hm->chol_info == 0) { c->have_gp = true; if (hyp_theta[b]) st[b] = PCABO_OK; continue; }
+    if (!hyp_theta[b]) continue;
+    st[b] = mll_attempts(c, 1);          // rare: jitter 1e-8, 1e-7, 1e-6 for this run alone (sets have_gp)
+  }
+  return PCABO_OK;
+}
+
+// what both entry points need before the first round; *act = the runs that take part
+static int batch_fit_prepare(pcabo_batch* batch, const char* who, std::vector<char>* act, int* status) {
+  if (batch->kernel != PCABO_KERNEL_MATERN52 && (batch->gp_pending || batch->have_gp))
+    return bset_err(batch, PCABO_ERR_ARG, "%s: the fit is restated for the Matern-5/2 kernel only", who);
+  if ((!batch->gp_pending && !batch->fitted) || !batch->fitZ)
+    return bset_err(batch, PCABO_ERR_ARG, "%s: call pcabo_batch_wpca_gp_condition_begin or pcabo_batch_gp_condition_begin first", who);
+  if (batch->score_enqueued || batch->opt_enqueued || batch->imap_enqueued)
+    return bset_err(batch, PCABO_ERR_ARG, "%s: a _begin call of this batch has not been ended", who);
+  BHIPCHK(hipSetDevice(batch->device));
+  if (batch->wpca_uncollected) { int rc = pcabo_batch_wpca_results(batch, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc != PCABO_OK) return rc; }
+  act->assign((size_t)batch->B, 0);
+  for (int b = 0; b < batch->B; ++b) {
+    (*act)[b] = batch->active[b] ? 1 : 0;
+    if (status) status[b] = batch->active[b] ? PCABO_OK : PCABO_ERR_ARG;
+  }
+  return PCABO_OK;
+}
+
+// the batch after its last round: conditioned (and waited for), every run at its own model
+static void batch_fit_done(pcabo_batch* batch) {
+  batch->gp_pending = false; batch->have_gp = true; batch->fitted = true;
+  // the device-resident optimiser reads the transposed root inverse of the FINAL factorisation (stream order: before its launch)
+  if (batch->dev_lbfgsb) {
+    pcabo_ctx* c0 = batch->ctx[0];
+    launch_rt_build(batch->stream, c0->dR, batch->n, batch->NP, c0->ld, c0->dGram, batch_zb(batch));
+    for (pcabo_ctx* c : batch->ctx) c->rt_stale = false;
+  }
+}
+
+extern "C" {
+
+int pcabo_batch_gp_mll(pcabo_batch* batch, const double* theta, double* loss, double* grad, int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (!theta || !loss) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_mll: theta and loss are required%s", "");
+  std::vector<char> act;
+  int rc = batch_fit_prepare(batch, "pcabo_batch_gp_mll", &act, status);
+  if (rc != PCABO_OK) return rc;
+  const int B = batch->B;
+  std::vector<const double*> th((size_t)B, nullptr);
+  std::vector<int> st((size_t)B, PCABO_ERR_ARG);
+  for (int b = 0; b < B; ++b) {
+    if (!act[b]) continue;
+    if (mll_theta_ok(theta + 3 * b)) th[b] = theta + 3 * b;
+    else set_err(batch->ctx[b], PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
+  }
+  batch->fit_rounds = 0;
+  rc = batch_mll_round(batch, th, st.data());
+  if (rc != PCABO_OK) return rc;
+  batch_fit_done(batch);
+  int worst = PCABO_OK;
+  for (int b = 0; b < B; ++b) {
+    if (st[b] == PCABO_OK) mll_assemble(batch->ctx[b]->hMll, batch->n, theta + 3 * b, loss + b, grad ? grad + 3 * b : nullptr);
+    else if (act[b]) worst = st[b];
+    if (status) status[b] = st[b];
+  }
+  if (worst != PCABO_OK && !status) return bset_err(batch, worst, "pcabo_batch_gp_mll: a run of the batch failed (status array not given)%s", "");
+  return PCABO_OK;
+}
+
+int pcabo_batch_gp_fit(pcabo_batch* batch, double* theta_inout, double* loss, int* info, int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (!theta_inout) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_fit: theta_inout is required%s", "");
+  std::vector<char> act;
+  int rc = batch_fit_prepare(batch, "pcabo_batch_gp_fit", &act, status);
+  if (rc != PCABO_OK) return rc;
+  const int B = batch->B;
+  // a run is STEPPING (its driver asks for evaluations), at its END point (one more evaluation: the result is not the last point
+  // evaluated), RESTING at its result, or OUT (parked, or failed: it rests at the shared model)
+  enum { STEPPING, END, RESTING, OUT };
+  struct Run { LbfgsbDriver fit; int state = OUT, st = PCABO_ERR_ARG, stop_task = 0; double xr[3] = {0, 0, 0}, fr = 0.0; };
+  std::vector<Run> runs((size_t)B);
+  const double lower[3] = {1e-4, -INFINITY, -INFINITY}, upper[3] = {INFINITY, INFINITY, INFINITY};
+  for (int b = 0; b < B; ++b) {
+    if (!act[b]) continue;
+    Run& r = runs[b];
+    r.fit.keep_accepted = true;                          // scipy's defaults and limits, the published order (as pcabo_gp_fit)
+    r.fit.init(3, theta_inout + 3 * b, lower, upper);
+    r.state = STEPPING; r.st = PCABO_OK;
+  }
+  // the optimiser has stopped (or met a theta the factorisation cannot take): where does the run end?
+  auto finish = [&](Run& r) {
+    const double* xr = r.stop_task ? r.fit.xacc.data() : r.fit.x.data();
+    memcpy(r.xr, xr, sizeof(r.xr));
+    r.fr = r.fit.fc;
+    // (END after a NOT_PD stop in any case: the run's slab holds the trial theta's failed factorisation)
+    r.state = (r.stop_task == PCABO_FIT_TASK_NOT_PD || !r.fit.have_cache || memcmp(r.xr, r.fit.xc.data(), sizeof(r.xr)) != 0) ? END : RESTING;
+  };
+  std::vector<const double*> th((size_t)B, nullptr);
+  std::vector<int> st((size_t)B, PCABO_OK);
+  batch->fit_rounds = 0;
+  for (;;) {
+    int pending = 0;
+    for (int b = 0; b < B; ++b) {
+      Run& r = runs[b];
+      if (r.state == STEPPING && !r.fit.advance()) finish(r);
+      if (r.state == STEPPING && !mll_theta_ok(r.fit.x.data())) {
+        if (r.fit.have_cache) {                          // a trial theta outside the model's domain: abnormal end, last accepted iterate
+          r.stop_task = PCABO_FIT_TASK_DOMAIN;
+          finish(r);
+        } else {                                         // (the start itself)
+          set_err(batch->ctx[b], PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
+          r.state = OUT; r.st = PCABO_ERR_ARG;
+        }
+      }
+      th[b] = r.state == STEPPING ? r.fit.x.data() : (r.state == OUT ? nullptr : r.xr);
+      if (r.state == STEPPING || r.state == END) ++pending;
+    }
+    if (pending == 0 && batch->fit_rounds > 0) break;
+    rc = batch_mll_round(batch, th, st.data());
+    if (rc != PCABO_OK) return rc;
+    for (int b = 0; b < B; ++b) {
+      Run& r = runs[b];
+      if (r.state == OUT) continue;
+      if (st[b] != PCABO_OK && st[b] != PCABO_ERR_NOT_PD) { r.state = OUT; r.st = st[b]; continue; }
+      if (r.state == STEPPING) {
+        if (st[b] == PCABO_ERR_NOT_PD) {                 // a trial theta the factorisation cannot take: stop, keep the last iterate
+          if (!r.fit.have_cache) { r.state = OUT; r.st = PCABO_ERR_NOT_PD; continue; }      // (not even the start)
+          r.stop_task = PCABO_FIT_TASK_NOT_PD;
+          finish(r);
+          continue;
+        }
+        double f = 0.0;
+        mll_assemble(batch->ctx[b]->hMll, batch->n, r.fit.x.data(), &f, r.fit.g.data());
+        r.fit.absorb(f);
+      } else {                                           // END, RESTING: the result theta
+        if (st[b] != PCABO_OK) { r.state = OUT; r.st = st[b]; continue; }
+        if (r.state == END) {
+          mll_assemble(batch->ctx[b]->hMll, batch->n, r.xr, &r.fr, nullptr);
+          r.state = RESTING;
+        }
+      }
+    }
+  }
+  batch_fit_done(batch);
+  int worst = PCABO_OK;
+  for (int b = 0; b < B; ++b) {
+    const Run& r = runs[b];
+    if (status) status[b] = r.st;
+    if (!act[b]) continue;
+    if (r.st != PCABO_OK) { worst = r.st; batch->ctx[b]->have_gp = false; continue; }
+    memcpy(theta_inout + 3 * b, r.xr, sizeof(r.xr));
+    if (loss) loss[b] = r.fr;
+    if (info) {
+      int* io = info + 4 * b;
+      io[0] = r.fit.niter; io[1] = r.fit.nfev;
+      io[2] = r.stop_task ? 2 : r.fit.opt.warnflag();
+      io[3] = r.stop_task ? r.stop_task : r.fit.opt.task();
+    }
+  }
+  if (worst != PCABO_OK && !status) return bset_err(batch, worst, "pcabo_batch_gp_fit: a run of the batch failed (status array not given)%s", "");
+  return PCABO_OK;
+}
+
+// launch sequences (rounds) the last pcabo_batch_gp_fit / pcabo_batch_gp_mll took: with the runs' evaluation counts it gives
+// the share of run-evaluations spent on runs that had already finished
+int pcabo_batch_gp_fit_rounds(pcabo_batch* batch) { return batch ? batch->fit_rounds : PCABO_ERR_ARG; }
+
+}  // extern "C"
+
+extern "C" {
 
 // The scoring of the raw samples in two halves: _begin packs the points, enqueues copy - scoring launch - copy back and
 // returns; _end waits for the stream and finishes (jitter retries of single runs included).  pcabo_batch_busy tells a caller
@@ -1880,7 +2132,8 @@ static int batch_score_impl(pcabo_batch* batch, const double* Xq, int q, const d
   if (!batch) return PCABO_ERR_ARG;
   if (!Xq || !best_f || (!val && phase != 1) || q < 1 || q > batch->max_q || (acq != PCABO_ACQ_LOG_EI && acq != PCABO_ACQ_PI))
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: bad argument%s", "");
-  if (!batch->gp_pending) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: no conditioning in flight%s", "");
+  // (after pcabo_batch_gp_fit the conditioning has been waited for already: the fitted state is scored by the same launches)
+  if (!batch->gp_pending && !batch->fitted) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: no conditioning in flight%s", "");
   if (phase == 2 && !batch->score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval_end: no _begin before it%s", "");
   if (phase != 2 && batch->score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: a scoring is already enqueued%s", "");
   if (batch->wpca_uncollected) { int rc = pcabo_batch_wpca_results(batch, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc != PCABO_OK) return rc; }
@@ -2027,7 +2280,7 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
     if (ks != s) { BHIPCHK(hipEventRecord(batch->evOptIn, s)); BHIPCHK(hipStreamWaitEvent(ks, batch->evOptIn, 0)); }
     if (launch_lbfgsb_group(ks, batch->dOptTab, nent, mode, num_restarts, maxiter, batch->n, batch->NP, c0->ld, c0->dXq, c0->dZnT,
                             c0->dR, c0->dGram, c0->dAlpha, c0->dBounds4, c0->dYstats, c0->dBestF, c0->dK, inv_ls, maximize ? 1 : 0,
-                            acq, batch->kernel, c0->dGrad, c0->dVal, batch->zs) != 0)
+                            acq, batch->kernel, c0->dGrad, c0->dVal, batch->zs, batch_hyp(batch)) != 0)
       return bset_err(batch, PCABO_ERR_HIP, "the device-resident optimiser could not be launched%s", "");
     if (ks != s) { BHIPCHK(hipEventRecord(batch->evOptOut, ks)); BHIPCHK(hipStreamWaitEvent(s, batch->evOptOut, 0)); }
     BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (size_t)(64 + 8 * ngroups) * sizeof(double), B, hipMemcpyDeviceToHost, s));
@@ -2299,7 +2552,7 @@ int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, con
   BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, c0->hXq, batch->hzs, (size_t)(q + 2) * kmax * sizeof(double), B, hipMemcpyHostToDevice, s));
   if (launch_lbfgsb_group(s, batch->dOptTab, nent, 0, q, 1, batch->n, batch->NP, c0->ld, c0->dXq, c0->dZnT, c0->dR, c0->dGram,
                           c0->dAlpha, c0->dBounds4, c0->dYstats, c0->dBestF, c0->dK, 1.0 / batch->lengthscale, maximize ? 1 : 0, acq,
-                          batch->kernel, c0->dGrad, c0->dVal, batch->zs) != 0)
+                          batch->kernel, c0->dGrad, c0->dVal, batch->zs, batch_hyp(batch)) != 0)
     return bset_err(batch, PCABO_ERR_HIP, "the device-resident optimiser could not be launched%s", "");
   BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (size_t)q * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipMemcpy2DAsync(c0->hGrad, batch->hzs, c0->dGrad, batch->zs, (size_t)q * kmax * sizeof(double), B, hipMemcpyDeviceToHost, s));

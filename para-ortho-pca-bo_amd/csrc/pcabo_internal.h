@@ -70,6 +70,7 @@ struct AcqBatch {
   int table = 0;                   // 1: blockIdx.y indexes the active-query table that travels in the QueryArgs slot
                                    //    (32-bit entries: run << 16 | query of that run); 0: run = blockIdx.z
   int xq_host = 0;                 // 1: Xq is a pinned HOST pointer (stride hzs), read by the kernel over PCIe
+  const double* hyp = nullptr;     // run 0's hyperparameter block (PCABO_HYP_*) after a lock-step fit (null: prm.inv_ls)
 };
 
 // Small results the host needs after a device phase; lives in pinned host memory.
@@ -275,7 +276,14 @@ __device__ inline double read_lane(double v, int lane) {
 
 void launch_rank(hipStream_t s, const double* f, int n, int maximize, long long* ranks);
 // B > 1: batched launch over the B contexts of a batch (blockIdx.z = run, buffer strides zs / hzs bytes, see zrun)
-struct ZB { int B = 1; size_t zs = 0, hzs = 0; };
+// hyp: run 0's hyperparameter block, set once the runs of a batch carry their own fitted model (pcabo_batch_gp_fit): k_zstats,
+// k_znorm and k_gram then read the mean constant, 1 / lengthscale and the noise of THEIR run from it instead of the scalar
+// argument.  The host writes the very doubles the single-context path passes by value (1.0 / softplus(rho) is formed there).
+#define PCABO_HYP_INV_LS 0
+#define PCABO_HYP_NOISE 1
+#define PCABO_HYP_MEAN_C 2
+#define PCABO_HYP_WORDS 4
+struct ZB { int B = 1; size_t zs = 0, hzs = 0; const double* hyp = nullptr; };
 void launch_wpca_prep(hipStream_t s, const double* X, const long long* ranks, const double* noise, int n, int d,
                       int DP, double* weights, double* data_mean, double* pca_mean, double* Wc, ZB zb = ZB());
 void launch_cov(hipStream_t s, const double* Wc, int n, int DP, double* C, ZB zb = ZB());
@@ -306,8 +314,10 @@ void launch_alpha(hipStream_t s, const double* R, const double* ys, int n, int N
                   ZB zb = ZB());
 // marginal-likelihood pieces of a conditioned state (kernels_fit.hip, Matern-5/2): partial = 2 doubles per lower 64 x 64 tile,
 // out[6] = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, sum_ij W_ij dK_ij/dlog l}
+// zb.B > 1: one launch pair for the B runs of a batch (blockIdx.z = run, k / KP of a run from k_dev, n and NP common)
 void launch_mll_grad(hipStream_t s, const double* R, const double* AT, const double* nrm, const double* alpha, const double* L,
-                     const double* ys, int n, int NP, int KP, int ld, double* partial, double* out);
+                     const double* ys, int n, int NP, int KP, int ld, double* partial, double* out,
+                     const int* k_dev = nullptr, ZB zb = ZB());
 void launch_acq(hipStream_t s, const QueryArgs* qa, const double* Xq, int q, int n, int k, int NP, int ld,
                 const double* ZnT, const double* R, const double* alpha, const double* bounds4, const double* ystats,
                 AcqParams p, double* partial, unsigned int* counters, double* val,
@@ -343,4 +353,5 @@ bool lbfgsb_device_possible(int NP, int kmax, int batch_limit);
 int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int mode, int num_restarts, int maxiter, int n, int NP,
                         int ld, const double* Xq, const double* ZnT, const double* R, const double* RT, const double* alpha,
                         const double* bounds4, const double* ystats, const double* bestf, const int* k_dev, double inv_ls,
-                        int maximize, int acq, int kernel, double* out_x, double* out_v, size_t zs);
+                        int maximize, int acq, int kernel, double* out_x, double* out_v, size_t zs,
+                        const double* hyp = nullptr);   // hyp: per-run hyperparameter blocks (stride zs), 1 / lengthscale read from them

@@ -60,6 +60,7 @@ EXPORTS = [
     "pcabo_batch_busy", "pcabo_batch_gp_condition_end_eval_begin", "pcabo_batch_gp_condition_end_eval_end",
     "pcabo_batch_optimize_acqf_begin", "pcabo_batch_optimize_acqf_end", "pcabo_batch_inverse_map_begin", "pcabo_batch_inverse_map_end",
     "pcabo_batch_set_input_strides", "pcabo_batch_gp_condition_begin",
+    "pcabo_batch_gp_mll", "pcabo_batch_gp_fit", "pcabo_batch_gp_fit_rounds",
     "pcabo_batch_set_profiling", "pcabo_batch_get_profile", "pcabo_batch_set_active", "pcabo_batch_set_workers", "pcabo_batch_set_option",
     "pcabo_device_lbfgsb_limits",
     "pcabo_bbob_table_doubles", "pcabo_bbob_create", "pcabo_bbob_destroy", "pcabo_bbob_eval",
@@ -153,6 +154,9 @@ def _load() -> C.CDLL:
     lib.pcabo_batch_set_profiling.argtypes = [vp, C.c_int]
     lib.pcabo_batch_set_active.argtypes = [vp, vp]
     lib.pcabo_batch_get_profile.argtypes = [vp, vp]
+    lib.pcabo_batch_gp_mll.argtypes = [vp, vp, vp, vp, vp]
+    lib.pcabo_batch_gp_fit.argtypes = [vp, vp, vp, vp, vp]
+    lib.pcabo_batch_gp_fit_rounds.argtypes = [vp]
     for name in EXPORTS:
         getattr(lib, name).restype = C.c_int
     lib.pcabo_batch_ctx.restype = vp
@@ -586,6 +590,34 @@ class Batch:
         self._chk(LIB.pcabo_batch_gp_condition_end_eval(self._h, _ptr(buf), q, _ptr(bf), int(bool(maximize)), int(acq),
                                                         _ptr(val), _ptr(status)))
         return val, status
+
+    # ---- opt-in GP hyperparameter fit of all runs in lock-step (pcabo_batch_gp_mll / pcabo_batch_gp_fit) -----------------
+    # Both work on the inputs of the last wpca_gp_condition_begin / gp_condition_begin and leave every run conditioned at its
+    # own theta; gp_wait_eval / gp_eval_begin + gp_eval_end and optimize_acqf then use the runs' own models.
+    def gp_mll(self, thetas):
+        """thetas (B, 3) = (noise, mean constant, raw lengthscale) per run.  One dict per run as Context.gp_mll returns it, plus
+        `status` (0; a parked run or one that could not be factored: only `status`)."""
+        th = _f64(thetas, (self.B, 3))
+        loss, grad = np.zeros(self.B), np.zeros((self.B, 3))
+        status = np.zeros(self.B, dtype=np.int32)
+        self._chk(LIB.pcabo_batch_gp_mll(self._h, _ptr(th), _ptr(loss), _ptr(grad), _ptr(status)))
+        return [{**Context._fit_result(th[b], loss[b]), "grad": grad[b].copy(), "status": 0} if status[b] == 0
+                else {"status": int(status[b])} for b in range(self.B)]
+
+    def gp_fit(self, theta0=None):
+        """Fit every run's (noise, mean constant, raw lengthscale) from theta0 ((3,) for all runs, (B, 3), or None: the model's
+        initial values), all runs stepped side by side, one launch sequence per round; bit for bit the fits Context.gp_fit
+        finds for the runs one by one.  One dict per run as Context.gp_fit returns it, plus `status` (a parked run, or one whose
+        start could not be factored: only `status`).  `fit_rounds`: the launch sequences the call took."""
+        th0 = np.asarray(FIT_THETA0 if theta0 is None else theta0, dtype=np.float64)
+        th = np.ascontiguousarray(np.broadcast_to(th0, (self.B, 3)), dtype=np.float64).copy()
+        loss, info = np.zeros(self.B), np.zeros((self.B, 4), dtype=np.int32)
+        status = np.zeros(self.B, dtype=np.int32)
+        self._chk(LIB.pcabo_batch_gp_fit(self._h, _ptr(th), _ptr(loss), _ptr(info), _ptr(status)))
+        self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
+        return [{**Context._fit_result(th[b], loss[b]), "iterations": int(info[b, 0]), "evaluations": int(info[b, 1]),
+                 "warnflag": int(info[b, 2]), "task": int(info[b, 3]), "status": 0} if status[b] == 0
+                else {"status": int(status[b])} for b in range(self.B)]
 
     # ---- the two waiting calls in halves (one thread advancing several batches: pcabo.batchrun.run_interleaved) -------------
     def busy(self) -> bool:

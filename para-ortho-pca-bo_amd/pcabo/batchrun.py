@@ -59,7 +59,7 @@ class BatchedPCABO:
                  maximization: bool = False, device: int = 0, num_restarts: int = 10, raw_samples: int = 512,
                  record_trace: bool = False, host_threads: int = 0, device_objective: bool = False, workers: int = 0,
                  trace_filter=None, acq_kernel: str = "group", lbfgsb_cus: int = 0, torch_threads: Optional[int] = 4,
-                 gc_freeze: bool = True):
+                 gc_freeze: bool = True, fit_gp: bool = False):
         self.problems, self.seeds = list(problems), [int(s) for s in seeds]
         self.B = len(self.problems)
         assert self.B == len(self.seeds) and self.B >= 1
@@ -89,7 +89,15 @@ class BatchedPCABO:
         # reached), the other runs go on, and `run()` reports the failures at the end.
         self.failed = [None] * self.B
         self._frozen = [None] * self.B
-        self.timing = {"pca": 0.0, "wait_score": 0.0, "init_pick": 0.0, "lbfgsb": 0.0, "tail": 0.0, "host_prep": 0.0}
+        self.timing = {"pca": 0.0, "wait_score": 0.0, "init_pick": 0.0, "lbfgsb": 0.0, "tail": 0.0, "host_prep": 0.0, "fit": 0.0}
+        # fit_gp (not in the reference, which never trains its GP; PCA_BO / Vanilla_BO fit_gp=True for one run): every iteration
+        # the runs fit (noise, mean constant, lengthscale) by the marginal likelihood TOGETHER - one launch sequence per round of
+        # the fit for all runs (Batch.gp_fit) - and the acquisition works on every run's own fitted model.  A run takes, bit for
+        # bit, the fits and the path the same run takes alone.  gp_hyperparameters[b]: the run's last fit (Context.gp_fit's dict).
+        self._fit_gp = bool(fit_gp)
+        self.gp_hyperparameters = [None] * self.B
+        self.fit_rounds = 0                # launch sequences of all fits so far / evaluations they carried for live runs
+        self.fit_evaluations = 0
         # record_trace: one entry per (run, iteration) that `trace_filter(b, n)` admits (None: all) with what the oracle
         # needs to replay that iteration from the same state - the run's numpy / torch generator states in front of the
         # iteration (in the form np.random.set_state / torch.set_rng_state take), best_f, and what the device produced
@@ -212,6 +220,25 @@ class BatchedPCABO:
         self._batch.set_active([self.failed[i] is None for i in range(self.B)])
         warnings.warn(f"run {b} (seed {self.seeds[b]}) stopped at n = {n}: {message}", RuntimeWarning)
 
+    def _fit_all(self, n: int) -> float:
+        """The lock-step GP fit of this iteration (a blocking call: every round of the fit waits for the device inside the
+        library); parked runs do not fit.  Returns the seconds it took."""
+        t = perf_counter()
+        fits = self._batch.gp_fit()
+        self.fit_rounds += self._batch.fit_rounds
+        for b, hp in enumerate(fits):
+            if self.failed[b] is not None:
+                continue
+            if hp["status"] != 0:
+                self._park(b, n, f"GP hyperparameter fit failed (status {hp['status']})")
+                continue
+            self.fit_evaluations += hp["evaluations"]
+            if hp["warnflag"] != 0:        # like botorch (and fit_gp_hyperparameters of a single run): keep the iterate, warn
+                warnings.warn(f"GP hyperparameter fit of run {b} did not converge (warnflag {hp['warnflag']}, task {hp['task']}); "
+                              "keeping the last accepted iterate", RuntimeWarning)
+            self.gp_hyperparameters[b] = hp
+        return perf_counter() - t
+
     # ---- one lock-step BO iteration (PCA_BO.py:178-298 for every run) ------------------------------------------------
     def iteration(self) -> None:
         for _ in self._iteration_steps():
@@ -277,6 +304,7 @@ class BatchedPCABO:
         res = bt.wpca_results()
         self.k_hist.append(np.array([r["k"] for r in res], dtype=np.int32))
         t2 = perf_counter()
+        tfit = self._fit_all(n) if self._fit_gp else 0.0
         bounds = bt.acq_bounds()
         raw = [None] * B
         rawbuf = bt.raw_row_buffer(self.raw_samples)      # the runs' raw samples are drawn straight into the rows the scoring packs
@@ -428,7 +456,8 @@ class BatchedPCABO:
         tm = self.timing
         tm["host_prep"] += t1 - t0
         tm["pca"] += t2 - t1
-        tm["wait_score"] += t4 - t2
+        tm["wait_score"] += (t4 - t2) - tfit
+        tm["fit"] += tfit
         tm["init_pick"] += t5 - t4
         tm["lbfgsb"] += t6 - t5
         tm["tail"] += t7 - t6
@@ -500,6 +529,10 @@ class BatchedVanillaBO(BatchedPCABO):
         for b in range(B):
             bt.ctx[b].match_best_f_dtype(best_f[b])
         t3 = t2 = perf_counter()
+        tfit = 0.0
+        if self._fit_gp:
+            yield "conditioning"
+            tfit = self._fit_all(n)
         token = bt.gp_eval_begin(raw, best_f, self.maximization, self.acq_code)
         yield "scoring"
         vals, status = bt.gp_eval_end(token)
@@ -586,7 +619,8 @@ class BatchedVanillaBO(BatchedPCABO):
         tm = self.timing
         tm["host_prep"] += t1 - t0
         tm["pca"] += t2 - t1
-        tm["wait_score"] += t4 - t3
+        tm["wait_score"] += (t4 - t3) - tfit
+        tm["fit"] += tfit
         tm["init_pick"] += t5 - t4
         tm["lbfgsb"] += t6 - t5
         tm["tail"] += t7 - t6
@@ -687,7 +721,7 @@ def run_interleaved(runners: Sequence["BatchedPCABO"], started: bool = False) ->
 
 def bench_block(device: int, B: int, fid: int, dim: int, budget_factor: int = 10, doe_factor: float = 3.0,
                 sub_batches: int = 1, workers: int = 0, acq_kernel: str = "group", schedule: str = "threads",
-                lbfgsb_cus: int = 0, device_objective: bool = False, algorithm: str = "pca") -> dict:
+                lbfgsb_cus: int = 0, device_objective: bool = False, algorithm: str = "pca", fit_gp: bool = False) -> dict:
     """Aggregate BO iterations / second of B runs (instances 0..B-1 of one BBOB function and dimension, seeds per
     ExperimentRunner.py:146) advancing together on one GPU - as one lock-step batch, or as `sub_batches` lock-step batches
     side by side (run_side_by_side); DoE and set-up untimed."""
@@ -700,7 +734,8 @@ def bench_block(device: int, B: int, fid: int, dim: int, budget_factor: int = 10
         subs.append((BatchedVanillaBO if algorithm == "vanilla" else BatchedPCABO)(
             [BBOBProblem(fid, i, dim) for i in inst], [1000 * fid + 10 * dim + i for i in inst], budget, n_doe,
                                  device=device, workers=workers or (workers_for(S) if S > 1 else 0), host_threads=max(1, 8 // S),
-                                 acq_kernel=acq_kernel, lbfgsb_cus=lbfgsb_cus, device_objective=device_objective))
+                                 acq_kernel=acq_kernel, lbfgsb_cus=lbfgsb_cus, device_objective=device_objective,
+                                 fit_gp=fit_gp))
     for r in subs:
         r.start()
     torch.cuda.synchronize()
@@ -742,6 +777,11 @@ def bench_block(device: int, B: int, fid: int, dim: int, budget_factor: int = 10
     extra["schedule"] = schedule
     extra["device_objective"] = bool(device_objective)
     extra["algorithm"] = algorithm
+    extra["fit_gp"] = bool(fit_gp)
+    if fit_gp:
+        rounds = sum(r.fit_rounds for r in subs)
+        extra["fit_rounds"] = rounds
+        extra["fit_evaluations"] = sum(r.fit_evaluations for r in subs)
     # algorithmic bytes of the L-BFGS-B evaluations (SURVEY.md 8d per-unit figures: one value+gradient evaluation of a restart
     # group reads the triangles of R and of its transpose, the normalised points twice and alpha): evaluations the optimisers
     # report x bytes at that iteration's (n, k)

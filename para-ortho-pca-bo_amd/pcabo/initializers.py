@@ -144,11 +144,11 @@ def initialize_q_batch_rows(acq_vals: np.ndarray, n: int, generators, eta: float
             if flags[b] == 2:
                 out.append(np.arange(n))
             elif flags[b] == 1:
-                warnings.warn("All acquisition values for raw samples points are the same. "
-                              "Choosing initial conditions at random.", RuntimeWarning)
-                tg = generators[b].torch_generator()
-                out.append(torch.randperm(n=n_samples, generator=tg)[:n].numpy())
-                generators[b].absorb(tg)
+                # all values equal by the library's statistic (Welford: exactly 0).  torch's own reduction decides, as it does
+                # for a single run: the mean of equal values can round, std comes out as ~1e-16 instead of 0, and botorch then
+                # draws its multinomial over equal weights rather than a random permutation (met on the flat posteriors a fitted
+                # GP has early in a run).  Nothing was drawn from the run's generator yet.
+                out.append(initialize_q_batch(acq_vals[b], n, eta, generator=generators[b]))
             else:
                 out.append(idx[b])
         return out
