@@ -1,8 +1,10 @@
 // Sanitizer driver for the host side of libpcabo (Makefile targets asan / ubsan / tsan; tests/test_host_sanitizers.py runs them).
 // Everything here is CPU code of the product compiled by g++ with -fsanitize=...: csrc/lbfgsb.cpp, csrc/host_entry.cpp (the
-// L-BFGS-B driver and the Sobol helpers), csrc/host_side.h (RestartGroup, RunRestarts, run_rounds, GangPool) and csrc/lb_plan.h (the
-// work plan of the device optimiser's passes).  The batch's round loop is the product's run_rounds with a stub evaluator: where the
-// product launches an acquisition kernel and polls its flags, the workers here evaluate a bounded test objective on the CPU.
+// L-BFGS-B driver and the Sobol helpers), csrc/host_side.h (RestartGroup, RunRestarts, run_rounds, GangPool; FitRun, fit_rounds,
+// mll_assemble) and csrc/lb_plan.h (the work plan of the device optimiser's passes).  The batch's round loop is the product's
+// run_rounds with a stub evaluator: where the product launches an acquisition kernel and polls its flags, the workers here evaluate
+// a bounded test objective on the CPU.  The GP fit is the product's FitRun / fit_rounds over a small dense GP in plain C++ that hands
+// back the six sums the likelihood kernels produce (test_fit_run: lock-step = alone, the NOT_PD / DOMAIN stops, resting runs).
 // Exit code 0 and "host selftest ok" = every check passed; a sanitizer report aborts the process (halt_on_error).
 #include "../../include/pcabo.h"
 #include "host_side.h"
@@ -322,6 +324,207 @@ void test_gang_pool(int workers, int runs) {
   CHECK(rounds.load() > 0, "no rounds");
 }
 
+// ---- the GP hyperparameter fit (FitRun, fit_rounds, mll_assemble of host_side.h) over a stub evaluator --------------------------
+// A small dense GP on the CPU: Matern-5/2 with one lengthscale on the points as given, targets as given (the product's kernels
+// normalise and standardise first; the stepper does not care), Cholesky and inverse by textbook loops.  h = the six sums the
+// likelihood kernels hand to mll_assemble; false: K + s2 I is not positive definite.
+struct TinyGP { int n = 0, k = 0; std::vector<double> Z, y; };
+bool tiny_gp_sums(const TinyGP& gp, const double* th, double* h) {
+  const int n = gp.n;
+  const double s2 = th[0], c = th[1], ls = softplus_host(th[2]), s5 = std::sqrt(5.0);
+  std::vector<double> K((size_t)n * n), dK((size_t)n * n), L((size_t)n * n, 0.0), Li((size_t)n * n, 0.0), Kin((size_t)n * n), a(n, 0.0);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) {
+      double r2 = 0.0;
+      for (int t = 0; t < gp.k; ++t) { const double d = (gp.Z[i * gp.k + t] - gp.Z[j * gp.k + t]) / ls; r2 += d * d; }
+      const double r = std::sqrt(r2), e = std::exp(-s5 * r);
+      K[i * n + j] = (1.0 + s5 * r + 5.0 / 3.0 * r2) * e + (i == j ? s2 : 0.0);
+      dK[i * n + j] = 5.0 / 3.0 * r2 * (1.0 + s5 * r) * e;                 // dK / dlog l
+    }
+  for (int j = 0; j < n; ++j)
+    for (int i = j; i < n; ++i) {
+      double v = K[i * n + j];
+      for (int p = 0; p < j; ++p) v -= L[i * n + p] * L[j * n + p];
+      if (i == j) { if (!(v > 0.0)) return false; L[j * n + j] = std::sqrt(v); }
+      else L[i * n + j] = v / L[j * n + j];
+    }
+  for (int j = 0; j < n; ++j) {                                            // Li = L^-1, column by column
+    Li[j * n + j] = 1.0 / L[j * n + j];
+    for (int i = j + 1; i < n; ++i) {
+      double v = 0.0;
+      for (int p = j; p < i; ++p) v -= L[i * n + p] * Li[p * n + j];
+      Li[i * n + j] = v / L[i * n + i];
+    }
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) {                                          // K^-1 = Li^T Li, alpha = K^-1 (y - c)
+      double v = 0.0;
+      for (int p = std::max(i, j); p < n; ++p) v += Li[p * n + i] * Li[p * n + j];
+      Kin[i * n + j] = v;
+      a[i] += v * (gp.y[j] - c);
+    }
+  for (int t = 0; t < 6; ++t) h[t] = 0.0;
+  for (int i = 0; i < n; ++i) {
+    h[0] += std::log(L[i * n + i]); h[1] += (gp.y[i] - c) * a[i]; h[2] += a[i]; h[3] += a[i] * a[i]; h[4] += Kin[i * n + i];
+    for (int j = 0; j < n; ++j) h[5] += (a[i] * a[j] - Kin[i * n + j]) * dK[i * n + j];
+  }
+  return true;
+}
+TinyGP tiny_gp(int seed, int n = 12, int k = 2) {
+  Lcg r(seed);
+  TinyGP gp; gp.n = n; gp.k = k; gp.Z.resize((size_t)n * k); gp.y.resize(n);
+  for (auto& v : gp.Z) v = r.uni();
+  for (int i = 0; i < n; ++i) gp.y[i] = std::sin(3.0 * gp.Z[i * k] + 0.3 * seed) + gp.Z[i * k + 1] * gp.Z[i * k + 1] - 0.6 + 0.1 * (r.uni() - 0.5);
+  return gp;
+}
+
+// What a fit leaves behind, bit for bit
+struct FitOut { int status; double theta[3], loss; int info[4]; };
+FitOut fit_out(const FitRun& r) {
+  FitOut o;
+  std::memset(&o, 0, sizeof(o));
+  o.status = r.status;
+  if (r.status == PCABO_OK) { std::memcpy(o.theta, r.xr, sizeof(o.theta)); o.loss = r.fr; r.report(o.info); }
+  return o;
+}
+const double FIT_START[3] = {0.006737946999085467, 0.0, 0.0};               // the model's initial values: (e^-5, 0, 0)
+
+// The runs' fits over their GPs in lock-step (start[b] null: a parked run).  fail_at[b] > 0: run b's evaluation number fail_at[b]
+// (1 = the start) answers PCABO_ERR_NOT_PD.  evals[b]: the thetas run b was evaluated at, the rounds it rested not counted;
+// rested[b]: the rounds it rode along at its result.
+struct FitDrive { std::vector<FitOut> out; std::vector<std::vector<double>> evals; std::vector<int> rested; int rounds = 0; };
+FitDrive drive_fits(const std::vector<TinyGP>& gps, const std::vector<const double*>& start, const std::vector<int>& fail_at) {
+  const size_t B = gps.size();
+  std::vector<FitRun> runs(B);
+  std::vector<double> hs(6 * B, 0.0);
+  FitDrive d;
+  d.evals.resize(B); d.rested.assign(B, 0);
+  for (size_t b = 0; b < B; ++b) { runs[b].bind(&hs[6 * b]); if (start[b]) runs[b].init(start[b]); }
+  const int rc = fit_rounds(runs, gps[0].n, [&](const std::vector<const double*>& th, int* st) {
+    ++d.rounds;
+    for (size_t b = 0; b < B; ++b) {
+      const FitRun& r = runs[b];
+      if (!th[b]) { CHECK(r.state == FitRun::OUT, "run %zu: no theta but not out", b); continue; }
+      const bool resting = r.state == FitRun::RESTING;
+      if (resting) {                                                         // rides along at its result
+        CHECK(std::memcmp(th[b], r.xr, sizeof(r.xr)) == 0, "run %zu rests away from its result", b);
+        ++d.rested[b];
+      } else {
+        d.evals[b].insert(d.evals[b].end(), th[b], th[b] + 3);
+      }
+      const bool fail = !resting && fail_at[b] > 0 && (int)d.evals[b].size() / 3 == fail_at[b];
+      st[b] = !fail && tiny_gp_sums(gps[b], th[b], &hs[6 * b]) ? PCABO_OK : PCABO_ERR_NOT_PD;
+    }
+    return (int)PCABO_OK;
+  });
+  CHECK(rc == PCABO_OK, "fit_rounds: %d", rc);
+  for (const FitRun& r : runs) {
+    CHECK(r.state == FitRun::RESTING || r.state == FitRun::OUT, "a run is still stepping after the rounds");
+    d.out.push_back(fit_out(r));
+  }
+  return d;
+}
+
+void test_fit_run() {
+  // (0) mll_assemble's gradient belongs to its loss: central differences over the dense GP, step 1e-6 (times theta for s2).
+  // Truncation ~ step^2 f''' / 6 and rounding ~ 1e-16 |f| / step both stay below 1e-8 here; the bound asked is 1e-6 (1 + |g|).
+  {
+    const TinyGP gp = tiny_gp(3);
+    const double th[3] = {0.02, 0.15, -0.4};
+    double h[6], f = 0.0, g[3], worst = 0.0;
+    CHECK(tiny_gp_sums(gp, th, h), "the dense GP could not be factored");
+    mll_assemble(h, gp.n, th, &f, g);
+    for (int i = 0; i < 3; ++i) {
+      const double step = i == 0 ? 1e-6 * th[0] : 1e-6;
+      double tp[3] = {th[0], th[1], th[2]}, tm[3] = {th[0], th[1], th[2]}, fp = 0.0, fm = 0.0;
+      tp[i] += step; tm[i] -= step;
+      CHECK(tiny_gp_sums(gp, tp, h), "factor"); mll_assemble(h, gp.n, tp, &fp, nullptr);
+      CHECK(tiny_gp_sums(gp, tm, h), "factor"); mll_assemble(h, gp.n, tm, &fm, nullptr);
+      const double fd = (fp - fm) / (tp[i] - tm[i]), err = std::fabs(fd - g[i]) / (1.0 + std::fabs(g[i]));
+      if (err > worst) worst = err;
+      CHECK(err < 1e-6, "gradient %d: %.12g against the difference quotient %.12g", i, g[i], fd);
+    }
+    std::printf("mll_assemble against central differences: worst %.2e (bound 1e-6)\n", worst);
+  }
+  // (a) B runs in lock-step = every run alone: theta, loss, info bit for bit; finished runs ride along at their result and are
+  // not counted
+  const int B = 5;
+  std::vector<TinyGP> gps;
+  for (int b = 0; b < B; ++b) gps.push_back(tiny_gp(10 + b));
+  const FitDrive all = drive_fits(gps, std::vector<const double*>(B, FIT_START), std::vector<int>(B, 0));
+  int rested = 0, nfev_min = 1 << 30, nfev_max = 0;
+  for (int b = 0; b < B; ++b) {
+    const FitDrive one = drive_fits({gps[b]}, {FIT_START}, {0});
+    CHECK(all.out[b].status == PCABO_OK && all.out[b].info[0] > 2, "run %d: status %d after %d iterations", b, all.out[b].status, all.out[b].info[0]);
+    CHECK(std::memcmp(&all.out[b], &one.out[0], sizeof(FitOut)) == 0, "run %d in lock-step differs from the run alone", b);
+    CHECK(all.evals[b] == one.evals[0], "run %d was evaluated at other points in lock-step", b);
+    CHECK(all.out[b].info[1] <= (int)all.evals[b].size() / 3, "run %d counts %d evaluations of %zu", b, all.out[b].info[1], all.evals[b].size() / 3);
+    CHECK(one.rested[0] == 0 && one.rounds == (int)one.evals[0].size() / 3, "a run alone took a round without an evaluation");
+    rested += all.rested[b];
+    nfev_min = std::min(nfev_min, all.out[b].info[1]); nfev_max = std::max(nfev_max, all.out[b].info[1]);
+  }
+  CHECK(nfev_min < nfev_max && rested > 0, "no run finished before another (evaluations %d .. %d): nothing rode along", nfev_min, nfev_max);
+  {                                                        // a parked run (never started) stays out and is never evaluated
+    const FitDrive d = drive_fits({gps[0], gps[1]}, {nullptr, FIT_START}, {0, 0});
+    CHECK(d.out[0].status == PCABO_ERR_ARG && d.evals[0].empty(), "a parked run was stepped");
+    CHECK(std::memcmp(&d.out[1], &all.out[1], sizeof(FitOut)) == 0, "a run beside a parked run differs from the run alone");
+  }
+  // (b) PCABO_ERR_NOT_PD at evaluation e of run 0, for every e, run 1 beside it undisturbed: the fit stops at the last accepted
+  // iterate (warnflag 2, task NOT_PD) and asks for one more evaluation THERE - also when that iterate was the last point
+  // evaluated (the failing trial was the first of its line search).  At e = 1 (the start) the run fails.
+  const int total = (int)all.evals[0].size() / 3;
+  int end_at_last_evaluated = 0;
+  for (int e = 1; e <= total; ++e) {
+    const FitDrive d = drive_fits({gps[0], gps[1]}, {FIT_START, FIT_START}, {e, 0});
+    CHECK(std::memcmp(&d.out[1], &all.out[1], sizeof(FitOut)) == 0, "failure %d of run 0 disturbed run 1", e);
+    const FitOut& o = d.out[0];
+    const std::vector<double>& ev = d.evals[0];
+    if (e == 1) { CHECK(o.status == PCABO_ERR_NOT_PD && ev.size() == 3, "start not factored: status %d", o.status); continue; }
+    CHECK(o.status == PCABO_OK && o.info[2] == 2 && o.info[3] == PCABO_FIT_TASK_NOT_PD, "failure %d: status %d warnflag %d task %d", e, o.status, o.info[2], o.info[3]);
+    CHECK(o.info[1] == e - 1, "failure %d: %d evaluations counted", e, o.info[1]);
+    CHECK((int)ev.size() / 3 == e + 1 && std::memcmp(&ev[3 * e], o.theta, sizeof(o.theta)) == 0, "failure %d: no evaluation at the result behind it", e);
+    bool evaluated = false;                                // the result is a point the run had evaluated
+    for (int i = 0; i < e - 1; ++i) evaluated = evaluated || std::memcmp(&ev[3 * i], o.theta, sizeof(o.theta)) == 0;
+    CHECK(evaluated, "failure %d: the result was never evaluated", e);
+    if (std::memcmp(&ev[3 * (e - 2)], o.theta, sizeof(o.theta)) == 0) ++end_at_last_evaluated;
+    double h[6], f = 0.0;
+    CHECK(tiny_gp_sums(gps[0], o.theta, h), "factor"); mll_assemble(h, gps[0].n, o.theta, &f, nullptr);
+    CHECK(f == o.loss, "failure %d: the loss is not the one at the result", e);
+  }
+  CHECK(end_at_last_evaluated > 0, "no failure met the first trial of a line search");
+  // (c) a trial theta outside the model's domain.  The sums of a loss that falls linearly in rho (slope G, no pull on s2 and c):
+  // after the first iteration the line search keeps extrapolating (rho = -1, -3, -11, ... -683) until softplus(rho) underflows to
+  // 0 - the fit stops at the last accepted iterate, task DOMAIN, and is evaluated once more there.  A start out there is the run's
+  // error, PCABO_ERR_ARG, and nothing is evaluated.
+  {
+    std::vector<FitRun> run(1);
+    double h[6] = {0, 0, 0, 0, 0, 0};
+    int evals = 0;
+    std::vector<double> rhos;
+    const int n = 12;
+    const double G = 0.5;
+    const auto linear = [&](const std::vector<const double*>& th, int* st) {
+      const double s2 = th[0][0], rho = th[0][2], u = std::log(s2) + 4.0;
+      CHECK(mll_theta_ok(th[0]), "asked to evaluate a theta outside the domain");
+      h[1] = 2.0 * n * G * rho; h[5] = -2.0 * n * G * softplus_host(rho) * (1.0 + std::exp(-rho)); h[3] = 2.0 * (1.0 + u) / s2;
+      ++evals; rhos.push_back(rho); st[0] = PCABO_OK;
+      return (int)PCABO_OK;
+    };
+    run[0].bind(h); run[0].init(FIT_START);
+    CHECK(fit_rounds(run, n, linear) == PCABO_OK, "fit_rounds");
+    const FitOut o = fit_out(run[0]);
+    CHECK(o.status == PCABO_OK && o.info[2] == 2 && o.info[3] == PCABO_FIT_TASK_DOMAIN, "domain stop: status %d warnflag %d task %d", o.status, o.info[2], o.info[3]);
+    CHECK(o.info[0] >= 1 && evals == o.info[1] + 1 && evals > 3, "domain stop: %d iterations, %d evaluations, %d counted", o.info[0], evals, o.info[1]);
+    CHECK(rhos.back() == o.theta[2] && rhos[evals - 2] < -600.0 && std::count(rhos.begin(), rhos.end(), o.theta[2]) == 2,
+          "domain stop: the result rho %g is not an earlier iterate evaluated again at the end (last trial %g)", o.theta[2], rhos[evals - 2]);
+    const double far[3] = {FIT_START[0], 0.0, -800.0};
+    evals = 0;
+    run[0].init(far);
+    CHECK(fit_rounds(run, n, linear) == PCABO_OK, "fit_rounds");
+    CHECK(run[0].status == PCABO_ERR_ARG && run[0].state == FitRun::OUT && evals == 0, "start outside the domain: status %d, %d evaluations", run[0].status, evals);
+  }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -332,6 +535,7 @@ int main(int argc, char** argv) {
   test_torch_rng();
   test_plan();
   test_restart_group();
+  test_fit_run();
   test_gang_pool(1, 3);
   test_gang_pool(workers, 11);
   if (g_fail) { std::fprintf(stderr, "host selftest: %d check(s) failed\n", g_fail); return 1; }

@@ -1,12 +1,14 @@
 // Host-side pieces of the optimisers that need no HIP: the restart group (a joint problem on LbfgsbDriver, csrc/lbfgsb.h), the
-// restart groups of one run and the round loop over several runs, and the worker pool of a batch.  Included by pcabo_api.hip (the
-// product) and by host_selftest.cpp (the sanitizer builds of the Makefile: `make asan ubsan tsan` compile this header, lbfgsb.cpp
-// and host_entry.cpp with g++ and run them without a GPU).
+// restart groups of one run and the round loop over several runs, the GP hyperparameter fit of one run (FitRun) and the lock-step
+// rounds over several (fit_rounds), and the worker pool of a batch.  Included by pcabo_api.hip (the product) and by
+// host_selftest.cpp (the sanitizer builds of the Makefile: `make asan ubsan tsan` compile this header, lbfgsb.cpp and
+// host_entry.cpp with g++ and run them without a GPU).
 #pragma once
 #include "../../include/pcabo.h"
 #include "lbfgsb.h"
 
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
@@ -121,6 +123,118 @@ int run_rounds(RunRestarts* runs, const std::vector<int>& order, Stage&& stage, 
     if (rc != PCABO_OK) return rc;
     for (auto& pe : pend)
       if (!pe.second->absorb(pe.first->val, pe.first->grad, pe.second->q0)) pe.first->status = PCABO_ERR_NAN;
+  }
+}
+
+// ---- GP hyperparameter fit (DESIGN.md "GP hyperparameter fit") ---------------------------------------------------------------
+// theta = {noise s2, mean constant c, raw lengthscale rho}; lengthscale = softplus(rho) as torch computes it (threshold 20).
+inline double softplus_host(double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); }
+inline bool mll_theta_ok(const double* theta) {
+  const double s2 = theta[0], c = theta[1], ls = softplus_host(theta[2]);
+  return s2 > 0.0 && std::isfinite(s2) && std::isfinite(c) && ls > 0.0 && std::isfinite(ls);
+}
+// Loss and gradient of one evaluation, assembled on the host (the prior on s2 and the chain rule through softplus are host
+// arithmetic): h = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, sum W dK/dlog l} of a state conditioned at theta
+inline void mll_assemble(const double* h, int n, const double* theta, double* loss, double* grad) {
+  const double s2 = theta[0], rho = theta[2];
+  const double ls = softplus_host(rho);
+  const double LOG2PI = 1.8378770664093453;
+  const double lnz = std::log(s2), u = lnz + 4.0;
+  const double log_n = -0.5 * h[1] - h[0] - 0.5 * n * LOG2PI;
+  const double log_prior = -lnz - 0.5 * LOG2PI - 0.5 * u * u;              // LogNormal(-4, 1) at s2
+  *loss = -(log_n + log_prior) / n;
+  if (grad) {
+    const double sig = 1.0 / (1.0 + std::exp(-rho));                       // d softplus / d rho
+    grad[0] = -((0.5 * (h[3] - h[4])) + (-1.0 - u) / s2) / n;
+    grad[1] = -h[2] / n;
+    grad[2] = -(0.5 * h[5] * sig / ls) / n;
+  }
+}
+
+// The fit of one run: scipy.optimize.minimize(method="L-BFGS-B") with its defaults (LbfgsbDriver: the start clipped into the box,
+// scipy's memoisation of the last point, its limits) and the rules around it.  A run is STEPPING (its driver asks for evaluations),
+// at its END point (one more evaluation: the result is not the last point evaluated), RESTING at its result, or OUT (never
+// started, or failed: status says why).  A trial theta outside the model's domain (a line-search step so long that softplus(rho)
+// underflows to 0, a non-finite value) and one the factorisation cannot take end the fit abnormally at the last accepted iterate
+// (warnflag 2, task PCABO_FIT_TASK_*); when that theta is the start itself the run fails (PCABO_ERR_ARG / PCABO_ERR_NOT_PD).
+struct FitRun {
+  enum { STEPPING, END, RESTING, OUT };
+  LbfgsbDriver fit;
+  int state = OUT, status = PCABO_ERR_ARG, stop_task = 0;
+  double xr[3] = {0, 0, 0}, fr = 0.0;  // the result and the loss there
+  const double* h = nullptr;           // where the evaluator leaves the six sums of this run (bind)
+  void bind(const double* h_) { h = h_; }
+  void init(const double* theta0) {
+    const double lower[3] = {1e-4, -INFINITY, -INFINITY}, upper[3] = {INFINITY, INFINITY, INFINITY};
+    fit.keep_accepted = true;                            // scipy's defaults and limits, the published order
+    fit.init(3, theta0, lower, upper);
+    state = STEPPING; status = PCABO_OK; stop_task = 0;
+  }
+  // The theta to evaluate next, or null: the run has its result, or is out.
+  const double* next() {
+    if (state == STEPPING && !fit.advance()) finish();
+    if (state == STEPPING && !mll_theta_ok(fit.x.data())) {
+      if (fit.have_cache) { stop_task = PCABO_FIT_TASK_DOMAIN; finish(); }
+      else { state = OUT; status = PCABO_ERR_ARG; }      // (the start itself)
+    }
+    return state == STEPPING ? fit.x.data() : (state == END ? xr : nullptr);
+  }
+  // Where a run that wants no evaluation rides along in a lock-step round: at its result, or null (out: the shared model)
+  const double* rest() const { return state == RESTING ? xr : nullptr; }
+  // The outcome of evaluating the theta handed out last (next() or rest()): st, and on PCABO_OK the six sums in h
+  void took(int st, int n) {
+    if (state == OUT) return;
+    if (state == STEPPING && st == PCABO_ERR_NOT_PD && fit.have_cache) {   // a trial theta, not the start: stop, keep the last iterate
+      stop_task = PCABO_FIT_TASK_NOT_PD;
+      finish();
+      return;
+    }
+    if (st != PCABO_OK) { state = OUT; status = st; return; }
+    if (state == STEPPING) {
+      double f = 0.0;
+      mll_assemble(h, n, fit.x.data(), &f, fit.g.data());
+      fit.absorb(f);
+    } else if (state == END) {
+      mll_assemble(h, n, xr, &fr, nullptr);
+      state = RESTING;
+    }
+  }
+  // niter, nfev, warnflag, task of a run whose status is PCABO_OK
+  void report(int* info) const {
+    info[0] = fit.niter; info[1] = fit.nfev;
+    info[2] = stop_task ? 2 : fit.opt.warnflag();
+    info[3] = stop_task ? stop_task : fit.opt.task();
+  }
+
+ private:
+  // the optimiser has stopped (it restores the last iterate itself) or met a theta it cannot take (the last accepted iterate):
+  // the state is left conditioned at the result, so one more evaluation unless the result is the last point evaluated (after a
+  // NOT_PD stop in any case: the state holds the trial theta's failed factorisation)
+  void finish() {
+    std::memcpy(xr, stop_task ? fit.xacc.data() : fit.x.data(), sizeof(xr));
+    fr = fit.fc;
+    state = (stop_task == PCABO_FIT_TASK_NOT_PD || !fit.have_cache || std::memcmp(xr, fit.xc.data(), sizeof(xr)) != 0) ? END : RESTING;
+  }
+};
+
+// The rounds of the runs' fits in lock-step until no run wants an evaluation: eval(th, st) evaluates run b at th[b] (null: a run
+// that is out), leaves its six sums where the run was bound and its outcome in st[b], and returns PCABO_OK or an error, which
+// ends the rounds and is returned.  n: the number of training points of every run.
+template <class Eval>
+int fit_rounds(std::vector<FitRun>& runs, int n, Eval&& eval) {
+  std::vector<const double*> th(runs.size(), nullptr);
+  std::vector<int> st(runs.size(), PCABO_OK);
+  for (;;) {
+    int pending = 0;
+    for (size_t b = 0; b < runs.size(); ++b) {
+      const double* t = runs[b].next();
+      if (t) ++pending;
+      th[b] = t ? t : runs[b].rest();
+    }
+    if (pending == 0) return PCABO_OK;
+    const int rc = eval(th, st.data());
+    if (rc != PCABO_OK) return rc;
+    for (size_t b = 0; b < runs.size(); ++b) runs[b].took(st[b], n);
   }
 }
 

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <optional>
 #include <vector>
 #include <dirent.h>
 #include <fcntl.h>
@@ -495,6 +496,99 @@ static bool ctx_sizes_ok(int max_n, int max_d, int max_q) {
   return max_n >= 2 && max_d >= 1 && max_d <= PCABO_MAXD && max_q >= 1 && max_q < PCABO_CNT_DONE;
 }
 
+// ---- rows D-H: ONE launch sequence for a single context and for the B runs of a batch -----------------------------------
+// ctx = the context, or run 0 of a batch with zb = its strides (blockIdx.z = run).  phase(1..4) is called at the four cuts of the
+// sequence - before k_zstats, before the Cholesky, before the root inverse, behind alpha - and returns PCABO_OK (0) or an error that
+// ends the sequence: a caller puts there what it has at that place in stream order (its profiling marks; behind alpha the launches
+// that go in front of the copy of chol_info).  Errors are left in ctx.
+struct RowsDH {
+  const double *Z, *y, *unb;             // the points, the targets, the user's Normalize bounds (or null) on the device
+  int n, k, KP; const int* k_dev;        // k and KP by value, or k_dev: read on the device
+  double inv_ls, noise, mean_c; int kernel;   // by value (zero where zb.hyp carries every run's own)
+  ZB zb;
+  hipEvent_t ev[2];                      // recorded behind k_zstats (null: none): the search box is on its way to the host
+  int* cnt_S; bool* cnt_dirty;           // the owner's ticket state (null: the tickets are left alone)
+};
+template <class Phase>
+static int enqueue_factor(pcabo_ctx* ctx, hipStream_t s, int n, int NP, ZB zb, Phase&& phase) {
+  if (const int rc = phase(2)) return rc;
+  if (launch_cholesky(s, ctx->dL, NP, ctx->ld, ctx->dInfo, ctx->dDiag, zb) != 0)
+    return set_err(ctx, PCABO_ERR_HIP, "the Cholesky launches could not be set up (device or kernel attribute)%s", "");
+  if (const int rc = phase(3)) return rc;
+  launch_trinv(s, ctx->dL, NP, ctx->ld, ctx->dR, zb);
+  launch_alpha(s, ctx->dR, ctx->dYs, n, NP, ctx->ld, ctx->dTmp, ctx->dAlpha, zb);
+  if (const int rc = phase(4)) return rc;
+  if (zb.zs) HIPCHK(hipMemcpy2DAsync((void*)&ctx->hm->chol_info, zb.hzs, ctx->dInfo, zb.zs, sizeof(int), zb.B, hipMemcpyDeviceToHost, s));
+  else HIPCHK(hipMemcpyAsync((void*)&ctx->hm->chol_info, ctx->dInfo, sizeof(int), hipMemcpyDeviceToHost, s));
+  return PCABO_OK;
+}
+template <class Phase>
+static int enqueue_rows_dh(pcabo_ctx* ctx, hipStream_t s, const RowsDH& a, Phase&& phase) {
+  const int NP = round_up(a.n, PCABO_BS);
+  // the per-query tickets count modulo the number of slab groups: they only need a reset when that number changes
+  // (every 64th iteration) or after a launch that did not complete
+  if (a.cnt_S && (acq_slabs(NP) != *a.cnt_S || *a.cnt_dirty)) {
+    if (a.zb.zs) HIPCHK(hipMemset2DAsync(ctx->dCounters, a.zb.zs, 0, (PCABO_CNT_DONE + 1) * sizeof(unsigned int), a.zb.B, s));
+    else HIPCHK(hipMemsetAsync(ctx->dCounters, 0, (PCABO_CNT_DONE + 1) * sizeof(unsigned int), s));
+    *a.cnt_S = acq_slabs(NP); *a.cnt_dirty = false;
+  }
+  if (const int rc = phase(1)) return rc;
+  launch_zstats(s, a.Z, a.y, a.n, a.k, a.unb, ctx->dBounds4, ctx->dZnMean, ctx->dYstats, ctx->dYs, ctx->hm, a.k_dev, a.zb, a.mean_c);
+  for (hipEvent_t e : a.ev) if (e) HIPCHK(hipEventRecord(e, s));
+  launch_znorm(s, a.Z, a.n, a.k, NP, a.KP, ctx->ld, ctx->dBounds4, ctx->dZnMean, a.inv_ls, ctx->dZnT, ctx->dAT, ctx->dNrm, a.k_dev, a.zb);
+  launch_gram(s, ctx->dAT, ctx->dNrm, a.n, NP, a.KP, ctx->ld, a.noise, a.kernel, nullptr, a.k_dev, ctx->dL, ctx->dInfo, a.zb);
+  return enqueue_factor(ctx, s, a.n, NP, a.zb, phase);
+}
+
+// The single context's profile groups over those phases: 1 Normalize + Gram, 2 Cholesky, 3 root inverse + alpha (kk: the reduced
+// dimension of group 1's work model).  Unprofiled, no event is recorded.
+struct CondProf {
+  pcabo_ctx* c; int kk;
+  std::optional<ProfScope> ps;
+  int operator()(int phase) {
+    const double n = c->n;
+    ps.reset();
+    if (phase == 1) ps.emplace(c, 1, 8.0 * n * kk + 4.0 * n * (n + 1.0), 2.0 * n * n * kk + 12.0 * n * n);
+    if (phase == 2) ps.emplace(c, 2, 16.0 * n * n, n * n * n / 3.0);
+    if (phase == 3) ps.emplace(c, 3, 16.0 * n * n, n * n * n / 3.0 + 2.0 * n * n);
+    return PCABO_OK;
+  }
+};
+
+static int launch_factorisation(pcabo_ctx* ctx, double jitter) {
+  hipStream_t s = ctx->stream;
+  if (jitter > 0.0) {      // a retry: K is built again (same kernel, same bits, flag cleared), then the jitter goes on its diagonal
+    launch_gram(s, ctx->dAT, ctx->dNrm, ctx->n, ctx->NP, round_up(ctx->k, 4), ctx->ld, ctx->noise, ctx->kernel, nullptr, nullptr,
+                ctx->dL, ctx->dInfo);
+    launch_add_jitter(s, ctx->dL, ctx->n, ctx->ld, jitter);
+  }
+  return enqueue_factor(ctx, s, ctx->n, ctx->NP, ZB(), CondProf{ctx, 0});
+}
+
+// psd_safe_cholesky's ladder for one context from `attempt` on (jitter 0, 1e-8, 1e-7, 1e-6).  Attempt 0 finds its factorisation
+// already on the stream; a later one redoes it with that attempt's jitter.  Each attempt: extra() (launches the caller wants behind
+// the factorisation; PCABO_OK or an error), one wait, the look at chol_info.  PCABO_OK, PCABO_ERR_NOT_PD or the launch / HIP error.
+template <class Extra>
+static int factor_attempts(pcabo_ctx* ctx, int attempt, Extra&& extra) {
+  double jitter = 1e-8;
+  for (int a = 2; a <= attempt; ++a) jitter *= 10.0;
+  for (;; ++attempt) {
+    if (attempt > 0) {
+      const int rc = launch_factorisation(ctx, jitter);
+      if (rc != PCABO_OK) return rc;
+      jitter *= 10.0;
+    }
+    const int rc = extra();
+    if (rc != PCABO_OK) return rc;
+    HIPCHK(wait_stream(ctx->stream));
+    HIPCHK(hipGetLastError());
+    if (ctx->hm->chol_info == 0) return PCABO_OK;
+    if (attempt == 3)
+      return set_err(ctx, PCABO_ERR_NOT_PD, "K + s2 I not positive definite after jitter retries (pivot %s%d)", "", ctx->hm->chol_info);
+  }
+}
+static int factor_attempts(pcabo_ctx* ctx, int attempt) { return factor_attempts(ctx, attempt, [] { return (int)PCABO_OK; }); }
+
 extern "C" {
 
 int pcabo_ctx_create(int device, int max_n, int max_d, int max_q, pcabo_ctx** out) {
@@ -655,55 +749,33 @@ int pcabo_wpca(pcabo_ctx* ctx, const double* X, const double* f, const int64_t* 
   return PCABO_OK;
 }
 
-static int launch_factorisation(pcabo_ctx* ctx, double jitter) {
-  hipStream_t s = ctx->stream;
-  if (jitter > 0.0) {      // a retry: K is built again (same kernel, same bits, flag cleared), then the jitter goes on its diagonal
-    launch_gram(s, ctx->dAT, ctx->dNrm, ctx->n, ctx->NP, round_up(ctx->k, 4), ctx->ld, ctx->noise, ctx->kernel, nullptr, nullptr,
-                ctx->dL, ctx->dInfo);
-    launch_add_jitter(s, ctx->dL, ctx->n, ctx->ld, jitter);
-  }
-  {
-    ProfScope ps(ctx, 2, 16.0 * ctx->n * ctx->n, (double)ctx->n * ctx->n * ctx->n / 3.0);
-    if (launch_cholesky(s, ctx->dL, ctx->NP, ctx->ld, ctx->dInfo, ctx->dDiag) != 0)
-      return set_err(ctx, PCABO_ERR_HIP, "the Cholesky launches could not be set up (device or kernel attribute)%s", "");
-  }
-  {
-    ProfScope ps(ctx, 3, 16.0 * ctx->n * ctx->n, (double)ctx->n * ctx->n * ctx->n / 3.0 + 2.0 * ctx->n * ctx->n);
-    launch_trinv(s, ctx->dL, ctx->NP, ctx->ld, ctx->dR);
-    launch_alpha(s, ctx->dR, ctx->dYs, ctx->n, ctx->NP, ctx->ld, ctx->dTmp, ctx->dAlpha);
-  }
-  HIPCHK(hipMemcpyAsync((void*)&ctx->hm->chol_info, ctx->dInfo, sizeof(int), hipMemcpyDeviceToHost, s));
-  return PCABO_OK;
-}
-
 // Rows D-H on the stream, inputs on the device.  k < 0: the reduced dimension is still on its way (the launches sit
 // right behind the wPCA) - the three kernels that need it read it from ctx->dK.
 static int enqueue_condition(pcabo_ctx* ctx, const double* y_dev, int n, int k, const double* unb, double lengthscale,
                              double noise, int kernel, double mean_c = 0.0) {
-  hipStream_t s = ctx->stream;
-  const int* k_dev = k < 0 ? ctx->dK : nullptr;
-  const int kk = k < 0 ? ctx->max_d : k;              // work model only
   ctx->n = n;
   ctx->NP = round_up(n, PCABO_BS);
   if (k >= 0) { ctx->k = k; ctx->KP = round_up(k, 4); }
   ctx->lengthscale = lengthscale; ctx->noise = noise; ctx->kernel = kernel;
   ctx->have_gp = false;
   ctx->gp_pending = true;
-  // the per-query tickets count modulo the number of slab groups: they only need a reset when that number changes
-  // (every 64th iteration) or after a launch that did not complete
-  if (acq_slabs(ctx->NP) != ctx->cnt_S || ctx->cnt_dirty) {
-    HIPCHK(hipMemsetAsync(ctx->dCounters, 0, (PCABO_CNT_DONE + 1) * sizeof(unsigned int), s));
-    ctx->cnt_S = acq_slabs(ctx->NP); ctx->cnt_dirty = false;
+  const RowsDH a{ctx->dZ, y_dev, unb, n, k, ctx->KP, k < 0 ? ctx->dK : nullptr, 1.0 / lengthscale, noise, mean_c, kernel, ZB(),
+                 {ctx->evBounds, nullptr}, &ctx->cnt_S, &ctx->cnt_dirty};
+  return enqueue_rows_dh(ctx, ctx->stream, a, CondProf{ctx, k < 0 ? ctx->max_d : k});   // asynchronous: pcabo_gp_condition_end() waits and checks
+}
+
+// Z (or NULL: the projection a matching pcabo_wpca left in dZ), y and the user's Normalize bounds onto the device; *unb = the
+// device copy of the bounds or NULL
+static int stage_gp_inputs(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, const double** unb) {
+  HIPCHK(hipSetDevice(ctx->device));
+  if (Z) STAGE_IN(ctx->dZ, Z, (size_t)n * k, double);
+  STAGE_IN(ctx->dY, y, n, double);
+  *unb = nullptr;
+  if (norm_bounds) {
+    HIPCHK(hipMemcpyAsync(ctx->dUserNB, norm_bounds, (size_t)2 * k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    *unb = ctx->dUserNB;
   }
-  {
-    ProfScope ps(ctx, 1, 8.0 * n * kk + 4.0 * n * (n + 1.0), 2.0 * n * n * kk + 12.0 * n * n);
-    launch_zstats(s, ctx->dZ, y_dev, n, k, unb, ctx->dBounds4, ctx->dZnMean, ctx->dYstats, ctx->dYs, ctx->hm, k_dev, ZB(), mean_c);
-    HIPCHK(hipEventRecord(ctx->evBounds, s));
-    launch_znorm(s, ctx->dZ, n, k, ctx->NP, ctx->KP, ctx->ld, ctx->dBounds4, ctx->dZnMean, 1.0 / lengthscale, ctx->dZnT,
-                 ctx->dAT, ctx->dNrm, k_dev);
-    launch_gram(s, ctx->dAT, ctx->dNrm, n, ctx->NP, ctx->KP, ctx->ld, noise, kernel, nullptr, k_dev, ctx->dL, ctx->dInfo);
-  }
-  return launch_factorisation(ctx, 0.0);       // asynchronous: pcabo_gp_condition_end() waits and checks
+  return PCABO_OK;
 }
 
 static bool gp_args_ok(const pcabo_ctx* ctx, int n, double lengthscale, double noise, int kernel) {
@@ -718,15 +790,9 @@ int pcabo_gp_condition_begin(pcabo_ctx* ctx, const double* Z, const double* y, i
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition: bad argument or size beyond context capacity%s", "");
   if (!Z && (!ctx->have_wpca || ctx->n != n || ctx->k != k))
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition: Z == NULL needs a matching pcabo_wpca call first%s", "");
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  if (Z) STAGE_IN(ctx->dZ, Z, (size_t)n * k, double);
-  STAGE_IN(ctx->dY, y, n, double);
   const double* unb = nullptr;
-  if (norm_bounds) {
-    HIPCHK(hipMemcpyAsync(ctx->dUserNB, norm_bounds, (size_t)2 * k * sizeof(double), hipMemcpyHostToDevice, s));
-    unb = ctx->dUserNB;
-  }
+  const int rc = stage_gp_inputs(ctx, Z, y, n, k, norm_bounds, &unb);
+  if (rc != PCABO_OK) return rc;
   return enqueue_condition(ctx, ctx->dY, n, k, unb, lengthscale, noise, kernel);
 }
 
@@ -782,18 +848,9 @@ int pcabo_gp_condition_end(pcabo_ctx* ctx) {
   HIPCHK(hipSetDevice(ctx->device));
   if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
   ctx->gp_pending = false;
-  double jitter = 0.0;
-  for (int attempt = 0; attempt < 4; ++attempt) {       // psd_safe_cholesky: 0, 1e-8, 1e-7, 1e-6
-    HIPCHK(wait_stream(ctx->stream));
-    HIPCHK(hipGetLastError());
-    if (ctx->hm->chol_info == 0) { ctx->have_gp = true; return PCABO_OK; }
-    if (attempt == 3) break;
-    jitter = (attempt == 0) ? 1e-8 : jitter * 10.0;
-    int rc = launch_factorisation(ctx, jitter);
-    if (rc != PCABO_OK) return rc;
-  }
-  return set_err(ctx, PCABO_ERR_NOT_PD, "K + s2 I not positive definite after jitter retries (pivot %s%d)", "",
-                 ctx->hm->chol_info);
+  const int rc = factor_attempts(ctx, 0);
+  if (rc == PCABO_OK) ctx->have_gp = true;
+  return rc;
 }
 
 int pcabo_gp_condition(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds,
@@ -804,8 +861,8 @@ int pcabo_gp_condition(pcabo_ctx* ctx, const double* Z, const double* y, int n, 
 }
 
 // ---- opt-in GP hyperparameter fit (DESIGN.md "GP hyperparameter fit") -------------------------------------------
-// theta = {noise s2, mean constant c, raw lengthscale rho}; lengthscale = softplus(rho) as torch computes it (threshold 20).
-static double softplus_host(double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); }
+// theta = {noise s2, mean constant c, raw lengthscale rho}.  The host arithmetic of an evaluation (softplus_host, mll_theta_ok,
+// mll_assemble) and the rules of a fit (FitRun, fit_rounds) are in host_side.h, shared by the single context and the batch.
 
 // Inputs of a fit staged like pcabo_gp_condition_begin's; *unb = the device copy of the user's Normalize bounds or NULL.
 static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, const double* Z, const double* y, int n, int k,
@@ -818,78 +875,39 @@ static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, const double* Z, co
   if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
   if (!Z && (!ctx->have_wpca || ctx->n != n || ctx->k != k))
     return set_err(ctx, PCABO_ERR_ARG, "%s: Z == NULL needs a matching pcabo_wpca call first", who);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  if (Z) STAGE_IN(ctx->dZ, Z, (size_t)n * k, double);
-  STAGE_IN(ctx->dY, y, n, double);
-  *unb = nullptr;
-  if (norm_bounds) {
-    HIPCHK(hipMemcpyAsync(ctx->dUserNB, norm_bounds, (size_t)2 * k * sizeof(double), hipMemcpyHostToDevice, s));
-    *unb = ctx->dUserNB;
-  }
-  return PCABO_OK;
+  return stage_gp_inputs(ctx, Z, y, n, k, norm_bounds, unb);
 }
 
-// One evaluation: the conditioning at theta (k_zstats with the mean constant -> k_znorm -> k_gram -> Cholesky -> root inverse
-// -> alpha, the jitter retries of pcabo_gp_condition_end), k_mll_grad + k_mll_finish, one 48-byte copy and one wait per attempt.
-// Loss and gradient are assembled on the host: the prior on s2 and the chain rule through softplus are host arithmetic.
-// The three pieces below are shared by the single context (mll_eval) and the lock-step fit of a batch (batch_mll_round).
-static bool mll_theta_ok(const double* theta) {
-  const double s2 = theta[0], c = theta[1], ls = softplus_host(theta[2]);
-  return s2 > 0.0 && std::isfinite(s2) && std::isfinite(c) && ls > 0.0 && std::isfinite(ls);
-}
-
-// The attempts of one evaluation from `attempt` on (psd_safe_cholesky: 0, 1e-8, 1e-7, 1e-6).  Attempt 0 finds its
-// factorisation already on the stream; a later one redoes it with that attempt's jitter.  Each attempt: the likelihood
-// kernels, the copy of their 6 results, one wait.  A run of a batch whose lock-step round failed enters at attempt 1.
+// The attempts of one evaluation from `attempt` on (factor_attempts): each one runs the likelihood kernels behind its
+// factorisation and copies their 6 results (48 bytes) in front of its wait.  A run of a batch whose lock-step round failed enters
+// at attempt 1.
 static int mll_attempts(pcabo_ctx* ctx, int attempt) {
-  hipStream_t s = ctx->stream;
-  const int nb = ctx->NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
-  double* out = ctx->dMll + 2 * (size_t)tiles;
-  double jitter = 1e-8;
-  for (int a = 2; a <= attempt; ++a) jitter *= 10.0;
-  for (;; ++attempt) {
-    if (attempt > 0) {
-      const int rc = launch_factorisation(ctx, jitter);
-      if (rc != PCABO_OK) return rc;
-      jitter *= 10.0;
-    }
-    launch_mll_grad(s, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
+  const int rc = factor_attempts(ctx, attempt, [ctx]() -> int {
+    const int nb = ctx->NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
+    double* out = ctx->dMll + 2 * (size_t)tiles;
+    launch_mll_grad(ctx->stream, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
     HOST_OUT(ctx->hMll, out, 6, double);
-    HIPCHK(wait_stream(s));
-    HIPCHK(hipGetLastError());
-    if (ctx->hm->chol_info == 0) break;
-    if (attempt == 3)
-      return set_err(ctx, PCABO_ERR_NOT_PD, "K + s2 I not positive definite after jitter retries (pivot %s%d)", "", ctx->hm->chol_info);
-  }
-  ctx->have_gp = true;
-  return PCABO_OK;
+    return PCABO_OK;
+  });
+  if (rc == PCABO_OK) ctx->have_gp = true;
+  return rc;
 }
 
-// h = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, sum W dK/dlog l} of a state conditioned at theta
-static void mll_assemble(const double* h, int n, const double* theta, double* loss, double* grad) {
-  const double s2 = theta[0], rho = theta[2];
-  const double ls = softplus_host(rho);
-  const double LOG2PI = 1.8378770664093453;
-  const double lnz = std::log(s2), u = lnz + 4.0;
-  const double log_n = -0.5 * h[1] - h[0] - 0.5 * n * LOG2PI;
-  const double log_prior = -lnz - 0.5 * LOG2PI - 0.5 * u * u;              // LogNormal(-4, 1) at s2
-  *loss = -(log_n + log_prior) / n;
-  if (grad) {
-    const double sig = 1.0 / (1.0 + std::exp(-rho));                       // d softplus / d rho
-    grad[0] = -((0.5 * (h[3] - h[4])) + (-1.0 - u) / s2) / n;
-    grad[1] = -h[2] / n;
-    grad[2] = -(0.5 * h[5] * sig / ls) / n;
-  }
+// One evaluation at a theta inside the model's domain: the conditioning there (k_zstats with the mean constant -> k_znorm -> k_gram
+// -> Cholesky -> root inverse -> alpha), then mll_attempts; the 6 sums are left in ctx->hMll.
+static int mll_launch(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta) {
+  const int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, softplus_host(theta[2]), theta[0], PCABO_KERNEL_MATERN52, theta[1]);
+  if (rc != PCABO_OK) return rc;
+  ctx->gp_pending = false;
+  return mll_attempts(ctx, 0);
+}
+static int theta_domain_err(pcabo_ctx* ctx) {
+  return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
 }
 
 static int mll_eval(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta, double* loss, double* grad) {
-  if (!mll_theta_ok(theta))
-    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
-  int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, softplus_host(theta[2]), theta[0], PCABO_KERNEL_MATERN52, theta[1]);
-  if (rc != PCABO_OK) return rc;
-  ctx->gp_pending = false;
-  rc = mll_attempts(ctx, 0);
+  if (!mll_theta_ok(theta)) return theta_domain_err(ctx);
+  const int rc = mll_launch(ctx, n, k, unb, theta);
   if (rc != PCABO_OK) return rc;
   mll_assemble(ctx->hMll, n, theta, loss, grad);
   return PCABO_OK;
@@ -905,8 +923,8 @@ int pcabo_gp_mll(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k,
   return mll_eval(ctx, n, k, unb, theta, loss, grad);
 }
 
-// scipy.optimize.minimize(method="L-BFGS-B") with its defaults around mll_eval (LbfgsbDriver, as pcabo_lbfgsb_minimize: x0
-// clipped into the box, scipy's memoisation of the last point, its iteration / evaluation limits).
+// scipy.optimize.minimize(method="L-BFGS-B") with its defaults around mll_launch: one FitRun, every round one evaluation.  The
+// context is left conditioned at the result.
 int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
                  double* theta_inout, double* loss, int* info) {
   if (!ctx) return PCABO_ERR_ARG;
@@ -914,43 +932,16 @@ int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k,
   const double* unb = nullptr;
   int rc = stage_fit_inputs(ctx, "pcabo_gp_fit", Z, y, n, k, norm_bounds, kernel, &unb);
   if (rc != PCABO_OK) return rc;
-  const double lower[3] = {1e-4, -INFINITY, -INFINITY}, upper[3] = {INFINITY, INFINITY, INFINITY};
-  LbfgsbDriver fit;                                      // scipy's defaults and limits, the published order
-  fit.keep_accepted = true;
-  fit.init(3, theta_inout, lower, upper);
-  int stop_task = 0;                                     // PCABO_FIT_TASK_*: a trial theta ended the fit (abnormal, warnflag 2)
-  while (fit.advance()) {
-    double f = 0.0;
-    // a trial theta outside the model's domain (a line-search step so long that softplus(rho) underflows to 0, a non-finite
-    // value): like one the factorisation cannot take it ends the fit abnormally at the last accepted iterate
-    if (fit.have_cache && !mll_theta_ok(fit.x.data())) { stop_task = PCABO_FIT_TASK_DOMAIN; break; }
-    rc = mll_eval(ctx, n, k, unb, fit.x.data(), &f, fit.g.data());
-    if (rc == PCABO_ERR_NOT_PD) {                        // a trial theta the factorisation cannot take: stop, keep the last iterate
-      if (!fit.have_cache) return rc;                    // (not even the start)
-      stop_task = PCABO_FIT_TASK_NOT_PD;
-      break;
-    }
-    if (rc != PCABO_OK) return rc;
-    fit.absorb(f);
-  }
-  const bool not_pd = stop_task != 0;
-  // the result: where the optimiser ended (it restores the last iterate itself), after a NOT_PD stop the last accepted iterate.
-  // Leave the context conditioned there (it is conditioned at the last evaluated point) and report the loss there.
-  const double* xr = not_pd ? fit.xacc.data() : fit.x.data();
-  double fr = fit.fc;
-  // (after a NOT_PD stop the context holds the trial theta's failed factorisation: it is conditioned again in any case)
-  if (stop_task == PCABO_FIT_TASK_NOT_PD || !fit.have_cache || memcmp(xr, fit.xc.data(), 3 * sizeof(double)) != 0) {
-    double gr[3];
-    rc = mll_eval(ctx, n, k, unb, xr, &fr, gr);
-    if (rc != PCABO_OK) return rc;
-  }
-  memcpy(theta_inout, xr, 3 * sizeof(double));
-  if (loss) *loss = fr;
-  if (info) {
-    info[0] = fit.niter; info[1] = fit.nfev;
-    info[2] = not_pd ? 2 : fit.opt.warnflag();
-    info[3] = not_pd ? stop_task : fit.opt.task();
-  }
+  std::vector<FitRun> run(1);
+  run[0].init(theta_inout);
+  run[0].bind(ctx->hMll);
+  fit_rounds(run, n, [&](const std::vector<const double*>& th, int* st) { st[0] = mll_launch(ctx, n, k, unb, th[0]); return (int)PCABO_OK; });
+  const FitRun& r = run[0];
+  if (r.status == PCABO_ERR_ARG) return theta_domain_err(ctx);
+  if (r.status != PCABO_OK) return r.status;
+  memcpy(theta_inout, r.xr, sizeof(r.xr));
+  if (loss) *loss = r.fr;
+  if (info) r.report(info);
   return PCABO_OK;
 }
 
@@ -1539,6 +1530,39 @@ static void batch_free(pcabo_batch* batch) {
   delete batch;
 }
 
+// Rows D-H of all runs on the batch's stream behind whatever the caller has enqueued (enqueue_rows_dh with the batch's strides, k read
+// on the device, the batch's phase marks 1..4), the device optimiser's transposed root inverse behind alpha, and the batch's state
+// afterwards.  Z / y / unb: run 0's inputs on the device; k >= 0: the reduced dimension of every run, < 0: the wPCA in flight will say.
+static int batch_enqueue_condition(pcabo_batch* batch, const double* Z, const double* y, const double* unb, int n, int d, int k,
+                                   double lengthscale, double gp_noise, int kernel) {
+  pcabo_ctx* c0 = batch->ctx[0];
+  hipStream_t s = batch->stream;
+  const ZB zb = batch_zb(batch);
+  const int NP = round_up(n, PCABO_BS);
+  const RowsDH a{Z, y, unb, n, -1, 0, c0->dK, 1.0 / lengthscale, gp_noise, 0.0, kernel, zb,
+                 {batch->evBounds, k < 0 ? nullptr : batch->evPca}, &batch->cnt_S, &batch->cnt_dirty};
+  const int rc = enqueue_rows_dh(c0, s, a, [&](int phase) {
+    if (batch->prof) (void)hipEventRecord(batch->pev[phase], s);
+    // the device-resident optimiser reads the root inverse transposed as well (the Gram buffer is free: K is only kept on demand)
+    if (phase == 4 && batch->dev_lbfgsb) launch_rt_build(s, c0->dR, n, NP, c0->ld, c0->dGram, zb);
+    return (int)PCABO_OK;
+  });
+  if (rc != PCABO_OK) return bset_err(batch, rc, "%s", c0->err);
+  BHIPCHK(hipGetLastError());
+  batch->n = n; batch->d = d; batch->NP = NP;
+  batch->lengthscale = lengthscale; batch->noise = gp_noise; batch->kernel = kernel;
+  batch->wpca_uncollected = k < 0; batch->gp_pending = true; batch->have_gp = false;
+  batch->fitZ = Z; batch->fitY = y; batch->fitUnb = unb; batch->fitted = false;
+  for (pcabo_ctx* c : batch->ctx) {      // the per-run contexts see the same state (single-context calls keep working)
+    c->n = n; c->d = d; c->NP = NP; c->lengthscale = lengthscale; c->noise = gp_noise; c->kernel = kernel;
+    c->have_gp = false; c->have_wpca = false; c->gp_pending = false; c->wpca_uncollected = false;
+    if (k >= 0) { c->k = k; c->KP = round_up(k, 4); }
+    else { c->gcur = batch->gcur; c->dG = c->dGbuf[c->gcur]; c->vprev_d = d; }
+    c->cnt_S = batch->cnt_S; c->cnt_dirty = false;
+  }
+  return PCABO_OK;
+}
+
 extern "C" {
 
 int pcabo_batch_create(int device, int B, int max_n, int max_d, int max_q, pcabo_batch** out) {
@@ -1724,8 +1748,7 @@ int pcabo_batch_wpca_gp_condition_begin(pcabo_batch* batch, const double* X, con
   const double* inY = c0->dIn + off_y;
   const ZB zb = batch_zb(batch);
   const int DP = round_up(d, 16);
-  auto mark = [&](int i) { if (batch->prof) (void)hipEventRecord(batch->pev[i], s); };
-  mark(0);
+  if (batch->prof) (void)hipEventRecord(batch->pev[0], s);
   // rows A-C
   launch_wpca_prep(s, inX, inRanks, inNoise, n, d, DP, c0->dWeights, c0->dDataMean, c0->dPcaMean, c0->dWc, zb);
   launch_cov(s, c0->dWc, n, DP, c0->dC, zb);
@@ -1740,39 +1763,7 @@ int pcabo_batch_wpca_gp_condition_begin(pcabo_batch* batch, const double* X, con
                            ((size_t)3 * batch->max_d + (size_t)rcount * d) * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipEventRecord(batch->evPca, s));
   // rows D-H, queued behind the projection (k is read on the device)
-  const int NP = round_up(n, PCABO_BS);
-  if (acq_slabs(NP) != batch->cnt_S || batch->cnt_dirty) {
-    BHIPCHK(hipMemset2DAsync(c0->dCounters, batch->zs, 0, (PCABO_CNT_DONE + 1) * sizeof(unsigned int), B, s));
-    batch->cnt_S = acq_slabs(NP); batch->cnt_dirty = false;
-  }
-  mark(1);
-  launch_zstats(s, c0->dZ, inY, n, -1, nullptr, c0->dBounds4, c0->dZnMean, c0->dYstats, c0->dYs, c0->hm, c0->dK, zb);
-  BHIPCHK(hipEventRecord(batch->evBounds, s));
-  launch_znorm(s, c0->dZ, n, -1, NP, 0, c0->ld, c0->dBounds4, c0->dZnMean, 1.0 / lengthscale, c0->dZnT, c0->dAT, c0->dNrm,
-               c0->dK, zb);
-  launch_gram(s, c0->dAT, c0->dNrm, n, NP, 0, c0->ld, gp_noise, kernel, nullptr, c0->dK, c0->dL, c0->dInfo, zb);
-  mark(2);
-  launch_cholesky(s, c0->dL, NP, c0->ld, c0->dInfo, c0->dDiag, zb);
-  mark(3);
-  launch_trinv(s, c0->dL, NP, c0->ld, c0->dR, zb);
-  launch_alpha(s, c0->dR, c0->dYs, n, NP, c0->ld, c0->dTmp, c0->dAlpha, zb);
-  mark(4);
-  // the device-resident optimiser reads the root inverse transposed as well (the Gram buffer is free: K is only kept on demand)
-  if (batch->dev_lbfgsb) launch_rt_build(s, c0->dR, n, NP, c0->ld, c0->dGram, zb);
-  BHIPCHK(hipMemcpy2DAsync((void*)&c0->hm->chol_info, batch->hzs, c0->dInfo, batch->zs, sizeof(int), B, hipMemcpyDeviceToHost, s));
-  BHIPCHK(hipGetLastError());
-  batch->n = n; batch->d = d; batch->NP = NP;
-  batch->lengthscale = lengthscale; batch->noise = gp_noise; batch->kernel = kernel;
-  batch->wpca_uncollected = true; batch->gp_pending = true; batch->have_gp = false;
-  batch->fitZ = c0->dZ; batch->fitY = inY; batch->fitUnb = nullptr; batch->fitted = false;
-  for (int b = 0; b < B; ++b) {          // the per-run contexts see the same state (single-context calls keep working)
-    pcabo_ctx* c = batch->ctx[b];
-    c->n = n; c->d = d; c->NP = NP; c->lengthscale = lengthscale; c->noise = gp_noise; c->kernel = kernel;
-    c->have_gp = false; c->have_wpca = false; c->gp_pending = false; c->wpca_uncollected = false;
-    c->gcur = batch->gcur; c->dG = c->dGbuf[c->gcur]; c->vprev_d = d;
-    c->cnt_S = batch->cnt_S; c->cnt_dirty = false;
-  }
-  return PCABO_OK;
+  return batch_enqueue_condition(batch, c0->dZ, inY, nullptr, n, d, -1, lengthscale, gp_noise, kernel);
 }
 
 // Rows D-H for every run WITHOUT the weighted PCA: the GPs live on the given points (pcabo_gp_condition_begin for B runs; the
@@ -1804,42 +1795,8 @@ int pcabo_batch_gp_condition_begin(pcabo_batch* batch, const double* Z, const do
   BHIPCHK(hipMemcpy2DAsync(c0->dK, batch->zs, &c0->hm->k, batch->hzs, sizeof(int), B, hipMemcpyHostToDevice, s));
   if (norm_bounds)
     BHIPCHK(hipMemcpy2DAsync(c0->dUserNB, batch->zs, c0->hSmall, batch->hzs, (size_t)2 * k * sizeof(double), B, hipMemcpyHostToDevice, s));
-  const double* inZ = c0->dIn;
-  const double* inY = c0->dIn + off_y;
-  const ZB zb = batch_zb(batch);
-  auto mark = [&](int i) { if (batch->prof) (void)hipEventRecord(batch->pev[i], s); };
-  mark(0);
-  const int NP = round_up(n, PCABO_BS);
-  if (acq_slabs(NP) != batch->cnt_S || batch->cnt_dirty) {
-    BHIPCHK(hipMemset2DAsync(c0->dCounters, batch->zs, 0, (PCABO_CNT_DONE + 1) * sizeof(unsigned int), B, s));
-    batch->cnt_S = acq_slabs(NP); batch->cnt_dirty = false;
-  }
-  mark(1);
-  launch_zstats(s, inZ, inY, n, -1, norm_bounds ? c0->dUserNB : nullptr, c0->dBounds4, c0->dZnMean, c0->dYstats, c0->dYs, c0->hm, c0->dK, zb);
-  BHIPCHK(hipEventRecord(batch->evBounds, s));
-  BHIPCHK(hipEventRecord(batch->evPca, s));
-  launch_znorm(s, inZ, n, -1, NP, 0, c0->ld, c0->dBounds4, c0->dZnMean, 1.0 / lengthscale, c0->dZnT, c0->dAT, c0->dNrm, c0->dK, zb);
-  launch_gram(s, c0->dAT, c0->dNrm, n, NP, 0, c0->ld, gp_noise, kernel, nullptr, c0->dK, c0->dL, c0->dInfo, zb);
-  mark(2);
-  launch_cholesky(s, c0->dL, NP, c0->ld, c0->dInfo, c0->dDiag, zb);
-  mark(3);
-  launch_trinv(s, c0->dL, NP, c0->ld, c0->dR, zb);
-  launch_alpha(s, c0->dR, c0->dYs, n, NP, c0->ld, c0->dTmp, c0->dAlpha, zb);
-  mark(4);
-  if (batch->dev_lbfgsb) launch_rt_build(s, c0->dR, n, NP, c0->ld, c0->dGram, zb);
-  BHIPCHK(hipMemcpy2DAsync((void*)&c0->hm->chol_info, batch->hzs, c0->dInfo, batch->zs, sizeof(int), B, hipMemcpyDeviceToHost, s));
-  BHIPCHK(hipGetLastError());
-  batch->n = n; batch->d = k; batch->NP = NP;
-  batch->lengthscale = lengthscale; batch->noise = gp_noise; batch->kernel = kernel;
-  batch->wpca_uncollected = false; batch->gp_pending = true; batch->have_gp = false;
-  batch->fitZ = inZ; batch->fitY = inY; batch->fitUnb = norm_bounds ? c0->dUserNB : nullptr; batch->fitted = false;
-  for (int b = 0; b < B; ++b) {
-    pcabo_ctx* c = batch->ctx[b];
-    c->n = n; c->d = k; c->k = k; c->KP = round_up(k, 4); c->NP = NP; c->lengthscale = lengthscale; c->noise = gp_noise; c->kernel = kernel;
-    c->have_gp = false; c->have_wpca = false; c->gp_pending = false; c->wpca_uncollected = false;
-    c->cnt_S = batch->cnt_S; c->cnt_dirty = false;
-  }
-  return PCABO_OK;
+  if (batch->prof) (void)hipEventRecord(batch->pev[0], s);
+  return batch_enqueue_condition(batch, c0->dIn, c0->dIn + off_y, norm_bounds ? c0->dUserNB : nullptr, n, k, k, lengthscale, gp_noise, kernel);
 }
 
 int pcabo_batch_wpca_results(pcabo_batch* batch, double* data_mean, double* pca_mean, double* comps, double* evr, int* k) {
@@ -1932,18 +1889,17 @@ static int batch_mll_round(pcabo_batch* batch, const std::vector<const double*>&
   BHIPCHK(hipMemcpy2DAsync(c0->dHyp, batch->zs, c0->hHyp, batch->hzs, PCABO_HYP_WORDS * sizeof(double), B, hipMemcpyHostToDevice, s));
   ZB zb = batch_zb(batch);
   zb.hyp = c0->dHyp;
-  launch_zstats(s, batch->fitZ, batch->fitY, n, -1, batch->fitUnb, c0->dBounds4, c0->dZnMean, c0->dYstats, c0->dYs, c0->hm, c0->dK, zb);
-  launch_znorm(s, batch->fitZ, n, -1, NP, 0, c0->ld, c0->dBounds4, c0->dZnMean, 0.0, c0->dZnT, c0->dAT, c0->dNrm, c0->dK, zb);
-  launch_gram(s, c0->dAT, c0->dNrm, n, NP, 0, c0->ld, 0.0, batch->kernel, nullptr, c0->dK, c0->dL, c0->dInfo, zb);
-  if (launch_cholesky(s, c0->dL, NP, c0->ld, c0->dInfo, c0->dDiag, zb) != 0)
-    return bset_err(batch, PCABO_ERR_HIP, "the Cholesky launches could not be set up (device or kernel attribute)%s", "");
-  launch_trinv(s, c0->dL, NP, c0->ld, c0->dR, zb);
-  launch_alpha(s, c0->dR, c0->dYs, n, NP, c0->ld, c0->dTmp, c0->dAlpha, zb);
-  const int nb = NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
-  double* out = c0->dMll + 2 * (size_t)tiles;
-  launch_mll_grad(s, c0->dR, c0->dAT, c0->dNrm, c0->dAlpha, c0->dL, c0->dYs, n, NP, 0, c0->ld, c0->dMll, out, c0->dK, zb);
-  BHIPCHK(hipMemcpy2DAsync(c0->hMll, batch->hzs, out, batch->zs, 6 * sizeof(double), B, hipMemcpyDeviceToHost, s));
-  BHIPCHK(hipMemcpy2DAsync((void*)&c0->hm->chol_info, batch->hzs, c0->dInfo, batch->zs, sizeof(int), B, hipMemcpyDeviceToHost, s));
+  const RowsDH a{batch->fitZ, batch->fitY, batch->fitUnb, n, -1, 0, c0->dK, 0.0, 0.0, 0.0, batch->kernel, zb, {nullptr, nullptr}, nullptr, nullptr};
+  const int rc = enqueue_rows_dh(c0, s, a, [&](int phase) -> int {
+    if (phase != 4) return PCABO_OK;     // behind alpha: the likelihood kernels and the strided copy of the runs' 6 results
+    pcabo_ctx* ctx = c0;
+    const int nb = NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
+    double* out = c0->dMll + 2 * (size_t)tiles;
+    launch_mll_grad(s, c0->dR, c0->dAT, c0->dNrm, c0->dAlpha, c0->dL, c0->dYs, n, NP, 0, c0->ld, c0->dMll, out, c0->dK, zb);
+    HIPCHK(hipMemcpy2DAsync(c0->hMll, batch->hzs, out, batch->zs, 6 * sizeof(double), B, hipMemcpyDeviceToHost, s));
+    return PCABO_OK;
+  });
+  if (rc != PCABO_OK) return bset_err(batch, rc, "%s", c0->err);
   BHIPCHK(wait_stream(s));
   BHIPCHK(hipGetLastError());
   ++batch->fit_rounds;
@@ -1999,7 +1955,7 @@ int pcabo_batch_gp_mll(pcabo_batch* batch, const double* theta, double* loss, do
   for (int b = 0; b < B; ++b) {
     if (!act[b]) continue;
     if (mll_theta_ok(theta + 3 * b)) th[b] = theta + 3 * b;
-    else set_err(batch->ctx[b], PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
+    else theta_domain_err(batch->ctx[b]);
   }
   batch->fit_rounds = 0;
   rc = batch_mll_round(batch, th, st.data());
@@ -2022,88 +1978,28 @@ int pcabo_batch_gp_fit(pcabo_batch* batch, double* theta_inout, double* loss, in
   int rc = batch_fit_prepare(batch, "pcabo_batch_gp_fit", &act, status);
   if (rc != PCABO_OK) return rc;
   const int B = batch->B;
-  // a run is STEPPING (its driver asks for evaluations), at its END point (one more evaluation: the result is not the last point
-  // evaluated), RESTING at its result, or OUT (parked, or failed: it rests at the shared model)
-  enum { STEPPING, END, RESTING, OUT };
-  struct Run { LbfgsbDriver fit; int state = OUT, st = PCABO_ERR_ARG, stop_task = 0; double xr[3] = {0, 0, 0}, fr = 0.0; };
-  std::vector<Run> runs((size_t)B);
-  const double lower[3] = {1e-4, -INFINITY, -INFINITY}, upper[3] = {INFINITY, INFINITY, INFINITY};
+  std::vector<FitRun> runs((size_t)B);                   // (a parked run stays OUT: it rides along at the shared model)
   for (int b = 0; b < B; ++b) {
-    if (!act[b]) continue;
-    Run& r = runs[b];
-    r.fit.keep_accepted = true;                          // scipy's defaults and limits, the published order (as pcabo_gp_fit)
-    r.fit.init(3, theta_inout + 3 * b, lower, upper);
-    r.state = STEPPING; r.st = PCABO_OK;
+    runs[b].bind(batch->ctx[b]->hMll);
+    if (act[b]) runs[b].init(theta_inout + 3 * b);
   }
-  // the optimiser has stopped (or met a theta the factorisation cannot take): where does the run end?
-  auto finish = [&](Run& r) {
-    const double* xr = r.stop_task ? r.fit.xacc.data() : r.fit.x.data();
-    memcpy(r.xr, xr, sizeof(r.xr));
-    r.fr = r.fit.fc;
-    // (END after a NOT_PD stop in any case: the run's slab holds the trial theta's failed factorisation)
-    r.state = (r.stop_task == PCABO_FIT_TASK_NOT_PD || !r.fit.have_cache || memcmp(r.xr, r.fit.xc.data(), sizeof(r.xr)) != 0) ? END : RESTING;
-  };
-  std::vector<const double*> th((size_t)B, nullptr);
-  std::vector<int> st((size_t)B, PCABO_OK);
   batch->fit_rounds = 0;
-  for (;;) {
-    int pending = 0;
-    for (int b = 0; b < B; ++b) {
-      Run& r = runs[b];
-      if (r.state == STEPPING && !r.fit.advance()) finish(r);
-      if (r.state == STEPPING && !mll_theta_ok(r.fit.x.data())) {
-        if (r.fit.have_cache) {                          // a trial theta outside the model's domain: abnormal end, last accepted iterate
-          r.stop_task = PCABO_FIT_TASK_DOMAIN;
-          finish(r);
-        } else {                                         // (the start itself)
-          set_err(batch->ctx[b], PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
-          r.state = OUT; r.st = PCABO_ERR_ARG;
-        }
-      }
-      th[b] = r.state == STEPPING ? r.fit.x.data() : (r.state == OUT ? nullptr : r.xr);
-      if (r.state == STEPPING || r.state == END) ++pending;
-    }
-    if (pending == 0 && batch->fit_rounds > 0) break;
-    rc = batch_mll_round(batch, th, st.data());
-    if (rc != PCABO_OK) return rc;
-    for (int b = 0; b < B; ++b) {
-      Run& r = runs[b];
-      if (r.state == OUT) continue;
-      if (st[b] != PCABO_OK && st[b] != PCABO_ERR_NOT_PD) { r.state = OUT; r.st = st[b]; continue; }
-      if (r.state == STEPPING) {
-        if (st[b] == PCABO_ERR_NOT_PD) {                 // a trial theta the factorisation cannot take: stop, keep the last iterate
-          if (!r.fit.have_cache) { r.state = OUT; r.st = PCABO_ERR_NOT_PD; continue; }      // (not even the start)
-          r.stop_task = PCABO_FIT_TASK_NOT_PD;
-          finish(r);
-          continue;
-        }
-        double f = 0.0;
-        mll_assemble(batch->ctx[b]->hMll, batch->n, r.fit.x.data(), &f, r.fit.g.data());
-        r.fit.absorb(f);
-      } else {                                           // END, RESTING: the result theta
-        if (st[b] != PCABO_OK) { r.state = OUT; r.st = st[b]; continue; }
-        if (r.state == END) {
-          mll_assemble(batch->ctx[b]->hMll, batch->n, r.xr, &r.fr, nullptr);
-          r.state = RESTING;
-        }
-      }
-    }
-  }
+  const auto round = [&](const std::vector<const double*>& th, int* st) { return batch_mll_round(batch, th, st); };
+  rc = fit_rounds(runs, batch->n, round);
+  // (no run wanted an evaluation: one round all the same, the batch is left conditioned at the shared model)
+  if (rc == PCABO_OK && batch->fit_rounds == 0) rc = round(std::vector<const double*>((size_t)B, nullptr), nullptr);
+  if (rc != PCABO_OK) return rc;
   batch_fit_done(batch);
   int worst = PCABO_OK;
   for (int b = 0; b < B; ++b) {
-    const Run& r = runs[b];
-    if (status) status[b] = r.st;
+    const FitRun& r = runs[b];
+    if (status) status[b] = r.status;
     if (!act[b]) continue;
-    if (r.st != PCABO_OK) { worst = r.st; batch->ctx[b]->have_gp = false; continue; }
+    if (r.status == PCABO_ERR_ARG) theta_domain_err(batch->ctx[b]);
+    if (r.status != PCABO_OK) { worst = r.status; batch->ctx[b]->have_gp = false; continue; }
     memcpy(theta_inout + 3 * b, r.xr, sizeof(r.xr));
     if (loss) loss[b] = r.fr;
-    if (info) {
-      int* io = info + 4 * b;
-      io[0] = r.fit.niter; io[1] = r.fit.nfev;
-      io[2] = r.stop_task ? 2 : r.fit.opt.warnflag();
-      io[3] = r.stop_task ? r.stop_task : r.fit.opt.task();
-    }
+    if (info) r.report(info + 4 * b);
   }
   if (worst != PCABO_OK && !status) return bset_err(batch, worst, "pcabo_batch_gp_fit: a run of the batch failed (status array not given)%s", "");
   return PCABO_OK;
@@ -2171,21 +2067,11 @@ static int batch_score_impl(pcabo_batch* batch, const double* Xq, int q, const d
     int st = PCABO_OK;
     if (c->hm->chol_info != 0) {
       // rare: this run's K needed jitter (psd_safe_cholesky: 1e-8, 1e-7, 1e-6) - redo it alone, then score again
-      double jitter = 0.0;
-      st = PCABO_ERR_NOT_PD;
-      for (int attempt = 0; attempt < 3; ++attempt) {
-        jitter = attempt == 0 ? 1e-8 : jitter * 10.0;
-        int r2 = launch_factorisation(c, jitter);
-        if (r2 != PCABO_OK) { st = r2; break; }
-        if (wait_stream(c->stream) != hipSuccess) { st = PCABO_ERR_HIP; break; }
-        if (c->hm->chol_info == 0) { st = PCABO_OK; break; }
-      }
+      st = factor_attempts(c, 1);
       if (st == PCABO_OK) {
         c->have_gp = true;
         if (batch->dev_lbfgsb) launch_rt_build(c->stream, c->dR, c->n, c->NP, c->ld, c->dGram);
         st = pcabo_acq_eval(c, Xq + (size_t)b * q * batch->max_d, q, best_f[b], maximize, acq, c->hVal, nullptr);
-      } else {
-        set_err(c, st, "K + s2 I not positive definite after jitter retries (pivot %s%d)", "", c->hm->chol_info);
       }
     }
     c->have_gp = st == PCABO_OK;
@@ -2545,7 +2431,7 @@ int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, con
     if (c->rt_stale) { launch_rt_build(s, c->dR, c->n, c->NP, c->ld, c->dGram); c->rt_stale = false; }
     memcpy(c->hXq, Xq + (size_t)b * q * MD, (size_t)q * c->k * sizeof(double));
     for (int q0 = 0; q0 < q; q0 += PCABO_GROUP_Q)
-      batch->hOptTab[nent++] = ((unsigned)b << 16) | ((unsigned)q0 << 8) | (unsigned)std::min(PCABO_GROUP_Q, q - q0);
+      batch->hOptTab[nent++] = group_entry(b, q0, std::min(PCABO_GROUP_Q, q - q0));
   }
   if (nent == 0) return PCABO_OK;
   BHIPCHK(hipMemcpyAsync(batch->dOptTab, batch->hOptTab, (size_t)nent * sizeof(unsigned), hipMemcpyHostToDevice, s));
