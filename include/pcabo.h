@@ -42,7 +42,11 @@ typedef enum {
 } pcabo_status;
 
 enum { PCABO_KERNEL_MATERN52 = 0, PCABO_KERNEL_RBF = 1 };
-enum { PCABO_ACQ_LOG_EI = 0, PCABO_ACQ_PI = 1 };
+/* PCABO_ACQ_UCB: botorch's UpperConfidenceBound, value = (maximize ? mean : -mean) + kappa * sigma with kappa = sqrt(beta).  It has
+ * no best_f, so wherever an entry point takes `best_f` (`best_f[B]` in the pcabo_batch_* calls) that slot carries kappa instead:
+ * finite and >= 0, else PCABO_ERR_ARG.  The caller takes the square root (botorch: of the float32 tensor torch.as_tensor(beta));
+ * PCABO_OPT_BESTF_F32 applies to the slot as it does to best_f. */
+enum { PCABO_ACQ_LOG_EI = 0, PCABO_ACQ_PI = 1, PCABO_ACQ_UCB = 2 };
 enum { PCABO_PTR_HOST = 0, PCABO_PTR_DEVICE = 1 };
 
 /* ABI version of this header (checked by the Python loader). */
@@ -165,7 +169,7 @@ int pcabo_acq_bounds(pcabo_ctx* ctx, double* bounds);
  * Replaces LogExpectedImprovement / ProbabilityOfImprovement .forward + torch autograd as driven
  * by botorch (PCA_BO.py:199-203, 607-614).
  *   Xq[q*k] [bulk]; best_f as the reference passes it (current_best; it is rounded to float32
- *   like torch.as_tensor(python float) does); val[q] [bulk]; grad[q*k] [bulk] or NULL. */
+ *   like torch.as_tensor(python float) does; PCABO_ACQ_UCB: kappa, see the enum); val[q] [bulk]; grad[q*k] [bulk] or NULL. */
 int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq,
                    double* val, double* grad);
 /* Name suggested by SURVEY.md 8b; identical to pcabo_acq_eval(..., PCABO_ACQ_LOG_EI, ...). */

@@ -67,6 +67,11 @@ class AnalyticAcquisitionFunction:
     def __init__(self, model=None, best_f: float = 0.0, maximize: bool = True):
         self.model, self.best_f, self.maximize = model, best_f, maximize
 
+    @property
+    def device_scalar(self) -> float:
+        """The one scalar the device takes with `acq_code` (the `best_f` slot of the C ABI): best_f here, kappa for UCB."""
+        return self.best_f
+
 
 class LogExpectedImprovement(AnalyticAcquisitionFunction):
     acq_code = _native.ACQ_LOG_EI
@@ -77,14 +82,22 @@ class ProbabilityOfImprovement(AnalyticAcquisitionFunction):
 
 
 class UpperConfidenceBound(AnalyticAcquisitionFunction):
-    """The reference constructs its acquisition with `best_f=` (PCA_BO.py:199-203), which botorch's
-    UpperConfidenceBound(model, beta, ...) does not accept: the first BO iteration raises TypeError.
-    That behaviour is kept."""
+    """botorch's signature: UpperConfidenceBound(model, beta, maximize=True); value = +-mean + sqrt(beta) sigma.
+    The reference constructs its acquisition with `best_f=` (PCA_BO.py:199-203), which that signature does not accept: the
+    first BO iteration raises TypeError.  That behaviour is kept; the optimisers' `ucb_beta` keyword (not in the reference)
+    is what constructs it the way botorch accepts."""
+    acq_code = _native.ACQ_UCB
 
     def __init__(self, model=None, beta=None, maximize: bool = True, **kwargs):
         if kwargs or beta is None:
             raise TypeError("UpperConfidenceBound.__init__() got an unexpected keyword argument 'best_f'")
         super().__init__(model, 0.0, maximize)
+        self.beta = beta
+        self.kappa = _acqopt.ucb_kappa(beta)       # float32 sqrt like botorch's beta tensor; the device gets kappa, never beta
+
+    @property
+    def device_scalar(self) -> float:
+        return self.kappa
 
 
 class _FittedPCA:
@@ -147,6 +160,9 @@ class PCA_BO(AbstractBayesianOptimizer):
         # hyperparameter fit"); takes the unfused wPCA -> fit path.  False keeps the reference's fixed hyperparameters.
         self.__fit_gp = bool(kwargs.pop("fit_gp", False))
         self.gp_hyperparameters = None     # fit_gp=True: the last fit's result (Context.gp_fit), None otherwise
+        # ucb_beta (not in the reference, whose UCB cannot run): with acquisition_function "UCB" every iteration builds
+        # UpperConfidenceBound(model, beta=ucb_beta, maximize=...), botorch's own signature.  None keeps the reference's TypeError.
+        self.__ucb_beta = _acqopt.checked_ucb_beta(kwargs.pop("ucb_beta", None), acquisition_function)
         self.__gc_entered = False
         super().__init__(budget, n_DoE, **kwargs)
         self.random_seed = random_seed
@@ -234,8 +250,12 @@ class PCA_BO(AbstractBayesianOptimizer):
         self._transform_points_to_reduced_space()
         self._initialize_model(**kwargs)
         self.__ctx.match_best_f_dtype(self.current_best)      # float32 like torch.as_tensor(python float), or all 64 bits
-        self.acquisition_function = self.acquisition_function_class(
-            model=self.__ctx, best_f=self.current_best, maximize=self.maximization)
+        if self.__ucb_beta is not None:
+            self.acquisition_function = self.acquisition_function_class(
+                model=self.__ctx, beta=self.__ucb_beta, maximize=self.maximization)
+        else:
+            self.acquisition_function = self.acquisition_function_class(
+                model=self.__ctx, best_f=self.current_best, maximize=self.maximization)
         new_z = self.optimize_acqf_and_get_observation()
         for new_z_arr in new_z:
             if self.number_of_function_evaluations >= self.budget:
@@ -440,14 +460,14 @@ class PCA_BO(AbstractBayesianOptimizer):
         if self.__gp_pending and self.__early_scoring:
             # the raw samples are scored right behind the conditioning on the stream: one wait for both
             t0 = perf_counter()
-            raw_vals = ctx.gp_wait_eval(raw, acq.best_f, acq.maximize, acq.acq_code)
+            raw_vals = ctx.gp_wait_eval(raw, acq.device_scalar, acq.maximize, acq.acq_code)
             self.__gp_pending = False
             self.phase_breakdown["raw_eval"] = self.phase_breakdown.get("raw_eval", 0.0) + perf_counter() - t0
         elif self.__gp_pending:
             ctx.gp_wait()
             self.__gp_pending = False
         new_z, cand, vals, info = _acqopt.optimize_acqf(
-            ctx, bounds, acq.best_f, acq.maximize, acq.acq_code, num_restarts, raw_samples, batch_limit, 200,
+            ctx, bounds, acq.device_scalar, acq.maximize, acq.acq_code, num_restarts, raw_samples, batch_limit, 200,
             raw=raw, raw_vals=raw_vals, breakdown=self.phase_breakdown,
             trace=self.trace[-1] if self.__record_trace else None,
             before_lbfgsb=self._prefetch_noise)   # the draw overlaps with the optimiser's time inside the library; started

@@ -41,6 +41,7 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         self.__resident = bool(kwargs.pop("resident", True))         # see PCA_BO: False = one launch per evaluation
         self.__fit_gp = bool(kwargs.pop("fit_gp", False))             # see PCA_BO: marginal-likelihood fit every iteration
         self.gp_hyperparameters = None
+        self.__ucb_beta = _acqopt.checked_ucb_beta(kwargs.pop("ucb_beta", None), acquisition_function)   # see PCA_BO
         super().__init__(budget, n_DoE, **kwargs)
         self.random_seed = random_seed
         smoke_test = os.environ.get("SMOKE_TEST")
@@ -100,8 +101,12 @@ class Vanilla_BO(AbstractBayesianOptimizer):
                                "torch_state": torch.get_rng_state(), "best_f": self.current_best})
         self._initialise_model(**kwargs)
         self.__ctx.match_best_f_dtype(self.current_best)      # float32 like torch.as_tensor(python float), or all 64 bits
-        self.acquisition_function = self.acquisition_function_class(
-            model=self.__ctx, best_f=self.current_best, maximize=self.maximization)
+        if self.__ucb_beta is not None:
+            self.acquisition_function = self.acquisition_function_class(
+                model=self.__ctx, beta=self.__ucb_beta, maximize=self.maximization)
+        else:
+            self.acquisition_function = self.acquisition_function_class(
+                model=self.__ctx, best_f=self.current_best, maximize=self.maximization)
         new_x = self.optimize_acqf_and_get_observation()
         for new_x_arr in new_x:
             if self.number_of_function_evaluations >= self.budget:
@@ -156,10 +161,10 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         raw_vals = None                    # (fit_gp: the GP is conditioned already, the optimiser scores the raw samples)
         if not self.__fit_gp:
             t0 = perf_counter()            # the raw samples are scored right behind the conditioning: one wait for both
-            raw_vals = ctx.gp_wait_eval(raw, acq.best_f, acq.maximize, acq.acq_code)
+            raw_vals = ctx.gp_wait_eval(raw, acq.device_scalar, acq.maximize, acq.acq_code)
             self.phase_breakdown["raw_eval"] = self.phase_breakdown.get("raw_eval", 0.0) + perf_counter() - t0
         new_x, cand, vals, info = _acqopt.optimize_acqf(
-            ctx, self.__box, acq.best_f, acq.maximize, acq.acq_code, cfg["NUM_RESTARTS"], cfg["RAW_SAMPLES"], 5, 200,
+            ctx, self.__box, acq.device_scalar, acq.maximize, acq.acq_code, cfg["NUM_RESTARTS"], cfg["RAW_SAMPLES"], 5, 200,
             raw=raw, raw_vals=raw_vals, breakdown=self.phase_breakdown,
             trace=self.trace[-1] if self.__record_trace else None)
         self.timing_logs["optimize_acqf"].append(perf_counter() - start)

@@ -125,7 +125,7 @@ class ExperimentRunner:
                  experiment_name: str = "experiment", acquisition_function: str = "expected_improvement",
                  pca_components: Optional[int] = None, var_threshold: float = 0.95, verbose: bool = False,
                  progress: bool = True, batched: int = 0, side_by_side: int = 2, batch_acq_kernel: str = "group",
-                 fit_gp: bool = False, batched_fit_gp: bool = False):
+                 fit_gp: bool = False, batched_fit_gp: bool = False, ucb_beta: Optional[float] = None):
         # fit_gp (not in the reference): every run fits its GP's hyperparameters by the marginal likelihood each iteration
         # (PCA_BO / Vanilla_BO fit_gp=True), one run after the other.  For the lock-step batches: batched_fit_gp below.
         self.fit_gp = bool(fit_gp)
@@ -139,6 +139,10 @@ class ExperimentRunner:
         if self.batched_fit_gp and int(batched) <= 1:
             raise ValueError("batched_fit_gp=True fits the GPs of the lock-step batches: it needs batched > 1 (for one run after "
                              "the other use fit_gp=True)")
+        # ucb_beta (not in the reference, where acquisition_function="upper_confidence_bound" raises at the first BO iteration):
+        # handed to every optimiser and lock-step batch, which then build botorch's UpperConfidenceBound(model, beta=ucb_beta)
+        from pcabo.acqopt import checked_ucb_beta
+        self.ucb_beta = checked_ucb_beta(ucb_beta, acquisition_function)
         self.algorithms = algorithms
         self.dimensions = dimensions
         self.problem_ids = problem_ids
@@ -276,7 +280,8 @@ class ExperimentRunner:
                 runner = Driver(probs, seeds, budget, n_doe, n_components=self.pca_components or 0,
                                       var_threshold=self.var_threshold, acquisition_function=self.acquisition_function,
                                       device=self.device, workers=workers_for(len(group)) if len(group) > 1 else 0,
-                                      host_threads=max(1, 8 // len(group)), acq_kernel=kernel, fit_gp=self.batched_fit_gp)
+                                      host_threads=max(1, 8 // len(group)), acq_kernel=kernel, fit_gp=self.batched_fit_gp,
+                                      ucb_beta=self.ucb_beta)
                 jobs.append((dim, chunk, probs, n_doe, runner))
             kernel = group[0][2]
             start_time = time()
@@ -336,6 +341,8 @@ class ExperimentRunner:
                 provenance = {"arithmetic_mode": ",".join(f"d{dim}={self.arithmetic_modes[dim]}" for dim in self.dimensions)}
                 if self.fit_gp or self.batched_fit_gp:
                     provenance["gp_fit"] = "map"         # hyperparameters fitted by the marginal likelihood (+ noise prior)
+                if self.ucb_beta is not None:            # (only when set: the files of every other configuration stay as they were)
+                    provenance["ucb_beta"] = f"{self.ucb_beta}"
                 logger.set_experiment_attributes({
                     "budget_factor": f"{self.budget_factor}",
                     "doe_factor": f"{self.doe_factor}",
@@ -352,6 +359,8 @@ class ExperimentRunner:
                 for time_profile in getattr(optimizer_class, "TIME_PROFILES", []):
                     logger.add_run_attribute(f"{time_profile}_time", 0.0)
                 logger.add_run_attribute("time", 0.0)
+                if self.ucb_beta is not None:
+                    logger.add_run_attribute("ucb_beta", self.ucb_beta)
 
                 if self.batched > 1 and HAVE_IOH:     # pragma: no cover
                     import warnings
@@ -383,6 +392,8 @@ class ExperimentRunner:
                                       device=self.device)
                         if self.fit_gp:
                             common["fit_gp"] = True
+                        if self.ucb_beta is not None:
+                            common["ucb_beta"] = self.ucb_beta
                         if algorithm == "vanilla":
                             optimizer = Vanilla_BO(**common)
                         else:

@@ -8,7 +8,7 @@
 //   ks_j = matern52(|xn - zn_j| / l)                       j = 0..n-1
 //   mu_s = ks . alpha ;  v = R ks ;  var_s = 1 - |v|^2     (fast_pred_var: root-inverse cache)
 //   mu = m_y + s_y mu_s ;  sigma = sqrt(clamp(s_y^2 var_s))
-//   u = +-(mu - best_f)/sigma ;  logEI = h(u) + log sigma
+//   u = +-(mu - best_f)/sigma ;  logEI = h(u) + log sigma     (PI: Phi(u); UCB: +-mu + kappa sigma, kappa in the best_f slot)
 // and the reverse-mode gradient  w = R^T v,  grad = sum_j (c_mu alpha_j + c_s w_j) dks_j/dx.
 //
 // Work decomposition (latency- and issue-bound: ~1 MFLOP per query at n = 450, 10-15 us per launch):
@@ -789,8 +789,22 @@ __device__ void acq_scalar_core(double vv, double mus, int q, double ym, double 
   if (!(var >= 1e-10)) { var = 1e-10; clamped = true; }     // gpytorch min_variance (double)
   if (var < 1e-12) { var = 1e-12; clamped = true; }          // botorch _mean_and_sigma(min_var)
   const double sigma = sqrt(var);
-  double u = (mu - p.best_f) / sigma;
   const double sgn = p.maximize ? 1.0 : -1.0;
+  if (p.acq == 2) {
+    // PCABO_ACQ_UCB: value = sgn mu + kappa sigma, kappa in the best_f slot - linear in mu and sigma, no u (wave-uniform branch).
+    // The one fused multiply-add is spelled out: left to the compiler, a b + c d is contracted one way in one kernel and the
+    // other way in the next, and a run in a batch must take the bits it takes alone.
+    if (l == 0) {
+      const double kappa = p.best_f, value = __fma_rn(kappa, sigma, sgn * mu);
+      val[q] = value;
+      if (host_val) host_val[q] = value;
+      coef[0] = sgn * ysd;                                              // d value / d mu_s
+      coef[1] = clamped ? 0.0 : kappa * (-(ysd * ysd) / sigma);         // dsigma = -s_y^2 g_sigma / sigma
+    }
+    STAMP_FIN(12);
+    return;
+  }
+  double u = (mu - p.best_f) / sigma;
   u *= sgn;
   double value, dv_du, dv_dsig;
   if (p.acq == 0) {
@@ -923,7 +937,8 @@ __global__ __launch_bounds__(256) void k_acq_group(
   const int KS = (k + 1) & ~1;                        // stride of a query's coordinates in LDS
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
   double* s_ks = s_dyn;                               // [GQ][NP]  kernel vectors, later t_sigma = w * cf
-  double* s_tile = s_ks + GQ * NP;                    // [4 waves][64][GT_LD] wave-private transposing tiles (64 rows x 16 columns)
+  // (the region also becomes s_gout [2 GQ][KS], which is the larger of the two where NP < 2 KS: few points, many components)
+  double* s_tile = s_ks + GQ * (NP > 2 * KS ? NP : 2 * KS);   // [4 waves][64][GT_LD] wave-private transposing tiles (64 rows x 16 columns)
   double* s_v = s_tile + 4 * 64 * GT_LD;              // [64][8]   v of the slab's rows (queries contiguous)
   double* s_tm = s_v + 64 * 8;                        // [GQ][64]  alpha_j cf_q[j] for the slab's own rows
   double* s_coef = s_tm + GQ * 64;                    // [GQ][2]
@@ -1291,7 +1306,8 @@ int launch_acq_group(hipStream_t st, const QueryArgs* tab, int entries, const do
                      const double* ZnT, const double* R, const double* alpha, const double* bounds4, const double* ystats,
                      AcqParams p, double* partial, unsigned int* counters, double* val, double* grad, double* host_val,
                      double* host_grad, HostMirror* hm, unsigned long long seq, AcqBatch ab) {
-  const size_t lds = ((size_t)GQ * NP + 4 * 64 * GT_LD + 64 * 8 + GQ * 64 + 2 * GQ + 4 + 2 * GQ + GQ * (((size_t)k + 1) & ~(size_t)1) + 8) * sizeof(double);
+  const size_t ks2 = 2 * (((size_t)k + 1) & ~(size_t)1);       // s_ks doubles as s_gout [2 GQ][KS]: the larger of the two
+  const size_t lds = ((size_t)GQ * std::max((size_t)NP, ks2) + 4 * 64 * GT_LD + 64 * 8 + GQ * 64 + 2 * GQ + 4 + 2 * GQ + GQ * (((size_t)k + 1) & ~(size_t)1) + 8) * sizeof(double);
   const dim3 grid(NP / 64, entries), block(256);
   // Dynamic LDS beyond the 64 KB default needs the attribute - per DEVICE, and for every instantiation that can ask for
   // more: <2> does from (NP, k) = (512, 83) on (65 808 bytes at k = 89), <5> always.  Launched from the worker threads of

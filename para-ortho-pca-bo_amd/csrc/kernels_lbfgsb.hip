@@ -1447,7 +1447,7 @@ __host__ __device__ inline void lb_build_plan(const LbLds L, int n, int S) { lb_
 struct LbEval {
   gcd *ZnT, *R, *RT, *alpha, *nlo, *nhi;
   int n, k, NP, ld, S;
-  double best_f, ym, ysd, inv_ls;
+  double best_f, ym, ysd, inv_ls;      // best_f: kappa for PCABO_ACQ_UCB (AcqParams::best_f)
   int maximize, acq, kernel;
 };
 
@@ -1481,8 +1481,15 @@ __device__ inline void lb_scalar_core(double vv, double mus, const LbEval& E, do
   if (!(var >= 1e-10)) { var = 1e-10; clamped = true; }
   if (var < 1e-12) { var = 1e-12; clamped = true; }
   const double sigma = sqrt(var);
-  double u = (mu - E.best_f) / sigma;
   const double sgn = E.maximize ? 1.0 : -1.0;
+  if (E.acq == 2) {                     // PCABO_ACQ_UCB: kappa in the best_f slot; linear in mu and sigma, no u
+    const double kappa = E.best_f;
+    *value = __fma_rn(kappa, sigma, sgn * mu);    // as acq_scalar_core spells it
+    *c_mu = sgn * E.ysd;
+    *c_sg = clamped ? 0.0 : kappa * (-(E.ysd * E.ysd) / sigma);
+    return;
+  }
+  double u = (mu - E.best_f) / sigma;
   u *= sgn;
   double val, dv_du, dv_dsig;
   if (E.acq == 0) {

@@ -958,9 +958,19 @@ int pcabo_acq_bounds(pcabo_ctx* ctx, double* bounds) {
   return PCABO_OK;
 }
 
+// The one validity rule for (acq, scalar) of every acquisition entry point: a known PCABO_ACQ_* code and, for PCABO_ACQ_UCB,
+// whose kappa = sqrt(beta) travels in the best_f slot, a finite kappa >= 0.  Null, or what is wrong.
+static const char* acq_arg_error(int acq, double scalar) {
+  if (acq != PCABO_ACQ_LOG_EI && acq != PCABO_ACQ_PI && acq != PCABO_ACQ_UCB) return "unknown acquisition code";
+  if (acq == PCABO_ACQ_UCB && !(std::isfinite(scalar) && scalar >= 0.0))
+    return "PCABO_ACQ_UCB takes kappa = sqrt(beta) in the best_f slot: it must be finite and >= 0";
+  return nullptr;
+}
+
 static AcqParams make_params(pcabo_ctx* ctx, double best_f, int maximize, int acq, int want_grad) {
   AcqParams p;
-  // torch.as_tensor(python float) gives a float32 tensor; a numpy float64 scalar keeps its 64 bits (PCABO_OPT_BESTF_F32)
+  // torch.as_tensor(python float) gives a float32 tensor; a numpy float64 scalar keeps its 64 bits (PCABO_OPT_BESTF_F32);
+  // PCABO_ACQ_UCB: the slot carries kappa, which the Python layer passes float32-representable already
   p.best_f = ctx->bestf_f32 ? (double)(float)best_f : best_f;
   p.y_mean = 0.0; p.y_std = 1.0;
   p.inv_ls = 1.0 / ctx->lengthscale;
@@ -1051,8 +1061,9 @@ static bool group_mode(const pcabo_ctx* ctx, int q, int want_grad) {
 int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq, double* val,
                    double* grad) {
   if (!ctx) return PCABO_ERR_ARG;
-  if (!Xq || !val || q < 1 || q > ctx->max_q || (acq != PCABO_ACQ_LOG_EI && acq != PCABO_ACQ_PI))
+  if (!Xq || !val || q < 1 || q > ctx->max_q)
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: bad argument or q beyond context capacity%s", "");
+  if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: %s", why);
   if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: call pcabo_gp_condition first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
@@ -1091,8 +1102,9 @@ int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int m
 int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq,
                                 double* val) {
   if (!ctx) return PCABO_ERR_ARG;
-  if (!Xq || !val || q < 1 || q > ctx->max_q || (acq != PCABO_ACQ_LOG_EI && acq != PCABO_ACQ_PI))
+  if (!Xq || !val || q < 1 || q > ctx->max_q)
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: bad argument or q beyond context capacity%s", "");
+  if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: %s", why);
   if (!ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: no conditioning in flight%s", "");
   if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
   if (q <= PCABO_INLAUNCH_MAXQ || ctx->ptr_mode != PCABO_PTR_HOST) {      // nothing to gain: the two calls in a row
@@ -1147,9 +1159,9 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
                         int maxiter, double best_f, int maximize, int acq, double* cand, double* vals, int* info,
                         int* failed) {
   if (!ctx) return PCABO_ERR_ARG;
-  if (!ics || !bounds || !cand || !vals || num_restarts < 1 || batch_limit < 1 || num_restarts > ctx->max_q ||
-      (acq != PCABO_ACQ_LOG_EI && acq != PCABO_ACQ_PI))
+  if (!ics || !bounds || !cand || !vals || num_restarts < 1 || batch_limit < 1 || num_restarts > ctx->max_q)
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: bad argument%s", "");
+  if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: %s", why);
   if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: call pcabo_gp_condition first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
   const int k = ctx->k;
@@ -1851,7 +1863,16 @@ static AcqBatch batch_ab(const pcabo_batch* batch, int table, int xq_host) {
   return ab;
 }
 
-// best_f of every run -> its device word (rounded per run like the single-context calls do)
+// acq_arg_error for a batch call: the scalars of the active runs only (a parked run's slot is never read by a kernel that counts)
+static const char* batch_acq_arg_error(const pcabo_batch* batch, int acq, const double* best_f) {
+  if (const char* why = acq_arg_error(acq, 0.0)) return why;
+  for (int b = 0; b < batch->B; ++b)
+    if (batch->active[b])
+      if (const char* why = acq_arg_error(acq, best_f[b])) return why;
+  return nullptr;
+}
+
+// best_f of every run (PCABO_ACQ_UCB: its kappa) -> its device word (rounded per run like the single-context calls do)
 static int batch_put_best_f(pcabo_batch* batch, const double* best_f) {
   pcabo_ctx* c0 = batch->ctx[0];
   for (int b = 0; b < batch->B; ++b) {
@@ -2026,8 +2047,9 @@ int pcabo_batch_busy(pcabo_batch* batch) {
 static int batch_score_impl(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize,
                             int acq, double* val, int* status, int phase /* 0 both, 1 begin, 2 end */) {
   if (!batch) return PCABO_ERR_ARG;
-  if (!Xq || !best_f || (!val && phase != 1) || q < 1 || q > batch->max_q || (acq != PCABO_ACQ_LOG_EI && acq != PCABO_ACQ_PI))
+  if (!Xq || !best_f || (!val && phase != 1) || q < 1 || q > batch->max_q)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: bad argument%s", "");
+  if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: %s", why);
   // (after pcabo_batch_gp_fit the conditioning has been waited for already: the fitted state is scored by the same launches)
   if (!batch->gp_pending && !batch->fitted) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: no conditioning in flight%s", "");
   if (phase == 2 && !batch->score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval_end: no _begin before it%s", "");
@@ -2274,9 +2296,9 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
                               const double* bounds, int maxiter, const double* best_f, int maximize, int acq,
                               double* cand, double* vals, int* info, int* failed, int* status) {
   if (!batch) return PCABO_ERR_ARG;
-  if (!ics || !bounds || !best_f || !cand || !vals || num_restarts < 1 || batch_limit < 1 ||
-      num_restarts > PCABO_INLAUNCH_MAXQ || (acq != PCABO_ACQ_LOG_EI && acq != PCABO_ACQ_PI))
+  if (!ics || !bounds || !best_f || !cand || !vals || num_restarts < 1 || batch_limit < 1 || num_restarts > PCABO_INLAUNCH_MAXQ)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: bad argument (num_restarts <= 32)%s", "");
+  if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: %s", why);
   if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: no conditioned GP%s", "");
   BHIPCHK(hipSetDevice(batch->device));
   const int B = batch->B, MD = batch->max_d, kmax = batch_max_k(batch), G = batch->G;
@@ -2384,9 +2406,9 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
 int pcabo_batch_optimize_acqf_begin(pcabo_batch* batch, const double* ics, int num_restarts, int batch_limit,
                                     const double* bounds, int maxiter, const double* best_f, int maximize, int acq) {
   if (!batch) return PCABO_ERR_ARG;
-  if (!ics || !bounds || !best_f || num_restarts < 1 || batch_limit < 1 || num_restarts > PCABO_INLAUNCH_MAXQ ||
-      (acq != PCABO_ACQ_LOG_EI && acq != PCABO_ACQ_PI))
+  if (!ics || !bounds || !best_f || num_restarts < 1 || batch_limit < 1 || num_restarts > PCABO_INLAUNCH_MAXQ)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: bad argument (num_restarts <= 32)%s", "");
+  if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: %s", why);
   if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: no conditioned GP%s", "");
   if (batch->dev_lbfgsb != 1) return 1;
   BHIPCHK(hipSetDevice(batch->device));
@@ -2409,8 +2431,9 @@ int pcabo_batch_optimize_acqf_end(pcabo_batch* batch, int num_restarts, int batc
 int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq,
                                 double* val, double* grad) {
   if (!batch) return PCABO_ERR_ARG;
-  if (!Xq || !best_f || !val || !grad || q < 1 || q > PCABO_INLAUNCH_MAXQ || (acq != PCABO_ACQ_LOG_EI && acq != PCABO_ACQ_PI))
+  if (!Xq || !best_f || !val || !grad || q < 1 || q > PCABO_INLAUNCH_MAXQ)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: bad argument (q <= 32)%s", "");
+  if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: %s", why);
   if (!batch->have_gp || !batch->dev_lbfgsb)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: needs a conditioned GP and PCABO_OPT_DEVICE_LBFGSB%s", "");
   // the pinned table / point / value / gradient buffers below belong to an enqueued call until its _end has collected them

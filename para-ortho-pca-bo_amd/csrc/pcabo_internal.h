@@ -52,7 +52,7 @@ static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // Model / problem constants handed to the acquisition kernels by value.
 struct AcqParams {
-  double best_f;        // already rounded like torch.as_tensor(float) does
+  double best_f;        // already rounded like torch.as_tensor(float) does; PCABO_ACQ_UCB: the slot carries kappa = sqrt(beta)
   double y_mean, y_std; // filled on device from the standardisation kernel (host copy unused)
   double inv_ls;        // 1 / lengthscale
   int maximize;

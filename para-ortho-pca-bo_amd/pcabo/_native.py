@@ -15,7 +15,7 @@ import numpy as np
 
 ABI_VERSION = 2
 KERNEL_MATERN52, KERNEL_RBF = 0, 1
-ACQ_LOG_EI, ACQ_PI = 0, 1
+ACQ_LOG_EI, ACQ_PI, ACQ_UCB = 0, 1, 2
 PTR_HOST, PTR_DEVICE = 0, 1
 OPT_RESIDENT, OPT_BESTF_F32, OPT_GROUP_ACQ, OPT_DEVICE_LBFGSB, OPT_LBFGSB_CUS = 0, 1, 2, 3, 4
 FIT_THETA0 = (0.006737946999085467, 0.0, 0.0)   # GP fit: (noise, mean constant, raw lengthscale) of a freshly built model
@@ -351,7 +351,7 @@ class Context:
         self._keep = None
 
     def gp_wait_eval(self, Xq, best_f, maximize=False, acq=ACQ_LOG_EI) -> np.ndarray:
-        """gp_wait() + acq_eval(Xq, grad=False) with the evaluation enqueued behind the conditioning."""
+        """gp_wait() + acq_eval(Xq, grad=False) with the evaluation enqueued behind the conditioning (`best_f`: see acq_eval)."""
         Xq = _f64(Xq).reshape(-1, self.k)
         q = Xq.shape[0]
         val = np.empty(q)
@@ -367,6 +367,8 @@ class Context:
 
     # ---- row I --------------------------------------------------------------------------------
     def acq_eval(self, Xq, best_f, maximize=False, acq=ACQ_LOG_EI, grad=True):
+        """Acquisition values (and gradients) at Xq.  `best_f`: the acquisition's scalar - the incumbent for ACQ_LOG_EI and ACQ_PI;
+        for ACQ_UCB, which has no incumbent, the slot carries kappa = sqrt(beta) (finite, >= 0; include/pcabo.h)."""
         Xq = _f64(Xq).reshape(-1, self.k)
         q = Xq.shape[0]
         val = np.empty(q)
@@ -377,6 +379,8 @@ class Context:
 
     # ---- rows M-N -----------------------------------------------------------------------------
     def optimize_acqf(self, ics, bounds, best_f, maximize=False, acq=ACQ_LOG_EI, batch_limit=5, maxiter=200):
+        """Multi-start L-BFGS-B from `ics` inside `bounds`; `best_f` as in acq_eval (ACQ_UCB: kappa).  Returns (candidates, values,
+        per-group (iterations, evaluations, warnflag, task), botorch's retry flag)."""
         ics = _f64(ics).reshape(-1, self.k)
         nr = ics.shape[0]
         bounds = _f64(bounds, (2, self.k))
@@ -579,7 +583,8 @@ class Batch:
         return [buf[b, : 2 * int(self.k[b])].reshape(2, int(self.k[b])).copy() for b in range(self.B)]
 
     def gp_wait_eval(self, Xq_list, best_f, maximize=False, acq=ACQ_LOG_EI):
-        """Xq_list[b]: q x k_b points of run b.  Returns (values[B, q], status[B])."""
+        """Xq_list[b]: q x k_b points of run b; best_f[B]: every run's scalar (ACQ_UCB: its kappa = sqrt(beta), as in
+        Context.acq_eval - the same holds for every `best_f` of this class).  Returns (values[B, q], status[B])."""
         q = Xq_list[0].shape[0]
         buf = np.zeros((self.B, q * self.max_d))
         for b, xq in enumerate(Xq_list):

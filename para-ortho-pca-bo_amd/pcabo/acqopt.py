@@ -14,11 +14,33 @@ from . import _native
 from . import initializers as _init
 
 
+def ucb_kappa(beta) -> float:
+    """kappa = sqrt(beta) as botorch's UpperConfidenceBound forms it: it stores `torch.as_tensor(beta)` - float32 for a Python
+    float - and takes `.sqrt()` of that tensor.  The device never takes the root: kappa travels in the `best_f` slot."""
+    import torch
+    return float(torch.as_tensor(float(beta)).sqrt())
+
+
+def checked_ucb_beta(ucb_beta, acquisition_name: str) -> Optional[float]:
+    """The `ucb_beta` keyword of the optimisers, validated where they are constructed: None stays None (UCB then fails as the
+    reference's does); otherwise a finite float >= 0 together with the upper-confidence-bound acquisition, else ValueError."""
+    if ucb_beta is None:
+        return None
+    beta = float(ucb_beta)
+    if not (np.isfinite(beta) and beta >= 0.0):
+        raise ValueError(f"ucb_beta must be finite and >= 0, got {ucb_beta!r}")
+    if acquisition_name.strip().lower() not in ("ucb", "upper_confidence_bound"):
+        raise ValueError(f"ucb_beta is the parameter of the upper-confidence-bound acquisition; it was given together with "
+                         f"{acquisition_name!r}")
+    return beta
+
+
 def optimize_acqf(ctx: "_native.Context", bounds: np.ndarray, best_f: float, maximize: bool, acq_code: int,
                   num_restarts: int, raw_samples: int, batch_limit: int = 5, maxiter: int = 200, engine=None,
                   breakdown: Optional[dict] = None, trace: Optional[dict] = None, raw: Optional[np.ndarray] = None,
                   raw_vals: Optional[np.ndarray] = None, before_lbfgsb=None):
-    """Returns (candidate[1, k], all restart candidates, their values, L-BFGS-B info).  `engine`: a scrambled Sobol
+    """Returns (candidate[1, k], all restart candidates, their values, L-BFGS-B info).  `best_f`: the acquisition's scalar
+    (the incumbent; for ACQ_UCB kappa - it takes the standardised Boltzmann pick like log-EI).  `engine`: a scrambled Sobol
     engine prepared earlier (same RNG consumption, earlier in time); `raw`: the raw samples already drawn from it
     (while the device was still factorising); `raw_vals`: their acquisition values if the caller already has them
     (`Context.gp_wait_eval`).  The retry path draws and scores afresh.  `before_lbfgsb()`: called once, after the

@@ -24,6 +24,7 @@ import torch
 from . import _native
 from .hostrng import HostMT
 from . import initializers as _init
+from .acqopt import checked_ucb_beta, ucb_kappa
 from .lhs import lhs_center
 
 LENGTHSCALE = 0.6931471805599453     # softplus(0)
@@ -59,7 +60,7 @@ class BatchedPCABO:
                  maximization: bool = False, device: int = 0, num_restarts: int = 10, raw_samples: int = 512,
                  record_trace: bool = False, host_threads: int = 0, device_objective: bool = False, workers: int = 0,
                  trace_filter=None, acq_kernel: str = "group", lbfgsb_cus: int = 0, torch_threads: Optional[int] = 4,
-                 gc_freeze: bool = True, fit_gp: bool = False):
+                 gc_freeze: bool = True, fit_gp: bool = False, ucb_beta: Optional[float] = None):
         self.problems, self.seeds = list(problems), [int(s) for s in seeds]
         self.B = len(self.problems)
         assert self.B == len(self.seeds) and self.B >= 1
@@ -67,10 +68,18 @@ class BatchedPCABO:
         assert all(int(p.meta_data.n_variables) == self.dimension for p in self.problems), "one dimension per batch"
         self.budget, self.n_DoE = int(budget), int(n_DoE) if n_DoE else self.dimension
         self.n_components, self.var_threshold, self.maximization = int(n_components), float(var_threshold), bool(maximization)
-        name = {"EI": "expected_improvement", "PI": "probability_of_improvement"}.get(acquisition_function, acquisition_function)
-        if name not in ("expected_improvement", "probability_of_improvement"):
+        name = {"EI": "expected_improvement", "PI": "probability_of_improvement",
+                "UCB": "upper_confidence_bound"}.get(acquisition_function, acquisition_function)
+        # ucb_beta (not in the reference, whose UCB cannot run; Algorithms.PCA_BO has the same keyword): what makes the upper
+        # confidence bound a choice here.  Every run passes kappa = sqrt(beta) where the other acquisitions pass their best_f.
+        self.ucb_beta = checked_ucb_beta(ucb_beta, acquisition_function)
+        self._kappa = None if self.ucb_beta is None else ucb_kappa(self.ucb_beta)
+        codes = {"expected_improvement": _native.ACQ_LOG_EI, "probability_of_improvement": _native.ACQ_PI}
+        if self._kappa is not None:
+            codes["upper_confidence_bound"] = _native.ACQ_UCB
+        if name not in codes:
             raise ValueError("Oddly defined name")
-        self.acq_code = _native.ACQ_LOG_EI if name == "expected_improvement" else _native.ACQ_PI
+        self.acq_code = codes[name]
         self.num_restarts, self.raw_samples, self.device = int(num_restarts), int(raw_samples), int(device)
         self.bounds = [np.column_stack([np.asarray(p.bounds.lb, dtype=float), np.asarray(p.bounds.ub, dtype=float)])
                        for p in self.problems]
@@ -143,6 +152,12 @@ class BatchedPCABO:
         self._group_acq = acq_kernel != "latency"
         self._device_lbfgsb = {"device": 1, "device-twin": 2}.get(acq_kernel, 0)
         self._lbfgsb_cus = int(lbfgsb_cus)         # "device": the optimiser's launches confined to that many CUs (0: the whole chip)
+
+    def _acq_scalars(self) -> list:
+        """What every run hands the device in the `best_f` slot this iteration: its incumbent, or kappa for UCB."""
+        if self.acq_code == _native.ACQ_UCB:
+            return [self._kappa] * self.B
+        return [self.current_best[b] for b in range(self.B)]
 
     # ---- seeding + DoE (AbstractAlgorithm.py:310-328, AbstractBayesianOptimizer.py:142-176) --------------------------
     def start(self) -> None:
@@ -319,7 +334,7 @@ class BatchedPCABO:
         for b in range(B):
             draw(b)
         raw = _native.sobol_draw_rows(engines, self.raw_samples, bt.acq_bounds_packed, rawbuf)       # all runs' points, one call
-        best_f = [self.current_best[b] for b in range(B)]
+        best_f = self._acq_scalars()
         for b in range(B):
             bt.ctx[b].match_best_f_dtype(best_f[b])
         t3 = perf_counter()
@@ -333,8 +348,8 @@ class BatchedPCABO:
             if self.failed[b] is not None:
                 vals[b] = np.linspace(0.0, 1.0, vals.shape[1])          # anything finite: the pick below is discarded
         t4 = perf_counter()
-        pick = _init.initialize_q_batch if self.acq_code == _native.ACQ_LOG_EI else _init.initialize_q_batch_nonneg
-        if self.acq_code == _native.ACQ_LOG_EI:   # all runs' Boltzmann weights at once, a run's own generator for its draw
+        pick = _init.initialize_q_batch if self.acq_code != _native.ACQ_PI else _init.initialize_q_batch_nonneg
+        if self.acq_code != _native.ACQ_PI:       # all runs' Boltzmann weights at once, a run's own generator for its draw
             idx = _init.initialize_q_batch_rows(vals, self.num_restarts, self._tg,
                                                 skip=[b for b in range(B) if self.failed[b] is not None])
         else:
@@ -525,7 +540,7 @@ class BatchedVanillaBO(BatchedPCABO):
         rawbuf = bt.raw_row_buffer(self.raw_samples)
         engines = [built[b][1] if b in built else _init.scrambled_sobol_engine(d, self._tg[b]) for b in range(B)]
         raw = _native.sobol_draw_rows(engines, self.raw_samples, self._boxes_packed, rawbuf)
-        best_f = [self.current_best[b] for b in range(B)]
+        best_f = self._acq_scalars()
         for b in range(B):
             bt.ctx[b].match_best_f_dtype(best_f[b])
         t3 = t2 = perf_counter()
@@ -543,8 +558,8 @@ class BatchedVanillaBO(BatchedPCABO):
             if self.failed[b] is not None:
                 vals[b] = np.linspace(0.0, 1.0, vals.shape[1])
         t4 = perf_counter()
-        pick = _init.initialize_q_batch if self.acq_code == _native.ACQ_LOG_EI else _init.initialize_q_batch_nonneg
-        if self.acq_code == _native.ACQ_LOG_EI:
+        pick = _init.initialize_q_batch if self.acq_code != _native.ACQ_PI else _init.initialize_q_batch_nonneg
+        if self.acq_code != _native.ACQ_PI:
             idx = _init.initialize_q_batch_rows(vals, self.num_restarts, self._tg,
                                                 skip=[b for b in range(B) if self.failed[b] is not None])
         else:
