@@ -140,6 +140,21 @@ int pcabo_gp_mll(pcabo_ctx* ctx, const double* Z /* NULL: Z of the last wPCA */,
 #define PCABO_FIT_TASK_DOMAIN (-3)
 int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
                  double* theta_inout /*3*/, double* loss, int* info /*4*/);
+/* The same fit with one lengthscale per input (automatic relevance determination, MaternKernel(nu=2.5, ard_num_dims=k); DESIGN.md
+ * "ARD lengthscales").  theta = {s2, c, rho_1 .. rho_k}, l_c = softplus(rho_c); the start is {exp(-5), 0, 0 .. 0}, and equal rho is
+ * exactly the model of pcabo_gp_mll / pcabo_gp_fit.  Loss, prior, bound, optimiser, info, stops and error codes as there (Matern-5/2
+ * only; a theta outside the domain - s2 <= 0, a lengthscale that is 0 or not finite - is PCABO_ERR_ARG, except that the fit, like
+ * pcabo_gp_fit, clips a finite start s2 below its bound 1e-4 to the bound instead of refusing it).  grad[c + 2] =
+ * d loss / d rho_c.  The fit alone adds the optimiser bound rho_c >= ln 2^-40 = -27.73 (a lengthscale of 2^-40 of the range, below
+ * which a folded range is held anyway): it keeps the long trial steps that the flat directions of irrelevant inputs produce inside
+ * the domain, and a start below it is clipped to it as one with s2 < 1e-4 is.  The context is left conditioned at theta and acquisition calls follow directly: the lengthscales are folded
+ * into the Normalize ranges, (hi_c - lo_c) l_c, and the model runs at lengthscale 1 on them - the search box (pcabo_acq_bounds) is
+ * not folded.  The next pcabo_gp_condition* / pcabo_wpca_gp_condition_begin returns to the unfolded model.
+ * Single contexts only: on a member context of a batch both return PCABO_ERR_ARG (the lock-step batches fit one lengthscale). */
+int pcabo_gp_mll_ard(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
+                     const double* theta /*2+k*/, double* loss, double* grad /*2+k or NULL*/);
+int pcabo_gp_fit_ard(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
+                     double* theta_inout /*2+k*/, double* loss, int* info /*4*/);
 
 /* Rows A-H as ONE enqueue: pcabo_wpca immediately followed by pcabo_gp_condition_begin(Z = NULL,
  * norm_bounds = NULL), i.e. PCA_BO._transform_points_to_reduced_space + _initialize_model of one iteration
@@ -192,7 +207,9 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
 /* Row O: x = z Ck + pca_mean + data_mean (PCA_BO.py:410-434). z[k] [host] -> x[d] [host]. */
 int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x);
 
-/* Introspection used by the parity tests (all [host] outputs, row-major n x n / vectors). */
+/* Introspection used by the parity tests (all [host] outputs, row-major n x n / vectors).
+ * After pcabo_gp_mll_ard / pcabo_gp_fit_ard norm_bounds are the FOLDED Normalize bounds the model runs on:
+ * hi_c = lo_c + (hi_c - lo_c) l_c (the model's lengthscale is then 1). */
 int pcabo_get_gp_state(pcabo_ctx* ctx, double* K_chol /*n*n lower*/, double* Rinv /*n*n lower*/,
                        double* alpha /*n*/, double* y_mean_std /*2*/, double* norm_bounds /*2*k*/);
 int pcabo_get_gram(pcabo_ctx* ctx, double* K /*n*n, symmetric, incl. noise*/);

@@ -50,10 +50,20 @@ NOISE = 0.006737946999085467         # exp(-5), mode of the LogNormal(-4, 1) noi
 OOB_PENALTY = 1000
 
 
-def fit_gp_hyperparameters(ctx, y, Z=None, norm_bounds=None) -> dict:
-    """fit_gpytorch_mll(ExactMarginalLogLikelihood(...)) of a freshly built model, on the device (Context.gp_fit); like botorch,
-    a fit that does not converge keeps its last iterate and warns."""
-    hp = ctx.gp_fit(y, Z=Z, norm_bounds=norm_bounds, kernel=_native.KERNEL_MATERN52)
+def checked_ard(ard, fit_gp) -> bool:
+    """The `ard` keyword of PCA_BO / Vanilla_BO: one lengthscale per input is a mode of the fit."""
+    if ard and not fit_gp:
+        raise ValueError("ard=True fits one lengthscale per input: it needs fit_gp=True")
+    return bool(ard)
+
+
+def fit_gp_hyperparameters(ctx, y, Z=None, norm_bounds=None, ard=False) -> dict:
+    """fit_gpytorch_mll(ExactMarginalLogLikelihood(...)) of a freshly built model, on the device (Context.gp_fit; ard: one
+    lengthscale per input, Context.gp_fit_ard); like botorch, a fit that does not converge keeps its last iterate and warns."""
+    if ard:
+        hp = ctx.gp_fit_ard(y, Z=Z, norm_bounds=norm_bounds)
+    else:
+        hp = ctx.gp_fit(y, Z=Z, norm_bounds=norm_bounds, kernel=_native.KERNEL_MATERN52)
     if hp["warnflag"] != 0:
         warnings.warn(f"GP hyperparameter fit did not converge (warnflag {hp['warnflag']}, task {hp['task']}); keeping the last "
                       "accepted iterate", RuntimeWarning)
@@ -159,7 +169,10 @@ class PCA_BO(AbstractBayesianOptimizer):
         # by the marginal likelihood from the model's initial values before the acquisition (Context.gp_fit, DESIGN.md "GP
         # hyperparameter fit"); takes the unfused wPCA -> fit path.  False keeps the reference's fixed hyperparameters.
         self.__fit_gp = bool(kwargs.pop("fit_gp", False))
-        self.gp_hyperparameters = None     # fit_gp=True: the last fit's result (Context.gp_fit), None otherwise
+        # ard=True (needs fit_gp=True): the fit trains one lengthscale per principal component (Context.gp_fit_ard, DESIGN.md "ARD
+        # lengthscales"): Normalize stretches every component to the same unit box, and a single lengthscale cannot tell them apart
+        self.__ard = checked_ard(kwargs.pop("ard", False), self.__fit_gp)
+        self.gp_hyperparameters = None     # fit_gp=True: the last fit's result (Context.gp_fit / gp_fit_ard), None otherwise
         # ucb_beta (not in the reference, whose UCB cannot run): with acquisition_function "UCB" every iteration builds
         # UpperConfidenceBound(model, beta=ucb_beta, maximize=...), botorch's own signature.  None keeps the reference's TypeError.
         self.__ucb_beta = _acqopt.checked_ucb_beta(kwargs.pop("ucb_beta", None), acquisition_function)
@@ -432,7 +445,7 @@ class PCA_BO(AbstractBayesianOptimizer):
             self.timing_logs["SingleTaskGP"].append(perf_counter() - start)
             return
         if self.__fit_gp:                  # the fit leaves the context conditioned at the fitted hyperparameters
-            self.gp_hyperparameters = fit_gp_hyperparameters(self.__ctx, np.array(self.f_evals, dtype=np.float64))
+            self.gp_hyperparameters = fit_gp_hyperparameters(self.__ctx, np.array(self.f_evals, dtype=np.float64), ard=self.__ard)
             self.timing_logs["SingleTaskGP"].append(perf_counter() - start)
             return
         # enqueue only: the device conditions the GP while the host prepares the Sobol engine (gp_wait below)

@@ -24,7 +24,7 @@ from pcabo import initializers as _init
 from .AbstractBayesianOptimizer import AbstractBayesianOptimizer
 from .PCA_BO import (ALLOWED_ACQUISITION_FUNCTION_STRINGS, ALLOWED_SHORTHAND_ACQUISITION_FUNCTION_STRINGS,
                      AnalyticAcquisitionFunction, LogExpectedImprovement, ProbabilityOfImprovement,
-                     UpperConfidenceBound, LENGTHSCALE, NOISE, fit_gp_hyperparameters)
+                     UpperConfidenceBound, LENGTHSCALE, NOISE, fit_gp_hyperparameters, checked_ard)
 
 
 class Vanilla_BO(AbstractBayesianOptimizer):
@@ -40,6 +40,7 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         self.__gc_entered = False
         self.__resident = bool(kwargs.pop("resident", True))         # see PCA_BO: False = one launch per evaluation
         self.__fit_gp = bool(kwargs.pop("fit_gp", False))             # see PCA_BO: marginal-likelihood fit every iteration
+        self.__ard = checked_ard(kwargs.pop("ard", False), self.__fit_gp)   # see PCA_BO: one lengthscale per input
         self.gp_hyperparameters = None
         self.__ucb_beta = _acqopt.checked_ucb_beta(kwargs.pop("ucb_beta", None), acquisition_function)   # see PCA_BO
         super().__init__(budget, n_DoE, **kwargs)
@@ -146,7 +147,7 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         y = np.array(self.f_evals, dtype=np.float64)
         start = perf_counter()
         if self.__fit_gp:
-            self.gp_hyperparameters = fit_gp_hyperparameters(self.__ctx, y, Z=X, norm_bounds=self.__identity)
+            self.gp_hyperparameters = fit_gp_hyperparameters(self.__ctx, y, Z=X, norm_bounds=self.__identity, ard=self.__ard)
             self.timing_logs["SingleTaskGP"].append(perf_counter() - start)
             return
         self.__ctx.gp_condition(y, Z=X, norm_bounds=self.__identity, lengthscale=LENGTHSCALE, noise=NOISE,

@@ -8,6 +8,7 @@
 #include "lbfgsb.h"
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <condition_variable>
 #include <cstring>
@@ -151,29 +152,90 @@ inline void mll_assemble(const double* h, int n, const double* theta, double* lo
   }
 }
 
+// ARD (pcabo_gp_mll_ard / pcabo_gp_fit_ard): theta = {s2, c, rho_1 .. rho_k}, one lengthscale softplus(rho_c) per input; the sums are
+// h = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, S_1 .. S_k}, S_c = sum_ij W_ij dK_ij/dlog l_c (their sum is the
+// scalar fit's S, and equal rho is the scalar model).  Loss, prior and the s2 / c gradients are mll_assemble's expressions.
+constexpr int FIT_ARD_MAXVAR = 2 + 128;  // 2 + the largest reduced dimension (PCABO_MAXD)
+// The fit's lower bound on every rho_c: ln 2^-40, a lengthscale of 2^-40 of the Normalize range, which is where k_zstats holds a
+// folded range (below it the device no longer evaluates the model at rho_c, and K = I to rounding anyway).  The flat directions of
+// the irrelevant inputs give L-BFGS-B trial steps of thousands in rho_c; as a bound, the line search's longest step ends there
+// and backtracks, where softplus(rho_c) = 0 would end the fit by the domain stop.  No fitted model is near it.
+constexpr double FIT_ARD_RHO_MIN = -27.725887222397812;
+inline bool mll_theta_ok_ard(const double* theta, int k) {
+  const double s2 = theta[0], c = theta[1];
+  if (!(s2 > 0.0 && std::isfinite(s2) && std::isfinite(c))) return false;
+  for (int j = 0; j < k; ++j) {
+    const double ls = softplus_host(theta[2 + j]);
+    if (!(ls > 0.0 && std::isfinite(ls))) return false;
+  }
+  return true;
+}
+inline void mll_assemble_ard(const double* h, int n, int k, const double* theta, double* loss, double* grad) {
+  const double s2 = theta[0];
+  const double LOG2PI = 1.8378770664093453;
+  const double lnz = std::log(s2), u = lnz + 4.0;
+  const double log_n = -0.5 * h[1] - h[0] - 0.5 * n * LOG2PI;
+  const double log_prior = -lnz - 0.5 * LOG2PI - 0.5 * u * u;              // LogNormal(-4, 1) at s2
+  *loss = -(log_n + log_prior) / n;
+  if (grad) {
+    grad[0] = -((0.5 * (h[3] - h[4])) + (-1.0 - u) / s2) / n;
+    grad[1] = -h[2] / n;
+    for (int j = 0; j < k; ++j) {
+      const double rho = theta[2 + j], ls = softplus_host(rho);
+      const double sig = rho > 20.0 ? 1.0 : 1.0 / (1.0 + std::exp(-rho));  // d softplus / d rho (its linear branch: 1)
+      grad[2 + j] = -(0.5 * h[5 + j] * sig / ls) / n;
+    }
+  }
+}
+
 // The fit of one run: scipy.optimize.minimize(method="L-BFGS-B") with its defaults (LbfgsbDriver: the start clipped into the box,
 // scipy's memoisation of the last point, its limits) and the rules around it.  A run is STEPPING (its driver asks for evaluations),
 // at its END point (one more evaluation: the result is not the last point evaluated), RESTING at its result, or OUT (never
 // started, or failed: status says why).  A trial theta outside the model's domain (a line-search step so long that softplus(rho)
 // underflows to 0, a non-finite value) and one the factorisation cannot take end the fit abnormally at the last accepted iterate
 // (warnflag 2, task PCABO_FIT_TASK_*); when that theta is the start itself the run fails (PCABO_ERR_ARG / PCABO_ERR_NOT_PD).
-struct FitRun {
+// CAP: the most variables a run can hold.  FitRun (CAP = 3) is the scalar fit of nvar = 3 variables; the ARD fit (FitRunArd) has
+// nvar = 2 + k of its FIT_ARD_MAXVAR, picked by init_ard.  The rules are the same; the domain test and the assembly differ, and
+// every rho_c has the lower bound FIT_ARD_RHO_MIN, which keeps the line search's trial steps inside the domain.
+template <int CAP>
+struct FitRunT {
   enum { STEPPING, END, RESTING, OUT };
   LbfgsbDriver fit;
   int state = OUT, status = PCABO_ERR_ARG, stop_task = 0;
-  double xr[3] = {0, 0, 0}, fr = 0.0;  // the result and the loss there
-  const double* h = nullptr;           // where the evaluator leaves the six sums of this run (bind)
+  int nvar = 3, ard_k = 0;             // ard_k > 0: the ARD model of ard_k lengthscales
+  double xr[CAP] = {}, fr = 0.0;       // the result (nvar doubles) and the loss there
+  const double* h = nullptr;           // where the evaluator leaves the sums of this run (bind)
   void bind(const double* h_) { h = h_; }
   void init(const double* theta0) {
     const double lower[3] = {1e-4, -INFINITY, -INFINITY}, upper[3] = {INFINITY, INFINITY, INFINITY};
+    nvar = 3; ard_k = 0;
     fit.keep_accepted = true;                            // scipy's defaults and limits, the published order
     fit.init(3, theta0, lower, upper);
     state = STEPPING; status = PCABO_OK; stop_task = 0;
   }
+  void init_ard(const double* theta0, int k) {
+    static_assert(CAP == FIT_ARD_MAXVAR, "only FitRunArd holds 2 + k variables");
+    assert(k >= 1 && 2 + k <= CAP);
+    std::vector<double> lower((size_t)2 + k, -INFINITY), upper((size_t)2 + k, INFINITY);
+    lower[0] = 1e-4;
+    for (int j = 0; j < k; ++j) lower[(size_t)2 + j] = FIT_ARD_RHO_MIN;
+    nvar = 2 + k; ard_k = k;
+    for (int j = 0; j < k; ++j) {                        // a start with a lengthscale outside the domain fails; it is not clipped
+      const double ls = softplus_host(theta0[2 + j]);
+      if (!(ls > 0.0 && std::isfinite(ls))) { state = OUT; status = PCABO_ERR_ARG; stop_task = 0; return; }
+    }
+    fit.keep_accepted = true;
+    fit.init(nvar, theta0, lower.data(), upper.data());
+    state = STEPPING; status = PCABO_OK; stop_task = 0;
+  }
+  bool theta_ok(const double* th) const { return ard_k ? mll_theta_ok_ard(th, ard_k) : mll_theta_ok(th); }
+  void assemble(int n, const double* th, double* f, double* g) const {
+    if (ard_k) mll_assemble_ard(h, n, ard_k, th, f, g); else mll_assemble(h, n, th, f, g);
+  }
   // The theta to evaluate next, or null: the run has its result, or is out.
   const double* next() {
     if (state == STEPPING && !fit.advance()) finish();
-    if (state == STEPPING && !mll_theta_ok(fit.x.data())) {
+    if (state == STEPPING && !theta_ok(fit.x.data())) {
       if (fit.have_cache) { stop_task = PCABO_FIT_TASK_DOMAIN; finish(); }
       else { state = OUT; status = PCABO_ERR_ARG; }      // (the start itself)
     }
@@ -181,7 +243,7 @@ struct FitRun {
   }
   // Where a run that wants no evaluation rides along in a lock-step round: at its result, or null (out: the shared model)
   const double* rest() const { return state == RESTING ? xr : nullptr; }
-  // The outcome of evaluating the theta handed out last (next() or rest()): st, and on PCABO_OK the six sums in h
+  // The outcome of evaluating the theta handed out last (next() or rest()): st, and on PCABO_OK the sums in h
   void took(int st, int n) {
     if (state == OUT) return;
     if (state == STEPPING && st == PCABO_ERR_NOT_PD && fit.have_cache) {   // a trial theta, not the start: stop, keep the last iterate
@@ -192,10 +254,10 @@ struct FitRun {
     if (st != PCABO_OK) { state = OUT; status = st; return; }
     if (state == STEPPING) {
       double f = 0.0;
-      mll_assemble(h, n, fit.x.data(), &f, fit.g.data());
+      assemble(n, fit.x.data(), &f, fit.g.data());
       fit.absorb(f);
     } else if (state == END) {
-      mll_assemble(h, n, xr, &fr, nullptr);
+      assemble(n, xr, &fr, nullptr);
       state = RESTING;
     }
   }
@@ -211,17 +273,20 @@ struct FitRun {
   // the state is left conditioned at the result, so one more evaluation unless the result is the last point evaluated (after a
   // NOT_PD stop in any case: the state holds the trial theta's failed factorisation)
   void finish() {
-    std::memcpy(xr, stop_task ? fit.xacc.data() : fit.x.data(), sizeof(xr));
+    const size_t bytes = (size_t)nvar * sizeof(double);
+    std::memcpy(xr, stop_task ? fit.xacc.data() : fit.x.data(), bytes);
     fr = fit.fc;
-    state = (stop_task == PCABO_FIT_TASK_NOT_PD || !fit.have_cache || std::memcmp(xr, fit.xc.data(), sizeof(xr)) != 0) ? END : RESTING;
+    state = (stop_task == PCABO_FIT_TASK_NOT_PD || !fit.have_cache || std::memcmp(xr, fit.xc.data(), bytes) != 0) ? END : RESTING;
   }
 };
+typedef FitRunT<3> FitRun;
+typedef FitRunT<FIT_ARD_MAXVAR> FitRunArd;
 
 // The rounds of the runs' fits in lock-step until no run wants an evaluation: eval(th, st) evaluates run b at th[b] (null: a run
-// that is out), leaves its six sums where the run was bound and its outcome in st[b], and returns PCABO_OK or an error, which
+// that is out), leaves its sums where the run was bound and its outcome in st[b], and returns PCABO_OK or an error, which
 // ends the rounds and is returned.  n: the number of training points of every run.
-template <class Eval>
-int fit_rounds(std::vector<FitRun>& runs, int n, Eval&& eval) {
+template <class Run, class Eval>
+int fit_rounds(std::vector<Run>& runs, int n, Eval&& eval) {
   std::vector<const double*> th(runs.size(), nullptr);
   std::vector<int> st(runs.size(), PCABO_OK);
   for (;;) {

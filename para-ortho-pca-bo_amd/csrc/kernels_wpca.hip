@@ -507,7 +507,8 @@ __global__ __launch_bounds__(WP_THREADS) void k_zstats(const double* __restrict_
                                                        double* __restrict__ bounds4, double* __restrict__ zn_mean,
                                                        double* __restrict__ ystats, double* __restrict__ ys,
                                                        HostMirror* hm, const int* __restrict__ k_dev, size_t zs,
-                                                       size_t hzs, double mean_c, const double* __restrict__ hyp) {
+                                                       size_t hzs, double mean_c, const double* __restrict__ hyp,
+                                                       const double* __restrict__ ard_ls) {
   ZRUN(Z); ZRUN(y); ZRUN(user_nb); ZRUN(bounds4); ZRUN(zn_mean); ZRUN(ystats); ZRUN(ys); ZRUN(k_dev); ZRUN(hyp);
   if (hyp) mean_c = hyp[PCABO_HYP_MEAN_C];      // a batch whose runs carry their own fitted model
   hm = zrun(hm, hzs, blockIdx.z);
@@ -546,6 +547,12 @@ __global__ __launch_bounds__(WP_THREADS) void k_zstats(const double* __restrict_
     double rng = b - a;
     double nlo = a - 0.1 * rng, nhi = b + 0.1 * rng;
     if (user_nb) { nlo = user_nb[tid]; nhi = user_nb[k + tid]; }
+    // ARD fit (pcabo_gp_mll_ard, single context only): the lengthscale of this input is folded into its Normalize range, so
+    // every kernel downstream divides by (hi - lo) l_c and runs with 1 / lengthscale = 1.  The search box below is not folded.
+    // A folded range must survive the addition to lo and keep the normalised points finite: below 2^-40 of the larger of |lo|
+    // and the range it is held there.  That is a lengthscale some 1e-12 of the data's spread, where K = I to rounding just as
+    // for the exact model (a line search's trial steps reach such values; no fitted model does).
+    if (ard_ls) nhi = nlo + fmax((nhi - nlo) * ard_ls[tid], fmax(fabs(nlo), nhi - nlo) * 0x1p-40);
     double alo = a - 0.5 * rng, ahi = b + 0.5 * rng;
     if (ahi - alo < 0.1) { double mid = (ahi + alo) / 2; alo = mid - 0.1 / 2; ahi = mid + 0.1 / 2; }
     bounds4[tid] = nlo; bounds4[PCABO_MAXD + tid] = nhi;
@@ -680,9 +687,9 @@ void launch_project(hipStream_t s, const double* X, const double* data_mean, con
 }
 void launch_zstats(hipStream_t s, const double* Z, const double* y, int n, int k, const double* user_norm_bounds,
                    double* bounds4, double* zn_mean, double* ystats, double* ys, HostMirror* hm, const int* k_dev, ZB zb,
-                   double mean_c) {
+                   double mean_c, const double* ard_ls) {
   hipLaunchKernelGGL(k_zstats, dim3(1, 1, zb.B), dim3(WP_THREADS), 0, s, Z, y, n, k, user_norm_bounds, bounds4, zn_mean,
-                     ystats, ys, hm, k_dev, zb.zs, zb.hzs, mean_c, zb.hyp);
+                     ystats, ys, hm, k_dev, zb.zs, zb.hzs, mean_c, zb.hyp, ard_ls);
 }
 void launch_znorm(hipStream_t s, const double* Z, int n, int k, int NP, int KP, int ld, const double* bounds4,
                   const double* zn_mean, double inv_ls, double* ZnT, double* AT, double* nrm, const int* k_dev, ZB zb) {

@@ -108,7 +108,9 @@ struct pcabo_ctx {
   int cnt_S = 0; bool cnt_dirty = true;  // slab-group count the tickets are consistent with / a launch may have died
   double* dKS = nullptr;                 // q x ld kernel vectors of the GEMM scoring path
   double* dBestF = nullptr;              // best_f of this run for the batched acquisition launches (set by the batch)
-  double* dMll = nullptr;                // GP fit: 2 partial sums per lower 64 x 64 tile of K^-1, then the 6 results (k_mll_finish)
+  double* dMll = nullptr;                // GP fit: 2 partial sums per lower 64 x 64 tile of K^-1, then the 6 results (k_mll_finish);
+                                         // ARD: 1 + KP sums per tile, then the 5 + KP results (k_mll_finish_ard)
+  double* dArdLs = nullptr;              // ARD fit: the k lengthscales k_zstats folds into the Normalize ranges
   double* dHyp = nullptr;                // lock-step fit of a batch: this run's {1 / lengthscale, noise, mean constant} (PCABO_HYP_*)
   char *dRegion = nullptr, *hRegion = nullptr;   // the two allocations everything above / below is carved from
   size_t region_bytes = 0, hregion_bytes = 0;
@@ -117,7 +119,8 @@ struct pcabo_ctx {
   // pinned host
   HostMirror* hm = nullptr;
   double *hXq = nullptr, *hVal = nullptr, *hGrad = nullptr, *hSmall = nullptr, *hBestF = nullptr;
-  double* hMll = nullptr;                // GP fit: the 6 results of one evaluation
+  double* hMll = nullptr;                // GP fit: the 6 results of one evaluation (ARD: 5 + KP)
+  double* hArdLs = nullptr;              // ARD fit: the lengthscales on their way to dArdLs
   double* hHyp = nullptr;                // lock-step fit of a batch: the host copy of dHyp
   MailPair* dMail = nullptr;             // mailbox of the resident acquisition kernel, in device memory
   bool mail_bar = false;                 // the host can write dMail itself through the PCIe BAR (the resident mode needs it)
@@ -398,7 +401,8 @@ static size_t carve_device(pcabo_ctx* ctx, char* base) {
   ctx->dKS = c.take<double>(Q * N);        // kernel vectors of a large value-only batch (GEMM scoring)
   ctx->dCounters = c.take<unsigned int>(PCABO_CNT_DONE + 1);
   const size_t nb = N / PCABO_BS;
-  ctx->dMll = c.take<double>(nb * (nb + 1) + 8);
+  ctx->dMll = c.take<double>(std::max<size_t>(nb * (nb + 1), nb * (nb + 1) / 2 * (1 + (size_t)ctx->KPcap) + ctx->KPcap) + 8);
+  ctx->dArdLs = c.take<double>(PCABO_MAXD);
   ctx->dHyp = c.take<double>(PCABO_HYP_WORDS);
   return (c.off + 4095) & ~(size_t)4095;
 }
@@ -413,7 +417,8 @@ static size_t carve_host(pcabo_ctx* ctx, char* base) {
   ctx->hSmall = c.take<double>(d * d + 8 * d + 64);
   ctx->hIn = c.take<double>(n * (2 * d + 2));
   ctx->hBestF = c.take<double>(2);
-  ctx->hMll = c.take<double>(8);
+  ctx->hMll = c.take<double>(8 + (size_t)ctx->KPcap);
+  ctx->hArdLs = c.take<double>(PCABO_MAXD);
   ctx->hHyp = c.take<double>(PCABO_HYP_WORDS);
   return (c.off + 4095) & ~(size_t)4095;
 }
@@ -508,6 +513,7 @@ struct RowsDH {
   ZB zb;
   hipEvent_t ev[2];                      // recorded behind k_zstats (null: none): the search box is on its way to the host
   int* cnt_S; bool* cnt_dirty;           // the owner's ticket state (null: the tickets are left alone)
+  const double* ard_ls = nullptr;        // ARD fit of a single context: k lengthscales on the device, folded by k_zstats (inv_ls = 1)
 };
 template <class Phase>
 static int enqueue_factor(pcabo_ctx* ctx, hipStream_t s, int n, int NP, ZB zb, Phase&& phase) {
@@ -533,7 +539,7 @@ static int enqueue_rows_dh(pcabo_ctx* ctx, hipStream_t s, const RowsDH& a, Phase
     *a.cnt_S = acq_slabs(NP); *a.cnt_dirty = false;
   }
   if (const int rc = phase(1)) return rc;
-  launch_zstats(s, a.Z, a.y, a.n, a.k, a.unb, ctx->dBounds4, ctx->dZnMean, ctx->dYstats, ctx->dYs, ctx->hm, a.k_dev, a.zb, a.mean_c);
+  launch_zstats(s, a.Z, a.y, a.n, a.k, a.unb, ctx->dBounds4, ctx->dZnMean, ctx->dYstats, ctx->dYs, ctx->hm, a.k_dev, a.zb, a.mean_c, a.ard_ls);
   for (hipEvent_t e : a.ev) if (e) HIPCHK(hipEventRecord(e, s));
   launch_znorm(s, a.Z, a.n, a.k, NP, a.KP, ctx->ld, ctx->dBounds4, ctx->dZnMean, a.inv_ls, ctx->dZnT, ctx->dAT, ctx->dNrm, a.k_dev, a.zb);
   launch_gram(s, ctx->dAT, ctx->dNrm, a.n, NP, a.KP, ctx->ld, a.noise, a.kernel, nullptr, a.k_dev, ctx->dL, ctx->dInfo, a.zb);
@@ -752,7 +758,7 @@ int pcabo_wpca(pcabo_ctx* ctx, const double* X, const double* f, const int64_t* 
 // Rows D-H on the stream, inputs on the device.  k < 0: the reduced dimension is still on its way (the launches sit
 // right behind the wPCA) - the three kernels that need it read it from ctx->dK.
 static int enqueue_condition(pcabo_ctx* ctx, const double* y_dev, int n, int k, const double* unb, double lengthscale,
-                             double noise, int kernel, double mean_c = 0.0) {
+                             double noise, int kernel, double mean_c = 0.0, const double* ard_ls = nullptr) {
   ctx->n = n;
   ctx->NP = round_up(n, PCABO_BS);
   if (k >= 0) { ctx->k = k; ctx->KP = round_up(k, 4); }
@@ -760,7 +766,7 @@ static int enqueue_condition(pcabo_ctx* ctx, const double* y_dev, int n, int k, 
   ctx->have_gp = false;
   ctx->gp_pending = true;
   const RowsDH a{ctx->dZ, y_dev, unb, n, k, ctx->KP, k < 0 ? ctx->dK : nullptr, 1.0 / lengthscale, noise, mean_c, kernel, ZB(),
-                 {ctx->evBounds, nullptr}, &ctx->cnt_S, &ctx->cnt_dirty};
+                 {ctx->evBounds, nullptr}, &ctx->cnt_S, &ctx->cnt_dirty, ard_ls};
   return enqueue_rows_dh(ctx, ctx->stream, a, CondProf{ctx, k < 0 ? ctx->max_d : k});   // asynchronous: pcabo_gp_condition_end() waits and checks
 }
 
@@ -881,9 +887,15 @@ static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, const double* Z, co
 // The attempts of one evaluation from `attempt` on (factor_attempts): each one runs the likelihood kernels behind its
 // factorisation and copies their 6 results (48 bytes) in front of its wait.  A run of a batch whose lock-step round failed enters
 // at attempt 1.
-static int mll_attempts(pcabo_ctx* ctx, int attempt) {
-  const int rc = factor_attempts(ctx, attempt, [ctx]() -> int {
+static int mll_attempts(pcabo_ctx* ctx, int attempt, bool ard = false) {
+  const int rc = factor_attempts(ctx, attempt, [ctx, ard]() -> int {
     const int nb = ctx->NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
+    if (ard) {                           // 1 + KP sums per tile, 5 + KP results
+      double* out = ctx->dMll + (size_t)(1 + ctx->KP) * tiles;
+      launch_mll_grad_ard(ctx->stream, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
+      HOST_OUT(ctx->hMll, out, 5 + ctx->KP, double);
+      return PCABO_OK;
+    }
     double* out = ctx->dMll + 2 * (size_t)tiles;
     launch_mll_grad(ctx->stream, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
     HOST_OUT(ctx->hMll, out, 6, double);
@@ -903,6 +915,9 @@ static int mll_launch(pcabo_ctx* ctx, int n, int k, const double* unb, const dou
 }
 static int theta_domain_err(pcabo_ctx* ctx) {
   return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
+}
+static int theta_domain_err_ard(pcabo_ctx* ctx, const char* who) {
+  return set_err(ctx, PCABO_ERR_ARG, "%s: theta outside the model's domain (noise > 0, lengthscales > 0, finite values)", who);
 }
 
 static int mll_eval(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta, double* loss, double* grad) {
@@ -940,6 +955,60 @@ int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k,
   if (r.status == PCABO_ERR_ARG) return theta_domain_err(ctx);
   if (r.status != PCABO_OK) return r.status;
   memcpy(theta_inout, r.xr, sizeof(r.xr));
+  if (loss) *loss = r.fr;
+  if (info) r.report(info);
+  return PCABO_OK;
+}
+
+// ---- ARD: one lengthscale per input (DESIGN.md "ARD lengthscales") ----------------------------------------------------------
+// theta = {s2, c, rho_1 .. rho_k}.  The lengthscales softplus(rho_c) go to the device and k_zstats folds them into the Normalize
+// ranges, so the evaluation is the scalar one at lengthscale 1 on the folded ranges (ctx->lengthscale = 1: the acquisition kernels
+// read the folded bounds4 and need no change); k_mll_grad_ard adds the per-input sums.  The next conditioning call passes no
+// lengthscales and returns to the unfolded model.
+static_assert(FIT_ARD_MAXVAR == 2 + PCABO_MAXD, "host_side.h sizes an ARD run for PCABO_MAXD lengthscales");
+static int mll_launch_ard(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta) {
+  for (int c = 0; c < k; ++c) ctx->hArdLs[c] = softplus_host(theta[2 + c]);    // (the last evaluation's copy has been waited for)
+  HIPCHK(hipMemcpyAsync(ctx->dArdLs, ctx->hArdLs, (size_t)k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, 1.0, theta[0], PCABO_KERNEL_MATERN52, theta[1], ctx->dArdLs);
+  if (rc != PCABO_OK) return rc;
+  ctx->gp_pending = false;
+  return mll_attempts(ctx, 0, true);
+}
+static int ard_entry(pcabo_ctx* ctx, const char* who, const double* Z, const double* y, int n, int k, const double* norm_bounds,
+                     int kernel, const double** unb) {
+  if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch; the ARD fit is for single contexts", who);
+  return stage_fit_inputs(ctx, who, Z, y, n, k, norm_bounds, kernel, unb);
+}
+
+int pcabo_gp_mll_ard(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
+                     const double* theta, double* loss, double* grad) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (!theta || !loss) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll_ard: theta and loss are required%s", "");
+  const double* unb = nullptr;
+  int rc = ard_entry(ctx, "pcabo_gp_mll_ard", Z, y, n, k, norm_bounds, kernel, &unb);
+  if (rc != PCABO_OK) return rc;
+  if (!mll_theta_ok_ard(theta, k)) return theta_domain_err_ard(ctx, "pcabo_gp_mll_ard");
+  rc = mll_launch_ard(ctx, n, k, unb, theta);
+  if (rc != PCABO_OK) return rc;
+  mll_assemble_ard(ctx->hMll, n, k, theta, loss, grad);
+  return PCABO_OK;
+}
+
+int pcabo_gp_fit_ard(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
+                     double* theta_inout, double* loss, int* info) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (!theta_inout) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_fit_ard: theta_inout is required%s", "");
+  const double* unb = nullptr;
+  int rc = ard_entry(ctx, "pcabo_gp_fit_ard", Z, y, n, k, norm_bounds, kernel, &unb);
+  if (rc != PCABO_OK) return rc;
+  std::vector<FitRunArd> run(1);
+  run[0].init_ard(theta_inout, k);
+  run[0].bind(ctx->hMll);
+  fit_rounds(run, n, [&](const std::vector<const double*>& th, int* st) { st[0] = mll_launch_ard(ctx, n, k, unb, th[0]); return (int)PCABO_OK; });
+  const FitRunArd& r = run[0];
+  if (r.status == PCABO_ERR_ARG) return theta_domain_err_ard(ctx, "pcabo_gp_fit_ard");
+  if (r.status != PCABO_OK) return r.status;
+  memcpy(theta_inout, r.xr, (size_t)(2 + k) * sizeof(double));
   if (loss) *loss = r.fr;
   if (info) r.report(info);
   return PCABO_OK;

@@ -296,7 +296,9 @@ void launch_project(hipStream_t s, const double* X, const double* data_mean, con
 void launch_zstats(hipStream_t s, const double* Z, const double* y, int n, int k, const double* user_norm_bounds,
                    double* bounds4 /*norm_lo,norm_hi,acq_lo,acq_hi each MAXD*/, double* zn_mean, double* ystats,
                    double* ys, HostMirror* hm, const int* k_dev = nullptr, ZB zb = ZB(),
-                   double mean_c = 0.0);   // mean_c: constant mean of a fitted GP (y_s and the statistics carry m + s c)
+                   double mean_c = 0.0,    // mean_c: constant mean of a fitted GP (y_s and the statistics carry m + s c)
+                   const double* ard_ls = nullptr);   // ARD fit: k lengthscales on the device, folded into the Normalize ranges
+                                                      // (norm_hi = norm_lo + (norm_hi - norm_lo) l_c; null: nothing changes)
 void launch_znorm(hipStream_t s, const double* Z, int n, int k, int NP, int KP, int ld, const double* bounds4,
                   const double* zn_mean, double inv_ls, double* ZnT, double* AT, double* nrm,
                   const int* k_dev = nullptr, ZB zb = ZB());   // k_dev != NULL: k (and KP) are read on the device, the arguments ignored
@@ -318,6 +320,10 @@ void launch_alpha(hipStream_t s, const double* R, const double* ys, int n, int N
 void launch_mll_grad(hipStream_t s, const double* R, const double* AT, const double* nrm, const double* alpha, const double* L,
                      const double* ys, int n, int NP, int KP, int ld, double* partial, double* out,
                      const int* k_dev = nullptr, ZB zb = ZB());
+// the ARD form (one lengthscale per input, folded into the Normalize ranges of a single context): partial = 1 + KP doubles per
+// tile, out[5 + KP] = {the first five sums above, S_c = sum_ij W_ij dK_ij/dlog l_c for c < KP}
+void launch_mll_grad_ard(hipStream_t s, const double* R, const double* AT, const double* nrm, const double* alpha, const double* L,
+                         const double* ys, int n, int NP, int KP, int ld, double* partial, double* out);
 void launch_acq(hipStream_t s, const QueryArgs* qa, const double* Xq, int q, int n, int k, int NP, int ld,
                 const double* ZnT, const double* R, const double* alpha, const double* bounds4, const double* ystats,
                 AcqParams p, double* partial, unsigned int* counters, double* val,

@@ -37,6 +37,9 @@ def parse_arguments(argv=None):
     p.add_argument("--fit_gp", action="store_true",
                    help="fit the GP's noise, mean constant and lengthscale by the marginal likelihood every iteration (not in the "
                         "reference, which keeps them fixed; not with --batched)")
+    p.add_argument("--ard", action="store_true",
+                   help="with --fit_gp: one lengthscale per input (automatic relevance determination) instead of one for all; "
+                        "not with --batched")
     p.add_argument("--batched_fit_gp", action="store_true",
                    help="the same fit inside the lock-step batches (needs --batched > 1): the runs of a batch fit side by side, "
                         "one launch sequence per round, and write the rows --fit_gp writes one run after the other")
@@ -57,7 +60,7 @@ def main():
         budget_factor=a.budget_factor, doe_factor=a.doe_factor, root_dir=os.getcwd(), experiment_name=a.experiment_dir,
         acquisition_function=a.acquisition, pca_components=0, var_threshold=a.var_threshold, verbose=a.verbose,
         progress=(rank == 0), batched=a.batched, side_by_side=a.side_by_side, batch_acq_kernel=a.batch_acq_kernel,
-        fit_gp=a.fit_gp, batched_fit_gp=a.batched_fit_gp, ucb_beta=a.ucb_beta)
+        fit_gp=a.fit_gp, batched_fit_gp=a.batched_fit_gp, ucb_beta=a.ucb_beta, ard=a.ard)
     t0 = time.time()
     experiment.run_experiment()
     dt = time.time() - t0

@@ -49,7 +49,7 @@ EXPORTS = [
     "pcabo_abi_version", "pcabo_device_count", "pcabo_ctx_create", "pcabo_ctx_destroy",
     "pcabo_set_pointer_mode", "pcabo_set_option", "pcabo_last_error", "pcabo_wpca", "pcabo_gp_condition", "pcabo_gp_condition_begin",
     "pcabo_gp_condition_end", "pcabo_gp_condition_end_eval", "pcabo_wpca_gp_condition_begin", "pcabo_wpca_results",
-    "pcabo_gp_mll", "pcabo_gp_fit",
+    "pcabo_gp_mll", "pcabo_gp_fit", "pcabo_gp_mll_ard", "pcabo_gp_fit_ard",
     "pcabo_acq_bounds",
     "pcabo_acq_eval", "pcabo_logei", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
     "pcabo_get_gram", "pcabo_lbfgsb_minimize", "pcabo_lbfgsb_set_vector_kernels", "pcabo_lbfgsb_set_sum_order", "pcabo_sobol_scramble", "pcabo_sobol_draw", "pcabo_sobol_draw_rows", "pcabo_torch_randint2", "pcabo_torch_multinomial_rows", "pcabo_boltzmann_pick_rows", "pcabo_set_profiling",
@@ -103,6 +103,8 @@ def _load() -> C.CDLL:
     lib.pcabo_gp_condition_end.argtypes = [vp]
     lib.pcabo_gp_mll.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, dp, vp]
     lib.pcabo_gp_fit.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, dp, vp]
+    lib.pcabo_gp_mll_ard.argtypes = lib.pcabo_gp_mll.argtypes
+    lib.pcabo_gp_fit_ard.argtypes = lib.pcabo_gp_fit.argtypes
     lib.pcabo_wpca_results.argtypes = [vp, vp, vp, vp, vp, ip]
     lib.pcabo_gp_condition_end_eval.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp]
     lib.pcabo_wpca_gp_condition_begin.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp,
@@ -344,6 +346,46 @@ class Context:
                                    _ptr(info)))
         self.n, self.k = y.shape[0], k
         return {**self._fit_result(th, loss.value), "iterations": int(info[0]), "evaluations": int(info[1]),
+                "warnflag": int(info[2]), "task": int(info[3])}
+
+    # ---- the same fit with one lengthscale per input (pcabo_gp_mll_ard / pcabo_gp_fit_ard) ------
+    @staticmethod
+    def _fit_result_ard(theta, loss):
+        rho = theta[2:]                                 # softplus as torch (and the library) compute it
+        ls = np.where(rho > 20.0, rho, np.log1p(np.exp(np.minimum(rho, 20.0))))
+        return {"lengthscales": ls, "noise": float(theta[0]), "mean_constant": float(theta[1]), "loss": float(loss),
+                "theta": theta.copy()}
+
+    @staticmethod
+    def _theta_ard(theta, k):
+        if theta is None:                               # a freshly built model: (noise, mean constant, rho_1 .. rho_k = 0)
+            return np.array(FIT_THETA0[:2] + (0.0,) * k, dtype=np.float64)
+        return _f64(theta, (2 + k,)).copy()
+
+    def gp_mll_ard(self, y, theta, Z=None, norm_bounds=None, kernel=KERNEL_MATERN52):
+        """Loss of the ARD fit and its gradient at theta = (noise, mean constant, rho_1 .. rho_k), lengthscale_c =
+        softplus(rho_c); the context is left conditioned at theta (the lengthscales folded into the Normalize ranges, which
+        gp_state() then reports).  Returns `lengthscales` (k,), `noise`, `mean_constant`, `loss`, `theta` and `grad` (2 + k,)."""
+        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
+        th = self._theta_ard(theta, k)
+        loss, g = C.c_double(0.0), np.empty(2 + k)
+        self._chk(LIB.pcabo_gp_mll_ard(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th),
+                                       C.byref(loss), _ptr(g)))
+        self.n, self.k = y.shape[0], k
+        return {**self._fit_result_ard(th, loss.value), "grad": g}
+
+    def gp_fit_ard(self, y, theta0=None, Z=None, norm_bounds=None, kernel=KERNEL_MATERN52):
+        """gp_fit with one lengthscale per input, from theta0 (default: the model's initial values, every rho_c = 0).  Returns
+        `theta`, `noise`, `mean_constant`, `lengthscales` (k,), `loss`, `iterations`, `evaluations`, `warnflag`, `task`; the
+        context is left conditioned at the fit.  The fit keeps every rho_c >= ln 2^-40 = -27.73 (an optimiser bound like the
+        noise's 1e-4; a start below it is clipped to it)."""
+        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
+        th = self._theta_ard(theta0, k)
+        loss, info = C.c_double(0.0), np.zeros(4, dtype=np.int32)
+        self._chk(LIB.pcabo_gp_fit_ard(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th),
+                                       C.byref(loss), _ptr(info)))
+        self.n, self.k = y.shape[0], k
+        return {**self._fit_result_ard(th, loss.value), "iterations": int(info[0]), "evaluations": int(info[1]),
                 "warnflag": int(info[2]), "task": int(info[3])}
 
     def gp_wait(self) -> None:

@@ -60,7 +60,10 @@ class BatchedPCABO:
                  maximization: bool = False, device: int = 0, num_restarts: int = 10, raw_samples: int = 512,
                  record_trace: bool = False, host_threads: int = 0, device_objective: bool = False, workers: int = 0,
                  trace_filter=None, acq_kernel: str = "group", lbfgsb_cus: int = 0, torch_threads: Optional[int] = 4,
-                 gc_freeze: bool = True, fit_gp: bool = False, ucb_beta: Optional[float] = None):
+                 gc_freeze: bool = True, fit_gp: bool = False, ucb_beta: Optional[float] = None, ard: bool = False):
+        if ard:                            # (the lock-step fit has one lengthscale per run: DESIGN.md "ARD lengthscales", scope)
+            raise ValueError("ard=True is a mode of the single-run classes Algorithms.PCA_BO / Vanilla_BO (fit_gp=True, ard=True): "
+                             "the lock-step batches fit one lengthscale")
         self.problems, self.seeds = list(problems), [int(s) for s in seeds]
         self.B = len(self.problems)
         assert self.B == len(self.seeds) and self.B >= 1
