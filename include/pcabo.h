@@ -103,7 +103,9 @@ int pcabo_wpca(pcabo_ctx* ctx, const double* X, const double* f, const int64_t* 
  *   y[n]             [bulk] objective values (un-standardised)
  *   norm_bounds[2*k] [host] Normalize bounds (lo row, hi row) or NULL for PCA_BO.py:514-518
  *   lengthscale, noise: model constants (reference values: ln 2 and exp(-5)); kernel: PCABO_KERNEL_*
- * On Cholesky breakdown jitter 1e-8, 1e-7, 1e-6 is added (psd_safe_cholesky) before PCABO_ERR_NOT_PD. */
+ * On Cholesky breakdown jitter 1e-8, 1e-7, 1e-6 is added (psd_safe_cholesky) before PCABO_ERR_NOT_PD.
+ * A K that is not finite - a column of Z in which all points agree and no norm_bounds: a Normalize range of 0 - ends
+ * there too (gpytorch raises on the NaN); the context then holds no GP until the next successful conditioning. */
 int pcabo_gp_condition(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k,
                        const double* norm_bounds, double lengthscale, double noise, int kernel);
 

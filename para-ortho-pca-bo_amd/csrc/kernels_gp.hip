@@ -58,11 +58,13 @@ __global__ __launch_bounds__(256) void k_gram(const double* __restrict__ AT, con
         v = (i == j) ? 1.0 : 0.0;
       } else {
         double sq = (i == j) ? 0.0 : (nrm[i] + nj) - 2.0 * acc[t][r];
-        sq = fmax(sq, 0.0);
+        // (the clamps keep a NaN - a Normalize range of 0, 0 / 0 in k_znorm - where fmax would turn it into a distance of 0 and
+        // K into a matrix of ones that factors: the NaN has to reach a pivot, PCABO_ERR_NOT_PD; finite values: the same bits)
+        sq = sq < 0.0 ? 0.0 : sq;
         if (kernel == 1) {
           v = exp(-0.5 * sq);
         } else {
-          double dist = sqrt(fmax(sq, 1e-30));
+          double dist = sqrt(sq < 1e-30 ? 1e-30 : sq);
           v = ((s5 * dist + 1.0) + (5.0 / 3.0) * (dist * dist)) * exp(-s5 * dist);
         }
         if (i == j) v += noise;

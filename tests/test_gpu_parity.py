@@ -169,19 +169,34 @@ def test_rbf_kernel_and_user_bounds(native):
     c.close()
 
 
-def test_not_positive_definite_is_reported(native):
-    """Duplicate points with zero noise: K is singular; jitter retries (1e-8..1e-6) then -2 or success."""
-    Z = np.tile(np.array([[0.1, 0.2]]), (40, 1))
-    Z[::2] += 0.5
-    y = np.arange(40.0)
-    c = native.Context(max_n=64, max_d=4, max_q=16)
-    try:
-        c.gp_condition(y, Z=Z, noise=0.0)
-        st = c.gp_state()
-        assert np.isfinite(st["L"]).all()          # accepted only with jitter on the diagonal
-    except native.PcaboError as e:
-        assert e.code == -2
-    c.close()
+def test_not_positive_definite_is_reported(native, capsys):
+    """Duplicate points with zero noise: K is singular up to rounding, psd_safe_cholesky's ladder (0, 1e-8, 1e-7, 1e-6)
+    decides.  Through the API (noise >= 0) a Gram matrix can only be rounding-indefinite: rung 0 goes either way, by the
+    last bit of a pivot, and is not pinned; a decisively indefinite K cannot be built, so PCABO_ERR_NOT_PD itself is
+    reached only through NaN (test_gpu_gp_edges.py).  Rung 1 is decisively positive definite for all three inputs
+    (tests/test_gp_reference_cpu.py: lambda_min(K + 1e-8 I) >= 1e3 n eps ||K||), so on the 40-point twins, on 130 points
+    paired across the tile boundary (i, i + 65) and on near-duplicates 1e-9 apart the call MUST succeed, at a rung <= 1e-8
+    read off the factor itself (median of diag(L L^T) - diag(gram()), within 1e-12 of a rung), with |L L^T - (K + j I)|,
+    R and alpha within 16 units of the extended-precision factorisation of K + j I (tests/gp_reference.py)."""
+    import ctypes as C
+    import gp_reference as G
+    lines = []
+    for case in G.jitter_cases():
+        n = case.n
+        c = native.Context(max_n=max(n, 64), max_d=4, max_q=16)
+        c.gp_condition(case.y, Z=case.Z, noise=0.0)                     # must not raise
+        L, R, alpha, ys = np.empty((n, n)), np.empty((n, n)), np.empty(n), np.empty(2)   # (no np.tril: the upper triangles too)
+        c._chk(native.LIB.pcabo_get_gp_state(c._h, *[a.ctypes.data_as(C.c_void_p) for a in (L, R, alpha, ys)], None))
+        K = c.gram()
+        c.close()
+        j = G.judge_ladder(case, K, L, R, alpha, ys[0], ys[1])
+        lines.append("  %-9s rung %-6g (seen %.3e)  %s" % (case.id, j.rung, j.seen, "  ".join("%s %.3g" % kv for kv in j.ratios.items())))
+        assert j.finite, case.id                                        # accepted only with a factor that is one
+        assert abs(j.seen - j.rung) <= 1e-12 and j.rung <= 1e-8, (case.id, j.seen, j.rung)
+        assert j.flags_ok, case.id
+        assert all(v <= 16.0 for v in j.ratios.values()), (case.id, j.rung, j.ratios)
+    with capsys.disabled():
+        print("\njitter ladder, device / reference units\n" + "\n".join(lines))
 
 
 def test_scoring_enqueued_behind_the_conditioning_equals_wait_then_score(native):
@@ -952,14 +967,17 @@ def test_acq_group_bits_are_pinned(native):
         assert got[case] == golden[case], case
 
 
-@pytest.mark.parametrize("n,k,B", [(450, 20, 34), (1050, 30, 17), (200, 6, 70), (450, 12, 136)])
+@pytest.mark.parametrize("n,k,B", [(450, 20, 34), (1050, 30, 17), (200, 6, 70), (450, 12, 136),
+                                   (64, 3, 257), (65, 3, 129), (129, 5, 86), (129, 5, 342)])
 def test_oversubscribed_batch_factors_equal_the_single_context_bit_for_bit(native, n, k, B):
     """launch_cholesky has two forms: one launch per panel (k_chol_step: single runs, small batches) and, once a batch holds more
     tile rows than the chip has CUs (B * nblk > 256), look-backs + panel launches - over groups of two block columns up to 1 024
     tile rows (k_chol_lookn, round 4: the row tiles L[I][p] read once per group), column by column beyond (k_chol_lookback); all
     with XCD-aware tile placement.  Both accumulate a panel's products from zero
     and subtract panels in ascending order, so a run's L, R and alpha must be the SAME BITS in a batch of any size and alone -
-    the invariant the batch drivers, the sharded runner and tests/golden/gp_factor_hashes.json rest on."""
+    the invariant the batch drivers, the sharded runner and tests/golden/gp_factor_hashes.json rest on.
+    The last four cases are the forms at their smallest shapes: nblk = 1 (only panel launches), nblk = 2 (one k_chol_lookn
+    group), nblk = 3 (a group and a single-column tail) and nblk = 3 beyond 1 024 tile rows (k_chol_lookback)."""
     from pcabo import _native as N
     rng = np.random.default_rng(1000 * n + B)
     Z = rng.uniform(0, 1, (B, n, k))

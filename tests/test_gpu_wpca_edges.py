@@ -312,7 +312,8 @@ def test_bounds_statistics_and_inverse_map(ctx, capsys):
     `k_zstats`) and n = 450 (both), boxes narrower than 0.1 (`shifted`, the small components of `cluster`) and
     wider.  norm_bounds / acq_bounds against oracle.normalize_bounds / acq_bounds of the device's Z to
     4 eps max(|zmin|, |zmax|, |rng|); y_mean, y_std and inverse_map against extended precision, limit 16.
-    `k_znorm` has no getter: gp_condition() runs it, nothing here reads its output.
+    `k_znorm` has no getter: gp_condition() runs it, nothing here reads its output (`test_gpu_gp_edges.py` judges it
+    through K).
 
     The round trip inverse_map(Z[i]) ~ X[i] is NOT checked: its bound sqrt(sum_dead rho) sqrt(n / w_min) is
     infinite, the worst-ranked point has weight ln n - ln n = 0."""
