@@ -72,9 +72,15 @@ int pcabo_last_error(pcabo_ctx* ctx, char* buf, int buflen);
  * PCABO_OPT_GROUP_ACQ (default 0; 1 for the contexts of a batch): value+gradient evaluations of up to 32 points run through the
  *   throughput kernel (one work-group per restart group of <= 5 points and 64-row slab) instead of the per-query
  *   latency kernels; implies one launch per evaluation.  Same formulas, another summation order (~1e-15 relative), so a
- *   run is bit-reproducible within a mode, not across modes. */
+ *   run is bit-reproducible within a mode, not across modes.
+ * PCABO_OPT_HIDDEN_TAIL (default 1; no effect on the contexts of a batch): work of an iteration that need not sit behind the
+ *   factorisation is taken off the main stream's chain.  pcabo_gp_condition_end_eval copies the samples and forms their kernel
+ *   vectors on a second stream of the context beside the Cholesky (they need only the Normalize bounds and ZnT; the sums with
+ *   alpha follow behind it), and pcabo_inverse_map runs on the host from the pinned wPCA results (no launch, no wait).
+ *   0 = one stream and the k_inverse_map launch.  Same operations in the same order per element: same bits. */
 enum { PCABO_OPT_RESIDENT = 0, PCABO_OPT_BESTF_F32 = 1, PCABO_OPT_GROUP_ACQ = 2,
-       PCABO_OPT_DEVICE_LBFGSB = 3, PCABO_OPT_LBFGSB_CUS = 4 /* batches only, see pcabo_batch_set_option */ };
+       PCABO_OPT_DEVICE_LBFGSB = 3, PCABO_OPT_LBFGSB_CUS = 4 /* batches only, see pcabo_batch_set_option */,
+       PCABO_OPT_HIDDEN_TAIL = 5 };
 int pcabo_set_option(pcabo_ctx* ctx, int option, int value);
 
 /* Rows A-C (+D,J): rank-weighted PCA of the evaluated points.

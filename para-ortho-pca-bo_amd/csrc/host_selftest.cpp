@@ -525,6 +525,44 @@ void test_fit_run() {
   }
 }
 
+// The host's inverse map (host_side.h) against the loop of k_inverse_map written out coordinate by coordinate: one fused
+// multiply-add per term, c ascending, then the two means.  Bytes equal, for both forms of the chain, at the edges of the kernel's
+// 8-way unroll and with exact and signed zeros; one case whose result differs between a fused and an unfused multiply-add.
+void test_inverse_map_host() {
+  const auto reference = [](const double* z, const double* comps, const double* pm, const double* dm, int k, int d, double* x) {
+    for (int j = 0; j < d; ++j) {
+      double s = 0.0;
+      for (int c = 0; c < k; ++c) s = std::fma(z[c], comps[(size_t)c * d + j], s);
+      x[j] = (s + pm[j]) + dm[j];
+    }
+  };
+  for (int k : {1, 7, 8, 9, 36, 40})
+    for (int d : {1, 40, 100}) {
+      Lcg r(1000 * k + d);
+      std::vector<double> z(k), comps((size_t)k * d), pm(d), dm(d), x(d), xs(d), xr(d);
+      for (int rep = 0; rep < 51; ++rep) {
+        for (auto& v : z) v = 2e3 * r.uni() - 1e3;
+        for (auto& v : comps) v = 2.0 * r.uni() - 1.0;
+        for (auto& v : pm) v = 2.0 * r.uni() - 1.0;
+        for (auto& v : dm) v = 10.0 * r.uni() - 5.0;
+        if (rep == 50) {                                   // exact zeros and signed zeros
+          for (int c = 0; c < k; ++c) z[c] = (c & 1) ? -0.0 : 0.0;
+          for (size_t i = 0; i < comps.size(); i += 3) comps[i] = (i & 1) ? -0.0 : 0.0;
+          for (int j = 0; j < d; ++j) { pm[j] = (j & 1) ? -0.0 : 0.0; dm[j] = (j & 2) ? -0.0 : 0.0; }
+        }
+        reference(z.data(), comps.data(), pm.data(), dm.data(), k, d, xr.data());
+        inverse_map_host(z.data(), comps.data(), pm.data(), dm.data(), k, d, x.data());
+        inverse_map_host(z.data(), comps.data(), pm.data(), dm.data(), k, d, xs.data(), false);
+        CHECK(std::memcmp(x.data(), xr.data(), d * sizeof(double)) == 0, "inverse map k %d d %d rep %d: not the fused chain's bits", k, d, rep);
+        CHECK(std::memcmp(xs.data(), xr.data(), d * sizeof(double)) == 0, "inverse map k %d d %d rep %d: std::fma form differs", k, d, rep);
+      }
+    }
+  const double e30 = std::ldexp(1.0, -30), z[2] = {-(1.0 + 2.0 * e30), 1.0 + e30}, comps[2] = {1.0, 1.0 + e30}, zero = 0.0;
+  double x = -1.0;
+  inverse_map_host(z, comps, &zero, &zero, 2, 1, &x);
+  CHECK(x == std::ldexp(1.0, -60), "inverse map: the chain is not fused (got %g, an unfused product gives 0)", x);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -536,6 +574,7 @@ int main(int argc, char** argv) {
   test_plan();
   test_restart_group();
   test_fit_run();
+  test_inverse_map_host();
   test_gang_pool(1, 3);
   test_gang_pool(workers, 11);
   if (g_fail) { std::fprintf(stderr, "host selftest: %d check(s) failed\n", g_fail); return 1; }

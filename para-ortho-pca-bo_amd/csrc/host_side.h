@@ -352,3 +352,38 @@ struct GangPool {
     quit = false;
   }
 };
+
+// Row O on the host, x = z Ck + m_w + mu_x (PCA_BO.py:427), with the bits of k_inverse_map: per coordinate j the device runs
+// s = fma(z[c], comps[c][j], s) from s = 0 with c ascending (its `s += z[c] * comps[c][j]` compiles to one fused multiply-add per
+// term), then (s + pca_mean[j]) + data_mean[j] in two plain additions.  A fused multiply-add rounds once wherever it runs, so
+// the host's chain gives the same x; the loops are turned round (c outside, j along the row of comps) which changes no
+// coordinate's order.  x doubles as the accumulator.  With the FMA instruction set the inner loop is a vector fma; without it
+// std::fma computes the same correctly rounded result term by term.
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+#define PCABO_HOST_FMA_ISA 1
+__attribute__((target("fma"))) inline void inverse_map_chain_fma(const double* z, const double* comps, int k, int d, double* x) {
+  for (int c = 0; c < k; ++c) {
+    const double zc = z[c];
+    const double* row = comps + (size_t)c * d;
+    for (int j = 0; j < d; ++j) x[j] = __builtin_fma(zc, row[j], x[j]);
+  }
+}
+#endif
+inline void inverse_map_chain(const double* z, const double* comps, int k, int d, double* x) {
+  for (int c = 0; c < k; ++c) {
+    const double zc = z[c];
+    const double* row = comps + (size_t)c * d;
+    for (int j = 0; j < d; ++j) x[j] = std::fma(zc, row[j], x[j]);
+  }
+}
+inline void inverse_map_host(const double* z, const double* comps, const double* pca_mean, const double* data_mean, int k, int d,
+                             double* x, bool allow_isa = true) {
+  for (int j = 0; j < d; ++j) x[j] = 0.0;
+#ifdef PCABO_HOST_FMA_ISA
+  static const bool have_fma = __builtin_cpu_supports("fma");
+  if (allow_isa && have_fma) inverse_map_chain_fma(z, comps, k, d, x);
+  else
+#endif
+    inverse_map_chain(z, comps, k, d, x);
+  for (int j = 0; j < d; ++j) x[j] = (x[j] + pca_mean[j]) + data_mean[j];
+}

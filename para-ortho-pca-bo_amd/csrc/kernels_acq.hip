@@ -1470,6 +1470,90 @@ __global__ __launch_bounds__(256) void k_score_gemm(const double* __restrict__ R
 
 bool score_gemm_possible(int q) { return q >= 64; }
 
+// k_score_ks in two halves, for a single context that forms the kernel vectors on a second stream while alpha and R are still
+// being computed (pcabo_gp_condition_end_eval).  Each half keeps k_score_ks' operations and their order per element, so KS and the
+// mu_s records have its bits:
+//   k_score_ks_only  the kernel-vector half - the samples, ZnT, the Normalize bounds and the hyper-parameters, no alpha;
+//   k_score_mu       the mu_s half - lane j of block (jb, 16 samples) reads back the ks that lane j of k_score_ks held (0 beyond n),
+//                    multiplies by alpha_j, wave_sum per 64 points, the four waves added in order, slot 1 of record jb.
+__global__ __launch_bounds__(256) void k_score_ks_only(const double* __restrict__ Xq, int q_total, int n, int k, int NP, int ld,
+                                                       const double* __restrict__ ZnT, const double* __restrict__ bounds4,
+                                                       AcqParams prm, double* __restrict__ KS) {
+  __shared__ double s_xn[SC_QB][PCABO_MAXD];
+  const int tid = threadIdx.x;
+  const int j = blockIdx.x * 256 + tid, q0 = blockIdx.y * SC_QB;
+  for (int idx = tid; idx < SC_QB * k; idx += 256) {
+    const int q = idx / k, c = idx - q * k;
+    const int qq = q0 + q < q_total ? q0 + q : q_total - 1;
+    const double lo = bounds4[c], hi = bounds4[PCABO_MAXD + c];
+    s_xn[q][c] = (Xq[(size_t)qq * k + c] - lo) / (hi - lo);
+  }
+  __syncthreads();
+  double sq[SC_QB];
+#pragma unroll
+  for (int q = 0; q < SC_QB; ++q) sq[q] = 0.0;
+  if (j < n) {
+    for (int c0 = 0; c0 < k; c0 += 8) {
+      double z[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) z[u] = (c0 + u < k) ? ZnT[(size_t)(c0 + u) * ld + j] : 0.0;
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (c0 + u < k) {
+#pragma unroll
+          for (int q = 0; q < SC_QB; ++q) { const double d = s_xn[q][c0 + u] - z[u]; sq[q] += d * d; }
+        }
+    }
+  }
+  const double inv_ls = prm.inv_ls, s5 = 2.23606797749979;
+#pragma unroll
+  for (int q = 0; q < SC_QB; ++q) {
+    double ks = 0.0;
+    if (j < n) {
+      const double sqq = sq[q] * (inv_ls * inv_ls);
+      if (prm.kernel == 1) ks = exp(-0.5 * sqq);
+      else {
+        const double dist = sqrt(fmax(sqq, 1e-30));
+        ks = ((s5 * dist + 1.0) + (5.0 / 3.0) * (dist * dist)) * exp(-s5 * dist);
+      }
+    }
+    if (j < NP && q0 + q < q_total) KS[(size_t)(q0 + q) * ld + j] = ks;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_score_mu(const double* __restrict__ KS, int q_total, int n, int ld,
+                                                  const double* __restrict__ alpha, double* __restrict__ partial, int S) {
+  __shared__ double s_mu[4][SC_QB];
+  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
+  const int j = blockIdx.x * 256 + tid, q0 = blockIdx.y * SC_QB;
+  const double aj = j < n ? alpha[j] : 0.0;
+#pragma unroll
+  for (int q = 0; q < SC_QB; ++q) {
+    const double ks = (j < n && q0 + q < q_total) ? KS[(size_t)(q0 + q) * ld + j] : 0.0;
+    const double m = wave_sum(aj * ks);
+    if (l == 0) s_mu[w][q] = m;
+  }
+  __syncthreads();
+  if (tid < SC_QB && q0 + tid < q_total)
+    partial[((size_t)(q0 + tid) * S + blockIdx.x) * PSTRIDE + 1] = ((s_mu[0][tid] + s_mu[1][tid]) + s_mu[2][tid]) + s_mu[3][tid];
+}
+
+void launch_score_ks_only(hipStream_t st, const double* Xq, int q, int n, int k, int NP, int ld, const double* ZnT,
+                          const double* bounds4, AcqParams p, double* KS) {
+  const int njb = (NP + 255) / 256;
+  hipLaunchKernelGGL(k_score_ks_only, dim3(njb, (q + SC_QB - 1) / SC_QB, 1), dim3(256), 0, st, Xq, q, n, k, NP, ld, ZnT, bounds4, p, KS);
+}
+// launch_score behind launch_score_ks_only: the mu_s records, V = R KS^T, the scalar chain per sample
+void launch_score_tail(hipStream_t st, int q, int n, int k, int NP, int ld, const double* R, const double* alpha,
+                       const double* bounds4, const double* ystats, AcqParams p, const double* KS, double* partial, double* val) {
+  const int S = NP / 64, njb = (NP + 255) / 256;
+  hipLaunchKernelGGL(k_score_mu, dim3(njb, (q + SC_QB - 1) / SC_QB, 1), dim3(256), 0, st, KS, q, n, ld, alpha, partial, S);
+  hipLaunchKernelGGL(k_score_gemm, dim3(S, (q + 63) / 64, 1), dim3(256), 0, st, R, KS, q, NP, ld, njb, partial, (size_t)0);
+  p.want_grad = 0;
+  hipLaunchKernelGGL(k_acq_combine, dim3((q + 3) / 4, 1, 1), dim3(256), 0, st, partial, q, S, k, bounds4, ystats, p, val,
+                     (double*)nullptr, AcqBatch());
+}
+
 // Value-only scoring of q >= 64 points: KS, then V = R KS^T on MFMA, then the scalar chain per query (k_acq_combine).
 void launch_score(hipStream_t st, const double* Xq, int q, int n, int k, int NP, int ld, const double* ZnT, const double* R,
                   const double* alpha, const double* bounds4, const double* ystats, AcqParams p, double* KS, double* partial,

@@ -410,7 +410,8 @@ void launch_gram(hipStream_t s, const double* AT, const double* nrm, int n, int 
 void launch_add_jitter(hipStream_t s, double* K, int n, int ld, double jitter) {
   hipLaunchKernelGGL(k_add_jitter, dim3((n + 255) / 256), dim3(256), 0, s, K, n, ld, jitter);
 }
-int launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb) {
+bool chol_step_form(int NP, ZB zb) { return zb.B * (NP / BS) <= 256; }
+int launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb, double* R_folded) {
   const int nblk = NP / BS;
   // Two forms of the same left-looking factorisation, bit-identical (tests/golden/gp_factor_hashes.json):
   //  * k_chol_step (kernels_gpw.hip): ONE launch per panel - final update + panel of column J beside the look-ahead of
@@ -422,7 +423,8 @@ int launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double*
   //  * round 4, the oversubscribed case in groups of NC = 4 block columns (k_chol_lookn): one look-back over all earlier panels
   //    for the four columns together (the row tiles L[I][p] read once instead of four times), then per panel of the group the
   //    panel launch and one single-step update of the group's remaining columns - the same number of launches, the same bits.
-  if (zb.B * nblk <= 256) return launch_chol_steps(s, L, NP, ld, info, diag_scratch, zb);
+  if (chol_step_form(NP, zb)) return launch_chol_steps(s, L, NP, ld, info, diag_scratch, zb, R_folded);
+  if (R_folded) return -1;                            // (the caller asks chol_step_form first)
   if (zb.B * nblk > 1024) {
     // several waves of work-groups per launch: two independent 4-wave groups per CU overlap one's loads with the other's MFMAs
     // better than one 8-wave group in lock-step (measured round 4, us: 120 runs at n = 1050: 2 468 against 2 602 grouped; the

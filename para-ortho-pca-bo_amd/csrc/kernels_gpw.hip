@@ -254,14 +254,137 @@ __global__ __launch_bounds__(128) void k_chol_panel_m(double* __restrict__ A, in
 // Per element the arithmetic is what it was: the products of panel p accumulate from zero over ascending k on
 // v_mfma_f64_16x16x4 and are then subtracted from the tile, panels in ascending order (the value just passes through
 // memory between p = J-2 and p = J-1) - tests/golden/gp_factor_hashes.json holds bit for bit.
+//
+// A single context also folds the root inverse R = L^-1 into these launches (Rinv != null), work that used to
+// sit behind the last panel as k_trinv_diag_w + k_trinv_cols although most of it depends only on panels finished long before:
+//   * wave 2 of panel group 0 inverts the diagonal block, k_trinv_diag_w's right-looking substitution with a column of the
+//     inverse per lane, reading the finished columns of the factor from the LDS tile one 16-column sub-panel behind wave 0 (the
+//     way wave 1's solve follows it) and writing the diagonal tile of R; the rows below the sub-panel's own 16 take its steps on
+//     the matrix cores, as wave 0's trailing updates do (panel_m_inverse_step);
+//   * launch J carries 4 (J-1) more groups, one per 16-column chunk left of the diagonal, for row block J-1 of R:
+//     S = - sum_K L[J-1][K] X_K, X_{J-1} = Rdiag_{J-1} S - k_trinv_cols' MFMA sequence for that block row.  Everything they read
+//     was final when launch J-1 ended: L[J-1][K] after launch K, Rdiag_{J-1} from launch J-1, the rows above from launches <= J-1.
+// The last row block follows in one drain launch (k_trinv_rowblock).  Per element the operations and their order are those of
+// the two separate kernels: same bits.  Ordering comes from the launch order alone.
 #define SLD PCABO_TLD
+// wave 2 of panel group 0, sub-panel JB.  Lane c holds column c of the inverse X for the 16 rows of block JB and runs their steps
+//   x[m] *= 1 / L[m][m];  x[r] -= L[r][m] x[m]  (m < r, both in the block)
+// then the rows below take the block's 16 steps as rank-16 updates on the matrix cores, X[r][c] += sum_m (-L[r][m]) X[m][c] with m
+// ascending - per element the chain of fused multiply-adds of k_trinv_diag_w's loop (see "Trailing updates" above).  Only the
+// column tiles ct <= JB take part: right of them X[m][c] is an exact +0 (c > m) and fma(-L, +0, x) returns x.
+// xa[rt][ct] (rt > ct): the tile of X below the diagonal, as accumulators; s_x: the finished rows of X in the LDS (leading
+// dimension WLD), operands of the updates; dst: the diagonal tile of R.
+template <int JB>
+__device__ inline void panel_m_inverse_step(double4_t (&xa)[4][4], const double* s_d, double* s_x, int c, double* dst, int ld) {
+  constexpr int base = 16 * JB;
+  __syncthreads();                               // wait for sub-panel JB of the factor
+  if (JB > 0) {
+#pragma unroll
+    for (int ct = 0; ct < JB; ++ct)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) s_x[(base + (c >> 4) + 4 * q) * WLD + 16 * ct + (c & 15)] = xa[JB][ct][q];
+    PANEL_LDS_SYNC();
+  }
+  double x[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const double below = JB > 0 ? s_x[(base + j) * WLD + (c < base ? c : 0)] : 0.0;
+    x[j] = c < base ? below : (base + j == c ? 1.0 : 0.0);
+  }
+  const double rdv = 1.0 / s_d[(base + (c & 15)) * WLD + base + (c & 15)];      // lane j (< 16): 1 / L[base + j][base + j]
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const double xm = x[j] * lane_get(rdv, j);
+    x[j] = xm;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (i > j) x[i] = fma(-s_d[(base + i) * WLD + base + j], xm, x[i]);
+  }
+  // the block's rows are final: they leave for the diagonal tile of R now (zeros above the diagonal), not behind the last sub-panel
+#pragma unroll
+  for (int j = 0; j < 16; ++j) dst[(size_t)(base + j) * ld + c] = (base + j >= c) ? x[j] : 0.0;
+  if (JB < 3) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s_x[(base + j) * WLD + c] = x[j];
+    PANEL_LDS_SYNC();
+    double bx[JB + 1][4];                          // bx[ct][kk] = X[base + 4 kk + (c >> 4)][16 ct + (c & 15)]
+#pragma unroll
+    for (int ct = 0; ct <= JB; ++ct)
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) bx[ct][kk] = s_x[(base + 4 * kk + (c >> 4)) * WLD + 16 * ct + (c & 15)];
+#pragma unroll
+    for (int rt = JB + 1; rt < 4; ++rt) {
+      double al[4];                                // - L[16 rt + (c & 15)][base + 4 kk + (c >> 4)]
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) al[kk] = -s_d[(16 * rt + (c & 15)) * WLD + base + 4 * kk + (c >> 4)];
+#pragma unroll
+      for (int ct = 0; ct <= JB; ++ct)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) xa[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(al[kk], bx[ct][kk], xa[rt][ct], 0, 0, 0);
+    }
+  }
+}
+// One 16-column chunk (columns c0 ..) of row block I of R, I > c0 / 64: the body of k_trinv_cols' walk for that block row - the
+// operand tiles of the next step travel in registers while the MFMAs of the current one run.  s_t: 64 x 64 tile (leading
+// dimension SLD), s_xk: 64 x 16 block.  All 256 threads of the group.
+__device__ inline void trinv_rowblock_chunk(const double* L, double* R, int I, int c0, int ld, double* s_t, double* s_xk) {
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+  const int Jc = c0 / BS;
+  double pt[16], px[4];
+  auto fetch_tile = [&](const double* src) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { const int idx = tid + 256 * u; pt[u] = src[(size_t)(idx >> 6) * ld + (idx & 63)]; }
+  };
+  auto fetch_x = [&](int Kb) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { const int idx = tid + 256 * u; px[u] = R[(size_t)(Kb * BS + (idx >> 4)) * ld + c0 + (idx & 15)]; }
+  };
+  auto put_tile = [&]() {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { const int idx = tid + 256 * u; s_t[(idx >> 6) * SLD + (idx & 63)] = pt[u]; }
+  };
+  auto put_x = [&]() {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s_xk[tid + 256 * u] = px[u];
+  };
+  fetch_tile(L + (size_t)(I * BS) * ld + Jc * BS); fetch_x(Jc);
+  double4_t acc = {0.0, 0.0, 0.0, 0.0};
+  for (int Kb = Jc; Kb < I; ++Kb) {
+    __syncthreads();                             // the previous step's MFMAs have read the LDS tiles
+    put_tile(); put_x();
+    if (Kb + 1 < I) { fetch_tile(L + (size_t)(I * BS) * ld + (Kb + 1) * BS); fetch_x(Kb + 1); }
+    else fetch_tile(R + (size_t)(I * BS) * ld + I * BS);           // Rdiag_I, for the closing product
+    __syncthreads();
+    for (int kk = 0; kk < BS; kk += 4) {
+      double a = s_t[(16 * w + (l & 15)) * SLD + kk + (l >> 4)];
+      double b = s_xk[(kk + (l >> 4)) * 16 + (l & 15)];
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+    }
+  }
+  __syncthreads();
+  for (int r = 0; r < 4; ++r) s_xk[(16 * w + (l >> 4) + 4 * r) * 16 + (l & 15)] = -acc[r];
+  put_tile();
+  __syncthreads();
+  double4_t x = {0.0, 0.0, 0.0, 0.0};
+  for (int kk = 0; kk < BS; kk += 4) {
+    double a = s_t[(16 * w + (l & 15)) * SLD + kk + (l >> 4)];
+    double b = s_xk[(kk + (l >> 4)) * 16 + (l & 15)];
+    x = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, x, 0, 0, 0);
+  }
+  for (int r = 0; r < 4; ++r)
+    R[(size_t)(I * BS + 16 * w + (l >> 4) + 4 * r) * ld + c0 + (l & 15)] = x[r];
+}
 __global__ __launch_bounds__(256) void k_chol_step(double* __restrict__ A, int J, int nblk, int ld, int* __restrict__ info,
-                                                   double* __restrict__ diag_scratch, size_t zs) {
+                                                   double* __restrict__ diag_scratch, size_t zs, double* Rinv) {
   ZRUN(A); ZRUN(info); ZRUN(diag_scratch);
   extern __shared__ __attribute__((aligned(16))) double s_mem[];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
   const int nP = nblk - J, nLA = J >= 1 ? nblk - J - 1 : 0;
   const int bx = blockIdx.x;
+  if (bx > nP + nLA) {                                 // (only launched with Rinv, J >= 2) row block J-1 of R, one chunk per group
+    trinv_rowblock_chunk(A, Rinv, J - 1, 16 * (bx - (nP + nLA + 1)), ld, s_mem, s_mem + BS * SLD);
+    return;
+  }
   if (bx == nP + nLA) {                                // (only launched for J >= 1) panel J-1's diagonal factor -> its place
     double* Add = A + (size_t)((J - 1) * BS) * ld + (J - 1) * BS;
     const double* src = diag_scratch + (size_t)((J - 1) & 1) * BS * BS;
@@ -430,6 +553,19 @@ __global__ __launch_bounds__(256) void k_chol_step(double* __restrict__ A, int J
     panel_m_solve_step<1>(acc, s_d, s_rs, s_a, r);
     panel_m_solve_step<2>(acc, s_d, s_rs, s_a, r);
     panel_m_solve_step<3>(acc, s_d, s_rs, s_a, r);
+  } else if (w == 2 && b == 0 && Rinv) {
+    // the inverse of the diagonal block, one sub-panel behind wave 0 (one barrier per sub-panel, like the other waves)
+    double4_t xa[4][4];
+#pragma unroll
+    for (int rt = 1; rt < 4; ++rt)
+#pragma unroll
+      for (int ct = 0; ct < rt; ++ct) xa[rt][ct] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    double* s_xi = s_a;                                // (group 0 has no off-diagonal tile: its memory holds the inverse)
+    double* dst = Rinv + (size_t)(J * BS) * ld + J * BS;
+    panel_m_inverse_step<0>(xa, s_d, s_xi, r, dst, ld);
+    panel_m_inverse_step<1>(xa, s_d, s_xi, r, dst, ld);
+    panel_m_inverse_step<2>(xa, s_d, s_xi, r, dst, ld);
+    panel_m_inverse_step<3>(xa, s_d, s_xi, r, dst, ld);
   } else {
     for (int jb = 0; jb < BS / 16; ++jb) __syncthreads();      // the other waves keep the four barriers of the sub-panels paired
   }
@@ -524,8 +660,19 @@ __global__ __launch_bounds__(64) void k_trinv_diag_w(const double* __restrict__ 
 void launch_chol_panel(hipStream_t s, double* L, int p, int nblocks, int ld, int* info, double* diag_scratch, ZB zb) {
   hipLaunchKernelGGL(k_chol_panel_m, dim3(nblocks, 1, zb.B), dim3(128), 0, s, L, p, ld, info, diag_scratch, zb.zs);
 }
-// diag_scratch: TWO 64 x 64 tiles
-int launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb) {
+// The last row block of a root inverse folded into the panel launches: 4 (nblk - 1) chunks, one group each
+__global__ __launch_bounds__(256) void k_trinv_rowblock(const double* L, int I, int ld, double* R) {
+  __shared__ __attribute__((aligned(16))) double s_t[BS * SLD];
+  __shared__ __attribute__((aligned(16))) double s_xk[BS * 16];
+  trinv_rowblock_chunk(L, R, I, 16 * blockIdx.x, ld, s_t, s_xk);
+}
+void launch_trinv_drain(hipStream_t s, const double* L, int NP, int ld, double* R) {
+  const int nblk = NP / BS;
+  if (nblk >= 2) hipLaunchKernelGGL(k_trinv_rowblock, dim3(4 * (nblk - 1)), dim3(256), 0, s, L, nblk - 1, ld, R);
+}
+// diag_scratch: TWO 64 x 64 tiles.  R != null (one run only): the root inverse goes into R beside the panels, all but its last row
+// block, which launch_trinv_drain adds.
+int launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb, double* R) {
   static std::mutex attr_mu;
   static bool attr_done[64] = {false};
   int dev = 0;
@@ -539,8 +686,8 @@ int launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, doubl
   }
   const int nblk = NP / BS;
   for (int J = 0; J < nblk; ++J) {
-    const int groups = (nblk - J) + (J >= 1 ? nblk - J - 1 : 0) + (J >= 1 ? 1 : 0);
-    hipLaunchKernelGGL(k_chol_step, dim3(groups, 1, zb.B), dim3(256), CHOL_STEP_LDS, s, L, J, nblk, ld, info, diag_scratch, zb.zs);
+    const int groups = (nblk - J) + (J >= 1 ? nblk - J - 1 : 0) + (J >= 1 ? 1 : 0) + (R && J >= 2 ? 4 * (J - 1) : 0);
+    hipLaunchKernelGGL(k_chol_step, dim3(groups, 1, zb.B), dim3(256), CHOL_STEP_LDS, s, L, J, nblk, ld, info, diag_scratch, zb.zs, R);
   }
   return 0;
 }

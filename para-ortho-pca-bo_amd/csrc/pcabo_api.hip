@@ -81,6 +81,13 @@ struct pcabo_ctx {
   hipStream_t stream = nullptr;
   hipEvent_t evBounds = nullptr;         // recorded after k_zstats: the search box is on the host before the Cholesky ends
   hipEvent_t evPca = nullptr;            // recorded after the wPCA results left for the host (conditioning may follow it)
+  // PCABO_OPT_HIDDEN_TAIL, single contexts: the raw samples' copy and their kernel vectors (k_score_ks_only) run on a second stream
+  // beside the factorisation.  evZn: recorded behind k_znorm on the main stream, the second stream waits for it; evKS: recorded
+  // behind the kernel vectors, the main stream waits for it in front of the launches that need them.
+  hipStream_t stream2 = nullptr;
+  hipEvent_t evZn = nullptr, evKS = nullptr;
+  bool zn_recorded = false;              // evZn belongs to the conditioning in flight
+  bool opt_hidden_tail = true;
   int max_n = 0, max_d = 0, max_q = 0;
   int NPcap = 0, ld = 0, DPcap = 0, KPcap = 0, Scap = 0;
   int ptr_mode = PCABO_PTR_HOST;
@@ -441,6 +448,11 @@ static int ctx_setup(pcabo_ctx* ctx, int device, int max_n, int max_d, int max_q
   presence_register(ctx->device); ctx->registered = true;
   HIPCHK(hipEventCreateWithFlags(&ctx->evBounds, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&ctx->evPca, hipEventDisableTiming));
+  if (!stream) {
+    HIPCHK(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&ctx->evZn, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ctx->evKS, hipEventDisableTiming));
+  }
   ctx->region_bytes = carve_device(ctx, nullptr);
   ctx->hregion_bytes = carve_host(ctx, nullptr);
   if (dreg) {
@@ -480,6 +492,7 @@ static int ctx_setup(pcabo_ctx* ctx, int device, int max_n, int max_d, int max_q
 
 static void ctx_teardown(pcabo_ctx* ctx) {
   (void)hipSetDevice(ctx->device);        // tear-down: nothing useful to do with an error from here on
+  if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (auto& p : ctx->pairs) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   if (!ctx->in_batch) {
@@ -490,6 +503,9 @@ static void ctx_teardown(pcabo_ctx* ctx) {
   }
   if (ctx->evBounds) (void)hipEventDestroy(ctx->evBounds);
   if (ctx->evPca) (void)hipEventDestroy(ctx->evPca);
+  if (ctx->evZn) (void)hipEventDestroy(ctx->evZn);
+  if (ctx->evKS) (void)hipEventDestroy(ctx->evKS);
+  if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->stream && !ctx->in_batch) (void)hipStreamDestroy(ctx->stream);
   ctx->helper.shutdown();
   for (auto& h : ctx->more_helpers) h->shutdown();
@@ -514,14 +530,18 @@ struct RowsDH {
   hipEvent_t ev[2];                      // recorded behind k_zstats (null: none): the search box is on its way to the host
   int* cnt_S; bool* cnt_dirty;           // the owner's ticket state (null: the tickets are left alone)
   const double* ard_ls = nullptr;        // ARD fit of a single context: k lengthscales on the device, folded by k_zstats (inv_ls = 1)
+  hipEvent_t ev_zn = nullptr;            // recorded behind k_znorm (null: none): ZnT and the Normalize bounds are final
 };
 template <class Phase>
 static int enqueue_factor(pcabo_ctx* ctx, hipStream_t s, int n, int NP, ZB zb, Phase&& phase) {
   if (const int rc = phase(2)) return rc;
-  if (launch_cholesky(s, ctx->dL, NP, ctx->ld, ctx->dInfo, ctx->dDiag, zb) != 0)
+  // a single context folds the root inverse into the panel launches (PCABO_OPT_HIDDEN_TAIL); a batch keeps the separate launches
+  const bool fold = !ctx->in_batch && ctx->opt_hidden_tail && zb.zs == 0 && zb.B == 1 && chol_step_form(NP, zb);
+  if (launch_cholesky(s, ctx->dL, NP, ctx->ld, ctx->dInfo, ctx->dDiag, zb, fold ? ctx->dR : nullptr) != 0)
     return set_err(ctx, PCABO_ERR_HIP, "the Cholesky launches could not be set up (device or kernel attribute)%s", "");
   if (const int rc = phase(3)) return rc;
-  launch_trinv(s, ctx->dL, NP, ctx->ld, ctx->dR, zb);
+  if (fold) launch_trinv_drain(s, ctx->dL, NP, ctx->ld, ctx->dR);
+  else launch_trinv(s, ctx->dL, NP, ctx->ld, ctx->dR, zb);
   launch_alpha(s, ctx->dR, ctx->dYs, n, NP, ctx->ld, ctx->dTmp, ctx->dAlpha, zb);
   if (const int rc = phase(4)) return rc;
   if (zb.zs) HIPCHK(hipMemcpy2DAsync((void*)&ctx->hm->chol_info, zb.hzs, ctx->dInfo, zb.zs, sizeof(int), zb.B, hipMemcpyDeviceToHost, s));
@@ -542,6 +562,7 @@ static int enqueue_rows_dh(pcabo_ctx* ctx, hipStream_t s, const RowsDH& a, Phase
   launch_zstats(s, a.Z, a.y, a.n, a.k, a.unb, ctx->dBounds4, ctx->dZnMean, ctx->dYstats, ctx->dYs, ctx->hm, a.k_dev, a.zb, a.mean_c, a.ard_ls);
   for (hipEvent_t e : a.ev) if (e) HIPCHK(hipEventRecord(e, s));
   launch_znorm(s, a.Z, a.n, a.k, NP, a.KP, ctx->ld, ctx->dBounds4, ctx->dZnMean, a.inv_ls, ctx->dZnT, ctx->dAT, ctx->dNrm, a.k_dev, a.zb);
+  if (a.ev_zn) HIPCHK(hipEventRecord(a.ev_zn, s));
   launch_gram(s, ctx->dAT, ctx->dNrm, a.n, NP, a.KP, ctx->ld, a.noise, a.kernel, nullptr, a.k_dev, ctx->dL, ctx->dInfo, a.zb);
   return enqueue_factor(ctx, s, a.n, NP, a.zb, phase);
 }
@@ -629,6 +650,7 @@ int pcabo_set_option(pcabo_ctx* ctx, int option, int value) {
     case PCABO_OPT_RESIDENT: ctx->opt_resident = value != 0 && !ctx->in_batch; return PCABO_OK;   // (never inside a batch)
     case PCABO_OPT_BESTF_F32: ctx->bestf_f32 = value != 0; return PCABO_OK;
     case PCABO_OPT_GROUP_ACQ: ctx->opt_group_acq = value != 0; return PCABO_OK;
+    case PCABO_OPT_HIDDEN_TAIL: ctx->opt_hidden_tail = value != 0; return PCABO_OK;
     default: return set_err(ctx, PCABO_ERR_ARG, "pcabo_set_option: unknown option %s%d", "", option);
   }
 }
@@ -765,8 +787,10 @@ static int enqueue_condition(pcabo_ctx* ctx, const double* y_dev, int n, int k, 
   ctx->lengthscale = lengthscale; ctx->noise = noise; ctx->kernel = kernel;
   ctx->have_gp = false;
   ctx->gp_pending = true;
+  // (a profiled context keeps everything on one stream: its event pairs time the main stream alone)
+  ctx->zn_recorded = ctx->stream2 && ctx->opt_hidden_tail && !ctx->prof;
   const RowsDH a{ctx->dZ, y_dev, unb, n, k, ctx->KP, k < 0 ? ctx->dK : nullptr, 1.0 / lengthscale, noise, mean_c, kernel, ZB(),
-                 {ctx->evBounds, nullptr}, &ctx->cnt_S, &ctx->cnt_dirty, ard_ls};
+                 {ctx->evBounds, nullptr}, &ctx->cnt_S, &ctx->cnt_dirty, ard_ls, ctx->zn_recorded ? ctx->evZn : nullptr};
   return enqueue_rows_dh(ctx, ctx->stream, a, CondProf{ctx, k < 0 ? ctx->max_d : k});   // asynchronous: pcabo_gp_condition_end() waits and checks
 }
 
@@ -1100,6 +1124,18 @@ static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = t
   return acq_published(ctx, wait_flags(ctx->hm, 0, nq, seq, deadline_in(20), &s));
 }
 
+// The part of the GEMM scoring that needs alpha and R, for nq samples whose kernel vectors are in ctx->dKS: the mu_s sums, V = R KS^T,
+// the scalar chain per sample, the values' copy and the wait (eval_staged's GEMM branch without its first kernel's KS half).
+static int score_tail(pcabo_ctx* ctx, int nq, AcqParams& p) {
+  hipStream_t s = ctx->stream;
+  launch_score_tail(s, nq, ctx->n, ctx->k, ctx->NP, ctx->ld, ctx->dR, ctx->dAlpha, ctx->dBounds4, ctx->dYstats, p, ctx->dKS,
+                    ctx->dPartial, ctx->dVal);
+  HIPCHK(hipMemcpyAsync(ctx->hVal, ctx->dVal, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(wait_stream(s));
+  HIPCHK(hipGetLastError());
+  return PCABO_OK;
+}
+
 // The same for restart groups through the throughput kernel (PCABO_OPT_GROUP_ACQ): group g = the gn[g] <= 5 points staged
 // at query slots g0[g].. of ctx->hXq, which the kernel reads in place (pinned memory); one work-group per (group, 64-row slab).
 static int eval_staged_groups(pcabo_ctx* ctx, const int* g0, const int* gn, int ng, AcqParams& p) {
@@ -1184,12 +1220,27 @@ int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double 
   HIPCHK(hipSetDevice(ctx->device));
   memcpy(ctx->hXq, Xq, (size_t)q * ctx->k * sizeof(double));
   AcqParams p = make_params(ctx, best_f, maximize, acq, 0);
-  int rc = eval_staged(ctx, q, p);                  // ends with a stream synchronisation: the conditioning is over too
+  // The kernel vectors of the samples need the Normalize bounds and ZnT only: they and the samples' copy go to the second stream
+  // and run beside the factorisation; what needs alpha and R follows on the main stream (score_tail).
+  const bool hidden = ctx->zn_recorded && ctx->opt_hidden_tail && !ctx->prof && score_gemm_possible(q);
+  ctx->zn_recorded = false;
+  int rc;
+  if (hidden) {
+    HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->evZn, 0));
+    HIPCHK(hipMemcpyAsync(ctx->dXq, ctx->hXq, (size_t)q * ctx->k * sizeof(double), hipMemcpyHostToDevice, ctx->stream2));
+    launch_score_ks_only(ctx->stream2, ctx->dXq, q, ctx->n, ctx->k, ctx->NP, ctx->ld, ctx->dZnT, ctx->dBounds4, p, ctx->dKS);
+    HIPCHK(hipEventRecord(ctx->evKS, ctx->stream2));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evKS, 0));
+    rc = score_tail(ctx, q, p);
+  } else {
+    rc = eval_staged(ctx, q, p);                    // ends with a stream synchronisation: the conditioning is over too
+  }
   if (rc != PCABO_OK) { ctx->gp_pending = false; return rc; }
   if (ctx->hm->chol_info != 0) {                    // rare: jitter retries, then the evaluation again
     rc = pcabo_gp_condition_end(ctx);
     if (rc != PCABO_OK) return rc;
-    rc = eval_staged(ctx, q, p);
+    // (K + jitter I changes R and alpha, not the kernel vectors: only the launches behind them run again)
+    rc = hidden ? score_tail(ctx, q, p) : eval_staged(ctx, q, p);
     if (rc != PCABO_OK) return rc;
   } else {
     ctx->gp_pending = false;
@@ -1419,6 +1470,14 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
 int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x) {
   if (!ctx || !z || !x) return PCABO_ERR_ARG;
   if (!ctx->have_wpca) return set_err(ctx, PCABO_ERR_ARG, "pcabo_inverse_map: call pcabo_wpca first%s", "");
+  if (!ctx->in_batch && ctx->opt_hidden_tail) {
+    // A single context has [data_mean | pca_mean | evr | comps] in pinned host memory since the wPCA results were collected:
+    // the k d multiply-adds run here, with the kernel's bits (inverse_map_host) - no launch, no flag wait, no device copy of x.
+    if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
+    const double* h = ctx->hSmall;
+    inverse_map_host(z, h + 3 * (size_t)ctx->max_d, h + ctx->max_d, h, ctx->k, ctx->d, x);
+    return PCABO_OK;
+  }
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   // z travels through the pinned query block (the kernel reads it in place over PCIe: 36 doubles), x comes back the way the

@@ -307,10 +307,15 @@ void launch_gram(hipStream_t s, const double* AT, const double* nrm, int n, int 
                  ZB zb = ZB());
 void launch_add_jitter(hipStream_t s, double* K, int n, int ld, double jitter);
 // 0, or -1 when nothing was factored (the device or a kernel attribute could not be set up)
-int launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb = ZB());
+// R_folded != null (one run, chol_step_form(NP, zb) only): the root inverse is computed beside the panels, all but its last row
+// block - launch_trinv_drain instead of launch_trinv behind it
+int launch_cholesky(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch, ZB zb = ZB(), double* R_folded = nullptr);
+bool chol_step_form(int NP, ZB zb);
+void launch_trinv_drain(hipStream_t s, const double* L, int NP, int ld, double* R);
 void launch_trinv(hipStream_t s, const double* L, int NP, int ld, double* R, ZB zb = ZB());
 void launch_chol_panel(hipStream_t s, double* L, int p, int nblocks, int ld, int* info, double* diag_scratch, ZB zb = ZB());
-int launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch /* two tiles */, ZB zb = ZB());
+int launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, double* diag_scratch /* two tiles */, ZB zb = ZB(),
+                      double* R = nullptr);
 void launch_trinv_diag_w(hipStream_t s, const double* L, int nblk, int ld, double* R, ZB zb = ZB());
 void launch_alpha(hipStream_t s, const double* R, const double* ys, int n, int NP, int ld, double* tmp, double* alpha,
                   ZB zb = ZB());
@@ -344,6 +349,11 @@ bool score_gemm_possible(int q);
 void launch_score(hipStream_t st, const double* Xq, int q, int n, int k, int NP, int ld, const double* ZnT, const double* R,
                   const double* alpha, const double* bounds4, const double* ystats, AcqParams p, double* KS, double* partial,
                   double* val, AcqBatch ab = AcqBatch(), int B = 1);
+// launch_score's first kernel without its mu_s sums (no alpha), and the rest of launch_score behind it: together launch_score's bits
+void launch_score_ks_only(hipStream_t st, const double* Xq, int q, int n, int k, int NP, int ld, const double* ZnT,
+                          const double* bounds4, AcqParams p, double* KS);
+void launch_score_tail(hipStream_t st, int q, int n, int k, int NP, int ld, const double* R, const double* alpha,
+                       const double* bounds4, const double* ystats, AcqParams p, const double* KS, double* partial, double* val);
 // resident mode available for this shape? (fast path + every group of the grid co-resident)
 bool acq_server_possible(int q, int n, int k, int NP);
 int acq_slabs(int NP);

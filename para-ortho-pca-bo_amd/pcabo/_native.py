@@ -18,6 +18,7 @@ KERNEL_MATERN52, KERNEL_RBF = 0, 1
 ACQ_LOG_EI, ACQ_PI, ACQ_UCB = 0, 1, 2
 PTR_HOST, PTR_DEVICE = 0, 1
 OPT_RESIDENT, OPT_BESTF_F32, OPT_GROUP_ACQ, OPT_DEVICE_LBFGSB, OPT_LBFGSB_CUS = 0, 1, 2, 3, 4
+OPT_HIDDEN_TAIL = 5
 FIT_THETA0 = (0.006737946999085467, 0.0, 0.0)   # GP fit: (noise, mean constant, raw lengthscale) of a freshly built model
 FIT_TASK_NOT_PD = -2                            # gp_fit's `task` when a trial theta could not be factored even with jitter
 PROFILE_GROUPS = ("wpca", "gram", "cholesky", "root_inverse_alpha", "acq_partial", "acq_large_batches")
