@@ -28,6 +28,7 @@
 //   to read host memory over PCIe.  Batches of more than 32 queries use the launch boundary instead of tickets
 //   (k_acq_combine) and, on the fast path, give each group 8 queries per load of its register tiles.
 #include "pcabo_internal.h"
+#include "acq_math.h"
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -218,22 +219,14 @@ __global__ __launch_bounds__(256) void k_acq_fused(
   __syncthreads();
   STAMP(1);
   // kernel vector and the radial derivative factor
-  const double s5 = 2.23606797749979;
   for (int j = tid; j < NP; j += 256) {
     double ks = 0.0, cf = 0.0;
     if (j < n) {
       double sq = 0.0;
       for (int c = 0; c < k; ++c) { double dlt = s_xn[c] - ZnT[(size_t)c * ld + j]; sq += dlt * dlt; }
       sq *= inv_ls * inv_ls;
-      if (kernel == 1) {
-        ks = exp(-0.5 * sq);
-        cf = -ks * inv_ls * inv_ls;
-      } else {
-        double dist = sqrt(fmax(sq, 1e-30));
-        double e = exp(-s5 * dist);
-        ks = ((s5 * dist + 1.0) + (5.0 / 3.0) * (dist * dist)) * e;
-        cf = -(5.0 / 3.0) * (1.0 + s5 * dist) * e * inv_ls * inv_ls;
-      }
+      acq_cov(sq, kernel, &ks, &cf);
+      cf = cf * inv_ls * inv_ls;
     }
     s_ks[j] = ks;
     s_cf[j] = cf;
@@ -628,7 +621,6 @@ __global__ __launch_bounds__(256) void k_acq_fast(
     for (int b = 0; b < NB; ++b) s_p4[w * NP + l + 64 * b] = sq[b];
   }
   __syncthreads();
-  const double s5 = 2.23606797749979;
 #pragma unroll
   for (int m = 0; m < NM; ++m) {
     const int j = tid + 256 * m;
@@ -637,15 +629,8 @@ __global__ __launch_bounds__(256) void k_acq_fast(
       if (j < n) {
         double sq = ((s_p4[j] + s_p4[NP + j]) + s_p4[2 * NP + j]) + s_p4[3 * NP + j];
         sq *= inv_ls * inv_ls;
-        if (kernel == 1) {
-          ks = exp(-0.5 * sq);
-          cf = -ks * inv_ls * inv_ls;
-        } else {
-          double dist = sqrt(fmax(sq, 1e-30));
-          double e = exp(-s5 * dist);
-          ks = ((s5 * dist + 1.0) + (5.0 / 3.0) * (dist * dist)) * e;
-          cf = -(5.0 / 3.0) * (1.0 + s5 * dist) * e * inv_ls * inv_ls;
-        }
+        acq_cov(sq, kernel, &ks, &cf);
+        cf = cf * inv_ls * inv_ls;
       }
       s_ks[j] = ks;
       s_cf[j] = cf;
@@ -750,80 +735,17 @@ __global__ __launch_bounds__(256) void k_acq_fast(
   }   // rounds
 }
 
-// ---- scalar log-EI helper, value and derivative (botorch/acquisition/analytic.py::_log_ei_helper)
-__device__ inline void log_ei_helper(double u, double* h, double* dh) {
-  const double inv_sqrt2 = 0.7071067811865476;
-  const double inv_sqrt_2pi = 0.3989422804014327;
-  const double log2pi = 1.8378770664093453;
-  if (u > -1.0) {
-    double phi = inv_sqrt_2pi * exp(-0.5 * u * u);
-    double Phi = 0.5 * erfc(-inv_sqrt2 * u);
-    double ei = phi + u * Phi;
-    *h = log(ei);
-    *dh = Phi / ei;
-    return;
-  }
-  double log_phi = -0.5 * (u * u + log2pi);
-  if (u > -1e6) {
-    // botorch: w = log(erfcx(-u/sqrt2) |u|) + log(sqrt(pi/2)); h = log_phi + log1mexp(w).  With E = e^w formed
-    // directly, log1mexp(w) = log1p(-E) and expm1(-w) = (1 - E)/E: the same conditioning (both routes lose
-    // eps/(1 - E)), three transcendental calls fewer on the one wave every round waits for.
-    const double ex = erfcx(-inv_sqrt2 * u);
-    const double E = (ex * fabs(u)) * 1.2533141373155003;       // sqrt(pi/2)
-    *h = log_phi + log1p(-E);
-    const double dw = (u + 0.7978845608028654 / ex) + 1.0 / u;  // sqrt(2/pi)/erfcx + u + 1/u
-    *dh = -u - dw * E / (1.0 - E);
-  } else {
-    *h = log_phi - 2.0 * log(fabs(u));
-    *dh = -u - 2.0 / u;
-  }
-}
-
-// Scalar chain of one query (one wave): mean, sigma, u -> value and the two coefficients of the gradient's chain
-// rule, from the summed |v|^2 and mu_s.  coef receives {c_mu, c_sg}.
+// Scalar chain of one query (one wave, acq_math.h: acq_scalar_chain): value to device and host memory, coef receives
+// {c_mu, c_sg}.
 __device__ void acq_scalar_core(double vv, double mus, int q, double ym, double ysd, const AcqParams& p, double* val,
                                 double* host_val, double* coef, int l) {
-  const double mu = ym + ysd * mus;
-  double var = (1.0 - vv) * (ysd * ysd);
-  bool clamped = false;
-  if (!(var >= 1e-10)) { var = 1e-10; clamped = true; }     // gpytorch min_variance (double)
-  if (var < 1e-12) { var = 1e-12; clamped = true; }          // botorch _mean_and_sigma(min_var)
-  const double sigma = sqrt(var);
-  const double sgn = p.maximize ? 1.0 : -1.0;
-  if (p.acq == 2) {
-    // PCABO_ACQ_UCB: value = sgn mu + kappa sigma, kappa in the best_f slot - linear in mu and sigma, no u (wave-uniform branch).
-    // The one fused multiply-add is spelled out: left to the compiler, a b + c d is contracted one way in one kernel and the
-    // other way in the next, and a run in a batch must take the bits it takes alone.
-    if (l == 0) {
-      const double kappa = p.best_f, value = __fma_rn(kappa, sigma, sgn * mu);
-      val[q] = value;
-      if (host_val) host_val[q] = value;
-      coef[0] = sgn * ysd;                                              // d value / d mu_s
-      coef[1] = clamped ? 0.0 : kappa * (-(ysd * ysd) / sigma);         // dsigma = -s_y^2 g_sigma / sigma
-    }
-    STAMP_FIN(12);
-    return;
-  }
-  double u = (mu - p.best_f) / sigma;
-  u *= sgn;
-  double value, dv_du, dv_dsig;
-  if (p.acq == 0) {
-    double h, dh;
-    log_ei_helper(u, &h, &dh);
-    value = h + log(sigma);
-    dv_du = dh;
-    dv_dsig = 1.0 / sigma;
-  } else {
-    value = 0.5 * erfc(-0.7071067811865476 * u);
-    dv_du = 0.3989422804014327 * exp(-0.5 * u * u);
-    dv_dsig = 0.0;
-  }
+  double value, c_mu, c_sg;
+  acq_scalar_chain(vv, mus, ym, ysd, p.best_f, p.maximize, p.acq, &value, &c_mu, &c_sg);
   if (l == 0) {
     val[q] = value;
     if (host_val) host_val[q] = value;
-    // du = sgn dmu/sigma - u dsigma/sigma ; dsigma = -s_y^2 g_sigma / sigma (0 where the variance was clamped)
-    coef[0] = dv_du * sgn * ysd / sigma;
-    coef[1] = clamped ? 0.0 : (dv_dsig - dv_du * u / sigma) * (-(ysd * ysd) / sigma);
+    coef[0] = c_mu;
+    coef[1] = c_sg;
   }
   STAMP_FIN(12);
 }
@@ -964,7 +886,6 @@ __global__ __launch_bounds__(256) void k_acq_group(
   // R's rows of the slab are zero beyond their diagonal block); all columns of a thread advance together so that a
   // coordinate read from LDS serves every one of them; CB components' loads are in flight per trip -----------------
   double cfr[NT][GQ];
-  const double s5 = 2.23606797749979;
   {
     const int jlim = n < ncol ? n : ncol;
     double sq[NT][GQ];
@@ -1003,16 +924,8 @@ __global__ __launch_bounds__(256) void k_acq_group(
       for (int q = 0; q < GQ; ++q) {
         double ks = 0.0, cf = 0.0;
         if (j < jlim) {
-          const double sqq = sq[t][q] * (inv_ls * inv_ls);
-          if (kernel == 1) {
-            ks = exp(-0.5 * sqq);
-            cf = -ks * inv_ls * inv_ls;
-          } else {
-            const double dist = sqrt(fmax(sqq, 1e-30));
-            const double e = exp(-s5 * dist);
-            ks = ((s5 * dist + 1.0) + (5.0 / 3.0) * (dist * dist)) * e;
-            cf = -(5.0 / 3.0) * (1.0 + s5 * dist) * e * inv_ls * inv_ls;
-          }
+          acq_cov(sq[t][q] * (inv_ls * inv_ls), kernel, &ks, &cf);
+          cf = cf * inv_ls * inv_ls;
         }
         if (j < NP) s_ks[q * NP + j] = ks;
         cfr[t][q] = cf;
@@ -1345,20 +1258,13 @@ int launch_acq_group(hipStream_t st, const QueryArgs* tab, int entries, const do
 // same records k_acq_combine sums for the slab kernels.  mu_s = alpha . ks is formed where ks is, in k_score_ks.
 // 0.10 GFLOP per run at n = 450: one work-group per (row block, 64 queries) instead of one per (16-row slab, 8 queries).
 #define SC_QB 16
-__global__ __launch_bounds__(256) void k_score_ks(const double* __restrict__ Xq, int q_total, int n, int k, int NP, int ld,
-                                                  const double* __restrict__ ZnT, const double* __restrict__ alpha,
-                                                  const double* __restrict__ bounds4, AcqParams prm,
-                                                  double* __restrict__ KS, double* __restrict__ partial, int S, AcqBatch ab) {
-  if (ab.zs) {
-    const unsigned run_ = blockIdx.z;
-    Xq = zrun(Xq, ab.zs, run_); ZnT = zrun(ZnT, ab.zs, run_); alpha = zrun(alpha, ab.zs, run_);
-    bounds4 = zrun(bounds4, ab.zs, run_); KS = zrun(KS, ab.zs, run_); partial = zrun(partial, ab.zs, run_);
-    if (ab.k_dev) k = *zrun(ab.k_dev, ab.zs, run_);
-    if (ab.hyp) prm.inv_ls = zrun(ab.hyp, ab.zs, run_)[PCABO_HYP_INV_LS];
-  }
+// The kernel-vector half, shared by k_score_ks and k_score_ks_only: the work-group's 16 queries normalised into LDS, thread j's
+// squared distances to them, the covariance, the store of KS.  ks[q] is what the thread stored (0 beyond n).
+__device__ inline void score_ks_block(const double* __restrict__ Xq, int q_total, int n, int k, int NP, int ld,
+                                      const double* __restrict__ ZnT, const double* __restrict__ bounds4, const AcqParams& prm,
+                                      double* __restrict__ KS, double (&ks)[SC_QB]) {
   __shared__ double s_xn[SC_QB][PCABO_MAXD];
-  __shared__ double s_mu[4][SC_QB];
-  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const int j = blockIdx.x * 256 + tid, q0 = blockIdx.y * SC_QB;
   for (int idx = tid; idx < SC_QB * k; idx += 256) {
     const int q = idx / k, c = idx - q * k;
@@ -1383,21 +1289,34 @@ __global__ __launch_bounds__(256) void k_score_ks(const double* __restrict__ Xq,
         }
     }
   }
-  const double inv_ls = prm.inv_ls, s5 = 2.23606797749979;
+  const double inv_ls = prm.inv_ls;
+#pragma unroll
+  for (int q = 0; q < SC_QB; ++q) {
+    ks[q] = j < n ? acq_cov_value(sq[q] * (inv_ls * inv_ls), prm.kernel) : 0.0;
+    if (j < NP && q0 + q < q_total) KS[(size_t)(q0 + q) * ld + j] = ks[q];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_score_ks(const double* __restrict__ Xq, int q_total, int n, int k, int NP, int ld,
+                                                  const double* __restrict__ ZnT, const double* __restrict__ alpha,
+                                                  const double* __restrict__ bounds4, AcqParams prm,
+                                                  double* __restrict__ KS, double* __restrict__ partial, int S, AcqBatch ab) {
+  if (ab.zs) {
+    const unsigned run_ = blockIdx.z;
+    Xq = zrun(Xq, ab.zs, run_); ZnT = zrun(ZnT, ab.zs, run_); alpha = zrun(alpha, ab.zs, run_);
+    bounds4 = zrun(bounds4, ab.zs, run_); KS = zrun(KS, ab.zs, run_); partial = zrun(partial, ab.zs, run_);
+    if (ab.k_dev) k = *zrun(ab.k_dev, ab.zs, run_);
+    if (ab.hyp) prm.inv_ls = zrun(ab.hyp, ab.zs, run_)[PCABO_HYP_INV_LS];
+  }
+  __shared__ double s_mu[4][SC_QB];
+  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
+  const int j = blockIdx.x * 256 + tid, q0 = blockIdx.y * SC_QB;
+  double ks[SC_QB];
+  score_ks_block(Xq, q_total, n, k, NP, ld, ZnT, bounds4, prm, KS, ks);
   const double aj = j < n ? alpha[j] : 0.0;
 #pragma unroll
   for (int q = 0; q < SC_QB; ++q) {
-    double ks = 0.0;
-    if (j < n) {
-      const double sqq = sq[q] * (inv_ls * inv_ls);
-      if (prm.kernel == 1) ks = exp(-0.5 * sqq);
-      else {
-        const double dist = sqrt(fmax(sqq, 1e-30));
-        ks = ((s5 * dist + 1.0) + (5.0 / 3.0) * (dist * dist)) * exp(-s5 * dist);
-      }
-    }
-    if (j < NP && q0 + q < q_total) KS[(size_t)(q0 + q) * ld + j] = ks;
-    const double m = wave_sum(aj * ks);
+    const double m = wave_sum(aj * ks[q]);
     if (l == 0) s_mu[w][q] = m;
   }
   __syncthreads();
@@ -1479,46 +1398,8 @@ bool score_gemm_possible(int q) { return q >= 64; }
 __global__ __launch_bounds__(256) void k_score_ks_only(const double* __restrict__ Xq, int q_total, int n, int k, int NP, int ld,
                                                        const double* __restrict__ ZnT, const double* __restrict__ bounds4,
                                                        AcqParams prm, double* __restrict__ KS) {
-  __shared__ double s_xn[SC_QB][PCABO_MAXD];
-  const int tid = threadIdx.x;
-  const int j = blockIdx.x * 256 + tid, q0 = blockIdx.y * SC_QB;
-  for (int idx = tid; idx < SC_QB * k; idx += 256) {
-    const int q = idx / k, c = idx - q * k;
-    const int qq = q0 + q < q_total ? q0 + q : q_total - 1;
-    const double lo = bounds4[c], hi = bounds4[PCABO_MAXD + c];
-    s_xn[q][c] = (Xq[(size_t)qq * k + c] - lo) / (hi - lo);
-  }
-  __syncthreads();
-  double sq[SC_QB];
-#pragma unroll
-  for (int q = 0; q < SC_QB; ++q) sq[q] = 0.0;
-  if (j < n) {
-    for (int c0 = 0; c0 < k; c0 += 8) {
-      double z[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) z[u] = (c0 + u < k) ? ZnT[(size_t)(c0 + u) * ld + j] : 0.0;
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (c0 + u < k) {
-#pragma unroll
-          for (int q = 0; q < SC_QB; ++q) { const double d = s_xn[q][c0 + u] - z[u]; sq[q] += d * d; }
-        }
-    }
-  }
-  const double inv_ls = prm.inv_ls, s5 = 2.23606797749979;
-#pragma unroll
-  for (int q = 0; q < SC_QB; ++q) {
-    double ks = 0.0;
-    if (j < n) {
-      const double sqq = sq[q] * (inv_ls * inv_ls);
-      if (prm.kernel == 1) ks = exp(-0.5 * sqq);
-      else {
-        const double dist = sqrt(fmax(sqq, 1e-30));
-        ks = ((s5 * dist + 1.0) + (5.0 / 3.0) * (dist * dist)) * exp(-s5 * dist);
-      }
-    }
-    if (j < NP && q0 + q < q_total) KS[(size_t)(q0 + q) * ld + j] = ks;
-  }
+  double ks[SC_QB];
+  score_ks_block(Xq, q_total, n, k, NP, ld, ZnT, bounds4, prm, KS, ks);
 }
 
 __global__ __launch_bounds__(256) void k_score_mu(const double* __restrict__ KS, int q_total, int n, int ld,

@@ -30,6 +30,8 @@
 #include "pcabo_internal.h"
 #include "lbfgsb.h"
 #include "lb_plan.h"
+#include "lb_linesearch.h"
+#include "acq_math.h"
 #include <cfloat>
 #include <cmath>
 #include <mutex>
@@ -973,134 +975,14 @@ __device__ __noinline__ void lb_subsm(const LbLds L, int lane) {
   }
 }
 
-// ---- More-Thuente line search (lbfgsb.cpp: dcstep / dcsrch), every lane the same scalars ------------------------------------------
-struct LsState { int task, brackt, stage; double ginit, gtest, gx, gy, finit, fx, fy, stx, sty, stmin, stmax, width, width1; };
-
-__device__ inline void lb_dcstep(double* stx, double* fx, double* dx, double* sty, double* fy, double* dy, double* stp, double fp,
-                          double dp, int* brackt, double stpmin, double stpmax) {
-  const double sgnd = dp * (*dx / fabs(*dx));
-  double stpf, stpc, stpq, theta, s, gamma, p, q, r;
-  if (fp > *fx) {
-    theta = 3.0 * (*fx - fp) / (*stp - *stx) + *dx + dp;
-    s = fmax(fabs(theta), fmax(fabs(*dx), fabs(dp)));
-    gamma = s * sqrt((theta / s) * (theta / s) - (*dx / s) * (dp / s));
-    if (*stp < *stx) gamma = -gamma;
-    p = (gamma - *dx) + theta;
-    q = ((gamma - *dx) + gamma) + dp;
-    r = p / q;
-    stpc = *stx + r * (*stp - *stx);
-    stpq = *stx + ((*dx / ((*fx - fp) / (*stp - *stx) + *dx)) / 2.0) * (*stp - *stx);
-    if (fabs(stpc - *stx) < fabs(stpq - *stx)) stpf = stpc;
-    else stpf = stpc + (stpq - stpc) / 2.0;
-    *brackt = 1;
-  } else if (sgnd < 0.0) {
-    theta = 3.0 * (*fx - fp) / (*stp - *stx) + *dx + dp;
-    s = fmax(fabs(theta), fmax(fabs(*dx), fabs(dp)));
-    gamma = s * sqrt((theta / s) * (theta / s) - (*dx / s) * (dp / s));
-    if (*stp > *stx) gamma = -gamma;
-    p = (gamma - dp) + theta;
-    q = ((gamma - dp) + gamma) + *dx;
-    r = p / q;
-    stpc = *stp + r * (*stx - *stp);
-    stpq = *stp + (dp / (dp - *dx)) * (*stx - *stp);
-    if (fabs(stpc - *stp) > fabs(stpq - *stp)) stpf = stpc;
-    else stpf = stpq;
-    *brackt = 1;
-  } else if (fabs(dp) < fabs(*dx)) {
-    theta = 3.0 * (*fx - fp) / (*stp - *stx) + *dx + dp;
-    s = fmax(fabs(theta), fmax(fabs(*dx), fabs(dp)));
-    gamma = s * sqrt(fmax(0.0, (theta / s) * (theta / s) - (*dx / s) * (dp / s)));
-    if (*stp > *stx) gamma = -gamma;
-    p = (gamma - dp) + theta;
-    q = (gamma + (*dx - dp)) + gamma;
-    r = p / q;
-    if (r < 0.0 && gamma != 0.0) stpc = *stp + r * (*stx - *stp);
-    else if (*stp > *stx) stpc = stpmax;
-    else stpc = stpmin;
-    stpq = *stp + (dp / (dp - *dx)) * (*stx - *stp);
-    if (*brackt) {
-      if (fabs(stpc - *stp) < fabs(stpq - *stp)) stpf = stpc;
-      else stpf = stpq;
-      if (*stp > *stx) stpf = fmin(*stp + 0.66 * (*sty - *stp), stpf);
-      else stpf = fmax(*stp + 0.66 * (*sty - *stp), stpf);
-    } else {
-      if (fabs(stpc - *stp) > fabs(stpq - *stp)) stpf = stpc;
-      else stpf = stpq;
-      stpf = fmin(stpmax, stpf);
-      stpf = fmax(stpmin, stpf);
-    }
-  } else {
-    if (*brackt) {
-      theta = 3.0 * (fp - *fy) / (*sty - *stp) + *dy + dp;
-      s = fmax(fabs(theta), fmax(fabs(*dy), fabs(dp)));
-      gamma = s * sqrt((theta / s) * (theta / s) - (*dy / s) * (dp / s));
-      if (*stp > *sty) gamma = -gamma;
-      p = (gamma - dp) + theta;
-      q = ((gamma - dp) + gamma) + *dy;
-      r = p / q;
-      stpc = *stp + r * (*sty - *stp);
-      stpf = stpc;
-    } else if (*stp > *stx) stpf = stpmax;
-    else stpf = stpmin;
-  }
-  if (fp > *fx) { *sty = *stp; *fy = fp; *dy = dp; }
-  else {
-    if (sgnd < 0.0) { *sty = *stx; *fy = *fx; *dy = *dx; }
-    *stx = *stp; *fx = fp; *dx = dp;
-  }
-  *stp = stpf;
-}
-
-__device__ inline void lb_dcsrch(double f, double g, double* stp, double ftol, double gtol, double xtol, double stpmin,
-                          double stpmax, LsState& s) {
-  const double xtrapl = 1.1, xtrapu = 4.0, p5 = 0.5, p66 = 0.66;
-  if (s.task == 0) {
-    if (*stp < stpmin || *stp > stpmax || g >= 0.0) { s.task = 4; return; }
-    s.brackt = 0; s.stage = 1; s.finit = f; s.ginit = g; s.gtest = ftol * s.ginit;
-    s.width = stpmax - stpmin; s.width1 = s.width / p5;
-    s.stx = 0.0; s.fx = s.finit; s.gx = s.ginit; s.sty = 0.0; s.fy = s.finit; s.gy = s.ginit;
-    s.stmin = 0.0; s.stmax = *stp + xtrapu * *stp;
-    s.task = 1;
-    return;
-  }
-  const double ftest = s.finit + *stp * s.gtest;
-  if (s.stage == 1 && f <= ftest && g >= 0.0) s.stage = 2;
-  int task = 1;
-  if (s.brackt && (*stp <= s.stmin || *stp >= s.stmax)) task = 3;
-  if (s.brackt && s.stmax - s.stmin <= xtol * s.stmax) task = 3;
-  if (*stp == stpmax && f <= ftest && g <= s.gtest) task = 3;
-  if (*stp == stpmin && (f > ftest || g >= s.gtest)) task = 3;
-  if (f <= ftest && fabs(g) <= gtol * (-s.ginit)) task = 2;
-  if (task == 2 || task == 3) { s.task = task; return; }
-  if (s.stage == 1 && f <= s.fx && f > ftest) {
-    double fm = f - *stp * s.gtest, fxm = s.fx - s.stx * s.gtest, fym = s.fy - s.sty * s.gtest;
-    double gm = g - s.gtest, gxm = s.gx - s.gtest, gym = s.gy - s.gtest;
-    lb_dcstep(&s.stx, &fxm, &gxm, &s.sty, &fym, &gym, stp, fm, gm, &s.brackt, s.stmin, s.stmax);
-    s.fx = fxm + s.stx * s.gtest; s.fy = fym + s.sty * s.gtest; s.gx = gxm + s.gtest; s.gy = gym + s.gtest;
-  } else {
-    lb_dcstep(&s.stx, &s.fx, &s.gx, &s.sty, &s.fy, &s.gy, stp, f, g, &s.brackt, s.stmin, s.stmax);
-  }
-  if (s.brackt) {
-    if (fabs(s.sty - s.stx) >= p66 * s.width1) *stp = s.stx + p5 * (s.sty - s.stx);
-    s.width1 = s.width;
-    s.width = fabs(s.sty - s.stx);
-  }
-  if (s.brackt) { s.stmin = fmin(s.stx, s.sty); s.stmax = fmax(s.stx, s.sty); }
-  else { s.stmin = *stp + xtrapl * (*stp - s.stx); s.stmax = *stp + xtrapu * (*stp - s.stx); }
-  *stp = fmax(*stp, stpmin);
-  *stp = fmin(*stp, stpmax);
-  if ((s.brackt && (*stp <= s.stmin || *stp >= s.stmax)) || (s.brackt && s.stmax - s.stmin <= xtol * s.stmax))
-    *stp = s.stx;
-  s.task = 1;
-}
-
-__device__ inline void ls_load(const LbLds L, LsState& s) {
+// ---- More-Thuente line search (lb_linesearch.h, shared with lbfgsb.cpp), every lane the same scalars: its state in LDS ------------
+__device__ inline void ls_load(const LbLds L, LbLineSearch& s) {
   s.task = ISR(LS_TASK); s.brackt = ISR(LS_BRACKT); s.stage = ISR(LS_STAGE);
   s.ginit = SR(LS_GINIT); s.gtest = SR(LS_GTEST); s.gx = SR(LS_GX); s.gy = SR(LS_GY); s.finit = SR(LS_FINIT);
   s.fx = SR(LS_FX); s.fy = SR(LS_FY); s.stx = SR(LS_STX); s.sty = SR(LS_STY); s.stmin = SR(LS_STMIN); s.stmax = SR(LS_STMAX);
   s.width = SR(LS_WIDTH); s.width1 = SR(LS_WIDTH1);
 }
-__device__ inline void ls_store(const LbLds L, const LsState& s, int lane) {
+__device__ inline void ls_store(const LbLds L, const LbLineSearch& s, int lane) {
   if (lane == 0) {
     ISC(LS_TASK) = s.task; ISC(LS_BRACKT) = s.brackt; ISC(LS_STAGE) = s.stage;
     SC(LS_GINIT) = s.ginit; SC(LS_GTEST) = s.gtest; SC(LS_GX) = s.gx; SC(LS_GY) = s.gy; SC(LS_FINIT) = s.finit;
@@ -1114,7 +996,7 @@ __device__ __noinline__ void lb_lnsrlb(const LbLds L, int lane) {
   const int n = L.n;
   const double big = 1e10, ftol = 1e-3, gtol = 0.9, xtol = 0.1;
   const double f = SR(S_F);
-  LsState ls;
+  LbLineSearch ls;
   double stp, stpmx;
   const bool first_call = ISR(I_PHASE) != 2;
   LBT_BEGIN();
@@ -1152,8 +1034,6 @@ __device__ __noinline__ void lb_lnsrlb(const LbLds L, int lane) {
     stp = 1.0;                                        // (boxed: never min(1 / dnorm, stpmx))
     for (int i = lane; i < n; i += 64) { L.t()[i] = L.x()[i]; L.r()[i] = L.g()[i]; }
     if (lane == 0) { SC(S_STPMX) = stpmx; SC(S_FOLD) = f; ISC(I_IFUN) = 0; ISC(I_IBACK) = 0; }
-    ls.task = 0; ls.brackt = 0; ls.stage = 1;
-    ls.ginit = ls.gtest = ls.gx = ls.gy = ls.finit = ls.fx = ls.fy = ls.stx = ls.sty = ls.stmin = ls.stmax = ls.width = ls.width1 = 0.0;
     LSYNC();
   } else {
     ls_load(L, ls);
@@ -1451,63 +1331,6 @@ struct LbEval {
   int maximize, acq, kernel;
 };
 
-__device__ inline void lb_log_ei_helper(double u, double* h, double* dh) {
-  const double inv_sqrt2 = 0.7071067811865476, inv_sqrt_2pi = 0.3989422804014327, log2pi = 1.8378770664093453;
-  if (u > -1.0) {
-    const double phi = inv_sqrt_2pi * exp(-0.5 * u * u);
-    const double Phi = 0.5 * erfc(-inv_sqrt2 * u);
-    const double ei = phi + u * Phi;
-    *h = log(ei);
-    *dh = Phi / ei;
-    return;
-  }
-  const double log_phi = -0.5 * (u * u + log2pi);
-  if (u > -1e6) {
-    const double ex = erfcx(-inv_sqrt2 * u);
-    const double E = (ex * fabs(u)) * 1.2533141373155003;
-    *h = log_phi + log1p(-E);
-    const double dw = (u + 0.7978845608028654 / ex) + 1.0 / u;
-    *dh = -u - dw * E / (1.0 - E);
-  } else {
-    *h = log_phi - 2.0 * log(fabs(u));
-    *dh = -u - 2.0 / u;
-  }
-}
-// scalar chain of one query (kernels_acq.hip: acq_scalar_core): value and the two coefficients of the gradient's chain rule
-__device__ inline void lb_scalar_core(double vv, double mus, const LbEval& E, double* value, double* c_mu, double* c_sg) {
-  const double mu = E.ym + E.ysd * mus;
-  double var = (1.0 - vv) * (E.ysd * E.ysd);
-  bool clamped = false;
-  if (!(var >= 1e-10)) { var = 1e-10; clamped = true; }
-  if (var < 1e-12) { var = 1e-12; clamped = true; }
-  const double sigma = sqrt(var);
-  const double sgn = E.maximize ? 1.0 : -1.0;
-  if (E.acq == 2) {                     // PCABO_ACQ_UCB: kappa in the best_f slot; linear in mu and sigma, no u
-    const double kappa = E.best_f;
-    *value = __fma_rn(kappa, sigma, sgn * mu);    // as acq_scalar_core spells it
-    *c_mu = sgn * E.ysd;
-    *c_sg = clamped ? 0.0 : kappa * (-(E.ysd * E.ysd) / sigma);
-    return;
-  }
-  double u = (mu - E.best_f) / sigma;
-  u *= sgn;
-  double val, dv_du, dv_dsig;
-  if (E.acq == 0) {
-    double h, dh;
-    lb_log_ei_helper(u, &h, &dh);
-    val = h + log(sigma);
-    dv_du = dh;
-    dv_dsig = 1.0 / sigma;
-  } else {
-    val = 0.5 * erfc(-0.7071067811865476 * u);
-    dv_du = 0.3989422804014327 * exp(-0.5 * u * u);
-    dv_dsig = 0.0;
-  }
-  *value = val;
-  *c_mu = dv_du * sgn * E.ysd / sigma;
-  *c_sg = clamped ? 0.0 : (dv_dsig - dv_du * u / sigma) * (-(E.ysd * E.ysd) / sigma);
-}
-
 // x in L.x() (nq * k) -> L.vals()[q] (acquisition values) and, with want_grad, L.g()[q * k + c] = -d value_q / d x_qc
 // (the gradient of the minimised objective -sum_q value_q).  Ends with a work-group barrier.
 // Every global load of a loop trip is issued before the first use: one CU has to pull ~0.8 MB per triangular pass through ~1 us
@@ -1631,19 +1454,11 @@ __device__ __noinline__ void lb_eval(const LbLds L_, int nq, bool want_grad) {
       sq[q] = half ? got + s1[q] : s0[q] + got;
     }
     if (j < n) {
-      const double s5 = 2.23606797749979, il2 = E.inv_ls * E.inv_ls;
+      const double il2 = E.inv_ls * E.inv_ls;
 #pragma unroll
       for (int q = 0; q < LB_GQ; ++q) {
-        const double sqq = sq[q] * il2;
-        if (E.kernel == 1) {
-          ksv[q] = exp(-0.5 * sqq);
-          cf[q] = -ksv[q] * il2;
-        } else {
-          const double dist = sqrt(fmax(sqq, 1e-30));
-          const double e = exp(-s5 * dist);
-          ksv[q] = ((s5 * dist + 1.0) + (5.0 / 3.0) * (dist * dist)) * e;
-          cf[q] = -(5.0 / 3.0) * (1.0 + s5 * dist) * e * il2;
-        }
+        acq_cov(sq[q] * il2, E.kernel, &ksv[q], &cf[q]);
+        cf[q] = cf[q] * il2;
       }
     }
 #pragma unroll
@@ -1727,7 +1542,7 @@ __device__ __noinline__ void lb_eval(const LbLds L_, int nq, bool want_grad) {
     double vv = 0.0, mus = 0.0;
     for (int s = 0; s < S; ++s) { vv += L.red()[s * 10 + tid]; mus += L.red()[s * 10 + LB_GQ + tid]; }
     double value, cmu, csg;
-    lb_scalar_core(vv, mus, E, &value, &cmu, &csg);
+    acq_scalar_chain(vv, mus, E.ym, E.ysd, E.best_f, E.maximize, E.acq, &value, &cmu, &csg);
     L.vals()[tid] = value; L.cq()[2 * tid] = cmu; L.cq()[2 * tid + 1] = csg;
   }
   if (!want_grad) { __syncthreads(); return; }

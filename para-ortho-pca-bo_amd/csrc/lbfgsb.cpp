@@ -868,124 +868,6 @@ void Lbfgsb::subsm(const double* xx, const double* gg) {
   }
 }
 
-void Lbfgsb::dcstep(double* stx, double* fx, double* dx, double* sty, double* fy, double* dy, double* stp, double fp,
-                    double dp, bool* brackt, double stpmin, double stpmax) {
-  const double sgnd = dp * (*dx / std::fabs(*dx));
-  double stpf, stpc, stpq, theta, s, gamma, p, q, r;
-  if (fp > *fx) {
-    theta = 3.0 * (*fx - fp) / (*stp - *stx) + *dx + dp;
-    s = std::fmax(std::fabs(theta), std::fmax(std::fabs(*dx), std::fabs(dp)));
-    gamma = s * std::sqrt((theta / s) * (theta / s) - (*dx / s) * (dp / s));
-    if (*stp < *stx) gamma = -gamma;
-    p = (gamma - *dx) + theta;
-    q = ((gamma - *dx) + gamma) + dp;
-    r = p / q;
-    stpc = *stx + r * (*stp - *stx);
-    stpq = *stx + ((*dx / ((*fx - fp) / (*stp - *stx) + *dx)) / 2.0) * (*stp - *stx);
-    if (std::fabs(stpc - *stx) < std::fabs(stpq - *stx)) stpf = stpc;
-    else stpf = stpc + (stpq - stpc) / 2.0;
-    *brackt = true;
-  } else if (sgnd < 0.0) {
-    theta = 3.0 * (*fx - fp) / (*stp - *stx) + *dx + dp;
-    s = std::fmax(std::fabs(theta), std::fmax(std::fabs(*dx), std::fabs(dp)));
-    gamma = s * std::sqrt((theta / s) * (theta / s) - (*dx / s) * (dp / s));
-    if (*stp > *stx) gamma = -gamma;
-    p = (gamma - dp) + theta;
-    q = ((gamma - dp) + gamma) + *dx;
-    r = p / q;
-    stpc = *stp + r * (*stx - *stp);
-    stpq = *stp + (dp / (dp - *dx)) * (*stx - *stp);
-    if (std::fabs(stpc - *stp) > std::fabs(stpq - *stp)) stpf = stpc;
-    else stpf = stpq;
-    *brackt = true;
-  } else if (std::fabs(dp) < std::fabs(*dx)) {
-    theta = 3.0 * (*fx - fp) / (*stp - *stx) + *dx + dp;
-    s = std::fmax(std::fabs(theta), std::fmax(std::fabs(*dx), std::fabs(dp)));
-    gamma = s * std::sqrt(std::fmax(0.0, (theta / s) * (theta / s) - (*dx / s) * (dp / s)));
-    if (*stp > *stx) gamma = -gamma;
-    p = (gamma - dp) + theta;
-    q = (gamma + (*dx - dp)) + gamma;
-    r = p / q;
-    if (r < 0.0 && gamma != 0.0) stpc = *stp + r * (*stx - *stp);
-    else if (*stp > *stx) stpc = stpmax;
-    else stpc = stpmin;
-    stpq = *stp + (dp / (dp - *dx)) * (*stx - *stp);
-    if (*brackt) {
-      if (std::fabs(stpc - *stp) < std::fabs(stpq - *stp)) stpf = stpc;
-      else stpf = stpq;
-      if (*stp > *stx) stpf = std::fmin(*stp + 0.66 * (*sty - *stp), stpf);
-      else stpf = std::fmax(*stp + 0.66 * (*sty - *stp), stpf);
-    } else {
-      if (std::fabs(stpc - *stp) > std::fabs(stpq - *stp)) stpf = stpc;
-      else stpf = stpq;
-      stpf = std::fmin(stpmax, stpf);
-      stpf = std::fmax(stpmin, stpf);
-    }
-  } else {
-    if (*brackt) {
-      theta = 3.0 * (fp - *fy) / (*sty - *stp) + *dy + dp;
-      s = std::fmax(std::fabs(theta), std::fmax(std::fabs(*dy), std::fabs(dp)));
-      gamma = s * std::sqrt((theta / s) * (theta / s) - (*dy / s) * (dp / s));
-      if (*stp > *sty) gamma = -gamma;
-      p = (gamma - dp) + theta;
-      q = ((gamma - dp) + gamma) + *dy;
-      r = p / q;
-      stpc = *stp + r * (*sty - *stp);
-      stpf = stpc;
-    } else if (*stp > *stx) stpf = stpmax;
-    else stpf = stpmin;
-  }
-  if (fp > *fx) { *sty = *stp; *fy = fp; *dy = dp; }
-  else {
-    if (sgnd < 0.0) { *sty = *stx; *fy = *fx; *dy = *dx; }
-    *stx = *stp; *fx = fp; *dx = dp;
-  }
-  *stp = stpf;
-}
-
-void Lbfgsb::dcsrch(double f, double g, double* stp, double ftol, double gtol, double xtol, double stpmin,
-                    double stpmax, Dcsrch& s) {
-  const double xtrapl = 1.1, xtrapu = 4.0, p5 = 0.5, p66 = 0.66;
-  if (s.task == 0) {
-    if (*stp < stpmin || *stp > stpmax || g >= 0.0) { s.task = 4; return; }
-    s.brackt = false; s.stage = 1; s.finit = f; s.ginit = g; s.gtest = ftol * s.ginit;
-    s.width = stpmax - stpmin; s.width1 = s.width / p5;
-    s.stx = 0.0; s.fx = s.finit; s.gx = s.ginit; s.sty = 0.0; s.fy = s.finit; s.gy = s.ginit;
-    s.stmin = 0.0; s.stmax = *stp + xtrapu * *stp;
-    s.task = 1;
-    return;
-  }
-  const double ftest = s.finit + *stp * s.gtest;
-  if (s.stage == 1 && f <= ftest && g >= 0.0) s.stage = 2;
-  int task = 1;
-  if (s.brackt && (*stp <= s.stmin || *stp >= s.stmax)) task = 3;
-  if (s.brackt && s.stmax - s.stmin <= xtol * s.stmax) task = 3;
-  if (*stp == stpmax && f <= ftest && g <= s.gtest) task = 3;
-  if (*stp == stpmin && (f > ftest || g >= s.gtest)) task = 3;
-  if (f <= ftest && std::fabs(g) <= gtol * (-s.ginit)) task = 2;
-  if (task == 2 || task == 3) { s.task = task; return; }
-  if (s.stage == 1 && f <= s.fx && f > ftest) {
-    double fm = f - *stp * s.gtest, fxm = s.fx - s.stx * s.gtest, fym = s.fy - s.sty * s.gtest;
-    double gm = g - s.gtest, gxm = s.gx - s.gtest, gym = s.gy - s.gtest;
-    dcstep(&s.stx, &fxm, &gxm, &s.sty, &fym, &gym, stp, fm, gm, &s.brackt, s.stmin, s.stmax);
-    s.fx = fxm + s.stx * s.gtest; s.fy = fym + s.sty * s.gtest; s.gx = gxm + s.gtest; s.gy = gym + s.gtest;
-  } else {
-    dcstep(&s.stx, &s.fx, &s.gx, &s.sty, &s.fy, &s.gy, stp, f, g, &s.brackt, s.stmin, s.stmax);
-  }
-  if (s.brackt) {
-    if (std::fabs(s.sty - s.stx) >= p66 * s.width1) *stp = s.stx + p5 * (s.sty - s.stx);
-    s.width1 = s.width;
-    s.width = std::fabs(s.sty - s.stx);
-  }
-  if (s.brackt) { s.stmin = std::fmin(s.stx, s.sty); s.stmax = std::fmax(s.stx, s.sty); }
-  else { s.stmin = *stp + xtrapl * (*stp - s.stx); s.stmax = *stp + xtrapu * (*stp - s.stx); }
-  *stp = std::fmax(*stp, stpmin);
-  *stp = std::fmin(*stp, stpmax);
-  if ((s.brackt && (*stp <= s.stmin || *stp >= s.stmax)) || (s.brackt && s.stmax - s.stmin <= xtol * s.stmax))
-    *stp = s.stx;
-  s.task = 1;
-}
-
 // One call of the line-search driver.  Sets task_ to LBFGSB_FG (x holds the trial point) or
 // LBFGSB_NEW_X (line search finished); info_ != 0 on failure.
 void Lbfgsb::lnsrlb(double* x, double f, const double* g) {
@@ -1021,14 +903,14 @@ void Lbfgsb::lnsrlb(double* x, double f, const double* g) {
     fold_ = f;
     ifun_ = 0;
     iback_ = 0;
-    ls_ = Dcsrch();
+    ls_ = LbLineSearch();
   }
   gd_ = sum_order_ == 1 ? tree_dot(n, g, d_.data()) : ddot(n, g, d_.data());
   if (ifun_ == 0) {
     gdold_ = gd_;
     if (gd_ >= 0.0) { info_ = -4; return; }     // ascent direction: line search impossible
   }
-  dcsrch(f, gd_, &stp_, ftol, gtol, xtol, 0.0, stpmx_, ls_);
+  lb_dcsrch(f, gd_, &stp_, ftol, gtol, xtol, 0.0, stpmx_, ls_);
   xstep_ = stp_ * dnorm_;
   if (ls_.task != 2 && ls_.task != 3) {
     task_ = LBFGSB_FG;

@@ -9,6 +9,7 @@
 // same iterates as scipy's implementation; tests/test_lbfgsb_vs_scipy.py pins it against scipy.
 #pragma once
 #include <vector>
+#include "lb_linesearch.h"
 
 #define LBFGSB_MAXM 32   // largest history length supported (scipy's default is 10)
 
@@ -66,14 +67,7 @@ class Lbfgsb {
   double gdold_ = 0, dtd_ = 0, xstep_ = 0;
   int task_ = LBFGSB_START;
   int phase_ = 0;            // 0 start, 1 waiting for f,g at x0, 2 inside the line search, 3 after NEW_X
-  // dcsrch state
-  struct Dcsrch {
-    int task = 0;            // 0 START, 1 FG, 2 CONVERGENCE, 3 WARNING, 4 ERROR
-    bool brackt = false;
-    int stage = 1;
-    double ginit = 0, gtest = 0, gx = 0, gy = 0, finit = 0, fx = 0, fy = 0, stx = 0, sty = 0, stmin = 0, stmax = 0;
-    double width = 0, width1 = 0;
-  } ls_;
+  LbLineSearch ls_;        // dcsrch state (lb_linesearch.h)
 
   void reset_memory();
   void projgr(const double* x, const double* g);
@@ -88,10 +82,6 @@ class Lbfgsb {
   void lnsrlb(double* x, double f, const double* g);
   void matupd(double rr, double dr);
   void formt();
-  static void dcsrch(double f, double g, double* stp, double ftol, double gtol, double xtol, double stpmin,
-                     double stpmax, Dcsrch& s);
-  static void dcstep(double* stx, double* fx, double* dx, double* sty, double* fy, double* dy, double* stp, double fp,
-                     double dp, bool* brackt, double stpmin, double stpmax);
 };
 
 // scipy.optimize.minimize(method="L-BFGS-B") around Lbfgsb: what scipy's _minimize_lbfgsb does around setulb.  The start is

@@ -1,5 +1,5 @@
-"""The upper-confidence-bound acquisition on the device (PCABO_ACQ_UCB: the third branch of `acq_scalar_core` in
-kernels_acq.hip and of `lb_scalar_core` in kernels_lbfgsb.hip; kappa = sqrt(beta) travels in the `best_f` slot):
+"""The upper-confidence-bound acquisition on the device (PCABO_ACQ_UCB: the third branch of `acq_scalar_chain` in
+acq_math.h, which kernels_acq.hip and `lb_eval` in kernels_lbfgsb.hip share; kappa = sqrt(beta) travels in the `best_f` slot):
 
   * value and gradient of every evaluation path against the reference UCB on the oracle's exact GP (tests/ucb_reference.py);
   * bad kappa / unknown acquisition codes are argument errors that leave the context usable;

@@ -1,7 +1,7 @@
 """The upper confidence bound on the oracle's exact GP, and the states the UCB tests share.
 
 No tests here: `test_ucb_cpu.py` drives the host optimiser over this surface, `test_gpu_ucb.py` judges the HIP kernels
-(`acq_scalar_core` in kernels_acq.hip, `lb_scalar_core` in kernels_lbfgsb.hip) and whole runs by it.
+(`acq_scalar_chain` in acq_math.h, called from kernels_acq.hip and kernels_lbfgsb.hip) and whole runs by it.
 
 botorch's `UpperConfidenceBound` as published (botorch/acquisition/analytic.py):
 
