@@ -14,7 +14,10 @@
 
 extern "C" {
 
-namespace { std::atomic<int> g_minimize_sum_order{0}; }       // pcabo_lbfgsb_set_sum_order: read by pcabo_lbfgsb_minimize alone
+namespace {
+std::atomic<int> g_minimize_sum_order{0};                     // pcabo_lbfgsb_set_sum_order: read by pcabo_lbfgsb_minimize alone
+thread_local unsigned g_last_branches[LBB_COUNT] = {};        // the branch counters of this thread's last pcabo_lbfgsb_minimize
+}
 
 int pcabo_lbfgsb_minimize(int nvar, double* x, const double* lower, const double* upper, pcabo_fg_callback fg,
                           void* user, int m, double factr, double pgtol, int maxiter, int maxfun, int maxls,
@@ -28,7 +31,32 @@ int pcabo_lbfgsb_minimize(int nvar, double* x, const double* lower, const double
   if (nit) *nit = run.niter;
   if (nfev) *nfev = run.nfev;
   if (task_out) *task_out = run.opt.task();
+  { std::vector<double> end((size_t)nvar); run.end_point(end.data()); }      // (counted only: botorch's end, as the restart groups take it)
+  std::copy(run.opt.branches(), run.opt.branches() + LBB_COUNT, g_last_branches);
   return run.opt.warnflag();
+}
+
+// Debug exports, not part of the ABI in include/pcabo.h (tests/test_lbfgsb_branches_cpu.py).  The names of the optimiser's branch
+// counters (lbfgsb.h), comma-separated, into buf; returns their number.
+int pcabo_debug_lbfgsb_branch_names(char* buf, int cap) {
+  if (buf && cap > 0) {
+    size_t at = 0;
+    buf[0] = 0;
+    for (int i = 0; i < LBB_COUNT; ++i) {
+      const char* nm = lbfgsb_branch_name(i);
+      const size_t len = strlen(nm);
+      if (at + len + 2 > (size_t)cap) break;
+      if (i) buf[at++] = ',';
+      memcpy(buf + at, nm, len + 1);
+      at += len;
+    }
+  }
+  return LBB_COUNT;
+}
+// The counters of the calling thread's last pcabo_lbfgsb_minimize into out[0 .. min(cap, LBB_COUNT)); returns LBB_COUNT.
+int pcabo_debug_lbfgsb_branches(unsigned* out, int cap) {
+  if (out) for (int i = 0; i < LBB_COUNT && i < cap; ++i) out[i] = g_last_branches[i];
+  return LBB_COUNT;
 }
 
 int pcabo_lbfgsb_set_vector_kernels(int enabled) { return lbfgsb_set_vector_kernels(enabled); }

@@ -67,17 +67,15 @@ struct RunRestarts {
   // botorch's end: the end points clamped into the box, into cand.  A group whose clamped end point is its last evaluated point
   // copies that evaluation's values (the ones a launch there would give) into vals; any other is handed to redo(group), which must
   // evaluate it there.  Returns the number of groups handed on.
-  template <class Redo> int end_points(double* cand, double* vals, Redo&& redo) const {
+  template <class Redo> int end_points(double* cand, double* vals, Redo&& redo) {
     int n = 0;
-    for (const RestartGroup& rg : grp) {
-      double* c = cand + (size_t)rg.q0 * rg.k;
-      for (size_t t = 0; t < rg.x.size(); ++t) c[t] = rg.x[t] < rg.lo[t] ? rg.lo[t] : (rg.x[t] > rg.hi[t] ? rg.hi[t] : rg.x[t]);
-      if (rg.have_cache && memcmp(c, rg.xc.data(), rg.x.size() * sizeof(double)) == 0) std::copy(rg.vc.begin(), rg.vc.end(), vals + rg.q0);
+    for (RestartGroup& rg : grp) {
+      if (rg.end_point(cand + (size_t)rg.q0 * rg.k)) std::copy(rg.vc.begin(), rg.vc.end(), vals + rg.q0);   // (LbfgsbDriver: clamp, compare, count)
       else { redo(rg); ++n; }
     }
     return n;
   }
-  int end_points(double* cand, double* vals) const { return end_points(cand, vals, [](const RestartGroup&) {}); }
+  int end_points(double* cand, double* vals) { return end_points(cand, vals, [](const RestartGroup&) {}); }
   // niter, nfev, warnflag, task of group gi into info[4 (slot0 + gi) .. + 3] (info may be null); true: some group failed
   // (warnflag 2)
   bool report(int* info, size_t slot0) const {

@@ -1677,11 +1677,12 @@ __global__ __launch_bounds__(LB_THREADS) void k_lbfgsb_group(
     const double* __restrict__ Xq, const double* __restrict__ ZnT, const double* __restrict__ R, const double* __restrict__ RT,
     const double* __restrict__ alpha, const double* __restrict__ bounds4, const double* __restrict__ ystats,
     const double* __restrict__ bestf, const int* __restrict__ k_dev, double inv_ls, int maximize, int acq, int kernel,
-    double* __restrict__ out_x, double* __restrict__ out_v, size_t zs, const double* __restrict__ hyp) {
+    double* __restrict__ out_x, double* __restrict__ out_v, size_t zs, const double* __restrict__ hyp, int group_size) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
   const unsigned ent = table[blockIdx.x];
   const unsigned run_ = ent >> 16;
-  const int q0 = (int)((ent >> 8) & 0xffu), nq = (int)(ent & 0xffu), gi = q0 / LB_GQ;
+  const int q0 = (int)((ent >> 8) & 0xffu), nq = (int)(ent & 0xffu);
+  const int gi = q0 / group_size;                       // the host reads group gi's counters: groups start at multiples of the call's batch_limit
   Xq = zrun(Xq, zs, run_); ZnT = zrun(ZnT, zs, run_); R = zrun(R, zs, run_); RT = zrun(RT, zs, run_);
   alpha = zrun(alpha, zs, run_); bounds4 = zrun(bounds4, zs, run_); ystats = zrun(ystats, zs, run_);
   bestf = zrun(bestf, zs, run_); k_dev = zrun(k_dev, zs, run_); out_x = zrun(out_x, zs, run_); out_v = zrun(out_v, zs, run_);
@@ -1828,7 +1829,9 @@ bool lbfgsb_device_possible(int NP, int kmax, int batch_limit) {
 int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int mode, int num_restarts, int maxiter, int n, int NP,
                         int ld, const double* Xq, const double* ZnT, const double* R, const double* RT, const double* alpha,
                         const double* bounds4, const double* ystats, const double* bestf, const int* k_dev, double inv_ls,
-                        int maximize, int acq, int kernel, double* out_x, double* out_v, size_t zs, const double* hyp) {
+                        int maximize, int acq, int kernel, double* out_x, double* out_v, size_t zs, const double* hyp,
+                        int batch_limit) {
+  if (batch_limit < 1 || batch_limit > LB_GQ) return -1;
   const size_t lds = lb_lds_doubles(NP) * sizeof(double);
   if (lds > 150 * 1024) return -1;
   if (lb_lds_doubles(NP) < (size_t)OFF_KS + 2 * LB_TILE) return -1;      // the step's two transposition tiles lie in the evaluation's arrays
@@ -1844,6 +1847,6 @@ int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int 
     }
   }
   hipLaunchKernelGGL(k_lbfgsb_group, dim3(entries), dim3(LB_THREADS), lds, st, table, mode, num_restarts, maxiter, n, NP, ld, Xq,
-                     ZnT, R, RT, alpha, bounds4, ystats, bestf, k_dev, inv_ls, maximize, acq, kernel, out_x, out_v, zs, hyp);
+                     ZnT, R, RT, alpha, bounds4, ystats, bestf, k_dev, inv_ls, maximize, acq, kernel, out_x, out_v, zs, hyp, batch_limit);
   return 0;
 }

@@ -240,6 +240,15 @@ int dtrsl_recip(const double* t, int ldt, int nn, double* b, int job) {
 
 }  // namespace
 
+const char* lbfgsb_branch_name(int which) {
+  static const char* const names[LBB_COUNT] = {
+#define LBFGSB_BRANCH_NAME(name) #name,
+    LBFGSB_BRANCH_LIST(LBFGSB_BRANCH_NAME)
+#undef LBFGSB_BRANCH_NAME
+  };
+  return which >= 0 && which < LBB_COUNT ? names[which] : nullptr;
+}
+
 int lbfgsb_set_vector_kernels(int enabled) {
   const bool was = &vec_kernels() != &g_scalar_kernels;
   g_kernels.store(enabled ? default_kernels() : &g_scalar_kernels, std::memory_order_release);
@@ -266,6 +275,7 @@ void Lbfgsb::init(int n, int m, const double* lower, const double* upper, double
   wa_.assign((size_t)8 * m, 0.0);
   index_.assign(n, 0); iwhere_.assign(n, 0); indx2_.assign(n, 0);
   task_ = LBFGSB_START; phase_ = 0;
+  for (unsigned& b : branch_) b = 0;
 }
 
 void Lbfgsb::reset_memory() {
@@ -309,14 +319,17 @@ bool Lbfgsb::active_init(double* x) {
       else if (nbd_[i] >= 2 && x[i] >= u_[i]) { if (x[i] > u_[i]) { prjctd_ = true; x[i] = u_[i]; } }
     }
   }
+  int nfixed = 0;
   for (int i = 0; i < n_; ++i) {
     if (nbd_[i] != 2) boxed_ = false;
     if (nbd_[i] == 0) iwhere_[i] = -1;
     else {
       cnstnd_ = true;
       iwhere_[i] = (nbd_[i] == 2 && u_[i] - l_[i] <= 0.0) ? 3 : 0;
+      nfixed += iwhere_[i] == 3;
     }
   }
+  if (nfixed) count(LBB_fixed_variable);
   return true;
 }
 
@@ -412,8 +425,10 @@ void Lbfgsb::cauchy(const double* x, const double* g) {
   double* xcp = z_.data();
   int* iorder = indx2_.data();
   if (sbgnrm_ <= 0.0) { std::memcpy(xcp, x, sizeof(double) * n); return; }
+  if (col == 0) count(LBB_cauchy_first_iter);
   bool bnded = true;
   int nfree = n, nbreak = 0, ibkmin = 0, nmove = 0;
+  int onbound = 0, ncross = 0, ties = 0;          // (branch counters: variables held on a bound, breakpoints crossed, tied minima)
   double bkmin = 0.0;
   const int col2 = 2 * col;
   double f1 = 0.0;
@@ -433,7 +448,7 @@ void Lbfgsb::cauchy(const double* x, const double* g) {
         else if (std::fabs(neggi) <= 0.0) iw = -3;
         iwhere_[i] = iw;
       }
-      if (iw != 0) { d[i] = 0.0; continue; }
+      if (iw != 0) { d[i] = 0.0; onbound += iw == 1 || iw == 2; continue; }
       d[i] = neggi;
       f1 -= neggi * neggi;
       sc_rows_[nmove] = i;
@@ -466,6 +481,7 @@ void Lbfgsb::cauchy(const double* x, const double* g) {
     }
     if (iwhere_[i] != 0 && iwhere_[i] != -1) {
       d[i] = 0.0;
+      onbound += iwhere_[i] == 1 || iwhere_[i] == 2;
     } else {
       d[i] = neggi;
       f1 -= neggi * neggi;
@@ -488,6 +504,7 @@ void Lbfgsb::cauchy(const double* x, const double* g) {
       }
     }
   }
+  if (onbound) count(LBB_cauchy_start_on_bound);
   if (sum_order_ == 1) {
     // f1 = -(sum of neggi^2 over the moving variables), d itself is the full-length coefficient vector (0.0 elsewhere)
     for (int i = 0; i < n; ++i) sc_full_[i] = d[i] * d[i];
@@ -538,10 +555,17 @@ void Lbfgsb::cauchy(const double* x, const double* g) {
         ibp = iorder[nleft - 1];
       }
       const double dt = tj - tj0;
+      // a smallest remaining breakpoint that is not the only one with its value: the order in which such a pair is crossed is
+      // the heap's.  Counted as the device's search counts it (every pass of its loop, which it enters once the first
+      // breakpoint is known to be crossed), without looking at the set: after hpsolb the next smallest is the root of the heap
+      // that is left, and the first breakpoint had a twin exactly when the second pass pops its value again.
+      if (iter == 2 && tj == tj0) ++ties;
+      if (iter >= 2 && nleft > 1 && t[0] == tj) ++ties;
       if (dtm < dt) break;                     // minimiser inside this segment
       tsum += dt;
       --nleft;
       ++iter;
+      ++ncross;
       const double dibp = d[ibp];
       d[ibp] = 0.0;
       double zibp;
@@ -581,6 +605,9 @@ void Lbfgsb::cauchy(const double* x, const double* g) {
       break;
     }
   }
+  if (ncross) count(LBB_cauchy_break_crossed);
+  if (ties) count(LBB_cauchy_ties, (unsigned)ties);
+  if (skip_to_999) count(LBB_cauchy_all_at_bounds);
   if (!skip_to_999) {
     if (dtm <= 0.0) dtm = 0.0;
     tsum += dtm;
@@ -604,6 +631,8 @@ void Lbfgsb::freev() {
       if (iwhere_[k] <= 0) { indx2_[nenter_] = k; ++nenter_; }
     }
   }
+  if (nenter_ > 0) count(LBB_freev_enter);
+  if (ileave_ < n) count(LBB_freev_leave);
   wrk_ = (ileave_ < n) || (nenter_ > 0) || updatd_;
   nfree_ = 0;
   int iact = n;
@@ -832,6 +861,7 @@ void Lbfgsb::subsm(const double* xx, const double* gg) {
     }
   }
   if (iword_ == 0) return;
+  count(LBB_subsm_touched_bound);
   double dd_p = 0.0;
   if (sum_order_ == 1) {
     for (int i = 0; i < n; ++i) sc_coef_[i] = (x[i] - xx[i]) * gg[i];
@@ -839,6 +869,7 @@ void Lbfgsb::subsm(const double* xx, const double* gg) {
   } else
   for (int i = 0; i < n; ++i) dd_p += (x[i] - xx[i]) * gg[i];
   if (dd_p > 0.0) {
+    count(LBB_subsm_truncated);
     std::memcpy(x, xp_.data(), sizeof(double) * n);
     double alpha = 1.0, temp1 = alpha;
     int ibd = 0;
@@ -908,7 +939,7 @@ void Lbfgsb::lnsrlb(double* x, double f, const double* g) {
   gd_ = sum_order_ == 1 ? tree_dot(n, g, d_.data()) : ddot(n, g, d_.data());
   if (ifun_ == 0) {
     gdold_ = gd_;
-    if (gd_ >= 0.0) { info_ = -4; return; }     // ascent direction: line search impossible
+    if (gd_ >= 0.0) { info_ = -4; count(LBB_ls_ascent); return; }     // ascent direction: line search impossible
   }
   lb_dcsrch(f, gd_, &stp_, ftol, gtol, xtol, 0.0, stpmx_, ls_);
   xstep_ = stp_ * dnorm_;
@@ -922,6 +953,7 @@ void Lbfgsb::lnsrlb(double* x, double f, const double* g) {
       for (int i = 0; i < n; ++i) x[i] = stp_ * d_[i] + t_[i];
   } else {
     task_ = LBFGSB_NEW_X;
+    if (iback_ >= 1) count(LBB_ls_backtracked);
   }
 }
 
@@ -931,6 +963,7 @@ void Lbfgsb::matupd(double rr, double dr) {
     col_ = iupdat_;
     itail_ = (head_ + iupdat_ - 1) % m;
   } else {
+    count(LBB_history_wrap);
     itail_ = nxt(itail_, m);
     head_ = nxt(head_, m);
   }
@@ -1009,15 +1042,16 @@ int Lbfgsb::step(double* x, double* fp, double* g) {
   if (phase_ == 1) {
     nfgv_ = 1;
     projgr(x, g);
-    if (sbgnrm_ <= pgtol_) { task_ = LBFGSB_CONV_PG; return task_; }
+    if (sbgnrm_ <= pgtol_) { task_ = LBFGSB_CONV_PG; count(LBB_start_conv_pg); return task_; }
     need_iteration_start = true;
   } else if (phase_ == 2) {
     resume_linesearch = true;
   } else {  // phase_ == 3: back from NEW_X
-    if (sbgnrm_ <= pgtol_) { task_ = LBFGSB_CONV_PG; return task_; }
+    if (sbgnrm_ <= pgtol_) { task_ = LBFGSB_CONV_PG; count(LBB_conv_pg); return task_; }
     const double ddum = std::fmax(std::fmax(std::fabs(fold_), std::fabs(f)), 1.0);
     if ((fold_ - f) <= tol_ * ddum) {
       task_ = LBFGSB_CONV_F;
+      count(LBB_conv_f);
       if (iback_ >= 10) info_ = -5;
       return task_;
     }
@@ -1026,19 +1060,21 @@ int Lbfgsb::step(double* x, double* fp, double* g) {
     double dr, ddum2;
     if (stp_ == 1.0) { dr = gd_ - gdold_; ddum2 = -gdold_; }
     else {
+      count(LBB_update_scaled_step);
       dr = (gd_ - gdold_) * stp_;
       for (int i = 0; i < n; ++i) d_[i] *= stp_;
       ddum2 = -gdold_ * stp_;
     }
     if (dr <= epsmch_ * ddum2) {
       ++nskip_;
+      count(LBB_update_skipped);
       updatd_ = false;
     } else {
       updatd_ = true;
       ++iupdat_;
       matupd(rr, dr);
       formt();
-      if (info_ != 0) reset_memory();
+      if (info_ != 0) { count(LBB_reset_after_formt); reset_memory(); }
     }
     need_iteration_start = true;
   }
@@ -1055,18 +1091,19 @@ int Lbfgsb::step(double* x, double* fp, double* g) {
         nseg_ = 0;
       } else {
         cauchy(x, g);
-        if (info_ != 0) { reset_memory(); need_iteration_start = true; continue; }
+        if (info_ != 0) { count(LBB_reset_after_cauchy); reset_memory(); need_iteration_start = true; continue; }
         nintol_ += nseg_;
         freev();
         nact_ = n - nfree_;
       }
       // ----- 333: subspace minimisation -----
+      if (nfree_ == 0) count(LBB_subsm_skipped_nfree0);
       if (nfree_ != 0 && col_ != 0) {
-        if (wrk_) formk();
-        if (info_ != 0) { reset_memory(); need_iteration_start = true; continue; }
+        if (wrk_) formk(); else count(LBB_formk_skipped);
+        if (info_ != 0) { count(LBB_reset_after_formk); reset_memory(); need_iteration_start = true; continue; }
         cmprlb(x, g);
         if (info_ == 0) subsm(x, g);
-        if (info_ != 0) { reset_memory(); need_iteration_start = true; continue; }
+        if (info_ != 0) { count(LBB_reset_after_subsm); reset_memory(); need_iteration_start = true; continue; }
       }
       // ----- 555: line search direction -----
       for (int i = 0; i < n; ++i) d_[i] = z_[i] - x[i];
@@ -1083,10 +1120,12 @@ int Lbfgsb::step(double* x, double* fp, double* g) {
       if (col_ == 0) {
         if (info_ == 0) { info_ = -9; --nfgv_; --ifun_; --iback_; }
         task_ = LBFGSB_ABNORMAL;
+        count(LBB_abnormal);
         ++iter_;
         return task_;
       }
       if (info_ == 0) --nfgv_;
+      count(LBB_ls_failed_restart);
       reset_memory();
       need_iteration_start = true;
       continue;
@@ -1119,13 +1158,13 @@ bool LbfgsbDriver::advance() {
   while (active) {
     const int task = opt.step(x.data(), &f, g.data());
     if (task == LBFGSB_FG) {
-      if (have_cache && memcmp(x.data(), xc.data(), x.size() * sizeof(double)) == 0) { f = fc; g = gc; continue; }
+      if (have_cache && memcmp(x.data(), xc.data(), x.size() * sizeof(double)) == 0) { f = fc; g = gc; opt.count(LBB_cache_hit); continue; }
       return true;
     }
     if (task == LBFGSB_NEW_X) {
       niter += 1;
       if (keep_accepted) xacc = x;
-      if (niter >= maxiter) opt.stop(LBFGSB_STOP_ITER);
+      if (niter >= maxiter) { opt.stop(LBFGSB_STOP_ITER); opt.count(LBB_stop_iter); }
       else if (nfev > maxfun) opt.stop(LBFGSB_STOP_FUN);
       continue;
     }
@@ -1134,8 +1173,16 @@ bool LbfgsbDriver::advance() {
   return false;
 }
 
+bool LbfgsbDriver::end_point(double* c) {
+  for (size_t i = 0; i < x.size(); ++i) c[i] = opt.clamped((int)i, x[i]);
+  if (have_cache && memcmp(c, xc.data(), x.size() * sizeof(double)) == 0) return true;
+  opt.count(LBB_endpoint_reevaluated);
+  return false;
+}
+
 void LbfgsbDriver::absorb(double fx) {
   f = fx;
   nfev += 1;
+  opt.count(LBB_evaluations);
   xc = x; gc = g; fc = f; have_cache = true;
 }

@@ -25,6 +25,24 @@ enum {
   LBFGSB_ERROR = 90        // invalid input (l > u, ...)
 };
 
+// Branch counters (tests/test_lbfgsb_branches_cpu.py, tests/test_gpu_lbfgsb_branches.py): which branches of the step a run took.
+// Plain integers, one increment per routine call or event; they take part in no floating-point operation.
+#define LBFGSB_BRANCH_LIST(X)                                                                                                   \
+  X(start_conv_pg) X(conv_pg) X(conv_f) X(stop_iter) X(abnormal)                                                                \
+  X(update_skipped) X(update_scaled_step) X(history_wrap)                                                                       \
+  X(cauchy_first_iter) X(cauchy_start_on_bound) X(cauchy_break_crossed) X(cauchy_all_at_bounds) X(cauchy_ties)                  \
+  X(freev_enter) X(freev_leave) X(formk_skipped) X(subsm_skipped_nfree0) X(subsm_touched_bound) X(subsm_truncated)              \
+  X(ls_backtracked) X(ls_ascent) X(ls_failed_restart)                                                                           \
+  X(reset_after_cauchy) X(reset_after_formk) X(reset_after_subsm) X(reset_after_formt)                                          \
+  X(fixed_variable) X(cache_hit) X(endpoint_reevaluated) X(evaluations)
+enum LbfgsbBranch {
+#define LBFGSB_BRANCH_ENUM(name) LBB_##name,
+  LBFGSB_BRANCH_LIST(LBFGSB_BRANCH_ENUM)
+#undef LBFGSB_BRANCH_ENUM
+  LBB_COUNT
+};
+const char* lbfgsb_branch_name(int which);   // "start_conv_pg", ... (null beyond LBB_COUNT)
+
 // 0: scalar O(m n) loops, 1: the default (AVX2 where available); same iterates either way.  Returns the previous setting.
 int lbfgsb_set_vector_kernels(int enabled);
 
@@ -44,10 +62,20 @@ class Lbfgsb {
     return 2;
   }
   int iterations() const { return iter_; }
+  // the branch counters since init (LBB_COUNT of them); count() is for the driver's own events
+  const unsigned* branches() const { return branch_; }
+  void count(int which, unsigned by = 1) { branch_[which] += by; }
+  // v clamped into the bounds of variable i (the end point botorch evaluates)
+  double clamped(int i, double v) const {
+    if (nbd_[i] != 0 && nbd_[i] <= 2 && v < l_[i]) v = l_[i];
+    if (nbd_[i] >= 2 && v > u_[i]) v = u_[i];
+    return v;
+  }
 
  private:
   // problem
   int n_ = 0, m_ = 0, maxls_ = 20;
+  unsigned branch_[LBB_COUNT] = {};
   int sum_order_ = 0;        // 0: the published order, 1: the 64-lane tree order (the device optimiser's twin)
   double factr_ = 1e7, pgtol_ = 1e-5;
   std::vector<double> l_, u_;
@@ -101,4 +129,7 @@ struct LbfgsbDriver {
             int maxfun = 15000, int m = 10, double factr = 1e7, double pgtol = 1e-5, int maxls = 20);
   bool advance();                      // step until f, g are needed at x (true) or the run has stopped (false)
   void absorb(double fx);              // one evaluation at x: fx, and the gradient the caller wrote into g
+  // botorch's end of a run that has stopped: x clamped into the box, into c.  True: that is the last evaluated point (its values
+  // are the cached evaluation's); false: it needs one more evaluation there (counted: endpoint_reevaluated)
+  bool end_point(double* c);
 };

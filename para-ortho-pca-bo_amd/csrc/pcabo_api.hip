@@ -1625,6 +1625,9 @@ struct pcabo_batch {
   bool imap_enqueued = false;            // pcabo_batch_inverse_map_begin without its _end yet
   bool opt_enqueued = false; int opt_restarts = 0, opt_limit = 0; std::vector<int> opt_act;   // pcabo_batch_optimize_acqf_begin without its _end yet
   int dev_lbfgsb = 0;                    // PCABO_OPT_DEVICE_LBFGSB: 1 device-resident L-BFGS-B, 2 its host-stepped twin
+  // debug record of the last optimise call on the device path (pcabo_debug_batch_lbfgsb_*; tests): the twin's branch counters
+  // [B][groups][LBB_COUNT], or the eight doubles per group the kernel wrote [B][groups][8]
+  std::vector<unsigned> dbg_branches; std::vector<double> dbg_group_out; int dbg_groups = 0;
   unsigned *dOptTab = nullptr, *hOptTab = nullptr;   // launch table of the device-resident optimiser (B * 32 entries)
   int opt_cus = 0;                       // PCABO_OPT_LBFGSB_CUS: > 0 = the optimiser's launches run on a stream confined to that many CUs
   hipStream_t optStream = nullptr; int optStream_cus = 0;
@@ -2316,7 +2319,7 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
     if (ks != s) { BHIPCHK(hipEventRecord(batch->evOptIn, s)); BHIPCHK(hipStreamWaitEvent(ks, batch->evOptIn, 0)); }
     if (launch_lbfgsb_group(ks, batch->dOptTab, nent, mode, num_restarts, maxiter, batch->n, batch->NP, c0->ld, c0->dXq, c0->dZnT,
                             c0->dR, c0->dGram, c0->dAlpha, c0->dBounds4, c0->dYstats, c0->dBestF, c0->dK, inv_ls, maximize ? 1 : 0,
-                            acq, batch->kernel, c0->dGrad, c0->dVal, batch->zs, batch_hyp(batch)) != 0)
+                            acq, batch->kernel, c0->dGrad, c0->dVal, batch->zs, batch_hyp(batch), batch_limit) != 0)
       return bset_err(batch, PCABO_ERR_HIP, "the device-resident optimiser could not be launched%s", "");
     if (ks != s) { BHIPCHK(hipEventRecord(batch->evOptOut, ks)); BHIPCHK(hipStreamWaitEvent(s, batch->evOptOut, 0)); }
     BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (size_t)(64 + 8 * ngroups) * sizeof(double), B, hipMemcpyDeviceToHost, s));
@@ -2356,10 +2359,13 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
     batch->opt_enqueued = false;
     BHIPCHK(wait_stream(s));
     BHIPCHK(hipGetLastError());
+    batch->dbg_groups = ngroups; batch->dbg_branches.clear();
+    batch->dbg_group_out.assign((size_t)B * ngroups * 8, 0.0);
     for (int b : act) {
       const pcabo_ctx* c = batch->ctx[b];
       const int k = c->k;
       int any_failed = 0;
+      std::copy(c->hVal + 64, c->hVal + 64 + 8 * ngroups, batch->dbg_group_out.begin() + (size_t)b * ngroups * 8);
       for (int gi = 0; gi < ngroups; ++gi) {
         const double* o = c->hVal + 64 + 8 * gi;
         if (info) { int* io = info + ((size_t)b * ngroups + gi) * 4; io[0] = (int)o[0]; io[1] = (int)o[1]; io[2] = (int)o[2]; io[3] = (int)o[3]; }
@@ -2412,12 +2418,37 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
     for (const auto& [b, rg] : redo)
       std::copy(runs[b].val + rg->q0, runs[b].val + rg->q0 + rg->nq, vals + (size_t)b * num_restarts + rg->q0);
   }
+  batch->dbg_groups = ngroups; batch->dbg_group_out.clear();
+  batch->dbg_branches.assign((size_t)B * ngroups * LBB_COUNT, 0u);
   for (int b = 0; b < B; ++b) {
     const bool any_failed = runs[b].report(info, (size_t)b * ngroups);
     if (failed) failed[b] = any_failed;
     if (status) status[b] = runs[b].status;
+    for (size_t gi = 0; gi < runs[b].grp.size(); ++gi) {
+      RestartGroup& rg = runs[b].grp[gi];
+      // (endpoint_reevaluated is counted where end_points above handed the group to the end-point launch)
+      std::copy(rg.opt.branches(), rg.opt.branches() + LBB_COUNT, batch->dbg_branches.begin() + ((size_t)b * ngroups + gi) * LBB_COUNT);
+    }
   }
   return PCABO_OK;
+}
+
+// Debug exports, not part of the ABI in include/pcabo.h (tests/test_gpu_lbfgsb_branches.py).  After a twin call
+// (PCABO_OPT_DEVICE_LBFGSB = 2) of pcabo_batch_optimize_acqf: the branch counters of lbfgsb.h per (run, restart group), out[B][groups]
+// [LBB_COUNT]; returns the number of groups per run, 0 if the last call was no twin call, -1 if cap (in entries) is too small.
+extern "C" int pcabo_debug_batch_lbfgsb_branches(pcabo_batch* batch, unsigned* out, int cap) {
+  if (!batch || batch->dbg_branches.empty()) return 0;
+  if (!out || (size_t)cap < batch->dbg_branches.size()) return -1;
+  std::copy(batch->dbg_branches.begin(), batch->dbg_branches.end(), out);
+  return batch->dbg_groups;
+}
+// After a device-mode call (value 1; the blocking call or _end): the eight doubles k_lbfgsb_group writes per (run, restart group) -
+// niter, nfev, warnflag, task, status, evaluations, ties, evaluation-cap flag; out[B][groups][8] (zeros for a run that took no part).
+extern "C" int pcabo_debug_batch_lbfgsb_device_out(pcabo_batch* batch, double* out, int cap) {
+  if (!batch || batch->dbg_group_out.empty()) return 0;
+  if (!out || (size_t)cap < batch->dbg_group_out.size()) return -1;
+  std::copy(batch->dbg_group_out.begin(), batch->dbg_group_out.end(), out);
+  return batch->dbg_groups;
 }
 
 int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_restarts, int batch_limit,
@@ -2433,6 +2464,7 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
   const int ngroups = (num_restarts + batch_limit - 1) / batch_limit;
   int rc = batch_put_best_f(batch, best_f);
   if (rc != PCABO_OK) return rc;
+  batch->dbg_branches.clear(); batch->dbg_group_out.clear();      // (a call that takes the host-paced path leaves no debug record)
   if (batch->dev_lbfgsb) {
     const int drc = batch_optimize_device(batch, ics, num_restarts, batch_limit, bounds, maxiter, maximize, acq, cand, vals, info,
                                           failed, status);

@@ -173,6 +173,26 @@ LIB.pcabo_lbfgsb_minimize.argtypes = [
     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
 
 
+# debug exports (not in include/pcabo.h): the branch counters of the host L-BFGS-B and what the device optimiser writes per group
+LIB.pcabo_debug_lbfgsb_branch_names.argtypes = [C.c_char_p, C.c_int]
+LIB.pcabo_debug_lbfgsb_branches.argtypes = [C.c_void_p, C.c_int]
+
+
+def _branch_names():
+    buf = C.create_string_buffer(2048)
+    count = LIB.pcabo_debug_lbfgsb_branch_names(buf, 2048)
+    names = tuple(buf.value.decode().split(","))
+    assert len(names) == count
+    return names
+
+
+LBFGSB_BRANCHES = _branch_names()               # the counters' names, in the order of the enum in csrc/lbfgsb.h
+DEVICE_GROUP_FIELDS = ("niter", "nfev", "warnflag", "task", "status", "evaluations", "ties", "evaluation_cap")
+if hasattr(LIB, "pcabo_debug_batch_lbfgsb_branches"):       # (the host-only checker builds of the library have no batch)
+    LIB.pcabo_debug_batch_lbfgsb_branches.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    LIB.pcabo_debug_batch_lbfgsb_device_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+
+
 def device_count() -> int:
     return int(LIB.pcabo_device_count())
 
@@ -770,6 +790,27 @@ class Batch:
         self._chk(LIB.pcabo_batch_device_acq_eval(self._h, _ptr(xq), int(q), _ptr(bf), int(bool(maximize)), int(acq), _ptr(val), _ptr(grad)))
         return [val[b].copy() for b in range(B)], [grad[b, : q * int(self.k[b])].reshape(q, int(self.k[b])).copy() for b in range(B)]
 
+    def twin_branches(self):
+        """After a twin call (device_lbfgsb = 2) of optimize_acqf: per run a list with one dict per restart group, the host
+        optimiser's branch counters (LBFGSB_BRANCHES)."""
+        nb = len(LBFGSB_BRANCHES)
+        buf = np.zeros(self.B * 32 * nb, dtype=np.uint32)
+        ng = LIB.pcabo_debug_batch_lbfgsb_branches(self._h, _ptr(buf), int(buf.size))
+        if ng <= 0:
+            raise PcaboError(-1, "twin_branches: the last optimise call of this batch was no twin call")
+        arr = buf[: self.B * ng * nb].reshape(self.B, ng, nb)
+        return [[dict(zip(LBFGSB_BRANCHES, (int(v) for v in arr[b, gi]))) for gi in range(ng)] for b in range(self.B)]
+
+    def device_group_out(self):
+        """After a device-mode call (device_lbfgsb = 1) of optimize_acqf / optimize_end: per run a list with one dict per restart
+        group of what the kernel wrote for it (DEVICE_GROUP_FIELDS)."""
+        buf = np.zeros(self.B * 32 * 8)
+        ng = LIB.pcabo_debug_batch_lbfgsb_device_out(self._h, _ptr(buf), int(buf.size))
+        if ng <= 0:
+            raise PcaboError(-1, "device_group_out: the last optimise call of this batch did not run on the device")
+        arr = buf[: self.B * ng * 8].reshape(self.B, ng, 8)
+        return [[dict(zip(DEVICE_GROUP_FIELDS, (int(v) for v in arr[b, gi]))) for gi in range(ng)] for b in range(self.B)]
+
     def set_profiling(self, on: bool) -> None:
         self._chk(LIB.pcabo_batch_set_profiling(self._h, int(bool(on))))
 
@@ -929,4 +970,7 @@ def lbfgsb_minimize(fun, x0, bounds, m=10, factr=1e7, pgtol=1e-5, maxiter=15000,
     warn = LIB.pcabo_lbfgsb_minimize(nvar, _ptr(x), _ptr(lo), _ptr(hi), cfun, None, int(m), float(factr), float(pgtol),
                                      int(maxiter), int(maxfun), int(maxls), C.byref(f_out), C.byref(nit),
                                      C.byref(nfev), C.byref(task))
-    return {"x": x, "fun": f_out.value, "nit": nit.value, "nfev": nfev.value, "warnflag": warn, "task": task.value}
+    br = np.zeros(len(LBFGSB_BRANCHES), dtype=np.uint32)
+    LIB.pcabo_debug_lbfgsb_branches(_ptr(br), int(br.size))
+    return {"x": x, "fun": f_out.value, "nit": nit.value, "nfev": nfev.value, "warnflag": warn, "task": task.value,
+            "branches": dict(zip(LBFGSB_BRANCHES, (int(v) for v in br)))}

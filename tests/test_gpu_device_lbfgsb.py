@@ -5,6 +5,8 @@ group's whole optimisation (botorch gen_candidates_scipy -> scipy L-BFGS-B, PCA_
     device equal, bit for bit, the same runs with the host stepping the same evaluation kernel launch by launch ("device-twin");
   * the evaluation (a third summation order) against the oracle: value + gradient at teacher-forced states;
   * runs in device mode replayed by the oracle with the thresholds of the host-paced batches.
+
+The same equality branch by branch, on directed cases with the twin's branch counters: tests/test_gpu_lbfgsb_branches.py.
 """
 import numpy as np
 import pytest
