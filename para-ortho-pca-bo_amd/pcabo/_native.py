@@ -568,6 +568,19 @@ class Batch:
         except Exception:
             pass
 
+    @staticmethod
+    def _block(a, row):
+        """(array, stride between the runs' blocks in doubles) for an input of `row` doubles per run: the blocks as they lie in the
+        caller's array - a stride instead of a dense copy - where its layout allows; (None, 0) for None."""
+        if a is None:
+            return None, 0
+        a = np.asarray(a, dtype=np.float64)
+        item = a.itemsize
+        inner_ok = all(a.strides[i] == item * int(np.prod(a.shape[i + 1:])) for i in range(1, a.ndim))
+        if a.dtype == np.float64 and inner_ok and a.strides[0] % item == 0 and a.strides[0] // item >= row:
+            return a, a.strides[0] // item
+        return np.ascontiguousarray(a, dtype=np.float64), row
+
     def wpca_gp_condition_begin(self, X, ranks, noise, y, maximize=False, var_threshold=0.95, n_components=0,
                                 lengthscale=0.6931471805599453, gp_noise=0.006737946999085467, kernel=KERNEL_MATERN52):
         """X[B,n,d], ranks[B,n] (int64), noise[B,n,d] or None, y[B,n]: enqueue rows A-H of every run."""
@@ -576,20 +589,9 @@ class Batch:
         assert B == self.B
         ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(B, n)
         y = np.asarray(y, dtype=np.float64).reshape(B, n)
-
-        def block(a, row):          # the runs' blocks as they lie in the caller's array: a stride instead of a dense copy
-            if a is None:
-                return None, 0
-            a = np.asarray(a, dtype=np.float64)
-            item = a.itemsize
-            inner_ok = all(a.strides[i] == item * int(np.prod(a.shape[i + 1:])) for i in range(1, a.ndim))
-            if a.dtype == np.float64 and inner_ok and a.strides[0] % item == 0 and a.strides[0] // item >= row:
-                return a, a.strides[0] // item
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            return a, row
-        X, sx = block(X, n * d)
-        nz, sn = block(noise, n * d)
-        y, sy = block(y, n)
+        X, sx = self._block(X, n * d)
+        nz, sn = self._block(noise, n * d)
+        y, sy = self._block(y, n)
         strides = (0 if sx == n * d else sx, 0 if sn == n * d else sn, 0 if sy == n else sy)
         if strides != getattr(self, "_in_strides", (0, 0, 0)):
             self._chk(LIB.pcabo_batch_set_input_strides(self._h, *strides))
@@ -607,15 +609,8 @@ class Batch:
         B, n, k = Z.shape
         assert B == self.B
         y = np.asarray(y, dtype=np.float64).reshape(B, n)
-
-        def block(a, row):
-            item = a.itemsize
-            inner_ok = all(a.strides[i] == item * int(np.prod(a.shape[i + 1:])) for i in range(1, a.ndim))
-            if inner_ok and a.strides[0] % item == 0 and a.strides[0] // item >= row:
-                return a, a.strides[0] // item
-            return np.ascontiguousarray(a), row
-        Z, sx = block(Z, n * k)
-        y, sy = block(y, n)
+        Z, sx = self._block(Z, n * k)
+        y, sy = self._block(y, n)
         strides = (0 if sx == n * k else sx, 0, 0 if sy == n else sy)
         if strides != getattr(self, "_in_strides", (0, 0, 0)):
             self._chk(LIB.pcabo_batch_set_input_strides(self._h, *strides))
@@ -742,41 +737,35 @@ class Batch:
         self._chk(rc)
         return (nr, int(batch_limit))
 
-    def optimize_end(self, token):
-        nr, batch_limit = token
-        B, MD = self.B, self.max_d
-        ng = (nr + batch_limit - 1) // batch_limit
-        cand, vals = np.zeros((B, nr * MD)), np.zeros((B, nr))
-        info = np.zeros((B, ng, 4), dtype=np.int32)
-        failed, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
-        self._chk(LIB.pcabo_batch_optimize_acqf_end(self._h, nr, batch_limit, _ptr(cand), _ptr(vals), _ptr(info), _ptr(failed), _ptr(status)))
+    def _optimise_outputs(self, nr, batch_limit):
+        """The buffers an optimise call fills (candidates, values, counters per restart group, retry flags, status per run)."""
+        B, ng = self.B, (nr + batch_limit - 1) // batch_limit
+        return (np.zeros((B, nr * self.max_d)), np.zeros((B, nr)), np.zeros((B, ng, 4), dtype=np.int32),
+                np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32))
+
+    def _unpack_optimised(self, nr, cand, vals, info, failed):
+        """Per run (cand nr x k_b, vals, info, failed) out of the packed rows."""
         out = []
-        for b in range(B):
+        for b in range(self.B):
             k = int(self.k[b])
             out.append((cand[b, : nr * k].reshape(nr, k).copy(), vals[b].copy(), info[b].copy(), bool(failed[b])))
-        return out, status
+        return out
+
+    def optimize_end(self, token):
+        nr, batch_limit = token
+        cand, vals, info, failed, status = self._optimise_outputs(nr, batch_limit)
+        self._chk(LIB.pcabo_batch_optimize_acqf_end(self._h, nr, batch_limit, _ptr(cand), _ptr(vals), _ptr(info), _ptr(failed), _ptr(status)))
+        return self._unpack_optimised(nr, cand, vals, info, failed), status
 
     def optimize_acqf(self, ics_list, bounds_list, best_f, maximize=False, acq=ACQ_LOG_EI, batch_limit=5, maxiter=200):
         """ics_list[b]: num_restarts x k_b; bounds_list[b]: 2 x k_b.  Returns per run (cand, vals, info, failed) + status."""
-        B, MD = self.B, self.max_d
-        nr = ics_list[0].shape[0]
-        ng = (nr + batch_limit - 1) // batch_limit
-        ics, bnd = np.zeros((B, nr * MD)), np.zeros((B, 2 * MD))
-        for b in range(B):
-            ics[b, : ics_list[b].size] = np.ascontiguousarray(ics_list[b], dtype=np.float64).ravel()
-            bnd[b, : bounds_list[b].size] = np.ascontiguousarray(bounds_list[b], dtype=np.float64).ravel()
-        bf = _f64(best_f, (B,))
-        cand, vals = np.zeros((B, nr * MD)), np.zeros((B, nr))
-        info = np.zeros((B, ng, 4), dtype=np.int32)
-        failed, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        nr, ics, bnd = self._pack_ics(ics_list, bounds_list)
+        bf = _f64(best_f, (self.B,))
+        cand, vals, info, failed, status = self._optimise_outputs(nr, batch_limit)
         self._chk(LIB.pcabo_batch_optimize_acqf(self._h, _ptr(ics), nr, int(batch_limit), _ptr(bnd), int(maxiter), _ptr(bf),
                                                 int(bool(maximize)), int(acq), _ptr(cand), _ptr(vals), _ptr(info),
                                                 _ptr(failed), _ptr(status)))
-        out = []
-        for b in range(B):
-            k = int(self.k[b])
-            out.append((cand[b, : nr * k].reshape(nr, k).copy(), vals[b].copy(), info[b].copy(), bool(failed[b])))
-        return out, status
+        return self._unpack_optimised(nr, cand, vals, info, failed), status
 
     def device_acq_eval(self, xq_list, best_f, maximize=False, acq=ACQ_LOG_EI):
         """Value and gradient at xq_list[b] (q x k_b, q <= 32) through the evaluation of the device-resident optimiser."""
@@ -825,18 +814,20 @@ class Batch:
         self._chk(LIB.pcabo_batch_get_profile(self._h, _ptr(ms)))
         return dict(zip(("wpca", "gram", "cholesky", "root_inverse_alpha"), ms.tolist()))
 
-    def inverse_map(self, z_list):
+    def _pack_z(self, z_list) -> np.ndarray:
         z = np.zeros((self.B, self.max_d))
         for b, zb in enumerate(z_list):
             z[b, : zb.size] = np.asarray(zb, dtype=np.float64).ravel()
+        return z
+
+    def inverse_map(self, z_list):
+        z = self._pack_z(z_list)
         x = np.empty((self.B, self.d))
         self._chk(LIB.pcabo_batch_inverse_map(self._h, _ptr(z), _ptr(x)))
         return x
 
     def inverse_map_begin(self, z_list) -> None:
-        z = np.zeros((self.B, self.max_d))
-        for b, zb in enumerate(z_list):
-            z[b, : zb.size] = np.asarray(zb, dtype=np.float64).ravel()
+        z = self._pack_z(z_list)
         self._chk(LIB.pcabo_batch_inverse_map_begin(self._h, _ptr(z)))
 
     def inverse_map_end(self):

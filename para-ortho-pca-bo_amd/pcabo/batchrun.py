@@ -200,12 +200,6 @@ class BatchedPCABO:
         from concurrent.futures import ThreadPoolExecutor
         self._pool = ThreadPoolExecutor(max_workers=max(1, self._host_threads))
 
-    def _each(self, fn):
-        """fn(b) for every run, on the host threads."""
-        if self._pool is None or self._host_threads <= 1:
-            return [fn(b) for b in range(self.B)]
-        return list(self._pool.map(fn, range(self.B)))
-
     def _assign_new_best(self, b: int, appended: bool = False) -> None:
         """AbstractBayesianOptimizer.assign_new_best (:196-208): best = min / max of f_evals, its index searched from the previous
         best index.  `appended`: only the last value is new - the same result without walking the list (a strictly better value
@@ -263,18 +257,60 @@ class BatchedPCABO:
             pass                                  # (every wait then happens inside the library call that follows the yield)
 
     def _iteration_steps(self):
-        """The iteration as a generator: it yields wherever the next library call would wait for the device, so that ONE host
-        thread can advance several batches (run_interleaved resumes a batch once its stream has drained).  Driven straight
-        through (iteration()) it is the blocking iteration: same calls, same order, same results."""
-        B, d, n, bt = self.B, self.dimension, self.n, self._batch
+        """The iteration of both classes (BatchedVanillaBO overrides the methods in which it differs) as a generator: it yields
+        wherever the next library call would wait for the device, so that ONE host thread can advance several batches (run_interleaved
+        resumes a batch once its stream has drained).  Driven straight through (iteration()): same calls, same order, same results."""
+        B, n, bt = self.B, self.n, self._batch
         t0 = perf_counter()
-        pre = {}
-        if self.record_trace:
-            for b in range(B):
-                if self.failed[b] is None and (self._trace_filter is None or self._trace_filter(b, n)):
-                    pre[b] = {"numpy_state": self._rs[b].get_state(), "torch_state": self._tg[b].get_state().clone(),
-                              "best_f": self.current_best[b]}
+        pre = {b: {"numpy_state": self._rs[b].get_state(), "torch_state": self._tg[b].get_state().clone(), "best_f": self.current_best[b]}
+               for b in range(B) if self.failed[b] is None and (self._trace_filter is None or self._trace_filter(b, n))} \
+            if self.record_trace else {}
         self._pre_states = pre            # (kept on the object: still there when a run stops in this iteration)
+        bounds, raw, best_f, t1, t2, tfit = yield from self._condition_and_draw(n)
+        token = bt.gp_eval_begin(raw, best_f, self.maximization, self.acq_code)
+        yield "scoring"
+        vals = self._scoring_end(token, n)
+        t4 = perf_counter()
+        idx = self._pick(vals)
+        ics = [raw[b][idx[b]] for b in range(B)]
+        t5 = perf_counter()
+        engines_job = None
+        if self._pool is not None and not self.record_trace and n + 1 < self.budget:
+            self._draw_noise_ahead(n)
+            engines_job = self._build_engines_ahead()
+        token = bt.optimize_begin(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200) \
+            if self._device_lbfgsb == 1 else None
+        if token is not None:             # the device-resident optimiser: one launch, collected when it has drained
+            yield "optimize"
+            outs, status = bt.optimize_end(token)
+        else:
+            outs, status = bt.optimize_acqf(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200)
+        self._after_optimiser(engines_job, outs, status, n)
+        t6 = perf_counter()
+        # per run: the candidate it goes on with (None: parked), its optimiser's counters (a parked run keeps the batch call's)
+        chosen, infos = [None] * B, [out[2] for out in outs]
+        for b in range(B):
+            cand, v, _, failed = outs[b]
+            if self.failed[b] is not None:
+                continue
+            if failed:
+                ics[b], cand, v, infos[b] = self._retry(b, bounds[b], best_f[b])
+            best = int(np.argmax(v))
+            chosen[b] = cand[best]
+            if b in pre:
+                self.trace.append({"b": b, "n": n, "k": int(bt.k[b]), "ic_idx": np.asarray(idx[b]).copy(), "ics": ics[b].copy(),
+                                   "cands": cand.copy(), "vals": v.copy(), "info": infos[b].copy(), "chosen": best,
+                                   "retried": failed, **pre[b]})
+        self.lbfgsb_info.append(infos)
+        yield from self._new_points(chosen, n)
+        for phase, seconds in (("host_prep", t1 - t0), ("pca", t2 - t1), ("wait_score", (t4 - t2) - tfit), ("fit", tfit),
+                               ("init_pick", t5 - t4), ("lbfgsb", t6 - t5), ("tail", perf_counter() - t6)):
+            self.timing[phase] += seconds
+
+    def _condition_and_draw(self, n):
+        """From the evaluated points to conditioned GPs and raw samples to score (a generator: it waits for the weighted PCA).  Returns
+        (the runs' search boxes, raw samples, `best_f` scalars, the clocks at the ends of `host_prep` and `pca`, the fit's seconds)."""
+        B, d, bt = self.B, self.dimension, self._batch
         F = np.ascontiguousarray(self._F[:, :n])      # B x n (a parked run: its finite stand-in, see _park)
         # ranks as the reference forms them per run (PCA_BO.py:330-333; the penalty value repeats, so how numpy's unstable sort
         # orders ties matters): argsort along the rows of the B x n array sorts every row with the routine a 1-D array gets - the
@@ -288,164 +324,138 @@ class BatchedPCABO:
 
         def prep(b):
             fut = ahead.get(b)
-            if fut is not None:
-                nz = fut.result()
-                if nz.shape != (n, d):
-                    raise RuntimeError("noise drawn ahead is out of step with the run")
-                if nz.base is not noise:
-                    noise[b] = nz
-            else:
-                noise[b] = self._rs[b].normal(0, 1e-8, size=(n, d))                   # PCA_BO.py:376, the run's own stream
-        if len(ahead) == B:                        # all drawn ahead: nothing left that a pool thread would do faster
+            nz = fut.result() if fut is not None else self._rs[b].normal(0, 1e-8, size=(n, d))     # PCA_BO.py:376, the run's own stream
+            if nz.shape != (n, d):
+                raise RuntimeError("noise drawn ahead is out of step with the run")
+            if nz.base is not noise:
+                noise[b] = nz
+        if len(ahead) == B or self._host_threads <= 1:     # all drawn ahead: nothing left that a pool thread would do faster
             for b in range(B):
                 prep(b)
         else:
-            self._each(prep)
+            list(self._pool.map(prep, range(B)))
         t1 = perf_counter()
         bt.wpca_gp_condition_begin(self._X[:, :n], ranks, noise, self._F[:, :n], maximize=self.maximization,
                                    var_threshold=self.var_threshold, n_components=self.n_components,
                                    lengthscale=LENGTHSCALE, gp_noise=NOISE)
         # while the device runs the eigen-decompositions: the scrambled Sobol engines, with last iteration's k
         engines, saved = [None] * B, [None] * B
-
         built, self._engines_ahead = self._engines_ahead, {}
-
-        def guess(b):
+        for b in range(B):                # (torch's small ops do not gain from the host threads: measured slower)
             if b in built:
                 saved[b], engines[b] = built[b]
             elif self.k_prev[b]:
                 saved[b] = self._tg[b].get_state()
                 engines[b] = _init.scrambled_sobol_engine(self.k_prev[b], self._tg[b])
-        for b in range(B):                # (torch's small ops do not gain from the host threads: measured slower)
-            guess(b)
         yield "conditioning"
         res = bt.wpca_results()
         self.k_hist.append(np.array([r["k"] for r in res], dtype=np.int32))
         t2 = perf_counter()
         tfit = self._fit_all(n) if self._fit_gp else 0.0
         bounds = bt.acq_bounds()
-        raw = [None] * B
         rawbuf = bt.raw_row_buffer(self.raw_samples)      # the runs' raw samples are drawn straight into the rows the scoring packs
-
-        def draw(b):
+        for b in range(B):
             if engines[b] is not None and res[b]["k"] != self.k_prev[b]:
                 self._tg[b].set_state(saved[b])                                        # wrong guess: as if never drawn
                 engines[b] = None
             if engines[b] is None:
                 engines[b] = _init.scrambled_sobol_engine(res[b]["k"], self._tg[b])
             self.k_prev[b] = res[b]["k"]
-        for b in range(B):
-            draw(b)
         raw = _native.sobol_draw_rows(engines, self.raw_samples, bt.acq_bounds_packed, rawbuf)       # all runs' points, one call
+        return bounds, raw, self._best_f_matched(), t1, t2, tfit
+
+    def _best_f_matched(self) -> list:
+        """_acq_scalars(), with every run's context told which dtype botorch would store its value in."""
         best_f = self._acq_scalars()
-        for b in range(B):
-            bt.ctx[b].match_best_f_dtype(best_f[b])
-        t3 = perf_counter()
-        token = bt.gp_eval_begin(raw, best_f, self.maximization, self.acq_code)
-        yield "scoring"
-        vals, status = bt.gp_eval_end(token)
-        for b in range(B):
+        for b in range(self.B):
+            self._batch.ctx[b].match_best_f_dtype(best_f[b])
+        return best_f
+
+    def _scoring_end(self, token, n: int) -> np.ndarray:
+        """The acquisition values on all runs' raw samples (waits for the scoring); a run that cannot be scored is parked."""
+        vals, status = self._batch.gp_eval_end(token)
+        for b in range(self.B):
             if self.failed[b] is None and (status[b] != 0 or not np.isfinite(vals[b]).all()):
                 self._park(b, n, "GP conditioning failed (K not positive definite)" if status[b] != 0
                            else "non-finite acquisition values on the raw samples")
             if self.failed[b] is not None:
                 vals[b] = np.linspace(0.0, 1.0, vals.shape[1])          # anything finite: the pick below is discarded
-        t4 = perf_counter()
-        pick = _init.initialize_q_batch if self.acq_code != _native.ACQ_PI else _init.initialize_q_batch_nonneg
+        return vals
+
+    def _pick(self, vals: np.ndarray) -> list:
+        """Every run's initial conditions among its raw samples (row indices), drawn with the run's own generator."""
         if self.acq_code != _native.ACQ_PI:       # all runs' Boltzmann weights at once, a run's own generator for its draw
-            idx = _init.initialize_q_batch_rows(vals, self.num_restarts, self._tg,
-                                                skip=[b for b in range(B) if self.failed[b] is not None])
-        else:
-            idx = [pick(vals[b], self.num_restarts, generator=self._tg[b]) if self.failed[b] is None
-                   else np.arange(self.num_restarts) for b in range(B)]
-        ics = [raw[b][idx[b]] for b in range(B)]
-        t5 = perf_counter()
-        if self._pool is not None and not self.record_trace and n + 1 < self.budget:
-            # one task per pool thread, each drawing the blocks of its share of the runs (a submit per run cost the host thread
-            # 0.7 ms per iteration at 30 runs); every run's block comes from its own stream, so the grouping changes nothing
-            alive = [b for b in range(B) if self.failed[b] is None]
-            nxt = self._noise_next = np.empty((B, n + 1, d)) if len(alive) == B else None
-            if nxt is None:
-                nxt = np.empty((B, n + 1, d))
-            T = max(1, min(self._host_threads, len(alive)))
-            for t in range(T):
-                mine = alive[t::T]
+            return _init.initialize_q_batch_rows(vals, self.num_restarts, self._tg,
+                                                 skip=[b for b in range(self.B) if self.failed[b] is not None])
+        return [_init.initialize_q_batch_nonneg(vals[b], self.num_restarts, generator=self._tg[b]) if self.failed[b] is None
+                else np.arange(self.num_restarts) for b in range(self.B)]
 
-                def draw_many(mine=mine, shape=(n + 1, d), dest=nxt):
-                    out = {}
-                    for b in mine:
-                        dest[b] = self._rs[b].normal(0, 1e-8, shape)
-                        out[b] = dest[b]
-                    return out
-                job = self._pool.submit(draw_many)
-                for b in mine:
-                    self._noise_ahead[b] = _Share(job, b)
-            live = [b for b in range(B) if self.failed[b] is None and self.k_prev[b]]
+    def _draw_noise_ahead(self, n: int) -> None:
+        """The next iteration's noise blocks, on the pool while the optimiser runs (see __init__)."""
+        B, d = self.B, self.dimension
+        # one task per pool thread, each drawing the blocks of its share of the runs (a submit per run cost the host thread
+        # 0.7 ms per iteration at 30 runs); every run's block comes from its own stream, so the grouping changes nothing
+        alive = [b for b in range(B) if self.failed[b] is None]
+        nxt = np.empty((B, n + 1, d))
+        self._noise_next = nxt if len(alive) == B else None
+        T = max(1, min(self._host_threads, len(alive)))
 
-            def build_engines():
-                out = {}
-                for b in live:
-                    st = self._tg[b].get_state()
-                    out[b] = (st, _init.scrambled_sobol_engine(self.k_prev[b], self._tg[b]))
-                return out
-            engines_job = self._pool.submit(build_engines)
-        else:
-            engines_job = None
-        token = bt.optimize_begin(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200) \
-            if self._device_lbfgsb == 1 else None
-        if token is not None:             # the device-resident optimiser: one launch, collected when it has drained
-            yield "optimize"
-            outs, status = bt.optimize_end(token)
-        else:
-            outs, status = bt.optimize_acqf(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200)
+        def draw_many(mine):
+            out = {}
+            for b in mine:
+                nxt[b] = self._rs[b].normal(0, 1e-8, (n + 1, d))
+                out[b] = nxt[b]
+            return out
+        for t in range(T):
+            job = self._pool.submit(draw_many, alive[t::T])
+            for b in alive[t::T]:
+                self._noise_ahead[b] = _Share(job, b)
+
+    def _build_engines_ahead(self):
+        """The next iteration's Sobol engines, with this iteration's k as the guess, on one pool thread (see __init__)."""
+        live = [b for b in range(self.B) if self.failed[b] is None and self.k_prev[b]]
+        return self._pool.submit(lambda: {b: (self._tg[b].get_state(), _init.scrambled_sobol_engine(self.k_prev[b], self._tg[b]))
+                                          for b in live})             # (the state is taken before the engine draws from it)
+
+    def _after_optimiser(self, engines_job, outs, status, n: int) -> None:
+        """Keep the engines built ahead - except where the run's generator is needed first - and park what the optimiser gave up."""
         if engines_job is not None:
-            # botorch's retry below draws from a run's generator: a run that needs it takes its generator back first
-            built = engines_job.result()
-            for b in list(built):
+            # botorch's retry draws from a run's generator: a run that needs it takes its generator back first
+            for b, made in engines_job.result().items():
                 if status[b] != 0 or outs[b][3]:
-                    self._tg[b].set_state(built[b][0])
-                    del built[b]
-            self._engines_ahead = built
-        for b in range(B):
+                    self._tg[b].set_state(made[0])
+                else:
+                    self._engines_ahead[b] = made
+        for b in range(self.B):
             if self.failed[b] is None and status[b] != 0:
                 self._park(b, n, "NaN in the acquisition gradient (botorch raises here)" if status[b] == -4
                            else f"acquisition optimisation failed (status {int(status[b])})")
-        t6 = perf_counter()
-        z_new, infos = [], []
-        for b in range(B):
-            cand, v, info, failed = outs[b]
-            if self.failed[b] is not None:
-                z_new.append(np.zeros(int(bt.k[b])))
-                infos.append(info)
-                continue
-            retried = False
-            if failed:       # botorch: OptimizationWarning -> one retry with freshly drawn initial conditions (this run alone)
-                warnings.warn("Optimization failed in `gen_candidates_scipy`; trying again with a new set of "
-                              "initial conditions.", RuntimeWarning)
-                self.retries += 1
-                retried = True
-                c = bt.ctx[b]
-                raw_b = _init.draw_sobol(bounds[b], self.raw_samples, _init.scrambled_sobol_engine(int(bt.k[b]), self._tg[b]))
-                vals_b = c.acq_eval(raw_b, best_f[b], self.maximization, self.acq_code, grad=False)
-                ics_b = raw_b[pick(vals_b, self.num_restarts, generator=self._tg[b])]
-                cand, v, info, failed = c.optimize_acqf(ics_b, bounds[b], best_f[b], self.maximization, self.acq_code,
-                                                        batch_limit=5, maxiter=200)
-                ics[b] = ics_b
-            best = int(np.argmax(v))
-            z_new.append(cand[best])
-            infos.append(info)
-            if b in pre:
-                self.trace.append({"b": b, "n": n, "k": int(bt.k[b]), "ic_idx": np.asarray(idx[b]).copy(), "ics": ics[b].copy(),
-                                   "cands": cand.copy(), "vals": v.copy(), "info": info.copy(), "chosen": best,
-                                   "retried": retried, **pre[b]})
-        self.lbfgsb_info.append(infos)
-        bt.inverse_map_begin(z_new)
+
+    def _retry(self, b: int, bounds, best_f):
+        """botorch: OptimizationWarning -> one retry with freshly drawn initial conditions (this run alone, on its own context).
+        Returns (the new initial conditions, candidates, values, the optimiser's counters)."""
+        warnings.warn("Optimization failed in `gen_candidates_scipy`; trying again with a new set of "
+                      "initial conditions.", RuntimeWarning)
+        self.retries += 1
+        c = self._batch.ctx[b]
+        pick = _init.initialize_q_batch if self.acq_code != _native.ACQ_PI else _init.initialize_q_batch_nonneg
+        raw = _init.draw_sobol(bounds, self.raw_samples, _init.scrambled_sobol_engine(int(self._batch.k[b]), self._tg[b]))
+        vals = c.acq_eval(raw, best_f, self.maximization, self.acq_code, grad=False)
+        ics = raw[pick(vals, self.num_restarts, generator=self._tg[b])]
+        cand, v, info, _ = c.optimize_acqf(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200)
+        return ics, cand, v, info
+
+    def _new_points(self, chosen, n: int):
+        """From every live run's chosen candidate to its next evaluated point (a generator: it waits for the inverse map)."""
+        bt = self._batch
+        bt.inverse_map_begin([np.zeros(int(bt.k[b])) if z is None else z for b, z in enumerate(chosen)])
         yield "inverse map"
         X_new = bt.inverse_map_end()
         f_dev = None
         if self._dev_obj is not None and not self.maximization:
             f_dev, raw_dev, oob_dev = self._dev_obj.evaluate(X_new)
-        for b in range(B):
+        new = []
+        for b in range(self.B):
             if self.failed[b] is not None:
                 continue
             new_x = X_new[b].copy()
@@ -456,29 +466,21 @@ class BatchedPCABO:
                     p.evaluations += 1
                     p.best_raw = min(p.best_raw, float(raw_dev[b]))
                     p.log.append((float(raw_dev[b]), new_x.copy()))
-                self.x_evals[b].append(new_x)
-                self.f_evals[b].append(new_f)
-                self._X[b, n] = new_x
-                self._F[b, n] = new_f
-                self._assign_new_best(b, appended=True)
-                continue
-            outside = not np.all(new_x >= self.bounds[b][:, 0]) or not np.all(new_x <= self.bounds[b][:, 1])
-            # out-of-box candidates are not evaluated; they cost budget and a fixed penalty (PCA_BO.py:260-263)
-            new_f = (-OOB_PENALTY if self.maximization else OOB_PENALTY) if outside else self.problems[b](new_x)
+            else:
+                outside = not np.all(new_x >= self.bounds[b][:, 0]) or not np.all(new_x <= self.bounds[b][:, 1])
+                # out-of-box candidates are not evaluated; they cost budget and a fixed penalty (PCA_BO.py:260-263)
+                new_f = (-OOB_PENALTY if self.maximization else OOB_PENALTY) if outside else self.problems[b](new_x)
+            new.append((b, new_x, new_f))
+        self._append(n, new)
+
+    def _append(self, n: int, new) -> None:
+        """new: (run, point, objective value) of every run that goes on - its (n + 1)-th evaluated point."""
+        for b, new_x, new_f in new:
             self.x_evals[b].append(new_x)
             self.f_evals[b].append(new_f)
             self._X[b, n] = new_x
             self._F[b, n] = new_f
             self._assign_new_best(b, appended=True)
-        t7 = perf_counter()
-        tm = self.timing
-        tm["host_prep"] += t1 - t0
-        tm["pca"] += t2 - t1
-        tm["wait_score"] += (t4 - t2) - tfit
-        tm["fit"] += tfit
-        tm["init_pick"] += t5 - t4
-        tm["lbfgsb"] += t6 - t5
-        tm["tail"] += t7 - t6
 
     def finish(self) -> None:
         if getattr(self, "_saved_torch_threads", None) is not None:
@@ -524,124 +526,32 @@ class BatchedVanillaBO(BatchedPCABO):
         self._boxes_packed = np.ascontiguousarray(np.stack([bx.ravel() for bx in self._boxes]))             # B x [lo(d), hi(d)]
         self.k_prev = [d] * self.B
 
-    def _iteration_steps(self):
-        B, d, n, bt = self.B, self.dimension, self.n, self._batch
-        t0 = perf_counter()
-        pre = {}
-        if self.record_trace:
-            for b in range(B):
-                if self.failed[b] is None and (self._trace_filter is None or self._trace_filter(b, n)):
-                    pre[b] = {"numpy_state": self._rs[b].get_state(), "torch_state": self._tg[b].get_state().clone(),
-                              "best_f": self.current_best[b]}
-        self._pre_states = pre
+    def _condition_and_draw(self, n):
+        B, d, bt = self.B, self.dimension, self._batch
         t1 = perf_counter()
         bt.gp_condition_begin(self._X[:, :n], self._F[:, :n], norm_bounds=self._identity, lengthscale=LENGTHSCALE, gp_noise=NOISE)
         # the scrambled Sobol engines (dimension d, always): built during the last iteration's optimiser phase, or now - while the
         # device conditions the GPs
         built, self._engines_ahead = self._engines_ahead, {}
-        bounds = self._boxes
         rawbuf = bt.raw_row_buffer(self.raw_samples)
         engines = [built[b][1] if b in built else _init.scrambled_sobol_engine(d, self._tg[b]) for b in range(B)]
         raw = _native.sobol_draw_rows(engines, self.raw_samples, self._boxes_packed, rawbuf)
-        best_f = self._acq_scalars()
-        for b in range(B):
-            bt.ctx[b].match_best_f_dtype(best_f[b])
-        t3 = t2 = perf_counter()
+        best_f = self._best_f_matched()
+        t2 = perf_counter()
         tfit = 0.0
         if self._fit_gp:
             yield "conditioning"
             tfit = self._fit_all(n)
-        token = bt.gp_eval_begin(raw, best_f, self.maximization, self.acq_code)
-        yield "scoring"
-        vals, status = bt.gp_eval_end(token)
-        for b in range(B):
-            if self.failed[b] is None and (status[b] != 0 or not np.isfinite(vals[b]).all()):
-                self._park(b, n, "GP conditioning failed (K not positive definite)" if status[b] != 0
-                           else "non-finite acquisition values on the raw samples")
-            if self.failed[b] is not None:
-                vals[b] = np.linspace(0.0, 1.0, vals.shape[1])
-        t4 = perf_counter()
-        pick = _init.initialize_q_batch if self.acq_code != _native.ACQ_PI else _init.initialize_q_batch_nonneg
-        if self.acq_code != _native.ACQ_PI:
-            idx = _init.initialize_q_batch_rows(vals, self.num_restarts, self._tg,
-                                                skip=[b for b in range(B) if self.failed[b] is not None])
-        else:
-            idx = [pick(vals[b], self.num_restarts, generator=self._tg[b]) if self.failed[b] is None
-                   else np.arange(self.num_restarts) for b in range(B)]
-        ics = [raw[b][idx[b]] for b in range(B)]
-        t5 = perf_counter()
-        engines_job = None
-        if self._pool is not None and not self.record_trace and n + 1 < self.budget:
-            live = [b for b in range(B) if self.failed[b] is None]
+        return self._boxes, raw, best_f, t1, t2, tfit
 
-            def build_engines():
-                out = {}
-                for b in live:
-                    st = self._tg[b].get_state()
-                    out[b] = (st, _init.scrambled_sobol_engine(d, self._tg[b]))
-                return out
-            engines_job = self._pool.submit(build_engines)
-        token = bt.optimize_begin(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200) \
-            if self._device_lbfgsb == 1 else None
-        if token is not None:
-            yield "optimize"
-            outs, status = bt.optimize_end(token)
-        else:
-            outs, status = bt.optimize_acqf(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200)
-        if engines_job is not None:
-            built = engines_job.result()
-            for b in list(built):
-                if status[b] != 0 or outs[b][3]:          # botorch's retry draws from the run's generator first
-                    self._tg[b].set_state(built[b][0])
-                    del built[b]
-            self._engines_ahead = built
-        for b in range(B):
-            if self.failed[b] is None and status[b] != 0:
-                self._park(b, n, "NaN in the acquisition gradient (botorch raises here)" if status[b] == -4
-                           else f"acquisition optimisation failed (status {int(status[b])})")
-        t6 = perf_counter()
-        infos = []
-        for b in range(B):
-            cand, v, info, failed = outs[b]
-            infos.append(info)
-            if self.failed[b] is not None:
-                continue
-            retried = False
-            if failed:
-                warnings.warn("Optimization failed in `gen_candidates_scipy`; trying again with a new set of "
-                              "initial conditions.", RuntimeWarning)
-                self.retries += 1
-                retried = True
-                c = bt.ctx[b]
-                raw_b = _init.draw_sobol(bounds[b], self.raw_samples, _init.scrambled_sobol_engine(d, self._tg[b]))
-                vals_b = c.acq_eval(raw_b, best_f[b], self.maximization, self.acq_code, grad=False)
-                ics_b = raw_b[pick(vals_b, self.num_restarts, generator=self._tg[b])]
-                cand, v, info, failed = c.optimize_acqf(ics_b, bounds[b], best_f[b], self.maximization, self.acq_code,
-                                                        batch_limit=5, maxiter=200)
-                ics[b] = ics_b
-                infos[-1] = info
-            best = int(np.argmax(v))
-            if b in pre:
-                self.trace.append({"b": b, "n": n, "k": d, "ic_idx": np.asarray(idx[b]).copy(), "ics": ics[b].copy(),
-                                   "cands": cand.copy(), "vals": v.copy(), "info": info.copy(), "chosen": best,
-                                   "retried": retried, **pre[b]})
-            new_x = np.asarray(cand[best], dtype=np.float64).ravel().copy()
-            new_f = self.problems[b](new_x)                # (Vanilla_BO.py:221-232: the candidate lies in the box and is evaluated)
-            self.x_evals[b].append(new_x)
-            self.f_evals[b].append(new_f)
-            self._X[b, n] = new_x
-            self._F[b, n] = new_f
-            self._assign_new_best(b, appended=True)
-        self.lbfgsb_info.append(infos)
-        t7 = perf_counter()
-        tm = self.timing
-        tm["host_prep"] += t1 - t0
-        tm["pca"] += t2 - t1
-        tm["wait_score"] += (t4 - t3) - tfit
-        tm["fit"] += tfit
-        tm["init_pick"] += t5 - t4
-        tm["lbfgsb"] += t6 - t5
-        tm["tail"] += t7 - t6
+    def _draw_noise_ahead(self, n: int) -> None:
+        pass                                       # (no noise in front of a PCA here: the engines are all there is to make ahead)
+
+    def _new_points(self, chosen, n: int):
+        # (Vanilla_BO.py:221-232: the candidate lies in the box and is evaluated)
+        points = [(b, np.asarray(z, dtype=np.float64).ravel().copy()) for b, z in enumerate(chosen) if z is not None]
+        self._append(n, [(b, x, self.problems[b](x)) for b, x in points])
+        return ()                                  # (nothing to wait for: no inverse map, no fourth yield)
 
 
 def workers_for(side_by_side: int) -> int:

@@ -218,6 +218,63 @@ def test_device_mode_blown_up_run_and_parked_run(native):
         assert np.array_equal(np.vstack(r.x_evals[b]), np.vstack(alone.x_evals[a])), b
 
 
+def _same(a, b) -> bool:
+    """Equality of trace fields: arrays and tensors bit for bit, tuples (numpy's generator state) member by member."""
+    if isinstance(a, (tuple, list)):
+        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, torch.Tensor):
+        return isinstance(b, torch.Tensor) and torch.equal(a, b)
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.dtype == b.dtype and np.array_equal(a, b)
+    return type(a) is type(b) and a == b
+
+
+def test_vanilla_device_mode_with_a_parked_run_and_trace(native):
+    """BatchedVanillaBO where no other GPU test takes it: the device-resident optimiser with the trace recorded and a run
+    parked on the way, driven by iteration() and through run_interleaved - the two drives must agree bit for bit, trace
+    included, and the runs that go on must take the path they take in a batch without the parked one."""
+    from pcabo.batchrun import BatchedVanillaBO, run_interleaved
+    torch.set_num_threads(4)
+    fid, dim, budget, n_doe, insts = 15, 5, 24, 10, [0, 1, 2]
+
+    def make(which):
+        return BatchedVanillaBO([BBOBProblem(fid, i, dim) for i in which], [_seed(fid, dim, i) for i in which], budget, n_doe,
+                                acq_kernel="device", record_trace=True)
+    by_iteration = make(insts)
+    by_iteration.start()
+    for it in range(budget - n_doe):
+        if it == 3:
+            by_iteration._park(1, by_iteration.n, "parked by the test")
+        by_iteration.iteration()
+    by_iteration.finish()
+    interleaved = make(insts)
+    steps, begun = interleaved._iteration_steps, []
+
+    def steps_with_parking():                  # (run_interleaved asks for every iteration's steps: park in front of the fourth)
+        if len(begun) == 3:
+            interleaved._park(1, interleaved.n, "parked by the test")
+        begun.append(interleaved.n)
+        return steps()
+    interleaved._iteration_steps = steps_with_parking
+    run_interleaved([interleaved])
+    alone = make([0, 2])
+    alone.run()
+    for r in (by_iteration, interleaved):
+        assert r.failed == [None, (n_doe + 3, "parked by the test"), None]
+        assert [len(f) for f in r.f_evals] == [budget, n_doe + 3, budget]
+    for b in range(3):
+        assert np.array_equal(np.vstack(by_iteration.x_evals[b]), np.vstack(interleaved.x_evals[b])), b
+        assert np.array_equal(np.array(by_iteration.f_evals[b]), np.array(interleaved.f_evals[b])), b
+    assert len(by_iteration.trace) == len(interleaved.trace) == 2 * (budget - n_doe) + 3
+    for ta, tb in zip(by_iteration.trace, interleaved.trace):
+        assert sorted(ta) == sorted(tb)
+        for key in ta:
+            assert _same(ta[key], tb[key]), (ta["b"], ta["n"], key)
+    for b, a in ((0, 0), (2, 1)):
+        assert np.array_equal(np.vstack(by_iteration.x_evals[b]), np.vstack(alone.x_evals[a])), b
+        assert np.array_equal(np.array(by_iteration.f_evals[b]), np.array(alone.f_evals[a])), b
+
+
 def test_experiment_runner_in_device_mode(native, tmp_path):
     """ExperimentRunner(batch_acq_kernel="device"): the reference's runner surface over device-mode batches interleaved on one
     host thread; the results and the IOHprofiler files do not depend on how the runs are grouped into batches."""
