@@ -79,8 +79,8 @@ int pcabo_last_error(pcabo_ctx* ctx, char* buf, int buflen);
  *   alpha follow behind it), and pcabo_inverse_map runs on the host from the pinned wPCA results (no launch, no wait).
  *   0 = one stream and the k_inverse_map launch.  Same operations in the same order per element: same bits. */
 enum { PCABO_OPT_RESIDENT = 0, PCABO_OPT_BESTF_F32 = 1, PCABO_OPT_GROUP_ACQ = 2,
-       PCABO_OPT_DEVICE_LBFGSB = 3, PCABO_OPT_LBFGSB_CUS = 4 /* batches only, see pcabo_batch_set_option */,
-       PCABO_OPT_HIDDEN_TAIL = 5 };
+       PCABO_OPT_DEVICE_LBFGSB = 3 /* batches only, see pcabo_batch_set_option */,
+       PCABO_OPT_HIDDEN_TAIL = 5 /* (4 was an option that has been removed: the number is not reused) */ };
 int pcabo_set_option(pcabo_ctx* ctx, int option, int value);
 
 /* Rows A-C (+D,J): rank-weighted PCA of the evaluated points.
@@ -313,11 +313,7 @@ int pcabo_batch_set_workers(pcabo_batch* batch, int workers);
  *   without a host round trip (csrc/kernels_lbfgsb.hip; needs n <= 512, k <= 40, batch_limit <= 5 and finite bounds - other
  *   calls take the host-paced path).  Its evaluation sums in an order of its own (a third arithmetic mode, ~1e-15 relative from
  *   the other two).  2 = the same evaluation kernel driven by the HOST's L-BFGS-B, one launch per round: slow, the reference
- *   the device stepping is compared with bit for bit (tests/test_gpu_device_lbfgsb.py).
- * PCABO_OPT_LBFGSB_CUS (default 0 = the whole chip): the launches of the device-resident optimiser go to a stream confined to the
- *   first `value` compute units (hipExtStreamCreateWithCUMask).  Its work-groups hold a whole CU each for milliseconds; with
- *   several batches of one process in flight the rest of the chip stays free for the short kernels of the others.  Results do
- *   not depend on it. */
+ *   the device stepping is compared with bit for bit (tests/test_gpu_device_lbfgsb.py). */
 int pcabo_batch_set_option(pcabo_batch* batch, int option, int value);
 /* Shapes the device-resident optimiser (PCABO_OPT_DEVICE_LBFGSB = 1) covers: points n <= *max_n, reduced dimension k <= *max_k,
  * batch_limit <= *max_group.  A call beyond them is NOT served by it: pcabo_batch_optimize_acqf takes the host-paced path for that

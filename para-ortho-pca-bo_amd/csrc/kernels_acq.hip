@@ -1215,10 +1215,11 @@ __global__ __launch_bounds__(256) void k_acq_group(
 bool acq_group_possible(int NP, int k) { return NP <= 1280 && k <= PCABO_MAXD; }
 
 // Returns 0, or -1 when nothing was launched (the caller must not wait for per-query flags then).
-int launch_acq_group(hipStream_t st, const QueryArgs* tab, int entries, const double* Xq, int n, int k, int NP, int ld,
-                     const double* ZnT, const double* R, const double* alpha, const double* bounds4, const double* ystats,
-                     AcqParams p, double* partial, unsigned int* counters, double* val, double* grad, double* host_val,
-                     double* host_grad, HostMirror* hm, unsigned long long seq, AcqBatch ab) {
+int launch_acq_group(hipStream_t st, const QueryArgs* tab, int entries, const double* Xq, const GpModel& m, AcqParams p,
+                     double* partial, unsigned int* counters, double* val, double* grad, double* host_val, double* host_grad,
+                     HostMirror* hm, unsigned long long seq, AcqBatch ab) {
+  const int n = m.n, k = m.k, NP = m.NP, ld = m.ld;
+  const double *ZnT = m.ZnT, *R = m.R, *alpha = m.alpha, *bounds4 = m.bounds4, *ystats = m.ystats;
   const size_t ks2 = 2 * (((size_t)k + 1) & ~(size_t)1);       // s_ks doubles as s_gout [2 GQ][KS]: the larger of the two
   const size_t lds = ((size_t)GQ * std::max((size_t)NP, ks2) + 4 * 64 * GT_LD + 64 * 8 + GQ * 64 + 2 * GQ + 4 + 2 * GQ + GQ * (((size_t)k + 1) & ~(size_t)1) + 8) * sizeof(double);
   const dim3 grid(NP / 64, entries), block(256);
@@ -1419,32 +1420,30 @@ __global__ __launch_bounds__(256) void k_score_mu(const double* __restrict__ KS,
     partial[((size_t)(q0 + tid) * S + blockIdx.x) * PSTRIDE + 1] = ((s_mu[0][tid] + s_mu[1][tid]) + s_mu[2][tid]) + s_mu[3][tid];
 }
 
-void launch_score_ks_only(hipStream_t st, const double* Xq, int q, int n, int k, int NP, int ld, const double* ZnT,
-                          const double* bounds4, AcqParams p, double* KS) {
-  const int njb = (NP + 255) / 256;
-  hipLaunchKernelGGL(k_score_ks_only, dim3(njb, (q + SC_QB - 1) / SC_QB, 1), dim3(256), 0, st, Xq, q, n, k, NP, ld, ZnT, bounds4, p, KS);
+void launch_score_ks_only(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS) {
+  const int njb = (m.NP + 255) / 256;
+  hipLaunchKernelGGL(k_score_ks_only, dim3(njb, (q + SC_QB - 1) / SC_QB, 1), dim3(256), 0, st, Xq, q, m.n, m.k, m.NP, m.ld, m.ZnT,
+                     m.bounds4, p, KS);
 }
 // launch_score behind launch_score_ks_only: the mu_s records, V = R KS^T, the scalar chain per sample
-void launch_score_tail(hipStream_t st, int q, int n, int k, int NP, int ld, const double* R, const double* alpha,
-                       const double* bounds4, const double* ystats, AcqParams p, const double* KS, double* partial, double* val) {
-  const int S = NP / 64, njb = (NP + 255) / 256;
-  hipLaunchKernelGGL(k_score_mu, dim3(njb, (q + SC_QB - 1) / SC_QB, 1), dim3(256), 0, st, KS, q, n, ld, alpha, partial, S);
-  hipLaunchKernelGGL(k_score_gemm, dim3(S, (q + 63) / 64, 1), dim3(256), 0, st, R, KS, q, NP, ld, njb, partial, (size_t)0);
+void launch_score_tail(hipStream_t st, int q, const GpModel& m, AcqParams p, const double* KS, double* partial, double* val) {
+  const int S = m.NP / 64, njb = (m.NP + 255) / 256;
+  hipLaunchKernelGGL(k_score_mu, dim3(njb, (q + SC_QB - 1) / SC_QB, 1), dim3(256), 0, st, KS, q, m.n, m.ld, m.alpha, partial, S);
+  hipLaunchKernelGGL(k_score_gemm, dim3(S, (q + 63) / 64, 1), dim3(256), 0, st, m.R, KS, q, m.NP, m.ld, njb, partial, (size_t)0);
   p.want_grad = 0;
-  hipLaunchKernelGGL(k_acq_combine, dim3((q + 3) / 4, 1, 1), dim3(256), 0, st, partial, q, S, k, bounds4, ystats, p, val,
+  hipLaunchKernelGGL(k_acq_combine, dim3((q + 3) / 4, 1, 1), dim3(256), 0, st, partial, q, S, m.k, m.bounds4, m.ystats, p, val,
                      (double*)nullptr, AcqBatch());
 }
 
 // Value-only scoring of q >= 64 points: KS, then V = R KS^T on MFMA, then the scalar chain per query (k_acq_combine).
-void launch_score(hipStream_t st, const double* Xq, int q, int n, int k, int NP, int ld, const double* ZnT, const double* R,
-                  const double* alpha, const double* bounds4, const double* ystats, AcqParams p, double* KS, double* partial,
-                  double* val, AcqBatch ab, int B) {
-  const int S = NP / 64, njb = (NP + 255) / 256;
-  hipLaunchKernelGGL(k_score_ks, dim3(njb, (q + SC_QB - 1) / SC_QB, B), dim3(256), 0, st, Xq, q, n, k, NP, ld, ZnT, alpha, bounds4,
-                     p, KS, partial, S, ab);
-  hipLaunchKernelGGL(k_score_gemm, dim3(S, (q + 63) / 64, B), dim3(256), 0, st, R, KS, q, NP, ld, njb, partial, ab.zs);
+void launch_score(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS, double* partial, double* val,
+                  AcqBatch ab, int B) {
+  const int S = m.NP / 64, njb = (m.NP + 255) / 256;
+  hipLaunchKernelGGL(k_score_ks, dim3(njb, (q + SC_QB - 1) / SC_QB, B), dim3(256), 0, st, Xq, q, m.n, m.k, m.NP, m.ld, m.ZnT, m.alpha,
+                     m.bounds4, p, KS, partial, S, ab);
+  hipLaunchKernelGGL(k_score_gemm, dim3(S, (q + 63) / 64, B), dim3(256), 0, st, m.R, KS, q, m.NP, m.ld, njb, partial, ab.zs);
   p.want_grad = 0;
-  hipLaunchKernelGGL(k_acq_combine, dim3((q + 3) / 4, 1, B), dim3(256), 0, st, partial, q, S, k, bounds4, ystats, p, val,
+  hipLaunchKernelGGL(k_acq_combine, dim3((q + 3) / 4, 1, B), dim3(256), 0, st, partial, q, S, m.k, m.bounds4, m.ystats, p, val,
                      (double*)nullptr, ab);
 }
 
@@ -1461,12 +1460,11 @@ bool acq_server_possible(int q, int n, int k, int NP) {
   return (S + 1) * q <= cus && S <= 32;      // slab groups + one finishing group per query (acq_server_finish_main)
 }
 
-void launch_acq(hipStream_t st, const QueryArgs* qa, const double* Xq, int q, int n, int k, int NP, int ld,
-                const double* ZnT, const double* R, const double* alpha, const double* bounds4, const double* ystats,
-                AcqParams p, double* partial, unsigned int* counters, double* val,
-                double* grad, double* host_val, double* host_grad, HostMirror* hm, unsigned long long seq,
-                MailPair* dev_mail, MailPair* part_pairs, AcqBatch ab, int B,
-                int table_entries) {
+void launch_acq(hipStream_t st, const QueryArgs* qa, const double* Xq, int q, const GpModel& m, AcqParams p, double* partial,
+                unsigned int* counters, double* val, double* grad, double* host_val, double* host_grad, HostMirror* hm,
+                unsigned long long seq, MailPair* dev_mail, MailPair* part_pairs, AcqBatch ab, int B, int table_entries) {
+  const int n = m.n, k = m.k, NP = m.NP, ld = m.ld;
+  const double *ZnT = m.ZnT, *R = m.R, *alpha = m.alpha, *bounds4 = m.bounds4, *ystats = m.ystats;
   // 16 rows per work-group while S*q groups fit the 256 CUs (NP <= 384 at q = 10), 32 rows beyond that: measured
   // on MI355X (q=10, with gradient) 16 rows win at n=120/250 (22.2 vs 23.0, 26.9 vs 27.8 us), 32 rows at n=449 (34.4 vs
   // 37.3 us).

@@ -1826,11 +1826,11 @@ bool lbfgsb_device_possible(int NP, int kmax, int batch_limit) {
 }
 
 
-int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int mode, int num_restarts, int maxiter, int n, int NP,
-                        int ld, const double* Xq, const double* ZnT, const double* R, const double* RT, const double* alpha,
-                        const double* bounds4, const double* ystats, const double* bestf, const int* k_dev, double inv_ls,
+int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int mode, int num_restarts, int maxiter, const GpModel& m,
+                        const double* Xq, const double* RT, const double* bestf, const int* k_dev, double inv_ls,
                         int maximize, int acq, int kernel, double* out_x, double* out_v, size_t zs, const double* hyp,
                         int batch_limit) {
+  const int NP = m.NP;
   if (batch_limit < 1 || batch_limit > LB_GQ) return -1;
   const size_t lds = lb_lds_doubles(NP) * sizeof(double);
   if (lds > 150 * 1024) return -1;
@@ -1846,7 +1846,7 @@ int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int 
       attr_done[dev] = true;
     }
   }
-  hipLaunchKernelGGL(k_lbfgsb_group, dim3(entries), dim3(LB_THREADS), lds, st, table, mode, num_restarts, maxiter, n, NP, ld, Xq,
-                     ZnT, R, RT, alpha, bounds4, ystats, bestf, k_dev, inv_ls, maximize, acq, kernel, out_x, out_v, zs, hyp, batch_limit);
+  hipLaunchKernelGGL(k_lbfgsb_group, dim3(entries), dim3(LB_THREADS), lds, st, table, mode, num_restarts, maxiter, m.n, NP, m.ld, Xq,
+                     m.ZnT, m.R, RT, m.alpha, m.bounds4, m.ystats, bestf, k_dev, inv_ls, maximize, acq, kernel, out_x, out_v, zs, hyp, batch_limit);
   return 0;
 }

@@ -1074,6 +1074,9 @@ static AcqParams make_params(pcabo_ctx* ctx, double best_f, int maximize, int ac
   return p;
 }
 
+// the conditioned model of a context as the acquisition launchers take it
+static GpModel gp_model(const pcabo_ctx* c) { return {c->n, c->k, c->NP, c->ld, c->dZnT, c->dR, c->dAlpha, c->dBounds4, c->dYstats}; }
+
 // The outcome of waiting for an acquisition launch's flags
 static int acq_published(pcabo_ctx* ctx, FlagWait w) {
   if (w == FLAGS_UNPUBLISHED) {
@@ -1106,12 +1109,10 @@ static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = t
       xdev = ctx->dXq;
     }
     ProfScope ps(ctx, 5, acq_bytes(ctx->n, k, nq, 0), acq_flops(ctx->n, k, nq, 0));
-    launch_score(s, xdev, nq, ctx->n, k, ctx->NP, ctx->ld, ctx->dZnT, ctx->dR, ctx->dAlpha, ctx->dBounds4, ctx->dYstats, p,
-                 ctx->dKS, ctx->dPartial, ctx->dVal);
+    launch_score(s, xdev, nq, gp_model(ctx), p, ctx->dKS, ctx->dPartial, ctx->dVal);
   } else {
     ProfScope ps(ctx, small ? 4 : 5, acq_bytes(ctx->n, k, nq, p.want_grad), acq_flops(ctx->n, k, nq, p.want_grad));
-    launch_acq(s, qa, xdev, nq, ctx->n, k, ctx->NP, ctx->ld, ctx->dZnT, ctx->dR, ctx->dAlpha, ctx->dBounds4, ctx->dYstats,
-               p, ctx->dPartial, ctx->dCounters, ctx->dVal, ctx->dGrad, small ? ctx->hVal : nullptr,
+    launch_acq(s, qa, xdev, nq, gp_model(ctx), p, ctx->dPartial, ctx->dCounters, ctx->dVal, ctx->dGrad, small ? ctx->hVal : nullptr,
                small ? ctx->hGrad : nullptr, small ? ctx->hm : nullptr, seq);
   }
   if (!small) {
@@ -1128,8 +1129,7 @@ static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = t
 // the scalar chain per sample, the values' copy and the wait (eval_staged's GEMM branch without its first kernel's KS half).
 static int score_tail(pcabo_ctx* ctx, int nq, AcqParams& p) {
   hipStream_t s = ctx->stream;
-  launch_score_tail(s, nq, ctx->n, ctx->k, ctx->NP, ctx->ld, ctx->dR, ctx->dAlpha, ctx->dBounds4, ctx->dYstats, p, ctx->dKS,
-                    ctx->dPartial, ctx->dVal);
+  launch_score_tail(s, nq, gp_model(ctx), p, ctx->dKS, ctx->dPartial, ctx->dVal);
   HIPCHK(hipMemcpyAsync(ctx->hVal, ctx->dVal, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(wait_stream(s));
   HIPCHK(hipGetLastError());
@@ -1148,9 +1148,8 @@ static int eval_staged_groups(pcabo_ctx* ctx, const int* g0, const int* gn, int 
     int nq = 0;
     for (int g = 0; g < ng; ++g) nq += gn[g];
     ProfScope ps(ctx, 4, acq_bytes(ctx->n, ctx->k, nq, p.want_grad), acq_flops(ctx->n, ctx->k, nq, p.want_grad));
-    if (launch_acq_group(s, &tab, ng, ctx->hXq, ctx->n, ctx->k, ctx->NP, ctx->ld, ctx->dZnT, ctx->dR, ctx->dAlpha, ctx->dBounds4,
-                         ctx->dYstats, p, ctx->dPartial, ctx->dCounters + PCABO_GROUP_CNT_OFFSET, ctx->dVal, ctx->dGrad, ctx->hVal,
-                         ctx->hGrad, ctx->hm, seq, AcqBatch()) != 0)
+    if (launch_acq_group(s, &tab, ng, ctx->hXq, gp_model(ctx), p, ctx->dPartial, ctx->dCounters + PCABO_GROUP_CNT_OFFSET, ctx->dVal,
+                         ctx->dGrad, ctx->hVal, ctx->hGrad, ctx->hm, seq, AcqBatch()) != 0)
       return set_err(ctx, PCABO_ERR_HIP, "the restart-group acquisition kernel could not be launched%s", "");
   }
   HIPCHK(hipGetLastError());
@@ -1228,7 +1227,7 @@ int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double 
   if (hidden) {
     HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->evZn, 0));
     HIPCHK(hipMemcpyAsync(ctx->dXq, ctx->hXq, (size_t)q * ctx->k * sizeof(double), hipMemcpyHostToDevice, ctx->stream2));
-    launch_score_ks_only(ctx->stream2, ctx->dXq, q, ctx->n, ctx->k, ctx->NP, ctx->ld, ctx->dZnT, ctx->dBounds4, p, ctx->dKS);
+    launch_score_ks_only(ctx->stream2, ctx->dXq, q, gp_model(ctx), p, ctx->dKS);
     HIPCHK(hipEventRecord(ctx->evKS, ctx->stream2));
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evKS, 0));
     rc = score_tail(ctx, q, p);
@@ -1355,9 +1354,8 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
     else if (round_no == 1 && ctx->opt_resident && ctx->mail_bar && !ctx->opt_group_acq && ctx->alone && only_context_here && !ctx->prof && acq_server_possible(nq, ctx->n, k, ctx->NP)) {
       // the evaluations of this call go to ONE resident launch (see k_acq_fast): no launch and no operand refill per round
       srv_cap = nq;
-      launch_acq(ctx->stream, nullptr, nullptr, srv_cap, ctx->n, k, ctx->NP, ctx->ld, ctx->dZnT, ctx->dR, ctx->dAlpha,
-                 ctx->dBounds4, ctx->dYstats, p, ctx->dPartial, ctx->dCounters, ctx->dVal, ctx->dGrad, ctx->hVal, ctx->hGrad,
-                 ctx->hm, ctx->seq + 1, ctx->dMail, ctx->dPairs);
+      launch_acq(ctx->stream, nullptr, nullptr, srv_cap, gp_model(ctx), p, ctx->dPartial, ctx->dCounters, ctx->dVal, ctx->dGrad,
+                 ctx->hVal, ctx->hGrad, ctx->hm, ctx->seq + 1, ctx->dMail, ctx->dPairs);
       HIPCHK(hipGetLastError());
       if (ngroups == 2 && grp[0].active && grp[1].active && nq == num_restarts) {
         // ---- the two restart groups free of each other ------------------------------------------------------------
@@ -1629,9 +1627,6 @@ struct pcabo_batch {
   // [B][groups][LBB_COUNT], or the eight doubles per group the kernel wrote [B][groups][8]
   std::vector<unsigned> dbg_branches; std::vector<double> dbg_group_out; int dbg_groups = 0;
   unsigned *dOptTab = nullptr, *hOptTab = nullptr;   // launch table of the device-resident optimiser (B * 32 entries)
-  int opt_cus = 0;                       // PCABO_OPT_LBFGSB_CUS: > 0 = the optimiser's launches run on a stream confined to that many CUs
-  hipStream_t optStream = nullptr; int optStream_cus = 0;
-  hipEvent_t evOptIn = nullptr, evOptOut = nullptr;
   int G = 0;                             // gangs = worker threads of the L-BFGS-B phase
   std::vector<hipStream_t> gstream;
   GangPool pool;
@@ -1664,9 +1659,6 @@ static void batch_free(pcabo_batch* batch) {
   for (hipEvent_t e : batch->pev) if (e) (void)hipEventDestroy(e);
   if (batch->dSlab) (void)hipFree(batch->dSlab);
   if (batch->hSlab) (void)hipHostFree(batch->hSlab);
-  if (batch->optStream) { (void)hipStreamSynchronize(batch->optStream); (void)hipStreamDestroy(batch->optStream); }
-  if (batch->evOptIn) (void)hipEventDestroy(batch->evOptIn);
-  if (batch->evOptOut) (void)hipEventDestroy(batch->evOptOut);
   if (batch->dOptTab) (void)hipFree(batch->dOptTab);
   if (batch->hOptTab) (void)hipHostFree(batch->hOptTab);
   if (batch->stream) (void)hipStreamDestroy(batch->stream);
@@ -1793,11 +1785,6 @@ int pcabo_batch_set_workers(pcabo_batch* batch, int workers) {
 // is bit-identical to the same run in a stand-alone context with default options.  Not during a call on this batch.
 int pcabo_batch_set_option(pcabo_batch* batch, int option, int value) {
   if (!batch) return PCABO_ERR_ARG;
-  if (option == PCABO_OPT_LBFGSB_CUS) {
-    if (value < 0 || value > 1024) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_set_option: PCABO_OPT_LBFGSB_CUS takes 0 .. 1024 (%s%d)", "", value);
-    batch->opt_cus = value;
-    return PCABO_OK;
-  }
   if (option == PCABO_OPT_DEVICE_LBFGSB) {
     if (value < 0 || value > 2) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_set_option: PCABO_OPT_DEVICE_LBFGSB takes 0, 1 or 2 (%s%d)", "", value);
     // switched on after a conditioning: dGram holds K (or an older RT), not this GP's transposed root inverse - the next
@@ -1987,6 +1974,20 @@ static int batch_max_k(const pcabo_batch* batch) {
   return km;
 }
 
+// the conditioned model of all runs as the batched launchers take it: run 0's operands (the others lie zs bytes apart each), the
+// batch's n / NP, the largest k of the runs
+static GpModel gp_model(const pcabo_batch* batch, int kmax) {
+  GpModel m = gp_model(batch->ctx[0]);
+  m.n = batch->n; m.k = kmax; m.NP = batch->NP;
+  return m;
+}
+// the acquisition constants of a batched launch (best_f travels per run: batch_put_best_f)
+static AcqParams batch_params(const pcabo_batch* batch, int maximize, int acq, int want_grad) {
+  AcqParams p = make_params(batch->ctx[0], 0.0, maximize, acq, want_grad);
+  p.inv_ls = 1.0 / batch->lengthscale; p.kernel = batch->kernel;
+  return p;
+}
+
 static AcqBatch batch_ab(const pcabo_batch* batch, int table, int xq_host) {
   AcqBatch ab;
   ab.zs = batch->zs; ab.hzs = batch->hzs; ab.k_dev = batch->ctx[0]->dK; ab.bestf = batch->ctx[0]->dBestF;
@@ -2021,7 +2022,7 @@ static int batch_put_best_f(pcabo_batch* batch, const double* best_f) {
 // k_znorm and k_gram from the runs' dHyp blocks, then k_mll_grad + k_mll_finish, one strided copy of B x 6 doubles and one wait.
 // hyp_theta[b]: the theta run b is conditioned at, or NULL for a run that rests at the batch's shared model (parked runs).
 // A run whose Cholesky failed in the round is redone alone on its own context (mll_attempts from the first jitter on), as
-// batch_score_impl does; st[b] is PCABO_OK, PCABO_ERR_NOT_PD or a HIP error for every run with a theta, untouched otherwise.
+// batch_score_collect does; st[b] is PCABO_OK, PCABO_ERR_NOT_PD or a HIP error for every run with a theta, untouched otherwise.
 static int batch_mll_round(pcabo_batch* batch, const std::vector<const double*>& hyp_theta, int* st) {
   const int B = batch->B, n = batch->n, NP = batch->NP;
   pcabo_ctx* c0 = batch->ctx[0];
@@ -2175,47 +2176,54 @@ int pcabo_batch_busy(pcabo_batch* batch) {
   return e == hipErrorNotReady ? 1 : (e == hipSuccess ? 0 : PCABO_ERR_HIP);
 }
 
-static int batch_score_impl(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize,
-                            int acq, double* val, int* status, int phase /* 0 both, 1 begin, 2 end */) {
-  if (!batch) return PCABO_ERR_ARG;
-  if (!Xq || !best_f || (!val && phase != 1) || q < 1 || q > batch->max_q)
+// What both halves of the scoring check (_end takes the call's arguments again: it needs them for a run it has to redo alone).
+// out_ok: the caller's val is there - asked before anything is written, also when only the second half will use it.
+static int batch_score_args(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int acq, bool out_ok) {
+  if (!Xq || !best_f || !out_ok || q < 1 || q > batch->max_q)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: bad argument%s", "");
   if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: %s", why);
   // (after pcabo_batch_gp_fit the conditioning has been waited for already: the fitted state is scored by the same launches)
   if (!batch->gp_pending && !batch->fitted) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: no conditioning in flight%s", "");
-  if (phase == 2 && !batch->score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval_end: no _begin before it%s", "");
-  if (phase != 2 && batch->score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: a scoring is already enqueued%s", "");
+  return PCABO_OK;
+}
+
+static int batch_score_enqueue(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq, bool out_ok = true) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (const int rc = batch_score_args(batch, Xq, q, best_f, acq, out_ok)) return rc;
+  if (batch->score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: a scoring is already enqueued%s", "");
   if (batch->wpca_uncollected) { int rc = pcabo_batch_wpca_results(batch, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc != PCABO_OK) return rc; }
   BHIPCHK(hipSetDevice(batch->device));
   hipStream_t s = batch->stream;
   const int B = batch->B, kmax = batch_max_k(batch);
   pcabo_ctx* c0 = batch->ctx[0];
-  if (phase != 2) {
   for (int b = 0; b < B; ++b)
     memcpy(batch->ctx[b]->hXq, Xq + (size_t)b * q * batch->max_d, (size_t)q * batch->ctx[b]->k * sizeof(double));
   BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, c0->hXq, batch->hzs, (size_t)q * kmax * sizeof(double), B, hipMemcpyHostToDevice, s));
-  int rc = batch_put_best_f(batch, best_f);
-  if (rc != PCABO_OK) return rc;
-  AcqParams p = make_params(c0, 0.0, maximize, acq, 0);
-  p.inv_ls = 1.0 / batch->lengthscale; p.kernel = batch->kernel;
+  if (const int rc = batch_put_best_f(batch, best_f)) return rc;
+  const AcqParams p = batch_params(batch, maximize, acq, 0);
   if (score_gemm_possible(q))
-    launch_score(s, c0->dXq, q, batch->n, kmax, batch->NP, c0->ld, c0->dZnT, c0->dR, c0->dAlpha, c0->dBounds4, c0->dYstats, p,
-                 c0->dKS, c0->dPartial, c0->dVal, batch_ab(batch, 0, 0), B);
+    launch_score(s, c0->dXq, q, gp_model(batch, kmax), p, c0->dKS, c0->dPartial, c0->dVal, batch_ab(batch, 0, 0), B);
   else
-    launch_acq(s, nullptr, c0->dXq, q, batch->n, kmax, batch->NP, c0->ld, c0->dZnT, c0->dR, c0->dAlpha, c0->dBounds4, c0->dYstats,
-               p, c0->dPartial, c0->dCounters, c0->dVal, c0->dGrad, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-               batch_ab(batch, 0, 0), B, 0);
+    launch_acq(s, nullptr, c0->dXq, q, gp_model(batch, kmax), p, c0->dPartial, c0->dCounters, c0->dVal, c0->dGrad, nullptr, nullptr,
+               nullptr, 0, nullptr, nullptr, batch_ab(batch, 0, 0), B, 0);
   BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (size_t)q * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipGetLastError());
   batch->score_enqueued = true;
-  }
-  if (phase == 1) return PCABO_OK;
-  BHIPCHK(wait_stream(s));
+  return PCABO_OK;
+}
+
+static int batch_score_collect(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq, double* val,
+                               int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (!batch->score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval_end: no _begin before it%s", "");
+  if (const int rc = batch_score_args(batch, Xq, q, best_f, acq, val != nullptr)) return rc;
+  BHIPCHK(hipSetDevice(batch->device));
+  BHIPCHK(wait_stream(batch->stream));
   BHIPCHK(hipGetLastError());
   batch->score_enqueued = false;
   batch->gp_pending = false; batch->have_gp = true;
   int worst = PCABO_OK;
-  for (int b = 0; b < B; ++b) {
+  for (int b = 0; b < batch->B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
     int st = PCABO_OK;
     if (c->hm->chol_info != 0) {
@@ -2238,14 +2246,15 @@ static int batch_score_impl(pcabo_batch* batch, const double* Xq, int q, const d
 
 int pcabo_batch_gp_condition_end_eval(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize,
                                       int acq, double* val, int* status) {
-  return batch_score_impl(batch, Xq, q, best_f, maximize, acq, val, status, 0);
+  const int rc = batch_score_enqueue(batch, Xq, q, best_f, maximize, acq, val != nullptr);
+  return rc != PCABO_OK ? rc : batch_score_collect(batch, Xq, q, best_f, maximize, acq, val, status);
 }
 int pcabo_batch_gp_condition_end_eval_begin(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq) {
-  return batch_score_impl(batch, Xq, q, best_f, maximize, acq, nullptr, nullptr, 1);
+  return batch_score_enqueue(batch, Xq, q, best_f, maximize, acq);
 }
 int pcabo_batch_gp_condition_end_eval_end(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize,
                                           int acq, double* val, int* status) {
-  return batch_score_impl(batch, Xq, q, best_f, maximize, acq, val, status, 2);
+  return batch_score_collect(batch, Xq, q, best_f, maximize, acq, val, status);
 }
 
 // a run's status at the start of an optimise call: parked by the caller, without a GP, or taking part
@@ -2253,139 +2262,120 @@ static int batch_run_status(const pcabo_batch* batch, int b) {
   return !batch->active[b] ? PCABO_ERR_ARG : !batch->ctx[b]->have_gp ? PCABO_ERR_NOT_PD : PCABO_OK;
 }
 
-// pcabo_batch_optimize_acqf with PCABO_OPT_DEVICE_LBFGSB: every restart group's L-BFGS-B inside one launch of k_lbfgsb_group
-// (value 1), or the host's L-BFGS-B over the same kernel's evaluation-only mode, one launch per round (value 2: the twin the
-// device stepping is compared with).  Returns PCABO_OK / an error, or 1 when the call is not eligible (the caller then takes
-// the host-paced path).
-static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_restarts, int batch_limit, const double* bounds,
-                                 int maxiter, int maximize, int acq, double* cand, double* vals, int* info, int* failed,
-                                 int* status, int phase = 0 /* 0 whole call, 1 enqueue only, 2 wait + collect */) {
-  const int B = batch->B, MD = batch->max_d, kmax = batch_max_k(batch);
-  const int ngroups = (num_restarts + batch_limit - 1) / batch_limit;
-  pcabo_ctx* c0 = batch->ctx[0];
-  if (phase == 2) {
-    if (!batch->opt_enqueued || batch->opt_restarts != num_restarts || batch->opt_limit != batch_limit)
-      return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_end: no matching _begin before it%s", "");
-  } else if (batch->opt_enqueued) {
-    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: an optimisation of this batch is already enqueued%s", "");
-  } else if (!lbfgsb_device_possible(batch->NP, kmax, batch_limit) || num_restarts > PCABO_INLAUNCH_MAXQ || maxiter < 1 ||
-      batch->max_q < 64 + 8 * ngroups || (size_t)(num_restarts + 2) * kmax > (size_t)batch->max_q * MD)
-    return 1;
-  std::vector<int> act;
-  if (phase == 2) act = batch->opt_act;
-  else
-  for (int b = 0; b < B; ++b) {
-    const pcabo_ctx* c = batch->ctx[b];
-    if (!batch->active[b] || !c->have_gp) continue;
+// ---- pcabo_batch_optimize_acqf with PCABO_OPT_DEVICE_LBFGSB: every restart group's L-BFGS-B inside one launch of k_lbfgsb_group
+// (value 1: device_opt_enqueue / device_opt_collect), or the host's L-BFGS-B over the same kernel's evaluation-only mode, one launch
+// per round (value 2, batch_optimize_twin: the twin the device stepping is compared with).
+
+// Does the call qualify (the kernel's size limits, room for its records in the runs' buffers, finite ordered bounds of every run
+// that takes part)?  act: those runs.  A call that does not takes the host-paced path.
+static bool device_opt_eligible(const pcabo_batch* batch, int num_restarts, int batch_limit, const double* bounds, int maxiter,
+                                std::vector<int>* act) {
+  const int MD = batch->max_d, kmax = batch_max_k(batch), ngroups = (num_restarts + batch_limit - 1) / batch_limit;
+  if (!lbfgsb_device_possible(batch->NP, kmax, batch_limit) || maxiter < 1 || batch->max_q < 64 + 8 * ngroups ||
+      (size_t)(num_restarts + 2) * kmax > (size_t)batch->max_q * MD)
+    return false;
+  act->clear();
+  for (int b = 0; b < batch->B; ++b) {
+    if (batch_run_status(batch, b) != PCABO_OK) continue;
+    const int k = batch->ctx[b]->k;
     const double* bd = bounds + (size_t)b * 2 * MD;
-    for (int j = 0; j < c->k; ++j)
-      if (!std::isfinite(bd[j]) || !std::isfinite(bd[c->k + j]) || bd[j] > bd[c->k + j]) return 1;
-    act.push_back(b);
+    for (int j = 0; j < k; ++j)
+      if (!std::isfinite(bd[j]) || !std::isfinite(bd[k + j]) || bd[j] > bd[k + j]) return false;
+    act->push_back(b);
   }
+  return true;
+}
+
+// One launch of k_lbfgsb_group over the first nent entries of the pinned table, enqueued on the batch's stream: the transposed root
+// inverse of the table's runs where a later conditioning outdated it, the table, the runs' points ([num_restarts x k | lower k |
+// upper k], strided over the runs), the kernel, and back val_doubles values / records and the num_restarts candidates or gradients
+// of every run.  The caller waits for the stream.
+static int device_opt_launch(pcabo_batch* batch, int nent, int mode, int num_restarts, int batch_limit, int maxiter, int maximize,
+                             int acq, size_t val_doubles) {
+  pcabo_ctx* c0 = batch->ctx[0];
   hipStream_t s = batch->stream;
-  if (phase != 2)
-  for (int b : act) {
-    pcabo_ctx* c = batch->ctx[b];
+  const int B = batch->B, kmax = batch_max_k(batch);
+  for (int e = 0; e < nent; ++e) {
+    pcabo_ctx* c = batch->ctx[batch->hOptTab[e] >> 16];
     if (c->rt_stale) { launch_rt_build(s, c->dR, c->n, c->NP, c->ld, c->dGram); c->rt_stale = false; }
   }
-  const size_t xq_doubles = (size_t)(num_restarts + 2) * kmax;
-  const double inv_ls = 1.0 / batch->lengthscale;
-  // PCABO_OPT_LBFGSB_CUS: the optimiser's work-groups take a whole CU each for milliseconds; confined to a part of the chip they
-  // leave the rest to the short kernels of the other batches of the process (conditioning, scoring)
-  hipStream_t ks = s;
-  if (batch->opt_cus > 0) {
-    if (batch->optStream && batch->optStream_cus != batch->opt_cus) {
-      (void)hipStreamSynchronize(batch->optStream); (void)hipStreamDestroy(batch->optStream); batch->optStream = nullptr;
-    }
-    if (!batch->optStream) {
-      hipDeviceProp_t prop;
-      BHIPCHK(hipGetDeviceProperties(&prop, batch->device));
-      const int total = prop.multiProcessorCount, words = (total + 31) / 32;
-      std::vector<uint32_t> mask((size_t)words, 0u);
-      for (int i = 0; i < std::min(batch->opt_cus, total); ++i) mask[i >> 5] |= 1u << (i & 31);
-      if (hipExtStreamCreateWithCUMask(&batch->optStream, (uint32_t)words, mask.data()) != hipSuccess) {
-        (void)hipGetLastError();
-        batch->optStream = nullptr;
-        return bset_err(batch, PCABO_ERR_HIP, "PCABO_OPT_LBFGSB_CUS: a stream with a CU mask could not be created (%s%d CUs)", "", batch->opt_cus);
+  BHIPCHK(hipMemcpyAsync(batch->dOptTab, batch->hOptTab, (size_t)nent * sizeof(unsigned), hipMemcpyHostToDevice, s));
+  BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, c0->hXq, batch->hzs, (size_t)(num_restarts + 2) * kmax * sizeof(double), B, hipMemcpyHostToDevice, s));
+  if (launch_lbfgsb_group(s, batch->dOptTab, nent, mode, num_restarts, maxiter, gp_model(batch, kmax), c0->dXq, c0->dGram, c0->dBestF,
+                          c0->dK, 1.0 / batch->lengthscale, maximize ? 1 : 0, acq, batch->kernel, c0->dGrad, c0->dVal, batch->zs,
+                          batch_hyp(batch), batch_limit) != 0)
+    return bset_err(batch, PCABO_ERR_HIP, "the device-resident optimiser could not be launched%s", "");
+  BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, val_doubles * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  BHIPCHK(hipMemcpy2DAsync(c0->hGrad, batch->hzs, c0->dGrad, batch->zs, (size_t)num_restarts * kmax * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  BHIPCHK(hipGetLastError());
+  return PCABO_OK;
+}
+
+// Device mode, first half: the launch table, the runs' starts and bounds, the one launch; the call's shape is kept for _collect.
+static int device_opt_enqueue(pcabo_batch* batch, const std::vector<int>& act, const double* ics, int num_restarts, int batch_limit,
+                              const double* bounds, int maxiter, int maximize, int acq) {
+  const int MD = batch->max_d, ngroups = (num_restarts + batch_limit - 1) / batch_limit;
+  int nent = 0;
+  for (size_t blk = 0; blk < act.size(); blk += 8)          // both groups of a run on one XCD (work-groups go round the 8 XCDs)
+    for (int gi = 0; gi < ngroups; ++gi)
+      for (size_t r = blk; r < std::min(act.size(), blk + 8); ++r) {
+        const int q0 = gi * batch_limit;
+        batch->hOptTab[nent++] = group_entry(act[r], q0, std::min(batch_limit, num_restarts - q0));
       }
-      batch->optStream_cus = batch->opt_cus;
-      if (!batch->evOptIn) { BHIPCHK(hipEventCreateWithFlags(&batch->evOptIn, hipEventDisableTiming)); BHIPCHK(hipEventCreateWithFlags(&batch->evOptOut, hipEventDisableTiming)); }
-    }
-    ks = batch->optStream;
+  for (int b : act) {
+    pcabo_ctx* c = batch->ctx[b];
+    const int k = c->k;
+    memcpy(c->hXq, ics + (size_t)b * num_restarts * MD, (size_t)num_restarts * k * sizeof(double));
+    memcpy(c->hXq + (size_t)num_restarts * k, bounds + (size_t)b * 2 * MD, (size_t)2 * k * sizeof(double));
   }
-  auto enqueue = [&](int nent, int mode) -> int {
-    BHIPCHK(hipMemcpyAsync(batch->dOptTab, batch->hOptTab, (size_t)nent * sizeof(unsigned), hipMemcpyHostToDevice, s));
-    BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, c0->hXq, batch->hzs, xq_doubles * sizeof(double), B, hipMemcpyHostToDevice, s));
-    if (ks != s) { BHIPCHK(hipEventRecord(batch->evOptIn, s)); BHIPCHK(hipStreamWaitEvent(ks, batch->evOptIn, 0)); }
-    if (launch_lbfgsb_group(ks, batch->dOptTab, nent, mode, num_restarts, maxiter, batch->n, batch->NP, c0->ld, c0->dXq, c0->dZnT,
-                            c0->dR, c0->dGram, c0->dAlpha, c0->dBounds4, c0->dYstats, c0->dBestF, c0->dK, inv_ls, maximize ? 1 : 0,
-                            acq, batch->kernel, c0->dGrad, c0->dVal, batch->zs, batch_hyp(batch), batch_limit) != 0)
-      return bset_err(batch, PCABO_ERR_HIP, "the device-resident optimiser could not be launched%s", "");
-    if (ks != s) { BHIPCHK(hipEventRecord(batch->evOptOut, ks)); BHIPCHK(hipStreamWaitEvent(s, batch->evOptOut, 0)); }
-    BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (size_t)(64 + 8 * ngroups) * sizeof(double), B, hipMemcpyDeviceToHost, s));
-    BHIPCHK(hipMemcpy2DAsync(c0->hGrad, batch->hzs, c0->dGrad, batch->zs, (size_t)num_restarts * kmax * sizeof(double), B, hipMemcpyDeviceToHost, s));
-    BHIPCHK(hipGetLastError());
-    return PCABO_OK;
-  };
-  auto launch = [&](int nent, int mode) -> int {
-    const int rc = enqueue(nent, mode);
-    if (rc != PCABO_OK) return rc;
-    BHIPCHK(wait_stream(s));
-    BHIPCHK(hipGetLastError());
-    return PCABO_OK;
-  };
-  if (batch->dev_lbfgsb == 1) {
-    std::vector<int> run_status(B);
-    for (int b = 0; b < B; ++b) run_status[b] = batch_run_status(batch, b);
-    // ---- everything on the device
-    int nent = 0;
-    if (phase != 2) {
-    for (size_t blk = 0; blk < act.size(); blk += 8)          // both groups of a run on one XCD (work-groups go round the 8 XCDs)
-      for (int gi = 0; gi < ngroups; ++gi)
-        for (size_t r = blk; r < std::min(act.size(), blk + 8); ++r) {
-          const int q0 = gi * batch_limit;
-          batch->hOptTab[nent++] = group_entry(act[r], q0, std::min(batch_limit, num_restarts - q0));
-        }
-    for (int b : act) {
-      pcabo_ctx* c = batch->ctx[b];
-      const int k = c->k;
-      memcpy(c->hXq, ics + (size_t)b * num_restarts * MD, (size_t)num_restarts * k * sizeof(double));
-      memcpy(c->hXq + (size_t)num_restarts * k, bounds + (size_t)b * 2 * MD, (size_t)2 * k * sizeof(double));
+  if (nent > 0)
+    if (const int rc = device_opt_launch(batch, nent, 1, num_restarts, batch_limit, maxiter, maximize, acq, (size_t)(64 + 8 * ngroups))) return rc;
+  batch->opt_act = act; batch->opt_restarts = num_restarts; batch->opt_limit = batch_limit; batch->opt_enqueued = true;
+  return PCABO_OK;
+}
+
+// Device mode, second half: wait, then candidates, values and the kernel's eight counters per restart group to the caller.
+static int device_opt_collect(pcabo_batch* batch, int num_restarts, int batch_limit, double* cand, double* vals, int* info, int* failed,
+                              int* status) {
+  if (!batch->opt_enqueued || batch->opt_restarts != num_restarts || batch->opt_limit != batch_limit)
+    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_end: no matching _begin before it%s", "");
+  const int B = batch->B, MD = batch->max_d, ngroups = (num_restarts + batch_limit - 1) / batch_limit;
+  std::vector<int> run_status(B);
+  for (int b = 0; b < B; ++b) run_status[b] = batch_run_status(batch, b);
+  batch->opt_enqueued = false;
+  BHIPCHK(wait_stream(batch->stream));
+  BHIPCHK(hipGetLastError());
+  batch->dbg_groups = ngroups; batch->dbg_branches.clear();
+  batch->dbg_group_out.assign((size_t)B * ngroups * 8, 0.0);
+  for (int b : batch->opt_act) {
+    const pcabo_ctx* c = batch->ctx[b];
+    const int k = c->k;
+    int any_failed = 0;
+    std::copy(c->hVal + 64, c->hVal + 64 + 8 * ngroups, batch->dbg_group_out.begin() + (size_t)b * ngroups * 8);
+    for (int gi = 0; gi < ngroups; ++gi) {
+      const double* o = c->hVal + 64 + 8 * gi;
+      if (info) { int* io = info + ((size_t)b * ngroups + gi) * 4; io[0] = (int)o[0]; io[1] = (int)o[1]; io[2] = (int)o[2]; io[3] = (int)o[3]; }
+      if ((int)o[2] == 2) any_failed = 1;
+      if ((int)o[4] != 0) run_status[b] = (int)o[4];
+      if ((int)o[7] != 0) run_status[b] = PCABO_ERR_TIMEOUT;       // evaluation cap (cannot happen within maxiter / maxls)
     }
-    if (nent > 0) { const int rc = enqueue(nent, 1); if (rc != PCABO_OK) return rc; }
-    batch->opt_act = act; batch->opt_restarts = num_restarts; batch->opt_limit = batch_limit; batch->opt_enqueued = true;
-    }
-    if (phase == 1) return PCABO_OK;
-    batch->opt_enqueued = false;
-    BHIPCHK(wait_stream(s));
-    BHIPCHK(hipGetLastError());
-    batch->dbg_groups = ngroups; batch->dbg_branches.clear();
-    batch->dbg_group_out.assign((size_t)B * ngroups * 8, 0.0);
-    for (int b : act) {
-      const pcabo_ctx* c = batch->ctx[b];
-      const int k = c->k;
-      int any_failed = 0;
-      std::copy(c->hVal + 64, c->hVal + 64 + 8 * ngroups, batch->dbg_group_out.begin() + (size_t)b * ngroups * 8);
-      for (int gi = 0; gi < ngroups; ++gi) {
-        const double* o = c->hVal + 64 + 8 * gi;
-        if (info) { int* io = info + ((size_t)b * ngroups + gi) * 4; io[0] = (int)o[0]; io[1] = (int)o[1]; io[2] = (int)o[2]; io[3] = (int)o[3]; }
-        if ((int)o[2] == 2) any_failed = 1;
-        if ((int)o[4] != 0) run_status[b] = (int)o[4];
-        if ((int)o[7] != 0) run_status[b] = PCABO_ERR_TIMEOUT;       // evaluation cap (cannot happen within maxiter / maxls)
-      }
-      if (run_status[b] == PCABO_ERR_NAN) set_err(batch->ctx[b], PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
-      memcpy(cand + (size_t)b * num_restarts * MD, c->hGrad, (size_t)num_restarts * k * sizeof(double));
-      memcpy(vals + (size_t)b * num_restarts, c->hVal, (size_t)num_restarts * sizeof(double));
-      if (failed) failed[b] = any_failed;
-    }
-    for (int b = 0; b < B; ++b) {
-      if (failed && batch_run_status(batch, b) != PCABO_OK) failed[b] = 0;
-      if (status) status[b] = run_status[b];
-    }
-    return PCABO_OK;
+    if (run_status[b] == PCABO_ERR_NAN) set_err(batch->ctx[b], PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
+    memcpy(cand + (size_t)b * num_restarts * MD, c->hGrad, (size_t)num_restarts * k * sizeof(double));
+    memcpy(vals + (size_t)b * num_restarts, c->hVal, (size_t)num_restarts * sizeof(double));
+    if (failed) failed[b] = any_failed;
   }
-  if (phase != 0) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin / _end need PCABO_OPT_DEVICE_LBFGSB = 1%s", "");
-  // ---- the twin: host L-BFGS-B (csrc/lbfgsb.cpp), evaluations through mode 0 of the same kernel, one launch per round
+  for (int b = 0; b < B; ++b) {
+    if (failed && batch_run_status(batch, b) != PCABO_OK) failed[b] = 0;
+    if (status) status[b] = run_status[b];
+  }
+  return PCABO_OK;
+}
+
+// The twin: host L-BFGS-B (csrc/lbfgsb.cpp), evaluations through mode 0 of the same kernel, one launch and one wait per round
+static int batch_optimize_twin(pcabo_batch* batch, const std::vector<int>& act, const double* ics, int num_restarts, int batch_limit,
+                               const double* bounds, int maxiter, int maximize, int acq, double* cand, double* vals, int* info,
+                               int* failed, int* status) {
+  const int B = batch->B, MD = batch->max_d, ngroups = (num_restarts + batch_limit - 1) / batch_limit;
   std::vector<RunRestarts> runs(B);
   for (int b = 0; b < B; ++b) runs[b].status = batch_run_status(batch, b);
   for (int b : act) {
@@ -2396,7 +2386,13 @@ static int batch_optimize_device(pcabo_batch* batch, const double* ics, int num_
   }
   int nent = 0;
   auto stage = [&](int b, const RestartGroup& rg) { batch->hOptTab[nent++] = group_entry(b, rg.q0, rg.nq); };
-  auto eval = [&] { const int n = nent; nent = 0; return launch(n, 0); };
+  auto eval = [&]() -> int {
+    const int n = nent; nent = 0;
+    if (const int rc = device_opt_launch(batch, n, 0, num_restarts, batch_limit, maxiter, maximize, acq, (size_t)(64 + 8 * ngroups))) return rc;
+    BHIPCHK(wait_stream(batch->stream));
+    BHIPCHK(hipGetLastError());
+    return PCABO_OK;
+  };
   int rc = run_rounds(runs.data(), act, stage, eval);
   for (int b : act) if (runs[b].status == PCABO_ERR_NAN) set_err(batch->ctx[b], PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
   if (rc != PCABO_OK) return rc;
@@ -2451,30 +2447,15 @@ extern "C" int pcabo_debug_batch_lbfgsb_device_out(pcabo_batch* batch, double* o
   return batch->dbg_groups;
 }
 
-int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_restarts, int batch_limit,
-                              const double* bounds, int maxiter, const double* best_f, int maximize, int acq,
-                              double* cand, double* vals, int* info, int* failed, int* status) {
-  if (!batch) return PCABO_ERR_ARG;
-  if (!ics || !bounds || !best_f || !cand || !vals || num_restarts < 1 || batch_limit < 1 || num_restarts > PCABO_INLAUNCH_MAXQ)
-    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: bad argument (num_restarts <= 32)%s", "");
-  if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: %s", why);
-  if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: no conditioned GP%s", "");
-  BHIPCHK(hipSetDevice(batch->device));
+// The host-paced optimiser: the batch's worker threads drive the runs' L-BFGS-B, one acquisition launch per gang and round.
+static int batch_optimize_host(pcabo_batch* batch, const double* ics, int num_restarts, int batch_limit, const double* bounds,
+                               int maxiter, int maximize, int acq, double* cand, double* vals, int* info, int* failed, int* status) {
   const int B = batch->B, MD = batch->max_d, kmax = batch_max_k(batch), G = batch->G;
   const int ngroups = (num_restarts + batch_limit - 1) / batch_limit;
-  int rc = batch_put_best_f(batch, best_f);
-  if (rc != PCABO_OK) return rc;
-  batch->dbg_branches.clear(); batch->dbg_group_out.clear();      // (a call that takes the host-paced path leaves no debug record)
-  if (batch->dev_lbfgsb) {
-    const int drc = batch_optimize_device(batch, ics, num_restarts, batch_limit, bounds, maxiter, maximize, acq, cand, vals, info,
-                                          failed, status);
-    if (drc != 1) return drc;                       // 1: not eligible (size, bounds) - the host-paced path below
-  }
   BHIPCHK(hipStreamSynchronize(batch->stream));
   pcabo_ctx* c0 = batch->ctx[0];
-  AcqParams pg = make_params(c0, 0.0, maximize, acq, 1);
-  pg.inv_ls = 1.0 / batch->lengthscale; pg.kernel = batch->kernel;
-  AcqParams pv = pg; pv.want_grad = 0;
+  const GpModel gm = gp_model(batch, kmax);
+  const AcqParams pg = batch_params(batch, maximize, acq, 1), pv = batch_params(batch, maximize, acq, 0);
   std::vector<RunRestarts> runs(B);
   for (int b = 0; b < B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
@@ -2504,13 +2485,11 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
       const int n = nent;
       nent = 0;
       if (groups) {
-        if (launch_acq_group(st, &tab, n, c0->hXq, batch->n, kmax, batch->NP, c0->ld, c0->dZnT, c0->dR, c0->dAlpha,
-                             c0->dBounds4, c0->dYstats, p, c0->dPartial, c0->dCounters + PCABO_GROUP_CNT_OFFSET, c0->dVal,
-                             c0->dGrad, c0->hVal, c0->hGrad, c0->hm, seq, batch_ab(batch, 1, 1)) != 0)
+        if (launch_acq_group(st, &tab, n, c0->hXq, gm, p, c0->dPartial, c0->dCounters + PCABO_GROUP_CNT_OFFSET, c0->dVal, c0->dGrad,
+                             c0->hVal, c0->hGrad, c0->hm, seq, batch_ab(batch, 1, 1)) != 0)
           return false;                              // nothing was launched: no flags to wait for
       } else {
-        launch_acq(st, &tab, c0->hXq, PCABO_INLAUNCH_MAXQ, batch->n, kmax, batch->NP, c0->ld, c0->dZnT, c0->dR,
-                   c0->dAlpha, c0->dBounds4, c0->dYstats, p, c0->dPartial, c0->dCounters, c0->dVal, c0->dGrad, c0->hVal,
+        launch_acq(st, &tab, c0->hXq, PCABO_INLAUNCH_MAXQ, gm, p, c0->dPartial, c0->dCounters, c0->dVal, c0->dGrad, c0->hVal,
                    c0->hGrad, c0->hm, seq, nullptr, nullptr, batch_ab(batch, 1, 1), B, n);
       }
       if (hipGetLastError() != hipSuccess) return false;
@@ -2560,6 +2539,29 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
   return PCABO_OK;
 }
 
+int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_restarts, int batch_limit,
+                              const double* bounds, int maxiter, const double* best_f, int maximize, int acq,
+                              double* cand, double* vals, int* info, int* failed, int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (!ics || !bounds || !best_f || !cand || !vals || num_restarts < 1 || batch_limit < 1 || num_restarts > PCABO_INLAUNCH_MAXQ)
+    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: bad argument (num_restarts <= 32)%s", "");
+  if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: %s", why);
+  if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: no conditioned GP%s", "");
+  // (the pinned point / value buffers and the runs' best_f words belong to an enqueued call until its _end)
+  if (batch->opt_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: an optimisation of this batch is already enqueued%s", "");
+  BHIPCHK(hipSetDevice(batch->device));
+  if (const int rc = batch_put_best_f(batch, best_f)) return rc;
+  batch->dbg_branches.clear(); batch->dbg_group_out.clear();      // (a call that takes the host-paced path leaves no debug record)
+  std::vector<int> act;
+  if (batch->dev_lbfgsb && device_opt_eligible(batch, num_restarts, batch_limit, bounds, maxiter, &act)) {
+    if (batch->dev_lbfgsb == 2)
+      return batch_optimize_twin(batch, act, ics, num_restarts, batch_limit, bounds, maxiter, maximize, acq, cand, vals, info, failed, status);
+    const int rc = device_opt_enqueue(batch, act, ics, num_restarts, batch_limit, bounds, maxiter, maximize, acq);
+    return rc != PCABO_OK ? rc : device_opt_collect(batch, num_restarts, batch_limit, cand, vals, info, failed, status);
+  }
+  return batch_optimize_host(batch, ics, num_restarts, batch_limit, bounds, maxiter, maximize, acq, cand, vals, info, failed, status);
+}
+
 // pcabo_batch_optimize_acqf in two halves for callers that drive several batches from one thread (PCABO_OPT_DEVICE_LBFGSB = 1
 // only: the whole optimisation is one launch, so _begin returns as soon as it is enqueued).  _begin returns PCABO_OK, an error,
 // or 1 when the call does not qualify for the device-resident optimiser - the caller then uses pcabo_batch_optimize_acqf.
@@ -2570,19 +2572,19 @@ int pcabo_batch_optimize_acqf_begin(pcabo_batch* batch, const double* ics, int n
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: bad argument (num_restarts <= 32)%s", "");
   if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: %s", why);
   if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: no conditioned GP%s", "");
+  if (batch->opt_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: an optimisation of this batch is already enqueued%s", "");
   if (batch->dev_lbfgsb != 1) return 1;
   BHIPCHK(hipSetDevice(batch->device));
-  const int rc = batch_put_best_f(batch, best_f);
-  if (rc != PCABO_OK) return rc;
-  return batch_optimize_device(batch, ics, num_restarts, batch_limit, bounds, maxiter, maximize, acq, nullptr, nullptr, nullptr,
-                               nullptr, nullptr, 1);
+  if (const int rc = batch_put_best_f(batch, best_f)) return rc;
+  std::vector<int> act;
+  if (!device_opt_eligible(batch, num_restarts, batch_limit, bounds, maxiter, &act)) return 1;
+  return device_opt_enqueue(batch, act, ics, num_restarts, batch_limit, bounds, maxiter, maximize, acq);
 }
 int pcabo_batch_optimize_acqf_end(pcabo_batch* batch, int num_restarts, int batch_limit, double* cand, double* vals, int* info,
                                   int* failed, int* status) {
   if (!batch || !cand || !vals) return PCABO_ERR_ARG;
   BHIPCHK(hipSetDevice(batch->device));
-  return batch_optimize_device(batch, nullptr, num_restarts, batch_limit, nullptr, 1, 0, PCABO_ACQ_LOG_EI, cand, vals, info, failed,
-                               status, 2);
+  return device_opt_collect(batch, num_restarts, batch_limit, cand, vals, info, failed, status);
 }
 
 // Value and gradient of the acquisition at q <= 32 points per run through the evaluation of the device-resident optimiser
@@ -2600,68 +2602,64 @@ int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, con
   if (batch->opt_enqueued || batch->score_enqueued || batch->imap_enqueued)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: a _begin call of this batch has not been ended%s", "");
   BHIPCHK(hipSetDevice(batch->device));
-  const int B = batch->B, MD = batch->max_d, kmax = batch_max_k(batch);
-  if (!lbfgsb_device_possible(batch->NP, kmax, PCABO_GROUP_Q) || batch->max_q < 64)
+  const int MD = batch->max_d;
+  if (!lbfgsb_device_possible(batch->NP, batch_max_k(batch), PCABO_GROUP_Q) || batch->max_q < 64)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: shape beyond the device optimiser (n <= 512, k <= 40)%s", "");
-  int rc = batch_put_best_f(batch, best_f);
-  if (rc != PCABO_OK) return rc;
-  pcabo_ctx* c0 = batch->ctx[0];
-  hipStream_t s = batch->stream;
+  if (const int rc = batch_put_best_f(batch, best_f)) return rc;
+  std::vector<int> runs;
+  for (int b = 0; b < batch->B; ++b) if (batch->ctx[b]->have_gp) runs.push_back(b);
   int nent = 0;
-  for (int b = 0; b < B; ++b) {
+  for (int b : runs) {
     pcabo_ctx* c = batch->ctx[b];
-    if (!c->have_gp) continue;
-    if (c->rt_stale) { launch_rt_build(s, c->dR, c->n, c->NP, c->ld, c->dGram); c->rt_stale = false; }
     memcpy(c->hXq, Xq + (size_t)b * q * MD, (size_t)q * c->k * sizeof(double));
     for (int q0 = 0; q0 < q; q0 += PCABO_GROUP_Q)
       batch->hOptTab[nent++] = group_entry(b, q0, std::min(PCABO_GROUP_Q, q - q0));
   }
   if (nent == 0) return PCABO_OK;
-  BHIPCHK(hipMemcpyAsync(batch->dOptTab, batch->hOptTab, (size_t)nent * sizeof(unsigned), hipMemcpyHostToDevice, s));
-  BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, c0->hXq, batch->hzs, (size_t)(q + 2) * kmax * sizeof(double), B, hipMemcpyHostToDevice, s));
-  if (launch_lbfgsb_group(s, batch->dOptTab, nent, 0, q, 1, batch->n, batch->NP, c0->ld, c0->dXq, c0->dZnT, c0->dR, c0->dGram,
-                          c0->dAlpha, c0->dBounds4, c0->dYstats, c0->dBestF, c0->dK, 1.0 / batch->lengthscale, maximize ? 1 : 0, acq,
-                          batch->kernel, c0->dGrad, c0->dVal, batch->zs, batch_hyp(batch)) != 0)
-    return bset_err(batch, PCABO_ERR_HIP, "the device-resident optimiser could not be launched%s", "");
-  BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (size_t)q * sizeof(double), B, hipMemcpyDeviceToHost, s));
-  BHIPCHK(hipMemcpy2DAsync(c0->hGrad, batch->hzs, c0->dGrad, batch->zs, (size_t)q * kmax * sizeof(double), B, hipMemcpyDeviceToHost, s));
-  BHIPCHK(wait_stream(s));
+  if (const int rc = device_opt_launch(batch, nent, 0, q, PCABO_GROUP_Q, 1, maximize, acq, (size_t)q)) return rc;
+  BHIPCHK(wait_stream(batch->stream));
   BHIPCHK(hipGetLastError());
-  for (int b = 0; b < B; ++b) {
+  for (int b : runs) {
     const pcabo_ctx* c = batch->ctx[b];
-    if (!c->have_gp) continue;
     memcpy(val + (size_t)b * q, c->hVal, (size_t)q * sizeof(double));
     memcpy(grad + (size_t)b * q * MD, c->hGrad, (size_t)q * c->k * sizeof(double));
   }
   return PCABO_OK;
 }
 
-static int batch_inverse_map_impl(pcabo_batch* batch, const double* z, double* x, int phase /* 0 whole call, 1 enqueue, 2 wait + collect */) {
-  if (!batch || (!z && phase != 2) || (!x && phase != 1)) return PCABO_ERR_ARG;
+// the inverse map of every run's candidate in two halves (x_ok: the caller's x is there - asked before anything is written)
+static int batch_inverse_map_enqueue(pcabo_batch* batch, const double* z, bool x_ok = true) {
+  if (!batch || !z || !x_ok) return PCABO_ERR_ARG;
   if (batch->n == 0 || batch->wpca_uncollected) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_inverse_map: no weighted PCA collected%s", "");
-  if (phase == 2 && !batch->imap_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_inverse_map_end: no _begin before it%s", "");
   BHIPCHK(hipSetDevice(batch->device));
   hipStream_t s = batch->stream;
   pcabo_ctx* c0 = batch->ctx[0];
   const int B = batch->B, MD = batch->max_d, d = batch->d;
-  if (phase != 2) {
-    for (int b = 0; b < B; ++b) memcpy(batch->ctx[b]->hXq, z + (size_t)b * MD, (size_t)batch->ctx[b]->k * sizeof(double));
-    BHIPCHK(hipMemcpy2DAsync(c0->dZq, batch->zs, c0->hXq, batch->hzs, (size_t)MD * sizeof(double), B, hipMemcpyHostToDevice, s));
-    launch_inverse_map(s, c0->dZq, c0->dComps, c0->dDataMean, c0->dPcaMean, 0, d, c0->dXout, c0->dK, batch_zb(batch));
-    BHIPCHK(hipMemcpy2DAsync(c0->hSmall, batch->hzs, c0->dXout, batch->zs, (size_t)d * sizeof(double), B, hipMemcpyDeviceToHost, s));
-    BHIPCHK(hipGetLastError());
-    batch->imap_enqueued = true;
-  }
-  if (phase == 1) return PCABO_OK;
-  batch->imap_enqueued = false;
-  BHIPCHK(wait_stream(s));
+  for (int b = 0; b < B; ++b) memcpy(batch->ctx[b]->hXq, z + (size_t)b * MD, (size_t)batch->ctx[b]->k * sizeof(double));
+  BHIPCHK(hipMemcpy2DAsync(c0->dZq, batch->zs, c0->hXq, batch->hzs, (size_t)MD * sizeof(double), B, hipMemcpyHostToDevice, s));
+  launch_inverse_map(s, c0->dZq, c0->dComps, c0->dDataMean, c0->dPcaMean, 0, d, c0->dXout, c0->dK, batch_zb(batch));
+  BHIPCHK(hipMemcpy2DAsync(c0->hSmall, batch->hzs, c0->dXout, batch->zs, (size_t)d * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipGetLastError());
-  for (int b = 0; b < B; ++b) memcpy(x + (size_t)b * d, batch->ctx[b]->hSmall, (size_t)d * sizeof(double));
+  batch->imap_enqueued = true;
   return PCABO_OK;
 }
-int pcabo_batch_inverse_map(pcabo_batch* batch, const double* z, double* x) { return batch_inverse_map_impl(batch, z, x, 0); }
-int pcabo_batch_inverse_map_begin(pcabo_batch* batch, const double* z) { return batch_inverse_map_impl(batch, z, nullptr, 1); }
-int pcabo_batch_inverse_map_end(pcabo_batch* batch, double* x) { return batch_inverse_map_impl(batch, nullptr, x, 2); }
+static int batch_inverse_map_collect(pcabo_batch* batch, double* x) {
+  if (!batch || !x) return PCABO_ERR_ARG;
+  if (!batch->imap_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_inverse_map_end: no _begin before it%s", "");
+  BHIPCHK(hipSetDevice(batch->device));
+  batch->imap_enqueued = false;
+  BHIPCHK(wait_stream(batch->stream));
+  BHIPCHK(hipGetLastError());
+  const int d = batch->d;
+  for (int b = 0; b < batch->B; ++b) memcpy(x + (size_t)b * d, batch->ctx[b]->hSmall, (size_t)d * sizeof(double));
+  return PCABO_OK;
+}
+int pcabo_batch_inverse_map(pcabo_batch* batch, const double* z, double* x) {
+  const int rc = batch_inverse_map_enqueue(batch, z, x != nullptr);
+  return rc != PCABO_OK ? rc : batch_inverse_map_collect(batch, x);
+}
+int pcabo_batch_inverse_map_begin(pcabo_batch* batch, const double* z) { return batch_inverse_map_enqueue(batch, z); }
+int pcabo_batch_inverse_map_end(pcabo_batch* batch, double* x) { return batch_inverse_map_collect(batch, x); }
 
 }  // extern "C"
 

@@ -61,6 +61,10 @@ struct AcqParams {
   int want_grad;
 };
 
+// The conditioned model as the acquisition launchers read it: the sizes and the device operands of a context, or of run 0 of a
+// batch with the batch's n / NP and the largest k of its runs (gp_model in pcabo_api.hip builds both).
+struct GpModel { int n, k, NP, ld; const double *ZnT, *R, *alpha, *bounds4, *ystats; };
+
 // Batched acquisition launches (all zero / null for a single context).  Runs are addressed as in zrun(); per run the
 // reduced dimension and best_f come from device memory (they differ between the runs of a batch).
 struct AcqBatch {
@@ -329,10 +333,9 @@ void launch_mll_grad(hipStream_t s, const double* R, const double* AT, const dou
 // tile, out[5 + KP] = {the first five sums above, S_c = sum_ij W_ij dK_ij/dlog l_c for c < KP}
 void launch_mll_grad_ard(hipStream_t s, const double* R, const double* AT, const double* nrm, const double* alpha, const double* L,
                          const double* ys, int n, int NP, int KP, int ld, double* partial, double* out);
-void launch_acq(hipStream_t s, const QueryArgs* qa, const double* Xq, int q, int n, int k, int NP, int ld,
-                const double* ZnT, const double* R, const double* alpha, const double* bounds4, const double* ystats,
-                AcqParams p, double* partial, unsigned int* counters, double* val,
-                double* grad, double* host_val, double* host_grad, HostMirror* hm, unsigned long long seq,
+void launch_acq(hipStream_t s, const QueryArgs* qa, const double* Xq, int q, const GpModel& m, AcqParams p, double* partial,
+                unsigned int* counters, double* val, double* grad, double* host_val, double* host_grad, HostMirror* hm,
+                unsigned long long seq,
                 MailPair* dev_mail = nullptr, MailPair* part_pairs = nullptr,
                 AcqBatch ab = AcqBatch(), int B = 1, int table_entries = 0);
 // throughput variant: one work-group per (restart group of <= 5 queries, 64-row slab); `tab` holds `entries` 32-bit words
@@ -340,20 +343,17 @@ void launch_acq(hipStream_t s, const QueryArgs* qa, const double* Xq, int q, int
 #define PCABO_GROUP_Q 5
 #define PCABO_GROUP_CNT_OFFSET 8192      // its tickets live in the upper half of the counter array (other slab count)
 bool acq_group_possible(int NP, int k);
-int launch_acq_group(hipStream_t st, const QueryArgs* tab, int entries, const double* Xq, int n, int k, int NP, int ld,
-                     const double* ZnT, const double* R, const double* alpha, const double* bounds4, const double* ystats,
-                     AcqParams p, double* partial, unsigned int* counters, double* val, double* grad, double* host_val,
-                     double* host_grad, HostMirror* hm, unsigned long long seq, AcqBatch ab);   // 0, or -1: nothing launched
+int launch_acq_group(hipStream_t st, const QueryArgs* tab, int entries, const double* Xq, const GpModel& m, AcqParams p,
+                     double* partial, unsigned int* counters, double* val, double* grad, double* host_val, double* host_grad,
+                     HostMirror* hm, unsigned long long seq, AcqBatch ab);   // 0, or -1: nothing launched
 // value-only scoring of a large batch as a GEMM (KS, then V = R KS^T on MFMA, then the scalar chain); KS: q x ld scratch
 bool score_gemm_possible(int q);
-void launch_score(hipStream_t st, const double* Xq, int q, int n, int k, int NP, int ld, const double* ZnT, const double* R,
-                  const double* alpha, const double* bounds4, const double* ystats, AcqParams p, double* KS, double* partial,
-                  double* val, AcqBatch ab = AcqBatch(), int B = 1);
+void launch_score(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS, double* partial, double* val,
+                  AcqBatch ab = AcqBatch(), int B = 1);
 // launch_score's first kernel without its mu_s sums (no alpha), and the rest of launch_score behind it: together launch_score's bits
-void launch_score_ks_only(hipStream_t st, const double* Xq, int q, int n, int k, int NP, int ld, const double* ZnT,
-                          const double* bounds4, AcqParams p, double* KS);
-void launch_score_tail(hipStream_t st, int q, int n, int k, int NP, int ld, const double* R, const double* alpha,
-                       const double* bounds4, const double* ystats, AcqParams p, const double* KS, double* partial, double* val);
+// (launch_score_ks_only reads the model's ZnT and bounds4 only: alpha and R may still be in the making)
+void launch_score_ks_only(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS);
+void launch_score_tail(hipStream_t st, int q, const GpModel& m, AcqParams p, const double* KS, double* partial, double* val);
 // resident mode available for this shape? (fast path + every group of the grid co-resident)
 bool acq_server_possible(int q, int n, int k, int NP);
 int acq_slabs(int NP);
@@ -367,9 +367,9 @@ void launch_inverse_map(hipStream_t s, const double* z, const double* comps, con
 // mode 0: one value+gradient evaluation at the points in Xq.  Returns 0, or -1 when the launch could not be set up.
 void launch_rt_build(hipStream_t s, const double* R, int n, int NP, int ld, double* RT, ZB zb = ZB());
 bool lbfgsb_device_possible(int NP, int kmax, int batch_limit);
-int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int mode, int num_restarts, int maxiter, int n, int NP,
-                        int ld, const double* Xq, const double* ZnT, const double* R, const double* RT, const double* alpha,
-                        const double* bounds4, const double* ystats, const double* bestf, const int* k_dev, double inv_ls,
+// (m.k is not read: every run's k comes from k_dev)
+int launch_lbfgsb_group(hipStream_t st, const unsigned* table, int entries, int mode, int num_restarts, int maxiter, const GpModel& m,
+                        const double* Xq, const double* RT, const double* bestf, const int* k_dev, double inv_ls,
                         int maximize, int acq, int kernel, double* out_x, double* out_v, size_t zs,
                         const double* hyp = nullptr,    // hyp: per-run hyperparameter blocks (stride zs), 1 / lengthscale read from them
                         int batch_limit = PCABO_GROUP_Q);   // mode 1: restarts per group of the call (group gi starts at gi batch_limit)

@@ -17,7 +17,7 @@ ABI_VERSION = 2
 KERNEL_MATERN52, KERNEL_RBF = 0, 1
 ACQ_LOG_EI, ACQ_PI, ACQ_UCB = 0, 1, 2
 PTR_HOST, PTR_DEVICE = 0, 1
-OPT_RESIDENT, OPT_BESTF_F32, OPT_GROUP_ACQ, OPT_DEVICE_LBFGSB, OPT_LBFGSB_CUS = 0, 1, 2, 3, 4
+OPT_RESIDENT, OPT_BESTF_F32, OPT_GROUP_ACQ, OPT_DEVICE_LBFGSB = 0, 1, 2, 3
 OPT_HIDDEN_TAIL = 5
 FIT_THETA0 = (0.006737946999085467, 0.0, 0.0)   # GP fit: (noise, mean constant, raw lengthscale) of a freshly built model
 FIT_TASK_NOT_PD = -2                            # gp_fit's `task` when a trial theta could not be factored even with jitter
@@ -515,7 +515,7 @@ class Batch:
     rows A-H of all runs, one scoring launch, shared acquisition launches for the L-BFGS-B rounds of all runs."""
 
     def __init__(self, B: int, max_n: int, max_d: int, max_q: int = 512, device: int = 0, workers: int = 0,
-                 group_acq: bool = True, device_lbfgsb: int = 0, lbfgsb_cus: int = 0):
+                 group_acq: bool = True, device_lbfgsb: int = 0):
         self._h = C.c_void_p()
         rc = LIB.pcabo_batch_create(int(device), int(B), int(max_n), int(max_d), int(max_q), C.byref(self._h))
         if rc != 0:
@@ -535,8 +535,6 @@ class Batch:
         if device_lbfgsb:            # 1: every restart group's L-BFGS-B inside one launch; 2: its host-stepped twin (tests)
             self._chk(LIB.pcabo_batch_set_option(self._h, OPT_DEVICE_LBFGSB, int(device_lbfgsb)))
         self.device_lbfgsb = int(device_lbfgsb)
-        if lbfgsb_cus:               # the optimiser's launches confined to that many CUs (several batches of one process in flight)
-            self._chk(LIB.pcabo_batch_set_option(self._h, OPT_LBFGSB_CUS, int(lbfgsb_cus)))
         advice = hw_queues_advice(min(B, int(workers) if workers else 8) + 2)      # gang streams + the batch's + the default stream
         if advice:
             import warnings

@@ -59,7 +59,7 @@ class BatchedPCABO:
                  var_threshold: float = 0.95, acquisition_function: str = "expected_improvement",
                  maximization: bool = False, device: int = 0, num_restarts: int = 10, raw_samples: int = 512,
                  record_trace: bool = False, host_threads: int = 0, device_objective: bool = False, workers: int = 0,
-                 trace_filter=None, acq_kernel: str = "group", lbfgsb_cus: int = 0, torch_threads: Optional[int] = 4,
+                 trace_filter=None, acq_kernel: str = "group", torch_threads: Optional[int] = 4,
                  gc_freeze: bool = True, fit_gp: bool = False, ucb_beta: Optional[float] = None, ard: bool = False):
         if ard:                            # (the lock-step fit has one lengthscale per run: DESIGN.md "ARD lengthscales", scope)
             raise ValueError("ard=True is a mode of the single-run classes Algorithms.PCA_BO / Vanilla_BO (fit_gp=True, ard=True): "
@@ -154,7 +154,6 @@ class BatchedPCABO:
                              "(n <= %d, k <= %d); use 'group'" % ((acq_kernel, self.dimension, self.budget) + _native.device_lbfgsb_limits()[:2]))
         self._group_acq = acq_kernel != "latency"
         self._device_lbfgsb = {"device": 1, "device-twin": 2}.get(acq_kernel, 0)
-        self._lbfgsb_cus = int(lbfgsb_cus)         # "device": the optimiser's launches confined to that many CUs (0: the whole chip)
 
     def _acq_scalars(self) -> list:
         """What every run hands the device in the `best_f` slot this iteration: its incumbent, or kappa for UCB."""
@@ -191,8 +190,7 @@ class BatchedPCABO:
             self._X[b, : self.n_DoE] = np.vstack(self.x_evals[b])
             self._F[b, : self.n_DoE] = self.f_evals[b]
         self._batch = _native.Batch(B, max_n=self.budget, max_d=d, max_q=max(self.raw_samples, 16), device=self.device,
-                                    workers=self._workers, group_acq=self._group_acq, device_lbfgsb=self._device_lbfgsb,
-                                    lbfgsb_cus=self._lbfgsb_cus)
+                                    workers=self._workers, group_acq=self._group_acq, device_lbfgsb=self._device_lbfgsb)
         if self._device_objective:
             from .bbob_device import DeviceObjectives
             self._dev_obj = DeviceObjectives(self.problems, device=self.device, penalty=OOB_PENALTY)
@@ -649,7 +647,7 @@ def run_interleaved(runners: Sequence["BatchedPCABO"], started: bool = False) ->
 
 def bench_block(device: int, B: int, fid: int, dim: int, budget_factor: int = 10, doe_factor: float = 3.0,
                 sub_batches: int = 1, workers: int = 0, acq_kernel: str = "group", schedule: str = "threads",
-                lbfgsb_cus: int = 0, device_objective: bool = False, algorithm: str = "pca", fit_gp: bool = False) -> dict:
+                device_objective: bool = False, algorithm: str = "pca", fit_gp: bool = False) -> dict:
     """Aggregate BO iterations / second of B runs (instances 0..B-1 of one BBOB function and dimension, seeds per
     ExperimentRunner.py:146) advancing together on one GPU - as one lock-step batch, or as `sub_batches` lock-step batches
     side by side (run_side_by_side); DoE and set-up untimed."""
@@ -662,7 +660,7 @@ def bench_block(device: int, B: int, fid: int, dim: int, budget_factor: int = 10
         subs.append((BatchedVanillaBO if algorithm == "vanilla" else BatchedPCABO)(
             [BBOBProblem(fid, i, dim) for i in inst], [1000 * fid + 10 * dim + i for i in inst], budget, n_doe,
                                  device=device, workers=workers or (workers_for(S) if S > 1 else 0), host_threads=max(1, 8 // S),
-                                 acq_kernel=acq_kernel, lbfgsb_cus=lbfgsb_cus, device_objective=device_objective,
+                                 acq_kernel=acq_kernel, device_objective=device_objective,
                                  fit_gp=fit_gp))
     for r in subs:
         r.start()

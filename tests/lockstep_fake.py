@@ -100,7 +100,7 @@ class FakeBatch:
     script = {}                     # set by run_case before the runner builds its batch
     created = []                    # every instance, in order (a runner drops its batch in finish())
 
-    def __init__(self, B, max_n, max_d, max_q=512, device=0, workers=0, group_acq=True, device_lbfgsb=0, lbfgsb_cus=0):
+    def __init__(self, B, max_n, max_d, max_q=512, device=0, workers=0, group_acq=True, device_lbfgsb=0):
         self.B, self.max_n, self.max_d, self.max_q, self.device = B, max_n, max_d, max_q, device
         self.device_lbfgsb = int(device_lbfgsb)
         self.n = self.d = 0
@@ -110,7 +110,8 @@ class FakeBatch:
         self.ctx = [_FakeContext(self, b) for b in range(B)]
         self.log, self.fired, self.script = [], [], dict(type(self).script)
         self._last_k, self._vanilla, self._raw_buf = None, False, None
-        self._log("Batch", B, max_n, max_d, max_q, device, workers, int(bool(group_acq)), self.device_lbfgsb, lbfgsb_cus)
+        # (the trailing 0 stood for an option of Batch that has been removed; the recorded digests of the logs include it)
+        self._log("Batch", B, max_n, max_d, max_q, device, workers, int(bool(group_acq)), self.device_lbfgsb, 0)
         type(self).created.append(self)
 
     def _log(self, name, *args):

@@ -280,7 +280,9 @@ def test_rccl_gather_best_through_the_c_abi(native):
 def test_strided_inputs_and_call_halves(native):
     """pcabo_batch_set_input_strides: X / y handed over as the first n rows of [B][budget][d] / [B][budget] arrays give the state
     the dense arrays give, bit for bit; the begin / end halves of the waiting calls give what the blocking calls give, and an _end
-    without its _begin is refused (PCABO_ERR_ARG) instead of waiting for nothing."""
+    without its _begin is refused (PCABO_ERR_ARG) instead of waiting for nothing.  A call that would reuse the buffers of a pending
+    _begin (a second _begin with other points and another best_f, device_acq_eval) is refused before it writes anything: the pending
+    call still ends with the blocking call's bits.  Option 4 (once the optimiser's CU mask) is unknown to pcabo_batch_set_option."""
     rng = np.random.default_rng(8)
     B, n, budget, d, q = 3, 90, 140, 9, 512
     Xfull = rng.uniform(-5, 5, (B, budget, d))
@@ -290,6 +292,8 @@ def test_strided_inputs_and_call_halves(native):
     outs = []
     for strided in (False, True):
         bt = native.Batch(B, max_n=budget, max_d=d, max_q=q, device_lbfgsb=1)
+        with pytest.raises(native.PcaboError):
+            bt._chk(native.LIB.pcabo_batch_set_option(bt._h, 4, 64))
         X = Xfull[:, :n] if strided else np.ascontiguousarray(Xfull[:, :n])
         y = yfull[:, :n] if strided else np.ascontiguousarray(yfull[:, :n])
         bt.wpca_gp_condition_begin(X, ranks, noise, y)
@@ -301,6 +305,10 @@ def test_strided_inputs_and_call_halves(native):
             with pytest.raises(native.PcaboError):
                 bt.gp_eval_end((np.zeros((B, q * d)), q, np.zeros(B), 0, native.ACQ_LOG_EI))
             tok = bt.gp_eval_begin(raw, best)
+            bt._raw_buf = None            # (the refused call packs its points into a buffer of its own, not into the token's)
+            other, worse = [raw[b][::-1] for b in range(B)], [v - 7.0 for v in best]
+            with pytest.raises(native.PcaboError):
+                bt.gp_eval_begin(other, worse)
             while bt.busy():
                 pass
             vals, status = bt.gp_eval_end(tok)
@@ -308,6 +316,10 @@ def test_strided_inputs_and_call_halves(native):
                 bt.optimize_end((10, 5))
             tok = bt.optimize_begin([raw[b][:10] for b in range(B)], boxes, best)
             assert tok is not None
+            with pytest.raises(native.PcaboError):
+                bt.optimize_begin([other[b][:10] for b in range(B)], boxes, worse)
+            with pytest.raises(native.PcaboError):
+                bt.device_acq_eval([other[b][:10] for b in range(B)], worse)
             o, st = bt.optimize_end(tok)
             z = [o[b][0][int(np.argmax(o[b][1]))] for b in range(B)]
             with pytest.raises(native.PcaboError):
