@@ -201,10 +201,8 @@ __global__ __launch_bounds__(256) void k_cov(const double* __restrict__ Wc, int 
 // Plane rotations are applied to column pairs until all columns are mutually orthogonal; then
 // G = C V = V diag(lambda): column norms are the eigenvalues and the normalised columns the
 // eigenvectors.  Round-robin ordering gives d/2 independent pairs per round, each handled by a
-// group of LP lanes (shuffle reductions, no LDS traffic for the dot products).
+// group of 16 lanes (one DPP row: row sums inside the VALU, no LDS traffic for the dot products).
 #define JAC_THREADS 1024
-__device__ inline double rcp_1nr(double x) { double r = __builtin_amdgcn_rcp(x); return fma(fma(-x, r, 1.0), r, r); }
-__device__ inline double rsq_1nr(double x) { double y = __builtin_amdgcn_rsq(x); return y * fma(-0.5 * x * y, y, 1.5); }
 #ifdef PCABO_ACQ_TIMING
 __device__ unsigned long long g_jac_stamps[8];
 extern "C" int pcabo_debug_jacobi_stamps(unsigned long long* out4) {
@@ -217,8 +215,59 @@ extern "C" int pcabo_debug_jacobi_stamps(unsigned long long* out4) {
 struct PcaSelect {        // arguments of the selection step that ends the kernel (rows C, PCA_BO.py:389-399)
   int n; double var_threshold; int n_components; double* comps; double* evr; int* k_dev; HostMirror* hm;
 };
-// NT: rows of a column pair that a lane keeps in registers between the dot products and the rotation (16 lanes per pair: NT = 4 covers
-// d <= 64, NT = 8 the whole range d <= 128 - configs[4]'s d = 100 used to take the second loop, two LDS reads per element and round)
+// ---- the arithmetic of one round, spelled out ------------------------------------------------------------------------
+// The results of this kernel are pinned bit for bit (tests/golden/wpca_bits_hashes.json): a run's trajectory is chaotic, a
+// last-bit change of an eigenvector moves later candidates at order one.  So every fused multiply-add of the round is written
+// down, in the order the kernel has always had, and the compiler may not contract (or un-contract) anything in these functions.
+// One partial chain of the dot products over a lane's rows x[0 .. NT), y[0 .. NT) (row t of the chain = row lane + 16 t of
+// the columns): a = x1 x1, then fma(x0, x0, a), then ascending from row 2; g starts from fma(x0, y0, +0.0).
+template <int NT>
+__device__ inline void jac_chain(const double* x, const double* y, double& a, double& b, double& g) {
+#pragma clang fp contract(off)
+  a = NT > 1 ? x[NT > 1 ? 1 : 0] * x[NT > 1 ? 1 : 0] : 0.0;
+  b = NT > 1 ? y[NT > 1 ? 1 : 0] * y[NT > 1 ? 1 : 0] : 0.0;
+  a = __builtin_fma(x[0], x[0], a);
+  b = __builtin_fma(y[0], y[0], b);
+  g = __builtin_fma(x[0], y[0], 0.0);
+  if (NT > 1) g = __builtin_fma(x[NT > 1 ? 1 : 0], y[NT > 1 ? 1 : 0], g);
+#pragma unroll
+  for (int t = 2; t < NT; ++t) {
+    a = __builtin_fma(x[t], x[t], a);
+    b = __builtin_fma(y[t], y[t], b);
+    g = __builtin_fma(x[t], y[t], g);
+  }
+}
+// rotation from hardware rcp/rsq estimates + Newton steps (c^2 + s^2 = 1 to ~1 ulp is what matters; the ANGLE only needs
+// ~1e-12: an error there is removed by the next rotation of the pair - one Newton step on the estimates, cs keeps two)
+__device__ inline void jac_rotation(double a, double b, double g, double& cs, double& sn) {
+#pragma clang fp contract(off)
+  double r = __builtin_amdgcn_rcp(g);
+  r = __builtin_fma(__builtin_fma(-g, r, 1.0), r, r);
+  const double zeta = ((b - a) * 0.5) * r;
+  const double hyp = __builtin_fma(zeta, zeta, 1.0);
+  double y = __builtin_amdgcn_rsq(hyp);
+  y = y * __builtin_fma((-0.5 * hyp) * y, y, 1.5);
+  const double den = __builtin_fma(hyp, y, fabs(zeta));
+  double q = __builtin_amdgcn_rcp(den);
+  q = __builtin_fma(__builtin_fma(-den, q, 1.0), q, q);
+  const double t = zeta >= 0.0 ? q : -q;
+  const double w = __builtin_fma(t, t, 1.0), hw = -0.5 * w;
+  double c = __builtin_amdgcn_rsq(w);
+  c = c * __builtin_fma(hw * c, c, 1.5);
+  c = c * __builtin_fma(hw * c, c, 1.5);
+  cs = c;
+  sn = c * t;
+}
+__device__ inline void jac_apply(double cs, double sn, double x, double y, double& xo, double& yo) {
+#pragma clang fp contract(off)
+  xo = __builtin_fma(cs, x, -(sn * y));
+  yo = __builtin_fma(sn, x, cs * y);
+}
+// NT: 16-row tiles of a column (d <= 16 NT; the columns are padded with zero rows to 16 NT, which add +0.0 to every sum and
+// rotate to +0.0, so no load or store of the round is predicated).  A pair is one DPP row of 16 lanes, lane l keeps rows
+// l + 16 t.  (Eight lanes per pair - half the waves, two chains per lane, the same 16-leaf tree and the same bits - was built
+// and measured slower at every d: a round is a dependent chain through ONE wave's instruction stream, and the longer stream
+// of the 8-lane wave costs more than a second wave on a SIMD does.  EXPERIMENTS.md section 20.)
 template <int NT>
 __global__ __launch_bounds__(JAC_THREADS) void k_jacobi(const double* __restrict__ C, int d, int DP,
                                                         const double* __restrict__ V0, double* __restrict__ Gout,
@@ -226,18 +275,20 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi(const double* __restrict
                                                         PcaSelect sel, size_t zs, size_t hzs) {
   ZRUN(C); ZRUN(V0); ZRUN(Gout); ZRUN(lam); ZRUN(sweeps_out); ZRUN(sel.comps); ZRUN(sel.evr); ZRUN(sel.k_dev);
   sel.hm = zrun(sel.hm, hzs, blockIdx.z);
-  extern __shared__ __attribute__((aligned(16))) double s_g[];   // d columns of length d, column-major, stride LD
-  __shared__ double s_lam[PCABO_MAXD], s_sgn[PCABO_MAXD];
+  constexpr int LP = 16;                   // lanes per column pair: one DPP row
+  constexpr int RP = 16 * NT;              // rows of a padded column
+  constexpr int LD = RP | 1;               // odd stride: column p and q of a pair never share banks systematically
+  extern __shared__ __attribute__((aligned(16))) double s_g[];   // d columns of RP rows (d real ones, then zeros), column-major, stride LD
+  __shared__ double s_lam[PCABO_MAXD], s_sgn[PCABO_MAXD], s_evr[PCABO_MAXD];
   __shared__ int s_order[PCABO_MAXD];
+  __shared__ int s_rot;                    // "a rotation asked for another sweep" (and, before the sweeps, "V0 is unusable")
   const int tid = threadIdx.x;
-  const int LD = d | 1;                    // odd stride: column p and q of a pair never share banks systematically
-  volatile int& s_rot = *reinterpret_cast<volatile int*>(s_g + (size_t)d * LD);   // flag lives after the matrix
   if (tid == 0) s_rot = 0;
   __syncthreads();
   // Warm start from LDS copies of C and V0 when they fit (3 d^2 doubles; d <= 64): read once, coalesced - the d-long
   // loops below otherwise walk global memory (50 us of the kernel at d = 40).
   const bool staged = V0 && d <= 64;           // the launcher sizes the dynamic LDS for it
-  double* s_c = s_g + (size_t)d * LD + 2;      // C row-major, stride LD      (after the matrix and the flag)
+  double* s_c = s_g + (size_t)d * LD;          // C row-major, stride LD      (after the matrix)
   double* s_v = s_c + (size_t)d * LD;          // V0: column `col` contiguous, stride LD
   if (staged) {
     for (int idx = tid; idx < d * d; idx += (int)blockDim.x) {
@@ -305,19 +356,23 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi(const double* __restrict
     }
     s_g[col * LD + row] = v;
   }
+  for (int idx = tid; idx < d * (RP - d); idx += (int)blockDim.x)        // the zero rows d .. RP of every column
+    s_g[idx / (RP - d) * LD + d + idx % (RP - d)] = 0.0;
   if (tid == 0) s_rot = 0;
   __syncthreads();
 
   const int de = (d + 1) & ~1;             // even number of players (a virtual empty column if d is odd)
   const int npairs = de / 2;
-  const int LP = (int)blockDim.x >= npairs * 16 ? 16 : 8;      // lanes per column pair (launcher sizes the block)
   const int grp = tid / LP, lane = tid % LP;
   const double tol = 1e-15;
   // round-robin schedule: group g > 0 plays p = (round + g) mod m against q = (round - g) mod m, group 0 plays
-  // `round` against the fixed last player; both indices advance by one (mod m) per round - kept incrementally
-  // (two runtime modulo operations per round were ~15 % of the round)
+  // `round` against the fixed last player; both indices advance by one (mod m) per round - kept incrementally, as the
+  // LDS offsets of the two columns (no multiply in the round).  The lower column of a pair is "p" (offsets order as indices).
+  // Only group 0 ever meets the virtual column (d odd: its fixed player), so whether a group works is known up front.
   const int m_rr = de - 1;
-  int pr = grp < npairs ? grp % m_rr : 0, qr = grp < npairs ? (m_rr - grp % m_rr) % m_rr : 0;
+  const bool active = grp < npairs && !(grp == 0 && (d & 1));
+  const int owrap = m_rr * LD, olast = (de - 1) * LD;
+  int opr = grp < npairs ? grp % m_rr * LD : 0, oqr = grp < npairs ? (m_rr - grp % m_rr) % m_rr * LD : 0;
   int sweep = 0;
 #ifdef PCABO_ACQ_TIMING
   const unsigned long long jc0 = clock64(), jw0 = wall_clock64();
@@ -331,68 +386,40 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi(const double* __restrict
 #ifdef PCABO_ACQ_TIMING
       if (tid == 0) ph_t = clock64();
 #endif
-      if (grp < npairs) {
-        int p = pr, q = grp == 0 ? de - 1 : qr;
-        pr = pr + 1 == m_rr ? 0 : pr + 1;
-        qr = qr + 1 == m_rr ? 0 : qr + 1;
-        if (p > q) { int t = p; p = q; q = t; }
-        if (q < d) {
-          double* gp = s_g + p * LD;
-          double* gq = s_g + q * LD;
-          // the lane's rows stay in registers between the dot products and the rotation (d <= 4 LP: 4 rows at most
-          // on the fast path; longer columns take the second loop)
-          double xr[NT], yr[NT];
-          double a = 0.0, b = 0.0, g = 0.0;
+      if (active) {
+        const int o1 = opr, o2 = grp == 0 ? olast : oqr;
+        opr = opr + LD == owrap ? 0 : opr + LD;
+        oqr = oqr + LD == owrap ? 0 : oqr + LD;
+        double* gp = s_g + (o1 < o2 ? o1 : o2) + lane;
+        double* gq = s_g + (o1 < o2 ? o2 : o1) + lane;
+        // the lane's rows stay in registers between the dot products and the rotation: row t = row lane + 16 t
+        double xr[NT], yr[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) { xr[t] = gp[16 * t]; yr[t] = gq[16 * t]; }
+        double a, b, g;
+        jac_chain<NT>(xr, yr, a, b, g);
+        // the three row sums level by level (the tree of row_sum16): independent adds between a DPP move and its use
+        a += dpp_row<0xB1>(a); b += dpp_row<0xB1>(b); g += dpp_row<0xB1>(g);          // quad_perm [1,0,3,2]
+        a += dpp_row<0x4E>(a); b += dpp_row<0x4E>(b); g += dpp_row<0x4E>(g);          // quad_perm [2,3,0,1]
+        a += dpp_row<0x141>(a); b += dpp_row<0x141>(b); g += dpp_row<0x141>(g);       // row_half_mirror
+        a += dpp_row<0x140>(a); b += dpp_row<0x140>(b); g += dpp_row<0x140>(g);       // row_mirror
+        const double ab = a * b, gg = g * g;
+        JSTAMP(ph_dot);
+        if (gg > tol * tol * ab && fabs(g) > 1e-300) {
+          double cs, sn;
+          jac_rotation(a, b, g, cs, sn);
+#ifdef PCABO_ACQ_TIMING
+          if (cs == 123.456) s_rot = 2;      // keeps cs live before the stamp
+#endif
+          JSTAMP(ph_rot);
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
-            const int r = lane + t * LP;
-            xr[t] = r < d ? gp[r] : 0.0;
-            yr[t] = r < d ? gq[r] : 0.0;
-            a += xr[t] * xr[t]; b += yr[t] * yr[t]; g += xr[t] * yr[t];
+            double xo, yo;
+            jac_apply(cs, sn, xr[t], yr[t], xo, yo);
+            gp[16 * t] = xo; gq[16 * t] = yo;
           }
-          for (int r = lane + NT * LP; r < d; r += LP) {
-            double x = gp[r], y = gq[r];
-            a += x * x; b += y * y; g += x * y;
-          }
-          if (LP == 16) {                       // the pair's 16 lanes are one DPP row: no LDS traffic, no waits
-            a = row_sum16(a); b = row_sum16(b); g = row_sum16(g);
-          } else if (LP == 8) {                 // half a DPP row: quad_perm x2 + row_half_mirror
-            a += dpp_get<0xB1, 0xf>(a); b += dpp_get<0xB1, 0xf>(b); g += dpp_get<0xB1, 0xf>(g);
-            a += dpp_get<0x4E, 0xf>(a); b += dpp_get<0x4E, 0xf>(b); g += dpp_get<0x4E, 0xf>(g);
-            a += dpp_get<0x141, 0xf>(a); b += dpp_get<0x141, 0xf>(b); g += dpp_get<0x141, 0xf>(g);
-          } else {
-            for (int off = LP >> 1; off > 0; off >>= 1) {
-              a += __shfl_xor(a, off, 64);
-              b += __shfl_xor(b, off, 64);
-              g += __shfl_xor(g, off, 64);
-            }
-          }
-          const double ab = a * b;
-          JSTAMP(ph_dot);
-          if (g * g > tol * tol * ab && fabs(g) > 1e-300) {
-            // rotation from hardware rcp/rsq estimates + Newton steps (c^2 + s^2 = 1 to ~1 ulp is what matters)
-            // (the ANGLE only needs ~1e-12: an error there is removed by the next rotation of the pair - one Newton
-            // step on the estimates; cs below keeps two)
-            const double zeta = (b - a) * 0.5 * rcp_1nr(g);
-            const double hyp = 1.0 + zeta * zeta;
-            const double t = (zeta >= 0.0 ? 1.0 : -1.0) * rcp_1nr(fabs(zeta) + hyp * rsq_1nr(hyp));
-            const double cs = fast_rsq(1.0 + t * t);
-            const double sn = cs * t;
-            if (cs == 123.456) s_rot = 2;      // (timing build only) keeps cs live before the stamp
-            JSTAMP(ph_rot);
-#pragma unroll
-            for (int u = 0; u < NT; ++u) {
-              const int r = lane + u * LP;
-              if (r < d) { gp[r] = cs * xr[u] - sn * yr[u]; gq[r] = sn * xr[u] + cs * yr[u]; }
-            }
-            for (int r = lane + NT * LP; r < d; r += LP) {
-              double x = gp[r], y = gq[r];
-              gp[r] = cs * x - sn * y;
-              gq[r] = sn * x + cs * y;
-            }
-            if (lane == 0 && g * g > 1e-16 * ab) s_rot = 1;   // a further sweep is needed
-            JSTAMP(ph_wr);
-          }
+          if (lane == 0 && gg > 1e-16 * ab) s_rot = 1;   // a further sweep is needed (a plain LDS store; read after the barrier)
+          JSTAMP(ph_wr);
         }
       }
       __syncthreads();
@@ -408,20 +435,40 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi(const double* __restrict
   if (tid == 0) { g_jac_stamps[0] = clock64() - jc0; g_jac_stamps[1] = wall_clock64() - jw0; g_jac_stamps[2] = (unsigned long long)sweep; g_jac_stamps[3] = (unsigned long long)(de - 1);
     g_jac_stamps[4] = ph_dot; g_jac_stamps[5] = ph_rot; g_jac_stamps[6] = ph_wr; g_jac_stamps[7] = ph_bar; }
 #endif
-  // eigenvalues = column norms; write normalised columns (eigenvectors), column-major d x d
-  for (int col = tid / 64; col < d; col += (int)blockDim.x / 64) {
-    int l = tid & 63;
-    double a = 0.0;
-    for (int r = l; r < d; r += 64) { double x = s_g[col * LD + r]; a += x * x; }
-    a = wave_sum(a);
-    double nrm = sqrt(a);
-    double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
-    for (int r = l; r < d; r += 64) {
-      const double v = s_g[col * LD + r] * inv;
-      Gout[(size_t)col * d + r] = v;
-      s_g[col * LD + r] = v;                                     // the selection below works on the normalised columns
+  // eigenvalues = column norms; write normalised columns (eigenvectors), column-major d x d.  A wave takes eight columns at a
+  // time (columns w + nw i): their sums of squares go through ONE wave_sum_multi<8> - the tree of wave_sum, bit for bit - after
+  // which lane l holds the sum of column l & 7, so the eight square roots and the eight divisions are one of each per wave.
+  {
+    const int nw = (int)blockDim.x >> 6, w = tid >> 6, l = tid & 63;
+    for (int c0 = w; c0 < d; c0 += 8 * nw) {
+      double x0[8], x1[8], v[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int col = c0 + nw * i;
+        x0[i] = col < d && l < d ? s_g[col * LD + l] : 0.0;
+        x1[i] = col < d && l + 64 < d ? s_g[col * LD + l + 64] : 0.0;      // (d <= 128: two rows per lane at most)
+        v[i] = __builtin_fma(x1[i], x1[i], __builtin_fma(x0[i], x0[i], 0.0));
+      }
+      wave_sum_multi<8>(v, l);
+      const double nrm = sqrt(v[0]);
+      const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int col = c0 + nw * i;
+        const double inv_i = read_lane(inv, i);
+        if (col < d && l < d) {
+          const double u = x0[i] * inv_i;
+          Gout[(size_t)col * d + l] = u;
+          s_g[col * LD + l] = u;                                     // the selection below works on the normalised columns
+        }
+        if (col < d && l + 64 < d) {
+          const double u = x1[i] * inv_i;
+          Gout[(size_t)col * d + l + 64] = u;
+          s_g[col * LD + l + 64] = u;
+        }
+      }
+      if (l < 8 && c0 + nw * l < d) { lam[c0 + nw * l] = nrm / cscale; s_lam[c0 + nw * l] = nrm; }      // (the ratios below do not see the scale)
     }
-    if (l == 0) { lam[col] = nrm / cscale; s_lam[col] = nrm; }      // (the ratios below do not see the scale)
   }
   if (tid == 0) *sweeps_out = sweep;
   // ---- selection (was a launch of its own: k_pca_finalize): eigenpairs by decreasing variance, explained-variance
@@ -435,16 +482,29 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi(const double* __restrict
   }
   __syncthreads();
   const int rcount = sel.n < d ? sel.n : d;           // sklearn keeps min(n, d) components
-  if (tid == 0) {
+  if (tid < rcount) {
+    // ratio of this component: every thread forms the total itself, in thread 0's order (LDS broadcast reads), so the rcount
+    // divisions run side by side; the cumulative sum and the count stay with one thread, in the same order (below)
     double tot = 0.0;
     for (int r = 0; r < rcount; ++r) tot += s_lam[s_order[r]];
+    const double e = s_lam[s_order[tid]] / tot;
+    sel.evr[tid] = e;
+    s_evr[tid] = e;
+    const double* v = s_g + s_order[tid] * LD;          // sign of each component: its max-|.| entry positive
+    double best = -1.0, sgn = 1.0;
+    for (int j = 0; j < d; ++j) {
+      double a = fabs(v[j]);
+      if (a > best) { best = a; sgn = v[j] < 0.0 ? -1.0 : 1.0; }
+    }
+    s_sgn[tid] = sgn;
+  }
+  __syncthreads();
+  if (tid == 0) {
     int k;
     double cum = 0.0;
     int cnt = 0;
     for (int r = 0; r < rcount; ++r) {
-      double e = s_lam[s_order[r]] / tot;
-      sel.evr[r] = e;
-      cum += e;
+      cum += s_evr[r];
       cnt += (cum <= sel.var_threshold);
     }
     if (sel.n_components > 0) k = sel.n_components < rcount ? sel.n_components : rcount;
@@ -456,16 +516,6 @@ __global__ __launch_bounds__(JAC_THREADS) void k_jacobi(const double* __restrict
     *sel.k_dev = k;
     sel.hm->k = k;
   }
-  if (tid < rcount) {                                   // sign of each component: its max-|.| entry positive
-    const double* v = s_g + s_order[tid] * LD;
-    double best = -1.0, sgn = 1.0;
-    for (int j = 0; j < d; ++j) {
-      double a = fabs(v[j]);
-      if (a > best) { best = a; sgn = v[j] < 0.0 ? -1.0 : 1.0; }
-    }
-    s_sgn[tid] = sgn;
-  }
-  __syncthreads();
   for (int idx = tid; idx < rcount * d; idx += (int)blockDim.x) {
     const int r = idx / d, j = idx % d;
     sel.comps[idx] = s_sgn[r] * s_g[s_order[r] * LD + j];
@@ -660,25 +710,39 @@ void launch_cov(hipStream_t s, const double* Wc, int n, int DP, double* C, ZB zb
   int n4 = (n + 3) & ~3;
   hipLaunchKernelGGL(k_cov, dim3(DP / 16, DP / 16, zb.B), dim3(256), 0, s, Wc, n4, DP, 1.0 / (double)(n - 1), C, zb.zs);
 }
+// NT = 16-row tiles a lane keeps per column: the smallest of 1, 2, 3, 4, 6, 8 that covers d (a tile of zero rows costs two LDS
+// reads, three fmas and two LDS writes per round and changes no bit).  16 lanes per pair at every d: npairs = ceil(d / 2) <= 64
+// pairs are at most 16 waves, one work-group.
+template <int NT>
+static void launch_jacobi_as(hipStream_t s, int threads, size_t lds, const double* C, int d, int DP, const double* V0, double* G,
+                             double* lam, int* sweeps, const PcaSelect& sel, const ZB& zb) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    // 160 KB per work-group minus the kernel's static arrays (3.5 KB); d = 128 needs 129 KB of dynamic LDS
+    (void)hipFuncSetAttribute((const void*)k_jacobi<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(k_jacobi<NT>, dim3(1, 1, zb.B), dim3(threads), lds, s, C, d, DP, V0, G, lam, sweeps, sel, zb.zs, zb.hzs);
+}
 void launch_jacobi(hipStream_t s, const double* C, int d, int DP, const double* V0, double* G, double* lam, int* sweeps,
                    int n, double var_threshold, int n_components, double* comps, double* evr, int* k_dev, HostMirror* hm,
                    ZB zb) {
-  size_t lds = ((size_t)d * (d | 1) + 2) * sizeof(double);
-  if (V0 && d <= 64) lds += (size_t)2 * d * (d | 1) * sizeof(double);      // LDS copies of C and V0 for the warm start
-  static bool attr_set = false;
-  if (!attr_set) {
-    // 160 KB per work-group minus the kernel's static arrays (2.5 KB); d = 128 needs 132 KB of dynamic LDS
-    (void)hipFuncSetAttribute((const void*)k_jacobi<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    (void)hipFuncSetAttribute((const void*)k_jacobi<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    attr_set = true;
-  }
+  const int nt = d <= 16 ? 1 : d <= 32 ? 2 : d <= 48 ? 3 : d <= 64 ? 4 : d <= 96 ? 6 : 8;
+  const size_t col = (size_t)(16 * nt | 1);                              // the kernel's LD
+  size_t lds = (size_t)d * col * sizeof(double);
+  if (V0 && d <= 64) lds += (size_t)2 * d * col * sizeof(double);        // LDS copies of C and V0 for the warm start
   const int npairs = ((d + 1) & ~1) / 2;
-  int threads = npairs * 16 <= JAC_THREADS ? npairs * 16 : npairs * 8;      // 16 lanes per column pair while they fit
-  threads = (threads + 63) & ~63;
+  int threads = (npairs * 16 + 63) & ~63;             // 16 lanes per column pair (<= JAC_THREADS: d <= PCABO_MAXD = 128)
   if (threads < d) threads = (d + 63) & ~63;          // the selection step at the end uses one thread per component
   PcaSelect sel{n, var_threshold, n_components, comps, evr, k_dev, hm};
-  if (d <= 64) hipLaunchKernelGGL(k_jacobi<4>, dim3(1, 1, zb.B), dim3(threads), lds, s, C, d, DP, V0, G, lam, sweeps, sel, zb.zs, zb.hzs);
-  else hipLaunchKernelGGL(k_jacobi<8>, dim3(1, 1, zb.B), dim3(threads), lds, s, C, d, DP, V0, G, lam, sweeps, sel, zb.zs, zb.hzs);
+  switch (nt) {
+    case 1: launch_jacobi_as<1>(s, threads, lds, C, d, DP, V0, G, lam, sweeps, sel, zb); break;
+    case 2: launch_jacobi_as<2>(s, threads, lds, C, d, DP, V0, G, lam, sweeps, sel, zb); break;
+    case 3: launch_jacobi_as<3>(s, threads, lds, C, d, DP, V0, G, lam, sweeps, sel, zb); break;
+    case 4: launch_jacobi_as<4>(s, threads, lds, C, d, DP, V0, G, lam, sweeps, sel, zb); break;
+    case 6: launch_jacobi_as<6>(s, threads, lds, C, d, DP, V0, G, lam, sweeps, sel, zb); break;
+    default: launch_jacobi_as<8>(s, threads, lds, C, d, DP, V0, G, lam, sweeps, sel, zb); break;
+  }
 }
 void launch_project(hipStream_t s, const double* X, const double* data_mean, const double* pca_mean,
                     const double* comps, const int* k_dev, int n, int d, double* Z, ZB zb) {

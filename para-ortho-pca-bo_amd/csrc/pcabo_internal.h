@@ -169,6 +169,15 @@ __device__ inline double dpp_get(double v) {
   int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
   return __hiloint2double(hi, lo);
 }
+// The same move for a permutation INSIDE a row with every row and bank enabled (quad_perm, row_half_mirror, row_mirror, row_ror):
+// each lane has a valid source, so no lane keeps `old`.  bound_ctrl says so to the compiler, which then drops the two
+// `v_mov_b32 v, 0` (and often an s_nop) that every dpp_get costs for filling `old`.
+template <int CTRL>
+__device__ inline double dpp_row(double v) {
+  int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+  int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
 __device__ inline double row_sum16(double v) {        // every lane: sum over its row of 16 lanes
   v += dpp_get<0xB1, 0xf>(v);      // quad_perm [1,0,3,2]
   v += dpp_get<0x4E, 0xf>(v);      // quad_perm [2,3,0,1]
