@@ -199,6 +199,27 @@ int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int m
 int pcabo_logei(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize,
                 double* val, double* grad);
 
+/* What the conditioned GP predicts at q points of the reduced space: the reference's model.posterior(test_points)
+ * (Algorithms/utils/visualization_utils.py:458-461).  Opt-in, not used by the BO loop (DESIGN.md "GP posterior queries").
+ * Semantics: gpytorch's and botorch's for SingleTaskGP(MaternKernel | RBFKernel, Standardize, Normalize) without an output scale,
+ * restated; parity with BoTorch itself is unpinned (the tests compare with this repository's own oracle).
+ *   Xq[q*k] [bulk]; flags: 0 or PCABO_POST_OBS_NOISE; mean[q], var[q], cov[q*q] [bulk], each may be NULL (not all three).
+ *   mean_a = y_mean + y_std sum_j alpha_j k(x_a, z_j).  After a fit y_mean carries the constant mean (m + s c); after an ARD fit the
+ *            folded Normalize ranges and lengthscale 1 are used as they stand; in a batch after its fit every run reads its own model.
+ *   var_a  = (1 - |v_a|^2) y_std^2, v = L^-1 k(Z, x_a): the latent variance, floored like gpytorch's (values below 1e-10, NaN
+ *            included, become 1e-10).  With PCABO_POST_OBS_NOISE: ((1 - |v_a|^2) + s2) y_std^2, then the same floor; s2 is the
+ *            likelihood noise the context was conditioned with (the fitted one after a fit).  Jitter the factorisation had to add
+ *            is part of K, not of s2.  botorch's second floor (1e-12) belongs to its analytic acquisitions and is not applied.
+ *   cov    = y_std^2 (k(Xq, Xq) [+ s2 I] - V^T V), full q x q, row-major, symmetric bit for bit, NOT floored (gpytorch's
+ *            covariance_matrix is not); its diagonal is bit-equal to the variance of the same call before the floor.
+ * PCABO_ERR_ARG, nothing launched: q < 1 or q > max_q; mean, var and cov all NULL; unknown flag bits; no GP in the context (never
+ * conditioned, or the last conditioning ended PCABO_ERR_NOT_PD / not finite); between pcabo_gp_condition_begin and its _end.
+ * The V (n x max_q) and cov (max_q^2) buffers are allocated by the first call that asks for a covariance and kept until destroy.
+ * Returns when the results are there.  A call changes nothing the later calls of the context read: what follows is bit for bit
+ * what it would have been without it. */
+enum { PCABO_POST_OBS_NOISE = 1 };
+int pcabo_gp_posterior(pcabo_ctx* ctx, const double* Xq, int q, int flags, double* mean, double* var, double* cov);
+
 /* Rows M-N: multi-start L-BFGS-B over the acquisition (botorch gen_candidates_scipy semantics:
  * restarts are optimised jointly in groups of `batch_limit`, objective -sum_j acq(x_j), scipy
  * L-BFGS-B defaults m=10, factr=1e7 (ftol 2.22e-9), pgtol=1e-5, maxls=20, maxfun=15000).
@@ -348,6 +369,14 @@ int pcabo_batch_acq_bounds(pcabo_batch* batch, double* bounds);
  * best_f[B]; val[B][q]; status[B] (PCABO_ERR_NOT_PD for a run whose factorisation failed after the jitter retries). */
 int pcabo_batch_gp_condition_end_eval(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize,
                                       int acq, double* val, int* status);
+/* pcabo_gp_posterior for every run in one launch sequence, each run bit for bit what it takes alone.  Host pointers.
+ * Xq[B][q*max_d]: run b's block holds a dense q x k_b array; mean[B][q], var[B][q], cov[B][q*q], each may be NULL (not all three).
+ * status[B] (may be NULL): PCABO_ERR_ARG for a run parked by pcabo_batch_set_active and for a run whose factorisation failed - both
+ * are skipped, their output blocks left as they are.  Needs a batch whose conditioning has been waited for
+ * (pcabo_batch_gp_condition_end_eval*, pcabo_batch_gp_fit): PCABO_ERR_ARG otherwise and for the refusals of pcabo_gp_posterior.
+ * The runs' V and cov buffers are ONE allocation made by the first call that asks for a covariance. */
+int pcabo_batch_gp_posterior(pcabo_batch* batch, const double* Xq, int q, int flags, double* mean, double* var, double* cov,
+                             int* status);
 /* Rows M-N for every run (pcabo_optimize_acqf semantics per run).  ics[B][num_restarts*max_d] (dense num_restarts x k_b per
  * block), bounds[B][2*max_d] as pcabo_batch_acq_bounds gives them, best_f[B]; cand[B][num_restarts*max_d] (dense per block),
  * vals[B][num_restarts], info[B][4*ngroups] or NULL, failed[B], status[B]. */

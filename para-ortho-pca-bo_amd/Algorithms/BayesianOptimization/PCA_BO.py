@@ -489,6 +489,16 @@ class PCA_BO(AbstractBayesianOptimizer):
         self.lbfgsb_info.append(info)
         return new_z
 
+    # ---- what the model predicts (the reference's model.posterior(test_points), visualization_utils.py:458-461) -------
+    def posterior(self, X, observation_noise: bool = False, covariance: bool = False) -> dict:
+        """Posterior of the current iteration's GP at X (m x d, original space): {"mean", "variance"[, "covariance"]}
+        (Context.gp_posterior).  X is mapped into the reduced space on the host with this iteration's centring and components.
+        RuntimeError when no run is open or the iteration's model is not conditioned yet.  Leaves the run's trajectory alone."""
+        if self.__ctx is None or self.pca is None or self.__gp_pending:
+            raise RuntimeError("posterior: no run is open, or the model of the current iteration is not conditioned yet")
+        X = np.asarray(X, dtype=np.float64).reshape(-1, self.dimension)
+        return self.__ctx.gp_posterior(self.pca.transform(X - self.data_mean), observation_noise, covariance)
+
     # ---- row O ------------------------------------------------------------------------------------
     def _transform_point_to_original_space(self, z: np.ndarray) -> np.ndarray:
         if self.pca is None:

@@ -172,6 +172,14 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         self.lbfgsb_info.append(info)
         return new_x
 
+    def posterior(self, X, observation_noise: bool = False, covariance: bool = False) -> dict:
+        """Posterior of the current iteration's GP at X (m x d): {"mean", "variance"[, "covariance"]} (Context.gp_posterior).
+        RuntimeError when no run is open or the iteration's model is not conditioned yet (the library refuses the call)."""
+        if self.__ctx is None:
+            raise RuntimeError("posterior: no run is open")
+        X = np.asarray(X, dtype=np.float64).reshape(-1, self.dimension)
+        return self.__ctx.gp_posterior(X, observation_noise, covariance)
+
     def __repr__(self):
         return super().__repr__()
 

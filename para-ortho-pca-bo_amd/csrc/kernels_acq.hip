@@ -33,7 +33,7 @@
 #include <cstdlib>
 #include <mutex>
 
-#define PSTRIDE (2 + 2 * PCABO_MAXD)   // doubles per (query, slab) partial record
+#define PSTRIDE PCABO_PSTRIDE           // doubles per (query, slab) partial record
 
 // Phase stamps for tools/gpu_acq_phases.py (diagnostic build only: `make timing` -> libpcabo_timing.so).
 #ifdef PCABO_ACQ_TIMING
@@ -1435,12 +1435,19 @@ void launch_score_tail(hipStream_t st, int q, const GpModel& m, AcqParams p, con
                      (double*)nullptr, AcqBatch());
 }
 
+// launch_score's first kernel on its own (any q >= 1): KS and the mu_s part of the first njb records of every query
+void launch_score_ks(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS, double* partial, AcqBatch ab,
+                     int B) {
+  const int S = m.NP / 64, njb = (m.NP + 255) / 256;
+  hipLaunchKernelGGL(k_score_ks, dim3(njb, (q + SC_QB - 1) / SC_QB, B), dim3(256), 0, st, Xq, q, m.n, m.k, m.NP, m.ld, m.ZnT, m.alpha,
+                     m.bounds4, p, KS, partial, S, ab);
+}
+
 // Value-only scoring of q >= 64 points: KS, then V = R KS^T on MFMA, then the scalar chain per query (k_acq_combine).
 void launch_score(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS, double* partial, double* val,
                   AcqBatch ab, int B) {
   const int S = m.NP / 64, njb = (m.NP + 255) / 256;
-  hipLaunchKernelGGL(k_score_ks, dim3(njb, (q + SC_QB - 1) / SC_QB, B), dim3(256), 0, st, Xq, q, m.n, m.k, m.NP, m.ld, m.ZnT, m.alpha,
-                     m.bounds4, p, KS, partial, S, ab);
+  launch_score_ks(st, Xq, q, m, p, KS, partial, ab, B);
   hipLaunchKernelGGL(k_score_gemm, dim3(S, (q + 63) / 64, B), dim3(256), 0, st, m.R, KS, q, m.NP, m.ld, njb, partial, ab.zs);
   p.want_grad = 0;
   hipLaunchKernelGGL(k_acq_combine, dim3((q + 3) / 4, 1, B), dim3(256), 0, st, partial, q, S, m.k, m.bounds4, m.ystats, p, val,

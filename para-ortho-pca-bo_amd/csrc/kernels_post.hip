@@ -1,0 +1,240 @@
+// Posterior of the conditioned GP at q query points of the reduced space: mean, variance and joint covariance
+// (pcabo_gp_posterior / pcabo_batch_gp_posterior; DESIGN.md "GP posterior queries").
+//
+// gpytorch's model.posterior(X) for SingleTaskGP(MaternKernel | RBFKernel, Standardize, Normalize) without an output scale, from the
+// state the conditioning kernels left (ZnT, R = L^-1, alpha, Standardize statistics):
+//   ks = k(xn, Zn),  V = R KS^T (NP x q)
+//   mean_a  = m_y + s_y sum_j alpha_j ks_aj
+//   var_a   = s_y^2 (1 [+ s2] - |v_a|^2), floored at 1e-10 (gpytorch's min_variance)
+//   cov_ab  = s_y^2 (k(xn_a, xn_b) [+ s2 delta_ab] - v_a . v_b), not floored
+// The launches are those of the value-only scoring (kernels_acq.hip) up to the scalar chain:
+//   k_score_ks      KS and the mu_s records, unchanged
+//   k_post_gemm     k_score_gemm's product - the same staging and the same MFMA sequence per tile, so |v|^2 has its bits - which also
+//                   stores V when a covariance is asked for
+//   k_post_combine  one wave per query: the S records added in acq_finish_query's order, then mean and variance instead of an
+//                   acquisition value; the variance before the floor is kept for the covariance's diagonal
+//   k_post_cov      V^T V per lower 64 x 64 tile on v_mfma_f64_16x16x4f64, the prior part rebuilt from the normalised queries in the
+//                   epilogue, tile and mirror written by the one work-group that owns them: no atomics, the same bits on every call
+// Batches: blockIdx.z = run, zrun addressing, k of a run from k_dev, 1 / lengthscale and the noise from its hyperparameter block.
+#include "pcabo_internal.h"
+#include "acq_math.h"
+
+__global__ __launch_bounds__(256) void k_post_gemm(const double* __restrict__ R, const double* __restrict__ KS,
+                                                   int q_total, int NP, int ld, int njb, double* __restrict__ partial,
+                                                   double* __restrict__ V /* NP x q_total, or null */, size_t zs, size_t vzs) {
+  ZRUN(R); ZRUN(KS); ZRUN(partial);
+  V = zrun(V, vzs, blockIdx.z);
+  __shared__ __attribute__((aligned(16))) double s_a[64 * PCABO_TLD];
+  __shared__ __attribute__((aligned(16))) double s_b[64 * PCABO_TLD];
+  __shared__ double s_red[4][64];
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+  const int I = blockIdx.x, qb = blockIdx.y, S = gridDim.x;
+  const double* Rrow = R + (size_t)(I * 64) * ld;
+  const double* Krow = KS + (size_t)(qb * 64) * ld;
+  double pa[16], pb[16];
+  auto fetch = [&](int J) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
+      pa[u] = Rrow[(size_t)r * ld + J * 64 + c];
+      pb[u] = (qb * 64 + r < q_total) ? Krow[(size_t)r * ld + J * 64 + c] : 0.0;
+    }
+  };
+  auto put = [&]() {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
+      s_a[r * PCABO_TLD + c] = pa[u];
+      s_b[r * PCABO_TLD + c] = pb[u];
+    }
+  };
+  double4_t acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  fetch(0);
+  for (int J = 0; J <= I; ++J) {              // R is lower triangular: column blocks beyond the diagonal hold zeros
+    __syncthreads();                          // the previous step's MFMAs have read the LDS tiles
+    put();
+    if (J < I) fetch(J + 1);
+    __syncthreads();
+    for (int kk = 0; kk < 64; kk += 4) {
+      const double a = s_a[(16 * w + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const double b = s_b[(16 * t + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
+        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  // acc[t][r] = V[16 w + (l >> 4) + 4 r][16 t + (l & 15)] of this tile: the tile itself, then its column norms
+  if (V) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int a = qb * 64 + 16 * t + (l & 15);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (a < q_total) V[(size_t)(I * 64 + 16 * w + (l >> 4) + 4 * r) * q_total + a] = acc[t][r];
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    double v = ((acc[t][0] * acc[t][0] + acc[t][1] * acc[t][1]) + acc[t][2] * acc[t][2]) + acc[t][3] * acc[t][3];
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    if (l < 16) s_red[w][16 * t + l] = v;
+  }
+  __syncthreads();
+  if (tid < 64 && qb * 64 + tid < q_total) {
+    double* rec = partial + ((size_t)(qb * 64 + tid) * S + I) * PCABO_PSTRIDE;
+    rec[0] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+    if (I >= njb) rec[1] = 0.0;               // (records 0 .. njb-1 got their mu_s part from k_score_ks)
+  }
+}
+
+// One wave per query: out[q] = mean, out[q_total + q] = variance (floored), out[2 q_total + q] = the variance before the floor.
+__global__ __launch_bounds__(256) void k_post_combine(const double* __restrict__ partial, int q_total, int S,
+                                                      const double* __restrict__ ystats, double s2, int obs_noise,
+                                                      double* __restrict__ out, size_t zs, const double* __restrict__ hyp) {
+  ZRUN(partial); ZRUN(ystats); ZRUN(out);
+  if (hyp) s2 = zrun(hyp, zs, blockIdx.z)[PCABO_HYP_NOISE];
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+  if (q >= q_total) return;
+  const double* base = partial + (size_t)q * S * PCABO_PSTRIDE;
+  const double ym = ystats[0], ysd = ystats[1];
+  double vv = 0.0, mus = 0.0;
+  for (int s = l; s < S; s += 64) { vv += base[(size_t)s * PCABO_PSTRIDE]; mus += base[(size_t)s * PCABO_PSTRIDE + 1]; }
+  vv = wave_sum(vv);
+  mus = wave_sum(mus);
+  const double mu = ym + ysd * mus;
+  double var = obs_noise ? ((1.0 - vv) + s2) * (ysd * ysd) : (1.0 - vv) * (ysd * ysd);
+  const double raw = var;
+  if (!(var >= 1e-10)) var = 1e-10;          // gpytorch min_variance (double)
+  if (l == 0) {
+    out[q] = mu;
+    out[(size_t)q_total + q] = var;
+    out[2 * (size_t)q_total + q] = raw;
+  }
+}
+
+// cov = s_y^2 (k(Xq, Xq) - V^T V) off the diagonal, the combine pass' unfloored variance on it.  Work-group t owns the lower tile
+// (A, Bt), A >= Bt, and writes it and its mirror.
+__global__ __launch_bounds__(256) void k_post_cov(const double* __restrict__ V, int q_total, int NP, const double* __restrict__ Xq,
+                                                  int k, const double* __restrict__ bounds4, const double* __restrict__ ystats,
+                                                  const double* __restrict__ raw_var, double inv_ls, int kernel,
+                                                  double* __restrict__ cov, size_t zs, size_t vzs, const int* __restrict__ k_dev,
+                                                  const double* __restrict__ hyp) {
+  ZRUN(Xq); ZRUN(bounds4); ZRUN(ystats); ZRUN(raw_var);
+  V = zrun(V, vzs, blockIdx.z); cov = zrun(cov, vzs, blockIdx.z);
+  if (k_dev) k = *zrun(k_dev, zs, blockIdx.z);
+  if (hyp) inv_ls = zrun(hyp, zs, blockIdx.z)[PCABO_HYP_INV_LS];
+  __shared__ __attribute__((aligned(16))) double s_a[64 * PCABO_TLD];
+  __shared__ __attribute__((aligned(16))) double s_b[64 * PCABO_TLD];
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+  int A = 0, Bt = blockIdx.x;
+  while (Bt > A) { Bt -= A + 1; ++A; }       // lower tiles row by row: (0,0) (1,0) (1,1) (2,0) ...
+  const size_t Q = (size_t)q_total;
+  double pa[16], pb[16];
+  auto fetch = [&](int P) {                   // rows 64 P .. of V: the columns of tile A and of tile Bt (zeros beyond q)
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
+      const double* row = V + (size_t)(P * 64 + r) * Q;
+      pa[u] = (A * 64 + c < q_total) ? row[A * 64 + c] : 0.0;
+      pb[u] = (Bt * 64 + c < q_total) ? row[Bt * 64 + c] : 0.0;
+    }
+  };
+  auto put = [&]() {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
+      s_a[r * PCABO_TLD + c] = pa[u];
+      s_b[r * PCABO_TLD + c] = pb[u];
+    }
+  };
+  double4_t acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  const int nP = NP / 64;
+  fetch(0);
+  for (int P = 0; P < nP; ++P) {              // row blocks in ascending order: the sum does not depend on a schedule
+    __syncthreads();
+    put();
+    if (P + 1 < nP) fetch(P + 1);
+    __syncthreads();
+    for (int kk = 0; kk < 64; kk += 4) {      // the tiles lie [row of V][query]: operand (query 16 w + (l & 15), row kk + (l >> 4))
+      const double a = s_a[(kk + (l >> 4)) * PCABO_TLD + 16 * w + (l & 15)];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const double b = s_b[(kk + (l >> 4)) * PCABO_TLD + 16 * t + (l & 15)];
+        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  // acc[t][r] = (V^T V)[64 A + 16 w + (l >> 4) + 4 r][64 Bt + 16 t + (l & 15)].  The prior part: squared distances of the
+  // normalised queries in the direct form, 64 coordinates at a time through the two tiles (query, coordinate), ascending.
+  double sq[4][4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sq[t][r] = 0.0;
+  for (int c0 = 0; c0 < k; c0 += 64) {
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
+      double xa = 0.0, xb = 0.0;
+      if (c0 + c < k) {
+        const double lo = bounds4[c0 + c], hi = bounds4[PCABO_MAXD + c0 + c];
+        if (A * 64 + r < q_total) xa = (Xq[(size_t)(A * 64 + r) * k + c0 + c] - lo) / (hi - lo);
+        if (Bt * 64 + r < q_total) xb = (Xq[(size_t)(Bt * 64 + r) * k + c0 + c] - lo) / (hi - lo);
+      }
+      s_a[r * PCABO_TLD + c] = xa;
+      s_b[r * PCABO_TLD + c] = xb;
+    }
+    __syncthreads();
+    const int cn = k - c0 < 64 ? k - c0 : 64;
+    for (int c = 0; c < cn; ++c) {
+      double xa[4], xb[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xa[r] = s_a[(16 * w + (l >> 4) + 4 * r) * PCABO_TLD + c];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) xb[t] = s_b[(16 * t + (l & 15)) * PCABO_TLD + c];
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { const double d = xa[r] - xb[t]; sq[t][r] += d * d; }
+    }
+  }
+  const double ysd = ystats[1], sy2 = ysd * ysd;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int j = 16 * t + (l & 15);
+    const size_t b = (size_t)Bt * 64 + j;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = 16 * w + (l >> 4) + 4 * r;
+      const size_t a = (size_t)A * 64 + i;
+      if (a >= Q || b >= Q) continue;
+      if (a == b) { cov[a * Q + a] = raw_var[a]; continue; }
+      if (A == Bt && i < j) continue;          // a diagonal tile: its upper half is the mirror of its lower half
+      const double c = (acq_cov_value(sq[t][r] * (inv_ls * inv_ls), kernel) - acc[t][r]) * sy2;
+      cov[a * Q + b] = c;
+      cov[b * Q + a] = c;
+    }
+  }
+}
+
+// The whole query: KS and the mu_s records (the scoring's first launch), V = R KS^T with its column norms, mean and variance per query
+// into post[3 q] and, with V / cov given, the q x q covariance.  B > 1: the runs of a batch (strides zs; vzs between their V / cov).
+void launch_posterior(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double s2, int obs_noise,
+                      double* KS, double* partial, double* post, double* V, double* cov, AcqBatch ab, size_t vzs, int B) {
+  const int S = m.NP / 64, njb = (m.NP + 255) / 256;
+  launch_score_ks(st, Xq, q, m, p, KS, partial, ab, B);
+  hipLaunchKernelGGL(k_post_gemm, dim3(S, (q + 63) / 64, B), dim3(256), 0, st, m.R, KS, q, m.NP, m.ld, njb, partial, V, ab.zs, vzs);
+  hipLaunchKernelGGL(k_post_combine, dim3((q + 3) / 4, 1, B), dim3(256), 0, st, partial, q, S, m.ystats, s2, obs_noise, post, ab.zs,
+                     ab.hyp);
+  if (!cov) return;
+  const int nt = (q + 63) / 64;
+  hipLaunchKernelGGL(k_post_cov, dim3(nt * (nt + 1) / 2, 1, B), dim3(256), 0, st, V, q, m.NP, Xq, m.k, m.bounds4, m.ystats,
+                     post + 2 * (size_t)q, p.inv_ls, p.kernel, cov, ab.zs, vzs, ab.k_dev, ab.hyp);
+}

@@ -119,6 +119,8 @@ struct pcabo_ctx {
                                          // ARD: 1 + KP sums per tile, then the 5 + KP results (k_mll_finish_ard)
   double* dArdLs = nullptr;              // ARD fit: the k lengthscales k_zstats folds into the Normalize ranges
   double* dHyp = nullptr;                // lock-step fit of a batch: this run's {1 / lengthscale, noise, mean constant} (PCABO_HYP_*)
+  double* dPostV = nullptr;              // pcabo_gp_posterior with a covariance: V (NPcap x max_q), then cov (max_q^2); allocated
+                                         // by the first such call, kept until destroy
   char *dRegion = nullptr, *hRegion = nullptr;   // the two allocations everything above / below is carved from
   size_t region_bytes = 0, hregion_bytes = 0;
   bool in_batch = false; int batch_index = 0;
@@ -501,6 +503,7 @@ static void ctx_teardown(pcabo_ctx* ctx) {
     if (ctx->dMail) (void)hipFree(ctx->dMail);
     if (ctx->dPairs) (void)hipFree(ctx->dPairs);
   }
+  if (ctx->dPostV) (void)hipFree(ctx->dPostV);
   if (ctx->evBounds) (void)hipEventDestroy(ctx->evBounds);
   if (ctx->evPca) (void)hipEventDestroy(ctx->evPca);
   if (ctx->evZn) (void)hipEventDestroy(ctx->evZn);
@@ -1253,6 +1256,49 @@ int pcabo_logei(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maxi
   return pcabo_acq_eval(ctx, Xq, q, best_f, maximize, PCABO_ACQ_LOG_EI, val, grad);
 }
 
+// ---- posterior queries (DESIGN.md "GP posterior queries") -------------------------------------------------------------------
+// The scoring launches up to the scalar chain, then mean and variance per query and, on request, the joint covariance
+// (kernels_post.hip).  The queries go straight from the caller's array to dXq and the results straight from the device to the
+// caller's arrays: of the context's state only dXq, dKS and dPartial are written, which every evaluation writes before it reads.
+// No sequence number is taken, no ticket touched, the second stream not used.
+static const char* post_arg_error(const double* Xq, int q, int max_q, int flags, bool any_out) {
+  if (!Xq) return "Xq is required";
+  if (q < 1 || q > max_q) return "q must lie in 1 .. max_q";
+  if (!any_out) return "mean, var and cov are all NULL";
+  if (flags & ~(int)PCABO_POST_OBS_NOISE) return "unknown flag bits";
+  return nullptr;
+}
+// doubles of a context's (or of one run's) V block; its cov block (max_q^2) lies behind it
+static size_t post_v_doubles(const pcabo_ctx* c) { return (size_t)c->NPcap * c->max_q; }
+// mean | variance | unfloored variance of a call with q queries: behind the q S records of the scoring in dPartial, whose
+// capacity (max_q NPcap / 16 records) is four times what the 64-row blocks of the GEMM route ever use
+static double* post_out(const pcabo_ctx* c, int NP, int q) { return c->dPartial + (size_t)q * (NP / 64) * PCABO_PSTRIDE; }
+
+int pcabo_gp_posterior(pcabo_ctx* ctx, const double* Xq, int q, int flags, double* mean, double* var, double* cov) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (const char* why = post_arg_error(Xq, q, ctx->max_q, flags, mean || var || cov))
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior: %s", why);
+  if (ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior: a conditioning is in flight, call pcabo_gp_condition_end first%s", "");
+  if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior: no conditioned GP, call pcabo_gp_condition first%s", "");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (cov && !ctx->dPostV) HIPCHK(dalloc(&ctx->dPostV, post_v_doubles(ctx) + (size_t)ctx->max_q * ctx->max_q));
+  hipStream_t s = ctx->stream;
+  const bool host = ctx->ptr_mode == PCABO_PTR_HOST;
+  const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  HIPCHK(hipMemcpyAsync(ctx->dXq, Xq, (size_t)q * ctx->k * sizeof(double), in, s));
+  const AcqParams p = make_params(ctx, 0.0, 1, PCABO_ACQ_UCB, 0);      // (the kernels read 1 / lengthscale and the kernel code)
+  const GpModel m = gp_model(ctx);
+  double* post = post_out(ctx, ctx->NP, q);
+  double* dcov = cov ? ctx->dPostV + post_v_doubles(ctx) : nullptr;
+  launch_posterior(s, ctx->dXq, q, m, p, ctx->noise, flags & PCABO_POST_OBS_NOISE, ctx->dKS, ctx->dPartial, post, cov ? ctx->dPostV : nullptr, dcov);
+  if (mean) HIPCHK(hipMemcpyAsync(mean, post, (size_t)q * sizeof(double), out, s));
+  if (var) HIPCHK(hipMemcpyAsync(var, post + q, (size_t)q * sizeof(double), out, s));
+  if (cov) HIPCHK(hipMemcpyAsync(cov, dcov, (size_t)q * q * sizeof(double), out, s));
+  HIPCHK(wait_stream(s));
+  HIPCHK(hipGetLastError());
+  return PCABO_OK;
+}
+
 // ---- resident acquisition kernel: host side of the mailbox ---------------------------------------------------------
 // One round: all cap*k coordinate pairs get the round's tag (coordinates of queries that are no longer active are
 // whatever is left in hXq), then one control pair per query (1 = evaluate, 0 = leave for good).  A pair leaves in one 16-byte store and
@@ -1626,6 +1672,8 @@ struct pcabo_batch {
   // debug record of the last optimise call on the device path (pcabo_debug_batch_lbfgsb_*; tests): the twin's branch counters
   // [B][groups][LBB_COUNT], or the eight doubles per group the kernel wrote [B][groups][8]
   std::vector<unsigned> dbg_branches; std::vector<double> dbg_group_out; int dbg_groups = 0;
+  char* dPost = nullptr; size_t post_vzs = 0;        // pcabo_batch_gp_posterior with a covariance: every run's V and cov block, post_vzs
+                                                     // bytes apart (one allocation, made by the first such call)
   unsigned *dOptTab = nullptr, *hOptTab = nullptr;   // launch table of the device-resident optimiser (B * 32 entries)
   int G = 0;                             // gangs = worker threads of the L-BFGS-B phase
   std::vector<hipStream_t> gstream;
@@ -1659,6 +1707,7 @@ static void batch_free(pcabo_batch* batch) {
   for (hipEvent_t e : batch->pev) if (e) (void)hipEventDestroy(e);
   if (batch->dSlab) (void)hipFree(batch->dSlab);
   if (batch->hSlab) (void)hipHostFree(batch->hSlab);
+  if (batch->dPost) (void)hipFree(batch->dPost);
   if (batch->dOptTab) (void)hipFree(batch->dOptTab);
   if (batch->hOptTab) (void)hipHostFree(batch->hOptTab);
   if (batch->stream) (void)hipStreamDestroy(batch->stream);
@@ -2255,6 +2304,51 @@ int pcabo_batch_gp_condition_end_eval_begin(pcabo_batch* batch, const double* Xq
 int pcabo_batch_gp_condition_end_eval_end(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize,
                                           int acq, double* val, int* status) {
   return batch_score_collect(batch, Xq, q, best_f, maximize, acq, val, status);
+}
+
+// pcabo_gp_posterior for the runs of a batch: one launch sequence (blockIdx.z = run), every run at its own k and - after a lock-step
+// fit - its own lengthscale and noise.  Parked runs and runs without a GP are computed with the others and not handed out.
+int pcabo_batch_gp_posterior(pcabo_batch* batch, const double* Xq, int q, int flags, double* mean, double* var, double* cov, int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (const char* why = post_arg_error(Xq, q, batch->max_q, flags, mean || var || cov))
+    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior: %s", why);
+  if (batch->gp_pending || batch->score_enqueued || batch->opt_enqueued || batch->imap_enqueued)
+    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior: a conditioning or a _begin call of this batch has not been ended%s", "");
+  if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior: no conditioned GP%s", "");
+  BHIPCHK(hipSetDevice(batch->device));
+  hipStream_t s = batch->stream;
+  const int B = batch->B, kmax = batch_max_k(batch);
+  pcabo_ctx* c0 = batch->ctx[0];
+  if (cov && !batch->dPost) {
+    batch->post_vzs = ((post_v_doubles(c0) + (size_t)batch->max_q * batch->max_q) * sizeof(double) + 255) & ~(size_t)255;
+    BHIPCHK(hipMalloc((void**)&batch->dPost, batch->post_vzs * (size_t)B));
+  }
+  BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, Xq, (size_t)q * batch->max_d * sizeof(double), (size_t)q * kmax * sizeof(double), B,
+                           hipMemcpyHostToDevice, s));
+  const AcqParams p = batch_params(batch, 1, PCABO_ACQ_UCB, 0);
+  const GpModel m = gp_model(batch, kmax);
+  const AcqBatch ab = batch_ab(batch, 0, 0);
+  double* post = post_out(c0, batch->NP, q);
+  double* dV = cov ? reinterpret_cast<double*>(batch->dPost) : nullptr;
+  double* dcov = cov ? dV + post_v_doubles(c0) : nullptr;
+  launch_posterior(s, c0->dXq, q, m, p, batch->noise, flags & PCABO_POST_OBS_NOISE, c0->dKS, c0->dPartial, post, dV, dcov, ab, batch->post_vzs, B);
+  std::vector<double> mv((size_t)B * 2 * q);
+  BHIPCHK(hipMemcpy2DAsync(mv.data(), (size_t)2 * q * sizeof(double), post, batch->zs, (size_t)2 * q * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  for (int b = 0; b < B; ++b) {
+    const bool ok = batch->active[b] && batch->ctx[b]->have_gp;
+    if (status) status[b] = ok ? PCABO_OK : PCABO_ERR_ARG;
+    if (ok && cov)
+      BHIPCHK(hipMemcpyAsync(cov + (size_t)b * q * q, batch->dPost + (size_t)b * batch->post_vzs + post_v_doubles(c0) * sizeof(double),
+                             (size_t)q * q * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  BHIPCHK(wait_stream(s));
+  BHIPCHK(hipGetLastError());
+  for (int b = 0; b < B; ++b) {
+    if (!(batch->active[b] && batch->ctx[b]->have_gp)) continue;
+    if (mean) memcpy(mean + (size_t)b * q, &mv[(size_t)b * 2 * q], (size_t)q * sizeof(double));
+    if (var) memcpy(var + (size_t)b * q, &mv[(size_t)b * 2 * q + q], (size_t)q * sizeof(double));
+  }
+  return PCABO_OK;
 }
 
 // a run's status at the start of an optimise call: parked by the caller, without a GP, or taking part

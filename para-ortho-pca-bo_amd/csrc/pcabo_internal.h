@@ -8,6 +8,7 @@
 #define PCABO_SLAB 16        // rows of R handled by one acquisition work-group
 #define PCABO_MAXD 128       // largest ambient / reduced dimension supported
 #define PCABO_TLD 66         // LDS leading dimension (doubles) of a 64x64 tile: conflict-free ds_read_b64
+#define PCABO_PSTRIDE (2 + 2 * PCABO_MAXD)   // doubles per (query, slab) partial record of the acquisition kernels: |v|^2, mu_s, two gradient parts
 
 #define PCABO_QA_MAX 416      // query coordinates that travel as kernel arguments (3.25 KB; 10 restarts x 40 dims = 400 fit).  With 448 the
                               // kernarg segment of k_acq_fast was exactly HIP's 4096-byte maximum; 416 leaves 256 bytes of head room
@@ -362,6 +363,15 @@ void launch_score(hipStream_t st, const double* Xq, int q, const GpModel& m, Acq
 // launch_score's first kernel without its mu_s sums (no alpha), and the rest of launch_score behind it: together launch_score's bits
 // (launch_score_ks_only reads the model's ZnT and bounds4 only: alpha and R may still be in the making)
 void launch_score_ks_only(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS);
+// launch_score's first kernel alone, for any q >= 1 (launch_posterior starts with it)
+void launch_score_ks(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS, double* partial,
+                     AcqBatch ab = AcqBatch(), int B = 1);
+// Posterior mean / variance / covariance at q >= 1 points (kernels_post.hip; KS and partial are the scoring's workspaces):
+// post[3 q] = mean | variance (floored) | variance before the floor; V (NP x q) and cov (q x q) both given or both null.
+// s2: the likelihood noise (a batch after its fit: read from ab.hyp); vzs: bytes between two runs' V / cov blocks.
+void launch_posterior(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double s2, int obs_noise,
+                      double* KS, double* partial, double* post, double* V, double* cov, AcqBatch ab = AcqBatch(),
+                      size_t vzs = 0, int B = 1);
 void launch_score_tail(hipStream_t st, int q, const GpModel& m, AcqParams p, const double* KS, double* partial, double* val);
 // resident mode available for this shape? (fast path + every group of the grid co-resident)
 bool acq_server_possible(int q, int n, int k, int NP);

@@ -19,6 +19,7 @@ ACQ_LOG_EI, ACQ_PI, ACQ_UCB = 0, 1, 2
 PTR_HOST, PTR_DEVICE = 0, 1
 OPT_RESIDENT, OPT_BESTF_F32, OPT_GROUP_ACQ, OPT_DEVICE_LBFGSB = 0, 1, 2, 3
 OPT_HIDDEN_TAIL = 5
+POST_OBS_NOISE = 1                              # gp_posterior: variance / covariance of an observation (likelihood noise added)
 FIT_THETA0 = (0.006737946999085467, 0.0, 0.0)   # GP fit: (noise, mean constant, raw lengthscale) of a freshly built model
 FIT_TASK_NOT_PD = -2                            # gp_fit's `task` when a trial theta could not be factored even with jitter
 PROFILE_GROUPS = ("wpca", "gram", "cholesky", "root_inverse_alpha", "acq_partial", "acq_large_batches")
@@ -52,7 +53,7 @@ EXPORTS = [
     "pcabo_gp_condition_end", "pcabo_gp_condition_end_eval", "pcabo_wpca_gp_condition_begin", "pcabo_wpca_results",
     "pcabo_gp_mll", "pcabo_gp_fit", "pcabo_gp_mll_ard", "pcabo_gp_fit_ard",
     "pcabo_acq_bounds",
-    "pcabo_acq_eval", "pcabo_logei", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
+    "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
     "pcabo_get_gram", "pcabo_lbfgsb_minimize", "pcabo_lbfgsb_set_vector_kernels", "pcabo_lbfgsb_set_sum_order", "pcabo_sobol_scramble", "pcabo_sobol_draw", "pcabo_sobol_draw_rows", "pcabo_torch_randint2", "pcabo_torch_multinomial_rows", "pcabo_boltzmann_pick_rows", "pcabo_set_profiling",
     "pcabo_get_profile", "pcabo_get_profile_calibration", "pcabo_reset_profile",
     "pcabo_batch_create", "pcabo_batch_destroy", "pcabo_batch_last_error", "pcabo_batch_ctx",
@@ -113,6 +114,8 @@ def _load() -> C.CDLL:
     lib.pcabo_acq_bounds.argtypes = [vp, vp]
     lib.pcabo_acq_eval.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp]
     lib.pcabo_logei.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, vp, vp]
+    lib.pcabo_gp_posterior.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.pcabo_batch_gp_posterior.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pcabo_optimize_acqf.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                         vp, vp, vp, ip]
     lib.pcabo_inverse_map.argtypes = [vp, vp, vp]
@@ -440,6 +443,21 @@ class Context:
                                      _ptr(g)))
         return (val, g) if grad else val
 
+    # ---- posterior queries (pcabo_gp_posterior) -------------------------------------------------
+    def gp_posterior(self, Xq, observation_noise=False, covariance=False) -> dict:
+        """What the conditioned GP predicts at Xq (q x k, reduced space): {"mean" (q,), "variance" (q,), floored at 1e-10 as
+        gpytorch's[, "covariance" (q, q), not floored]}; observation_noise adds the likelihood noise (include/pcabo.h)."""
+        Xq = _f64(Xq).reshape(-1, self.k)
+        q = Xq.shape[0]
+        mean, var = np.empty(q), np.empty(q)
+        cov = np.empty((q, q)) if covariance else None
+        self._chk(LIB.pcabo_gp_posterior(self._h, _ptr(Xq), q, POST_OBS_NOISE if observation_noise else 0, _ptr(mean), _ptr(var),
+                                         _ptr(cov)))
+        out = {"mean": mean, "variance": var}
+        if covariance:
+            out["covariance"] = cov
+        return out
+
     # ---- rows M-N -----------------------------------------------------------------------------
     def optimize_acqf(self, ics, bounds, best_f, maximize=False, acq=ACQ_LOG_EI, batch_limit=5, maxiter=200):
         """Multi-start L-BFGS-B from `ics` inside `bounds`; `best_f` as in acq_eval (ACQ_UCB: kappa).  Returns (candidates, values,
@@ -651,6 +669,28 @@ class Batch:
         self._chk(LIB.pcabo_batch_gp_condition_end_eval(self._h, _ptr(buf), q, _ptr(bf), int(bool(maximize)), int(acq),
                                                         _ptr(val), _ptr(status)))
         return val, status
+
+    def gp_posterior(self, Xq_list, observation_noise=False, covariance=False):
+        """Context.gp_posterior for every run in one launch sequence (Xq_list[b]: q x k_b, the same q for all runs; the batch's
+        conditioning has been waited for).  One dict per run, None for a run that was skipped (parked, or without a GP)."""
+        q = Xq_list[0].shape[0]
+        buf = np.zeros((self.B, q * self.max_d))
+        for b, xq in enumerate(Xq_list):
+            buf[b, : xq.size] = np.ascontiguousarray(xq, dtype=np.float64).ravel()
+        mean, var = np.zeros((self.B, q)), np.zeros((self.B, q))
+        cov = np.zeros((self.B, q, q)) if covariance else None
+        status = np.zeros(self.B, dtype=np.int32)
+        self._chk(LIB.pcabo_batch_gp_posterior(self._h, _ptr(buf), q, POST_OBS_NOISE if observation_noise else 0, _ptr(mean),
+                                               _ptr(var), _ptr(cov), _ptr(status)))
+        out = []
+        for b in range(self.B):
+            if status[b] != 0:
+                out.append(None)
+                continue
+            out.append({"mean": mean[b].copy(), "variance": var[b].copy()})
+            if covariance:
+                out[-1]["covariance"] = cov[b].copy()
+        return out
 
     # ---- opt-in GP hyperparameter fit of all runs in lock-step (pcabo_batch_gp_mll / pcabo_batch_gp_fit) -----------------
     # Both work on the inputs of the last wpca_gp_condition_begin / gp_condition_begin and leave every run conditioned at its
