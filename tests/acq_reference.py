@@ -1,0 +1,549 @@
+"""Extended-precision reference of log-EI and PI on a conditioned GP and the error units their results are judged in.
+
+No tests here: `test_acq_reference_cpu.py` proves the reference and its units on a plain numpy restatement,
+`test_gpu_acq_edges.py` judges the HIP kernels that evaluate the acquisition (`k_acq_fast`, `k_acq_fused`,
+`k_acq_group`, `k_acq_combine`, the GEMM scoring of kernels_acq.hip and `lb_eval` of kernels_lbfgsb.hip, all on the
+scalar maths of acq_math.h) by them.
+
+The reference starts from a CONDITIONED state {R, alpha, y_mean, y_std, norm_bounds}, fp64 arrays taken as exact (the
+conditioning has its own judge: gp_reference.py), so nothing of the conditioning's kappa-type factors enters.  For a
+query x, training points Z (n x k), lengthscale l:
+  xn = (x - lo) / (hi - lo),  zn likewise,  d_jc = xn_c - zn_jc,  sq_j = sum_c d_jc^2 / l^2      (the direct form)
+  ks_j = (1 + sqrt5 r + 5/3 r^2) exp(-sqrt5 r), r = sqrt(sq_j)  (Matern-5/2)   or   exp(-sq_j / 2)  (RBF)
+  cf_j: dks_j/dxn = cf_j d_j, cf_j = -5/3 (1 + sqrt5 r) exp(-sqrt5 r) / l^2   or   -ks_j / l^2
+  v = R ks,  vv = |v|^2,  mus = alpha . ks,  w = R^T v
+  A_c = sum_j alpha_j cf_j d_jc / (hi_c - lo_c),   B_c = sum_j w_j cf_j d_jc / (hi_c - lo_c)
+in `np.longdouble` (`linear()`), then per query in `mpmath` (80 digits), from the definitions and not from botorch's
+rearrangement (`scalars()`):
+  mu = y_mean + y_std mus,  var = (1 - vv) y_std^2 floored at 1e-10 (the query is then CLAMPED),  sigma = sqrt(var)
+  u = +-(mu - best_f) / sigma          (+ where maximising)
+  log-EI = log(phi(u) + u Phi(u)) + log sigma,    PI = Phi(u)
+  g_c = c_mu A_c + c_sg B_c,   c_mu = (dval/du)(+-y_std / sigma),
+  c_sg = ([log-EI] 1 / sigma - (dval/du) u / sigma)(-y_std^2 / sigma), 0 where clamped.
+For u <= -1e6 the kernels take botorch's asymptote; it is O(1 / u^2) absolute off a value of order u^2 / 2, far inside
+the unit there, so the exact value stays the reference.
+
+Error units: first-order bounds of what ANY fp64 implementation of this chain commits (eps = 2^-52), computed from
+reference quantities only - never from a run of the code under test.
+  dd_jc = 2 eps (|xn_c| + |zn_jc|) + eps |d_jc|
+  dsq_j = (2 sum_c |d_jc| dd_jc + (k + 2) eps sum_c d_jc^2) / l^2 + 3 eps sq_j
+  dks_j = |dks/dsq| dsq_j + eps |ks_j| (4 + arg),  arg = sqrt5 r  or  sq / 2  (as u_K of gp_reference)
+  dcf_j = |dcf/dsq| dsq_j + eps |cf_j| (4 + arg),  |dcf/dsq| = 25/6 exp(-sqrt5 r) / l^2  or  |ks| / 2 / l^2
+  dmus = sum |alpha_j| dks_j + (n + 2) eps sum |alpha_j ks_j|
+  dv = |R| dks + (n + 2) eps |R||ks|,   dvv = 2 sum |v_i| dv_i + (n + 2) eps vv
+  dw = |R^T| dv + (n + 2) eps |R^T||v|
+  dA_c, dB_c: the product rule over alpha_j (w_j +- dw_j), cf_j +- dcf_j, d_jc +- dd_jc, + (n + 4) eps sum of |terms|
+  dmu = y_std dmus + 2 eps (|y_mean| + |y_std mus|),   dvar = y_std^2 (dvv + eps (1 + 3 |1 - vv|))
+  dsigma = dvar / (2 sigma) + eps sigma  (0 where clamped)
+  du = (dmu + eps |mu - best_f|) / sigma + |u| dsigma / sigma + 2 eps |u|
+log-EI helper h(u) = log(phi + u Phi), by the branch of acq_math.h's `log_ei_helper` (`helper_units`):
+  u > -1:          dei = eps (phi (2 + u^2) + 3 |u| Phi + ei),  u_h = dei / ei + eps |h|,  u_dh = h' (3 eps + dei / ei)
+  -1e6 < u <= -1:  with E = erfcx(-u / sqrt2) |u| sqrt(pi / 2), 1 - E and dw = u + sqrt(2 / pi) / erfcx + 1 / u EXACT,
+                   u_h = 2 eps (u^2 / 2 + 1) + 4 eps E / (1 - E) + eps |log(1 - E)|
+                   u_dh = eps |u| + 5 eps |u| E / (1 - E) + |dw| E / (1 - E) (4 eps + (4 eps E + eps) / (1 - E) + 3 eps)
+                   (dw cancels from |u| down to 2 / |u|^3, E / (1 - E) ~ u^2: u_dh grows as 5 eps |u|^3 - that is
+                   botorch's formulation, which the kernels follow, and not a bug)
+  u <= -1e6:       u_h = 2 eps (u^2 / 2 + 2 log |u| + 2),  u_dh = 2 eps |u|
+a query whose u lies within du of a seam takes the larger unit of the two branches.
+  value: log-EI |h'| du + u_h + dsigma / sigma + eps (|log sigma| + |value|);  PI phi (du + 2 eps |u|) + 4 eps Phi
+  d(dval/du) = |d2val/du2| du + u_dh,  h'' = phi / ei - h'^2;   PI: |u| phi du + eps phi (3 + u^2)
+  dc_mu = (y_std / sigma)(d(dval/du) + |dval/du| (dsigma / sigma + 3 eps))
+  T = [log-EI] 1 / sigma - (dval/du) u / sigma,  c_sg = -T y_std^2 / sigma:
+  dT = [log-EI] (dsigma / sigma^2 + eps / sigma) + (d(dval/du) |u| + |dval/du| du + |dval/du u| (dsigma / sigma + 3 eps)) / sigma + eps |T|
+  dc_sg = (y_std^2 / sigma)(dT + |T| (dsigma / sigma + 3 eps))
+  dg_c = |c_mu| dA_c + |A_c| dc_mu + |c_sg| dB_c + |B_c| dc_sg + 2 eps (|c_mu A_c| + |c_sg B_c|)
+Underflow: as in gp_reference, an error up to 2^-1022 per element counts as none (PI and its gradient are 0 in fp64
+below u ~ -38).  `judge()` returns the worst ratio of values and of gradients; a NaN, or an error where the unit is
+0, is infinite.
+
+The module also holds the states, queries and scalars of the two test files (`make_state`, `cases`), a plain fp64 numpy
+restatement of the chain written as the kernels are (`restate`; keyword switches turn on one wrong variant each), and
+the conditions the device test relies on (`check_conditions`).
+"""
+import math
+from types import SimpleNamespace
+
+import mpmath
+import numpy as np
+
+from gp_reference import _ratio, hp_exp
+from wpca_reference import EPS, f64, hp, hp_sqrt
+
+LOG_EI, PI = 0, 1
+LENGTHSCALE, NOISE = 0.6931471805599453, 0.006737946999085467      # the defaults of gp_condition
+FLOOR = 1e-10                        # gpytorch's min_variance
+Q = 130                              # queries per state
+PREFIXES = (5, 6, 32, 40, 130)       # what the evaluation paths take of them
+VAR_MARGIN = 32.0                    # no variance within this many dvar of the floor
+SEAM_QUERY = 4                       # the query whose u the seam incumbents are computed for (its duplicate: 3)
+FIXED_QUERIES = (0, 1, 2, 3, SEAM_QUERY)      # placed by hand in make_state, never redrawn
+MP = mpmath.mp.clone()
+MP.dps = 80
+_S5 = math.sqrt(5.0)
+
+# state -> (n, k, scale of y, kernel, options): the smallest shapes that reach each code form.  A .. E are the states
+# of test_gpu_ucb.py, with the same seeds.
+STATES = {
+    "A": (9, 1, 1.0, "matern52", {}),           # k_acq_fast, NP = 64, one component
+    "B": (70, 6, 1.0, "matern52", {}),          # k_acq_fast, NP = 128, 16-row slabs
+    "B-rbf": (70, 6, 1.0, "rbf", {}),
+    "C": (449, 10, 1.0, "matern52", {}),        # k_acq_fast, NP = 512 (NB = 8), 32-row slabs; lb_eval with 2 row parts
+    "D": (50, 41, 1.0, "matern52", {}),         # k_acq_fused (k > 40); host-paced paths only
+    "E": (30, 3, 1e-7, "matern52", {}),         # every query's variance under the 1e-10 floor
+    "n64": (64, 1, 1.0, "matern52", {}),        # NB = 1, an exact block
+    "n65": (65, 3, 1.0, "matern52", {}),        # NB = 2 .. 7: every live k_acq_fast<SLAB, NB>, k cycling 1, 3, 8, 9, 40
+    "n129": (129, 8, 1.0, "matern52", {}),
+    "n193": (193, 9, 1.0, "matern52", {}),
+    "n257": (257, 40, 1.0, "matern52", {}),
+    "n321": (321, 1, 1.0, "matern52", {}),
+    "n385": (385, 3, 1.0, "matern52", {}),
+    "n513": (513, 6, 1.0, "matern52", {}),      # NP = 576 > 512: the generic kernel with 32-row slabs
+    "k128": (100, 128, 1.0, "matern52", {}),    # k = PCABO_MAXD: the group kernel's widened LDS region
+    "user": (100, 5, 1.0, "rbf", {"user_bounds": True, "lengthscale": 0.4, "noise": 1e-3}),
+    "mixed": (30, 3, 1.2e-6, "matern52", {}),   # like E; clamped and free variances among the first 32 queries
+    "T": (64, 3, 1.0, "matern52", {"tail_inputs": True}),     # Z and y of test_log_ei_tail_branches
+}
+SMALL_STATES = [s for s in STATES if STATES[s][0] <= 130]
+
+
+# ---- states and queries ------------------------------------------------------------------------------------------
+def search_box(Z):
+    """The acquisition's search box of the points Z (include/pcabo.h, `pcabo_acq_bounds`), 2 x k."""
+    zmin, zmax = Z.min(axis=0), Z.max(axis=0)
+    b = np.vstack([zmin - 0.5 * (zmax - zmin), zmax + 0.5 * (zmax - zmin)])
+    narrow = b[1] - b[0] < 0.1
+    mid = (b[0] + b[1]) / 2
+    b[0], b[1] = np.where(narrow, mid - 0.05, b[0]), np.where(narrow, mid + 0.05, b[1])
+    return b
+
+
+def make_state(name):
+    """Seeded inputs of a state: the training points and values of test_gpu_ucb.py's recipe and Q queries, uniform in
+    the search box widened by 20 %, with - inside every prefix the paths take - two training points (sq = 0 exactly),
+    a training point + 1e-9 and a duplicated query."""
+    n, k, yscale, kernel, opt = STATES[name]
+    if opt.get("tail_inputs"):
+        rng = np.random.default_rng(3)
+        Z, y = rng.uniform(-1, 1, size=(n, k)), rng.normal(size=n)
+    else:
+        rng = np.random.default_rng(1000 + 10 * n + k)
+        Z = rng.normal(size=(n, k))
+        y = (rng.normal(size=n) * 30.0 + 200.0) * yscale
+    st = SimpleNamespace(name=name, n=n, k=k, Z=np.ascontiguousarray(Z), y=y, kernel=kernel, norm_bounds=None,
+                         lengthscale=opt.get("lengthscale", LENGTHSCALE), noise=opt.get("noise", NOISE))
+    if opt.get("user_bounds"):
+        st.norm_bounds = np.vstack([Z.min(axis=0) - 1.0, Z.max(axis=0) + 2.0])
+    box = search_box(Z)
+    wide = np.vstack([box[0] - 0.1 * (box[1] - box[0]), box[1] + 0.1 * (box[1] - box[0])])
+    st.wide = wide
+    st.qrng = np.random.default_rng(5000 + 10 * n + k)
+    X = st.qrng.uniform(wide[0], wide[1], size=(Q, k))
+    X[0], X[1] = Z[0], Z[1]
+    X[2] = Z[2 % n] + 1e-9
+    X[3] = X[4]
+    st.X = X
+    st.redrawn = []
+    return st
+
+
+def restated_state(st):
+    """The conditioned state of `st` from gp_reference's fp64 restatement (numpy's Cholesky): what the CPU proof uses
+    where the device test reads the device's own state."""
+    import gp_reference as G
+    case = SimpleNamespace(Z=st.Z, y=st.y, lengthscale=st.lengthscale, noise=st.noise, norm_bounds=st.norm_bounds,
+                           kernel="rbf" if st.kernel == "rbf" else "matern")
+    r = G.restate(case)
+    return {"R": r.R, "alpha": r.alpha, "y_mean": r.y_mean, "y_std": r.y_std, "norm_bounds": r.norm_bounds}
+
+
+_PREPARED = {}
+
+
+def prepared(name):
+    """(state inputs, restated conditioned state, linear reference on it), once per process.  Queries whose variance
+    lies within VAR_MARGIN dvar of the floor are REDRAWN here (never skipped), deterministically, so that both test
+    files see the same queries."""
+    if name not in _PREPARED:
+        st = make_state(name)
+        gs = restated_state(st)
+        lin = linear(st, gs, st.X)
+        for _ in range(20):
+            near = [i for i in np.flatnonzero(near_floor(lin)) if i not in FIXED_QUERIES]
+            if not near:
+                break
+            for i in near:
+                st.X[i] = st.qrng.uniform(st.wide[0], st.wide[1])
+                st.redrawn.append(int(i))
+            lin = linear(st, gs, st.X)
+        _PREPARED[name] = (st, gs, lin)
+    return _PREPARED[name]
+
+
+# ---- the reference: linear algebra in long double ----------------------------------------------------------------
+def _cov(sq, kernel, ls):
+    """ks, cf, |dks/dsq|, |dcf/dsq|, arg of a scaled squared distance (any float type)."""
+    il2 = 1 / (hp(ls) * hp(ls))
+    if kernel == "rbf":
+        ks = hp_exp(-sq / 2)
+        return ks, -ks * il2, ks / 2, ks / 2 * il2, sq / 2
+    r, s5 = hp_sqrt(sq), hp_sqrt(hp(5.0))
+    e = hp_exp(-s5 * r)
+    ks = (1 + s5 * r + hp(5.0) / hp(3.0) * sq) * e
+    cf = -(hp(5.0) / hp(3.0)) * (1 + s5 * r) * e * il2
+    return ks, cf, hp(5.0) / hp(6.0) * (1 + s5 * r) * e, hp(25.0) / hp(6.0) * e * il2, s5 * r
+
+
+def linear(st, gs, X):
+    """Everything of the chain that is linear algebra, for the queries X (q x k) on the conditioned state `gs`, in
+    long double, with its units in fp64."""
+    X = np.asarray(X, dtype=np.float64)
+    q, k, n, ls = X.shape[0], st.k, st.n, float(st.lengthscale)
+    R, alpha = hp(np.tril(gs["R"])), hp(gs["alpha"])
+    lo, hi = hp(gs["norm_bounds"][0]), hp(gs["norm_bounds"][1])
+    span = hi - lo
+    xn, zn = (hp(X) - lo) / span, (hp(st.Z) - lo) / span
+    d = xn[:, None, :] - zn[None, :, :]                                         # q x n x k
+    ssq = (d * d).sum(axis=2)
+    sq = ssq / (hp(ls) * hp(ls))
+    ks, cf, dks_dsq, dcf_dsq, arg = _cov(sq, st.kernel, ls)
+    v = ks @ R.T                                                                # v_i = sum_j R_ij ks_j
+    vv = (v * v).sum(axis=1)
+    mus = ks @ alpha
+    w = v @ R                                                                   # w_j = sum_i R_ij v_i
+    A = ((alpha[None, :] * cf)[:, :, None] * d).sum(axis=1) / span
+    B = ((w * cf)[:, :, None] * d).sum(axis=1) / span
+    # units, fp64
+    aR, aal = np.abs(f64(R)), np.abs(f64(alpha))
+    D, CF, KS, W, V = np.abs(f64(d)), np.abs(f64(cf)), np.abs(f64(ks)), np.abs(f64(w)), np.abs(f64(v))
+    dd = 2.0 * EPS * (np.abs(f64(xn))[:, None, :] + np.abs(f64(zn))[None, :, :]) + EPS * D
+    dsq = (2.0 * (D * dd).sum(axis=2) + (k + 2) * EPS * f64(ssq)) / (ls * ls) + 3.0 * EPS * f64(sq)
+    dks = f64(dks_dsq) * dsq + EPS * KS * (4.0 + f64(arg))
+    dcf = f64(dcf_dsq) * dsq + EPS * CF * (4.0 + f64(arg))
+    dmus = dks @ aal + (n + 2) * EPS * (KS @ aal)
+    dv = dks @ aR.T + (n + 2) * EPS * (KS @ aR.T)
+    dvv = 2.0 * (V * dv).sum(axis=1) + (n + 2) * EPS * f64(vv)
+    dw = dv @ aR + (n + 2) * EPS * (V @ aR)
+    sp = f64(span)
+
+    def d_sum(coef, dcoef):
+        """unit of sum_j coef_j cf_j d_jc / span_c"""
+        t = (coef * CF)[:, :, None] * D
+        first = (dcoef * CF + coef * dcf)[:, :, None] * D + (coef * CF)[:, :, None] * dd
+        return (first.sum(axis=1) + (n + 4) * EPS * t.sum(axis=1)) / sp
+
+    dA = d_sum(np.broadcast_to(aal, (q, n)), np.zeros((q, n)))
+    dB = d_sum(W, dw)
+    return SimpleNamespace(q=q, k=k, n=n, vv=vv, mus=mus, A=A, B=B, dvv=dvv, dmus=dmus, dA=dA, dB=dB,
+                           y_mean=float(gs["y_mean"]), y_std=float(gs["y_std"]), sq_min=f64(sq).min(axis=1))
+
+
+def _posterior(lin):
+    """fp64 views of mean, unfloored variance, its unit and the floored sigma."""
+    ym, ysd = lin.y_mean, lin.y_std
+    mu = ym + ysd * f64(lin.mus)
+    var = f64((1 - lin.vv) * (hp(ysd) * hp(ysd)))
+    dvar = ysd * ysd * (lin.dvv + EPS * (1.0 + 3.0 * np.abs(f64(1 - lin.vv))))
+    return mu, var, dvar, np.sqrt(np.maximum(var, FLOOR))
+
+
+def near_floor(lin):
+    """Queries whose variance lies within VAR_MARGIN dvar of the floor: which side they fall on is rounding's choice."""
+    _, var, dvar, _ = _posterior(lin)
+    return np.abs(var - FLOOR) <= VAR_MARGIN * dvar
+
+
+# ---- the reference: scalar chain in mpmath -----------------------------------------------------------------------
+def _mpf(x):
+    """long double (or double) -> mpf, exactly."""
+    x = hp(x)
+    head = float(x)
+    return MP.mpf(head) + MP.mpf(float(x - hp(head)))
+
+
+def _ld(x):
+    """mpf -> long double, to its precision."""
+    head = float(x)
+    return hp(head) + hp(float(x - MP.mpf(head)))
+
+
+def _exact_helper(u):
+    """phi, Phi, ei = phi + u Phi, h = log ei, h' = Phi / ei, h'' = phi / ei - h'^2 of an mpf u."""
+    phi = MP.exp(-u * u / 2) / MP.sqrt(2 * MP.pi)
+    Phi = MP.erfc(-u / MP.sqrt(2)) / 2
+    ei = phi + u * Phi
+    dh = Phi / ei
+    return phi, Phi, ei, MP.log(ei), dh, phi / ei - dh * dh
+
+
+def helper_units(u, du=0.0):
+    """(h, h', h'', u_h, u_dh) of log_ei_helper at the double u, known to within du: the units of every branch that
+    [u - du, u + du] reaches, the larger of them."""
+    um = MP.mpf(u)
+    phi, Phi, ei, h, dh, d2h = _exact_helper(um)
+    au = abs(u)
+    branches = set()
+    for t in (u - du, u, u + du):
+        branches.add(0 if t > -1.0 else (1 if t > -1e6 else 2))
+    u_h = u_dh = 0.0
+    if 0 in branches:
+        dei = EPS * (float(phi) * (2.0 + u * u) + 3.0 * au * float(Phi) + float(ei))
+        rel = float(MP.mpf(dei) / ei)
+        u_h, u_dh = max(u_h, rel + EPS * abs(float(h))), max(u_dh, float(dh) * (3.0 * EPS + rel))
+    if 1 in branches:
+        x = -um / MP.sqrt(2)
+        ex = MP.exp(x * x) * MP.erfc(x)
+        E = ex * abs(um) * MP.sqrt(MP.pi / 2)
+        one_m = 1 - E
+        dw = um + MP.sqrt(2 / MP.pi) / ex + 1 / um
+        r = float(E / one_m)
+        u_h = max(u_h, 2.0 * EPS * (u * u / 2.0 + 1.0) + 4.0 * EPS * r + EPS * abs(float(MP.log(one_m))))
+        u_dh = max(u_dh, EPS * au + 5.0 * EPS * au * r
+                   + abs(float(dw)) * r * (4.0 * EPS + float((4.0 * EPS * E + EPS) / one_m) + 3.0 * EPS))
+    if 2 in branches:
+        u_h = max(u_h, 2.0 * EPS * (u * u / 2.0 + 2.0 * math.log(au) + 2.0))
+        u_dh = max(u_dh, 2.0 * EPS * au)
+    return h, dh, d2h, u_h, u_dh
+
+
+def scalars(lin, best_f, maximize, acq):
+    """Values and gradients of the acquisition at the queries of `lin` with their units."""
+    q, k = lin.q, lin.k
+    ym, ysd, sgn = lin.y_mean, lin.y_std, (1.0 if maximize else -1.0)
+    value, u_value = hp(np.zeros(q)), np.zeros(q)
+    grad, u_grad = hp(np.zeros((q, k))), np.zeros((q, k))
+    u_out, clamped_out = np.zeros(q), np.zeros(q, dtype=bool)
+    aA, aB = np.abs(f64(lin.A)), np.abs(f64(lin.B))
+    for i in range(q):
+        mus, vv = _mpf(lin.mus[i]), _mpf(lin.vv[i])
+        mu = MP.mpf(ym) + MP.mpf(ysd) * mus
+        var = (1 - vv) * MP.mpf(ysd) * MP.mpf(ysd)
+        clamped = not var >= MP.mpf(FLOOR)
+        if clamped:
+            var = MP.mpf(FLOOR)
+        sigma = MP.sqrt(var)
+        u = MP.mpf(sgn) * (mu - MP.mpf(best_f)) / sigma
+        uf, sf = float(u), float(sigma)
+        dmu = ysd * lin.dmus[i] + 2.0 * EPS * (abs(ym) + abs(ysd * float(mus)))
+        dvar = ysd * ysd * (lin.dvv[i] + EPS * (1.0 + 3.0 * abs(float(1 - vv))))
+        dsig = 0.0 if clamped else dvar / (2.0 * sf) + EPS * sf
+        du = (dmu + EPS * abs(float(mu - MP.mpf(best_f)))) / sf + abs(uf) * dsig / sf + 2.0 * EPS * abs(uf)
+        if acq == LOG_EI:
+            _, _, _, u_h, u_dh = helper_units(uf, du)          # the units at the double nearest u,
+            _, _, _, h, D, D2 = _exact_helper(u)               # the function at u itself
+            val = h + MP.log(sigma)
+            u_val = abs(float(D)) * du + u_h + dsig / sf + EPS * (abs(math.log(sf)) + abs(float(val)))
+            dD = abs(float(D2)) * du + u_dh
+            P = 1 / sigma
+        else:
+            phi, Phi = MP.exp(-u * u / 2) / MP.sqrt(2 * MP.pi), MP.erfc(-u / MP.sqrt(2)) / 2
+            val, D = Phi, phi
+            u_val = float(phi) * (du + 2.0 * EPS * abs(uf)) + 4.0 * EPS * float(Phi)
+            dD = abs(uf) * float(phi) * du + EPS * float(phi) * (3.0 + uf * uf)
+            P = MP.mpf(0)
+        Df = abs(float(D))
+        c_mu = D * MP.mpf(sgn) * MP.mpf(ysd) / sigma
+        dc_mu = (ysd / sf) * (dD + Df * (dsig / sf + 3.0 * EPS))
+        if clamped:
+            c_sg, dc_sg = MP.mpf(0), 0.0
+        else:
+            T = P - D * u / sigma
+            c_sg = T * (-(MP.mpf(ysd) * MP.mpf(ysd)) / sigma)
+            dT = ((dsig / (sf * sf) + EPS / sf) if acq == LOG_EI else 0.0) \
+                + (dD * abs(uf) + Df * du + Df * abs(uf) * (dsig / sf + 3.0 * EPS)) / sf + EPS * abs(float(T))
+            dc_sg = (ysd * ysd / sf) * (dT + abs(float(T)) * (dsig / sf + 3.0 * EPS))
+        cm, cs = _ld(c_mu), _ld(c_sg)
+        value[i], u_value[i] = _ld(val), u_val
+        grad[i] = cm * lin.A[i] + cs * lin.B[i]
+        acm, acs = abs(float(cm)), abs(float(cs))
+        u_grad[i] = acm * lin.dA[i] + aA[i] * dc_mu + acs * lin.dB[i] + aB[i] * dc_sg + 2.0 * EPS * (acm * aA[i] + acs * aB[i])
+        u_out[i], clamped_out[i] = uf, clamped
+    return SimpleNamespace(value=value, grad=grad, u_value=u_value, u_grad=u_grad, u=u_out, clamped=clamped_out)
+
+
+def judge(ref, values, grads=None, rows=None):
+    """(worst ratio of the values, worst ratio of the gradient components) of an implementation's results at the first
+    len(values) queries of `ref` (or at `rows`); NaN and an error where the unit is 0 are infinite."""
+    rows = slice(0, len(values)) if rows is None else rows
+    rv = _ratio(hp(values) - ref.value[rows], ref.u_value[rows])
+    rg = 0.0 if grads is None else _ratio(hp(grads) - ref.grad[rows], ref.u_grad[rows])
+    return rv, rg
+
+
+def well_conditioned(ref):
+    """Queries at which two fp64 evaluations of log-EI's gradient can agree to 1e-10 whatever their summation order.
+    In the middle branch of `log_ei_helper` each evaluation of h' carries 5 eps |u|^3 of rounding noise on |h'| ~ |u|
+    (u_dh above), so two of them differ by up to 10 eps u^2 relative: at |u| <= 67 that is 1e-11, a tenth of the bound,
+    the rest of which is left to the sums as everywhere else.  The tail branch (h' = -u - 2 / u, no cancellation)
+    qualifies where u is decisively inside it.  From the reference's u alone."""
+    return (np.abs(ref.u) <= 67.0) | (ref.u < -1e6 - 1.0)
+
+
+def agreement(ref, g_a, g_b):
+    """Worst |g_a - g_b| / u_grad over the components of two implementations' gradients at the first len(g_a) queries."""
+    return _ratio(hp(g_a) - hp(g_b), ref.u_grad[:len(g_a)])
+
+
+# ---- the scalars of a state --------------------------------------------------------------------------------------
+def cases(lin):
+    """[(label, acq, maximize, best_f)]: per direction log-EI at `near`, `mid` (50 s_y away) and `far` (1e9 s_y) as
+    tools/gpu_acq_paths_hashes.py chooses them, log-EI at three seam incumbents that put the u of query SEAM_QUERY at
+    -1, -1 - 1e-6 and -1e6 to rounding, and PI at `near` and `3sigma`."""
+    mu, _, _, sigma = _posterior(lin)
+    ym, ysd = lin.y_mean, lin.y_std
+    out = []
+    for maximize in (0, 1):
+        sgn = 1.0 if maximize else -1.0
+        near = float(np.median(mu[:32]))
+        inc = {"near": near, "3sigma": float(near + sgn * 3.0 * np.median(sigma[:32])),
+               "mid": float(ym + sgn * 50.0 * ysd), "far": float(ym + sgn * 1e9 * ysd)}
+        for tag, t in (("seam-1", -1.0), ("seam-1-1e-6", -1.0 - 1e-6), ("seam-1e6", -1e6)):
+            inc[tag] = float(mu[SEAM_QUERY] - sgn * t * sigma[SEAM_QUERY])        # u = sgn (mu - best) / sigma = t
+        out += [("log_ei,%d,%s" % (maximize, t), LOG_EI, maximize, inc[t])
+                for t in ("near", "mid", "far", "seam-1", "seam-1-1e-6", "seam-1e6")]
+        out += [("pi,%d,%s" % (maximize, t), PI, maximize, inc[t]) for t in ("near", "3sigma")]
+    return out
+
+
+def u_of(lin, best_f, maximize):
+    """u of every query in fp64 (for the conditions; the judged u is that of `scalars`)."""
+    mu, _, _, sigma = _posterior(lin)
+    return (1.0 if maximize else -1.0) * (mu - best_f) / sigma
+
+
+def check_conditions(name, st, lin):
+    """What the device test relies on, as a list of violations (empty: all hold)."""
+    bad = []
+    X, Z = st.X, st.Z
+    if not (np.array_equal(X[0], Z[0]) and np.array_equal(X[1], Z[1]) and np.array_equal(X[3], X[4])):
+        bad.append("the hand-placed queries are not in place")
+    if not (lin.sq_min[0] == 0.0 and lin.sq_min[1] == 0.0 and 0.0 < lin.sq_min[2] < 1e-12):
+        bad.append(("sq of the training-point queries", lin.sq_min[:3]))
+    if near_floor(lin).any():
+        bad.append(("variance within %g dvar of the floor" % VAR_MARGIN, np.flatnonzero(near_floor(lin))))
+    _, var, _, _ = _posterior(lin)
+    cl = var[:32] < FLOOR
+    if name == "E" and not cl.all():
+        bad.append("state E has free variances")
+    if name == "mixed" and not (cl.sum() >= 4 and (~cl).sum() >= 4 and cl[:5].any() and (~cl[:5]).any()):
+        bad.append(("state mixed is not mixed", int(cl.sum())))
+    if name not in ("E", "mixed") and cl.any():
+        bad.append("a clamped variance outside E and mixed")
+    for label, _, maximize, best_f in cases(lin):
+        u, tag = u_of(lin, best_f, maximize)[:32], label.split(",")[2]
+        ok = {"near": (u > -0.5).any(), "mid": ((u < -2.0) & (u > -1e5)).all(), "far": (u < -1e7).all(),
+              "3sigma": ((u < -1.0) & (u > -6.0)).any(), "seam-1": abs(u[SEAM_QUERY] + 1.0) < 1e-9,
+              "seam-1-1e-6": abs(u[SEAM_QUERY] + 1.0 + 1e-6) < 1e-9 and u[SEAM_QUERY] < -1.0,
+              "seam-1e6": abs(u[SEAM_QUERY] + 1e6) < 1e-3}[tag]
+        if not ok:
+            bad.append((label, "u does not reach its branch", float(u[SEAM_QUERY])))
+    return bad
+
+
+# ---- the chain in plain fp64, as the kernels write it -------------------------------------------------------------
+def helper_restated(u, sqrt_pi_2=1.2533141373155003, tail_from=None):
+    """`log_ei_helper` of acq_math.h on a numpy array, through scipy's erfcx / erfc / log1p: (h, h').  Wrong variants:
+    sqrt(pi / 2) truncated; the tail asymptote taken for tail_from < u < -1 as well."""
+    from scipy.special import erfc, erfcx
+    u = np.asarray(u, dtype=np.float64)
+    h, dh = np.empty_like(u), np.empty_like(u)
+    with np.errstate(all="ignore"):
+        up = u > -1.0
+        tail = u <= -1e6
+        if tail_from is not None:
+            tail = tail | ((u > tail_from) & (u <= -1.0))
+        mid = ~up & ~tail
+        x = u[up]
+        phi = 0.3989422804014327 * np.exp(-0.5 * x * x)
+        Phi = 0.5 * erfc(-0.7071067811865476 * x)
+        ei = phi + x * Phi
+        h[up], dh[up] = np.log(ei), Phi / ei
+        x = u[mid]
+        log_phi = -0.5 * (x * x + 1.8378770664093453)
+        ex = erfcx(-0.7071067811865476 * x)
+        E = (ex * np.abs(x)) * sqrt_pi_2
+        dw = (x + 0.7978845608028654 / ex) + 1.0 / x
+        h[mid], dh[mid] = log_phi + np.log1p(-E), -x - dw * E / (1.0 - E)
+        x = u[tail]
+        h[tail], dh[tail] = -0.5 * (x * x + 1.8378770664093453) - 2.0 * np.log(np.abs(x)), -x - 2.0 / x
+    return h, dh
+
+
+def restate(st, gs, X, best_f, maximize, acq, coef53=5.0 / 3.0, drop_last_v=False, sqrt_pi_2=1.2533141373155003,
+            cmu_unsigned=False, csg_keep_clamped=False, tail_from=None, pi_grad_Phi=False):
+    """numpy fp64 restatement of the chain: direct distance, R @ ks, the three branches of `log_ei_helper`.  Each
+    keyword switches on one wrong variant: the 5/3 of the Matern radial factor (pass a float32), the last row of v left
+    out of |v|^2, sqrt(pi / 2) truncated in the middle branch, c_mu without its sign, c_sg not zeroed at a clamped
+    variance, the tail asymptote in tail_from < u < -1, PI's gradient with Phi in place of phi."""
+    from scipy.special import erfc
+    X = np.asarray(X, dtype=np.float64)
+    R, alpha = np.tril(gs["R"]), np.asarray(gs["alpha"], dtype=np.float64)
+    lo, hi = gs["norm_bounds"][0], gs["norm_bounds"][1]
+    ym, ysd, ls = float(gs["y_mean"]), float(gs["y_std"]), float(st.lengthscale)
+    xn, zn = (X - lo) / (hi - lo), (st.Z - lo) / (hi - lo)
+    d = xn[:, None, :] - zn[None, :, :]
+    sq = (d * d).sum(axis=2) * ((1.0 / ls) * (1.0 / ls))
+    if st.kernel == "rbf":
+        ks = np.exp(-0.5 * sq)
+        rf = -ks
+    else:
+        dist = np.sqrt(np.maximum(sq, 1e-30))
+        e = np.exp(-_S5 * dist)
+        ks = ((_S5 * dist + 1.0) + (5.0 / 3.0) * (dist * dist)) * e
+        rf = -float(coef53) * (1.0 + _S5 * dist) * e
+    cf = rf * (1.0 / ls) * (1.0 / ls)
+    v = ks @ R.T
+    vv = (v[:, :-1] * v[:, :-1]).sum(axis=1) if drop_last_v else (v * v).sum(axis=1)
+    mus = ks @ alpha
+    w = v @ R
+    gm = np.einsum("qj,qjc->qc", alpha[None, :] * cf, d)
+    gs_ = np.einsum("qj,qjc->qc", w * cf, d)
+    mu = ym + ysd * mus
+    var = (1.0 - vv) * (ysd * ysd)
+    clamped = ~(var >= FLOOR)
+    sigma = np.sqrt(np.where(clamped, FLOOR, var))
+    sgn = 1.0 if maximize else -1.0
+    u = (mu - best_f) / sigma * sgn
+    with np.errstate(all="ignore"):
+        if acq == LOG_EI:
+            h, dv_du = helper_restated(u, sqrt_pi_2, tail_from)
+            val, dv_dsig = h + np.log(sigma), 1.0 / sigma
+        else:
+            val = 0.5 * erfc(-0.7071067811865476 * u)
+            dv_du = val if pi_grad_Phi else 0.3989422804014327 * np.exp(-0.5 * u * u)
+            dv_dsig = 0.0
+        c_mu = dv_du * (1.0 if cmu_unsigned else sgn) * ysd / sigma
+        c_sg = (dv_dsig - dv_du * u / sigma) * (-(ysd * ysd) / sigma)
+        if not csg_keep_clamped:
+            c_sg = np.where(clamped, 0.0, c_sg)
+        grad = (c_mu[:, None] * gm + c_sg[:, None] * gs_) / (hi - lo)
+    return val, grad
+
+
+def _float32_strength(ref):
+    """A wrong 5/3 scales cf, and with it every gradient, by 1 + rho exactly: the variant stands rho |g| / u_grad above the
+    reference, no more.  The largest such ratio over the queries, from reference quantities alone."""
+    rho = abs(float(np.float32(5.0 / 3.0)) / (5.0 / 3.0) - 1.0)
+    pos = ref.u_grad > 0.0
+    return float((rho * np.abs(f64(ref.grad))[pos] / ref.u_grad[pos]).max())
+
+
+# variant -> (keyword arguments of restate, what it damages, which cases it applies to[, the strength at which the
+# reference itself says the variant can be seen])
+# "tail asymptote in -1.5 < u < -1" stands for the issue's "wrong branch taken in -1.5 < u < -1".  Swapping the two
+# ACCURATE formulas of log_ei_helper there is no error: either is within its unit on both sides of u = -1 (at u = -1.3
+# the direct form loses a factor 4 to the cancellation of phi + u Phi, the erfcx form as much to E / (1 - E) = 2.8),
+# which is what the seam rule - the larger unit of the two branches - expresses, so no unit can or should see it.  The
+# only branch that is wrong there is the tail's: a gross error (1e10 units), which shows that a misplaced branch is
+# seen, not how sharp the units are at the seam - that is shown by the truncated sqrt(pi / 2).
+WRONG = {
+    "5/3 of the radial factor as a float32": (dict(coef53=np.float32(5.0 / 3.0)), "grad",
+                                              lambda st, label, ref: st.kernel != "rbf", _float32_strength),
+    "last row of v left out of |v|^2": (dict(drop_last_v=True), "any", lambda st, label, ref: not ref.clamped.all()),
+    "sqrt(pi/2) truncated to 8 digits": (dict(sqrt_pi_2=1.2533141), "value",
+                                         lambda st, label, ref: label.startswith("log_ei") and label.endswith("mid")),
+    "c_mu without its sign": (dict(cmu_unsigned=True), "grad", lambda st, label, ref: label.split(",")[1] == "0"),
+    "c_sg kept at a clamped variance": (dict(csg_keep_clamped=True), "grad", lambda st, label, ref: ref.clamped.any()),
+    "tail asymptote in -1.5 < u < -1": (dict(tail_from=-1.5), "value",
+                                        lambda st, label, ref: label.startswith("log_ei") and "seam-1-1e-6" in label),
+    "PI's gradient with Phi for phi": (dict(pi_grad_Phi=True), "grad", lambda st, label, ref: label.startswith("pi")),
+}
