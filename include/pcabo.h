@@ -220,6 +220,25 @@ int pcabo_logei(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maxi
 enum { PCABO_POST_OBS_NOISE = 1 };
 int pcabo_gp_posterior(pcabo_ctx* ctx, const double* Xq, int q, int flags, double* mean, double* var, double* cov);
 
+/* Joint samples of that posterior from the caller's base samples: MultivariateNormal.rsample(base_samples=...) behind botorch's
+ * GPyTorchPosterior, restated; parity with BoTorch itself is unpinned (DESIGN.md "GP posterior samples").  Opt-in, not used by the BO
+ * loop.  There is no device RNG: a draw is a function of (Xq, flags, base) alone.
+ *   mean[q], cov[q*q]: exactly what pcabo_gp_posterior returns for the same Xq and flags (without PCABO_POST_CENTRED).
+ *   A_j = cov + j y_std^2 I, j the first of 0, 1e-8, 1e-7, 1e-6 on which the Cholesky succeeds (the rungs of the GP's own
+ *         factorisation, psd_safe_cholesky's for float64); Lc = chol(A_j), lower.
+ *   samples[s*q + a] = mean_a + sum_{b <= a} Lc[a][b] base[s*q + b];  base[S*q], samples[S*q] [bulk], row-major.
+ *   flags: PCABO_POST_OBS_NOISE as above; PCABO_POST_CENTRED: the mean is not added (the centred process; base = I_q then reads Lc).
+ *   mean[q] [bulk] may be NULL; jitter_used [host] may be NULL: the rung j that was used.
+ * PCABO_ERR_ARG, nothing launched: the refusals of pcabo_gp_posterior; base or samples NULL; S < 1 or S > PCABO_POST_MAX_SAMPLES;
+ * unknown flag bits.  PCABO_ERR_NOT_PD: no rung could be factored; samples is not written.
+ * The first sampling call of a context allocates one block (the padded factor, base and samples at their capacities, the
+ * factorisation's own info word and scratch tiles) and, like a covariance query, the V / cov buffers; both are kept until destroy.
+ * Like pcabo_gp_posterior a call changes nothing that later calls of the context read. */
+enum { PCABO_POST_CENTRED = 2 };   /* pcabo_gp_posterior_sample only: pcabo_gp_posterior refuses it */
+#define PCABO_POST_MAX_SAMPLES 1024
+int pcabo_gp_posterior_sample(pcabo_ctx* ctx, const double* Xq, int q, int flags, const double* base, int S,
+                              double* samples, double* mean /*q, may be NULL*/, double* jitter_used /*may be NULL*/);
+
 /* Rows M-N: multi-start L-BFGS-B over the acquisition (botorch gen_candidates_scipy semantics:
  * restarts are optimised jointly in groups of `batch_limit`, objective -sum_j acq(x_j), scipy
  * L-BFGS-B defaults m=10, factr=1e7 (ftol 2.22e-9), pgtol=1e-5, maxls=20, maxfun=15000).
@@ -377,6 +396,15 @@ int pcabo_batch_gp_condition_end_eval(pcabo_batch* batch, const double* Xq, int 
  * The runs' V and cov buffers are ONE allocation made by the first call that asks for a covariance. */
 int pcabo_batch_gp_posterior(pcabo_batch* batch, const double* Xq, int q, int flags, double* mean, double* var, double* cov,
                              int* status);
+/* pcabo_gp_posterior_sample for every run in one launch sequence, each run bit for bit what it takes alone.  Host pointers.
+ * Xq[B][q*max_d] as above; base[B][S*q], samples[B][S*q]; mean[B][q], jitter_used[B], status[B] may be NULL.
+ * status[b]: PCABO_ERR_ARG for a parked run and for a run without a GP (skipped, their output blocks left as they are);
+ * PCABO_ERR_NOT_PD for a run none of whose rungs could be factored (its samples are not written) - the rungs after the first are
+ * tried for such a run alone and the other runs are not held up.  The refusals of pcabo_batch_gp_posterior and of
+ * pcabo_gp_posterior_sample apply.  The runs' sample blocks are ONE allocation made by the first call. */
+int pcabo_batch_gp_posterior_sample(pcabo_batch* batch, const double* Xq /*[B][q*max_d]*/, int q, int flags,
+                                    const double* base /*[B][S*q]*/, int S, double* samples /*[B][S*q]*/,
+                                    double* mean /*[B][q]*/, double* jitter_used /*[B]*/, int* status /*[B]*/);
 /* Rows M-N for every run (pcabo_optimize_acqf semantics per run).  ics[B][num_restarts*max_d] (dense num_restarts x k_b per
  * block), bounds[B][2*max_d] as pcabo_batch_acq_bounds gives them, best_f[B]; cand[B][num_restarts*max_d] (dense per block),
  * vals[B][num_restarts], info[B][4*ngroups] or NULL, failed[B], status[B]. */

@@ -499,6 +499,17 @@ class PCA_BO(AbstractBayesianOptimizer):
         X = np.asarray(X, dtype=np.float64).reshape(-1, self.dimension)
         return self.__ctx.gp_posterior(self.pca.transform(X - self.data_mean), observation_noise, covariance)
 
+    def posterior_samples(self, X, n_samples=1, seed=None, base_samples=None, observation_noise: bool = False,
+                          centred: bool = False) -> dict:
+        """Joint draws of the current iteration's GP at X (m x d, original space): {"samples" (S, m), "mean" (m,), "jitter"}
+        (Context.gp_posterior_samples).  The base is n_samples rows from a generator of its own seeded with `seed`, or the caller's
+        base_samples (S x m), which replace n_samples.  Mapping and RuntimeErrors as posterior(); leaves the run's trajectory alone."""
+        if self.__ctx is None or self.pca is None or self.__gp_pending:
+            raise RuntimeError("posterior_samples: no run is open, or the model of the current iteration is not conditioned yet")
+        X = np.asarray(X, dtype=np.float64).reshape(-1, self.dimension)
+        return self.__ctx.gp_posterior_samples(self.pca.transform(X - self.data_mean), None if base_samples is not None else n_samples,
+                                               base_samples, seed, observation_noise, centred)
+
     # ---- row O ------------------------------------------------------------------------------------
     def _transform_point_to_original_space(self, z: np.ndarray) -> np.ndarray:
         if self.pca is None:

@@ -180,6 +180,17 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         X = np.asarray(X, dtype=np.float64).reshape(-1, self.dimension)
         return self.__ctx.gp_posterior(X, observation_noise, covariance)
 
+    def posterior_samples(self, X, n_samples=1, seed=None, base_samples=None, observation_noise: bool = False,
+                          centred: bool = False) -> dict:
+        """Joint draws of the current iteration's GP at X (m x d): {"samples" (S, m), "mean" (m,), "jitter"}
+        (Context.gp_posterior_samples).  The base is n_samples rows from a generator of its own seeded with `seed`, or the caller's
+        base_samples (S x m), which replace n_samples.  RuntimeErrors as posterior()."""
+        if self.__ctx is None:
+            raise RuntimeError("posterior_samples: no run is open")
+        X = np.asarray(X, dtype=np.float64).reshape(-1, self.dimension)
+        return self.__ctx.gp_posterior_samples(X, None if base_samples is not None else n_samples, base_samples, seed,
+                                               observation_noise, centred)
+
     def __repr__(self):
         return super().__repr__()
 

@@ -16,6 +16,12 @@
 //   k_post_cov      V^T V per lower 64 x 64 tile on v_mfma_f64_16x16x4f64, the prior part rebuilt from the normalised queries in the
 //                   epilogue, tile and mirror written by the one work-group that owns them: no atomics, the same bits on every call
 // Batches: blockIdx.z = run, zrun addressing, k of a run from k_dev, 1 / lengthscale and the noise from its hyperparameter block.
+//
+// Joint samples (pcabo_gp_posterior_sample / pcabo_batch_gp_posterior_sample; DESIGN.md "GP posterior samples") go on behind the
+// covariance:
+//   k_post_chol_prep  cov + j s_y^2 I into the padded factor buffer (identity on the padding), the Cholesky's info word cleared
+//   launch_cholesky   the GP's own blocked factorisation, in place (kernels_gp.hip / kernels_gpw.hip), unchanged
+//   k_post_sample     out = [mean +] base Lc^T per 64 x 64 tile on v_mfma_f64_16x16x4f64, the column blocks of Lc in ascending order
 #include "pcabo_internal.h"
 #include "acq_math.h"
 
@@ -237,4 +243,107 @@ void launch_posterior(hipStream_t st, const double* Xq, int q, const GpModel& m,
   const int nt = (q + 63) / 64;
   hipLaunchKernelGGL(k_post_cov, dim3(nt * (nt + 1) / 2, 1, B), dim3(256), 0, st, V, q, m.NP, Xq, m.k, m.bounds4, m.ystats,
                      post + 2 * (size_t)q, p.inv_ls, p.kernel, cov, ab.zs, vzs, ab.k_dev, ab.hyp);
+}
+
+// ---- joint samples --------------------------------------------------------------------------------------------------------------
+// F (QP x QP, ld = QP, QP = 64 ceil(q / 64)) = cov + jitter s_y^2 I on the leading q x q part, the identity on the padding rows and
+// columns; one work-group per 64 x 64 tile.  The whole square is written, so a retry on the next rung starts from the untouched cov.
+// szs: bytes between two runs' sample blocks (F and info), vzs: between their cov blocks.
+__global__ __launch_bounds__(256) void k_post_chol_prep(const double* __restrict__ cov, int q_total, int QP,
+                                                        const double* __restrict__ ystats, double jitter, double* __restrict__ F,
+                                                        int* __restrict__ info, size_t zs, size_t vzs, size_t szs) {
+  ZRUN(ystats);
+  cov = zrun(cov, vzs, blockIdx.z); F = zrun(F, szs, blockIdx.z); info = zrun(info, szs, blockIdx.z);
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *info = 0;
+  const double ysd = ystats[1], add = jitter * (ysd * ysd);
+  const size_t Q = (size_t)q_total;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const int idx = tid + 256 * u;
+    const int a = blockIdx.y * 64 + (idx >> 6), b = blockIdx.x * 64 + (idx & 63);
+    double v;
+    if (a < q_total && b < q_total) {
+      v = cov[a * Q + b];
+      if (a == b) v += add;
+    } else {
+      v = (a == b) ? 1.0 : 0.0;
+    }
+    F[(size_t)a * QP + b] = v;
+  }
+}
+
+// out[s][a] = [mean_a +] sum_{b <= a} Lc[a][b] base[s][b]: work-group (x, y) owns samples 64 x .. and points 64 y .. and walks the
+// column blocks J <= y of Lc.  Lc is the factored F: below the diagonal the factor, ABOVE it whatever the input held (the Cholesky
+// never writes there), so the diagonal tile is masked to its lower half; rows and columns >= q (the identity padding) and samples
+// >= S are staged as zeros and never stored.  base and out: S x q dense.  mean: null for the centred process.
+__global__ __launch_bounds__(256) void k_post_sample(const double* __restrict__ F, int q_total, int QP, const double* __restrict__ base,
+                                                     int S, const double* __restrict__ mean, double* __restrict__ out, size_t zs,
+                                                     size_t szs) {
+  ZRUN(mean);
+  F = zrun(F, szs, blockIdx.z); base = zrun(base, szs, blockIdx.z); out = zrun(out, szs, blockIdx.z);
+  __shared__ __attribute__((aligned(16))) double s_a[64 * PCABO_TLD];
+  __shared__ __attribute__((aligned(16))) double s_b[64 * PCABO_TLD];
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+  const int s0 = blockIdx.x * 64, A = blockIdx.y;
+  const size_t Q = (size_t)q_total;
+  double pa[16], pb[16];
+  auto fetch = [&](int J) {                   // base rows s0 .., columns 64 J ..; Lc rows 64 A .., columns 64 J ..
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
+      const int b = J * 64 + c, a = A * 64 + r;
+      pa[u] = (s0 + r < S && b < q_total) ? base[(size_t)(s0 + r) * Q + b] : 0.0;
+      pb[u] = (a < q_total && b <= a) ? F[(size_t)a * QP + b] : 0.0;      // (b <= a < q: the lower triangle of the q x q part)
+    }
+  };
+  auto put = [&]() {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
+      s_a[r * PCABO_TLD + c] = pa[u];
+      s_b[r * PCABO_TLD + c] = pb[u];
+    }
+  };
+  double4_t acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  fetch(0);
+  for (int J = 0; J <= A; ++J) {              // ascending column blocks: the sum does not depend on a schedule
+    __syncthreads();
+    put();
+    if (J < A) fetch(J + 1);
+    __syncthreads();
+    for (int kk = 0; kk < 64; kk += 4) {
+      const double a = s_a[(16 * w + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const double b = s_b[(16 * t + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
+        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  // acc[t][r] = (base Lc^T)[s0 + 16 w + (l >> 4) + 4 r][64 A + 16 t + (l & 15)]
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int a = A * 64 + 16 * t + (l & 15);
+    if (a >= q_total) continue;
+    const double m = mean ? mean[a] : 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int s = s0 + 16 * w + (l >> 4) + 4 * r;
+      if (s < S) out[(size_t)s * Q + a] = mean ? m + acc[t][r] : acc[t][r];
+    }
+  }
+}
+
+void launch_post_chol_prep(hipStream_t st, const double* cov, int q, const double* ystats, double jitter, double* F, int* info,
+                           size_t zs, size_t vzs, size_t szs, int B) {
+  const int nb = (q + 63) / 64;
+  hipLaunchKernelGGL(k_post_chol_prep, dim3(nb, nb, B), dim3(256), 0, st, cov, q, nb * 64, ystats, jitter, F, info, zs, vzs, szs);
+}
+void launch_post_sample(hipStream_t st, const double* F, int q, const double* base, int S, const double* mean, double* out, size_t zs,
+                        size_t szs, int B) {
+  const int nb = (q + 63) / 64;
+  hipLaunchKernelGGL(k_post_sample, dim3((S + 63) / 64, nb, B), dim3(256), 0, st, F, q, nb * 64, base, S, mean, out, zs, szs);
 }

@@ -121,6 +121,7 @@ struct pcabo_ctx {
   double* dHyp = nullptr;                // lock-step fit of a batch: this run's {1 / lengthscale, noise, mean constant} (PCABO_HYP_*)
   double* dPostV = nullptr;              // pcabo_gp_posterior with a covariance: V (NPcap x max_q), then cov (max_q^2); allocated
                                          // by the first such call, kept until destroy
+  char* dSample = nullptr;               // pcabo_gp_posterior_sample: the sample block (SampleBlock), allocated by the first such call
   char *dRegion = nullptr, *hRegion = nullptr;   // the two allocations everything above / below is carved from
   size_t region_bytes = 0, hregion_bytes = 0;
   bool in_batch = false; int batch_index = 0;
@@ -504,6 +505,7 @@ static void ctx_teardown(pcabo_ctx* ctx) {
     if (ctx->dPairs) (void)hipFree(ctx->dPairs);
   }
   if (ctx->dPostV) (void)hipFree(ctx->dPostV);
+  if (ctx->dSample) (void)hipFree(ctx->dSample);
   if (ctx->evBounds) (void)hipEventDestroy(ctx->evBounds);
   if (ctx->evPca) (void)hipEventDestroy(ctx->evPca);
   if (ctx->evZn) (void)hipEventDestroy(ctx->evZn);
@@ -1261,11 +1263,18 @@ int pcabo_logei(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maxi
 // (kernels_post.hip).  The queries go straight from the caller's array to dXq and the results straight from the device to the
 // caller's arrays: of the context's state only dXq, dKS and dPartial are written, which every evaluation writes before it reads.
 // No sequence number is taken, no ticket touched, the second stream not used.
-static const char* post_arg_error(const double* Xq, int q, int max_q, int flags, bool any_out) {
+static const char* post_arg_error(const double* Xq, int q, int max_q, int flags, bool any_out, int known = PCABO_POST_OBS_NOISE) {
   if (!Xq) return "Xq is required";
   if (q < 1 || q > max_q) return "q must lie in 1 .. max_q";
   if (!any_out) return "mean, var and cov are all NULL";
-  if (flags & ~(int)PCABO_POST_OBS_NOISE) return "unknown flag bits";
+  if (flags & ~known) return "unknown flag bits";
+  return nullptr;
+}
+// ... and what a sampling call adds to them
+static const char* sample_arg_error(const double* Xq, int q, int max_q, int flags, const double* base, int S, const double* samples) {
+  if (const char* why = post_arg_error(Xq, q, max_q, flags, true, PCABO_POST_OBS_NOISE | PCABO_POST_CENTRED)) return why;
+  if (!base || !samples) return "base and samples are required";
+  if (S < 1 || S > PCABO_POST_MAX_SAMPLES) return "S must lie in 1 .. PCABO_POST_MAX_SAMPLES";
   return nullptr;
 }
 // doubles of a context's (or of one run's) V block; its cov block (max_q^2) lies behind it
@@ -1296,6 +1305,89 @@ int pcabo_gp_posterior(pcabo_ctx* ctx, const double* Xq, int q, int flags, doubl
   if (cov) HIPCHK(hipMemcpyAsync(cov, dcov, (size_t)q * q * sizeof(double), out, s));
   HIPCHK(wait_stream(s));
   HIPCHK(hipGetLastError());
+  return PCABO_OK;
+}
+
+// ---- posterior samples (DESIGN.md "GP posterior samples") ---------------------------------------------------------------------
+// The posterior query with its covariance, then cov + j s_y^2 I factored in a block of its own and the triangular product with the
+// caller's base samples.  The factorisation is the GP's (launch_cholesky) on the sample block's own info word and scratch tiles:
+// dInfo, dDiag and the host mirror's chol_info belong to the GP's factorisation and are not touched.
+//
+// One run's sample block: factor | two scratch tiles | base | samples | info word.  launch_cholesky applies ONE stride to the matrix,
+// the info word and the scratch, so in a batch the runs' blocks lie `bytes` apart and that stride serves all of them.
+struct SampleBlock {
+  size_t factor, diag, base, out, info, bytes;        // byte offsets inside the block; bytes: the block, a multiple of 256
+  explicit SampleBlock(int max_q) {
+    const size_t QP = (size_t)round_up(max_q, PCABO_BS), cap = (size_t)PCABO_POST_MAX_SAMPLES * max_q;
+    factor = 0;
+    diag = factor + QP * QP * sizeof(double);
+    base = diag + (size_t)2 * PCABO_BS * PCABO_BS * sizeof(double);
+    out = base + cap * sizeof(double);
+    info = out + cap * sizeof(double);
+    bytes = (info + sizeof(int) + 255) & ~(size_t)255;
+  }
+  double* F(char* p) const { return reinterpret_cast<double*>(p + factor); }
+  double* D(char* p) const { return reinterpret_cast<double*>(p + diag); }
+  double* Bs(char* p) const { return reinterpret_cast<double*>(p + base); }
+  double* Out(char* p) const { return reinterpret_cast<double*>(p + out); }
+  int* Info(char* p) const { return reinterpret_cast<int*>(p + info); }
+};
+static const double kSampleRungs[4] = {0.0, 1e-8, 1e-7, 1e-6};      // relative to s_y^2: the ladder of cholesky_attempts
+
+// One rung for B runs (blk: run 0's block, zb.zs: the block stride): prep from the untouched cov, the factorisation, the info
+// words on their way to the host.  PCABO_OK, or PCABO_ERR_HIP when nothing could be launched.
+static int sample_factor_enqueue(hipStream_t s, const SampleBlock& L, char* blk, const double* cov, const double* ystats, int q,
+                                 double jitter, size_t zs, size_t vzs, ZB zb, int* info_host) {
+  const int QP = round_up(q, PCABO_BS);
+  launch_post_chol_prep(s, cov, q, ystats, jitter, L.F(blk), L.Info(blk), zs, vzs, zb.zs, zb.B);
+  if (launch_cholesky(s, L.F(blk), QP, QP, L.Info(blk), L.D(blk), zb) != 0) return PCABO_ERR_HIP;
+  const hipError_t e = zb.B > 1 ? hipMemcpy2DAsync(info_host, sizeof(int), L.Info(blk), zb.zs, sizeof(int), zb.B, hipMemcpyDeviceToHost, s)
+                                : hipMemcpyAsync(info_host, L.Info(blk), sizeof(int), hipMemcpyDeviceToHost, s);
+  return e == hipSuccess ? PCABO_OK : PCABO_ERR_HIP;
+}
+// The ladder of one run from rung `first` on: the rung that could be factored (0 .. 3), -1 when none could, -2 on a HIP error
+static int sample_ladder(hipStream_t s, const SampleBlock& L, char* blk, const double* cov, const double* ystats, int q, int first) {
+  for (int r = first; r < 4; ++r) {
+    int info = -1;
+    if (sample_factor_enqueue(s, L, blk, cov, ystats, q, kSampleRungs[r], 0, 0, ZB(), &info) != PCABO_OK) return -2;
+    if (wait_stream(s) != hipSuccess) return -2;
+    if (info == 0) return r;
+  }
+  return -1;
+}
+
+int pcabo_gp_posterior_sample(pcabo_ctx* ctx, const double* Xq, int q, int flags, const double* base, int S, double* samples,
+                              double* mean, double* jitter_used) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (const char* why = sample_arg_error(Xq, q, ctx->max_q, flags, base, S, samples))
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior_sample: %s", why);
+  if (ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior_sample: a conditioning is in flight, call pcabo_gp_condition_end first%s", "");
+  if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior_sample: no conditioned GP, call pcabo_gp_condition first%s", "");
+  HIPCHK(hipSetDevice(ctx->device));
+  const SampleBlock L(ctx->max_q);
+  if (!ctx->dPostV) HIPCHK(dalloc(&ctx->dPostV, post_v_doubles(ctx) + (size_t)ctx->max_q * ctx->max_q));
+  if (!ctx->dSample) HIPCHK(dalloc(&ctx->dSample, L.bytes));
+  hipStream_t s = ctx->stream;
+  const bool host = ctx->ptr_mode == PCABO_PTR_HOST;
+  const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  char* blk = ctx->dSample;
+  HIPCHK(hipMemcpyAsync(ctx->dXq, Xq, (size_t)q * ctx->k * sizeof(double), in, s));
+  HIPCHK(hipMemcpyAsync(L.Bs(blk), base, (size_t)S * q * sizeof(double), in, s));
+  const AcqParams p = make_params(ctx, 0.0, 1, PCABO_ACQ_UCB, 0);
+  const GpModel m = gp_model(ctx);
+  double* post = post_out(ctx, ctx->NP, q);
+  double* dcov = ctx->dPostV + post_v_doubles(ctx);
+  launch_posterior(s, ctx->dXq, q, m, p, ctx->noise, flags & PCABO_POST_OBS_NOISE, ctx->dKS, ctx->dPartial, post, ctx->dPostV, dcov);
+  const int rung = sample_ladder(s, L, blk, dcov, m.ystats, q, 0);
+  if (rung == -2) return set_err(ctx, PCABO_ERR_HIP, "pcabo_gp_posterior_sample: HIP error: %s", hipGetErrorString(hipGetLastError()));
+  if (rung < 0)
+    return set_err(ctx, PCABO_ERR_NOT_PD, "pcabo_gp_posterior_sample: the posterior covariance of the %s%d queries is not positive definite after the jitter retries", "", q);
+  launch_post_sample(s, L.F(blk), q, L.Bs(blk), S, (flags & PCABO_POST_CENTRED) ? nullptr : post, L.Out(blk));
+  HIPCHK(hipMemcpyAsync(samples, L.Out(blk), (size_t)S * q * sizeof(double), out, s));
+  if (mean) HIPCHK(hipMemcpyAsync(mean, post, (size_t)q * sizeof(double), out, s));
+  HIPCHK(wait_stream(s));
+  HIPCHK(hipGetLastError());
+  if (jitter_used) *jitter_used = kSampleRungs[rung];
   return PCABO_OK;
 }
 
@@ -1674,6 +1766,7 @@ struct pcabo_batch {
   std::vector<unsigned> dbg_branches; std::vector<double> dbg_group_out; int dbg_groups = 0;
   char* dPost = nullptr; size_t post_vzs = 0;        // pcabo_batch_gp_posterior with a covariance: every run's V and cov block, post_vzs
                                                      // bytes apart (one allocation, made by the first such call)
+  char* dSample = nullptr;                           // pcabo_batch_gp_posterior_sample: every run's SampleBlock, its `bytes` apart
   unsigned *dOptTab = nullptr, *hOptTab = nullptr;   // launch table of the device-resident optimiser (B * 32 entries)
   int G = 0;                             // gangs = worker threads of the L-BFGS-B phase
   std::vector<hipStream_t> gstream;
@@ -1708,6 +1801,7 @@ static void batch_free(pcabo_batch* batch) {
   if (batch->dSlab) (void)hipFree(batch->dSlab);
   if (batch->hSlab) (void)hipHostFree(batch->hSlab);
   if (batch->dPost) (void)hipFree(batch->dPost);
+  if (batch->dSample) (void)hipFree(batch->dSample);
   if (batch->dOptTab) (void)hipFree(batch->dOptTab);
   if (batch->hOptTab) (void)hipHostFree(batch->hOptTab);
   if (batch->stream) (void)hipStreamDestroy(batch->stream);
@@ -2347,6 +2441,71 @@ int pcabo_batch_gp_posterior(pcabo_batch* batch, const double* Xq, int q, int fl
     if (!(batch->active[b] && batch->ctx[b]->have_gp)) continue;
     if (mean) memcpy(mean + (size_t)b * q, &mv[(size_t)b * 2 * q], (size_t)q * sizeof(double));
     if (var) memcpy(var + (size_t)b * q, &mv[(size_t)b * 2 * q + q], (size_t)q * sizeof(double));
+  }
+  return PCABO_OK;
+}
+
+// pcabo_gp_posterior_sample for the runs of a batch: the posterior with its covariance, the first rung and the product as one launch
+// sequence each (blockIdx.z = run, the sample blocks `bytes` apart); a run whose first rung fails climbs the rest of the ladder alone
+// on its own block, with the launches a single context makes.
+int pcabo_batch_gp_posterior_sample(pcabo_batch* batch, const double* Xq, int q, int flags, const double* base, int S, double* samples,
+                                    double* mean, double* jitter_used, int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (const char* why = sample_arg_error(Xq, q, batch->max_q, flags, base, S, samples))
+    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior_sample: %s", why);
+  if (batch->gp_pending || batch->score_enqueued || batch->opt_enqueued || batch->imap_enqueued)
+    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior_sample: a conditioning or a _begin call of this batch has not been ended%s", "");
+  if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior_sample: no conditioned GP%s", "");
+  BHIPCHK(hipSetDevice(batch->device));
+  hipStream_t s = batch->stream;
+  const int B = batch->B, kmax = batch_max_k(batch);
+  pcabo_ctx* c0 = batch->ctx[0];
+  const SampleBlock L(batch->max_q);
+  if (!batch->dPost) {
+    batch->post_vzs = ((post_v_doubles(c0) + (size_t)batch->max_q * batch->max_q) * sizeof(double) + 255) & ~(size_t)255;
+    BHIPCHK(hipMalloc((void**)&batch->dPost, batch->post_vzs * (size_t)B));
+  }
+  if (!batch->dSample) BHIPCHK(hipMalloc((void**)&batch->dSample, L.bytes * (size_t)B));
+  char* blk = batch->dSample;
+  const size_t row = (size_t)S * q * sizeof(double);
+  BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, Xq, (size_t)q * batch->max_d * sizeof(double), (size_t)q * kmax * sizeof(double), B,
+                           hipMemcpyHostToDevice, s));
+  BHIPCHK(hipMemcpy2DAsync(L.Bs(blk), L.bytes, base, row, row, B, hipMemcpyHostToDevice, s));
+  const AcqParams p = batch_params(batch, 1, PCABO_ACQ_UCB, 0);
+  const GpModel m = gp_model(batch, kmax);
+  const AcqBatch ab = batch_ab(batch, 0, 0);
+  double* post = post_out(c0, batch->NP, q);
+  double* dV = reinterpret_cast<double*>(batch->dPost);
+  double* dcov = dV + post_v_doubles(c0);
+  launch_posterior(s, c0->dXq, q, m, p, batch->noise, flags & PCABO_POST_OBS_NOISE, c0->dKS, c0->dPartial, post, dV, dcov, ab, batch->post_vzs, B);
+  std::vector<int> info((size_t)B, -1), rung((size_t)B, 0);
+  ZB zb; zb.B = B; zb.zs = L.bytes;
+  if (sample_factor_enqueue(s, L, blk, dcov, m.ystats, q, kSampleRungs[0], batch->zs, batch->post_vzs, zb, info.data()) != PCABO_OK)
+    return bset_err(batch, PCABO_ERR_HIP, "pcabo_batch_gp_posterior_sample: the factorisation could not be launched%s", "");
+  BHIPCHK(wait_stream(s));
+  for (int b = 0; b < B; ++b) {
+    const bool ok = batch->active[b] && batch->ctx[b]->have_gp;
+    if (!ok) { rung[b] = -1; if (status) status[b] = PCABO_ERR_ARG; continue; }
+    if (info[b] != 0) {
+      const double* cov_b = reinterpret_cast<const double*>(reinterpret_cast<const char*>(dcov) + (size_t)b * batch->post_vzs);
+      const double* ystats_b = reinterpret_cast<const double*>(reinterpret_cast<const char*>(m.ystats) + (size_t)b * batch->zs);
+      rung[b] = sample_ladder(s, L, blk + (size_t)b * L.bytes, cov_b, ystats_b, q, 1);
+      if (rung[b] == -2) return bset_err(batch, PCABO_ERR_HIP, "pcabo_batch_gp_posterior_sample: HIP error: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (status) status[b] = rung[b] >= 0 ? PCABO_OK : PCABO_ERR_NOT_PD;
+  }
+  launch_post_sample(s, L.F(blk), q, L.Bs(blk), S, (flags & PCABO_POST_CENTRED) ? nullptr : post, L.Out(blk), batch->zs, L.bytes, B);
+  std::vector<double> mv(mean ? (size_t)B * q : 0);
+  if (mean) BHIPCHK(hipMemcpy2DAsync(mv.data(), (size_t)q * sizeof(double), post, batch->zs, (size_t)q * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  for (int b = 0; b < B; ++b)
+    if (rung[b] >= 0)
+      BHIPCHK(hipMemcpyAsync(samples + (size_t)b * S * q, L.Out(blk + (size_t)b * L.bytes), row, hipMemcpyDeviceToHost, s));
+  BHIPCHK(wait_stream(s));
+  BHIPCHK(hipGetLastError());
+  for (int b = 0; b < B; ++b) {
+    if (rung[b] < 0) continue;
+    if (mean) memcpy(mean + (size_t)b * q, &mv[(size_t)b * q], (size_t)q * sizeof(double));
+    if (jitter_used) jitter_used[b] = kSampleRungs[rung[b]];
   }
   return PCABO_OK;
 }

@@ -372,6 +372,13 @@ void launch_score_ks(hipStream_t st, const double* Xq, int q, const GpModel& m, 
 void launch_posterior(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double s2, int obs_noise,
                       double* KS, double* partial, double* post, double* V, double* cov, AcqBatch ab = AcqBatch(),
                       size_t vzs = 0, int B = 1);
+// Joint samples behind launch_posterior's covariance (kernels_post.hip): F (QP x QP, QP = 64 ceil(q / 64)) = cov + jitter s_y^2 I,
+// identity on the padding, *info = 0 - ready for launch_cholesky(F, QP, QP, info, ...); then out (S x q) = [mean +] base (S x q) Lc^T
+// from the factored F.  zs: the runs' context stride (ystats, mean), vzs: between their cov blocks, szs: between their sample blocks.
+void launch_post_chol_prep(hipStream_t st, const double* cov, int q, const double* ystats, double jitter, double* F, int* info,
+                           size_t zs = 0, size_t vzs = 0, size_t szs = 0, int B = 1);
+void launch_post_sample(hipStream_t st, const double* F, int q, const double* base, int S, const double* mean /* or null */,
+                        double* out, size_t zs = 0, size_t szs = 0, int B = 1);
 void launch_score_tail(hipStream_t st, int q, const GpModel& m, AcqParams p, const double* KS, double* partial, double* val);
 // resident mode available for this shape? (fast path + every group of the grid co-resident)
 bool acq_server_possible(int q, int n, int k, int NP);

@@ -20,6 +20,8 @@ PTR_HOST, PTR_DEVICE = 0, 1
 OPT_RESIDENT, OPT_BESTF_F32, OPT_GROUP_ACQ, OPT_DEVICE_LBFGSB = 0, 1, 2, 3
 OPT_HIDDEN_TAIL = 5
 POST_OBS_NOISE = 1                              # gp_posterior: variance / covariance of an observation (likelihood noise added)
+POST_CENTRED = 2                                # gp_posterior_samples: the mean is not added (the centred process)
+POST_MAX_SAMPLES = 1024                         # gp_posterior_samples: most samples of one call
 FIT_THETA0 = (0.006737946999085467, 0.0, 0.0)   # GP fit: (noise, mean constant, raw lengthscale) of a freshly built model
 FIT_TASK_NOT_PD = -2                            # gp_fit's `task` when a trial theta could not be factored even with jitter
 PROFILE_GROUPS = ("wpca", "gram", "cholesky", "root_inverse_alpha", "acq_partial", "acq_large_batches")
@@ -53,7 +55,7 @@ EXPORTS = [
     "pcabo_gp_condition_end", "pcabo_gp_condition_end_eval", "pcabo_wpca_gp_condition_begin", "pcabo_wpca_results",
     "pcabo_gp_mll", "pcabo_gp_fit", "pcabo_gp_mll_ard", "pcabo_gp_fit_ard",
     "pcabo_acq_bounds",
-    "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
+    "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_gp_posterior_sample", "pcabo_batch_gp_posterior_sample", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
     "pcabo_get_gram", "pcabo_lbfgsb_minimize", "pcabo_lbfgsb_set_vector_kernels", "pcabo_lbfgsb_set_sum_order", "pcabo_sobol_scramble", "pcabo_sobol_draw", "pcabo_sobol_draw_rows", "pcabo_torch_randint2", "pcabo_torch_multinomial_rows", "pcabo_boltzmann_pick_rows", "pcabo_set_profiling",
     "pcabo_get_profile", "pcabo_get_profile_calibration", "pcabo_reset_profile",
     "pcabo_batch_create", "pcabo_batch_destroy", "pcabo_batch_last_error", "pcabo_batch_ctx",
@@ -116,6 +118,8 @@ def _load() -> C.CDLL:
     lib.pcabo_logei.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, vp, vp]
     lib.pcabo_gp_posterior.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
     lib.pcabo_batch_gp_posterior.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.pcabo_gp_posterior_sample.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, dp]
+    lib.pcabo_batch_gp_posterior_sample.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     lib.pcabo_optimize_acqf.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                         vp, vp, vp, ip]
     lib.pcabo_inverse_map.argtypes = [vp, vp, vp]
@@ -218,6 +222,25 @@ def _f64(a, shape=None) -> np.ndarray:
     if shape is not None:
         a = a.reshape(shape)
     return a
+
+
+def sample_base(q: int, n_samples=None, base_samples=None, seed=None) -> np.ndarray:
+    """The S x q base samples of a gp_posterior_samples call: the caller's `base_samples`, or `n_samples` standard normal rows from
+    np.random.default_rng(seed) - a generator of its own, so neither numpy's global state nor torch's moves (a run's trajectory
+    depends on both).  Exactly one of the two is given (ValueError otherwise, and for a base that is not S x q)."""
+    if (n_samples is None) == (base_samples is None):
+        raise ValueError("give exactly one of n_samples and base_samples")
+    if base_samples is not None:
+        if seed is not None:
+            raise ValueError("seed goes with n_samples: base_samples are the draw")
+        base = np.ascontiguousarray(base_samples, dtype=np.float64)
+        if base.ndim != 2 or base.shape[1] != q or base.shape[0] < 1:
+            raise ValueError(f"base_samples must be S x q = S x {q}, got {base.shape}")
+        return base
+    S = int(n_samples)
+    if S < 1:
+        raise ValueError("n_samples must be at least 1")
+    return np.random.default_rng(seed).standard_normal((S, q))
 
 
 class Context:
@@ -458,6 +481,22 @@ class Context:
             out["covariance"] = cov
         return out
 
+    # ---- posterior samples (pcabo_gp_posterior_sample) -------------------------------------------
+    def gp_posterior_samples(self, Xq, n_samples=None, base_samples=None, seed=None, observation_noise=False, centred=False) -> dict:
+        """Joint draws of the conditioned GP at Xq (q x k, reduced space): {"samples" (S, q) = mean + base Lc^T, "mean" (q,), "jitter":
+        the rung of 0, 1e-8, 1e-7, 1e-6 (relative to y_std^2) the covariance's Cholesky Lc needed}.  The base is `base_samples` (S x q)
+        or n_samples rows from sample_base's own generator; centred leaves the mean out of the samples (include/pcabo.h)."""
+        Xq = _f64(Xq).reshape(-1, self.k)
+        q = Xq.shape[0]
+        base = sample_base(q, n_samples, base_samples, seed)
+        S = base.shape[0]
+        samples, mean = np.empty((S, q)), np.empty(q)
+        jitter = C.c_double(0.0)
+        flags = (POST_OBS_NOISE if observation_noise else 0) | (POST_CENTRED if centred else 0)
+        self._chk(LIB.pcabo_gp_posterior_sample(self._h, _ptr(Xq), q, flags, _ptr(base), S, _ptr(samples), _ptr(mean),
+                                                C.byref(jitter)))
+        return {"samples": samples, "mean": mean, "jitter": float(jitter.value)}
+
     # ---- rows M-N -----------------------------------------------------------------------------
     def optimize_acqf(self, ics, bounds, best_f, maximize=False, acq=ACQ_LOG_EI, batch_limit=5, maxiter=200):
         """Multi-start L-BFGS-B from `ics` inside `bounds`; `best_f` as in acq_eval (ACQ_UCB: kappa).  Returns (candidates, values,
@@ -691,6 +730,32 @@ class Batch:
             if covariance:
                 out[-1]["covariance"] = cov[b].copy()
         return out
+
+    def gp_posterior_samples(self, Xq_list, n_samples=None, base_samples=None, seed=None, observation_noise=False, centred=False):
+        """Context.gp_posterior_samples for every run in one launch sequence (Xq_list[b]: q x k_b, the same q for all runs).
+        base_samples: (S, q) for all runs or (B, S, q); with n_samples every run gets the same seeded base.  One dict per run, None
+        for a run that was skipped (parked, without a GP, or with a covariance no rung could factor); `status` keeps the codes."""
+        q = Xq_list[0].shape[0]
+        if base_samples is not None and np.ndim(base_samples) == 3:
+            if seed is not None or n_samples is not None:
+                raise ValueError("give exactly one of n_samples and base_samples")
+            base = np.ascontiguousarray(base_samples, dtype=np.float64)
+            if base.shape[0] != self.B or base.shape[2] != q or base.shape[1] < 1:
+                raise ValueError(f"base_samples must be B x S x q = {self.B} x S x {q}, got {base.shape}")
+        else:
+            one = sample_base(q, n_samples, base_samples, seed)
+            base = np.ascontiguousarray(np.broadcast_to(one, (self.B,) + one.shape))
+        S = base.shape[1]
+        buf = np.zeros((self.B, q * self.max_d))
+        for b, xq in enumerate(Xq_list):
+            buf[b, : xq.size] = np.ascontiguousarray(xq, dtype=np.float64).ravel()
+        samples, mean, jitter = np.zeros((self.B, S, q)), np.zeros((self.B, q)), np.zeros(self.B)
+        status = self.sample_status = np.zeros(self.B, dtype=np.int32)
+        flags = (POST_OBS_NOISE if observation_noise else 0) | (POST_CENTRED if centred else 0)
+        self._chk(LIB.pcabo_batch_gp_posterior_sample(self._h, _ptr(buf), q, flags, _ptr(base), S, _ptr(samples), _ptr(mean),
+                                                      _ptr(jitter), _ptr(status)))
+        return [None if status[b] != 0 else {"samples": samples[b].copy(), "mean": mean[b].copy(), "jitter": float(jitter[b])}
+                for b in range(self.B)]
 
     # ---- opt-in GP hyperparameter fit of all runs in lock-step (pcabo_batch_gp_mll / pcabo_batch_gp_fit) -----------------
     # Both work on the inputs of the last wpca_gp_condition_begin / gp_condition_begin and leave every run conditioned at its

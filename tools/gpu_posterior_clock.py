@@ -6,7 +6,10 @@ Prints ms per call of the scoring, of a mean + variance query and of a query wit
 the FP64 MFMA peak.  k_post_cov's own time comes from a separate run under `rocprofv3 --kernel-trace --stats`.  With --scoring-only
 only the scoring is timed (a library without the posterior entry points, for the comparison with an earlier build).
 
-usage: gpu_posterior_clock.py [--shape 449x36] [--q 512] [--reps 200] [--scoring-only]"""
+A sampling row follows the covariance query of the same q: ms per call of Context.gp_posterior_samples with --samples base samples
+(observation noise on, so the first rung factors), and the work of k_post_sample in the same three forms.  No threshold.
+
+usage: gpu_posterior_clock.py [--shape 449x36] [--q 512] [--samples 256] [--reps 200] [--scoring-only]"""
 import argparse
 import json
 import os
@@ -38,6 +41,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="449x36")
     ap.add_argument("--q", type=int, default=512)
+    ap.add_argument("--samples", type=int, default=256)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--scoring-only", action="store_true")
     a = ap.parse_args()
@@ -59,6 +63,15 @@ def main():
         row["cov_model_flops"] = 2.0 * NP * a.q * a.q / 2.0
         row["cov_issued_flops"] = 2.0 * 64 * 64 * NP * (nt * (nt + 1) // 2)
         row["cov_issued_us_at_peak"] = row["cov_issued_flops"] / FP64_PEAK * 1e6
+        row["ms_cov_noisy_median"], row["ms_cov_noisy_min"] = clock(
+            lambda: ctx.gp_posterior(X, observation_noise=True, covariance=True), a.reps)
+        base = np.random.default_rng(1).standard_normal((a.samples, a.q))
+        draw = lambda: ctx.gp_posterior_samples(X, base_samples=base, observation_noise=True)      # noqa: E731
+        row["samples"], row["sample_jitter"] = a.samples, draw()["jitter"]
+        row["ms_sample_median"], row["ms_sample_min"] = clock(draw, a.reps)
+        row["sample_model_flops"] = 2.0 * a.samples * a.q * a.q / 2.0
+        row["sample_issued_flops"] = 2.0 * 64 * 64 * 64 * -(-a.samples // 64) * (nt * (nt + 1) // 2)
+        row["sample_issued_us_at_peak"] = row["sample_issued_flops"] / FP64_PEAK * 1e6
     ctx.close()
     print(json.dumps(row))
 
