@@ -1255,7 +1255,7 @@ int launch_acq_group(hipStream_t st, const QueryArgs* tab, int entries, const do
 //   V = R KS^T  (n x q),  |v_q|^2 = column norms  k_score_gemm: 64 x 64 output tiles on v_mfma_f64_16x16x4, operand
 //                                                tiles through LDS (leading dimension 66: conflict-free), the next tiles
 //                                                travelling in registers while the MFMAs of the current ones run
-// Only the column norms leave the kernel (V itself is never stored): per (query, 64-row block) one partial record, the
+// Only the column norms leave the kernel (the scoring never stores V itself): per (query, 64-row block) one partial record, the
 // same records k_acq_combine sums for the slab kernels.  mu_s = alpha . ks is formed where ks is, in k_score_ks.
 // 0.10 GFLOP per run at n = 450: one work-group per (row block, 64 queries) instead of one per (16-row slab, 8 queries).
 #define SC_QB 16
@@ -1326,9 +1326,12 @@ __global__ __launch_bounds__(256) void k_score_ks(const double* __restrict__ Xq,
     partial[((size_t)(q0 + tid) * S + blockIdx.x) * PSTRIDE + 1] = ((s_mu[0][tid] + s_mu[1][tid]) + s_mu[2][tid]) + s_mu[3][tid];
 }
 
+// STORE_V: the posterior's instantiation also stores the tile of V (NP x q_total, runs vzs bytes apart) for k_post_cov; the scoring's
+// has no trace of it.  The product and the column norms are one code, so |v|^2 has the same bits in both.
+template <bool STORE_V>
 __global__ __launch_bounds__(256) void k_score_gemm(const double* __restrict__ R, const double* __restrict__ KS,
                                                     int q_total, int NP, int ld, int njb, double* __restrict__ partial,
-                                                    size_t zs) {
+                                                    double* __restrict__ V, size_t zs, size_t vzs) {
   ZRUN(R); ZRUN(KS); ZRUN(partial);
   __shared__ __attribute__((aligned(16))) double s_a[64 * PCABO_TLD];
   __shared__ __attribute__((aligned(16))) double s_b[64 * PCABO_TLD];
@@ -1337,42 +1340,23 @@ __global__ __launch_bounds__(256) void k_score_gemm(const double* __restrict__ R
   const int I = blockIdx.x, qb = blockIdx.y, S = gridDim.x;
   const double* Rrow = R + (size_t)(I * 64) * ld;
   const double* Krow = KS + (size_t)(qb * 64) * ld;
-  double pa[16], pb[16];
-  auto fetch = [&](int J) {
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
-      pa[u] = Rrow[(size_t)r * ld + J * 64 + c];
-      pb[u] = (qb * 64 + r < q_total) ? Krow[(size_t)r * ld + J * 64 + c] : 0.0;
-    }
-  };
-  auto put = [&]() {
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
-      s_a[r * PCABO_TLD + c] = pa[u];
-      s_b[r * PCABO_TLD + c] = pb[u];
-    }
-  };
   double4_t acc[4];
+  // R is lower triangular: column blocks beyond the diagonal hold zeros
+  tile_product_f64<false>(s_a, s_b, I + 1, [&](int J, int r, int c, double& a, double& b) {
+    a = Rrow[(size_t)r * ld + J * 64 + c];
+    b = (qb * 64 + r < q_total) ? Krow[(size_t)r * ld + J * 64 + c] : 0.0;
+  }, acc);
+  // acc[t][r] = V[16 w + (l >> 4) + 4 r][16 t + (l & 15)] of this tile: the tile itself, then its column norms
+  if (STORE_V) {
+    V = zrun(V, vzs, blockIdx.z);
 #pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  fetch(0);
-  for (int J = 0; J <= I; ++J) {              // R is lower triangular: column blocks beyond the diagonal hold zeros
-    __syncthreads();                          // the previous step's MFMAs have read the LDS tiles
-    put();
-    if (J < I) fetch(J + 1);
-    __syncthreads();
-    for (int kk = 0; kk < 64; kk += 4) {
-      const double a = s_a[(16 * w + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
+    for (int t = 0; t < 4; ++t) {
+      const int a = qb * 64 + 16 * t + (l & 15);
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const double b = s_b[(16 * t + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
-        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
-      }
+      for (int r = 0; r < 4; ++r)
+        if (a < q_total) V[(size_t)(I * 64 + 16 * w + (l >> 4) + 4 * r) * q_total + a] = acc[t][r];
     }
   }
-  // column norms of this 64-row block: acc[t][r] = V[16 w + (l >> 4) + 4 r][16 t + (l & 15)]
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     double v = ((acc[t][0] * acc[t][0] + acc[t][1] * acc[t][1]) + acc[t][2] * acc[t][2]) + acc[t][3] * acc[t][3];
@@ -1386,6 +1370,15 @@ __global__ __launch_bounds__(256) void k_score_gemm(const double* __restrict__ R
     rec[0] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
     if (I >= njb) rec[1] = 0.0;               // (records 0 .. njb-1 got their mu_s part from k_score_ks)
   }
+}
+
+// V = R KS^T per (64-row block, 64 queries, run) with its column norms into the partial records; V given: stored as well.
+void launch_score_gemm(hipStream_t st, const GpModel& m, int q, const double* KS, double* partial, size_t zs, int B, double* V,
+                       size_t vzs) {
+  const dim3 grid(m.NP / 64, (q + 63) / 64, B);
+  const int njb = (m.NP + 255) / 256;
+  if (V) hipLaunchKernelGGL(k_score_gemm<true>, grid, dim3(256), 0, st, m.R, KS, q, m.NP, m.ld, njb, partial, V, zs, vzs);
+  else hipLaunchKernelGGL(k_score_gemm<false>, grid, dim3(256), 0, st, m.R, KS, q, m.NP, m.ld, njb, partial, V, zs, vzs);
 }
 
 bool score_gemm_possible(int q) { return q >= 64; }
@@ -1429,7 +1422,7 @@ void launch_score_ks_only(hipStream_t st, const double* Xq, int q, const GpModel
 void launch_score_tail(hipStream_t st, int q, const GpModel& m, AcqParams p, const double* KS, double* partial, double* val) {
   const int S = m.NP / 64, njb = (m.NP + 255) / 256;
   hipLaunchKernelGGL(k_score_mu, dim3(njb, (q + SC_QB - 1) / SC_QB, 1), dim3(256), 0, st, KS, q, m.n, m.ld, m.alpha, partial, S);
-  hipLaunchKernelGGL(k_score_gemm, dim3(S, (q + 63) / 64, 1), dim3(256), 0, st, m.R, KS, q, m.NP, m.ld, njb, partial, (size_t)0);
+  launch_score_gemm(st, m, q, KS, partial);
   p.want_grad = 0;
   hipLaunchKernelGGL(k_acq_combine, dim3((q + 3) / 4, 1, 1), dim3(256), 0, st, partial, q, S, m.k, m.bounds4, m.ystats, p, val,
                      (double*)nullptr, AcqBatch());
@@ -1446,9 +1439,9 @@ void launch_score_ks(hipStream_t st, const double* Xq, int q, const GpModel& m, 
 // Value-only scoring of q >= 64 points: KS, then V = R KS^T on MFMA, then the scalar chain per query (k_acq_combine).
 void launch_score(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS, double* partial, double* val,
                   AcqBatch ab, int B) {
-  const int S = m.NP / 64, njb = (m.NP + 255) / 256;
+  const int S = m.NP / 64;
   launch_score_ks(st, Xq, q, m, p, KS, partial, ab, B);
-  hipLaunchKernelGGL(k_score_gemm, dim3(S, (q + 63) / 64, B), dim3(256), 0, st, m.R, KS, q, m.NP, m.ld, njb, partial, ab.zs);
+  launch_score_gemm(st, m, q, KS, partial, ab.zs, B);
   p.want_grad = 0;
   hipLaunchKernelGGL(k_acq_combine, dim3((q + 3) / 4, 1, B), dim3(256), 0, st, partial, q, S, m.k, m.bounds4, m.ystats, p, val,
                      (double*)nullptr, ab);

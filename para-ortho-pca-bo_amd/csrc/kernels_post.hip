@@ -9,93 +9,22 @@
 //   cov_ab  = s_y^2 (k(xn_a, xn_b) [+ s2 delta_ab] - v_a . v_b), not floored
 // The launches are those of the value-only scoring (kernels_acq.hip) up to the scalar chain:
 //   k_score_ks      KS and the mu_s records, unchanged
-//   k_post_gemm     k_score_gemm's product - the same staging and the same MFMA sequence per tile, so |v|^2 has its bits - which also
-//                   stores V when a covariance is asked for
+//   k_score_gemm    the scoring's own kernel (launch_score_gemm), with a covariance asked for in the instantiation that also stores
+//                   V: one tile product and one column-norm epilogue, so |v|^2 has the scoring's bits because it is the same code
 //   k_post_combine  one wave per query: the S records added in acq_finish_query's order, then mean and variance instead of an
 //                   acquisition value; the variance before the floor is kept for the covariance's diagonal
-//   k_post_cov      V^T V per lower 64 x 64 tile on v_mfma_f64_16x16x4f64, the prior part rebuilt from the normalised queries in the
-//                   epilogue, tile and mirror written by the one work-group that owns them: no atomics, the same bits on every call
+//   k_post_cov      V^T V per lower 64 x 64 tile through the shared tile product (tile_product_f64, pcabo_internal.h; K-major
+//                   operands), the prior part rebuilt from the normalised queries in the epilogue, tile and mirror written by the one
+//                   work-group that owns them: no atomics, the same bits on every call
 // Batches: blockIdx.z = run, zrun addressing, k of a run from k_dev, 1 / lengthscale and the noise from its hyperparameter block.
 //
 // Joint samples (pcabo_gp_posterior_sample / pcabo_batch_gp_posterior_sample; DESIGN.md "GP posterior samples") go on behind the
 // covariance:
 //   k_post_chol_prep  cov + j s_y^2 I into the padded factor buffer (identity on the padding), the Cholesky's info word cleared
 //   launch_cholesky   the GP's own blocked factorisation, in place (kernels_gp.hip / kernels_gpw.hip), unchanged
-//   k_post_sample     out = [mean +] base Lc^T per 64 x 64 tile on v_mfma_f64_16x16x4f64, the column blocks of Lc in ascending order
+//   k_post_sample     out = [mean +] base Lc^T per 64 x 64 tile through tile_product_f64, the column blocks of Lc in ascending order
 #include "pcabo_internal.h"
 #include "acq_math.h"
-
-__global__ __launch_bounds__(256) void k_post_gemm(const double* __restrict__ R, const double* __restrict__ KS,
-                                                   int q_total, int NP, int ld, int njb, double* __restrict__ partial,
-                                                   double* __restrict__ V /* NP x q_total, or null */, size_t zs, size_t vzs) {
-  ZRUN(R); ZRUN(KS); ZRUN(partial);
-  V = zrun(V, vzs, blockIdx.z);
-  __shared__ __attribute__((aligned(16))) double s_a[64 * PCABO_TLD];
-  __shared__ __attribute__((aligned(16))) double s_b[64 * PCABO_TLD];
-  __shared__ double s_red[4][64];
-  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-  const int I = blockIdx.x, qb = blockIdx.y, S = gridDim.x;
-  const double* Rrow = R + (size_t)(I * 64) * ld;
-  const double* Krow = KS + (size_t)(qb * 64) * ld;
-  double pa[16], pb[16];
-  auto fetch = [&](int J) {
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
-      pa[u] = Rrow[(size_t)r * ld + J * 64 + c];
-      pb[u] = (qb * 64 + r < q_total) ? Krow[(size_t)r * ld + J * 64 + c] : 0.0;
-    }
-  };
-  auto put = [&]() {
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
-      s_a[r * PCABO_TLD + c] = pa[u];
-      s_b[r * PCABO_TLD + c] = pb[u];
-    }
-  };
-  double4_t acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  fetch(0);
-  for (int J = 0; J <= I; ++J) {              // R is lower triangular: column blocks beyond the diagonal hold zeros
-    __syncthreads();                          // the previous step's MFMAs have read the LDS tiles
-    put();
-    if (J < I) fetch(J + 1);
-    __syncthreads();
-    for (int kk = 0; kk < 64; kk += 4) {
-      const double a = s_a[(16 * w + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const double b = s_b[(16 * t + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
-        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
-      }
-    }
-  }
-  // acc[t][r] = V[16 w + (l >> 4) + 4 r][16 t + (l & 15)] of this tile: the tile itself, then its column norms
-  if (V) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int a = qb * 64 + 16 * t + (l & 15);
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (a < q_total) V[(size_t)(I * 64 + 16 * w + (l >> 4) + 4 * r) * q_total + a] = acc[t][r];
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    double v = ((acc[t][0] * acc[t][0] + acc[t][1] * acc[t][1]) + acc[t][2] * acc[t][2]) + acc[t][3] * acc[t][3];
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    if (l < 16) s_red[w][16 * t + l] = v;
-  }
-  __syncthreads();
-  if (tid < 64 && qb * 64 + tid < q_total) {
-    double* rec = partial + ((size_t)(qb * 64 + tid) * S + I) * PCABO_PSTRIDE;
-    rec[0] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
-    if (I >= njb) rec[1] = 0.0;               // (records 0 .. njb-1 got their mu_s part from k_score_ks)
-  }
-}
 
 // One wave per query: out[q] = mean, out[q_total + q] = variance (floored), out[2 q_total + q] = the variance before the floor.
 __global__ __launch_bounds__(256) void k_post_combine(const double* __restrict__ partial, int q_total, int S,
@@ -139,43 +68,13 @@ __global__ __launch_bounds__(256) void k_post_cov(const double* __restrict__ V, 
   int A = 0, Bt = blockIdx.x;
   while (Bt > A) { Bt -= A + 1; ++A; }       // lower tiles row by row: (0,0) (1,0) (1,1) (2,0) ...
   const size_t Q = (size_t)q_total;
-  double pa[16], pb[16];
-  auto fetch = [&](int P) {                   // rows 64 P .. of V: the columns of tile A and of tile Bt (zeros beyond q)
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
-      const double* row = V + (size_t)(P * 64 + r) * Q;
-      pa[u] = (A * 64 + c < q_total) ? row[A * 64 + c] : 0.0;
-      pb[u] = (Bt * 64 + c < q_total) ? row[Bt * 64 + c] : 0.0;
-    }
-  };
-  auto put = [&]() {
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
-      s_a[r * PCABO_TLD + c] = pa[u];
-      s_b[r * PCABO_TLD + c] = pb[u];
-    }
-  };
   double4_t acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  const int nP = NP / 64;
-  fetch(0);
-  for (int P = 0; P < nP; ++P) {              // row blocks in ascending order: the sum does not depend on a schedule
-    __syncthreads();
-    put();
-    if (P + 1 < nP) fetch(P + 1);
-    __syncthreads();
-    for (int kk = 0; kk < 64; kk += 4) {      // the tiles lie [row of V][query]: operand (query 16 w + (l & 15), row kk + (l >> 4))
-      const double a = s_a[(kk + (l >> 4)) * PCABO_TLD + 16 * w + (l & 15)];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const double b = s_b[(kk + (l >> 4)) * PCABO_TLD + 16 * t + (l & 15)];
-        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
-      }
-    }
-  }
+  // rows 64 P .. of V, ascending: the columns of tile A and of tile Bt (zeros beyond q).  The tiles lie [row of V][query]
+  tile_product_f64<true>(s_a, s_b, NP / 64, [&](int P, int r, int c, double& a, double& b) {
+    const double* row = V + (size_t)(P * 64 + r) * Q;
+    a = (A * 64 + c < q_total) ? row[A * 64 + c] : 0.0;
+    b = (Bt * 64 + c < q_total) ? row[Bt * 64 + c] : 0.0;
+  }, acc);
   // acc[t][r] = (V^T V)[64 A + 16 w + (l >> 4) + 4 r][64 Bt + 16 t + (l & 15)].  The prior part: squared distances of the
   // normalised queries in the direct form, 64 coordinates at a time through the two tiles (query, coordinate), ascending.
   double sq[4][4];
@@ -234,9 +133,9 @@ __global__ __launch_bounds__(256) void k_post_cov(const double* __restrict__ V, 
 // into post[3 q] and, with V / cov given, the q x q covariance.  B > 1: the runs of a batch (strides zs; vzs between their V / cov).
 void launch_posterior(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double s2, int obs_noise,
                       double* KS, double* partial, double* post, double* V, double* cov, AcqBatch ab, size_t vzs, int B) {
-  const int S = m.NP / 64, njb = (m.NP + 255) / 256;
+  const int S = m.NP / 64;
   launch_score_ks(st, Xq, q, m, p, KS, partial, ab, B);
-  hipLaunchKernelGGL(k_post_gemm, dim3(S, (q + 63) / 64, B), dim3(256), 0, st, m.R, KS, q, m.NP, m.ld, njb, partial, V, ab.zs, vzs);
+  launch_score_gemm(st, m, q, KS, partial, ab.zs, B, V, vzs);
   hipLaunchKernelGGL(k_post_combine, dim3((q + 3) / 4, 1, B), dim3(256), 0, st, partial, q, S, m.ystats, s2, obs_noise, post, ab.zs,
                      ab.hyp);
   if (!cov) return;
@@ -287,42 +186,13 @@ __global__ __launch_bounds__(256) void k_post_sample(const double* __restrict__ 
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
   const int s0 = blockIdx.x * 64, A = blockIdx.y;
   const size_t Q = (size_t)q_total;
-  double pa[16], pb[16];
-  auto fetch = [&](int J) {                   // base rows s0 .., columns 64 J ..; Lc rows 64 A .., columns 64 J ..
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
-      const int b = J * 64 + c, a = A * 64 + r;
-      pa[u] = (s0 + r < S && b < q_total) ? base[(size_t)(s0 + r) * Q + b] : 0.0;
-      pb[u] = (a < q_total && b <= a) ? F[(size_t)a * QP + b] : 0.0;      // (b <= a < q: the lower triangle of the q x q part)
-    }
-  };
-  auto put = [&]() {
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
-      s_a[r * PCABO_TLD + c] = pa[u];
-      s_b[r * PCABO_TLD + c] = pb[u];
-    }
-  };
   double4_t acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  fetch(0);
-  for (int J = 0; J <= A; ++J) {              // ascending column blocks: the sum does not depend on a schedule
-    __syncthreads();
-    put();
-    if (J < A) fetch(J + 1);
-    __syncthreads();
-    for (int kk = 0; kk < 64; kk += 4) {
-      const double a = s_a[(16 * w + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const double b = s_b[(16 * t + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
-        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
-      }
-    }
-  }
+  // ascending column blocks J <= A: base rows s0 .., columns 64 J ..; Lc rows 64 A .., columns 64 J ..
+  tile_product_f64<false>(s_a, s_b, A + 1, [&](int J, int r, int c, double& pa, double& pb) {
+    const int b = J * 64 + c, a = A * 64 + r;
+    pa = (s0 + r < S && b < q_total) ? base[(size_t)(s0 + r) * Q + b] : 0.0;
+    pb = (a < q_total && b <= a) ? F[(size_t)a * QP + b] : 0.0;      // (b <= a < q: the lower triangle of the q x q part)
+  }, acc);
   // acc[t][r] = (base Lc^T)[s0 + 16 w + (l >> 4) + 4 r][64 A + 16 t + (l & 15)]
 #pragma unroll
   for (int t = 0; t < 4; ++t) {

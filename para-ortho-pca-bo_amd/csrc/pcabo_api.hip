@@ -119,7 +119,7 @@ struct pcabo_ctx {
                                          // ARD: 1 + KP sums per tile, then the 5 + KP results (k_mll_finish_ard)
   double* dArdLs = nullptr;              // ARD fit: the k lengthscales k_zstats folds into the Normalize ranges
   double* dHyp = nullptr;                // lock-step fit of a batch: this run's {1 / lengthscale, noise, mean constant} (PCABO_HYP_*)
-  double* dPostV = nullptr;              // pcabo_gp_posterior with a covariance: V (NPcap x max_q), then cov (max_q^2); allocated
+  char* dPostV = nullptr;                // pcabo_gp_posterior with a covariance: V (NPcap x max_q), then cov (max_q^2); allocated
                                          // by the first such call, kept until destroy
   char* dSample = nullptr;               // pcabo_gp_posterior_sample: the sample block (SampleBlock), allocated by the first such call
   char *dRegion = nullptr, *hRegion = nullptr;   // the two allocations everything above / below is carved from
@@ -1258,139 +1258,6 @@ int pcabo_logei(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maxi
   return pcabo_acq_eval(ctx, Xq, q, best_f, maximize, PCABO_ACQ_LOG_EI, val, grad);
 }
 
-// ---- posterior queries (DESIGN.md "GP posterior queries") -------------------------------------------------------------------
-// The scoring launches up to the scalar chain, then mean and variance per query and, on request, the joint covariance
-// (kernels_post.hip).  The queries go straight from the caller's array to dXq and the results straight from the device to the
-// caller's arrays: of the context's state only dXq, dKS and dPartial are written, which every evaluation writes before it reads.
-// No sequence number is taken, no ticket touched, the second stream not used.
-static const char* post_arg_error(const double* Xq, int q, int max_q, int flags, bool any_out, int known = PCABO_POST_OBS_NOISE) {
-  if (!Xq) return "Xq is required";
-  if (q < 1 || q > max_q) return "q must lie in 1 .. max_q";
-  if (!any_out) return "mean, var and cov are all NULL";
-  if (flags & ~known) return "unknown flag bits";
-  return nullptr;
-}
-// ... and what a sampling call adds to them
-static const char* sample_arg_error(const double* Xq, int q, int max_q, int flags, const double* base, int S, const double* samples) {
-  if (const char* why = post_arg_error(Xq, q, max_q, flags, true, PCABO_POST_OBS_NOISE | PCABO_POST_CENTRED)) return why;
-  if (!base || !samples) return "base and samples are required";
-  if (S < 1 || S > PCABO_POST_MAX_SAMPLES) return "S must lie in 1 .. PCABO_POST_MAX_SAMPLES";
-  return nullptr;
-}
-// doubles of a context's (or of one run's) V block; its cov block (max_q^2) lies behind it
-static size_t post_v_doubles(const pcabo_ctx* c) { return (size_t)c->NPcap * c->max_q; }
-// mean | variance | unfloored variance of a call with q queries: behind the q S records of the scoring in dPartial, whose
-// capacity (max_q NPcap / 16 records) is four times what the 64-row blocks of the GEMM route ever use
-static double* post_out(const pcabo_ctx* c, int NP, int q) { return c->dPartial + (size_t)q * (NP / 64) * PCABO_PSTRIDE; }
-
-int pcabo_gp_posterior(pcabo_ctx* ctx, const double* Xq, int q, int flags, double* mean, double* var, double* cov) {
-  if (!ctx) return PCABO_ERR_ARG;
-  if (const char* why = post_arg_error(Xq, q, ctx->max_q, flags, mean || var || cov))
-    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior: %s", why);
-  if (ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior: a conditioning is in flight, call pcabo_gp_condition_end first%s", "");
-  if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior: no conditioned GP, call pcabo_gp_condition first%s", "");
-  HIPCHK(hipSetDevice(ctx->device));
-  if (cov && !ctx->dPostV) HIPCHK(dalloc(&ctx->dPostV, post_v_doubles(ctx) + (size_t)ctx->max_q * ctx->max_q));
-  hipStream_t s = ctx->stream;
-  const bool host = ctx->ptr_mode == PCABO_PTR_HOST;
-  const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  HIPCHK(hipMemcpyAsync(ctx->dXq, Xq, (size_t)q * ctx->k * sizeof(double), in, s));
-  const AcqParams p = make_params(ctx, 0.0, 1, PCABO_ACQ_UCB, 0);      // (the kernels read 1 / lengthscale and the kernel code)
-  const GpModel m = gp_model(ctx);
-  double* post = post_out(ctx, ctx->NP, q);
-  double* dcov = cov ? ctx->dPostV + post_v_doubles(ctx) : nullptr;
-  launch_posterior(s, ctx->dXq, q, m, p, ctx->noise, flags & PCABO_POST_OBS_NOISE, ctx->dKS, ctx->dPartial, post, cov ? ctx->dPostV : nullptr, dcov);
-  if (mean) HIPCHK(hipMemcpyAsync(mean, post, (size_t)q * sizeof(double), out, s));
-  if (var) HIPCHK(hipMemcpyAsync(var, post + q, (size_t)q * sizeof(double), out, s));
-  if (cov) HIPCHK(hipMemcpyAsync(cov, dcov, (size_t)q * q * sizeof(double), out, s));
-  HIPCHK(wait_stream(s));
-  HIPCHK(hipGetLastError());
-  return PCABO_OK;
-}
-
-// ---- posterior samples (DESIGN.md "GP posterior samples") ---------------------------------------------------------------------
-// The posterior query with its covariance, then cov + j s_y^2 I factored in a block of its own and the triangular product with the
-// caller's base samples.  The factorisation is the GP's (launch_cholesky) on the sample block's own info word and scratch tiles:
-// dInfo, dDiag and the host mirror's chol_info belong to the GP's factorisation and are not touched.
-//
-// One run's sample block: factor | two scratch tiles | base | samples | info word.  launch_cholesky applies ONE stride to the matrix,
-// the info word and the scratch, so in a batch the runs' blocks lie `bytes` apart and that stride serves all of them.
-struct SampleBlock {
-  size_t factor, diag, base, out, info, bytes;        // byte offsets inside the block; bytes: the block, a multiple of 256
-  explicit SampleBlock(int max_q) {
-    const size_t QP = (size_t)round_up(max_q, PCABO_BS), cap = (size_t)PCABO_POST_MAX_SAMPLES * max_q;
-    factor = 0;
-    diag = factor + QP * QP * sizeof(double);
-    base = diag + (size_t)2 * PCABO_BS * PCABO_BS * sizeof(double);
-    out = base + cap * sizeof(double);
-    info = out + cap * sizeof(double);
-    bytes = (info + sizeof(int) + 255) & ~(size_t)255;
-  }
-  double* F(char* p) const { return reinterpret_cast<double*>(p + factor); }
-  double* D(char* p) const { return reinterpret_cast<double*>(p + diag); }
-  double* Bs(char* p) const { return reinterpret_cast<double*>(p + base); }
-  double* Out(char* p) const { return reinterpret_cast<double*>(p + out); }
-  int* Info(char* p) const { return reinterpret_cast<int*>(p + info); }
-};
-static const double kSampleRungs[4] = {0.0, 1e-8, 1e-7, 1e-6};      // relative to s_y^2: the ladder of cholesky_attempts
-
-// One rung for B runs (blk: run 0's block, zb.zs: the block stride): prep from the untouched cov, the factorisation, the info
-// words on their way to the host.  PCABO_OK, or PCABO_ERR_HIP when nothing could be launched.
-static int sample_factor_enqueue(hipStream_t s, const SampleBlock& L, char* blk, const double* cov, const double* ystats, int q,
-                                 double jitter, size_t zs, size_t vzs, ZB zb, int* info_host) {
-  const int QP = round_up(q, PCABO_BS);
-  launch_post_chol_prep(s, cov, q, ystats, jitter, L.F(blk), L.Info(blk), zs, vzs, zb.zs, zb.B);
-  if (launch_cholesky(s, L.F(blk), QP, QP, L.Info(blk), L.D(blk), zb) != 0) return PCABO_ERR_HIP;
-  const hipError_t e = zb.B > 1 ? hipMemcpy2DAsync(info_host, sizeof(int), L.Info(blk), zb.zs, sizeof(int), zb.B, hipMemcpyDeviceToHost, s)
-                                : hipMemcpyAsync(info_host, L.Info(blk), sizeof(int), hipMemcpyDeviceToHost, s);
-  return e == hipSuccess ? PCABO_OK : PCABO_ERR_HIP;
-}
-// The ladder of one run from rung `first` on: the rung that could be factored (0 .. 3), -1 when none could, -2 on a HIP error
-static int sample_ladder(hipStream_t s, const SampleBlock& L, char* blk, const double* cov, const double* ystats, int q, int first) {
-  for (int r = first; r < 4; ++r) {
-    int info = -1;
-    if (sample_factor_enqueue(s, L, blk, cov, ystats, q, kSampleRungs[r], 0, 0, ZB(), &info) != PCABO_OK) return -2;
-    if (wait_stream(s) != hipSuccess) return -2;
-    if (info == 0) return r;
-  }
-  return -1;
-}
-
-int pcabo_gp_posterior_sample(pcabo_ctx* ctx, const double* Xq, int q, int flags, const double* base, int S, double* samples,
-                              double* mean, double* jitter_used) {
-  if (!ctx) return PCABO_ERR_ARG;
-  if (const char* why = sample_arg_error(Xq, q, ctx->max_q, flags, base, S, samples))
-    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior_sample: %s", why);
-  if (ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior_sample: a conditioning is in flight, call pcabo_gp_condition_end first%s", "");
-  if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior_sample: no conditioned GP, call pcabo_gp_condition first%s", "");
-  HIPCHK(hipSetDevice(ctx->device));
-  const SampleBlock L(ctx->max_q);
-  if (!ctx->dPostV) HIPCHK(dalloc(&ctx->dPostV, post_v_doubles(ctx) + (size_t)ctx->max_q * ctx->max_q));
-  if (!ctx->dSample) HIPCHK(dalloc(&ctx->dSample, L.bytes));
-  hipStream_t s = ctx->stream;
-  const bool host = ctx->ptr_mode == PCABO_PTR_HOST;
-  const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  char* blk = ctx->dSample;
-  HIPCHK(hipMemcpyAsync(ctx->dXq, Xq, (size_t)q * ctx->k * sizeof(double), in, s));
-  HIPCHK(hipMemcpyAsync(L.Bs(blk), base, (size_t)S * q * sizeof(double), in, s));
-  const AcqParams p = make_params(ctx, 0.0, 1, PCABO_ACQ_UCB, 0);
-  const GpModel m = gp_model(ctx);
-  double* post = post_out(ctx, ctx->NP, q);
-  double* dcov = ctx->dPostV + post_v_doubles(ctx);
-  launch_posterior(s, ctx->dXq, q, m, p, ctx->noise, flags & PCABO_POST_OBS_NOISE, ctx->dKS, ctx->dPartial, post, ctx->dPostV, dcov);
-  const int rung = sample_ladder(s, L, blk, dcov, m.ystats, q, 0);
-  if (rung == -2) return set_err(ctx, PCABO_ERR_HIP, "pcabo_gp_posterior_sample: HIP error: %s", hipGetErrorString(hipGetLastError()));
-  if (rung < 0)
-    return set_err(ctx, PCABO_ERR_NOT_PD, "pcabo_gp_posterior_sample: the posterior covariance of the %s%d queries is not positive definite after the jitter retries", "", q);
-  launch_post_sample(s, L.F(blk), q, L.Bs(blk), S, (flags & PCABO_POST_CENTRED) ? nullptr : post, L.Out(blk));
-  HIPCHK(hipMemcpyAsync(samples, L.Out(blk), (size_t)S * q * sizeof(double), out, s));
-  if (mean) HIPCHK(hipMemcpyAsync(mean, post, (size_t)q * sizeof(double), out, s));
-  HIPCHK(wait_stream(s));
-  HIPCHK(hipGetLastError());
-  if (jitter_used) *jitter_used = kSampleRungs[rung];
-  return PCABO_OK;
-}
-
 // ---- resident acquisition kernel: host side of the mailbox ---------------------------------------------------------
 // One round: all cap*k coordinate pairs get the round's tag (coordinates of queries that are no longer active are
 // whatever is left in hXq), then one control pair per query (1 = evaluate, 0 = leave for good).  A pair leaves in one 16-byte store and
@@ -1764,8 +1631,8 @@ struct pcabo_batch {
   // debug record of the last optimise call on the device path (pcabo_debug_batch_lbfgsb_*; tests): the twin's branch counters
   // [B][groups][LBB_COUNT], or the eight doubles per group the kernel wrote [B][groups][8]
   std::vector<unsigned> dbg_branches; std::vector<double> dbg_group_out; int dbg_groups = 0;
-  char* dPost = nullptr; size_t post_vzs = 0;        // pcabo_batch_gp_posterior with a covariance: every run's V and cov block, post_vzs
-                                                     // bytes apart (one allocation, made by the first such call)
+  char* dPost = nullptr;                             // pcabo_batch_gp_posterior with a covariance: every run's V and cov block,
+                                                     // PostSite::post_bytes apart (one allocation, made by the first such call)
   char* dSample = nullptr;                           // pcabo_batch_gp_posterior_sample: every run's SampleBlock, its `bytes` apart
   unsigned *dOptTab = nullptr, *hOptTab = nullptr;   // launch table of the device-resident optimiser (B * 32 entries)
   int G = 0;                             // gangs = worker threads of the L-BFGS-B phase
@@ -2400,108 +2267,237 @@ int pcabo_batch_gp_condition_end_eval_end(pcabo_batch* batch, const double* Xq, 
   return batch_score_collect(batch, Xq, q, best_f, maximize, acq, val, status);
 }
 
-// pcabo_gp_posterior for the runs of a batch: one launch sequence (blockIdx.z = run), every run at its own k and - after a lock-step
-// fit - its own lengthscale and noise.  Parked runs and runs without a GP are computed with the others and not handed out.
+// ---- posterior queries and samples, of a context and of the runs of a batch (DESIGN.md "GP posterior queries" / "samples") -----
+// Query: the scoring launches up to the scalar chain, then mean and variance per query and, on request, the joint covariance
+// (kernels_post.hip).  The queries go straight from the caller's array to dXq: of the state only dXq, dKS and dPartial are written,
+// which every evaluation writes before it reads.  No sequence number is taken, no ticket touched, the second stream not used.
+// Samples: the query with its covariance, then cov + j s_y^2 I factored in a block of its own and the triangular product with the
+// caller's base samples.  The factorisation is the GP's (launch_cholesky) on the sample block's own info word and scratch tiles:
+// dInfo, dDiag and the host mirror's chol_info belong to the GP's factorisation and are not touched.
+// A batch is one launch sequence (blockIdx.z = run), every run at its own k and - after a lock-step fit - its own lengthscale and
+// noise; parked runs and runs without a GP are computed with the others and not handed out.  A context is the same with one run.
+static const char* post_arg_error(const double* Xq, int q, int max_q, int flags, bool any_out, int known = PCABO_POST_OBS_NOISE) {
+  if (!Xq) return "Xq is required";
+  if (q < 1 || q > max_q) return "q must lie in 1 .. max_q";
+  if (!any_out) return "mean, var and cov are all NULL";
+  if (flags & ~known) return "unknown flag bits";
+  return nullptr;
+}
+// ... and what a sampling call adds to them
+static const char* sample_arg_error(const double* Xq, int q, int max_q, int flags, const double* base, int S, const double* samples) {
+  if (const char* why = post_arg_error(Xq, q, max_q, flags, true, PCABO_POST_OBS_NOISE | PCABO_POST_CENTRED)) return why;
+  if (!base || !samples) return "base and samples are required";
+  if (S < 1 || S > PCABO_POST_MAX_SAMPLES) return "S must lie in 1 .. PCABO_POST_MAX_SAMPLES";
+  return nullptr;
+}
+
+// One run's sample block: factor | two scratch tiles | base | samples | info word.  launch_cholesky applies ONE stride to the matrix,
+// the info word and the scratch, so in a batch the runs' blocks lie `bytes` apart and that stride serves all of them.
+struct SampleBlock {
+  size_t factor, diag, base, out, info, bytes;        // byte offsets inside the block; bytes: the block, a multiple of 256
+  explicit SampleBlock(int max_q) {
+    const size_t QP = (size_t)round_up(max_q, PCABO_BS), cap = (size_t)PCABO_POST_MAX_SAMPLES * max_q;
+    factor = 0;
+    diag = factor + QP * QP * sizeof(double);
+    base = diag + (size_t)2 * PCABO_BS * PCABO_BS * sizeof(double);
+    out = base + cap * sizeof(double);
+    info = out + cap * sizeof(double);
+    bytes = (info + sizeof(int) + 255) & ~(size_t)255;
+  }
+  double* F(char* p) const { return reinterpret_cast<double*>(p + factor); }
+  double* D(char* p) const { return reinterpret_cast<double*>(p + diag); }
+  double* Bs(char* p) const { return reinterpret_cast<double*>(p + base); }
+  double* Out(char* p) const { return reinterpret_cast<double*>(p + out); }
+  int* Info(char* p) const { return reinterpret_cast<int*>(p + info); }
+};
+static const double kSampleRungs[4] = {0.0, 1e-8, 1e-7, 1e-6};      // relative to s_y^2: the ladder of cholesky_attempts
+
+// Where a posterior call runs: a context, or the B runs of a batch (run 0's buffers, the others zs bytes apart).  A context is the
+// view with one run, every stride 0 and the default AcqBatch, so its launches carry the arguments of a single context.
+struct PostSite {
+  pcabo_ctx* ctx = nullptr;          // the context asked ...
+  pcabo_batch* batch = nullptr;      // ... or the batch: whose error text is written
+  pcabo_ctx* c0;                     // the context, or run 0: dXq, dKS and dPartial of the launches
+  hipStream_t s; int device, B = 1; size_t zs = 0;
+  bool busy, have_gp;
+  int xq_cols;                       // coordinates per staged query: k, or the largest k of the runs
+  GpModel m; AcqParams p; AcqBatch ab; double noise;
+  char** post_slot; size_t post_v, post_bytes, vzs = 0;   // the runs' V | cov blocks: V's doubles, a block's bytes, the launches' stride
+  char** sample_slot; SampleBlock L; size_t szs = 0;      // the runs' sample blocks and the launches' stride
+  hipMemcpyKind in = hipMemcpyHostToDevice, out = hipMemcpyDeviceToHost;
+
+  PostSite(pcabo_ctx* run0, int max_q, char** post, char** sample)      // both views: V (NPcap x max_q), cov (max_q^2) behind it
+      : c0(run0), post_slot(post), post_v((size_t)run0->NPcap * run0->max_q),
+        post_bytes(((post_v + (size_t)max_q * max_q) * sizeof(double) + 255) & ~(size_t)255), sample_slot(sample), L(max_q) {}
+  explicit PostSite(pcabo_ctx* c) : PostSite(c, c->max_q, &c->dPostV, &c->dSample) {
+    ctx = c; s = c->stream; device = c->device; busy = c->gp_pending; have_gp = c->have_gp; xq_cols = c->k; noise = c->noise;
+    m = gp_model(c); p = make_params(c, 0.0, 1, PCABO_ACQ_UCB, 0);      // (the kernels read 1 / lengthscale and the kernel code)
+    if (c->ptr_mode != PCABO_PTR_HOST) in = out = hipMemcpyDeviceToDevice;
+  }
+  explicit PostSite(pcabo_batch* b) : PostSite(b->ctx[0], b->max_q, &b->dPost, &b->dSample) {
+    batch = b; s = b->stream; device = b->device; B = b->B; zs = b->zs; vzs = post_bytes; szs = L.bytes; noise = b->noise;
+    busy = b->gp_pending || b->score_enqueued || b->opt_enqueued || b->imap_enqueued; have_gp = b->have_gp; xq_cols = batch_max_k(b);
+    m = gp_model(b, xq_cols); p = batch_params(b, 1, PCABO_ACQ_UCB, 0); ab = batch_ab(b, 0, 0);
+  }
+  int fail(int code, const char* fmt, const char* a = "", int v = 0) const {
+    return batch ? bset_err(batch, code, fmt, a, v) : set_err(ctx, code, fmt, a, v);
+  }
+  bool live(int b) const { return !batch || (batch->active[b] && batch->ctx[b]->have_gp); }   // is run b's result handed out?
+  double* V() const { return reinterpret_cast<double*>(*post_slot); }
+  double* cov(int b = 0) const { return reinterpret_cast<double*>(*post_slot + (size_t)b * post_bytes) + post_v; }
+  char* blk(int b = 0) const { return *sample_slot + (size_t)b * L.bytes; }
+  // mean | variance | unfloored variance of a call with q queries: behind the q S records of the scoring in dPartial, whose
+  // capacity (max_q NPcap / 16 records) is four times what the 64-row blocks of the GEMM route ever use
+  double* post(int q) const { return c0->dPartial + (size_t)q * (m.NP / 64) * PCABO_PSTRIDE; }
+};
+#define PHIPCHK(call)                                                                                           \
+  do {                                                                                                          \
+    hipError_t e_ = (call);                                                                                     \
+    if (e_ != hipSuccess) return w.fail(PCABO_ERR_HIP, "HIP error: %s (line %d)", hipGetErrorString(e_), __LINE__); \
+  } while (0)
+
+// The query of `name` on its way: state checks, the V | cov blocks and the sample blocks on their first use, Xq staged, the
+// launches.  want_cov: with V and the covariance; want_samples: the sample blocks exist afterwards.
+static int post_enqueue(const PostSite& w, const char* name, const double* Xq, int q, int flags, bool want_cov, bool want_samples) {
+  if (w.busy)
+    return w.fail(PCABO_ERR_ARG, w.batch ? "%s: a conditioning or a _begin call of this batch has not been ended"
+                                         : "%s: a conditioning is in flight, call pcabo_gp_condition_end first", name);
+  if (!w.have_gp) return w.fail(PCABO_ERR_ARG, w.batch ? "%s: no conditioned GP" : "%s: no conditioned GP, call pcabo_gp_condition first", name);
+  PHIPCHK(hipSetDevice(w.device));
+  if (want_cov && !*w.post_slot) PHIPCHK(hipMalloc((void**)w.post_slot, w.post_bytes * (size_t)w.B));
+  if (want_samples && !*w.sample_slot) PHIPCHK(hipMalloc((void**)w.sample_slot, w.L.bytes * (size_t)w.B));
+  if (w.batch)
+    PHIPCHK(hipMemcpy2DAsync(w.c0->dXq, w.zs, Xq, (size_t)q * w.batch->max_d * sizeof(double), (size_t)q * w.xq_cols * sizeof(double),
+                             w.B, w.in, w.s));
+  else
+    PHIPCHK(hipMemcpyAsync(w.c0->dXq, Xq, (size_t)q * w.xq_cols * sizeof(double), w.in, w.s));
+  launch_posterior(w.s, w.c0->dXq, q, w.m, w.p, w.noise, flags & PCABO_POST_OBS_NOISE, w.c0->dKS, w.c0->dPartial, w.post(q),
+                   want_cov ? w.V() : nullptr, want_cov ? w.cov() : nullptr, w.ab, w.vzs, w.B);
+  return PCABO_OK;
+}
+
+// One rung for zb.B runs (blk: the first one's block, zb.zs: the block stride): prep from the untouched cov, the factorisation, the
+// info words on their way to the host.  PCABO_OK, or PCABO_ERR_HIP when nothing could be launched.
+static int sample_factor_enqueue(hipStream_t s, const SampleBlock& L, char* blk, const double* cov, const double* ystats, int q,
+                                 double jitter, size_t zs, size_t vzs, ZB zb, int* info_host) {
+  const int QP = round_up(q, PCABO_BS);
+  launch_post_chol_prep(s, cov, q, ystats, jitter, L.F(blk), L.Info(blk), zs, vzs, zb.zs, zb.B);
+  if (launch_cholesky(s, L.F(blk), QP, QP, L.Info(blk), L.D(blk), zb) != 0) return PCABO_ERR_HIP;
+  const hipError_t e = zb.B > 1 ? hipMemcpy2DAsync(info_host, sizeof(int), L.Info(blk), zb.zs, sizeof(int), zb.B, hipMemcpyDeviceToHost, s)
+                                : hipMemcpyAsync(info_host, L.Info(blk), sizeof(int), hipMemcpyDeviceToHost, s);
+  return e == hipSuccess ? PCABO_OK : PCABO_ERR_HIP;
+}
+
+// The query with its covariance, the base samples staged, then the jitter ladder: the first rung as one launch sequence for all
+// runs; a live run whose info word is not 0 climbs the other rungs alone on its own block, with the launches of a single context.
+// rung[b]: the rung that could be factored (0 .. 3), -1 when none could or the run is not live.
+static int sample_enqueue(const PostSite& w, const char* name, const double* Xq, int q, int flags, const double* base, int S, int* rung) {
+  if (const int rc = post_enqueue(w, name, Xq, q, flags, true, true)) return rc;
+  const SampleBlock& L = w.L;
+  const size_t row = (size_t)S * q * sizeof(double);
+  if (w.batch) PHIPCHK(hipMemcpy2DAsync(L.Bs(w.blk()), L.bytes, base, row, row, w.B, w.in, w.s));
+  else PHIPCHK(hipMemcpyAsync(L.Bs(w.blk()), base, row, w.in, w.s));
+  std::vector<int> info((size_t)w.B, -1);
+  ZB zb; zb.B = w.B; zb.zs = w.szs;
+  if (sample_factor_enqueue(w.s, L, w.blk(), w.cov(), w.m.ystats, q, kSampleRungs[0], w.zs, w.vzs, zb, info.data()) != PCABO_OK)
+    return w.fail(PCABO_ERR_HIP, "%s: the factorisation could not be launched", name);
+  PHIPCHK(wait_stream(w.s));
+  for (int b = 0; b < w.B; ++b) {
+    rung[b] = w.live(b) && info[b] == 0 ? 0 : -1;
+    const double* ystats_b = reinterpret_cast<const double*>(reinterpret_cast<const char*>(w.m.ystats) + (size_t)b * w.zs);
+    for (int r = 1; r < 4 && w.live(b) && rung[b] < 0; ++r) {
+      if (sample_factor_enqueue(w.s, L, w.blk(b), w.cov(b), ystats_b, q, kSampleRungs[r], 0, 0, ZB(), &info[b]) != PCABO_OK)
+        return w.fail(PCABO_ERR_HIP, "%s: the factorisation could not be launched", name);
+      PHIPCHK(wait_stream(w.s));
+      if (info[b] == 0) rung[b] = r;
+    }
+  }
+  return PCABO_OK;
+}
+// ... and the product behind it, for all runs
+static void sample_product(const PostSite& w, int q, int flags, int S) {
+  launch_post_sample(w.s, w.L.F(w.blk()), q, w.L.Bs(w.blk()), S, (flags & PCABO_POST_CENTRED) ? nullptr : w.post(q), w.L.Out(w.blk()),
+                     w.zs, w.szs, w.B);
+}
+
+// A context copies straight from the device to the caller's arrays (device pointers in PCABO_PTR_DEVICE mode).
+int pcabo_gp_posterior(pcabo_ctx* ctx, const double* Xq, int q, int flags, double* mean, double* var, double* cov) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (const char* why = post_arg_error(Xq, q, ctx->max_q, flags, mean || var || cov))
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior: %s", why);
+  const PostSite w(ctx);
+  if (const int rc = post_enqueue(w, "pcabo_gp_posterior", Xq, q, flags, cov != nullptr, false)) return rc;
+  double* post = w.post(q);
+  if (mean) PHIPCHK(hipMemcpyAsync(mean, post, (size_t)q * sizeof(double), w.out, w.s));
+  if (var) PHIPCHK(hipMemcpyAsync(var, post + q, (size_t)q * sizeof(double), w.out, w.s));
+  if (cov) PHIPCHK(hipMemcpyAsync(cov, w.cov(), (size_t)q * q * sizeof(double), w.out, w.s));
+  PHIPCHK(wait_stream(w.s));
+  PHIPCHK(hipGetLastError());
+  return PCABO_OK;
+}
+
+int pcabo_gp_posterior_sample(pcabo_ctx* ctx, const double* Xq, int q, int flags, const double* base, int S, double* samples,
+                              double* mean, double* jitter_used) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (const char* why = sample_arg_error(Xq, q, ctx->max_q, flags, base, S, samples))
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_posterior_sample: %s", why);
+  const PostSite w(ctx);
+  int rung = -1;
+  if (const int rc = sample_enqueue(w, "pcabo_gp_posterior_sample", Xq, q, flags, base, S, &rung)) return rc;
+  if (rung < 0)
+    return set_err(ctx, PCABO_ERR_NOT_PD, "pcabo_gp_posterior_sample: the posterior covariance of the %s%d queries is not positive definite after the jitter retries", "", q);
+  sample_product(w, q, flags, S);
+  PHIPCHK(hipMemcpyAsync(samples, w.L.Out(w.blk()), (size_t)S * q * sizeof(double), w.out, w.s));
+  if (mean) PHIPCHK(hipMemcpyAsync(mean, w.post(q), (size_t)q * sizeof(double), w.out, w.s));
+  PHIPCHK(wait_stream(w.s));
+  PHIPCHK(hipGetLastError());
+  if (jitter_used) *jitter_used = kSampleRungs[rung];
+  return PCABO_OK;
+}
+
+// A batch gathers mean / variance of all runs with one 2-D copy and hands out only the live runs' results.
 int pcabo_batch_gp_posterior(pcabo_batch* batch, const double* Xq, int q, int flags, double* mean, double* var, double* cov, int* status) {
   if (!batch) return PCABO_ERR_ARG;
   if (const char* why = post_arg_error(Xq, q, batch->max_q, flags, mean || var || cov))
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior: %s", why);
-  if (batch->gp_pending || batch->score_enqueued || batch->opt_enqueued || batch->imap_enqueued)
-    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior: a conditioning or a _begin call of this batch has not been ended%s", "");
-  if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior: no conditioned GP%s", "");
-  BHIPCHK(hipSetDevice(batch->device));
-  hipStream_t s = batch->stream;
-  const int B = batch->B, kmax = batch_max_k(batch);
-  pcabo_ctx* c0 = batch->ctx[0];
-  if (cov && !batch->dPost) {
-    batch->post_vzs = ((post_v_doubles(c0) + (size_t)batch->max_q * batch->max_q) * sizeof(double) + 255) & ~(size_t)255;
-    BHIPCHK(hipMalloc((void**)&batch->dPost, batch->post_vzs * (size_t)B));
-  }
-  BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, Xq, (size_t)q * batch->max_d * sizeof(double), (size_t)q * kmax * sizeof(double), B,
-                           hipMemcpyHostToDevice, s));
-  const AcqParams p = batch_params(batch, 1, PCABO_ACQ_UCB, 0);
-  const GpModel m = gp_model(batch, kmax);
-  const AcqBatch ab = batch_ab(batch, 0, 0);
-  double* post = post_out(c0, batch->NP, q);
-  double* dV = cov ? reinterpret_cast<double*>(batch->dPost) : nullptr;
-  double* dcov = cov ? dV + post_v_doubles(c0) : nullptr;
-  launch_posterior(s, c0->dXq, q, m, p, batch->noise, flags & PCABO_POST_OBS_NOISE, c0->dKS, c0->dPartial, post, dV, dcov, ab, batch->post_vzs, B);
+  const PostSite w(batch);
+  if (const int rc = post_enqueue(w, "pcabo_batch_gp_posterior", Xq, q, flags, cov != nullptr, false)) return rc;
+  const int B = w.B;
   std::vector<double> mv((size_t)B * 2 * q);
-  BHIPCHK(hipMemcpy2DAsync(mv.data(), (size_t)2 * q * sizeof(double), post, batch->zs, (size_t)2 * q * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  PHIPCHK(hipMemcpy2DAsync(mv.data(), (size_t)2 * q * sizeof(double), w.post(q), w.zs, (size_t)2 * q * sizeof(double), B, w.out, w.s));
   for (int b = 0; b < B; ++b) {
-    const bool ok = batch->active[b] && batch->ctx[b]->have_gp;
-    if (status) status[b] = ok ? PCABO_OK : PCABO_ERR_ARG;
-    if (ok && cov)
-      BHIPCHK(hipMemcpyAsync(cov + (size_t)b * q * q, batch->dPost + (size_t)b * batch->post_vzs + post_v_doubles(c0) * sizeof(double),
-                             (size_t)q * q * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (status) status[b] = w.live(b) ? PCABO_OK : PCABO_ERR_ARG;
+    if (w.live(b) && cov) PHIPCHK(hipMemcpyAsync(cov + (size_t)b * q * q, w.cov(b), (size_t)q * q * sizeof(double), w.out, w.s));
   }
-  BHIPCHK(wait_stream(s));
-  BHIPCHK(hipGetLastError());
+  PHIPCHK(wait_stream(w.s));
+  PHIPCHK(hipGetLastError());
   for (int b = 0; b < B; ++b) {
-    if (!(batch->active[b] && batch->ctx[b]->have_gp)) continue;
+    if (!w.live(b)) continue;
     if (mean) memcpy(mean + (size_t)b * q, &mv[(size_t)b * 2 * q], (size_t)q * sizeof(double));
     if (var) memcpy(var + (size_t)b * q, &mv[(size_t)b * 2 * q + q], (size_t)q * sizeof(double));
   }
   return PCABO_OK;
 }
 
-// pcabo_gp_posterior_sample for the runs of a batch: the posterior with its covariance, the first rung and the product as one launch
-// sequence each (blockIdx.z = run, the sample blocks `bytes` apart); a run whose first rung fails climbs the rest of the ladder alone
-// on its own block, with the launches a single context makes.
 int pcabo_batch_gp_posterior_sample(pcabo_batch* batch, const double* Xq, int q, int flags, const double* base, int S, double* samples,
                                     double* mean, double* jitter_used, int* status) {
   if (!batch) return PCABO_ERR_ARG;
   if (const char* why = sample_arg_error(Xq, q, batch->max_q, flags, base, S, samples))
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior_sample: %s", why);
-  if (batch->gp_pending || batch->score_enqueued || batch->opt_enqueued || batch->imap_enqueued)
-    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior_sample: a conditioning or a _begin call of this batch has not been ended%s", "");
-  if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_posterior_sample: no conditioned GP%s", "");
-  BHIPCHK(hipSetDevice(batch->device));
-  hipStream_t s = batch->stream;
-  const int B = batch->B, kmax = batch_max_k(batch);
-  pcabo_ctx* c0 = batch->ctx[0];
-  const SampleBlock L(batch->max_q);
-  if (!batch->dPost) {
-    batch->post_vzs = ((post_v_doubles(c0) + (size_t)batch->max_q * batch->max_q) * sizeof(double) + 255) & ~(size_t)255;
-    BHIPCHK(hipMalloc((void**)&batch->dPost, batch->post_vzs * (size_t)B));
-  }
-  if (!batch->dSample) BHIPCHK(hipMalloc((void**)&batch->dSample, L.bytes * (size_t)B));
-  char* blk = batch->dSample;
-  const size_t row = (size_t)S * q * sizeof(double);
-  BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, Xq, (size_t)q * batch->max_d * sizeof(double), (size_t)q * kmax * sizeof(double), B,
-                           hipMemcpyHostToDevice, s));
-  BHIPCHK(hipMemcpy2DAsync(L.Bs(blk), L.bytes, base, row, row, B, hipMemcpyHostToDevice, s));
-  const AcqParams p = batch_params(batch, 1, PCABO_ACQ_UCB, 0);
-  const GpModel m = gp_model(batch, kmax);
-  const AcqBatch ab = batch_ab(batch, 0, 0);
-  double* post = post_out(c0, batch->NP, q);
-  double* dV = reinterpret_cast<double*>(batch->dPost);
-  double* dcov = dV + post_v_doubles(c0);
-  launch_posterior(s, c0->dXq, q, m, p, batch->noise, flags & PCABO_POST_OBS_NOISE, c0->dKS, c0->dPartial, post, dV, dcov, ab, batch->post_vzs, B);
-  std::vector<int> info((size_t)B, -1), rung((size_t)B, 0);
-  ZB zb; zb.B = B; zb.zs = L.bytes;
-  if (sample_factor_enqueue(s, L, blk, dcov, m.ystats, q, kSampleRungs[0], batch->zs, batch->post_vzs, zb, info.data()) != PCABO_OK)
-    return bset_err(batch, PCABO_ERR_HIP, "pcabo_batch_gp_posterior_sample: the factorisation could not be launched%s", "");
-  BHIPCHK(wait_stream(s));
-  for (int b = 0; b < B; ++b) {
-    const bool ok = batch->active[b] && batch->ctx[b]->have_gp;
-    if (!ok) { rung[b] = -1; if (status) status[b] = PCABO_ERR_ARG; continue; }
-    if (info[b] != 0) {
-      const double* cov_b = reinterpret_cast<const double*>(reinterpret_cast<const char*>(dcov) + (size_t)b * batch->post_vzs);
-      const double* ystats_b = reinterpret_cast<const double*>(reinterpret_cast<const char*>(m.ystats) + (size_t)b * batch->zs);
-      rung[b] = sample_ladder(s, L, blk + (size_t)b * L.bytes, cov_b, ystats_b, q, 1);
-      if (rung[b] == -2) return bset_err(batch, PCABO_ERR_HIP, "pcabo_batch_gp_posterior_sample: HIP error: %s", hipGetErrorString(hipGetLastError()));
-    }
-    if (status) status[b] = rung[b] >= 0 ? PCABO_OK : PCABO_ERR_NOT_PD;
-  }
-  launch_post_sample(s, L.F(blk), q, L.Bs(blk), S, (flags & PCABO_POST_CENTRED) ? nullptr : post, L.Out(blk), batch->zs, L.bytes, B);
+  const PostSite w(batch);
+  const int B = w.B;
+  std::vector<int> rung((size_t)B, -1);
+  if (const int rc = sample_enqueue(w, "pcabo_batch_gp_posterior_sample", Xq, q, flags, base, S, rung.data())) return rc;
+  sample_product(w, q, flags, S);
   std::vector<double> mv(mean ? (size_t)B * q : 0);
-  if (mean) BHIPCHK(hipMemcpy2DAsync(mv.data(), (size_t)q * sizeof(double), post, batch->zs, (size_t)q * sizeof(double), B, hipMemcpyDeviceToHost, s));
-  for (int b = 0; b < B; ++b)
+  if (mean) PHIPCHK(hipMemcpy2DAsync(mv.data(), (size_t)q * sizeof(double), w.post(q), w.zs, (size_t)q * sizeof(double), B, w.out, w.s));
+  for (int b = 0; b < B; ++b) {
+    if (status) status[b] = rung[b] >= 0 ? PCABO_OK : w.live(b) ? PCABO_ERR_NOT_PD : PCABO_ERR_ARG;
     if (rung[b] >= 0)
-      BHIPCHK(hipMemcpyAsync(samples + (size_t)b * S * q, L.Out(blk + (size_t)b * L.bytes), row, hipMemcpyDeviceToHost, s));
-  BHIPCHK(wait_stream(s));
-  BHIPCHK(hipGetLastError());
+      PHIPCHK(hipMemcpyAsync(samples + (size_t)b * S * q, w.L.Out(w.blk(b)), (size_t)S * q * sizeof(double), w.out, w.s));
+  }
+  PHIPCHK(wait_stream(w.s));
+  PHIPCHK(hipGetLastError());
   for (int b = 0; b < B; ++b) {
     if (rung[b] < 0) continue;
     if (mean) memcpy(mean + (size_t)b * q, &mv[(size_t)b * q], (size_t)q * sizeof(double));
@@ -2509,6 +2505,7 @@ int pcabo_batch_gp_posterior_sample(pcabo_batch* batch, const double* Xq, int q,
   }
   return PCABO_OK;
 }
+#undef PHIPCHK
 
 // a run's status at the start of an optimise call: parked by the caller, without a GP, or taking part
 static int batch_run_status(const pcabo_batch* batch, int b) {

@@ -194,6 +194,54 @@ __device__ inline double wave_sum(double v) {         // uniform result: sum ove
                           __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 
+// The LDS-staged 64 x 64 fp64 tile product of a work-group of 256 (k_score_gemm, k_post_cov, k_post_sample): `steps` steps of
+// depth 64, the operand tiles of a step through s_a / s_b (64 x PCABO_TLD doubles each), the next step's tiles travelling in
+// registers while the MFMAs of the current one run.  elem(step, r, c, a, b) names element (r, c) of the step's two tiles: the
+// caller's addressing, bounds guards and masks live there.  Wave w's acc[t] accumulates, steps and kk ascending,
+//   KMAJOR = false  sum_j s_a[16 w + i][j] s_b[16 t + i'][j]     (tiles [row][depth])
+//   KMAJOR = true   sum_j s_a[j][16 w + i] s_b[j][16 t + i']     (tiles [depth][row])
+// as acc[t][r] = result[16 w + (l >> 4) + 4 r][16 t + (l & 15)].  One MFMA order per accumulator for every caller: that order is
+// what gives |v|^2 the same bits in the scoring and in the posterior.  s_a / s_b may be reused after a barrier.
+template <bool KMAJOR, typename Elem>
+__device__ __forceinline__ void tile_product_f64(double* s_a, double* s_b, int steps, Elem elem, double4_t (&acc)[4]) {
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+  double pa[16], pb[16];
+  auto fetch = [&](int J) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u;
+      elem(J, idx >> 6, idx & 63, pa[u], pb[u]);
+    }
+  };
+  auto put = [&]() {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u, r = idx >> 6, c = idx & 63;
+      s_a[r * PCABO_TLD + c] = pa[u];
+      s_b[r * PCABO_TLD + c] = pb[u];
+    }
+  };
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  fetch(0);
+  for (int J = 0; J < steps; ++J) {
+    __syncthreads();                          // the previous step's MFMAs have read the LDS tiles
+    put();
+    if (J + 1 < steps) fetch(J + 1);
+    __syncthreads();
+    for (int kk = 0; kk < 64; kk += 4) {
+      const double a = KMAJOR ? s_a[(kk + (l >> 4)) * PCABO_TLD + 16 * w + (l & 15)]
+                              : s_a[(16 * w + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const double b = KMAJOR ? s_b[(kk + (l >> 4)) * PCABO_TLD + 16 * t + (l & 15)]
+                                : s_b[(16 * t + (l & 15)) * PCABO_TLD + kk + (l >> 4)];
+        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
+      }
+    }
+  }
+}
+
 // ---- N sums at once, bit for bit those of N wave_sum calls ----------------------------------------------------------
 // wave_sum adds the lanes as a balanced binary tree in lane order: level t adds the sums of lane blocks that differ in
 // lane bit t (f64 addition is commutative, so which of the two lanes holds which operand does not change a bit).  The
@@ -366,6 +414,10 @@ void launch_score_ks_only(hipStream_t st, const double* Xq, int q, const GpModel
 // launch_score's first kernel alone, for any q >= 1 (launch_posterior starts with it)
 void launch_score_ks(hipStream_t st, const double* Xq, int q, const GpModel& m, AcqParams p, double* KS, double* partial,
                      AcqBatch ab = AcqBatch(), int B = 1);
+// The scoring's second kernel alone: V = R KS^T on MFMA, its column norms into the partial records; grid (NP / 64, ceil(q / 64), B).
+// V (NP x q, runs vzs bytes apart) given: the instantiation that also stores it (launch_posterior with a covariance).
+void launch_score_gemm(hipStream_t st, const GpModel& m, int q, const double* KS, double* partial, size_t zs = 0, int B = 1,
+                       double* V = nullptr, size_t vzs = 0);
 // Posterior mean / variance / covariance at q >= 1 points (kernels_post.hip; KS and partial are the scoring's workspaces):
 // post[3 q] = mean | variance (floored) | variance before the floor; V (NP x q) and cov (q x q) both given or both null.
 // s2: the likelihood noise (a batch after its fit: read from ab.hyp); vzs: bytes between two runs' V / cov blocks.

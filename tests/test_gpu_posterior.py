@@ -1,4 +1,4 @@
-"""GP posterior queries on the MI355X (pcabo_gp_posterior / pcabo_batch_gp_posterior: k_score_ks, k_post_gemm, k_post_combine,
+"""GP posterior queries on the MI355X (pcabo_gp_posterior / pcabo_batch_gp_posterior: k_score_ks, k_score_gemm, k_post_combine,
 k_post_cov; Context.gp_posterior, Batch.gp_posterior, PCA_BO.posterior, Vanilla_BO.posterior) against tests/posterior_reference.py.
 
 Shapes (n, k, q) of CASES: n crosses one R block (9), an exact block (64), two blocks (65, 130), two 256-column blocks of k_score_ks
