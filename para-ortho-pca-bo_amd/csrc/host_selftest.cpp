@@ -4,7 +4,8 @@
 // mll_assemble) and csrc/lb_plan.h (the work plan of the device optimiser's passes).  The batch's round loop is the product's
 // run_rounds with a stub evaluator: where the product launches an acquisition kernel and polls its flags, the workers here evaluate
 // a bounded test objective on the CPU.  The GP fit is the product's FitRun / fit_rounds over a small dense GP in plain C++ that hands
-// back the six sums the likelihood kernels produce (test_fit_run: lock-step = alone, the NOT_PD / DOMAIN stops, resting runs).
+// back the sums the likelihood kernels produce, in both forms of the model (test_fit_run: lock-step = alone, the NOT_PD / DOMAIN
+// stops, resting runs, a shared-lengthscale run and an ARD run side by side).
 // Exit code 0 and "host selftest ok" = every check passed; a sanitizer report aborts the process (halt_on_error).
 #include "../../include/pcabo.h"
 #include "host_side.h"
@@ -325,21 +326,23 @@ void test_gang_pool(int workers, int runs) {
 }
 
 // ---- the GP hyperparameter fit (FitRun, fit_rounds, mll_assemble of host_side.h) over a stub evaluator --------------------------
-// A small dense GP on the CPU: Matern-5/2 with one lengthscale on the points as given, targets as given (the product's kernels
-// normalise and standardise first; the stepper does not care), Cholesky and inverse by textbook loops.  h = the six sums the
-// likelihood kernels hand to mll_assemble; false: K + s2 I is not positive definite.
+// A small dense GP on the CPU: Matern-5/2 on the points as given, targets as given (the product's kernels normalise and
+// standardise first; the stepper does not care), Cholesky and inverse by textbook loops.  th = {s2, c, rho} with one lengthscale,
+// ard: {s2, c, rho_1 .. rho_k} with one per input.  h = the 5 + m sums the likelihood kernels hand to mll_assemble (m = 1, ard:
+// m = k); false: K + s2 I is not positive definite.
 struct TinyGP { int n = 0, k = 0; std::vector<double> Z, y; };
-bool tiny_gp_sums(const TinyGP& gp, const double* th, double* h) {
-  const int n = gp.n;
-  const double s2 = th[0], c = th[1], ls = softplus_host(th[2]), s5 = std::sqrt(5.0);
-  std::vector<double> K((size_t)n * n), dK((size_t)n * n), L((size_t)n * n, 0.0), Li((size_t)n * n, 0.0), Kin((size_t)n * n), a(n, 0.0);
+bool tiny_gp_sums(const TinyGP& gp, const double* th, double* h, bool ard = false) {
+  const int n = gp.n, m = ard ? gp.k : 1;
+  const double s2 = th[0], c = th[1], s5 = std::sqrt(5.0);
+  const auto scaled = [&](int i, int j, int t) { return (gp.Z[i * gp.k + t] - gp.Z[j * gp.k + t]) / softplus_host(th[2 + (ard ? t : 0)]); };
+  std::vector<double> K((size_t)n * n), G((size_t)n * n), L((size_t)n * n, 0.0), Li((size_t)n * n, 0.0), Kin((size_t)n * n), a(n, 0.0);
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) {
       double r2 = 0.0;
-      for (int t = 0; t < gp.k; ++t) { const double d = (gp.Z[i * gp.k + t] - gp.Z[j * gp.k + t]) / ls; r2 += d * d; }
+      for (int t = 0; t < gp.k; ++t) { const double d = scaled(i, j, t); r2 += d * d; }
       const double r = std::sqrt(r2), e = std::exp(-s5 * r);
       K[i * n + j] = (1.0 + s5 * r + 5.0 / 3.0 * r2) * e + (i == j ? s2 : 0.0);
-      dK[i * n + j] = 5.0 / 3.0 * r2 * (1.0 + s5 * r) * e;                 // dK / dlog l
+      G[i * n + j] = 5.0 / 3.0 * (1.0 + s5 * r) * e;                       // dK / dlog l_t = G d_t^2, dK / dlog l = G r^2
     }
   for (int j = 0; j < n; ++j)
     for (int i = j; i < n; ++i) {
@@ -363,10 +366,14 @@ bool tiny_gp_sums(const TinyGP& gp, const double* th, double* h) {
       Kin[i * n + j] = v;
       a[i] += v * (gp.y[j] - c);
     }
-  for (int t = 0; t < 6; ++t) h[t] = 0.0;
+  for (int t = 0; t < 5 + m; ++t) h[t] = 0.0;
   for (int i = 0; i < n; ++i) {
     h[0] += std::log(L[i * n + i]); h[1] += (gp.y[i] - c) * a[i]; h[2] += a[i]; h[3] += a[i] * a[i]; h[4] += Kin[i * n + i];
-    for (int j = 0; j < n; ++j) h[5] += (a[i] * a[j] - Kin[i * n + j]) * dK[i * n + j];
+    for (int j = 0; j < n; ++j)
+      for (int t = 0; t < gp.k; ++t) {
+        const double d = scaled(i, j, t);
+        h[5 + (ard ? t : 0)] += (a[i] * a[j] - Kin[i * n + j]) * G[i * n + j] * (d * d);
+      }
   }
   return true;
 }
@@ -407,7 +414,7 @@ FitDrive drive_fits(const std::vector<TinyGP>& gps, const std::vector<const doub
       if (!th[b]) { CHECK(r.state == FitRun::OUT, "run %zu: no theta but not out", b); continue; }
       const bool resting = r.state == FitRun::RESTING;
       if (resting) {                                                         // rides along at its result
-        CHECK(std::memcmp(th[b], r.xr, sizeof(r.xr)) == 0, "run %zu rests away from its result", b);
+        CHECK(std::memcmp(th[b], r.xr, (size_t)r.nvar * sizeof(double)) == 0, "run %zu rests away from its result", b);
         ++d.rested[b];
       } else {
         d.evals[b].insert(d.evals[b].end(), th[b], th[b] + 3);
@@ -433,18 +440,39 @@ void test_fit_run() {
     const double th[3] = {0.02, 0.15, -0.4};
     double h[6], f = 0.0, g[3], worst = 0.0;
     CHECK(tiny_gp_sums(gp, th, h), "the dense GP could not be factored");
-    mll_assemble(h, gp.n, th, &f, g);
+    mll_assemble(h, gp.n, 1, false, th, &f, g);
     for (int i = 0; i < 3; ++i) {
       const double step = i == 0 ? 1e-6 * th[0] : 1e-6;
       double tp[3] = {th[0], th[1], th[2]}, tm[3] = {th[0], th[1], th[2]}, fp = 0.0, fm = 0.0;
       tp[i] += step; tm[i] -= step;
-      CHECK(tiny_gp_sums(gp, tp, h), "factor"); mll_assemble(h, gp.n, tp, &fp, nullptr);
-      CHECK(tiny_gp_sums(gp, tm, h), "factor"); mll_assemble(h, gp.n, tm, &fm, nullptr);
+      CHECK(tiny_gp_sums(gp, tp, h), "factor"); mll_assemble(h, gp.n, 1, false, tp, &fp, nullptr);
+      CHECK(tiny_gp_sums(gp, tm, h), "factor"); mll_assemble(h, gp.n, 1, false, tm, &fm, nullptr);
       const double fd = (fp - fm) / (tp[i] - tm[i]), err = std::fabs(fd - g[i]) / (1.0 + std::fabs(g[i]));
       if (err > worst) worst = err;
       CHECK(err < 1e-6, "gradient %d: %.12g against the difference quotient %.12g", i, g[i], fd);
     }
     std::printf("mll_assemble against central differences: worst %.2e (bound 1e-6)\n", worst);
+  }
+  // ... and in the ARD form, one rho per input (n = 8, k = 3; one rho above softplus's threshold, where the derivative is 1)
+  {
+    const TinyGP gp = tiny_gp(4, 8, 3);
+    const int nv = 5;
+    const double th[nv] = {0.03, -0.1, -0.4, 0.7, 20.5};
+    double h[8], f = 0.0, g[nv], worst = 0.0;
+    CHECK(mll_theta_ok(th, 3) && tiny_gp_sums(gp, th, h, true), "the dense ARD GP could not be factored");
+    mll_assemble(h, gp.n, 3, true, th, &f, g);
+    for (int i = 0; i < nv; ++i) {
+      const double step = i == 0 ? 1e-6 * th[0] : 1e-6;
+      double tp[nv], tm[nv], fp = 0.0, fm = 0.0;
+      std::memcpy(tp, th, sizeof(th)); std::memcpy(tm, th, sizeof(th));
+      tp[i] += step; tm[i] -= step;
+      CHECK(tiny_gp_sums(gp, tp, h, true), "factor"); mll_assemble(h, gp.n, 3, true, tp, &fp, nullptr);
+      CHECK(tiny_gp_sums(gp, tm, h, true), "factor"); mll_assemble(h, gp.n, 3, true, tm, &fm, nullptr);
+      const double fd = (fp - fm) / (tp[i] - tm[i]), err = std::fabs(fd - g[i]) / (1.0 + std::fabs(g[i]));
+      if (err > worst) worst = err;
+      CHECK(err < 1e-6, "ARD gradient %d: %.12g against the difference quotient %.12g", i, g[i], fd);
+    }
+    std::printf("mll_assemble (ARD) against central differences: worst %.2e (bound 1e-6)\n", worst);
   }
   // (a) B runs in lock-step = every run alone: theta, loss, info bit for bit; finished runs ride along at their result and are
   // not counted
@@ -488,7 +516,7 @@ void test_fit_run() {
     CHECK(evaluated, "failure %d: the result was never evaluated", e);
     if (std::memcmp(&ev[3 * (e - 2)], o.theta, sizeof(o.theta)) == 0) ++end_at_last_evaluated;
     double h[6], f = 0.0;
-    CHECK(tiny_gp_sums(gps[0], o.theta, h), "factor"); mll_assemble(h, gps[0].n, o.theta, &f, nullptr);
+    CHECK(tiny_gp_sums(gps[0], o.theta, h), "factor"); mll_assemble(h, gps[0].n, 1, false, o.theta, &f, nullptr);
     CHECK(f == o.loss, "failure %d: the loss is not the one at the result", e);
   }
   CHECK(end_at_last_evaluated > 0, "no failure met the first trial of a line search");
@@ -505,7 +533,7 @@ void test_fit_run() {
     const double G = 0.5;
     const auto linear = [&](const std::vector<const double*>& th, int* st) {
       const double s2 = th[0][0], rho = th[0][2], u = std::log(s2) + 4.0;
-      CHECK(mll_theta_ok(th[0]), "asked to evaluate a theta outside the domain");
+      CHECK(mll_theta_ok(th[0], 1), "asked to evaluate a theta outside the domain");
       h[1] = 2.0 * n * G * rho; h[5] = -2.0 * n * G * softplus_host(rho) * (1.0 + std::exp(-rho)); h[3] = 2.0 * (1.0 + u) / s2;
       ++evals; rhos.push_back(rho); st[0] = PCABO_OK;
       return (int)PCABO_OK;
@@ -522,6 +550,45 @@ void test_fit_run() {
     run[0].init(far);
     CHECK(fit_rounds(run, n, linear) == PCABO_OK, "fit_rounds");
     CHECK(run[0].status == PCABO_ERR_ARG && run[0].state == FitRun::OUT && evals == 0, "start outside the domain: status %d, %d evaluations", run[0].status, evals);
+  }
+  // (d) a shared-lengthscale run and an ARD run (k = 3, one start below the bound on rho_c: clipped to it) in one vector: each
+  // takes the fit it takes alone, bit for bit, and the ARD run keeps every rho_c at or above its bound
+  {
+    const TinyGP gp2[2] = {tiny_gp(10), tiny_gp(5, 12, 3)};
+    const double start_ard[5] = {FIT_START[0], 0.0, 0.0, -100.0, 0.0};
+    struct Out { int status, nvar, info[4]; double theta[5], loss; };
+    const auto drive = [&](const std::vector<int>& which) {
+      std::vector<FitRun> runs(which.size());
+      std::vector<double> hs(8 * which.size(), 0.0);
+      for (size_t b = 0; b < which.size(); ++b) {
+        runs[b].bind(&hs[8 * b]);
+        if (which[b]) runs[b].init(start_ard, 3, true); else runs[b].init(FIT_START);
+      }
+      CHECK(fit_rounds(runs, 12, [&](const std::vector<const double*>& th, int* st) {
+        for (size_t b = 0; b < which.size(); ++b)
+          if (th[b]) st[b] = tiny_gp_sums(gp2[which[b]], th[b], &hs[8 * b], which[b] != 0) ? PCABO_OK : PCABO_ERR_NOT_PD;
+        return (int)PCABO_OK;
+      }) == PCABO_OK, "fit_rounds");
+      std::vector<Out> out(which.size());
+      for (size_t b = 0; b < which.size(); ++b) {
+        Out& o = out[b];
+        std::memset(&o, 0, sizeof(o));
+        o.status = runs[b].status; o.nvar = runs[b].nvar;
+        CHECK(o.status == PCABO_OK && o.nvar == (which[b] ? 5 : 3), "run %zu: status %d, %d variables", b, o.status, o.nvar);
+        if (o.status != PCABO_OK) continue;
+        std::memcpy(o.theta, runs[b].xr, (size_t)o.nvar * sizeof(double)); o.loss = runs[b].fr; runs[b].report(o.info);
+      }
+      return out;
+    };
+    const std::vector<Out> both = drive({0, 1}), swapped = drive({1, 0});
+    for (int f = 0; f < 2; ++f) {
+      const std::vector<Out> one = drive({f});
+      CHECK(std::memcmp(&both[f], &one[0], sizeof(Out)) == 0 && std::memcmp(&swapped[1 - f], &one[0], sizeof(Out)) == 0,
+            "the %s run beside the other form differs from the run alone", f ? "ARD" : "shared-lengthscale");
+      CHECK(one[0].info[0] > 2 && one[0].info[1] > one[0].info[0], "form %d: %d iterations, %d evaluations", f, one[0].info[0], one[0].info[1]);
+    }
+    for (int j = 2; j < 5; ++j) CHECK(both[1].theta[j] >= FIT_ARD_RHO_MIN, "rho_%d = %g below its bound", j - 2, both[1].theta[j]);
+    CHECK(both[0].info[1] != both[1].info[1], "the two runs finished in the same round: neither rode along");
   }
 }
 

@@ -126,49 +126,38 @@ int run_rounds(RunRestarts* runs, const std::vector<int>& order, Stage&& stage, 
 }
 
 // ---- GP hyperparameter fit (DESIGN.md "GP hyperparameter fit") ---------------------------------------------------------------
-// theta = {noise s2, mean constant c, raw lengthscale rho}; lengthscale = softplus(rho) as torch computes it (threshold 20).
-inline double softplus_host(double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); }
-inline bool mll_theta_ok(const double* theta) {
-  const double s2 = theta[0], c = theta[1], ls = softplus_host(theta[2]);
-  return s2 > 0.0 && std::isfinite(s2) && std::isfinite(c) && ls > 0.0 && std::isfinite(ls);
-}
-// Loss and gradient of one evaluation, assembled on the host (the prior on s2 and the chain rule through softplus are host
-// arithmetic): h = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, sum W dK/dlog l} of a state conditioned at theta
-inline void mll_assemble(const double* h, int n, const double* theta, double* loss, double* grad) {
-  const double s2 = theta[0], rho = theta[2];
-  const double ls = softplus_host(rho);
-  const double LOG2PI = 1.8378770664093453;
-  const double lnz = std::log(s2), u = lnz + 4.0;
-  const double log_n = -0.5 * h[1] - h[0] - 0.5 * n * LOG2PI;
-  const double log_prior = -lnz - 0.5 * LOG2PI - 0.5 * u * u;              // LogNormal(-4, 1) at s2
-  *loss = -(log_n + log_prior) / n;
-  if (grad) {
-    const double sig = 1.0 / (1.0 + std::exp(-rho));                       // d softplus / d rho
-    grad[0] = -((0.5 * (h[3] - h[4])) + (-1.0 - u) / s2) / n;
-    grad[1] = -h[2] / n;
-    grad[2] = -(0.5 * h[5] * sig / ls) / n;
-  }
-}
-
-// ARD (pcabo_gp_mll_ard / pcabo_gp_fit_ard): theta = {s2, c, rho_1 .. rho_k}, one lengthscale softplus(rho_c) per input; the sums are
-// h = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, S_1 .. S_k}, S_c = sum_ij W_ij dK_ij/dlog l_c (their sum is the
-// scalar fit's S, and equal rho is the scalar model).  Loss, prior and the s2 / c gradients are mll_assemble's expressions.
+// theta = {noise s2, mean constant c, rho_1 .. rho_m}: m raw lengthscales, lengthscale = softplus(rho) as torch computes it
+// (threshold 20).  Two forms of the model: the shared lengthscale (m = 1, pcabo_gp_mll / pcabo_gp_fit and the batch) and ARD, one
+// lengthscale per input (m = k, pcabo_gp_mll_ard / pcabo_gp_fit_ard).  The scalar model is the ARD layout with one rho; the forms
+// differ in two rules, fit_rho_lower and softplus_slope, and in nothing else on the host.
 constexpr int FIT_ARD_MAXVAR = 2 + 128;  // 2 + the largest reduced dimension (PCABO_MAXD)
-// The fit's lower bound on every rho_c: ln 2^-40, a lengthscale of 2^-40 of the Normalize range, which is where k_zstats holds a
-// folded range (below it the device no longer evaluates the model at rho_c, and K = I to rounding anyway).  The flat directions of
-// the irrelevant inputs give L-BFGS-B trial steps of thousands in rho_c; as a bound, the line search's longest step ends there
-// and backtracks, where softplus(rho_c) = 0 would end the fit by the domain stop.  No fitted model is near it.
-constexpr double FIT_ARD_RHO_MIN = -27.725887222397812;
-inline bool mll_theta_ok_ard(const double* theta, int k) {
+inline double softplus_host(double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); }
+inline bool lengthscale_ok(double rho) {
+  const double ls = softplus_host(rho);
+  return ls > 0.0 && std::isfinite(ls);
+}
+inline bool mll_theta_ok(const double* theta, int m) {
   const double s2 = theta[0], c = theta[1];
   if (!(s2 > 0.0 && std::isfinite(s2) && std::isfinite(c))) return false;
-  for (int j = 0; j < k; ++j) {
-    const double ls = softplus_host(theta[2 + j]);
-    if (!(ls > 0.0 && std::isfinite(ls))) return false;
-  }
+  for (int j = 0; j < m; ++j)
+    if (!lengthscale_ok(theta[2 + j])) return false;
   return true;
 }
-inline void mll_assemble_ard(const double* h, int n, int k, const double* theta, double* loss, double* grad) {
+// Rule 1, the fit's lower bound on rho.  ARD bounds every rho_c by ln 2^-40, a lengthscale of 2^-40 of the Normalize range, which
+// is where k_zstats holds a folded range (below it the device no longer evaluates the model at rho_c, and K = I to rounding
+// anyway).  The flat directions of the irrelevant inputs give L-BFGS-B trial steps of thousands in rho_c; as a bound, the line
+// search's longest step ends there and backtracks, where softplus(rho_c) = 0 would end the fit by the domain stop.  No fitted model
+// is near it.  The shared lengthscale is not bounded.
+constexpr double FIT_ARD_RHO_MIN = -27.725887222397812;
+inline double fit_rho_lower(bool ard) { return ard ? FIT_ARD_RHO_MIN : -INFINITY; }
+// Rule 2, d softplus / d rho above the threshold.  ARD takes softplus's linear branch as derivative 1, which is torch's rule; the
+// shared lengthscale computes the sigmoid throughout, about 2e-9 below 1 there.  Both are kept as they were (one of them is
+// arguably a defect): dropping `ard &&` settles it.
+inline double softplus_slope(double rho, bool ard) { return ard && rho > 20.0 ? 1.0 : 1.0 / (1.0 + std::exp(-rho)); }
+// Loss and gradient of one evaluation, assembled on the host (the prior on s2 and the chain rule through softplus are host
+// arithmetic): h = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, S_1 .. S_m} of a state conditioned at theta,
+// S_c = sum_ij W_ij dK_ij/dlog l_c (m = 1: S = sum W dK/dlog l; the S_c of equal rho add up to it)
+inline void mll_assemble(const double* h, int n, int m, bool ard, const double* theta, double* loss, double* grad) {
   const double s2 = theta[0];
   const double LOG2PI = 1.8378770664093453;
   const double lnz = std::log(s2), u = lnz + 4.0;
@@ -178,9 +167,9 @@ inline void mll_assemble_ard(const double* h, int n, int k, const double* theta,
   if (grad) {
     grad[0] = -((0.5 * (h[3] - h[4])) + (-1.0 - u) / s2) / n;
     grad[1] = -h[2] / n;
-    for (int j = 0; j < k; ++j) {
+    for (int j = 0; j < m; ++j) {
       const double rho = theta[2 + j], ls = softplus_host(rho);
-      const double sig = rho > 20.0 ? 1.0 : 1.0 / (1.0 + std::exp(-rho));  // d softplus / d rho (its linear branch: 1)
+      const double sig = softplus_slope(rho, ard);
       grad[2 + j] = -(0.5 * h[5 + j] * sig / ls) / n;
     }
   }
@@ -192,44 +181,33 @@ inline void mll_assemble_ard(const double* h, int n, int k, const double* theta,
 // started, or failed: status says why).  A trial theta outside the model's domain (a line-search step so long that softplus(rho)
 // underflows to 0, a non-finite value) and one the factorisation cannot take end the fit abnormally at the last accepted iterate
 // (warnflag 2, task PCABO_FIT_TASK_*); when that theta is the start itself the run fails (PCABO_ERR_ARG / PCABO_ERR_NOT_PD).
-// CAP: the most variables a run can hold.  FitRun (CAP = 3) is the scalar fit of nvar = 3 variables; the ARD fit (FitRunArd) has
-// nvar = 2 + k of its FIT_ARD_MAXVAR, picked by init_ard.  The rules are the same; the domain test and the assembly differ, and
-// every rho_c has the lower bound FIT_ARD_RHO_MIN, which keeps the line search's trial steps inside the domain.
-template <int CAP>
-struct FitRunT {
+// A run holds nvar = 2 + m variables of FIT_ARD_MAXVAR; runs of both forms and of different m step side by side in fit_rounds.
+struct FitRun {
   enum { STEPPING, END, RESTING, OUT };
   LbfgsbDriver fit;
   int state = OUT, status = PCABO_ERR_ARG, stop_task = 0;
-  int nvar = 3, ard_k = 0;             // ard_k > 0: the ARD model of ard_k lengthscales
-  double xr[CAP] = {}, fr = 0.0;       // the result (nvar doubles) and the loss there
+  int nvar = 3;
+  bool ard = false;
+  double xr[FIT_ARD_MAXVAR] = {}, fr = 0.0;   // the result (nvar doubles) and the loss there
   const double* h = nullptr;           // where the evaluator leaves the sums of this run (bind)
   void bind(const double* h_) { h = h_; }
-  void init(const double* theta0) {
-    const double lower[3] = {1e-4, -INFINITY, -INFINITY}, upper[3] = {INFINITY, INFINITY, INFINITY};
-    nvar = 3; ard_k = 0;
-    fit.keep_accepted = true;                            // scipy's defaults and limits, the published order
-    fit.init(3, theta0, lower, upper);
-    state = STEPPING; status = PCABO_OK; stop_task = 0;
-  }
-  void init_ard(const double* theta0, int k) {
-    static_assert(CAP == FIT_ARD_MAXVAR, "only FitRunArd holds 2 + k variables");
-    assert(k >= 1 && 2 + k <= CAP);
-    std::vector<double> lower((size_t)2 + k, -INFINITY), upper((size_t)2 + k, INFINITY);
+  void init(const double* theta0, int m = 1, bool ard_ = false) {
+    assert(m >= 1 && 2 + m <= FIT_ARD_MAXVAR && (ard_ || m == 1));
+    nvar = 2 + m; ard = ard_;
+    state = OUT; status = PCABO_ERR_ARG; stop_task = 0;
+    for (int j = 0; j < m; ++j)                          // a start with a lengthscale outside the domain fails; it is not clipped
+      if (!lengthscale_ok(theta0[2 + j])) return;
+    double lower[FIT_ARD_MAXVAR], upper[FIT_ARD_MAXVAR];
+    std::fill(lower, lower + nvar, -INFINITY);
+    std::fill(upper, upper + nvar, INFINITY);
     lower[0] = 1e-4;
-    for (int j = 0; j < k; ++j) lower[(size_t)2 + j] = FIT_ARD_RHO_MIN;
-    nvar = 2 + k; ard_k = k;
-    for (int j = 0; j < k; ++j) {                        // a start with a lengthscale outside the domain fails; it is not clipped
-      const double ls = softplus_host(theta0[2 + j]);
-      if (!(ls > 0.0 && std::isfinite(ls))) { state = OUT; status = PCABO_ERR_ARG; stop_task = 0; return; }
-    }
-    fit.keep_accepted = true;
-    fit.init(nvar, theta0, lower.data(), upper.data());
-    state = STEPPING; status = PCABO_OK; stop_task = 0;
+    std::fill(lower + 2, lower + nvar, fit_rho_lower(ard));
+    fit.keep_accepted = true;                            // scipy's defaults and limits, the published order
+    fit.init(nvar, theta0, lower, upper);
+    state = STEPPING; status = PCABO_OK;
   }
-  bool theta_ok(const double* th) const { return ard_k ? mll_theta_ok_ard(th, ard_k) : mll_theta_ok(th); }
-  void assemble(int n, const double* th, double* f, double* g) const {
-    if (ard_k) mll_assemble_ard(h, n, ard_k, th, f, g); else mll_assemble(h, n, th, f, g);
-  }
+  bool theta_ok(const double* th) const { return mll_theta_ok(th, nvar - 2); }
+  void assemble(int n, const double* th, double* f, double* g) const { mll_assemble(h, n, nvar - 2, ard, th, f, g); }
   // The theta to evaluate next, or null: the run has its result, or is out.
   const double* next() {
     if (state == STEPPING && !fit.advance()) finish();
@@ -277,14 +255,12 @@ struct FitRunT {
     state = (stop_task == PCABO_FIT_TASK_NOT_PD || !fit.have_cache || std::memcmp(xr, fit.xc.data(), bytes) != 0) ? END : RESTING;
   }
 };
-typedef FitRunT<3> FitRun;
-typedef FitRunT<FIT_ARD_MAXVAR> FitRunArd;
 
 // The rounds of the runs' fits in lock-step until no run wants an evaluation: eval(th, st) evaluates run b at th[b] (null: a run
 // that is out), leaves its sums where the run was bound and its outcome in st[b], and returns PCABO_OK or an error, which
 // ends the rounds and is returned.  n: the number of training points of every run.
-template <class Run, class Eval>
-int fit_rounds(std::vector<Run>& runs, int n, Eval&& eval) {
+template <class Eval>
+int fit_rounds(std::vector<FitRun>& runs, int n, Eval&& eval) {
   std::vector<const double*> th(runs.size(), nullptr);
   std::vector<int> st(runs.size(), PCABO_OK);
   for (;;) {

@@ -115,8 +115,8 @@ struct pcabo_ctx {
   int cnt_S = 0; bool cnt_dirty = true;  // slab-group count the tickets are consistent with / a launch may have died
   double* dKS = nullptr;                 // q x ld kernel vectors of the GEMM scoring path
   double* dBestF = nullptr;              // best_f of this run for the batched acquisition launches (set by the batch)
-  double* dMll = nullptr;                // GP fit: 2 partial sums per lower 64 x 64 tile of K^-1, then the 6 results (k_mll_finish);
-                                         // ARD: 1 + KP sums per tile, then the 5 + KP results (k_mll_finish_ard)
+  double* dMll = nullptr;                // GP fit: 1 + M partial sums per lower 64 x 64 tile of K^-1, then the 5 + M results
+                                         // (k_mll_finish); M = 1, ARD: M = KP
   double* dArdLs = nullptr;              // ARD fit: the k lengthscales k_zstats folds into the Normalize ranges
   double* dHyp = nullptr;                // lock-step fit of a batch: this run's {1 / lengthscale, noise, mean constant} (PCABO_HYP_*)
   char* dPostV = nullptr;                // pcabo_gp_posterior with a covariance: V (NPcap x max_q), then cov (max_q^2); allocated
@@ -896,12 +896,15 @@ int pcabo_gp_condition(pcabo_ctx* ctx, const double* Z, const double* y, int n, 
 }
 
 // ---- opt-in GP hyperparameter fit (DESIGN.md "GP hyperparameter fit") -------------------------------------------
-// theta = {noise s2, mean constant c, raw lengthscale rho}.  The host arithmetic of an evaluation (softplus_host, mll_theta_ok,
-// mll_assemble) and the rules of a fit (FitRun, fit_rounds) are in host_side.h, shared by the single context and the batch.
+// theta = {noise s2, mean constant c, rho_1 .. rho_m}: the shared lengthscale (m = 1) or, ard, one per input (m = k).  The host
+// arithmetic of an evaluation (softplus_host, mll_theta_ok, mll_assemble) and the rules of a fit (FitRun, fit_rounds) are in
+// host_side.h, shared by the single context and the batch.
+static_assert(FIT_ARD_MAXVAR == 2 + PCABO_MAXD, "host_side.h sizes a run for PCABO_MAXD lengthscales");
 
 // Inputs of a fit staged like pcabo_gp_condition_begin's; *unb = the device copy of the user's Normalize bounds or NULL.
-static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, const double* Z, const double* y, int n, int k,
+static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, bool ard, const double* Z, const double* y, int n, int k,
                             const double* norm_bounds, int kernel, const double** unb) {
+  if (ard && ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch; the ARD fit is for single contexts", who);
   if (!y || k < 1 || k > ctx->max_d || n < 2 || n > ctx->max_n)
     return set_err(ctx, PCABO_ERR_ARG, "%s: bad argument or size beyond context capacity", who);
   if (kernel != PCABO_KERNEL_MATERN52)
@@ -914,20 +917,14 @@ static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, const double* Z, co
 }
 
 // The attempts of one evaluation from `attempt` on (factor_attempts): each one runs the likelihood kernels behind its
-// factorisation and copies their 6 results (48 bytes) in front of its wait.  A run of a batch whose lock-step round failed enters
-// at attempt 1.
-static int mll_attempts(pcabo_ctx* ctx, int attempt, bool ard = false) {
+// factorisation and copies their 5 + M results (M = 1, ard: M = KP) in front of its wait.  A run of a batch whose lock-step round
+// failed enters at attempt 1.
+static int mll_attempts(pcabo_ctx* ctx, int attempt, bool ard) {
   const int rc = factor_attempts(ctx, attempt, [ctx, ard]() -> int {
-    const int nb = ctx->NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
-    if (ard) {                           // 1 + KP sums per tile, 5 + KP results
-      double* out = ctx->dMll + (size_t)(1 + ctx->KP) * tiles;
-      launch_mll_grad_ard(ctx->stream, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
-      HOST_OUT(ctx->hMll, out, 5 + ctx->KP, double);
-      return PCABO_OK;
-    }
-    double* out = ctx->dMll + 2 * (size_t)tiles;
-    launch_mll_grad(ctx->stream, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
-    HOST_OUT(ctx->hMll, out, 6, double);
+    const int nb = ctx->NP / PCABO_BS, tiles = nb * (nb + 1) / 2, M = ard ? ctx->KP : 1;
+    double* out = ctx->dMll + (size_t)(1 + M) * tiles;
+    launch_mll_grad(ctx->stream, ard, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
+    HOST_OUT(ctx->hMll, out, 5 + M, double);
     return PCABO_OK;
   });
   if (rc == PCABO_OK) ctx->have_gp = true;
@@ -935,112 +932,81 @@ static int mll_attempts(pcabo_ctx* ctx, int attempt, bool ard = false) {
 }
 
 // One evaluation at a theta inside the model's domain: the conditioning there (k_zstats with the mean constant -> k_znorm -> k_gram
-// -> Cholesky -> root inverse -> alpha), then mll_attempts; the 6 sums are left in ctx->hMll.
-static int mll_launch(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta) {
-  const int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, softplus_host(theta[2]), theta[0], PCABO_KERNEL_MATERN52, theta[1]);
+// -> Cholesky -> root inverse -> alpha), then mll_attempts; the sums are left in ctx->hMll.
+// ard (DESIGN.md "ARD lengthscales"): the lengthscales softplus(rho_c) go to the device and k_zstats folds them into the Normalize
+// ranges, so the evaluation is the scalar one at lengthscale 1 on the folded ranges (ctx->lengthscale = 1: the acquisition kernels
+// read the folded bounds4 and need no change); k_mll_grad<true> adds the per-input sums.  The next conditioning call passes no
+// lengthscales and returns to the unfolded model.
+static int mll_launch(pcabo_ctx* ctx, bool ard, int n, int k, const double* unb, const double* theta) {
+  if (ard) {
+    for (int c = 0; c < k; ++c) ctx->hArdLs[c] = softplus_host(theta[2 + c]);    // (the last evaluation's copy has been waited for)
+    HIPCHK(hipMemcpyAsync(ctx->dArdLs, ctx->hArdLs, (size_t)k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  const int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, ard ? 1.0 : softplus_host(theta[2]), theta[0], PCABO_KERNEL_MATERN52,
+                                   theta[1], ard ? ctx->dArdLs : nullptr);
   if (rc != PCABO_OK) return rc;
   ctx->gp_pending = false;
-  return mll_attempts(ctx, 0);
+  return mll_attempts(ctx, 0, ard);
 }
-static int theta_domain_err(pcabo_ctx* ctx) {
-  return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
-}
-static int theta_domain_err_ard(pcabo_ctx* ctx, const char* who) {
+// (the shared-lengthscale form names pcabo_gp_mll whichever entry point met the theta: its text since the first fit)
+static int theta_domain_err(pcabo_ctx* ctx, const char* who, bool ard) {
+  if (!ard) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta outside the model's domain (noise > 0, finite values)%s", "");
   return set_err(ctx, PCABO_ERR_ARG, "%s: theta outside the model's domain (noise > 0, lengthscales > 0, finite values)", who);
 }
 
-static int mll_eval(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta, double* loss, double* grad) {
-  if (!mll_theta_ok(theta)) return theta_domain_err(ctx);
-  const int rc = mll_launch(ctx, n, k, unb, theta);
+// pcabo_gp_mll / pcabo_gp_mll_ard
+static int gp_mll_call(pcabo_ctx* ctx, const char* who, bool ard, const double* Z, const double* y, int n, int k,
+                       const double* norm_bounds, int kernel, const double* theta, double* loss, double* grad) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (!theta || !loss) return set_err(ctx, PCABO_ERR_ARG, "%s: theta and loss are required", who);
+  const double* unb = nullptr;
+  int rc = stage_fit_inputs(ctx, who, ard, Z, y, n, k, norm_bounds, kernel, &unb);
   if (rc != PCABO_OK) return rc;
-  mll_assemble(ctx->hMll, n, theta, loss, grad);
+  const int m = ard ? k : 1;
+  if (!mll_theta_ok(theta, m)) return theta_domain_err(ctx, who, ard);
+  rc = mll_launch(ctx, ard, n, k, unb, theta);
+  if (rc != PCABO_OK) return rc;
+  mll_assemble(ctx->hMll, n, m, ard, theta, loss, grad);
+  return PCABO_OK;
+}
+
+// pcabo_gp_fit / pcabo_gp_fit_ard: scipy.optimize.minimize(method="L-BFGS-B") with its defaults around mll_launch: one FitRun,
+// every round one evaluation.  The context is left conditioned at the result.
+static int gp_fit_call(pcabo_ctx* ctx, const char* who, bool ard, const double* Z, const double* y, int n, int k,
+                       const double* norm_bounds, int kernel, double* theta_inout, double* loss, int* info) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (!theta_inout) return set_err(ctx, PCABO_ERR_ARG, "%s: theta_inout is required", who);
+  const double* unb = nullptr;
+  int rc = stage_fit_inputs(ctx, who, ard, Z, y, n, k, norm_bounds, kernel, &unb);
+  if (rc != PCABO_OK) return rc;
+  std::vector<FitRun> run(1);
+  run[0].init(theta_inout, ard ? k : 1, ard);
+  run[0].bind(ctx->hMll);
+  fit_rounds(run, n, [&](const std::vector<const double*>& th, int* st) { st[0] = mll_launch(ctx, ard, n, k, unb, th[0]); return (int)PCABO_OK; });
+  const FitRun& r = run[0];
+  if (r.status == PCABO_ERR_ARG) return theta_domain_err(ctx, who, ard);
+  if (r.status != PCABO_OK) return r.status;
+  memcpy(theta_inout, r.xr, (size_t)r.nvar * sizeof(double));
+  if (loss) *loss = r.fr;
+  if (info) r.report(info);
   return PCABO_OK;
 }
 
 int pcabo_gp_mll(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
                  const double* theta, double* loss, double* grad) {
-  if (!ctx) return PCABO_ERR_ARG;
-  if (!theta || !loss) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll: theta and loss are required%s", "");
-  const double* unb = nullptr;
-  int rc = stage_fit_inputs(ctx, "pcabo_gp_mll", Z, y, n, k, norm_bounds, kernel, &unb);
-  if (rc != PCABO_OK) return rc;
-  return mll_eval(ctx, n, k, unb, theta, loss, grad);
+  return gp_mll_call(ctx, "pcabo_gp_mll", false, Z, y, n, k, norm_bounds, kernel, theta, loss, grad);
 }
-
-// scipy.optimize.minimize(method="L-BFGS-B") with its defaults around mll_launch: one FitRun, every round one evaluation.  The
-// context is left conditioned at the result.
 int pcabo_gp_fit(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
                  double* theta_inout, double* loss, int* info) {
-  if (!ctx) return PCABO_ERR_ARG;
-  if (!theta_inout) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_fit: theta_inout is required%s", "");
-  const double* unb = nullptr;
-  int rc = stage_fit_inputs(ctx, "pcabo_gp_fit", Z, y, n, k, norm_bounds, kernel, &unb);
-  if (rc != PCABO_OK) return rc;
-  std::vector<FitRun> run(1);
-  run[0].init(theta_inout);
-  run[0].bind(ctx->hMll);
-  fit_rounds(run, n, [&](const std::vector<const double*>& th, int* st) { st[0] = mll_launch(ctx, n, k, unb, th[0]); return (int)PCABO_OK; });
-  const FitRun& r = run[0];
-  if (r.status == PCABO_ERR_ARG) return theta_domain_err(ctx);
-  if (r.status != PCABO_OK) return r.status;
-  memcpy(theta_inout, r.xr, sizeof(r.xr));
-  if (loss) *loss = r.fr;
-  if (info) r.report(info);
-  return PCABO_OK;
+  return gp_fit_call(ctx, "pcabo_gp_fit", false, Z, y, n, k, norm_bounds, kernel, theta_inout, loss, info);
 }
-
-// ---- ARD: one lengthscale per input (DESIGN.md "ARD lengthscales") ----------------------------------------------------------
-// theta = {s2, c, rho_1 .. rho_k}.  The lengthscales softplus(rho_c) go to the device and k_zstats folds them into the Normalize
-// ranges, so the evaluation is the scalar one at lengthscale 1 on the folded ranges (ctx->lengthscale = 1: the acquisition kernels
-// read the folded bounds4 and need no change); k_mll_grad_ard adds the per-input sums.  The next conditioning call passes no
-// lengthscales and returns to the unfolded model.
-static_assert(FIT_ARD_MAXVAR == 2 + PCABO_MAXD, "host_side.h sizes an ARD run for PCABO_MAXD lengthscales");
-static int mll_launch_ard(pcabo_ctx* ctx, int n, int k, const double* unb, const double* theta) {
-  for (int c = 0; c < k; ++c) ctx->hArdLs[c] = softplus_host(theta[2 + c]);    // (the last evaluation's copy has been waited for)
-  HIPCHK(hipMemcpyAsync(ctx->dArdLs, ctx->hArdLs, (size_t)k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, 1.0, theta[0], PCABO_KERNEL_MATERN52, theta[1], ctx->dArdLs);
-  if (rc != PCABO_OK) return rc;
-  ctx->gp_pending = false;
-  return mll_attempts(ctx, 0, true);
-}
-static int ard_entry(pcabo_ctx* ctx, const char* who, const double* Z, const double* y, int n, int k, const double* norm_bounds,
-                     int kernel, const double** unb) {
-  if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch; the ARD fit is for single contexts", who);
-  return stage_fit_inputs(ctx, who, Z, y, n, k, norm_bounds, kernel, unb);
-}
-
 int pcabo_gp_mll_ard(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
                      const double* theta, double* loss, double* grad) {
-  if (!ctx) return PCABO_ERR_ARG;
-  if (!theta || !loss) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_mll_ard: theta and loss are required%s", "");
-  const double* unb = nullptr;
-  int rc = ard_entry(ctx, "pcabo_gp_mll_ard", Z, y, n, k, norm_bounds, kernel, &unb);
-  if (rc != PCABO_OK) return rc;
-  if (!mll_theta_ok_ard(theta, k)) return theta_domain_err_ard(ctx, "pcabo_gp_mll_ard");
-  rc = mll_launch_ard(ctx, n, k, unb, theta);
-  if (rc != PCABO_OK) return rc;
-  mll_assemble_ard(ctx->hMll, n, k, theta, loss, grad);
-  return PCABO_OK;
+  return gp_mll_call(ctx, "pcabo_gp_mll_ard", true, Z, y, n, k, norm_bounds, kernel, theta, loss, grad);
 }
-
 int pcabo_gp_fit_ard(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds, int kernel,
                      double* theta_inout, double* loss, int* info) {
-  if (!ctx) return PCABO_ERR_ARG;
-  if (!theta_inout) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_fit_ard: theta_inout is required%s", "");
-  const double* unb = nullptr;
-  int rc = ard_entry(ctx, "pcabo_gp_fit_ard", Z, y, n, k, norm_bounds, kernel, &unb);
-  if (rc != PCABO_OK) return rc;
-  std::vector<FitRunArd> run(1);
-  run[0].init_ard(theta_inout, k);
-  run[0].bind(ctx->hMll);
-  fit_rounds(run, n, [&](const std::vector<const double*>& th, int* st) { st[0] = mll_launch_ard(ctx, n, k, unb, th[0]); return (int)PCABO_OK; });
-  const FitRunArd& r = run[0];
-  if (r.status == PCABO_ERR_ARG) return theta_domain_err_ard(ctx, "pcabo_gp_fit_ard");
-  if (r.status != PCABO_OK) return r.status;
-  memcpy(theta_inout, r.xr, (size_t)(2 + k) * sizeof(double));
-  if (loss) *loss = r.fr;
-  if (info) r.report(info);
-  return PCABO_OK;
+  return gp_fit_call(ctx, "pcabo_gp_fit_ard", true, Z, y, n, k, norm_bounds, kernel, theta_inout, loss, info);
 }
 
 int pcabo_acq_bounds(pcabo_ctx* ctx, double* bounds) {
@@ -2030,9 +1996,11 @@ static int batch_put_best_f(pcabo_batch* batch, const double* best_f) {
 // ---- lock-step GP hyperparameter fit of a batch (DESIGN.md "GP hyperparameter fit", the batched form) -------------------
 // One round = ONE launch sequence for all B runs (blockIdx.z = run): every run is conditioned at its own theta, read by k_zstats,
 // k_znorm and k_gram from the runs' dHyp blocks, then k_mll_grad + k_mll_finish, one strided copy of B x 6 doubles and one wait.
+// The runs of a batch have the shared lengthscale (BATCH_FIT_M = 1 rho, 3 variables each); ARD is for single contexts.
 // hyp_theta[b]: the theta run b is conditioned at, or NULL for a run that rests at the batch's shared model (parked runs).
 // A run whose Cholesky failed in the round is redone alone on its own context (mll_attempts from the first jitter on), as
 // batch_score_collect does; st[b] is PCABO_OK, PCABO_ERR_NOT_PD or a HIP error for every run with a theta, untouched otherwise.
+constexpr int BATCH_FIT_M = 1, BATCH_FIT_NVAR = 2 + BATCH_FIT_M;
 static int batch_mll_round(pcabo_batch* batch, const std::vector<const double*>& hyp_theta, int* st) {
   const int B = batch->B, n = batch->n, NP = batch->NP;
   pcabo_ctx* c0 = batch->ctx[0];
@@ -2057,9 +2025,9 @@ static int batch_mll_round(pcabo_batch* batch, const std::vector<const double*>&
     if (phase != 4) return PCABO_OK;     // behind alpha: the likelihood kernels and the strided copy of the runs' 6 results
     pcabo_ctx* ctx = c0;
     const int nb = NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
-    double* out = c0->dMll + 2 * (size_t)tiles;
-    launch_mll_grad(s, c0->dR, c0->dAT, c0->dNrm, c0->dAlpha, c0->dL, c0->dYs, n, NP, 0, c0->ld, c0->dMll, out, c0->dK, zb);
-    HIPCHK(hipMemcpy2DAsync(c0->hMll, batch->hzs, out, batch->zs, 6 * sizeof(double), B, hipMemcpyDeviceToHost, s));
+    double* out = c0->dMll + (size_t)(1 + BATCH_FIT_M) * tiles;
+    launch_mll_grad(s, false, c0->dR, c0->dAT, c0->dNrm, c0->dAlpha, c0->dL, c0->dYs, n, NP, 0, c0->ld, c0->dMll, out, c0->dK, zb);
+    HIPCHK(hipMemcpy2DAsync(c0->hMll, batch->hzs, out, batch->zs, (5 + BATCH_FIT_M) * sizeof(double), B, hipMemcpyDeviceToHost, s));
     return PCABO_OK;
   });
   if (rc != PCABO_OK) return bset_err(batch, rc, "%s", c0->err);
@@ -2070,7 +2038,7 @@ static int batch_mll_round(pcabo_batch* batch, const std::vector<const double*>&
     pcabo_ctx* c = batch->ctx[b];
     if (c->hm->chol_info == 0) { c->have_gp = true; if (hyp_theta[b]) st[b] = PCABO_OK; continue; }
     if (!hyp_theta[b]) continue;
-    st[b] = mll_attempts(c, 1);          // rare: jitter 1e-8, 1e-7, 1e-6 for this run alone (sets have_gp)
+    st[b] = mll_attempts(c, 1, false);   // rare: jitter 1e-8, 1e-7, 1e-6 for this run alone (sets have_gp)
   }
   return PCABO_OK;
 }
@@ -2117,8 +2085,9 @@ int pcabo_batch_gp_mll(pcabo_batch* batch, const double* theta, double* loss, do
   std::vector<int> st((size_t)B, PCABO_ERR_ARG);
   for (int b = 0; b < B; ++b) {
     if (!act[b]) continue;
-    if (mll_theta_ok(theta + 3 * b)) th[b] = theta + 3 * b;
-    else theta_domain_err(batch->ctx[b]);
+    const double* t = theta + (size_t)BATCH_FIT_NVAR * b;
+    if (mll_theta_ok(t, BATCH_FIT_M)) th[b] = t;
+    else theta_domain_err(batch->ctx[b], "pcabo_batch_gp_mll", false);
   }
   batch->fit_rounds = 0;
   rc = batch_mll_round(batch, th, st.data());
@@ -2126,7 +2095,9 @@ int pcabo_batch_gp_mll(pcabo_batch* batch, const double* theta, double* loss, do
   batch_fit_done(batch);
   int worst = PCABO_OK;
   for (int b = 0; b < B; ++b) {
-    if (st[b] == PCABO_OK) mll_assemble(batch->ctx[b]->hMll, batch->n, theta + 3 * b, loss + b, grad ? grad + 3 * b : nullptr);
+    if (st[b] == PCABO_OK)
+      mll_assemble(batch->ctx[b]->hMll, batch->n, BATCH_FIT_M, false, theta + (size_t)BATCH_FIT_NVAR * b, loss + b,
+                   grad ? grad + (size_t)BATCH_FIT_NVAR * b : nullptr);
     else if (act[b]) worst = st[b];
     if (status) status[b] = st[b];
   }
@@ -2144,7 +2115,7 @@ int pcabo_batch_gp_fit(pcabo_batch* batch, double* theta_inout, double* loss, in
   std::vector<FitRun> runs((size_t)B);                   // (a parked run stays OUT: it rides along at the shared model)
   for (int b = 0; b < B; ++b) {
     runs[b].bind(batch->ctx[b]->hMll);
-    if (act[b]) runs[b].init(theta_inout + 3 * b);
+    if (act[b]) runs[b].init(theta_inout + (size_t)BATCH_FIT_NVAR * b, BATCH_FIT_M, false);
   }
   batch->fit_rounds = 0;
   const auto round = [&](const std::vector<const double*>& th, int* st) { return batch_mll_round(batch, th, st); };
@@ -2158,9 +2129,9 @@ int pcabo_batch_gp_fit(pcabo_batch* batch, double* theta_inout, double* loss, in
     const FitRun& r = runs[b];
     if (status) status[b] = r.status;
     if (!act[b]) continue;
-    if (r.status == PCABO_ERR_ARG) theta_domain_err(batch->ctx[b]);
+    if (r.status == PCABO_ERR_ARG) theta_domain_err(batch->ctx[b], "pcabo_batch_gp_fit", false);
     if (r.status != PCABO_OK) { worst = r.status; batch->ctx[b]->have_gp = false; continue; }
-    memcpy(theta_inout + 3 * b, r.xr, sizeof(r.xr));
+    memcpy(theta_inout + (size_t)BATCH_FIT_NVAR * b, r.xr, (size_t)r.nvar * sizeof(double));
     if (loss) loss[b] = r.fr;
     if (info) r.report(info + 4 * b);
   }

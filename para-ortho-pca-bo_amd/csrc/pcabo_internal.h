@@ -381,16 +381,14 @@ int launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, doubl
 void launch_trinv_diag_w(hipStream_t s, const double* L, int nblk, int ld, double* R, ZB zb = ZB());
 void launch_alpha(hipStream_t s, const double* R, const double* ys, int n, int NP, int ld, double* tmp, double* alpha,
                   ZB zb = ZB());
-// marginal-likelihood pieces of a conditioned state (kernels_fit.hip, Matern-5/2): partial = 2 doubles per lower 64 x 64 tile,
-// out[6] = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, sum_ij W_ij dK_ij/dlog l}
+// marginal-likelihood pieces of a conditioned state (kernels_fit.hip, Matern-5/2): partial = 1 + M doubles per lower 64 x 64 tile,
+// out[5 + M] = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, then M sums}.  The shared lengthscale: M = 1,
+// sum_ij W_ij dK_ij/dlog l.  ard (one lengthscale per input, folded into the Normalize ranges): M = KP, S_c = sum_ij W_ij
+// dK_ij/dlog l_c for c < KP.
 // zb.B > 1: one launch pair for the B runs of a batch (blockIdx.z = run, k / KP of a run from k_dev, n and NP common)
-void launch_mll_grad(hipStream_t s, const double* R, const double* AT, const double* nrm, const double* alpha, const double* L,
-                     const double* ys, int n, int NP, int KP, int ld, double* partial, double* out,
+void launch_mll_grad(hipStream_t s, bool ard, const double* R, const double* AT, const double* nrm, const double* alpha,
+                     const double* L, const double* ys, int n, int NP, int KP, int ld, double* partial, double* out,
                      const int* k_dev = nullptr, ZB zb = ZB());
-// the ARD form (one lengthscale per input, folded into the Normalize ranges of a single context): partial = 1 + KP doubles per
-// tile, out[5 + KP] = {the first five sums above, S_c = sum_ij W_ij dK_ij/dlog l_c for c < KP}
-void launch_mll_grad_ard(hipStream_t s, const double* R, const double* AT, const double* nrm, const double* alpha, const double* L,
-                         const double* ys, int n, int NP, int KP, int ld, double* partial, double* out);
 void launch_acq(hipStream_t s, const QueryArgs* qa, const double* Xq, int q, const GpModel& m, AcqParams p, double* partial,
                 unsigned int* counters, double* val, double* grad, double* host_val, double* host_grad, HostMirror* hm,
                 unsigned long long seq,

@@ -366,74 +366,66 @@ class Context:
         return y, Z, k, nb
 
     @staticmethod
-    def _fit_result(theta, loss):
-        rho = float(theta[2])                           # softplus as torch (and the library) compute it
-        return {"lengthscale": math.log1p(math.exp(rho)) if rho <= 20.0 else rho,
-                "noise": float(theta[0]), "mean_constant": float(theta[1]), "loss": float(loss), "theta": theta.copy()}
+    def _fit_result(theta, loss, ard=False):
+        if ard:                                         # softplus as torch (and the library) compute it
+            rho = theta[2:]
+            ls = {"lengthscales": np.where(rho > 20.0, rho, np.log1p(np.exp(np.minimum(rho, 20.0))))}
+        else:
+            rho = float(theta[2])
+            ls = {"lengthscale": math.log1p(math.exp(rho)) if rho <= 20.0 else rho}
+        return {**ls, "noise": float(theta[0]), "mean_constant": float(theta[1]), "loss": float(loss), "theta": theta.copy()}
+
+    @staticmethod
+    def _theta(theta, k, ard):
+        if not ard:
+            return _f64(theta, (3,)).copy()
+        if theta is None:                               # a freshly built model: (noise, mean constant, rho_1 .. rho_k = 0)
+            return np.array(FIT_THETA0[:2] + (0.0,) * k, dtype=np.float64)
+        return _f64(theta, (2 + k,)).copy()
+
+    def _gp_mll(self, ard, y, theta, Z, norm_bounds, kernel):
+        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
+        th = self._theta(theta, k, ard)
+        loss, g = C.c_double(0.0), np.empty(th.shape[0])
+        fn = LIB.pcabo_gp_mll_ard if ard else LIB.pcabo_gp_mll
+        self._chk(fn(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th), C.byref(loss), _ptr(g)))
+        self.n, self.k = y.shape[0], k
+        return {**self._fit_result(th, loss.value, ard), "grad": g}
+
+    def _gp_fit(self, ard, y, theta0, Z, norm_bounds, kernel):
+        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
+        th = self._theta(theta0, k, ard)
+        loss, info = C.c_double(0.0), np.zeros(4, dtype=np.int32)
+        fn = LIB.pcabo_gp_fit_ard if ard else LIB.pcabo_gp_fit
+        self._chk(fn(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th), C.byref(loss), _ptr(info)))
+        self.n, self.k = y.shape[0], k
+        return {**self._fit_result(th, loss.value, ard), "iterations": int(info[0]), "evaluations": int(info[1]),
+                "warnflag": int(info[2]), "task": int(info[3])}
 
     def gp_mll(self, y, theta=FIT_THETA0, Z=None, norm_bounds=None, kernel=KERNEL_MATERN52):
         """Loss of the GP fit and its gradient at theta = (noise, mean constant, raw lengthscale); the context is left
         conditioned at theta.  Returns the fit's dict (`lengthscale`, `noise`, `mean_constant`, `loss`) with `grad` (3,)."""
-        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
-        th = _f64(theta, (3,))
-        loss, g = C.c_double(0.0), np.empty(3)
-        self._chk(LIB.pcabo_gp_mll(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th), C.byref(loss),
-                                   _ptr(g)))
-        self.n, self.k = y.shape[0], k
-        return {**self._fit_result(th, loss.value), "grad": g}
+        return self._gp_mll(False, y, theta, Z, norm_bounds, kernel)
 
     def gp_fit(self, y, theta0=FIT_THETA0, Z=None, norm_bounds=None, kernel=KERNEL_MATERN52):
         """Fit (noise, mean constant, raw lengthscale) by the marginal likelihood from theta0 (default: the model's initial
         values); the context is left conditioned at the fit.  Returns `lengthscale`, `noise`, `mean_constant`, `loss`,
         `iterations`, `evaluations`, `warnflag` (scipy's), `task` and `theta`."""
-        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
-        th = _f64(theta0, (3,)).copy()
-        loss, info = C.c_double(0.0), np.zeros(4, dtype=np.int32)
-        self._chk(LIB.pcabo_gp_fit(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th), C.byref(loss),
-                                   _ptr(info)))
-        self.n, self.k = y.shape[0], k
-        return {**self._fit_result(th, loss.value), "iterations": int(info[0]), "evaluations": int(info[1]),
-                "warnflag": int(info[2]), "task": int(info[3])}
+        return self._gp_fit(False, y, theta0, Z, norm_bounds, kernel)
 
     # ---- the same fit with one lengthscale per input (pcabo_gp_mll_ard / pcabo_gp_fit_ard) ------
-    @staticmethod
-    def _fit_result_ard(theta, loss):
-        rho = theta[2:]                                 # softplus as torch (and the library) compute it
-        ls = np.where(rho > 20.0, rho, np.log1p(np.exp(np.minimum(rho, 20.0))))
-        return {"lengthscales": ls, "noise": float(theta[0]), "mean_constant": float(theta[1]), "loss": float(loss),
-                "theta": theta.copy()}
-
-    @staticmethod
-    def _theta_ard(theta, k):
-        if theta is None:                               # a freshly built model: (noise, mean constant, rho_1 .. rho_k = 0)
-            return np.array(FIT_THETA0[:2] + (0.0,) * k, dtype=np.float64)
-        return _f64(theta, (2 + k,)).copy()
-
     def gp_mll_ard(self, y, theta, Z=None, norm_bounds=None, kernel=KERNEL_MATERN52):
         """Loss of the ARD fit and its gradient at theta = (noise, mean constant, rho_1 .. rho_k), lengthscale_c =
         softplus(rho_c); the context is left conditioned at theta (the lengthscales folded into the Normalize ranges, which
         gp_state() then reports).  Returns `lengthscales` (k,), `noise`, `mean_constant`, `loss`, `theta` and `grad` (2 + k,)."""
-        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
-        th = self._theta_ard(theta, k)
-        loss, g = C.c_double(0.0), np.empty(2 + k)
-        self._chk(LIB.pcabo_gp_mll_ard(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th),
-                                       C.byref(loss), _ptr(g)))
-        self.n, self.k = y.shape[0], k
-        return {**self._fit_result_ard(th, loss.value), "grad": g}
+        return self._gp_mll(True, y, theta, Z, norm_bounds, kernel)
 
     def gp_fit_ard(self, y, theta0=None, Z=None, norm_bounds=None, kernel=KERNEL_MATERN52):
         """gp_fit with one lengthscale per input, from theta0 (default: the model's initial values, every rho_c = 0).  Returns
         `theta`, `noise`, `mean_constant`, `lengthscales` (k,), `loss`, `iterations`, `evaluations`, `warnflag`, `task`; the
         context is left conditioned at the fit.  The fit keeps every rho_c >= ln 2^-40 = -27.73 (an optimiser bound like the
         noise's 1e-4; a start below it is clipped to it)."""
-        y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
-        th = self._theta_ard(theta0, k)
-        loss, info = C.c_double(0.0), np.zeros(4, dtype=np.int32)
-        self._chk(LIB.pcabo_gp_fit_ard(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th),
-                                       C.byref(loss), _ptr(info)))
-        self.n, self.k = y.shape[0], k
-        return {**self._fit_result_ard(th, loss.value), "iterations": int(info[0]), "evaluations": int(info[1]),
-                "warnflag": int(info[2]), "task": int(info[3])}
+        return self._gp_fit(True, y, theta0, Z, norm_bounds, kernel)
 
     def gp_wait(self) -> None:
         self._chk(LIB.pcabo_gp_condition_end(self._h))

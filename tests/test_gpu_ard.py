@@ -1,4 +1,4 @@
-"""The GP fit with one lengthscale per input on the MI355X (pcabo_gp_mll_ard / pcabo_gp_fit_ard: k_mll_grad_ard, k_mll_finish_ard and
+"""The GP fit with one lengthscale per input on the MI355X (pcabo_gp_mll_ard / pcabo_gp_fit_ard: k_mll_grad<true>, k_mll_finish<true> and
 the lengthscales folded into the Normalize ranges by k_zstats; PCA_BO / Vanilla_BO fit_gp=True, ard=True) against the restatement of
 tests/ard_reference.py (torch float64 autograd + scipy's L-BFGS-B).
 

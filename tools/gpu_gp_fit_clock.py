@@ -6,7 +6,7 @@ Prints per shape: evaluations per fit, ms per fit, ms per evaluation (fit time /
 evaluation, (gp_mll - gp_condition) / gp_mll: k_mll_grad + k_mll_finish + the 48-byte copy.  Kernel times come from a separate
 run under `rocprofv3 --kernel-trace --stats` (one shape per run: --shapes 1050x89).
 
---ard adds the fit with one lengthscale per input (Context.gp_fit_ard / gp_mll_ard: k_mll_grad_ard + k_mll_finish_ard and a copy of
+--ard adds the fit with one lengthscale per input (Context.gp_fit_ard / gp_mll_ard: the ARD form of k_mll_grad + k_mll_finish and a copy of
 5 + KP doubles) on the same state, next to the scalar fit: evaluations, ms per fit, ms per evaluation, ms of gp_mll_ard alone and the
 two losses.  --relevant R lets y depend on the first R inputs only (0: on all of them, the scalar tool's state), the setting ARD is for.
 
