@@ -459,6 +459,17 @@ int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, con
 int pcabo_batch_gp_mll(pcabo_batch* batch, const double* theta /*B*3*/, double* loss /*B*/, double* grad /*B*3*/, int* status /*B*/);
 int pcabo_batch_gp_fit(pcabo_batch* batch, double* theta_inout /*B*3*/, double* loss /*B*/, int* info /*B*4*/, int* status /*B*/);
 int pcabo_batch_gp_fit_rounds(pcabo_batch* batch);
+/* The same two calls with one lengthscale per input (pcabo_gp_mll_ard / pcabo_gp_fit_ard for the B runs in lock-step).  Row b of
+ * theta (and of grad) starts ld_theta doubles behind row b - 1 and holds {s2, c, rho_1 .. rho_{k_b}}, k_b the run's own reduced
+ * dimension; ld_theta >= 2 + max_b k_b.  What lies beyond 2 + k_b in a row is ignored on input and left alone on output.
+ * Every run takes bit for bit the evaluations and the fit it takes alone through pcabo_gp_mll_ard / pcabo_gp_fit_ard; a run that
+ * takes part is left conditioned with its lengthscales folded into its Normalize ranges (pcabo_debug_gp_state), a parked run at
+ * the unfolded shared model.  Status codes, refusals and what follows the call as above; PCABO_ERR_ARG also for a ld_theta that
+ * is too small.  All runs of one call have this form of the model: the shared-lengthscale calls above are the other form. */
+int pcabo_batch_gp_mll_ard(pcabo_batch* batch, const double* theta /*B*ld_theta*/, int ld_theta, double* loss /*B*/,
+                           double* grad /*B*ld_theta*/, int* status /*B*/);
+int pcabo_batch_gp_fit_ard(pcabo_batch* batch, double* theta_inout /*B*ld_theta*/, int ld_theta, double* loss /*B*/,
+                           int* info /*B*4*/, int* status /*B*/);
 
 /* ---- BBOB f15-f24 objectives on the device, for runs that advance in lock-step ---------------------------------------
  * The reference evaluates `problem(x)` on the host, one candidate per BO iteration (PCA_BO.py:263; the problems come from

@@ -125,7 +125,7 @@ class ExperimentRunner:
                  experiment_name: str = "experiment", acquisition_function: str = "expected_improvement",
                  pca_components: Optional[int] = None, var_threshold: float = 0.95, verbose: bool = False,
                  progress: bool = True, batched: int = 0, side_by_side: int = 2, batch_acq_kernel: str = "group",
-                 fit_gp: bool = False, batched_fit_gp: bool = False, ucb_beta: Optional[float] = None, ard: bool = False):
+                 fit_gp: bool = False, batched_fit_gp: bool = False, ucb_beta: Optional[float] = None, ard: bool = False, batched_ard: bool = False):
         # fit_gp (not in the reference): every run fits its GP's hyperparameters by the marginal likelihood each iteration
         # (PCA_BO / Vanilla_BO fit_gp=True), one run after the other.  For the lock-step batches: batched_fit_gp below.
         self.fit_gp = bool(fit_gp)
@@ -139,13 +139,19 @@ class ExperimentRunner:
         if self.batched_fit_gp and int(batched) <= 1:
             raise ValueError("batched_fit_gp=True fits the GPs of the lock-step batches: it needs batched > 1 (for one run after "
                              "the other use fit_gp=True)")
-        # ard (with fit_gp): one lengthscale per input (PCA_BO / Vanilla_BO ard=True).  The lock-step batches fit one lengthscale.
+        # ard (with fit_gp): one lengthscale per input (PCA_BO / Vanilla_BO ard=True).  For the lock-step batches: batched_ard.
         self.ard = bool(ard)
         if self.ard and int(batched) > 1:
             raise ValueError("ard=True is a mode of the single-run classes (Algorithms.PCA_BO / Vanilla_BO, batched=0): the "
-                             "lock-step batches (batched > 1) fit one lengthscale")
+                             "lock-step batches (batched > 1) take batched_fit_gp=True, batched_ard=True")
         if self.ard and not self.fit_gp:
             raise ValueError("ard=True fits one lengthscale per input: it needs fit_gp=True")
+        # batched_ard (with batched_fit_gp; a keyword of its own like batched_fit_gp): the same inside the lock-step batches
+        # (pcabo.batchrun batched_ard=True, Batch.gp_fit_ard) - the rows fit_gp=True, ard=True writes one run after the other
+        self.batched_ard = bool(batched_ard)
+        if self.batched_ard and not self.batched_fit_gp:
+            raise ValueError("batched_ard=True fits one lengthscale per input in the lock-step batches: it needs batched > 1 and "
+                             "batched_fit_gp=True")
         # ucb_beta (not in the reference, where acquisition_function="upper_confidence_bound" raises at the first BO iteration):
         # handed to every optimiser and lock-step batch, which then build botorch's UpperConfidenceBound(model, beta=ucb_beta)
         from pcabo.acqopt import checked_ucb_beta
@@ -288,7 +294,7 @@ class ExperimentRunner:
                                       var_threshold=self.var_threshold, acquisition_function=self.acquisition_function,
                                       device=self.device, workers=workers_for(len(group)) if len(group) > 1 else 0,
                                       host_threads=max(1, 8 // len(group)), acq_kernel=kernel, fit_gp=self.batched_fit_gp,
-                                      ucb_beta=self.ucb_beta)
+                                      ucb_beta=self.ucb_beta, batched_ard=self.batched_ard)
                 jobs.append((dim, chunk, probs, n_doe, runner))
             kernel = group[0][2]
             start_time = time()
@@ -348,7 +354,7 @@ class ExperimentRunner:
                 provenance = {"arithmetic_mode": ",".join(f"d{dim}={self.arithmetic_modes[dim]}" for dim in self.dimensions)}
                 if self.fit_gp or self.batched_fit_gp:
                     # hyperparameters fitted by the marginal likelihood (+ noise prior); -ard: one lengthscale per input
-                    provenance["gp_fit"] = "map-ard" if self.ard else "map"
+                    provenance["gp_fit"] = "map-ard" if self.ard or self.batched_ard else "map"
                 if self.ucb_beta is not None:            # (only when set: the files of every other configuration stay as they were)
                     provenance["ucb_beta"] = f"{self.ucb_beta}"
                 logger.set_experiment_attributes({

@@ -590,6 +590,66 @@ void test_fit_run() {
     for (int j = 2; j < 5; ++j) CHECK(both[1].theta[j] >= FIT_ARD_RHO_MIN, "rho_%d = %g below its bound", j - 2, both[1].theta[j]);
     CHECK(both[0].info[1] != both[1].info[1], "the two runs finished in the same round: neither rode along");
   }
+  // (e) the batch's ARD round (pcabo_batch_gp_fit_ard): B ARD runs of different m = k_b (3, 1, 2, 4) stepped side by side, their
+  // sums at a common stride (5 + the largest m, as the strided copy of the results leaves them), one run parked (never started,
+  // never evaluated: it rides along at the shared model).  Every run takes the fit it takes alone, bit for bit; the runs do not all
+  // finish in the same round.
+  {
+    const int ks[4] = {3, 1, 2, 4}, KMAX = 4, HS = 5 + KMAX, B4 = 4;
+    std::vector<TinyGP> gps4;
+    for (int b = 0; b < B4; ++b) gps4.push_back(tiny_gp(20 + b, 12, std::max(ks[b], 2)));   // (tiny_gp's target reads two inputs)
+    for (int b = 0; b < B4; ++b)
+      if (ks[b] < gps4[b].k) {                             // keep the first ks[b] inputs only
+        TinyGP g; g.n = gps4[b].n; g.k = ks[b]; g.y = gps4[b].y; g.Z.resize((size_t)g.n * g.k);
+        for (int i = 0; i < g.n; ++i) for (int t = 0; t < g.k; ++t) g.Z[i * g.k + t] = gps4[b].Z[i * gps4[b].k + t];
+        gps4[b] = g;
+      }
+    struct Out { int status, nvar, info[4]; double theta[2 + 4], loss; };
+    const auto drive = [&](const std::vector<int>& which, int parked) {
+      const size_t nb = which.size();
+      std::vector<FitRun> runs(nb);
+      std::vector<double> hs((size_t)HS * nb, 0.0);
+      std::vector<int> evals(nb, 0);
+      for (size_t b = 0; b < nb; ++b) {
+        double start[2 + 4] = {FIT_START[0], 0.0, 0.0, 0.0, 0.0, 0.0};
+        runs[b].bind(&hs[(size_t)HS * b]);
+        if ((int)b != parked) runs[b].init(start, gps4[which[b]].k, true);
+      }
+      int rounds = 0;
+      CHECK(fit_rounds(runs, 12, [&](const std::vector<const double*>& th, int* st) {
+        ++rounds;
+        for (size_t b = 0; b < nb; ++b) {
+          if (!th[b]) { CHECK(runs[b].state == FitRun::OUT, "run %zu: no theta but not out", b); continue; }
+          CHECK((int)b != parked, "the parked run was evaluated");
+          if (runs[b].state != FitRun::RESTING) ++evals[b];
+          st[b] = tiny_gp_sums(gps4[which[b]], th[b], &hs[(size_t)HS * b], true) ? PCABO_OK : PCABO_ERR_NOT_PD;
+        }
+        return (int)PCABO_OK;
+      }) == PCABO_OK, "fit_rounds");
+      std::vector<Out> out(nb);
+      for (size_t b = 0; b < nb; ++b) {
+        Out& o = out[b];
+        std::memset(&o, 0, sizeof(o));
+        o.status = runs[b].status; o.nvar = runs[b].nvar;
+        if (o.status != PCABO_OK) continue;
+        CHECK(o.nvar == 2 + gps4[which[b]].k, "run %zu: %d variables", b, o.nvar);
+        std::memcpy(o.theta, runs[b].xr, (size_t)o.nvar * sizeof(double)); o.loss = runs[b].fr; runs[b].report(o.info);
+        CHECK(evals[b] >= o.info[1] && rounds >= evals[b], "run %zu: %d evaluations counted, %d made, %d rounds", b, o.info[1], evals[b], rounds);
+      }
+      return out;
+    };
+    const std::vector<Out> all4 = drive({0, 1, 2, 3}, -1), parked4 = drive({0, 1, 2, 3}, 1);
+    int emin = 1 << 30, emax = 0;
+    for (int b = 0; b < B4; ++b) {
+      const std::vector<Out> one = drive({b}, -1);
+      CHECK(one[0].status == PCABO_OK && one[0].info[0] > 2, "ARD run %d alone: status %d after %d iterations", b, one[0].status, one[0].info[0]);
+      CHECK(std::memcmp(&all4[b], &one[0], sizeof(Out)) == 0, "ARD run %d (m = %d) in lock-step differs from the run alone", b, ks[b]);
+      if (b == 1) CHECK(parked4[b].status == PCABO_ERR_ARG, "the parked ARD run has status %d", parked4[b].status);
+      else CHECK(std::memcmp(&parked4[b], &one[0], sizeof(Out)) == 0, "ARD run %d beside a parked run differs from the run alone", b);
+      emin = std::min(emin, one[0].info[1]); emax = std::max(emax, one[0].info[1]);
+    }
+    CHECK(emin < emax, "the ARD runs all took %d evaluations: nothing rode along", emin);
+  }
 }
 
 // The host's inverse map (host_side.h) against the loop of k_inverse_map written out coordinate by coordinate: one fused

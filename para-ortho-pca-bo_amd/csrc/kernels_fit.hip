@@ -71,8 +71,12 @@ __device__ __forceinline__ void mll_tile_products(const double* __restrict__ R, 
 //         wave order through LDS.
 // partial[(1 + M) t]: tile t's trace part, then its M sums; M = 1 (S), ARD: M = KP (S_c; rows c >= k of AT are zero).
 // k_mll_finish adds them in tile order.
-// Batched (pcabo_batch_gp_mll / pcabo_batch_gp_fit): blockIdx.z = run, every operand zs bytes further per run, KP from the run's
-// own k (the runs of a PCA batch differ in k); n and NP are common.  No sum crosses a run, so a run's bits are the single launch's.
+// Batched (pcabo_batch_gp_mll / pcabo_batch_gp_fit and their _ard forms): blockIdx.z = run, every operand zs bytes further per
+// run, KP from the run's own k (the runs of a PCA batch differ in k); n and NP are common.  No sum crosses a run, so a run's bits
+// are the single launch's.  ARD with M differing per run: run b's partial block starts at its own base (partial + b zs) and is
+// packed at ITS stride, 1 + KP_b doubles per tile, exactly as its single launch lays it out; only `out` lies at one offset for
+// all runs, which the host puts behind the widest block ((1 + KP_max) tiles doubles in), so one strided copy of 5 + KP_max
+// doubles per run brings every run's results back (a narrower run's words beyond 5 + KP_b are never written and never read).
 #define MLL_ARD_CHUNK 8
 template <bool ARD>
 __global__ __launch_bounds__(256) void k_mll_grad(const double* __restrict__ R, const double* __restrict__ AT,

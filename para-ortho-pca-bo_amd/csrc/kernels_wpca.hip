@@ -559,8 +559,11 @@ __global__ __launch_bounds__(WP_THREADS) void k_zstats(const double* __restrict_
                                                        HostMirror* hm, const int* __restrict__ k_dev, size_t zs,
                                                        size_t hzs, double mean_c, const double* __restrict__ hyp,
                                                        const double* __restrict__ ard_ls) {
-  ZRUN(Z); ZRUN(y); ZRUN(user_nb); ZRUN(bounds4); ZRUN(zn_mean); ZRUN(ystats); ZRUN(ys); ZRUN(k_dev); ZRUN(hyp);
+  ZRUN(Z); ZRUN(y); ZRUN(user_nb); ZRUN(bounds4); ZRUN(zn_mean); ZRUN(ystats); ZRUN(ys); ZRUN(k_dev); ZRUN(hyp); ZRUN(ard_ls);
   if (hyp) mean_c = hyp[PCABO_HYP_MEAN_C];      // a batch whose runs carry their own fitted model
+  // per-run fold switch of a batch's ARD round (uniform over the work-group: one run per blockIdx.z): a run that rests at the
+  // shared model is not folded (its range times 1.0 would not be its range: nlo + (nhi - nlo) is not nhi in floating point)
+  const bool fold = ard_ls && (!hyp || hyp[PCABO_HYP_ARD_FOLD] != 0.0);
   hm = zrun(hm, hzs, blockIdx.z);
   if (k_dev) k = *k_dev;          // enqueued behind the wPCA: the reduced dimension is not on the host yet
   __shared__ double s_red[WP_THREADS];
@@ -597,12 +600,13 @@ __global__ __launch_bounds__(WP_THREADS) void k_zstats(const double* __restrict_
     double rng = b - a;
     double nlo = a - 0.1 * rng, nhi = b + 0.1 * rng;
     if (user_nb) { nlo = user_nb[tid]; nhi = user_nb[k + tid]; }
-    // ARD fit (pcabo_gp_mll_ard, single context only): the lengthscale of this input is folded into its Normalize range, so
+    // ARD fit (pcabo_gp_mll_ard; pcabo_batch_gp_mll_ard: every run its own k lengthscales, zs bytes apart, and its own switch in
+    // its hyperparameter block): the lengthscale of this input is folded into its Normalize range, so
     // every kernel downstream divides by (hi - lo) l_c and runs with 1 / lengthscale = 1.  The search box below is not folded.
     // A folded range must survive the addition to lo and keep the normalised points finite: below 2^-40 of the larger of |lo|
     // and the range it is held there.  That is a lengthscale some 1e-12 of the data's spread, where K = I to rounding just as
     // for the exact model (a line search's trial steps reach such values; no fitted model does).
-    if (ard_ls) nhi = nlo + fmax((nhi - nlo) * ard_ls[tid], fmax(fabs(nlo), nhi - nlo) * 0x1p-40);
+    if (fold) nhi = nlo + fmax((nhi - nlo) * ard_ls[tid], fmax(fabs(nlo), nhi - nlo) * 0x1p-40);
     double alo = a - 0.5 * rng, ahi = b + 0.5 * rng;
     if (ahi - alo < 0.1) { double mid = (ahi + alo) / 2; alo = mid - 0.1 / 2; ahi = mid + 0.1 / 2; }
     bounds4[tid] = nlo; bounds4[PCABO_MAXD + tid] = nhi;

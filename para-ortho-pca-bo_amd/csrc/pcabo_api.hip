@@ -534,7 +534,8 @@ struct RowsDH {
   ZB zb;
   hipEvent_t ev[2];                      // recorded behind k_zstats (null: none): the search box is on its way to the host
   int* cnt_S; bool* cnt_dirty;           // the owner's ticket state (null: the tickets are left alone)
-  const double* ard_ls = nullptr;        // ARD fit of a single context: k lengthscales on the device, folded by k_zstats (inv_ls = 1)
+  const double* ard_ls = nullptr;        // ARD fit: k lengthscales on the device, folded by k_zstats (inv_ls = 1); a batch: run 0's,
+                                         // every run's own where its zb.hyp block has PCABO_HYP_ARD_FOLD set
   hipEvent_t ev_zn = nullptr;            // recorded behind k_znorm (null: none): ZnT and the Normalize bounds are final
 };
 template <class Phase>
@@ -904,7 +905,7 @@ static_assert(FIT_ARD_MAXVAR == 2 + PCABO_MAXD, "host_side.h sizes a run for PCA
 // Inputs of a fit staged like pcabo_gp_condition_begin's; *unb = the device copy of the user's Normalize bounds or NULL.
 static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, bool ard, const double* Z, const double* y, int n, int k,
                             const double* norm_bounds, int kernel, const double** unb) {
-  if (ard && ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch; the ARD fit is for single contexts", who);
+  if (ard && ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch (its ARD fit: pcabo_batch_gp_mll_ard / pcabo_batch_gp_fit_ard)", who);
   if (!y || k < 1 || k > ctx->max_d || n < 2 || n > ctx->max_n)
     return set_err(ctx, PCABO_ERR_ARG, "%s: bad argument or size beyond context capacity", who);
   if (kernel != PCABO_KERNEL_MATERN52)
@@ -1995,39 +1996,49 @@ static int batch_put_best_f(pcabo_batch* batch, const double* best_f) {
 
 // ---- lock-step GP hyperparameter fit of a batch (DESIGN.md "GP hyperparameter fit", the batched form) -------------------
 // One round = ONE launch sequence for all B runs (blockIdx.z = run): every run is conditioned at its own theta, read by k_zstats,
-// k_znorm and k_gram from the runs' dHyp blocks, then k_mll_grad + k_mll_finish, one strided copy of B x 6 doubles and one wait.
-// The runs of a batch have the shared lengthscale (BATCH_FIT_M = 1 rho, 3 variables each); ARD is for single contexts.
-// hyp_theta[b]: the theta run b is conditioned at, or NULL for a run that rests at the batch's shared model (parked runs).
+// k_znorm and k_gram from the runs' dHyp blocks, then k_mll_grad + k_mll_finish, one strided copy of the runs' results and one wait.
+// All runs of a round have one form of the model: the shared lengthscale (m = 1 rho, 3 variables each, 6 results) or, ard, one
+// lengthscale per input (run b: m = k_b, 5 + KP_b results; the copy brings 5 + KP_max doubles per run).  In the ARD form a run's
+// lengthscales softplus(rho_c) travel in its dArdLs (one strided copy per round) and k_zstats folds them into its Normalize ranges
+// where word PCABO_HYP_ARD_FOLD of its block says so; its 1 / lengthscale is 1.
+// hyp_theta[b]: the theta run b is conditioned at, or NULL for a run that rests at the batch's shared model (parked runs): the
+// shared lengthscale, no fold.
 // A run whose Cholesky failed in the round is redone alone on its own context (mll_attempts from the first jitter on), as
 // batch_score_collect does; st[b] is PCABO_OK, PCABO_ERR_NOT_PD or a HIP error for every run with a theta, untouched otherwise.
-constexpr int BATCH_FIT_M = 1, BATCH_FIT_NVAR = 2 + BATCH_FIT_M;
-static int batch_mll_round(pcabo_batch* batch, const std::vector<const double*>& hyp_theta, int* st) {
+static int batch_fit_m(const pcabo_batch* batch, bool ard, int b) { return ard ? batch->ctx[b]->k : 1; }
+static int batch_mll_round(pcabo_batch* batch, bool ard, const std::vector<const double*>& hyp_theta, int* st) {
   const int B = batch->B, n = batch->n, NP = batch->NP;
   pcabo_ctx* c0 = batch->ctx[0];
   hipStream_t s = batch->stream;
+  const int kmax = batch_max_k(batch), Mmax = ard ? round_up(kmax, 4) : 1;
   for (int b = 0; b < B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
     const double* th = hyp_theta[b];
-    // the very doubles the single-context path passes by value: 1.0 / softplus(rho), the noise, the mean constant
-    const double ls = th ? softplus_host(th[2]) : batch->lengthscale;
+    // the very doubles the single-context path passes by value: 1.0 / softplus(rho) (ard: 1.0 / 1.0), the noise, the mean constant
+    const bool fold = ard && th;
+    const double ls = !th ? batch->lengthscale : (ard ? 1.0 : softplus_host(th[2]));
     c->hHyp[PCABO_HYP_INV_LS] = 1.0 / ls;
     c->hHyp[PCABO_HYP_NOISE] = th ? th[0] : batch->noise;
     c->hHyp[PCABO_HYP_MEAN_C] = th ? th[1] : 0.0;
-    c->hHyp[3] = 0.0;
+    c->hHyp[PCABO_HYP_ARD_FOLD] = fold ? 1.0 : 0.0;
+    if (fold)                            // the very doubles mll_launch writes for a single context
+      for (int j = 0; j < c->k; ++j) c->hArdLs[j] = softplus_host(th[2 + j]);
     c->lengthscale = ls; c->noise = c->hHyp[PCABO_HYP_NOISE]; c->kernel = batch->kernel;   // single-context calls on a member see its model
     c->have_gp = false;
   }
   BHIPCHK(hipMemcpy2DAsync(c0->dHyp, batch->zs, c0->hHyp, batch->hzs, PCABO_HYP_WORDS * sizeof(double), B, hipMemcpyHostToDevice, s));
+  if (ard) BHIPCHK(hipMemcpy2DAsync(c0->dArdLs, batch->zs, c0->hArdLs, batch->hzs, (size_t)kmax * sizeof(double), B, hipMemcpyHostToDevice, s));
   ZB zb = batch_zb(batch);
   zb.hyp = c0->dHyp;
-  const RowsDH a{batch->fitZ, batch->fitY, batch->fitUnb, n, -1, 0, c0->dK, 0.0, 0.0, 0.0, batch->kernel, zb, {nullptr, nullptr}, nullptr, nullptr};
+  const RowsDH a{batch->fitZ, batch->fitY, batch->fitUnb, n, -1, 0, c0->dK, 0.0, 0.0, 0.0, batch->kernel, zb, {nullptr, nullptr}, nullptr, nullptr,
+                 ard ? c0->dArdLs : nullptr};
   const int rc = enqueue_rows_dh(c0, s, a, [&](int phase) -> int {
-    if (phase != 4) return PCABO_OK;     // behind alpha: the likelihood kernels and the strided copy of the runs' 6 results
+    if (phase != 4) return PCABO_OK;     // behind alpha: the likelihood kernels and the strided copy of the runs' results
     pcabo_ctx* ctx = c0;
     const int nb = NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
-    double* out = c0->dMll + (size_t)(1 + BATCH_FIT_M) * tiles;
-    launch_mll_grad(s, false, c0->dR, c0->dAT, c0->dNrm, c0->dAlpha, c0->dL, c0->dYs, n, NP, 0, c0->ld, c0->dMll, out, c0->dK, zb);
-    HIPCHK(hipMemcpy2DAsync(c0->hMll, batch->hzs, out, batch->zs, (5 + BATCH_FIT_M) * sizeof(double), B, hipMemcpyDeviceToHost, s));
+    double* out = c0->dMll + (size_t)(1 + Mmax) * tiles;      // one offset for all runs, behind the widest run's tile partials
+    launch_mll_grad(s, ard, c0->dR, c0->dAT, c0->dNrm, c0->dAlpha, c0->dL, c0->dYs, n, NP, 0, c0->ld, c0->dMll, out, c0->dK, zb);
+    HIPCHK(hipMemcpy2DAsync(c0->hMll, batch->hzs, out, batch->zs, (size_t)(5 + Mmax) * sizeof(double), B, hipMemcpyDeviceToHost, s));
     return PCABO_OK;
   });
   if (rc != PCABO_OK) return bset_err(batch, rc, "%s", c0->err);
@@ -2038,13 +2049,14 @@ static int batch_mll_round(pcabo_batch* batch, const std::vector<const double*>&
     pcabo_ctx* c = batch->ctx[b];
     if (c->hm->chol_info == 0) { c->have_gp = true; if (hyp_theta[b]) st[b] = PCABO_OK; continue; }
     if (!hyp_theta[b]) continue;
-    st[b] = mll_attempts(c, 1, false);   // rare: jitter 1e-8, 1e-7, 1e-6 for this run alone (sets have_gp)
+    st[b] = mll_attempts(c, 1, ard);     // rare: jitter 1e-8, 1e-7, 1e-6 for this run alone (sets have_gp)
   }
   return PCABO_OK;
 }
 
-// what both entry points need before the first round; *act = the runs that take part
-static int batch_fit_prepare(pcabo_batch* batch, const char* who, std::vector<char>* act, int* status) {
+// what both entry points need before the first round; *act = the runs that take part.  ld_theta: doubles between two runs' thetas
+// (the ARD form: at least 2 + the largest k of the runs, known once the wPCA results are in)
+static int batch_fit_prepare(pcabo_batch* batch, const char* who, bool ard, int ld_theta, std::vector<char>* act, int* status) {
   if (batch->kernel != PCABO_KERNEL_MATERN52 && (batch->gp_pending || batch->have_gp))
     return bset_err(batch, PCABO_ERR_ARG, "%s: the fit is restated for the Matern-5/2 kernel only", who);
   if ((!batch->gp_pending && !batch->fitted) || !batch->fitZ)
@@ -2053,6 +2065,8 @@ static int batch_fit_prepare(pcabo_batch* batch, const char* who, std::vector<ch
     return bset_err(batch, PCABO_ERR_ARG, "%s: a _begin call of this batch has not been ended", who);
   BHIPCHK(hipSetDevice(batch->device));
   if (batch->wpca_uncollected) { int rc = pcabo_batch_wpca_results(batch, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc != PCABO_OK) return rc; }
+  if (ard && ld_theta < 2 + batch_max_k(batch))
+    return bset_err(batch, PCABO_ERR_ARG, "%s: ld_theta is smaller than 2 + the largest reduced dimension of the runs (%d)", who, 2 + batch_max_k(batch));
   act->assign((size_t)batch->B, 0);
   for (int b = 0; b < batch->B; ++b) {
     (*act)[b] = batch->active[b] ? 1 : 0;
@@ -2072,53 +2086,55 @@ static void batch_fit_done(pcabo_batch* batch) {
   }
 }
 
-extern "C" {
-
-int pcabo_batch_gp_mll(pcabo_batch* batch, const double* theta, double* loss, double* grad, int* status) {
+// pcabo_batch_gp_mll / pcabo_batch_gp_mll_ard: row b of theta and grad starts ld doubles behind row b - 1 (2 + m_b of them used)
+static int batch_gp_mll_call(pcabo_batch* batch, const char* who, bool ard, const double* theta, int ld, double* loss, double* grad,
+                             int* status) {
   if (!batch) return PCABO_ERR_ARG;
-  if (!theta || !loss) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_mll: theta and loss are required%s", "");
+  if (!theta || !loss) return bset_err(batch, PCABO_ERR_ARG, "%s: theta and loss are required", who);
   std::vector<char> act;
-  int rc = batch_fit_prepare(batch, "pcabo_batch_gp_mll", &act, status);
+  int rc = batch_fit_prepare(batch, who, ard, ld, &act, status);
   if (rc != PCABO_OK) return rc;
   const int B = batch->B;
   std::vector<const double*> th((size_t)B, nullptr);
   std::vector<int> st((size_t)B, PCABO_ERR_ARG);
   for (int b = 0; b < B; ++b) {
     if (!act[b]) continue;
-    const double* t = theta + (size_t)BATCH_FIT_NVAR * b;
-    if (mll_theta_ok(t, BATCH_FIT_M)) th[b] = t;
-    else theta_domain_err(batch->ctx[b], "pcabo_batch_gp_mll", false);
+    const double* t = theta + (size_t)ld * b;
+    if (mll_theta_ok(t, batch_fit_m(batch, ard, b))) th[b] = t;
+    else theta_domain_err(batch->ctx[b], who, ard);
   }
   batch->fit_rounds = 0;
-  rc = batch_mll_round(batch, th, st.data());
+  rc = batch_mll_round(batch, ard, th, st.data());
   if (rc != PCABO_OK) return rc;
   batch_fit_done(batch);
   int worst = PCABO_OK;
   for (int b = 0; b < B; ++b) {
     if (st[b] == PCABO_OK)
-      mll_assemble(batch->ctx[b]->hMll, batch->n, BATCH_FIT_M, false, theta + (size_t)BATCH_FIT_NVAR * b, loss + b,
-                   grad ? grad + (size_t)BATCH_FIT_NVAR * b : nullptr);
+      mll_assemble(batch->ctx[b]->hMll, batch->n, batch_fit_m(batch, ard, b), ard, theta + (size_t)ld * b, loss + b,
+                   grad ? grad + (size_t)ld * b : nullptr);
     else if (act[b]) worst = st[b];
     if (status) status[b] = st[b];
   }
-  if (worst != PCABO_OK && !status) return bset_err(batch, worst, "pcabo_batch_gp_mll: a run of the batch failed (status array not given)%s", "");
+  if (worst != PCABO_OK && !status) return bset_err(batch, worst, "%s: a run of the batch failed (status array not given)", who);
   return PCABO_OK;
 }
 
-int pcabo_batch_gp_fit(pcabo_batch* batch, double* theta_inout, double* loss, int* info, int* status) {
+// pcabo_batch_gp_fit / pcabo_batch_gp_fit_ard
+static int batch_gp_fit_call(pcabo_batch* batch, const char* who, bool ard, double* theta_inout, int ld, double* loss, int* info,
+                             int* status) {
   if (!batch) return PCABO_ERR_ARG;
-  if (!theta_inout) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_fit: theta_inout is required%s", "");
+  if (!theta_inout) return bset_err(batch, PCABO_ERR_ARG, "%s: theta_inout is required", who);
   std::vector<char> act;
-  int rc = batch_fit_prepare(batch, "pcabo_batch_gp_fit", &act, status);
+  int rc = batch_fit_prepare(batch, who, ard, ld, &act, status);
   if (rc != PCABO_OK) return rc;
   const int B = batch->B;
   std::vector<FitRun> runs((size_t)B);                   // (a parked run stays OUT: it rides along at the shared model)
   for (int b = 0; b < B; ++b) {
     runs[b].bind(batch->ctx[b]->hMll);
-    if (act[b]) runs[b].init(theta_inout + (size_t)BATCH_FIT_NVAR * b, BATCH_FIT_M, false);
+    if (act[b]) runs[b].init(theta_inout + (size_t)ld * b, batch_fit_m(batch, ard, b), ard);
   }
   batch->fit_rounds = 0;
-  const auto round = [&](const std::vector<const double*>& th, int* st) { return batch_mll_round(batch, th, st); };
+  const auto round = [&](const std::vector<const double*>& th, int* st) { return batch_mll_round(batch, ard, th, st); };
   rc = fit_rounds(runs, batch->n, round);
   // (no run wanted an evaluation: one round all the same, the batch is left conditioned at the shared model)
   if (rc == PCABO_OK && batch->fit_rounds == 0) rc = round(std::vector<const double*>((size_t)B, nullptr), nullptr);
@@ -2129,14 +2145,31 @@ int pcabo_batch_gp_fit(pcabo_batch* batch, double* theta_inout, double* loss, in
     const FitRun& r = runs[b];
     if (status) status[b] = r.status;
     if (!act[b]) continue;
-    if (r.status == PCABO_ERR_ARG) theta_domain_err(batch->ctx[b], "pcabo_batch_gp_fit", false);
+    if (r.status == PCABO_ERR_ARG) theta_domain_err(batch->ctx[b], who, ard);
     if (r.status != PCABO_OK) { worst = r.status; batch->ctx[b]->have_gp = false; continue; }
-    memcpy(theta_inout + (size_t)BATCH_FIT_NVAR * b, r.xr, (size_t)r.nvar * sizeof(double));
+    memcpy(theta_inout + (size_t)ld * b, r.xr, (size_t)r.nvar * sizeof(double));
     if (loss) loss[b] = r.fr;
     if (info) r.report(info + 4 * b);
   }
-  if (worst != PCABO_OK && !status) return bset_err(batch, worst, "pcabo_batch_gp_fit: a run of the batch failed (status array not given)%s", "");
+  if (worst != PCABO_OK && !status) return bset_err(batch, worst, "%s: a run of the batch failed (status array not given)", who);
   return PCABO_OK;
+}
+
+extern "C" {
+
+int pcabo_batch_gp_mll(pcabo_batch* batch, const double* theta, double* loss, double* grad, int* status) {
+  return batch_gp_mll_call(batch, "pcabo_batch_gp_mll", false, theta, 3, loss, grad, status);
+}
+int pcabo_batch_gp_fit(pcabo_batch* batch, double* theta_inout, double* loss, int* info, int* status) {
+  return batch_gp_fit_call(batch, "pcabo_batch_gp_fit", false, theta_inout, 3, loss, info, status);
+}
+// The ARD form (DESIGN.md "ARD lengthscales"): row b of theta = (s2, c, rho_1 .. rho_{k_b}) in ld_theta >= 2 + max_b k_b doubles;
+// what lies beyond 2 + k_b in a row is neither read nor written (grad has the same layout).
+int pcabo_batch_gp_mll_ard(pcabo_batch* batch, const double* theta, int ld_theta, double* loss, double* grad, int* status) {
+  return batch_gp_mll_call(batch, "pcabo_batch_gp_mll_ard", true, theta, ld_theta, loss, grad, status);
+}
+int pcabo_batch_gp_fit_ard(pcabo_batch* batch, double* theta_inout, int ld_theta, double* loss, int* info, int* status) {
+  return batch_gp_fit_call(batch, "pcabo_batch_gp_fit_ard", true, theta_inout, ld_theta, loss, info, status);
 }
 
 // launch sequences (rounds) the last pcabo_batch_gp_fit / pcabo_batch_gp_mll took: with the runs' evaluation counts it gives

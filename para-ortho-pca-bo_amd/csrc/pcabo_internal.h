@@ -344,6 +344,7 @@ void launch_rank(hipStream_t s, const double* f, int n, int maximize, long long*
 #define PCABO_HYP_INV_LS 0
 #define PCABO_HYP_NOISE 1
 #define PCABO_HYP_MEAN_C 2
+#define PCABO_HYP_ARD_FOLD 3              // != 0: k_zstats folds this run's ARD lengthscales (read only where ard_ls is given)
 #define PCABO_HYP_WORDS 4
 struct ZB { int B = 1; size_t zs = 0, hzs = 0; const double* hyp = nullptr; };
 void launch_wpca_prep(hipStream_t s, const double* X, const long long* ranks, const double* noise, int n, int d,
@@ -360,7 +361,9 @@ void launch_zstats(hipStream_t s, const double* Z, const double* y, int n, int k
                    double* ys, HostMirror* hm, const int* k_dev = nullptr, ZB zb = ZB(),
                    double mean_c = 0.0,    // mean_c: constant mean of a fitted GP (y_s and the statistics carry m + s c)
                    const double* ard_ls = nullptr);   // ARD fit: k lengthscales on the device, folded into the Normalize ranges
-                                                      // (norm_hi = norm_lo + (norm_hi - norm_lo) l_c; null: nothing changes)
+                                                      // (norm_hi = norm_lo + (norm_hi - norm_lo) l_c; null: nothing changes).
+                                                      // Batched: run b's lie zb.zs bytes further per run and are folded only
+                                                      // where word PCABO_HYP_ARD_FOLD of its zb.hyp block is non-zero
 void launch_znorm(hipStream_t s, const double* Z, int n, int k, int NP, int KP, int ld, const double* bounds4,
                   const double* zn_mean, double inv_ls, double* ZnT, double* AT, double* nrm,
                   const int* k_dev = nullptr, ZB zb = ZB());   // k_dev != NULL: k (and KP) are read on the device, the arguments ignored

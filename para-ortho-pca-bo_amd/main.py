@@ -43,11 +43,17 @@ def parse_arguments(argv=None):
     p.add_argument("--batched_fit_gp", action="store_true",
                    help="the same fit inside the lock-step batches (needs --batched > 1): the runs of a batch fit side by side, "
                         "one launch sequence per round, and write the rows --fit_gp writes one run after the other")
+    p.add_argument("--batched_ard", action="store_true",
+                   help="with --batched N --batched_fit_gp: one lengthscale per input inside the lock-step batches (the rows "
+                        "--fit_gp --ard writes one run after the other)")
     p.add_argument("--ucb_beta", type=float, default=None,
                    help="beta of botorch's UpperConfidenceBound(model, beta): value = -mean + sqrt(beta) * sigma when minimising.  This "
                         "flag is what makes --acquisition upper_confidence_bound runnable (not in the reference, where that choice "
                         "raises TypeError at the first BO iteration - as it still does here without the flag)")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if a.batched_ard and not (a.batched > 1 and a.batched_fit_gp):
+        p.error("--batched_ard needs --batched N (N > 1) and --batched_fit_gp")
+    return a
 
 
 def main():
@@ -60,7 +66,7 @@ def main():
         budget_factor=a.budget_factor, doe_factor=a.doe_factor, root_dir=os.getcwd(), experiment_name=a.experiment_dir,
         acquisition_function=a.acquisition, pca_components=0, var_threshold=a.var_threshold, verbose=a.verbose,
         progress=(rank == 0), batched=a.batched, side_by_side=a.side_by_side, batch_acq_kernel=a.batch_acq_kernel,
-        fit_gp=a.fit_gp, batched_fit_gp=a.batched_fit_gp, ucb_beta=a.ucb_beta, ard=a.ard)
+        fit_gp=a.fit_gp, batched_fit_gp=a.batched_fit_gp, ucb_beta=a.ucb_beta, ard=a.ard, batched_ard=a.batched_ard)
     t0 = time.time()
     experiment.run_experiment()
     dt = time.time() - t0

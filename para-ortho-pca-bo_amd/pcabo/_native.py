@@ -64,7 +64,7 @@ EXPORTS = [
     "pcabo_batch_busy", "pcabo_batch_gp_condition_end_eval_begin", "pcabo_batch_gp_condition_end_eval_end",
     "pcabo_batch_optimize_acqf_begin", "pcabo_batch_optimize_acqf_end", "pcabo_batch_inverse_map_begin", "pcabo_batch_inverse_map_end",
     "pcabo_batch_set_input_strides", "pcabo_batch_gp_condition_begin",
-    "pcabo_batch_gp_mll", "pcabo_batch_gp_fit", "pcabo_batch_gp_fit_rounds",
+    "pcabo_batch_gp_mll", "pcabo_batch_gp_fit", "pcabo_batch_gp_fit_rounds", "pcabo_batch_gp_mll_ard", "pcabo_batch_gp_fit_ard",
     "pcabo_batch_set_profiling", "pcabo_batch_get_profile", "pcabo_batch_set_active", "pcabo_batch_set_workers", "pcabo_batch_set_option",
     "pcabo_device_lbfgsb_limits",
     "pcabo_bbob_table_doubles", "pcabo_bbob_create", "pcabo_bbob_destroy", "pcabo_bbob_eval",
@@ -167,6 +167,8 @@ def _load() -> C.CDLL:
     lib.pcabo_batch_gp_mll.argtypes = [vp, vp, vp, vp, vp]
     lib.pcabo_batch_gp_fit.argtypes = [vp, vp, vp, vp, vp]
     lib.pcabo_batch_gp_fit_rounds.argtypes = [vp]
+    lib.pcabo_batch_gp_mll_ard.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    lib.pcabo_batch_gp_fit_ard.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name).restype = C.c_int
     lib.pcabo_batch_ctx.restype = vp
@@ -776,6 +778,42 @@ class Batch:
         return [{**Context._fit_result(th[b], loss[b]), "iterations": int(info[b, 0]), "evaluations": int(info[b, 1]),
                  "warnflag": int(info[b, 2]), "task": int(info[b, 3]), "status": 0} if status[b] == 0
                 else {"status": int(status[b])} for b in range(self.B)]
+
+    # ---- the same with one lengthscale per input (pcabo_batch_gp_mll_ard / pcabo_batch_gp_fit_ard) ------------------------
+    def _ard_rows(self, thetas):
+        """(B, 2 + max k) rows for the library from one theta per run (None: the model's initial values), and the runs' k."""
+        ks = [int(k) for k in self.k]
+        if min(ks) < 1:
+            raise ValueError("the runs' reduced dimensions are not known yet: collect wpca_results() first")
+        rows = np.zeros((self.B, 2 + max(ks)))
+        for b, k in enumerate(ks):
+            rows[b, : 2 + k] = Context._theta(None if thetas is None else thetas[b], k, True)
+        return rows, ks
+
+    def gp_mll_ard(self, thetas):
+        """thetas[b] (2 + k_b,) = (noise, mean constant, rho_1 .. rho_{k_b}) of run b.  One dict per run as Context.gp_mll_ard
+        returns it (`theta` and `grad` of length 2 + k_b), plus `status` (0; a parked run or one that could not be factored:
+        only `status`)."""
+        th, ks = self._ard_rows(thetas)
+        loss, grad = np.zeros(self.B), np.zeros_like(th)
+        status = np.zeros(self.B, dtype=np.int32)
+        self._chk(LIB.pcabo_batch_gp_mll_ard(self._h, _ptr(th), th.shape[1], _ptr(loss), _ptr(grad), _ptr(status)))
+        self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
+        return [{**Context._fit_result(th[b, : 2 + k], loss[b], True), "grad": grad[b, : 2 + k].copy(), "status": 0}
+                if status[b] == 0 else {"status": int(status[b])} for b, k in enumerate(ks)]
+
+    def gp_fit_ard(self, theta0=None):
+        """Batch.gp_fit with one lengthscale per input: theta0[b] (2 + k_b,) per run, or None: the model's initial values (every
+        rho_c = 0).  Bit for bit the fits Context.gp_fit_ard finds for the runs one by one; one dict per run as it returns it,
+        plus `status`.  `fit_rounds`: the launch sequences the call took."""
+        th, ks = self._ard_rows(theta0)
+        loss, info = np.zeros(self.B), np.zeros((self.B, 4), dtype=np.int32)
+        status = np.zeros(self.B, dtype=np.int32)
+        self._chk(LIB.pcabo_batch_gp_fit_ard(self._h, _ptr(th), th.shape[1], _ptr(loss), _ptr(info), _ptr(status)))
+        self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
+        return [{**Context._fit_result(th[b, : 2 + k], loss[b], True), "iterations": int(info[b, 0]),
+                 "evaluations": int(info[b, 1]), "warnflag": int(info[b, 2]), "task": int(info[b, 3]), "status": 0}
+                if status[b] == 0 else {"status": int(status[b])} for b, k in enumerate(ks)]
 
     # ---- the two waiting calls in halves (one thread advancing several batches: pcabo.batchrun.run_interleaved) -------------
     def busy(self) -> bool:

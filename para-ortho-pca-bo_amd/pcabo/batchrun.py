@@ -60,10 +60,13 @@ class BatchedPCABO:
                  maximization: bool = False, device: int = 0, num_restarts: int = 10, raw_samples: int = 512,
                  record_trace: bool = False, host_threads: int = 0, device_objective: bool = False, workers: int = 0,
                  trace_filter=None, acq_kernel: str = "group", torch_threads: Optional[int] = 4,
-                 gc_freeze: bool = True, fit_gp: bool = False, ucb_beta: Optional[float] = None, ard: bool = False):
-        if ard:                            # (the lock-step fit has one lengthscale per run: DESIGN.md "ARD lengthscales", scope)
+                 gc_freeze: bool = True, fit_gp: bool = False, ucb_beta: Optional[float] = None, ard: bool = False,
+                 batched_ard: bool = False):
+        if ard:                            # (the batches' keyword is batched_ard: DESIGN.md "ARD lengthscales", scope)
             raise ValueError("ard=True is a mode of the single-run classes Algorithms.PCA_BO / Vanilla_BO (fit_gp=True, ard=True): "
-                             "the lock-step batches fit one lengthscale")
+                             "the lock-step batches take fit_gp=True, batched_ard=True")
+        if batched_ard and not fit_gp:
+            raise ValueError("batched_ard=True fits one lengthscale per input: it needs fit_gp=True")
         self.problems, self.seeds = list(problems), [int(s) for s in seeds]
         self.B = len(self.problems)
         assert self.B == len(self.seeds) and self.B >= 1
@@ -106,7 +109,10 @@ class BatchedPCABO:
         # the runs fit (noise, mean constant, lengthscale) by the marginal likelihood TOGETHER - one launch sequence per round of
         # the fit for all runs (Batch.gp_fit) - and the acquisition works on every run's own fitted model.  A run takes, bit for
         # bit, the fits and the path the same run takes alone.  gp_hyperparameters[b]: the run's last fit (Context.gp_fit's dict).
+        # batched_ard (with fit_gp): one lengthscale per input, as PCA_BO / Vanilla_BO ard=True fit it alone (Batch.gp_fit_ard;
+        # gp_hyperparameters[b] then is Context.gp_fit_ard's dict, with "lengthscales").
         self._fit_gp = bool(fit_gp)
+        self._fit_ard = bool(batched_ard)
         self.gp_hyperparameters = [None] * self.B
         self.fit_rounds = 0                # launch sequences of all fits so far / evaluations they carried for live runs
         self.fit_evaluations = 0
@@ -234,7 +240,7 @@ class BatchedPCABO:
         """The lock-step GP fit of this iteration (a blocking call: every round of the fit waits for the device inside the
         library); parked runs do not fit.  Returns the seconds it took."""
         t = perf_counter()
-        fits = self._batch.gp_fit()
+        fits = self._batch.gp_fit_ard() if self._fit_ard else self._batch.gp_fit()
         self.fit_rounds += self._batch.fit_rounds
         for b, hp in enumerate(fits):
             if self.failed[b] is not None:
