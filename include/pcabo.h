@@ -239,6 +239,27 @@ enum { PCABO_POST_CENTRED = 2 };   /* pcabo_gp_posterior_sample only: pcabo_gp_p
 int pcabo_gp_posterior_sample(pcabo_ctx* ctx, const double* Xq, int q, int flags, const double* base, int S,
                               double* samples, double* mean /*q, may be NULL*/, double* jitter_used /*may be NULL*/);
 
+/* Leave-one-out (LOO) predictions of the conditioned GP: for every observed point what the model says about it from the other
+ * n - 1 points (Rasmussen & Williams 5.4.2).  Opt-in, not used by the BO loop (DESIGN.md "Leave-one-out predictions").
+ * With R the root inverse, alpha the solved weights, ys the standardised targets (after a fit they carry the mean constant) and
+ * (m', s) the Standardize statistics (y_mean_std of pcabo_get_gp_state), for i < n, n the context's own:
+ *   d_i    = sum_{p >= i} R[p][i]^2     (K^-1)_ii, K as factored: the noise and any jitter rung included
+ *   r_i    = alpha_i / d_i              standardised LOO residual
+ *   mean_i = m' + s (ys_i - r_i)        prediction of y_i from the other n - 1 points, objective units
+ *   var_i  = s^2 / d_i                  predictive variance of the OBSERVATION y_i (noise included); never floored: d_i >= R_ii^2 > 0
+ *   z_i    = r_i sqrt(d_i)              standardised residual (y_i - mean_i) / sqrt(var_i); N(0, 1) for a calibrated model
+ *   lpd_i  = -1/2 (log(2 pi) + log(var_i) + z_i^2)      log predictive density of y_i
+ *   lpd_sum = sum_i lpd_i, added in index order on the host from the n values brought back: one comparable score per model.
+ * The hyperparameters and the Standardize / Normalize statistics are those of the FULL data: this is the usual LOO identity, not a
+ * refit of the transforms (nor of the hyperparameters) without point i.  The constant mean of a fit, folded ARD lengthscales and
+ * jitter need no special case: they are inside R, alpha, ys and (m', s).
+ *   mean[n], var[n], z[n], lpd[n], lpd_sum[1]: all [host] in either pointer mode; each may be NULL (not all five).
+ * PCABO_ERR_ARG, nothing launched: all outputs NULL; no GP in the context (never conditioned, or the last conditioning ended
+ * PCABO_ERR_NOT_PD / not finite); between pcabo_gp_condition_begin and its _end.
+ * One launch, no workspace of its own.  Returns when the results are there.  Like pcabo_gp_posterior a call changes nothing that
+ * later calls of the context read: what follows is bit for bit what it would have been without it. */
+int pcabo_gp_loo(pcabo_ctx* ctx, double* mean /*n*/, double* var /*n*/, double* z /*n*/, double* lpd /*n*/, double* lpd_sum /*1*/);
+
 /* Rows M-N: multi-start L-BFGS-B over the acquisition (botorch gen_candidates_scipy semantics:
  * restarts are optimised jointly in groups of `batch_limit`, objective -sum_j acq(x_j), scipy
  * L-BFGS-B defaults m=10, factr=1e7 (ftol 2.22e-9), pgtol=1e-5, maxls=20, maxfun=15000).
@@ -405,6 +426,13 @@ int pcabo_batch_gp_posterior(pcabo_batch* batch, const double* Xq, int q, int fl
 int pcabo_batch_gp_posterior_sample(pcabo_batch* batch, const double* Xq /*[B][q*max_d]*/, int q, int flags,
                                     const double* base /*[B][S*q]*/, int S, double* samples /*[B][S*q]*/,
                                     double* mean /*[B][q]*/, double* jitter_used /*[B]*/, int* status /*[B]*/);
+/* pcabo_gp_loo for every run in ONE launch and one strided copy back, each run bit for bit what it takes alone.  Host pointers.
+ * mean[B][n], var[B][n], z[B][n], lpd[B][n], lpd_sum[B], each may be NULL (not all five); n is the batch's.  After
+ * pcabo_batch_gp_fit / _ard every run reads its own model.  status[B] (may be NULL): PCABO_ERR_ARG for a run parked by
+ * pcabo_batch_set_active and for a run without a GP - both are skipped, their output blocks left as they are.  PCABO_ERR_ARG with
+ * nothing launched: the refusals of pcabo_gp_loo; a conditioning that has not been waited for or a _begin call without its _end. */
+int pcabo_batch_gp_loo(pcabo_batch* batch, double* mean /*[B][n]*/, double* var, double* z, double* lpd, double* lpd_sum /*[B]*/,
+                       int* status /*[B]*/);
 /* Rows M-N for every run (pcabo_optimize_acqf semantics per run).  ics[B][num_restarts*max_d] (dense num_restarts x k_b per
  * block), bounds[B][2*max_d] as pcabo_batch_acq_bounds gives them, best_f[B]; cand[B][num_restarts*max_d] (dense per block),
  * vals[B][num_restarts], info[B][4*ngroups] or NULL, failed[B], status[B]. */

@@ -510,6 +510,14 @@ class PCA_BO(AbstractBayesianOptimizer):
         return self.__ctx.gp_posterior_samples(self.pca.transform(X - self.data_mean), None if base_samples is not None else n_samples,
                                                base_samples, seed, observation_noise, centred)
 
+    def loo(self) -> dict:
+        """Leave-one-out predictions of the current iteration's GP at its own data: {"mean", "variance", "z", "lpd"} with one entry
+        per evaluated point, in evaluation order, and "lpd_sum" (Context.gp_loo).  RuntimeError when no run is open or the
+        iteration's model is not conditioned yet.  Leaves the run's trajectory alone."""
+        if self.__ctx is None or self.pca is None or self.__gp_pending:
+            raise RuntimeError("loo: no run is open, or the model of the current iteration is not conditioned yet")
+        return self.__ctx.gp_loo()
+
     # ---- row O ------------------------------------------------------------------------------------
     def _transform_point_to_original_space(self, z: np.ndarray) -> np.ndarray:
         if self.pca is None:

@@ -191,6 +191,13 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         return self.__ctx.gp_posterior_samples(X, None if base_samples is not None else n_samples, base_samples, seed,
                                                observation_noise, centred)
 
+    def loo(self) -> dict:
+        """Leave-one-out predictions of the current iteration's GP at its own data: {"mean", "variance", "z", "lpd"} with one entry
+        per evaluated point, in evaluation order, and "lpd_sum" (Context.gp_loo).  RuntimeErrors as posterior()."""
+        if self.__ctx is None:
+            raise RuntimeError("loo: no run is open")
+        return self.__ctx.gp_loo()
+
     def __repr__(self):
         return super().__repr__()
 

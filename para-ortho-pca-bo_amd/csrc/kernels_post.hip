@@ -23,6 +23,9 @@
 //   k_post_chol_prep  cov + j s_y^2 I into the padded factor buffer (identity on the padding), the Cholesky's info word cleared
 //   launch_cholesky   the GP's own blocked factorisation, in place (kernels_gp.hip / kernels_gpw.hip), unchanged
 //   k_post_sample     out = [mean +] base Lc^T per 64 x 64 tile through tile_product_f64, the column blocks of Lc in ascending order
+//
+// Leave-one-out predictions at the data themselves (pcabo_gp_loo / pcabo_batch_gp_loo; DESIGN.md "Leave-one-out predictions") need
+// no query: k_loo reads the lower triangle of R once and runs a scalar chain per point.
 #include "pcabo_internal.h"
 #include "acq_math.h"
 
@@ -205,6 +208,55 @@ __global__ __launch_bounds__(256) void k_post_sample(const double* __restrict__ 
       if (s < S) out[(size_t)s * Q + a] = mean ? m + acc[t][r] : acc[t][r];
     }
   }
+}
+
+// ---- leave-one-out predictions (pcabo_gp_loo / pcabo_batch_gp_loo; DESIGN.md "Leave-one-out predictions") ------------------------
+// For every observed point i < n, from R = L^-1, alpha, y_s and (m', s) as the conditioning left them (include/pcabo.h):
+//   d_i = sum_{p >= i} R[p][i]^2 = (K^-1)_ii,  r_i = alpha_i / d_i,  mean_i = m' + s (ys_i - r_i),  var_i = s^2 / d_i,
+//   z_i = r_i sqrt(d_i),  lpd_i = -1/2 (log 2 pi + log var_i + z_i^2);   out = mean | var | z | lpd, n doubles each.
+// One work-group per 64-column block J, lane = column: a row segment of R is one coalesced 512-byte read.  Wave w walks the rows
+// 64 J + w, + 4, ... < n in ascending order, LOO_ROWS of them in flight per trip, and adds their squares one after the other into
+// ONE accumulator; the four waves' sums are then added in wave order through LDS and wave 0 runs the scalar chain of its 64
+// columns.  Every sum has one order that no schedule changes: the same state gives the same bits on every call.  Entries above the
+// diagonal are masked (the definition's p >= i), rows >= n (the identity padding) are never read.
+// Batched: blockIdx.z = run, every operand zs bytes further per run; n and NP are common.  No sum crosses a run.
+#define LOO_ROWS 8
+__global__ __launch_bounds__(256) void k_loo(const double* __restrict__ R, const double* __restrict__ alpha,
+                                             const double* __restrict__ ys, const double* __restrict__ ystats, int n, int ld,
+                                             double* __restrict__ out, size_t zs) {
+  ZRUN(R); ZRUN(alpha); ZRUN(ys); ZRUN(ystats); ZRUN(out);
+  __shared__ double s_d[4][64];
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int c = blockIdx.x * 64 + l;              // (c < NP <= ld: inside the row also where c >= n)
+  const double* col = R + c;
+  double d = 0.0;
+  int p = blockIdx.x * 64 + w;
+  for (; p + 4 * (LOO_ROWS - 1) < n; p += 4 * LOO_ROWS) {
+    double v[LOO_ROWS];
+#pragma unroll
+    for (int u = 0; u < LOO_ROWS; ++u) v[u] = col[(size_t)(p + 4 * u) * ld];
+#pragma unroll
+    for (int u = 0; u < LOO_ROWS; ++u) { const double x = p + 4 * u >= c ? v[u] : 0.0; d = fma(x, x, d); }
+  }
+  for (; p < n; p += 4) { const double x = p >= c ? col[(size_t)p * ld] : 0.0; d = fma(x, x, d); }
+  s_d[w][l] = d;
+  __syncthreads();
+  if (w != 0 || c >= n) return;
+  d = ((s_d[0][l] + s_d[1][l]) + s_d[2][l]) + s_d[3][l];
+  const double m = ystats[0], s = ystats[1];
+  const double r = alpha[c] / d;
+  const double var = (s * s) / d;
+  const double z = r * sqrt(d);
+  const size_t N = (size_t)n;
+  out[c] = m + s * (ys[c] - r);
+  out[N + c] = var;
+  out[2 * N + c] = z;
+  out[3 * N + c] = -0.5 * ((1.8378770664093453 + log(var)) + z * z);      // log(2 pi)
+}
+
+void launch_loo(hipStream_t st, const double* R, const double* alpha, const double* ys, const double* ystats, int n, int ld,
+                double* out, size_t zs, int B) {
+  hipLaunchKernelGGL(k_loo, dim3((n + 63) / 64, 1, B), dim3(256), 0, st, R, alpha, ys, ystats, n, ld, out, zs);
 }
 
 void launch_post_chol_prep(hipStream_t st, const double* cov, int q, const double* ystats, double jitter, double* F, int* info,

@@ -2360,13 +2360,19 @@ struct PostSite {
     if (e_ != hipSuccess) return w.fail(PCABO_ERR_HIP, "HIP error: %s (line %d)", hipGetErrorString(e_), __LINE__); \
   } while (0)
 
-// The query of `name` on its way: state checks, the V | cov blocks and the sample blocks on their first use, Xq staged, the
-// launches.  want_cov: with V and the covariance; want_samples: the sample blocks exist afterwards.
-static int post_enqueue(const PostSite& w, const char* name, const double* Xq, int q, int flags, bool want_cov, bool want_samples) {
+// The state every call on a conditioned model needs: nothing of the context or the batch in flight, and a GP to ask.
+static int post_state_check(const PostSite& w, const char* name) {
   if (w.busy)
     return w.fail(PCABO_ERR_ARG, w.batch ? "%s: a conditioning or a _begin call of this batch has not been ended"
                                          : "%s: a conditioning is in flight, call pcabo_gp_condition_end first", name);
   if (!w.have_gp) return w.fail(PCABO_ERR_ARG, w.batch ? "%s: no conditioned GP" : "%s: no conditioned GP, call pcabo_gp_condition first", name);
+  return PCABO_OK;
+}
+
+// The query of `name` on its way: state checks, the V | cov blocks and the sample blocks on their first use, Xq staged, the
+// launches.  want_cov: with V and the covariance; want_samples: the sample blocks exist afterwards.
+static int post_enqueue(const PostSite& w, const char* name, const double* Xq, int q, int flags, bool want_cov, bool want_samples) {
+  if (const int rc = post_state_check(w, name)) return rc;
   PHIPCHK(hipSetDevice(w.device));
   if (want_cov && !*w.post_slot) PHIPCHK(hipMalloc((void**)w.post_slot, w.post_bytes * (size_t)w.B));
   if (want_samples && !*w.sample_slot) PHIPCHK(hipMalloc((void**)w.sample_slot, w.L.bytes * (size_t)w.B));
@@ -2506,6 +2512,62 @@ int pcabo_batch_gp_posterior_sample(pcabo_batch* batch, const double* Xq, int q,
     if (rung[b] < 0) continue;
     if (mean) memcpy(mean + (size_t)b * q, &mv[(size_t)b * q], (size_t)q * sizeof(double));
     if (jitter_used) jitter_used[b] = kSampleRungs[rung[b]];
+  }
+  return PCABO_OK;
+}
+
+// ---- leave-one-out predictions (DESIGN.md "Leave-one-out predictions") ----------------------------------------------------------
+// One launch of k_loo for the context or for all runs of the batch: it reads R, alpha, y_s and the Standardize statistics where the
+// conditioning (or the fit) left them and writes mean | var | z | lpd, 4 n doubles per run, to the head of dPartial, which every
+// evaluation writes before it reads.  Nothing else is touched: no sequence number, no ticket, no second stream.  The results are
+// host arrays in either pointer mode; lpd_sum is added here, from the n values brought back, in index order.
+static int loo_enqueue(const PostSite& w, const char* name, bool any_out) {
+  if (!any_out) return w.fail(PCABO_ERR_ARG, "%s: mean, var, z, lpd and lpd_sum are all NULL", name);
+  if (const int rc = post_state_check(w, name)) return rc;
+  PHIPCHK(hipSetDevice(w.device));
+  launch_loo(w.s, w.m.R, w.m.alpha, w.c0->dYs, w.m.ystats, w.m.n, w.m.ld, w.c0->dPartial, w.zs, w.B);
+  return PCABO_OK;
+}
+static double loo_sum(const double* lpd, size_t n) {
+  double sum = 0.0;
+  for (size_t i = 0; i < n; ++i) sum += lpd[i];
+  return sum;
+}
+
+int pcabo_gp_loo(pcabo_ctx* ctx, double* mean, double* var, double* z, double* lpd, double* lpd_sum) {
+  if (!ctx) return PCABO_ERR_ARG;
+  const PostSite w(ctx);
+  if (const int rc = loo_enqueue(w, "pcabo_gp_loo", mean || var || z || lpd || lpd_sum)) return rc;
+  const size_t n = (size_t)w.m.n;
+  std::vector<double> own(lpd_sum && !lpd ? n : 0);      // the sum is asked for without its terms
+  double* out[4] = {mean, var, z, lpd ? lpd : lpd_sum ? own.data() : nullptr};
+  for (int v = 0; v < 4; ++v)
+    if (out[v]) PHIPCHK(hipMemcpyAsync(out[v], w.c0->dPartial + (size_t)v * n, n * sizeof(double), hipMemcpyDeviceToHost, w.s));
+  PHIPCHK(wait_stream(w.s));
+  PHIPCHK(hipGetLastError());
+  if (lpd_sum) *lpd_sum = loo_sum(out[3], n);
+  return PCABO_OK;
+}
+
+// A batch gathers the 4 n doubles of every run with one 2-D copy and hands out only the live runs' results.
+int pcabo_batch_gp_loo(pcabo_batch* batch, double* mean, double* var, double* z, double* lpd, double* lpd_sum, int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  const PostSite w(batch);
+  if (const int rc = loo_enqueue(w, "pcabo_batch_gp_loo", mean || var || z || lpd || lpd_sum)) return rc;
+  const int B = w.B;
+  const size_t n = (size_t)w.m.n;
+  std::vector<double> all((size_t)B * 4 * n);
+  PHIPCHK(hipMemcpy2DAsync(all.data(), 4 * n * sizeof(double), w.c0->dPartial, w.zs, 4 * n * sizeof(double), B, hipMemcpyDeviceToHost, w.s));
+  PHIPCHK(wait_stream(w.s));
+  PHIPCHK(hipGetLastError());
+  double* out[4] = {mean, var, z, lpd};
+  for (int b = 0; b < B; ++b) {
+    if (status) status[b] = w.live(b) ? PCABO_OK : PCABO_ERR_ARG;
+    if (!w.live(b)) continue;
+    const double* run = &all[(size_t)b * 4 * n];
+    for (int v = 0; v < 4; ++v)
+      if (out[v]) memcpy(out[v] + (size_t)b * n, run + (size_t)v * n, n * sizeof(double));
+    if (lpd_sum) lpd_sum[b] = loo_sum(run + 3 * n, n);
   }
   return PCABO_OK;
 }

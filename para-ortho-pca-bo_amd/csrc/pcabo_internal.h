@@ -432,6 +432,10 @@ void launch_post_chol_prep(hipStream_t st, const double* cov, int q, const doubl
                            size_t zs = 0, size_t vzs = 0, size_t szs = 0, int B = 1);
 void launch_post_sample(hipStream_t st, const double* F, int q, const double* base, int S, const double* mean /* or null */,
                         double* out, size_t zs = 0, size_t szs = 0, int B = 1);
+// Leave-one-out predictions of the conditioned GP (kernels_post.hip): out[4 n] = mean | var | z | lpd from R, alpha, the standardised
+// targets ys and ystats = (m', s); one launch, grid (ceil(n / 64), 1, B), the runs of a batch zs bytes apart.
+void launch_loo(hipStream_t st, const double* R, const double* alpha, const double* ys, const double* ystats, int n, int ld,
+                double* out, size_t zs = 0, int B = 1);
 void launch_score_tail(hipStream_t st, int q, const GpModel& m, AcqParams p, const double* KS, double* partial, double* val);
 // resident mode available for this shape? (fast path + every group of the grid co-resident)
 bool acq_server_possible(int q, int n, int k, int NP);

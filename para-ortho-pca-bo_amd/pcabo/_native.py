@@ -55,7 +55,7 @@ EXPORTS = [
     "pcabo_gp_condition_end", "pcabo_gp_condition_end_eval", "pcabo_wpca_gp_condition_begin", "pcabo_wpca_results",
     "pcabo_gp_mll", "pcabo_gp_fit", "pcabo_gp_mll_ard", "pcabo_gp_fit_ard",
     "pcabo_acq_bounds",
-    "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_gp_posterior_sample", "pcabo_batch_gp_posterior_sample", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
+    "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_gp_posterior_sample", "pcabo_batch_gp_posterior_sample", "pcabo_gp_loo", "pcabo_batch_gp_loo", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
     "pcabo_get_gram", "pcabo_lbfgsb_minimize", "pcabo_lbfgsb_set_vector_kernels", "pcabo_lbfgsb_set_sum_order", "pcabo_sobol_scramble", "pcabo_sobol_draw", "pcabo_sobol_draw_rows", "pcabo_torch_randint2", "pcabo_torch_multinomial_rows", "pcabo_boltzmann_pick_rows", "pcabo_set_profiling",
     "pcabo_get_profile", "pcabo_get_profile_calibration", "pcabo_reset_profile",
     "pcabo_batch_create", "pcabo_batch_destroy", "pcabo_batch_last_error", "pcabo_batch_ctx",
@@ -120,6 +120,8 @@ def _load() -> C.CDLL:
     lib.pcabo_batch_gp_posterior.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.pcabo_gp_posterior_sample.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, dp]
     lib.pcabo_batch_gp_posterior_sample.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    lib.pcabo_gp_loo.argtypes = [vp, vp, vp, vp, vp, dp]
+    lib.pcabo_batch_gp_loo.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.pcabo_optimize_acqf.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                         vp, vp, vp, ip]
     lib.pcabo_inverse_map.argtypes = [vp, vp, vp]
@@ -491,6 +493,17 @@ class Context:
                                                 C.byref(jitter)))
         return {"samples": samples, "mean": mean, "jitter": float(jitter.value)}
 
+    # ---- leave-one-out predictions (pcabo_gp_loo) -------------------------------------------------
+    def gp_loo(self) -> dict:
+        """What the conditioned GP says about each of its n points from the other n - 1: {"mean" (n,), "variance" (n,) of the
+        observation, "z" (n,) standardised residuals, "lpd" (n,) log predictive densities, "lpd_sum"}; hyperparameters and
+        transforms are those of the full data (include/pcabo.h)."""
+        n = self.n
+        mean, var, z, lpd = np.empty(n), np.empty(n), np.empty(n), np.empty(n)
+        total = C.c_double(0.0)
+        self._chk(LIB.pcabo_gp_loo(self._h, _ptr(mean), _ptr(var), _ptr(z), _ptr(lpd), C.byref(total)))
+        return {"mean": mean, "variance": var, "z": z, "lpd": lpd, "lpd_sum": float(total.value)}
+
     # ---- rows M-N -----------------------------------------------------------------------------
     def optimize_acqf(self, ics, bounds, best_f, maximize=False, acq=ACQ_LOG_EI, batch_limit=5, maxiter=200):
         """Multi-start L-BFGS-B from `ics` inside `bounds`; `best_f` as in acq_eval (ACQ_UCB: kappa).  Returns (candidates, values,
@@ -724,6 +737,17 @@ class Batch:
             if covariance:
                 out[-1]["covariance"] = cov[b].copy()
         return out
+
+    def gp_loo(self):
+        """Context.gp_loo for every run in one launch (the batch's conditioning has been waited for).  One dict per run, None for
+        a run that was skipped (parked, or without a GP)."""
+        n = self.n
+        mean, var, z, lpd = (np.zeros((self.B, n)) for _ in range(4))
+        total = np.zeros(self.B)
+        status = np.zeros(self.B, dtype=np.int32)
+        self._chk(LIB.pcabo_batch_gp_loo(self._h, _ptr(mean), _ptr(var), _ptr(z), _ptr(lpd), _ptr(total), _ptr(status)))
+        return [None if status[b] != 0 else {"mean": mean[b].copy(), "variance": var[b].copy(), "z": z[b].copy(),
+                                             "lpd": lpd[b].copy(), "lpd_sum": float(total[b])} for b in range(self.B)]
 
     def gp_posterior_samples(self, Xq_list, n_samples=None, base_samples=None, seed=None, observation_noise=False, centred=False):
         """Context.gp_posterior_samples for every run in one launch sequence (Xq_list[b]: q x k_b, the same q for all runs).
