@@ -260,6 +260,30 @@ int pcabo_gp_posterior_sample(pcabo_ctx* ctx, const double* Xq, int q, int flags
  * later calls of the context read: what follows is bit for bit what it would have been without it. */
 int pcabo_gp_loo(pcabo_ctx* ctx, double* mean /*n*/, double* var /*n*/, double* z /*n*/, double* lpd /*n*/, double* lpd_sum /*1*/);
 
+/* Append p >= 1 points to the conditioned GP, one after the other (point i + 1 sees point i), and take them back: the model of
+ * botorch's condition_on_observations / fantasize.  Opt-in, not used by the BO loop (DESIGN.md "Extending a conditioned GP").
+ * Transforms and hyperparameters are HELD, only the data grow: the Normalize bounds, the Standardize statistics (m', s), the
+ * lengthscale, the noise s2, a fit's mean constant and folded ARD ranges stay those of the last conditioning or fit; a new point may
+ * lie outside the Normalize box.  With R = L^-1 as the library keeps it, per point x (k coordinates, reduced space) with value y:
+ *   xn_c = (x_c - lo_c) / (hi_c - lo_c),  ks_j = k(xn, zn_j) for j < n,  v = R ks,  w = R^T v,
+ *   d2 = (1 + s2 + rung) - |v|^2      rung: the jitter the conditioning's factorisation ended on (0 normally)
+ *   L[n] = [v, sqrt(d2)],  R[n] = [-w, 1] / sqrt(d2),  ys_n = (y - m') / s,  n <- n + 1,  alpha = R^T (R ys) on the n + 1 points.
+ *   PCABO_EXTEND_BELIEVER: yp may be NULL (it is not read) and ys_n = sum_j alpha_j ks_j, the model's own mean at the point.
+ *   Zp[p*k] [bulk], yp[p] [bulk].  Every sum has one order: the same call on the same state gives the same bytes.
+ * All or nothing: if d2 of a point is not positive and finite the call returns PCABO_ERR_NOT_PD with the context taken back to the n
+ * it had on entry.  PCABO_ERR_ARG, nothing launched and nothing written: p < 1; n + p > max_n; Zp NULL; yp NULL without the believer
+ * flag; a coordinate or value that is not finite (host-pointer mode); unknown flag bits; no conditioned GP; between
+ * pcabo_gp_condition_begin and its _end; a member context of a batch (the lock-step batches have no such call yet).
+ * pcabo_gp_truncate takes back the points from n0 on, n_base <= n0 <= n (else PCABO_ERR_ARG), n_base the n of the last conditioning
+ * or fit: the leading block of a triangular inverse is the inverse of the leading block, so this is bookkeeping plus alpha on n0
+ * points.  After pcabo_gp_truncate(ctx, n_base) every later call returns the bytes it would have returned before the first extend.
+ * pcabo_gp_extended reads both counts.  A new conditioning, fit or likelihood evaluation starts over: it sets n_base and forgets the
+ * extension.  The search box (pcabo_acq_bounds) stays that of the conditioning throughout. */
+enum { PCABO_EXTEND_BELIEVER = 1 };
+int pcabo_gp_extend(pcabo_ctx* ctx, const double* Zp, const double* yp, int p, int flags);
+int pcabo_gp_truncate(pcabo_ctx* ctx, int n0);
+int pcabo_gp_extended(pcabo_ctx* ctx, int* n_base /*may be NULL*/, int* n /*may be NULL*/);
+
 /* Rows M-N: multi-start L-BFGS-B over the acquisition (botorch gen_candidates_scipy semantics:
  * restarts are optimised jointly in groups of `batch_limit`, objective -sum_j acq(x_j), scipy
  * L-BFGS-B defaults m=10, factr=1e7 (ftol 2.22e-9), pgtol=1e-5, maxls=20, maxfun=15000).

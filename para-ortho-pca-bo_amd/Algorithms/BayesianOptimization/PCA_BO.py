@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import os
 import warnings
+from contextlib import contextmanager
 from time import perf_counter
 from typing import Callable, Optional, Union
 
@@ -160,6 +161,11 @@ class PCA_BO(AbstractBayesianOptimizer):
         # resident=False: one launch per acquisition evaluation instead of the resident kernel of pcabo_optimize_acqf
         # (PCABO_OPT_RESIDENT; same arithmetic - the tests compare whole runs bit for bit)
         self.__resident = bool(kwargs.pop("resident", True))
+        # fantasy_points: room for that many points behind the budget in the run's context, for fantasy() (0: the context holds the
+        # budget and fantasy() fits only while n + its points <= budget)
+        self.__fantasy_points = int(kwargs.pop("fantasy_points", 0))
+        if self.__fantasy_points < 0:
+            raise ValueError("fantasy_points must be >= 0")
         # fused_enqueue=False: pcabo_wpca and pcabo_gp_condition_begin as two calls instead of ONE enqueue of rows A-H (the
         # tests compare the two); early_scoring / engine_guess likewise switch the two host/device overlaps off
         self.__fused = bool(kwargs.pop("fused_enqueue", True))
@@ -240,7 +246,7 @@ class PCA_BO(AbstractBayesianOptimizer):
         AbstractBayesianOptimizer.__call__(self, problem, dim, bounds, **kwargs)
         if self._pbar is not None:
             self._pbar.update(self.n_DoE)
-        self.__ctx = _native.Context(max_n=self.budget, max_d=self.dimension,
+        self.__ctx = _native.Context(max_n=self.budget + self.__fantasy_points, max_d=self.dimension,
                                      max_q=max(self.__torch_config["RAW_SAMPLES"], 16), device=self.__device)
         if self.__acq_kernel == "group":
             self.__ctx.set_option(_native.OPT_GROUP_ACQ, 1)
@@ -517,6 +523,24 @@ class PCA_BO(AbstractBayesianOptimizer):
         if self.__ctx is None or self.pca is None or self.__gp_pending:
             raise RuntimeError("loo: no run is open, or the model of the current iteration is not conditioned yet")
         return self.__ctx.gp_loo()
+
+    @contextmanager
+    def fantasy(self, X, y=None):
+        """Inside the `with` body the current iteration's GP also holds the points X (m x d, original space, mapped like posterior())
+        with values y (objective units; None: believer mode, every point takes the model's own mean there): transforms and
+        hyperparameters held, only the data grow (Context.gp_extend).  posterior(), posterior_samples() and loo() see that model -
+        loo() then has m more entries.  On exit the points are taken back, also when the body raises, and the run goes on bit for
+        bit as without the visit.  The context must have room for n + m points: construct the optimiser with fantasy_points=m (the library
+        refuses the call otherwise: PcaboError, a RuntimeError).  RuntimeErrors as posterior()."""
+        if self.__ctx is None or self.pca is None or self.__gp_pending:
+            raise RuntimeError("fantasy: no run is open, or the model of the current iteration is not conditioned yet")
+        X = np.asarray(X, dtype=np.float64).reshape(-1, self.dimension)
+        n0 = self.__ctx.n
+        self.__ctx.gp_extend(self.pca.transform(X - self.data_mean), y)
+        try:
+            yield self
+        finally:
+            self.__ctx.gp_truncate(n0)
 
     # ---- row O ------------------------------------------------------------------------------------
     def _transform_point_to_original_space(self, z: np.ndarray) -> np.ndarray:

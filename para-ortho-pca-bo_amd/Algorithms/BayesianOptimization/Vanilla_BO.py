@@ -12,6 +12,7 @@ box (Vanilla_BO.py:206-213) and there is no out-of-bounds rule.  It runs on the 
 from __future__ import annotations
 
 import os
+from contextlib import contextmanager
 from time import perf_counter
 from typing import Callable, Optional, Union
 
@@ -39,6 +40,9 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         self.__gc_freeze = bool(kwargs.pop("gc_freeze", True))      # see pcabo/gcguard.py
         self.__gc_entered = False
         self.__resident = bool(kwargs.pop("resident", True))         # see PCA_BO: False = one launch per evaluation
+        self.__fantasy_points = int(kwargs.pop("fantasy_points", 0))  # see PCA_BO: room behind the budget for fantasy()
+        if self.__fantasy_points < 0:
+            raise ValueError("fantasy_points must be >= 0")
         self.__fit_gp = bool(kwargs.pop("fit_gp", False))             # see PCA_BO: marginal-likelihood fit every iteration
         self.__ard = checked_ard(kwargs.pop("ard", False), self.__fit_gp)   # see PCA_BO: one lengthscale per input
         self.gp_hyperparameters = None
@@ -87,7 +91,7 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         AbstractBayesianOptimizer.__call__(self, problem, dim, bounds, **kwargs)
         if self._pbar is not None:
             self._pbar.update(self.n_DoE)
-        self.__ctx = _native.Context(max_n=self.budget, max_d=self.dimension,
+        self.__ctx = _native.Context(max_n=self.budget + self.__fantasy_points, max_d=self.dimension,
                                      max_q=max(self.__torch_config["RAW_SAMPLES"], 16), device=self.__device)
         if not self.__resident:
             self.__ctx.set_option(_native.OPT_RESIDENT, 0)
@@ -197,6 +201,23 @@ class Vanilla_BO(AbstractBayesianOptimizer):
         if self.__ctx is None:
             raise RuntimeError("loo: no run is open")
         return self.__ctx.gp_loo()
+
+    @contextmanager
+    def fantasy(self, X, y=None):
+        """Inside the `with` body the current iteration's GP also holds the points X (m x d) with values y (None: believer mode, the
+        model's own mean there), transforms and hyperparameters held (Context.gp_extend); posterior(), posterior_samples() and loo()
+        see that model.  On exit the points are taken back, also when the body raises, and the run goes on bit for bit as without
+        the visit.  The context must have room for n + m points: construct the optimiser with fantasy_points=m (the library
+        refuses the call otherwise: PcaboError, a RuntimeError).  RuntimeErrors as posterior()."""
+        if self.__ctx is None:
+            raise RuntimeError("fantasy: no run is open")
+        X = np.asarray(X, dtype=np.float64).reshape(-1, self.dimension)
+        n0 = self.__ctx.n
+        self.__ctx.gp_extend(X, y)
+        try:
+            yield self
+        finally:
+            self.__ctx.gp_truncate(n0)
 
     def __repr__(self):
         return super().__repr__()

@@ -93,6 +93,8 @@ struct pcabo_ctx {
   int ptr_mode = PCABO_PTR_HOST;
   // problem state
   int n = 0, d = 0, k = 0, NP = 0, KP = 0;
+  int n_base = 0;                        // the n of the last conditioning or fit: points n_base .. n - 1 were appended by pcabo_gp_extend
+  double rung = 0.0;                     // the jitter the factorisation ended on (0, 1e-8, 1e-7, 1e-6): part of K's diagonal as factored
   bool have_wpca = false, have_gp = false, gp_pending = false;
   int wpca_n = 0, wpca_d = 0; bool wpca_uncollected = false;   // a wPCA whose results have not been waited for yet
   double lengthscale = 0.0, noise = 0.0;
@@ -538,6 +540,14 @@ struct RowsDH {
                                          // every run's own where its zb.hyp block has PCABO_HYP_ARD_FOLD set
   hipEvent_t ev_zn = nullptr;            // recorded behind k_znorm (null: none): ZnT and the Normalize bounds are final
 };
+// The per-query tickets are consistent only with acq_slabs(NP): where NP changes outside a conditioning (pcabo_gp_extend /
+// pcabo_gp_truncate) they are reset as enqueue_rows_dh resets them.
+static int ext_tickets(pcabo_ctx* ctx, hipStream_t s, int NP, int* cnt_S) {
+  if (acq_slabs(NP) == *cnt_S) return PCABO_OK;
+  HIPCHK(hipMemsetAsync(ctx->dCounters, 0, (PCABO_CNT_DONE + 1) * sizeof(unsigned int), s));
+  *cnt_S = acq_slabs(NP);
+  return PCABO_OK;
+}
 template <class Phase>
 static int enqueue_factor(pcabo_ctx* ctx, hipStream_t s, int n, int NP, ZB zb, Phase&& phase) {
   if (const int rc = phase(2)) return rc;
@@ -603,19 +613,20 @@ static int launch_factorisation(pcabo_ctx* ctx, double jitter) {
 // the factorisation; PCABO_OK or an error), one wait, the look at chol_info.  PCABO_OK, PCABO_ERR_NOT_PD or the launch / HIP error.
 template <class Extra>
 static int factor_attempts(pcabo_ctx* ctx, int attempt, Extra&& extra) {
-  double jitter = 1e-8;
+  double jitter = 1e-8, used = 0.0;
   for (int a = 2; a <= attempt; ++a) jitter *= 10.0;
   for (;; ++attempt) {
     if (attempt > 0) {
       const int rc = launch_factorisation(ctx, jitter);
       if (rc != PCABO_OK) return rc;
+      used = jitter;
       jitter *= 10.0;
     }
     const int rc = extra();
     if (rc != PCABO_OK) return rc;
     HIPCHK(wait_stream(ctx->stream));
     HIPCHK(hipGetLastError());
-    if (ctx->hm->chol_info == 0) return PCABO_OK;
+    if (ctx->hm->chol_info == 0) { ctx->rung = used; return PCABO_OK; }      // (pcabo_gp_extend borders K as it was factored)
     if (attempt == 3)
       return set_err(ctx, PCABO_ERR_NOT_PD, "K + s2 I not positive definite after jitter retries (pivot %s%d)", "", ctx->hm->chol_info);
   }
@@ -787,7 +798,8 @@ int pcabo_wpca(pcabo_ctx* ctx, const double* X, const double* f, const int64_t* 
 // right behind the wPCA) - the three kernels that need it read it from ctx->dK.
 static int enqueue_condition(pcabo_ctx* ctx, const double* y_dev, int n, int k, const double* unb, double lengthscale,
                              double noise, int kernel, double mean_c = 0.0, const double* ard_ls = nullptr) {
-  ctx->n = n;
+  ctx->n = ctx->n_base = n;
+  ctx->rung = 0.0;
   ctx->NP = round_up(n, PCABO_BS);
   if (k >= 0) { ctx->k = k; ctx->KP = round_up(k, 4); }
   ctx->lengthscale = lengthscale; ctx->noise = noise; ctx->kernel = kernel;
@@ -1666,7 +1678,7 @@ static int batch_enqueue_condition(pcabo_batch* batch, const double* Z, const do
   batch->wpca_uncollected = k < 0; batch->gp_pending = true; batch->have_gp = false;
   batch->fitZ = Z; batch->fitY = y; batch->fitUnb = unb; batch->fitted = false;
   for (pcabo_ctx* c : batch->ctx) {      // the per-run contexts see the same state (single-context calls keep working)
-    c->n = n; c->d = d; c->NP = NP; c->lengthscale = lengthscale; c->noise = gp_noise; c->kernel = kernel;
+    c->n = c->n_base = n; c->rung = 0.0; c->d = d; c->NP = NP; c->lengthscale = lengthscale; c->noise = gp_noise; c->kernel = kernel;
     c->have_gp = false; c->have_wpca = false; c->gp_pending = false; c->wpca_uncollected = false;
     if (k >= 0) { c->k = k; c->KP = round_up(k, 4); }
     else { c->gcur = batch->gcur; c->dG = c->dGbuf[c->gcur]; c->vprev_d = d; }
@@ -2024,7 +2036,7 @@ static int batch_mll_round(pcabo_batch* batch, bool ard, const std::vector<const
     if (fold)                            // the very doubles mll_launch writes for a single context
       for (int j = 0; j < c->k; ++j) c->hArdLs[j] = softplus_host(th[2 + j]);
     c->lengthscale = ls; c->noise = c->hHyp[PCABO_HYP_NOISE]; c->kernel = batch->kernel;   // single-context calls on a member see its model
-    c->have_gp = false;
+    c->have_gp = false; c->rung = 0.0;
   }
   BHIPCHK(hipMemcpy2DAsync(c0->dHyp, batch->zs, c0->hHyp, batch->hzs, PCABO_HYP_WORDS * sizeof(double), B, hipMemcpyHostToDevice, s));
   if (ard) BHIPCHK(hipMemcpy2DAsync(c0->dArdLs, batch->zs, c0->hArdLs, batch->hzs, (size_t)kmax * sizeof(double), B, hipMemcpyHostToDevice, s));
@@ -2569,6 +2581,132 @@ int pcabo_batch_gp_loo(pcabo_batch* batch, double* mean, double* var, double* z,
       if (out[v]) memcpy(out[v] + (size_t)b * n, run + (size_t)v * n, n * sizeof(double));
     if (lpd_sum) lpd_sum[b] = loo_sum(run + 3 * n, n);
   }
+  return PCABO_OK;
+}
+
+// ---- appending points to the conditioned GP and taking them back (DESIGN.md "Extending a conditioned GP") -----------------------
+// The fantasy model of botorch's condition_on_observations: transforms and hyperparameters held, only the data grow.  Per point
+// k_ext_ks, the two matrix-vector launches of launch_alpha on the kernel vector (v = R ks, w = R^T v) and k_ext_append
+// (kernels_ext.hip); behind the last point (believer mode: behind every point, the next one reads the mean) launch_alpha on the
+// grown y_s, then ONE copy of the info word and one wait.  A pivot that fails stops the writes of everything behind it on the
+// device; the host then takes the call back with truncate's launches.  The scratch is the head of dPartial (ExtScratch); the points
+// travel through dXq, as many rows at a time as fit.  Of the state that later calls read, n, NP, L, R, ZnT, AT, nrm, y_s and alpha
+// change, the tickets are reset where NP changes and the transposed root inverse of the device-resident optimiser is marked stale;
+// the search box, the pinned staging, the sequence numbers, the second stream and chol_info are not touched.
+struct ExtHeader { double rung; int info, pad; };
+static_assert(sizeof(ExtHeader) == EXT_HDR * sizeof(double), "the header the kernels of kernels_ext.hip read");
+
+static GpModel ext_model(const PostSite& w, int n) { GpModel m = w.m; m.n = n; m.NP = round_up(n, PCABO_BS); return m; }
+
+// The header: the rung, and the info word cleared.  hdr lives until the caller has waited for the stream.
+static int ext_put_header(const PostSite& w, const ExtScratch& e, ExtHeader* hdr) {
+  *hdr = ExtHeader{w.ctx->rung, 0, 0};
+  PHIPCHK(hipMemcpyAsync(e.small + EXT_HDR_RUNG, hdr, sizeof(ExtHeader), hipMemcpyHostToDevice, w.s));
+  return PCABO_OK;
+}
+
+// The host's side of a changed n: the counts, the tickets where NP changed, the transposed root inverse marked stale.
+static int ext_set_n(const PostSite& w, int n) {
+  pcabo_ctx* ctx = w.ctx;
+  ctx->n = n; ctx->NP = round_up(n, PCABO_BS); ctx->rt_stale = true;
+  return ext_tickets(ctx, w.s, ctx->NP, &ctx->cnt_S);
+}
+
+// alpha = R^T (R y_s) on n points - the conditioning's own launches
+static void ext_alpha(const PostSite& w, int n) {
+  pcabo_ctx* c = w.ctx;
+  launch_alpha(w.s, c->dR, c->dYs, n, round_up(n, PCABO_BS), c->ld, c->dTmp, c->dAlpha);
+}
+
+// Points n0 .. are taken back (the header is on the stream already) and alpha follows; no wait.
+static int ext_take_back(const PostSite& w, const ExtScratch& e, int n0, int n_now) {
+  pcabo_ctx* c = w.ctx;
+  launch_ext_truncate(w.s, e, n0, c->k, round_up(n_now, PCABO_BS), c->ld, c->dL, c->dR, c->dZnT, c->dAT, c->dNrm, c->dYs);
+  if (const int rc = ext_set_n(w, n0)) return rc;
+  ext_alpha(w, n0);
+  return PCABO_OK;
+}
+
+static int ext_wait(const PostSite& w) {
+  PHIPCHK(wait_stream(w.s));
+  PHIPCHK(hipGetLastError());
+  return PCABO_OK;
+}
+
+int pcabo_gp_extend(pcabo_ctx* ctx, const double* Zp, const double* yp, int p, int flags) {
+  if (!ctx) return PCABO_ERR_ARG;
+  const char* name = "pcabo_gp_extend";
+  if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch", name);
+  const PostSite w(ctx);
+  if (!Zp) return w.fail(PCABO_ERR_ARG, "%s: Zp is required", name);
+  if (flags & ~PCABO_EXTEND_BELIEVER) return w.fail(PCABO_ERR_ARG, "%s: unknown flag bits", name);
+  const bool believer = (flags & PCABO_EXTEND_BELIEVER) != 0;
+  if (!yp && !believer) return w.fail(PCABO_ERR_ARG, "%s: yp is required without PCABO_EXTEND_BELIEVER", name);
+  if (believer) yp = nullptr;
+  if (p < 1) return w.fail(PCABO_ERR_ARG, "%s: p must be at least 1", name);
+  if (const int rc = post_state_check(w, name)) return rc;
+  const int n0 = ctx->n, k = ctx->k;
+  if (n0 + p > ctx->max_n) return w.fail(PCABO_ERR_ARG, "%s: n + p exceeds max_n (%d)", name, ctx->max_n);
+  if ((round_up(n0 + p, PCABO_BS) + 255) / 256 > EXT_MU_MAX) return w.fail(PCABO_ERR_ARG, "%s: n + p beyond what the kernels cover", name);
+  if (w.in == hipMemcpyHostToDevice) {                 // host pointers: every coordinate and value
+    for (size_t i = 0; i < (size_t)p * k; ++i)
+      if (!std::isfinite(Zp[i])) return w.fail(PCABO_ERR_ARG, "%s: a coordinate is not finite", name);
+    for (int i = 0; yp && i < p; ++i)
+      if (!std::isfinite(yp[i])) return w.fail(PCABO_ERR_ARG, "%s: a value is not finite", name);
+  }
+  PHIPCHK(hipSetDevice(w.device));
+  const ExtScratch e(ctx->dPartial, (size_t)ctx->NPcap);
+  ExtHeader hdr;
+  if (const int rc = ext_put_header(w, e, &hdr)) return rc;
+  const int rows_cap = (int)(((size_t)ctx->max_q * ctx->max_d + 8) / ((size_t)k + 1));      // points that fit dXq with their values
+  double* dY = yp ? ctx->dXq + (size_t)rows_cap * k : nullptr;
+  int n = n0;
+  for (int i0 = 0; i0 < p; i0 += rows_cap) {
+    const int rows = std::min(rows_cap, p - i0);
+    PHIPCHK(hipMemcpyAsync(ctx->dXq, Zp + (size_t)i0 * k, (size_t)rows * k * sizeof(double), w.in, w.s));
+    if (yp) PHIPCHK(hipMemcpyAsync(dY, yp + i0, (size_t)rows * sizeof(double), w.in, w.s));
+    for (int i = 0; i < rows; ++i, ++n) {
+      const GpModel m = ext_model(w, n);
+      launch_ext_ks(w.s, ctx->dXq, i, dY, i, m, w.p.inv_ls, w.p.kernel, e);
+      launch_alpha(w.s, ctx->dR, e.ks, m.n, m.NP, m.ld, e.v, e.w);
+      launch_ext_append(w.s, m, e, i0 + i, believer ? 1 : 0, w.noise, w.p.inv_ls, ctx->dZnMean, ctx->dL, ctx->dR, ctx->dZnT, ctx->dAT,
+                        ctx->dNrm, ctx->dYs);
+      if (believer && i0 + i + 1 < p) ext_alpha(w, n + 1);
+    }
+  }
+  if (const int rc = ext_set_n(w, n)) return rc;
+  ext_alpha(w, n);
+  int fail = 0;
+  PHIPCHK(hipMemcpyAsync(&fail, reinterpret_cast<char*>(e.small + EXT_HDR_INFO), sizeof(int), hipMemcpyDeviceToHost, w.s));
+  if (const int rc = ext_wait(w)) return rc;
+  if (fail == 0) return PCABO_OK;
+  if (const int rc = ext_put_header(w, e, &hdr)) return rc;
+  if (const int rc = ext_take_back(w, e, n0, n)) return rc;
+  if (const int rc = ext_wait(w)) return rc;
+  return w.fail(PCABO_ERR_NOT_PD, "%s: the bordered matrix is not positive definite at new point %d; the call has been taken back", name, fail - 1);
+}
+
+int pcabo_gp_truncate(pcabo_ctx* ctx, int n0) {
+  if (!ctx) return PCABO_ERR_ARG;
+  const char* name = "pcabo_gp_truncate";
+  if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch", name);
+  const PostSite w(ctx);
+  if (const int rc = post_state_check(w, name)) return rc;
+  const int n = ctx->n;
+  if (n0 < ctx->n_base || n0 > n) return w.fail(PCABO_ERR_ARG, "%s: n0 must lie in n_base .. n", name);
+  if (n0 == n) return PCABO_OK;
+  PHIPCHK(hipSetDevice(w.device));
+  const ExtScratch e(ctx->dPartial, (size_t)ctx->NPcap);
+  ExtHeader hdr;
+  if (const int rc = ext_put_header(w, e, &hdr)) return rc;
+  if (const int rc = ext_take_back(w, e, n0, n)) return rc;
+  return ext_wait(w);
+}
+
+int pcabo_gp_extended(pcabo_ctx* ctx, int* n_base, int* n) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (n_base) *n_base = ctx->n_base;
+  if (n) *n = ctx->n;
   return PCABO_OK;
 }
 #undef PHIPCHK

@@ -436,6 +436,32 @@ void launch_post_sample(hipStream_t st, const double* F, int q, const double* ba
 // targets ys and ystats = (m', s); one launch, grid (ceil(n / 64), 1, B), the runs of a batch zs bytes apart.
 void launch_loo(hipStream_t st, const double* R, const double* alpha, const double* ys, const double* ystats, int n, int ld,
                 double* out, size_t zs = 0, int B = 1);
+// Appending points to a conditioned GP and taking them back (kernels_ext.hip).  The scratch of a run lies at the head of its
+// dPartial, which every evaluation writes before it reads: ks | v | w (N = NPcap doubles each) | small.  small holds the normalised
+// point, its standardised value, the rung and the info word (the header, written by the host before the first launch with info 0;
+// the kernels set 1 + index of the point whose pivot failed) and the believer mean's partial sums, one per 256 points.
+#define EXT_XN 0
+#define EXT_YS PCABO_MAXD
+#define EXT_HDR_RUNG (PCABO_MAXD + 1)
+#define EXT_HDR_INFO (PCABO_MAXD + 2)
+#define EXT_HDR 2                          // doubles of the header: rung, info word (an int in the second double)
+#define EXT_MU (PCABO_MAXD + 3)
+#define EXT_MU_MAX 64                      // partial sums: n <= 16384
+#define EXT_SMALL (EXT_MU + EXT_MU_MAX)
+struct ExtScratch {
+  double *ks, *v, *w, *small;
+  ExtScratch(double* partial, size_t N) : ks(partial), v(partial + N), w(partial + 2 * N), small(partial + 3 * N) {}
+};
+// m: the model BEFORE the point (n, NP); X / Y: the staged points and values of the call, row xi / entry yi this one's (Y null:
+// believer mode, the value is the model's mean there).  launch_alpha(R, e.ks, n, NP, ld, e.v, e.w) goes between the two.
+void launch_ext_ks(hipStream_t st, const double* X, int xi, const double* Y, int yi, const GpModel& m, double inv_ls, int kernel,
+                   const ExtScratch& e, AcqBatch ab = AcqBatch(), int B = 1);
+void launch_ext_append(hipStream_t st, const GpModel& m, const ExtScratch& e, int idx, int believer, double s2, double inv_ls,
+                       const double* zn_mean, double* L, double* R, double* ZnT, double* AT, double* nrm, double* ys,
+                       AcqBatch ab = AcqBatch(), int B = 1);
+// NP: the padded size before the call
+void launch_ext_truncate(hipStream_t st, const ExtScratch& e, int n0, int k, int NP, int ld, double* L, double* R, double* ZnT,
+                         double* AT, double* nrm, double* ys, AcqBatch ab = AcqBatch(), int B = 1);
 void launch_score_tail(hipStream_t st, int q, const GpModel& m, AcqParams p, const double* KS, double* partial, double* val);
 // resident mode available for this shape? (fast path + every group of the grid co-resident)
 bool acq_server_possible(int q, int n, int k, int NP);

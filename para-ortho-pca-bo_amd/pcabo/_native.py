@@ -55,7 +55,8 @@ EXPORTS = [
     "pcabo_gp_condition_end", "pcabo_gp_condition_end_eval", "pcabo_wpca_gp_condition_begin", "pcabo_wpca_results",
     "pcabo_gp_mll", "pcabo_gp_fit", "pcabo_gp_mll_ard", "pcabo_gp_fit_ard",
     "pcabo_acq_bounds",
-    "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_gp_posterior_sample", "pcabo_batch_gp_posterior_sample", "pcabo_gp_loo", "pcabo_batch_gp_loo", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
+    "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_gp_posterior_sample", "pcabo_batch_gp_posterior_sample", "pcabo_gp_loo", "pcabo_batch_gp_loo",
+    "pcabo_gp_extend", "pcabo_gp_truncate", "pcabo_gp_extended", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
     "pcabo_get_gram", "pcabo_lbfgsb_minimize", "pcabo_lbfgsb_set_vector_kernels", "pcabo_lbfgsb_set_sum_order", "pcabo_sobol_scramble", "pcabo_sobol_draw", "pcabo_sobol_draw_rows", "pcabo_torch_randint2", "pcabo_torch_multinomial_rows", "pcabo_boltzmann_pick_rows", "pcabo_set_profiling",
     "pcabo_get_profile", "pcabo_get_profile_calibration", "pcabo_reset_profile",
     "pcabo_batch_create", "pcabo_batch_destroy", "pcabo_batch_last_error", "pcabo_batch_ctx",
@@ -122,6 +123,9 @@ def _load() -> C.CDLL:
     lib.pcabo_batch_gp_posterior_sample.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     lib.pcabo_gp_loo.argtypes = [vp, vp, vp, vp, vp, dp]
     lib.pcabo_batch_gp_loo.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.pcabo_gp_extend.argtypes = [vp, vp, vp, C.c_int, C.c_int]
+    lib.pcabo_gp_truncate.argtypes = [vp, C.c_int]
+    lib.pcabo_gp_extended.argtypes = [vp, ip, ip]
     lib.pcabo_optimize_acqf.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                         vp, vp, vp, ip]
     lib.pcabo_inverse_map.argtypes = [vp, vp, vp]
@@ -503,6 +507,32 @@ class Context:
         total = C.c_double(0.0)
         self._chk(LIB.pcabo_gp_loo(self._h, _ptr(mean), _ptr(var), _ptr(z), _ptr(lpd), C.byref(total)))
         return {"mean": mean, "variance": var, "z": z, "lpd": lpd, "lpd_sum": float(total.value)}
+
+    # ---- appending points and taking them back (pcabo_gp_extend / pcabo_gp_truncate) -----------------
+    def gp_extend(self, Zp, y=None) -> int:
+        """Append the points Zp (p x k, reduced space) with values y to the conditioned GP, one after the other, transforms and
+        hyperparameters held (botorch's condition_on_observations); y=None is believer mode: every point takes the model's own
+        mean there.  All or nothing (PcaboError -2 leaves the context as it was).  Returns the new n (include/pcabo.h)."""
+        Zp = _f64(Zp).reshape(-1, self.k)
+        p = Zp.shape[0]
+        yv = None if y is None else _f64(y, (p,))
+        self._chk(LIB.pcabo_gp_extend(self._h, _ptr(Zp), _ptr(yv), p, 1 if y is None else 0))      # (PCABO_EXTEND_BELIEVER)
+        self.n += p
+        return self.n
+
+    def gp_truncate(self, n0=None) -> int:
+        """Take back the appended points from n0 on (None: all of them, back to n_base).  Returns the new n."""
+        n0 = self.n_base if n0 is None else int(n0)
+        self._chk(LIB.pcabo_gp_truncate(self._h, n0))
+        self.n = n0
+        return self.n
+
+    @property
+    def n_base(self) -> int:
+        """The n of the last conditioning or fit: gp_extend appends behind it."""
+        nb, n = C.c_int(0), C.c_int(0)
+        self._chk(LIB.pcabo_gp_extended(self._h, C.byref(nb), C.byref(n)))
+        return int(nb.value)
 
     # ---- rows M-N -----------------------------------------------------------------------------
     def optimize_acqf(self, ics, bounds, best_f, maximize=False, acq=ACQ_LOG_EI, batch_limit=5, maxiter=200):
