@@ -14,6 +14,30 @@ from . import _native
 from . import initializers as _init
 
 
+ALLOWED_ACQUISITION_FUNCTION_STRINGS = (
+    "expected_improvement",
+    "probability_of_improvement",
+    "upper_confidence_bound",
+)
+ALLOWED_SHORTHAND_ACQUISITION_FUNCTION_STRINGS = {
+    "EI": "expected_improvement",
+    "PI": "probability_of_improvement",
+    "UCB": "upper_confidence_bound",
+}
+
+
+def acquisition_long_name(name: str, odd_name: str = "Oddly defined name") -> str:
+    """The long name of an acquisition given by its short or long name (reference PCA_BO.py:654-677): surrounding blanks dropped,
+    a short name replaced by its long one, anything else ValueError(odd_name), where `{name}` stands for the stripped name.  Like
+    the reference, a long name in another letter case passes as it is spelled - and then selects no acquisition class."""
+    name = name.strip()
+    if name in ALLOWED_SHORTHAND_ACQUISITION_FUNCTION_STRINGS:
+        return ALLOWED_SHORTHAND_ACQUISITION_FUNCTION_STRINGS[name]
+    if name.lower() in ALLOWED_ACQUISITION_FUNCTION_STRINGS:
+        return name
+    raise ValueError(odd_name.format(name=name))
+
+
 def ucb_kappa(beta) -> float:
     """kappa = sqrt(beta) as botorch's UpperConfidenceBound forms it: it stores `torch.as_tensor(beta)` - float32 for a Python
     float - and takes `.sqrt()` of that tensor.  The device never takes the root: kappa travels in the `best_f` slot."""

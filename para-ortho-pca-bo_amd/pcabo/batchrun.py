@@ -24,7 +24,8 @@ import torch
 from . import _native
 from .hostrng import HostMT
 from . import initializers as _init
-from .acqopt import checked_ucb_beta, ucb_kappa
+from .acqopt import acquisition_long_name, checked_ucb_beta, ucb_kappa
+from .gcguard import RunGuard
 from .lhs import lhs_center
 
 LENGTHSCALE = 0.6931471805599453     # softplus(0)
@@ -74,8 +75,7 @@ class BatchedPCABO:
         assert all(int(p.meta_data.n_variables) == self.dimension for p in self.problems), "one dimension per batch"
         self.budget, self.n_DoE = int(budget), int(n_DoE) if n_DoE else self.dimension
         self.n_components, self.var_threshold, self.maximization = int(n_components), float(var_threshold), bool(maximization)
-        name = {"EI": "expected_improvement", "PI": "probability_of_improvement",
-                "UCB": "upper_confidence_bound"}.get(acquisition_function, acquisition_function)
+        name = acquisition_long_name(acquisition_function)
         # ucb_beta (not in the reference, whose UCB cannot run; Algorithms.PCA_BO has the same keyword): what makes the upper
         # confidence bound a choice here.  Every run passes kappa = sqrt(beta) where the other acquisitions pass their best_f.
         self.ucb_beta = checked_ucb_beta(ucb_beta, acquisition_function)
@@ -136,8 +136,7 @@ class BatchedPCABO:
         # the host threads while the L-BFGS-B rounds of this iteration run inside the library: same numbers from the same
         # per-run streams - nothing else draws from them after the DoE - 1.5 ms less in front of every lock-step iteration.
         # Off while per-iteration generator states are recorded (they must be the states BEFORE the draw).
-        self._torch_threads, self._saved_torch_threads = torch_threads, None
-        self._gc_freeze, self._gc_entered = bool(gc_freeze), False
+        self._guard = RunGuard(torch_threads, gc_freeze)
         self._noise_ahead = {}
         self._noise_next = None            # (B, n + 1, d) block the pool threads fill for the next iteration
         # likewise the scrambled Sobol engines of the next iteration (torch's two randint draws per run, 0.06 ms each and
@@ -172,14 +171,9 @@ class BatchedPCABO:
         B, d = self.B, self.dimension
         # torch's intra-op pool at the machine's core count turns the loop's small tensor operations (std, exp, multinomial on 512
         # values) into a fight between spinning OpenMP workers and the batches' own threads: main.py's default experiment ran at
-        # 704 it/s instead of ~3 000 until this was capped (Algorithms.PCA_BO does the same for a single run)
-        if self._torch_threads is not None and torch.get_num_threads() > int(self._torch_threads):
-            self._saved_torch_threads = torch.get_num_threads()
-            torch.set_num_threads(int(self._torch_threads))
-        if self._gc_freeze and not self._gc_entered:       # pcabo/gcguard.py: the collector's full passes stay out of the loop
-            from . import gcguard
-            gcguard.enter()
-            self._gc_entered = True
+        # 704 it/s instead of ~3 000 until this was capped (the single-run optimisers enter the same guard, pcabo/gcguard.py, which
+        # also keeps the collector's full passes out of the loop)
+        self._guard.enter()
         self._rs = [np.random.RandomState(s) for s in self.seeds]
         # a run's torch CPU generator as the state blob torch exports, advanced by libpcabo's host helpers (pcabo/hostrng.py: same
         # numbers and consumption as torch's randint / multinomial, checked at import; a real torch.Generator otherwise)
@@ -487,13 +481,7 @@ class BatchedPCABO:
             self._assign_new_best(b, appended=True)
 
     def finish(self) -> None:
-        if getattr(self, "_saved_torch_threads", None) is not None:
-            torch.set_num_threads(self._saved_torch_threads)
-            self._saved_torch_threads = None
-        if getattr(self, "_gc_entered", False):
-            from . import gcguard
-            gcguard.leave()
-            self._gc_entered = False
+        self._guard.leave()
         if self._pool is not None:
             self._pool.shutdown()
             self._pool = None

@@ -39,3 +39,34 @@ def leave() -> None:
                     gc.set_threshold(*_saved_threshold)
                     _saved_threshold = None
                 gc.unfreeze()
+
+
+class RunGuard:
+    """What a run (a single optimiser's, a lock-step batch's) switches on around its loop and off again after it, also after a
+    start that failed half-way: torch's intra-op threads capped at `torch_threads` (None: left alone) - torch only serves the Sobol
+    / multinomial draws here, and its default of one OpenMP worker per visible core (hundreds on a GPU host) leaves spinning workers
+    that starve the host threads driving the device loop (measured: 300 us instead of 34 us per L-BFGS-B round) - and, with
+    `gc_freeze`, the collector's guard above.  leave() puts back the thread count from before the run; both calls may be repeated."""
+
+    def __init__(self, torch_threads=4, gc_freeze: bool = True):
+        self._torch_threads, self._gc_freeze = torch_threads, bool(gc_freeze)
+        self._saved_threads, self._gc_entered = None, False
+
+    def enter(self) -> None:
+        if self._torch_threads is not None and self._saved_threads is None:
+            import torch
+            if torch.get_num_threads() > int(self._torch_threads):
+                self._saved_threads = torch.get_num_threads()
+                torch.set_num_threads(int(self._torch_threads))
+        if self._gc_freeze and not self._gc_entered:
+            enter()
+            self._gc_entered = True
+
+    def leave(self) -> None:
+        if self._gc_entered:
+            leave()
+            self._gc_entered = False
+        if self._saved_threads is not None:
+            import torch
+            torch.set_num_threads(self._saved_threads)
+            self._saved_threads = None

@@ -33,7 +33,7 @@ prob = BBOBProblem(15, 0, 40)
 opt._start(prob)
 for _ in range(5):
     opt._bo_iteration(prob)
-ctx = opt._PCA_BO__ctx
+ctx = opt.device_context
 for nm in ("wpca_gp_condition", "wpca", "gp_condition", "acq_bounds", "gp_wait", "inverse_map", "optimize_acqf", "acq_eval"):
     wrap(ctx, nm, "ctx." + nm)
 wrap(_init, "scrambled_sobol_engine"); wrap(_init, "draw_sobol")
