@@ -3,9 +3,11 @@
 The seeded tables of a problem (x_opt, rotations, conditioning, Gallagher peaks) come from `pcabo.bbob` - the legacy
 generators are sequential integer recurrences and run once per run on the host - and are uploaded once; the B candidates
 of a lock-step iteration are then evaluated in ONE launch (`pcabo_bbob_eval`, csrc/kernels_bbob.hip), which also applies
-PCA_BO's out-of-box rule (reference PCA_BO.py:248-263).  Values agree with `BBOBProblem.raw` to ~1e-13 relative (other
-summation order); the host evaluation stays the default of `pcabo.batchrun` so that a batched run is bit-identical to the
-same run alone.  Per-run table layout (doubles): [x_opt(d) | R(d*d) | M(d*d) | aux(101*(2d+1) + 4d + 8)]."""
+PCA_BO's out-of-box rule (reference PCA_BO.py:248-263).  Values are those of the definitions to within the worst-case
+float64 error bound of tests/bbob_reference.py (1 unit; measured on an MI355X over d = 2 ... 128, worst per function:
+f15 0.21, f16 0.66, f17 0.87, f18 0.81, f19 0.27, f20 0.61, f21 0.81, f22 0.74, f23 0.51, f24 0.21; `BBOBProblem.raw`
+0.13 ... 0.38 - EXPERIMENTS.md section 29), in another summation order than the host's, so not bit-equal to it; the host
+evaluation stays the default of `pcabo.batchrun` so that a batched run is bit-identical to the same run alone.  Per-run table layout (doubles): [x_opt(d) | R(d*d) | M(d*d) | aux(101*(2d+1) + 4d + 8)]."""
 from __future__ import annotations
 
 import ctypes as C
@@ -42,7 +44,9 @@ def _table(p: BBOBProblem, stride: int) -> np.ndarray:
 
 
 class DeviceObjectives:
-    """`problems`: B `BBOBProblem`s of one dimension.  `evaluate(X[B, d])` -> (f[B] incl. f_opt or the penalty, oob[B])."""
+    """`problems`: B `BBOBProblem`s of one dimension.  `evaluate(X[B, d])` -> (f[B] incl. f_opt, or the penalty for a
+    candidate outside [lb, ub]^d; raw[B] without f_opt, the penalty likewise; oob[B] bool).  `lb`, `ub` and `penalty` are
+    read at every call."""
 
     def __init__(self, problems, device: int = 0, penalty: float = 1000.0):
         self.problems = list(problems)
