@@ -440,13 +440,13 @@ void test_fit_run() {
     const double th[3] = {0.02, 0.15, -0.4};
     double h[6], f = 0.0, g[3], worst = 0.0;
     CHECK(tiny_gp_sums(gp, th, h), "the dense GP could not be factored");
-    mll_assemble(h, gp.n, 1, false, th, &f, g);
+    mll_assemble(h, gp.n, 1, th, &f, g);
     for (int i = 0; i < 3; ++i) {
       const double step = i == 0 ? 1e-6 * th[0] : 1e-6;
       double tp[3] = {th[0], th[1], th[2]}, tm[3] = {th[0], th[1], th[2]}, fp = 0.0, fm = 0.0;
       tp[i] += step; tm[i] -= step;
-      CHECK(tiny_gp_sums(gp, tp, h), "factor"); mll_assemble(h, gp.n, 1, false, tp, &fp, nullptr);
-      CHECK(tiny_gp_sums(gp, tm, h), "factor"); mll_assemble(h, gp.n, 1, false, tm, &fm, nullptr);
+      CHECK(tiny_gp_sums(gp, tp, h), "factor"); mll_assemble(h, gp.n, 1, tp, &fp, nullptr);
+      CHECK(tiny_gp_sums(gp, tm, h), "factor"); mll_assemble(h, gp.n, 1, tm, &fm, nullptr);
       const double fd = (fp - fm) / (tp[i] - tm[i]), err = std::fabs(fd - g[i]) / (1.0 + std::fabs(g[i]));
       if (err > worst) worst = err;
       CHECK(err < 1e-6, "gradient %d: %.12g against the difference quotient %.12g", i, g[i], fd);
@@ -460,19 +460,29 @@ void test_fit_run() {
     const double th[nv] = {0.03, -0.1, -0.4, 0.7, 20.5};
     double h[8], f = 0.0, g[nv], worst = 0.0;
     CHECK(mll_theta_ok(th, 3) && tiny_gp_sums(gp, th, h, true), "the dense ARD GP could not be factored");
-    mll_assemble(h, gp.n, 3, true, th, &f, g);
+    mll_assemble(h, gp.n, 3, th, &f, g);
     for (int i = 0; i < nv; ++i) {
       const double step = i == 0 ? 1e-6 * th[0] : 1e-6;
       double tp[nv], tm[nv], fp = 0.0, fm = 0.0;
       std::memcpy(tp, th, sizeof(th)); std::memcpy(tm, th, sizeof(th));
       tp[i] += step; tm[i] -= step;
-      CHECK(tiny_gp_sums(gp, tp, h, true), "factor"); mll_assemble(h, gp.n, 3, true, tp, &fp, nullptr);
-      CHECK(tiny_gp_sums(gp, tm, h, true), "factor"); mll_assemble(h, gp.n, 3, true, tm, &fm, nullptr);
+      CHECK(tiny_gp_sums(gp, tp, h, true), "factor"); mll_assemble(h, gp.n, 3, tp, &fp, nullptr);
+      CHECK(tiny_gp_sums(gp, tm, h, true), "factor"); mll_assemble(h, gp.n, 3, tm, &fm, nullptr);
       const double fd = (fp - fm) / (tp[i] - tm[i]), err = std::fabs(fd - g[i]) / (1.0 + std::fabs(g[i]));
       if (err > worst) worst = err;
       CHECK(err < 1e-6, "ARD gradient %d: %.12g against the difference quotient %.12g", i, g[i], fd);
     }
     std::printf("mll_assemble (ARD) against central differences: worst %.2e (bound 1e-6)\n", worst);
+  }
+  // ... and the shared lengthscale above the threshold: the loss takes ls = rho there, so the slope is 1, not the sigmoid
+  // (1 - 1.25e-9 at 20.5, which the difference quotients above cannot tell from 1); at the threshold itself it is the sigmoid
+  CHECK(softplus_slope(20.5) == 1.0, "the slope of softplus above the threshold is not 1");
+  CHECK(softplus_slope(20.0) < 1.0 && softplus_slope(20.0) > 0.999999997, "the slope at the threshold is not the sigmoid");
+  {
+    const double th[3] = {0.05, 0.3, 20.5}, h[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 2.0};
+    double f = 0.0, g[3];
+    mll_assemble(h, 4, 1, th, &f, g);
+    CHECK(g[2] == -(0.5 * 2.0 * 1.0 / 20.5) / 4, "the shared lengthscale's gradient at rho = 20.5 is not -S / (2 rho n)");
   }
   // (a) B runs in lock-step = every run alone: theta, loss, info bit for bit; finished runs ride along at their result and are
   // not counted
@@ -516,7 +526,7 @@ void test_fit_run() {
     CHECK(evaluated, "failure %d: the result was never evaluated", e);
     if (std::memcmp(&ev[3 * (e - 2)], o.theta, sizeof(o.theta)) == 0) ++end_at_last_evaluated;
     double h[6], f = 0.0;
-    CHECK(tiny_gp_sums(gps[0], o.theta, h), "factor"); mll_assemble(h, gps[0].n, 1, false, o.theta, &f, nullptr);
+    CHECK(tiny_gp_sums(gps[0], o.theta, h), "factor"); mll_assemble(h, gps[0].n, 1, o.theta, &f, nullptr);
     CHECK(f == o.loss, "failure %d: the loss is not the one at the result", e);
   }
   CHECK(end_at_last_evaluated > 0, "no failure met the first trial of a line search");

@@ -129,7 +129,7 @@ int run_rounds(RunRestarts* runs, const std::vector<int>& order, Stage&& stage, 
 // theta = {noise s2, mean constant c, rho_1 .. rho_m}: m raw lengthscales, lengthscale = softplus(rho) as torch computes it
 // (threshold 20).  Two forms of the model: the shared lengthscale (m = 1, pcabo_gp_mll / pcabo_gp_fit and the batch) and ARD, one
 // lengthscale per input (m = k, pcabo_gp_mll_ard / pcabo_gp_fit_ard).  The scalar model is the ARD layout with one rho; the forms
-// differ in two rules, fit_rho_lower and softplus_slope, and in nothing else on the host.
+// differ in one rule, fit_rho_lower, and in nothing else on the host.
 constexpr int FIT_ARD_MAXVAR = 2 + 128;  // 2 + the largest reduced dimension (PCABO_MAXD)
 inline double softplus_host(double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); }
 inline bool lengthscale_ok(double rho) {
@@ -150,14 +150,16 @@ inline bool mll_theta_ok(const double* theta, int m) {
 // is near it.  The shared lengthscale is not bounded.
 constexpr double FIT_ARD_RHO_MIN = -27.725887222397812;
 inline double fit_rho_lower(bool ard) { return ard ? FIT_ARD_RHO_MIN : -INFINITY; }
-// Rule 2, d softplus / d rho above the threshold.  ARD takes softplus's linear branch as derivative 1, which is torch's rule; the
-// shared lengthscale computes the sigmoid throughout, about 2e-9 below 1 there.  Both are kept as they were (one of them is
-// arguably a defect): dropping `ard &&` settles it.
-inline double softplus_slope(double rho, bool ard) { return ard && rho > 20.0 ? 1.0 : 1.0 / (1.0 + std::exp(-rho)); }
+// d softplus / d rho, of the softplus the loss evaluates: above the threshold softplus_host takes the linear branch, ls = rho, so the
+// derivative there is 1 (torch's rule), the sigmoid below.  Both forms of the model share it.  (The shared lengthscale used to
+// take the sigmoid throughout, 1 - e^-rho above the threshold: a gradient 1.25e-9 short of its loss's at rho = 20.5, which the
+// extended reference of tests/mll_reference.py sees at 10^2 to 10^5 of its units on the device.)
+inline double softplus_slope(double rho) { return rho > 20.0 ? 1.0 : 1.0 / (1.0 + std::exp(-rho)); }
 // Loss and gradient of one evaluation, assembled on the host (the prior on s2 and the chain rule through softplus are host
 // arithmetic): h = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, S_1 .. S_m} of a state conditioned at theta,
-// S_c = sum_ij W_ij dK_ij/dlog l_c (m = 1: S = sum W dK/dlog l; the S_c of equal rho add up to it)
-inline void mll_assemble(const double* h, int n, int m, bool ard, const double* theta, double* loss, double* grad) {
+// S_c = sum_ij W_ij dK_ij/dlog l_c (m = 1: S = sum W dK/dlog l; the S_c of equal rho add up to it).  The same arithmetic for
+// both forms of the model: only m tells them apart here.
+inline void mll_assemble(const double* h, int n, int m, const double* theta, double* loss, double* grad) {
   const double s2 = theta[0];
   const double LOG2PI = 1.8378770664093453;
   const double lnz = std::log(s2), u = lnz + 4.0;
@@ -169,7 +171,7 @@ inline void mll_assemble(const double* h, int n, int m, bool ard, const double* 
     grad[1] = -h[2] / n;
     for (int j = 0; j < m; ++j) {
       const double rho = theta[2 + j], ls = softplus_host(rho);
-      const double sig = softplus_slope(rho, ard);
+      const double sig = softplus_slope(rho);
       grad[2 + j] = -(0.5 * h[5 + j] * sig / ls) / n;
     }
   }
@@ -207,7 +209,7 @@ struct FitRun {
     state = STEPPING; status = PCABO_OK;
   }
   bool theta_ok(const double* th) const { return mll_theta_ok(th, nvar - 2); }
-  void assemble(int n, const double* th, double* f, double* g) const { mll_assemble(h, n, nvar - 2, ard, th, f, g); }
+  void assemble(int n, const double* th, double* f, double* g) const { mll_assemble(h, n, nvar - 2, th, f, g); }
   // The theta to evaluate next, or null: the run has its result, or is out.
   const double* next() {
     if (state == STEPPING && !fit.advance()) finish();

@@ -979,7 +979,7 @@ static int gp_mll_call(pcabo_ctx* ctx, const char* who, bool ard, const double* 
   if (!mll_theta_ok(theta, m)) return theta_domain_err(ctx, who, ard);
   rc = mll_launch(ctx, ard, n, k, unb, theta);
   if (rc != PCABO_OK) return rc;
-  mll_assemble(ctx->hMll, n, m, ard, theta, loss, grad);
+  mll_assemble(ctx->hMll, n, m, theta, loss, grad);
   return PCABO_OK;
 }
 
@@ -2122,7 +2122,7 @@ static int batch_gp_mll_call(pcabo_batch* batch, const char* who, bool ard, cons
   int worst = PCABO_OK;
   for (int b = 0; b < B; ++b) {
     if (st[b] == PCABO_OK)
-      mll_assemble(batch->ctx[b]->hMll, batch->n, batch_fit_m(batch, ard, b), ard, theta + (size_t)ld * b, loss + b,
+      mll_assemble(batch->ctx[b]->hMll, batch->n, batch_fit_m(batch, ard, b), theta + (size_t)ld * b, loss + b,
                    grad ? grad + (size_t)ld * b : nullptr);
     else if (act[b]) worst = st[b];
     if (status) status[b] = st[b];

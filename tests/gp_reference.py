@@ -209,6 +209,23 @@ def hp_lower_inverse(L):
 
 
 # ---- the reference -----------------------------------------------------------------------------------------------
+def dsq_bound(A, ZN, delta, ls):
+    """`dsq` of the module docstring (n x n) and the `e` it is built from (n x k), for the norm + GEMM form of the
+    squared distance: A the centred, scaled points, ZN the normalised ones (both rounded to fp64), delta the
+    per-column scale error, ls the lengthscale.  `mll_reference` bounds the likelihood kernels' distances with it:
+    they rebuild the Gram kernel's."""
+    n, k = A.shape
+    e = EPS * (np.abs(ZN) / ls + np.abs(A))
+    P, Q = np.zeros((n, n)), np.zeros((n, n))
+    for c in range(k):
+        D = np.abs(A[:, c, None] - A[None, :, c])
+        P += D * (e[:, c, None] + e[None, :, c])
+        Q += delta[c] * D * D
+    nrm = (A * A).sum(axis=1)
+    dsq = 2.0 * P + 2.0 * Q + (k + 2) * EPS * (nrm[:, None] + nrm[None, :] + 2.0 * (np.abs(A) @ np.abs(A).T))
+    return dsq, e
+
+
 def gram_reference(case):
     """Bounds, K and y_s of a case in extended precision with `u_K`, `u_ys`, `u_nb`."""
     Z = np.asarray(case.Z, dtype=np.float64)
@@ -249,14 +266,7 @@ def gram_reference(case):
     if delta is None:                                   # a column without a range: K is NaN, there is nothing to bound
         return ref
     A, ZN, V, SQ = f64(a), f64(zn), f64(v), f64(sq)
-    e = EPS * (np.abs(ZN) / ls + np.abs(A))
-    P, Q = np.zeros((n, n)), np.zeros((n, n))
-    for c in range(k):
-        D = np.abs(A[:, c, None] - A[None, :, c])
-        P += D * (e[:, c, None] + e[None, :, c])
-        Q += delta[c] * D * D
-    nrm = (A * A).sum(axis=1)
-    dsq = 2.0 * P + 2.0 * Q + (k + 2) * EPS * (nrm[:, None] + nrm[None, :] + 2.0 * (np.abs(A) @ np.abs(A).T))
+    dsq, _ = dsq_bound(A, ZN, delta, ls)
     sq_lo = np.maximum(SQ - dsq, 0.0)
     if case.kernel == "rbf":
         u_K = 0.5 * np.exp(-0.5 * sq_lo) * dsq + EPS * np.abs(V) * (4.0 + 0.5 * SQ)

@@ -8,6 +8,9 @@ block rows (130, 9); KP padding of 1 to 3; k across 64 (70, 33), (70, 65); n < k
 Caps, those tests/test_gpu_gp_fit.py states for the scalar fit (fixed beforehand, not fitted to the device): loss 1e-9 relative to
 max(|loss|, 1e-2), every gradient component 1e-7 relative to max(|g|, 1e-3 x the sum of absolute values of its terms).
 Measured on an MI355X: see EXPERIMENTS.md "ARD lengthscales" (the first test prints the worst ratios).
+
+The gradient cap is relative to 1e-3 of a term scale; every S_c in first-order error units of a long-double reference, at the
+shapes where KP, the chunks of eight and the tiles change: tests/test_gpu_mll_edges.py (reference and units: tests/mll_reference.py).
 """
 import math
 

@@ -3,6 +3,10 @@ restatement of tests/test_gp_fit_cpu.py (torch float64 autograd + scipy's L-BFGS
 
 States: the three late states of tests/golden/late_state_d40.npz (f15, d = 40, n = 320 / 384 / 420), a d = 10 state at n = 60
 and a seeded d = 100 state at n = 1050; the reduced points come from the oracle's weighted PCA with a seeded noise draw.
+
+These are workload shapes and a float64 twin whose rounding has the size of the device's.  The likelihood kernels at edge shapes
+(n = 2 .. 257, k = 1 .. 128, rho on softplus's linear branch), judged by a long-double reference in first-order error units:
+tests/test_gpu_mll_edges.py (reference and units: tests/mll_reference.py, proved in tests/test_mll_reference_cpu.py).
 """
 import math
 import os

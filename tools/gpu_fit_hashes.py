@@ -4,7 +4,8 @@ form (Context.gp_mll_ard / gp_fit_ard), on the smallest states that reach each p
 FitRun:
   eval_n{n}_k{k}_t{i}   the nine shapes of tests/test_gpu_ard.py (one padded tile .. k = PCABO_MAXD) at its five thetas; `ard` at
                         theta i, `scalar` at (noise, mean constant) of theta i with rho = RHOS[i].  t4 is rho = 25 in both forms:
-                        softplus's linear branch, where the two forms' derivative rules differ (host_side.h)
+                        softplus's linear branch, derivative 1 in both (host_side.h; the shared form took the sigmoid there
+                        until tests/test_gpu_mll_edges.py judged it, and its t4 gradients were regenerated with that fix)
   fit_n{n}_k{k}_{start} both fits at the three FIT_STATES of tests/ard_reference.py from the default and from a seeded start; from
                         the start `out` (one lengthscale outside the domain) the error code is recorded
   batch3                the first three states of tests/test_gpu_batch_fit.py (runs of different k), run 1 parked: Batch.gp_mll at
