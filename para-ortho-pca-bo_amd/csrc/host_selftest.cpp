@@ -5,7 +5,11 @@
 // run_rounds with a stub evaluator: where the product launches an acquisition kernel and polls its flags, the workers here evaluate
 // a bounded test objective on the CPU.  The GP fit is the product's FitRun / fit_rounds over a small dense GP in plain C++ that hands
 // back the sums the likelihood kernels produce, in both forms of the model (test_fit_run: lock-step = alone, the NOT_PD / DOMAIN
-// stops, resting runs, a shared-lengthscale run and an ARD run side by side).
+// stops, resting runs, a shared-lengthscale run and an ARD run side by side).  The single run's optimise call is the product's
+// too, without its launches: the helper threads of a call (OptCrew / CrewCall: test_crew, for every number of stepping threads
+// the rule gives, two calls on the same helpers) and the free-running pair of two groups (free_pair: test_free_pair) over a
+// mailbox in plain memory that a third thread answers in the resident kernel's place - both groups to their stop, a group that
+// is never answered (the time-out is a parameter: milliseconds here), a NaN gradient.  No check uses more than eight threads.
 // Exit code 0 and "host selftest ok" = every check passed; a sanitizer report aborts the process (halt_on_error).
 #include "../../include/pcabo.h"
 #include "host_side.h"
@@ -258,6 +262,241 @@ void test_restart_group() {
   CHECK(trail0.size() == trail1.size() && std::memcmp(trail0.data(), trail1.data(), trail0.size() * sizeof(double)) == 0,
         "a group of order 0 strays from its iterates while the process-wide order is 1 (%zu / %zu coordinates)",
         trail0.size(), trail1.size());
+}
+
+// ---- the single run's optimise call (OptCrew / CrewCall, pack_active / absorb_packed, free_pair of host_side.h) -------------------
+// One call's inputs, and what a call leaves behind (the end points and values as the product takes them, the info rows)
+struct OptProblem { int k, restarts, limit; Objective o; std::vector<double> ics, bounds; };
+OptProblem opt_problem(int seed, int k, int restarts, int limit) {
+  OptProblem P{k, restarts, limit, {}, {}, {}};
+  Lcg r(seed);
+  P.o.c.resize(k);
+  for (auto& v : P.o.c) v = 2.0 * r.uni() - 1.0;
+  P.ics.resize((size_t)restarts * k); P.bounds.resize(2 * k);
+  for (auto& v : P.ics) v = 4.0 * r.uni() - 2.0;
+  for (int c = 0; c < k; ++c) { P.bounds[c] = -1.0 - 0.1 * c; P.bounds[k + c] = 1.25 + 0.05 * c; }
+  return P;
+}
+struct CallOut { std::vector<double> cand, vals; std::vector<int> info; };
+CallOut call_out(RunRestarts& run, const OptProblem& P) {
+  CallOut c{std::vector<double>((size_t)P.restarts * P.k, 0.0), std::vector<double>(P.restarts, 0.0), std::vector<int>(4 * run.grp.size(), 0)};
+  run.end_points(c.cand.data(), c.vals.data());
+  run.report(c.info.data(), 0);
+  return c;
+}
+bool same_out(const CallOut& a, const CallOut& b) {
+  return a.cand.size() == b.cand.size() && a.info == b.info && std::memcmp(a.cand.data(), b.cand.data(), a.cand.size() * sizeof(double)) == 0 &&
+         std::memcmp(a.vals.data(), b.vals.data(), a.vals.size() * sizeof(double)) == 0;
+}
+// what the acquisition kernel would do with one query: the value -f and the gradient -g at x
+void stub_query(const double* x, int k, Objective& o, double* val, double* grad) {
+  *val = -fg_objective(x, grad, &o);
+  for (int c = 0; c < k; ++c) grad[c] = -grad[c];
+}
+// The product's lock-step rounds until no group is active: advance all, pack, the stub evaluation of the packed points, absorb.
+// trails[gi]: the points group gi was evaluated at.  Returns the number of rounds.
+int lockstep_rounds(CrewCall& call, RunRestarts& run, const OptProblem& P, double* val, double* grad, std::vector<std::vector<double>>* trails) {
+  std::vector<int> qoff(run.grp.size(), -1);
+  Objective o = P.o;
+  for (int rounds = 0;; ++rounds) {
+    call.advance_all();
+    const int nq = pack_active(run, qoff);
+    if (nq == 0) return rounds;
+    int expect = 0;
+    for (size_t gi = 0; gi < run.grp.size(); ++gi) {
+      const RestartGroup& rg = run.grp[gi];
+      CHECK(qoff[gi] == (rg.active ? expect : -1), "group %zu packed at %d", gi, qoff[gi]);
+      if (!rg.active) continue;
+      CHECK(std::memcmp(run.xq + (size_t)qoff[gi] * P.k, rg.x.data(), rg.x.size() * sizeof(double)) == 0, "group %zu: packed point", gi);
+      if (trails) (*trails)[gi].insert((*trails)[gi].end(), rg.x.begin(), rg.x.end());
+      expect += rg.nq;
+    }
+    CHECK(expect == nq && nq <= P.restarts, "%d points packed, %d counted", nq, expect);
+    for (int q = 0; q < nq; ++q) stub_query(run.xq + (size_t)q * P.k, P.k, o, val + q, grad + (size_t)q * P.k);
+    CHECK(absorb_packed(run, qoff), "NaN gradient");
+  }
+}
+
+// The stepping crew: for every number of threads the rule gives, a call's groups take the steps they take alone, byte for byte,
+// whichever thread steps them; the helpers persist from call to call.
+void test_crew() {
+  OptCrew crew;
+  const int counts[7] = {1, 2, 3, 11, 12, 16, 52}, threads[7] = {1, 2, 2, 2, 2, 3, 7};
+  for (int ci = 0; ci < 7; ++ci) {
+    const int ngroups = counts[ci], limit = 2;
+    const OptProblem P = opt_problem(200 + ngroups, 4, limit * ngroups - 1, limit);       // the last group is short
+    Objective o = P.o;
+    std::vector<std::vector<double>> alone(ngroups);
+    std::vector<RestartGroup> ref(ngroups);
+    for (int gi = 0; gi < ngroups; ++gi) {
+      ref[gi].init(P.ics.data(), P.bounds.data(), gi * limit, std::min(limit, P.restarts - gi * limit), P.k, 200);
+      drive_group(ref[gi], o, &alone[gi]);
+    }
+    for (int call_no = 0; call_no < 2; ++call_no) {
+      RunRestarts run;
+      std::vector<double> xq((size_t)P.restarts * P.k), val(P.restarts), grad((size_t)P.restarts * P.k);
+      run.init(P.ics.data(), P.bounds.data(), P.restarts, limit, P.k, 200);
+      run.bind(xq.data(), val.data(), grad.data());
+      std::vector<char> pending(ngroups, 0);
+      std::vector<std::vector<double>> trails(ngroups);
+      int rounds = 0;
+      {
+        CrewCall call(crew, run, pending);
+        CHECK((int)run.grp.size() == ngroups && call.nh + 1 == threads[ci] && (ngroups == 1 || call.T == threads[ci]),
+              "%d groups: %d helpers, T = %d", ngroups, call.nh, call.T);
+        rounds = lockstep_rounds(call, run, P, val.data(), grad.data(), &trails);
+      }
+      int longest = 0;
+      for (int gi = 0; gi < ngroups; ++gi) {
+        const RestartGroup &a = run.grp[gi], &b = ref[gi];
+        CHECK(trails[gi].size() == alone[gi].size() && std::memcmp(trails[gi].data(), alone[gi].data(), alone[gi].size() * sizeof(double)) == 0,
+              "%d groups, call %d: group %d was evaluated at other points than alone", ngroups, call_no, gi);
+        CHECK(a.niter == b.niter && a.nfev == b.nfev && a.opt.warnflag() == b.opt.warnflag() && a.opt.task() == b.opt.task() && !a.active,
+              "%d groups, call %d: group %d: niter %d nfev %d, alone %d %d", ngroups, call_no, gi, a.niter, a.nfev, b.niter, b.nfev);
+        CHECK(std::memcmp(a.x.data(), b.x.data(), b.x.size() * sizeof(double)) == 0, "%d groups: end point of group %d", ngroups, gi);
+        longest = std::max(longest, (int)(alone[gi].size() / b.x.size()));
+      }
+      CHECK(rounds == longest && rounds > 2, "%d groups: %d rounds, the longest group took %d", ngroups, rounds, longest);
+    }
+  }
+  CHECK(crew.more.size() == 5, "%zu further helpers", crew.more.size());
+  crew.shutdown();
+}
+
+// The mailbox of free_pair in plain memory, and a thread in the place of the resident kernel.  ctl[q] = 2 tag + 1 (evaluate) or
+// 2 tag (leave), release-stored behind the coordinates; the device answers query q by val[q], grad[q k ..] and then the tag,
+// release-stored into pub[q].  Queries below `split` are group 0's.
+struct StubMailbox {
+  int cap, k, split;
+  std::vector<double> x, val, grad;
+  std::vector<std::atomic<unsigned long long>> ctl, pub;
+  StubMailbox(int cap_, int k_, int split_) : cap(cap_), k(k_), split(split_), x((size_t)cap_ * k_), val(cap_), grad((size_t)cap_ * k_), ctl(cap_), pub(cap_) {
+    for (int q = 0; q < cap; ++q) { ctl[q].store(0); pub[q].store(0); }
+  }
+  void post(int q0, int nq, const double* xs, unsigned long long tag) {
+    std::memcpy(&x[(size_t)q0 * k], xs, (size_t)nq * k * sizeof(double));
+    for (int j = 0; j < nq; ++j) ctl[q0 + j].store(2 * tag + 1, std::memory_order_release);
+  }
+  unsigned long long tag_of(int q) const { return pub[q].load(std::memory_order_acquire); }
+  void leave(int q0, int nq, unsigned long long tag) { for (int j = 0; j < nq; ++j) ctl[q0 + j].store(2 * tag, std::memory_order_release); }
+};
+// How the stub device misbehaves.  mute: that group is never answered.  hold: that group gets no answer before the OTHER group
+// has posted, then `free_rounds` answers (each `pace_us` late per query) and then none until the other group has left - so the
+// held group is in the middle of its run, waiting or stepping, when the other group raises the abort flag, whichever thread
+// the scheduler lets run first.  nan_q / nan_eval: that query's nan_eval-th answer carries a NaN gradient.
+struct DeviceRules { int mute = -1, hold = -1, free_rounds = 0, pace_us = 0, nan_q = -1, nan_eval = 0; };
+void stub_device(StubMailbox& mb, Objective o, DeviceRules R, std::vector<int>& evals) {
+  std::vector<unsigned long long> seen(mb.cap, 0);
+  std::vector<char> gone(mb.cap, 0);
+  std::vector<int> after(mb.cap, 0);
+  bool posted[2] = {false, false};
+  int left[2] = {0, 0};
+  const int size[2] = {mb.split, mb.cap - mb.split};
+  while (left[0] + left[1] < mb.cap) {
+    for (int q = 0; q < mb.cap; ++q) {
+      if (gone[q]) continue;
+      const unsigned long long c = mb.ctl[q].load(std::memory_order_acquire);
+      if (c == seen[q]) continue;
+      const int g = q >= mb.split ? 1 : 0;
+      if (!(c & 1)) { seen[q] = c; gone[q] = 1; ++left[g]; continue; }
+      posted[g] = true;
+      if (g == R.mute) { seen[q] = c; continue; }
+      if (g == R.hold) {                                                           // held: looked at again on the next sweep
+        if (!posted[1 - g] || (after[q] >= R.free_rounds && left[1 - g] < size[1 - g])) continue;
+        if (R.pace_us) std::this_thread::sleep_for(std::chrono::microseconds(R.pace_us));
+        ++after[q];
+      }
+      seen[q] = c;
+      stub_query(&mb.x[(size_t)q * mb.k], mb.k, o, &mb.val[q], &mb.grad[(size_t)q * mb.k]);
+      if (++evals[q] == R.nan_eval && q == R.nan_q) mb.grad[(size_t)q * mb.k] = NAN;
+      mb.pub[q].store(c >> 1, std::memory_order_release);
+    }
+    __builtin_ia32_pause();
+  }
+}
+
+// The free-running pair: 7 restarts, limit 5 - two uneven groups, as the product's smallest such call.
+void test_free_pair() {
+  const OptProblem P = opt_problem(77, 3, 7, 5);
+  const unsigned long long seq0 = 1000;
+  OptCrew crew;
+  // the pure lock-step call: what every variant below must end on
+  CallOut want;
+  int rounds_of[2] = {0, 0};
+  {
+    RunRestarts run;
+    std::vector<double> xq((size_t)P.restarts * P.k), val(P.restarts), grad((size_t)P.restarts * P.k);
+    run.init(P.ics.data(), P.bounds.data(), P.restarts, P.limit, P.k, 200);
+    run.bind(xq.data(), val.data(), grad.data());
+    std::vector<char> pending(2, 0);
+    std::vector<std::vector<double>> trails(2);
+    CrewCall call(crew, run, pending);
+    lockstep_rounds(call, run, P, val.data(), grad.data(), &trails);
+    want = call_out(run, P);
+    for (int gi = 0; gi < 2; ++gi) rounds_of[gi] = (int)(trails[gi].size() / run.grp[gi].x.size());
+    CHECK(rounds_of[0] > 10 && rounds_of[1] > 10, "too short runs to interrupt: %d and %d rounds", rounds_of[0], rounds_of[1]);
+  }
+  // One call: the first round in lock-step (as the product does before it knows that both groups are active), the pair on the
+  // stub device under `rules`, then whatever the pair left in lock-step.
+  struct PairRun { FreePair fp; char pending[2]; bool active[2]; std::vector<int> evals; CallOut out; int rounds_after; };
+  const auto pair_call = [&](DeviceRules rules, std::chrono::nanoseconds timeout) {
+    PairRun R;
+    RunRestarts run;
+    StubMailbox mb(P.restarts, P.k, P.limit);
+    std::vector<double> xq((size_t)P.restarts * P.k);
+    run.init(P.ics.data(), P.bounds.data(), P.restarts, P.limit, P.k, 200);
+    run.bind(xq.data(), mb.val.data(), mb.grad.data());
+    std::vector<char> pending(2, 0);
+    std::vector<int> qoff(2, -1);
+    R.evals.assign(P.restarts, 0);
+    CrewCall call(crew, run, pending);
+    call.advance_all();
+    CHECK(pack_active(run, qoff) == P.restarts && qoff[0] == 0 && qoff[1] == P.limit, "both groups start active");
+    std::thread device(stub_device, std::ref(mb), P.o, rules, std::ref(R.evals));
+    R.fp = free_pair(call, run, mb, seq0, timeout);
+    device.join();                                                           // (every query has been told to leave)
+    for (int gi = 0; gi < 2; ++gi) { R.pending[gi] = pending[gi]; R.active[gi] = run.grp[gi].active; }
+    R.rounds_after = 0;
+    if (!R.fp.got_nan[0] && !R.fp.got_nan[1]) {
+      R.rounds_after = lockstep_rounds(call, run, P, mb.val.data(), mb.grad.data(), nullptr);
+      R.out = call_out(run, P);
+    }
+    return R;
+  };
+  // (a) both groups run to their stop, each on its own thread
+  for (int rep = 0; rep < 2; ++rep) {
+    const PairRun R = pair_call(DeviceRules(), std::chrono::seconds(3));
+    for (int gi = 0; gi < 2; ++gi) {
+      CHECK(!R.fp.timed_out[gi] && !R.fp.got_nan[gi] && !R.pending[gi] && !R.active[gi], "group %d did not run to its stop", gi);
+      CHECK(R.fp.used[gi] == (unsigned long long)rounds_of[gi] + 1 && R.evals[gi * P.limit] == rounds_of[gi],
+            "group %d used %llu tags and was answered %d times, %d rounds in lock-step", gi, R.fp.used[gi], R.evals[gi * P.limit], rounds_of[gi]);
+    }
+    CHECK(R.rounds_after == 0 && same_out(R.out, want), "the free pair ends elsewhere than the lock-step call");
+  }
+  // (b) group 1 is never answered: it times out and raises the abort flag; group 0, held in the middle of its run, sees it;
+  // both wait for their evaluation and the lock-step rounds finish the call on the same bytes.  Which group's time-out comes
+  // first must not hang on the scheduler of a busy machine: group 0's held round starts 4 rounds x 5 queries x 2 ms = 40 ms
+  // after group 1 has posted, so it would time out 40 ms after group 1 - hence a time-out of 100 ms and not of a few.
+  {
+    DeviceRules rules;
+    rules.mute = 1; rules.hold = 0; rules.free_rounds = 4; rules.pace_us = 2000;
+    const PairRun R = pair_call(rules, std::chrono::milliseconds(100));
+    CHECK(R.fp.timed_out[1] && !R.fp.timed_out[0] && !R.fp.got_nan[0] && !R.fp.got_nan[1], "time-outs %d %d", R.fp.timed_out[0], R.fp.timed_out[1]);
+    CHECK(R.pending[0] == 1 && R.pending[1] == 1 && R.active[0] && R.active[1], "pending %d %d", R.pending[0], R.pending[1]);
+    CHECK(R.fp.used[1] == 2 && R.fp.used[0] >= 2 && R.fp.used[0] < (unsigned long long)rounds_of[0] + 1, "tags used %llu %llu", R.fp.used[0], R.fp.used[1]);
+    CHECK(R.evals[P.limit] == 0 && R.rounds_after > 0, "group 1 was answered %d times", R.evals[P.limit]);
+    CHECK(same_out(R.out, want), "a call finished in lock-step after a time-out ends elsewhere than the lock-step call");
+  }
+  // (c) a NaN gradient in group 0's second answer: that group reports it, the other stops in the middle of its run
+  {
+    DeviceRules rules;
+    rules.hold = 1; rules.free_rounds = 2; rules.nan_q = 0; rules.nan_eval = 2;
+    const PairRun R = pair_call(rules, std::chrono::seconds(3));
+    CHECK(R.fp.got_nan[0] && !R.fp.got_nan[1] && !R.fp.timed_out[0] && !R.fp.timed_out[1], "NaN flags %d %d", R.fp.got_nan[0], R.fp.got_nan[1]);
+    CHECK(R.fp.used[0] == 3 && R.pending[1] == 1 && R.active[1] && R.fp.used[1] < (unsigned long long)rounds_of[1] + 1,
+          "group 0 used %llu tags, group 1 %llu (pending %d)", R.fp.used[0], R.fp.used[1], R.pending[1]);
+  }
+  crew.shutdown();
 }
 
 // The product's round loop (run_rounds, host_side.h) over several "runs", stepped by the pool's workers: each worker drives its
@@ -710,6 +949,8 @@ int main(int argc, char** argv) {
   test_torch_rng();
   test_plan();
   test_restart_group();
+  test_crew();
+  test_free_pair();
   test_fit_run();
   test_inverse_map_host();
   test_gang_pool(1, 3);

@@ -1,18 +1,24 @@
 // Host-side pieces of the optimisers that need no HIP: the restart group (a joint problem on LbfgsbDriver, csrc/lbfgsb.h), the
-// restart groups of one run and the round loop over several runs, the GP hyperparameter fit of one run (FitRun) and the lock-step
-// rounds over several (fit_rounds), and the worker pool of a batch.  Included by pcabo_api.hip (the product) and by
-// host_selftest.cpp (the sanitizer builds of the Makefile: `make asan ubsan tsan` compile this header, lbfgsb.cpp and
-// host_entry.cpp with g++ and run them without a GPU).
+// restart groups of one run and the round loop over several runs, the single run's optimise call (its helper threads OptHelper /
+// OptCrew / CrewCall, the packing of a round pack_active / absorb_packed, and the free-running pair of two groups free_pair, a
+// template over the mailbox it posts to), the GP hyperparameter fit of one run (FitRun) and the lock-step rounds over several
+// (fit_rounds), and the worker pool of a batch.  What stays in pcabo_api.hip is what needs HIP: the launches, the mailbox in
+// device memory and the resident kernel's session.  Included by pcabo_api.hip (the product) and by host_selftest.cpp (the
+// sanitizer builds of the Makefile: `make asan ubsan tsan` compile this header, lbfgsb.cpp and host_entry.cpp with g++ and run
+// them without a GPU).
 #pragma once
 #include "../../include/pcabo.h"
 #include "lbfgsb.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cassert>
+#include <chrono>
 #include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <utility>
@@ -123,6 +129,200 @@ int run_rounds(RunRestarts* runs, const std::vector<int>& order, Stage&& stage, 
     for (auto& pe : pend)
       if (!pe.second->absorb(pe.first->val, pe.first->grad, pe.second->q0)) pe.first->status = PCABO_ERR_NAN;
   }
+}
+
+// ---- the single run's optimise call (pcabo_optimize_acqf; DESIGN.md "Multi-start optimiser") ------------------------------------
+// One helper thread for the restart groups the calling thread does not step itself.  It lives as long as its context (creating
+// and joining a thread per call cost ~0.1 ms per BO iteration), sleeps on a condition variable between calls and spin-waits on
+// `go` only while a call is active.  `go`/`done` are monotonic round counters.
+struct OptHelper {
+  std::thread th;
+  std::mutex mu;
+  std::condition_variable cv;
+  std::atomic<unsigned> go{0}, done{0};
+  std::atomic<bool> quit{false}, active{false};
+  std::function<void()> fn;          // written by the caller only while the helper is idle (done == go)
+  void run() {
+    unsigned seen = 0;
+    while (true) {
+      {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return active.load(std::memory_order_acquire) || quit.load(std::memory_order_acquire); });
+      }
+      if (quit.load(std::memory_order_acquire)) return;
+      while (active.load(std::memory_order_acquire)) {
+        const unsigned cur = go.load(std::memory_order_acquire);
+        if (cur == seen) { __builtin_ia32_pause(); continue; }
+        seen = cur;
+        fn();
+        done.store(cur, std::memory_order_release);
+      }
+    }
+  }
+  void start() { if (!th.joinable()) th = std::thread([this] { run(); }); }
+  void begin(std::function<void()> f) {
+    start();
+    fn = std::move(f);
+    { std::lock_guard<std::mutex> lk(mu); active.store(true, std::memory_order_release); }
+    cv.notify_one();
+  }
+  void end() { active.store(false, std::memory_order_release); }
+  void shutdown() {
+    if (!th.joinable()) return;
+    { std::lock_guard<std::mutex> lk(mu); quit.store(true, std::memory_order_release); active.store(false, std::memory_order_release); }
+    cv.notify_one();
+    th.join();
+  }
+  // hand the helper its next piece of work / wait until it has done it (the helper must be idle: done == go)
+  unsigned post() {
+    const unsigned ticket = go.load(std::memory_order_relaxed) + 1;
+    go.store(ticket, std::memory_order_release);
+    return ticket;
+  }
+  void wait(unsigned ticket) const { while (done.load(std::memory_order_acquire) != ticket) __builtin_ia32_pause(); }
+};
+
+// The helpers of a context: one, and up to five more once a call has many restart groups.
+struct OptCrew {
+  OptHelper helper;
+  std::vector<std::unique_ptr<OptHelper>> more;
+  void shutdown() {
+    helper.shutdown();
+    for (auto& h : more) h->shutdown();
+    more.clear();
+  }
+};
+
+// The stepping threads of ONE call.  The groups are independent between evaluations: thread t of T steps the groups t, t + T, ...
+// (the calling thread is t = 0, helper i is t = i + 1), hand-off through the helpers' round counters, spin-waiting.  Two threads
+// up to 11 groups.  With many groups (the stress configuration: 256 restarts = 52 joint problems of up to 5 x 78 variables) two
+// threads spend longer on the state machines than the device on the evaluations (90-150 us against 100-180 us per round): then
+// up to five more helpers share the groups.  One group: no helper at all.
+// pending[gi] (char, not vector<bool>: groups are touched from several threads): the free-running pair below left group gi
+// waiting for the evaluation of its point, so it is not stepped again before that evaluation.
+inline int stepping_threads(int ngroups) { return ngroups >= 12 ? std::min(7, 1 + ngroups / 8) : 2; }
+struct CrewCall {
+  std::vector<RestartGroup>& grp;
+  std::vector<char>& pending;
+  const int ngroups, T;                  // T: threads that step groups, the caller included
+  OptHelper* hs[6];                      // hs[i] steps the groups i + 1 (mod T)
+  int nh = 0;
+  CrewCall(OptCrew& crew, RunRestarts& run, std::vector<char>& pending_)
+      : grp(run.grp), pending(pending_), ngroups((int)run.grp.size()), T(stepping_threads((int)run.grp.size())) {
+    if (T > 2) while ((int)crew.more.size() < T - 2) crew.more.emplace_back(new OptHelper());
+    if (ngroups > 1) hs[nh++] = &crew.helper;
+    for (int i = 0; i < T - 2; ++i) hs[nh++] = crew.more[i].get();
+    for (int i = 0; i < nh; ++i) hs[i]->begin(share(i + 1));
+  }
+  CrewCall(const CrewCall&) = delete;
+  ~CrewCall() { for (int i = 0; i < nh; ++i) hs[i]->end(); }
+  void advance(int gi) {
+    if (pending[gi]) pending[gi] = 0;
+    else grp[gi].advance();
+  }
+  void step_share(int first) { for (int gi = first; gi < ngroups; gi += T) advance(gi); }
+  std::function<void()> share(int first) { return [this, first] { step_share(first); }; }
+  // every group advances until it needs f, g at its x (or stops)
+  void advance_all() {
+    unsigned tickets[6];
+    for (int i = 0; i < nh; ++i) tickets[i] = hs[i]->post();
+    step_share(0);
+    for (int i = 0; i < nh; ++i) hs[i]->wait(tickets[i]);
+  }
+  // f1 on the first helper beside f0 on the calling thread, once (between two advance_all: the helper is idle)
+  template <class F1, class F0> void beside(F1&& f1, F0&& f0) {
+    OptHelper& hp = *hs[0];
+    hp.fn = std::forward<F1>(f1);
+    const unsigned ticket = hp.post();
+    f0();
+    hp.wait(ticket);
+    hp.fn = share(1);
+  }
+};
+
+// The points of the active groups, contiguously and in group order, into the run's xq; qoff[gi] = the first query slot of group
+// gi there, -1: not active.  Returns the number of points.  (run_rounds keeps each group at its q0 instead: a batch's launch
+// table names the slots, a single run's launch takes the first nq.)
+inline int pack_active(RunRestarts& run, std::vector<int>& qoff) {
+  int nq = 0;
+  for (size_t gi = 0; gi < run.grp.size(); ++gi) {
+    const RestartGroup& rg = run.grp[gi];
+    qoff[gi] = -1;
+    if (!rg.active) continue;
+    qoff[gi] = nq;
+    std::memcpy(run.xq + (size_t)nq * rg.k, rg.x.data(), rg.x.size() * sizeof(double));
+    nq += rg.nq;
+  }
+  return nq;
+}
+// ... and their evaluation, from the run's val / grad at the same slots, into the groups; false: a NaN in a gradient
+inline bool absorb_packed(RunRestarts& run, const std::vector<int>& qoff) {
+  for (size_t gi = 0; gi < run.grp.size(); ++gi)
+    if (qoff[gi] >= 0 && !run.grp[gi].absorb(run.val, run.grad, qoff[gi])) return false;
+  return true;
+}
+
+// The two restart groups of a call free of each other, on an evaluator that answers each query slot by itself (the resident
+// acquisition kernel): each group has its own slots, control words and round counter, so each thread drives its own group
+// (post - wait - L-BFGS-B step) without meeting the other: a round does not wait for the slower of the two steps and there is no
+// hand-off between the threads.  Same evaluations, same order per group.  Group 1 runs on the crew's first helper, group 0 on the
+// calling thread; both groups want the evaluation of their x when it starts and sit at their q0 of the run's val / grad.
+// The mailbox:
+//   post(q0, nq, x, tag)   the nq k coordinates of the queries q0 .. and their nq "evaluate" controls, under tag
+//   tag_of(q)              the tag query q's results were published under (acquire: the results are visible behind it)
+//   leave(q0, nq, tag)     "leave for good" for the queries q0 .., under tag
+// Round r of a group (r = 1, 2, ...) carries the tag seq0 + r; a group leaves at seq0 + r + 1 (used[gi]: the tags it has taken,
+// the leave included).  An answer later than `timeout` ends both groups (checked every 4096 spins, with the other group's abort);
+// a group that stops while its point is not evaluated sets pending[gi] and the caller's lock-step rounds finish the call.
+struct FreePair {
+  bool timed_out[2] = {false, false}, got_nan[2] = {false, false};
+  bool slow_first[2] = {false, false};   // the first answer took longer than `slow`: the evaluator was not ready at once
+  unsigned long long used[2] = {0, 0};
+};
+template <class Mailbox>
+void free_group(RestartGroup& rg, int gi, Mailbox& mb, const double* val, const double* grad, unsigned long long seq0,
+                std::atomic<int>& abort_flag, char& pending, FreePair& out, std::chrono::nanoseconds timeout,
+                std::chrono::nanoseconds slow) {
+  const int q0 = rg.q0, nq = rg.nq;
+  unsigned long long r = 0;
+  for (;;) {
+    if (abort_flag.load(std::memory_order_relaxed)) { pending = 1; break; }
+    const unsigned long long tag = seq0 + (++r);
+    mb.post(q0, nq, rg.x.data(), tag);
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long spins = 0;
+    bool ok = true;
+    for (int j = 0; j < nq && ok; ++j) {
+      while (mb.tag_of(q0 + j) != tag) {
+        if ((++spins & 0xFFF) == 0) {
+          if (abort_flag.load(std::memory_order_relaxed)) { ok = false; break; }
+          if (std::chrono::steady_clock::now() - t0 > timeout) {
+            out.timed_out[gi] = true; abort_flag.store(1, std::memory_order_relaxed); ok = false; break;
+          }
+        }
+      }
+    }
+    if (!ok) { pending = 1; break; }
+    if (r == 1 && std::chrono::steady_clock::now() - t0 > slow) out.slow_first[gi] = true;
+    if (!rg.absorb(val, grad, q0)) { out.got_nan[gi] = true; abort_flag.store(1, std::memory_order_relaxed); break; }
+    if (!rg.advance()) break;
+  }
+  // this group's slots may go (the evaluator waits for round r + 1 of their own count)
+  mb.leave(q0, nq, seq0 + r + 1);
+  out.used[gi] = r + 1;
+}
+template <class Mailbox>
+FreePair free_pair(CrewCall& crew, RunRestarts& run, Mailbox& mb, unsigned long long seq0,
+                   std::chrono::nanoseconds timeout = std::chrono::seconds(3),
+                   std::chrono::nanoseconds slow = std::chrono::milliseconds(1)) {
+  assert(run.grp.size() == 2 && crew.nh >= 1);
+  FreePair out;
+  std::atomic<int> abort_flag{0};
+  const auto drive = [&](int gi) {
+    free_group(run.grp[gi], gi, mb, run.val, run.grad, seq0, abort_flag, crew.pending[gi], out, timeout, slow);
+  };
+  crew.beside([&] { drive(1); }, [&] { drive(0); });
+  return out;
 }
 
 // ---- GP hyperparameter fit (DESIGN.md "GP hyperparameter fit") ---------------------------------------------------------------

@@ -33,49 +33,6 @@
 
 struct ProfPair { hipEvent_t a, b; int group; double bytes, flops; };
 
-// One helper thread per context for the odd-numbered restart groups of pcabo_optimize_acqf.  It lives as long as the
-// context (creating and joining a thread per call cost ~0.1 ms per BO iteration), sleeps on a condition variable
-// between calls and spin-waits on `go` only while a call is active.  `go`/`done` are monotonic round counters.
-struct OptHelper {
-  std::thread th;
-  std::mutex mu;
-  std::condition_variable cv;
-  std::atomic<unsigned> go{0}, done{0};
-  std::atomic<bool> quit{false}, active{false};
-  std::function<void()> fn;          // written by the caller only while the helper is idle (done == go)
-  void run() {
-    unsigned seen = 0;
-    while (true) {
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return active.load(std::memory_order_acquire) || quit.load(std::memory_order_acquire); });
-      }
-      if (quit.load(std::memory_order_acquire)) return;
-      while (active.load(std::memory_order_acquire)) {
-        const unsigned cur = go.load(std::memory_order_acquire);
-        if (cur == seen) { __builtin_ia32_pause(); continue; }
-        seen = cur;
-        fn();
-        done.store(cur, std::memory_order_release);
-      }
-    }
-  }
-  void start() { if (!th.joinable()) th = std::thread([this] { run(); }); }
-  void begin(std::function<void()> f) {
-    start();
-    fn = std::move(f);
-    { std::lock_guard<std::mutex> lk(mu); active.store(true, std::memory_order_release); }
-    cv.notify_one();
-  }
-  void end() { active.store(false, std::memory_order_release); }
-  void shutdown() {
-    if (!th.joinable()) return;
-    { std::lock_guard<std::mutex> lk(mu); quit.store(true, std::memory_order_release); active.store(false, std::memory_order_release); }
-    cv.notify_one();
-    th.join();
-  }
-};
-
 struct pcabo_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -140,10 +97,9 @@ struct pcabo_ctx {
   bool opt_resident = true;             // PCABO_OPT_RESIDENT: may pcabo_optimize_acqf use the resident acquisition kernel
   bool opt_group_acq = false;           // PCABO_OPT_GROUP_ACQ: gradient evaluations through k_acq_group (throughput variant)
   bool bestf_f32 = true;                // PCABO_OPT_BESTF_F32: best_f rounded like torch.as_tensor(python float)
-  int srv_penalty = 0;                   // > 0: the next calls use plain launches (the GPU looked shared, see pcabo_optimize_acqf)
+  int srv_penalty = 0;                   // > 0: the next calls use plain launches (the GPU looked shared, see ResidentSession)
   unsigned long long seq = 0;
-  OptHelper helper;
-  std::vector<std::unique_ptr<OptHelper>> more_helpers;   // many restart groups (>= 12): more threads step the state machines
+  OptCrew crew;                          // the helper threads of pcabo_optimize_acqf (host_side.h)
   bool registered = false;
   bool alone = true; int alone_age = 0;   // cached answer of presence_alone(), refreshed every few calls
   char err[512] = {0};
@@ -514,9 +470,7 @@ static void ctx_teardown(pcabo_ctx* ctx) {
   if (ctx->evKS) (void)hipEventDestroy(ctx->evKS);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->stream && !ctx->in_batch) (void)hipStreamDestroy(ctx->stream);
-  ctx->helper.shutdown();
-  for (auto& h : ctx->more_helpers) h->shutdown();
-  ctx->more_helpers.clear();
+  ctx->crew.shutdown();
   if (ctx->registered) presence_unregister(ctx->device);
 }
 
@@ -1122,9 +1076,14 @@ static int score_tail(pcabo_ctx* ctx, int nq, AcqParams& p) {
 
 // The same for restart groups through the throughput kernel (PCABO_OPT_GROUP_ACQ): group g = the gn[g] <= 5 points staged
 // at query slots g0[g].. of ctx->hXq, which the kernel reads in place (pinned memory); one work-group per (group, 64-row slab).
-static int eval_staged_groups(pcabo_ctx* ctx, const int* g0, const int* gn, int ng, AcqParams& p) {
+struct GroupLaunches {                   // at most 8 groups: PCABO_INLAUNCH_MAXQ queries in fives, or the restart groups of a call
+  int g0[8], gn[8], ng = 0;
+  void add(int q0, int n) { g0[ng] = q0; gn[ng] = n; ++ng; }
+};
+static int eval_staged_groups(pcabo_ctx* ctx, const GroupLaunches& t, AcqParams& p) {
   hipStream_t s = ctx->stream;
   const unsigned long long seq = ++ctx->seq;
+  const int *g0 = t.g0, *gn = t.gn, ng = t.ng;
   QueryArgs tab;
   unsigned* ent = reinterpret_cast<unsigned*>(tab.x);
   for (int g = 0; g < ng; ++g) ent[g] = ((unsigned)g0[g] << 8) | (unsigned)gn[g];
@@ -1165,9 +1124,10 @@ int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int m
   AcqParams p = make_params(ctx, best_f, maximize, acq, grad ? 1 : 0);
   int rc;
   if (group_mode(ctx, q, grad != nullptr) && ctx->ptr_mode == PCABO_PTR_HOST) {
-    int g0[(PCABO_INLAUNCH_MAXQ + PCABO_GROUP_Q - 1) / PCABO_GROUP_Q], gn[(PCABO_INLAUNCH_MAXQ + PCABO_GROUP_Q - 1) / PCABO_GROUP_Q], ng = 0;
-    for (int a = 0; a < q; a += PCABO_GROUP_Q) { g0[ng] = a; gn[ng] = std::min(PCABO_GROUP_Q, q - a); ++ng; }
-    rc = eval_staged_groups(ctx, g0, gn, ng, p);
+    static_assert((PCABO_INLAUNCH_MAXQ + PCABO_GROUP_Q - 1) / PCABO_GROUP_Q <= 8, "GroupLaunches holds 8 groups");
+    GroupLaunches t;
+    for (int a = 0; a < q; a += PCABO_GROUP_Q) t.add(a, std::min(PCABO_GROUP_Q, q - a));
+    rc = eval_staged_groups(ctx, t, p);
   } else {
     rc = eval_staged(ctx, q, p);
   }
@@ -1238,26 +1198,103 @@ int pcabo_logei(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maxi
 }
 
 // ---- resident acquisition kernel: host side of the mailbox ---------------------------------------------------------
-// One round: all cap*k coordinate pairs get the round's tag (coordinates of queries that are no longer active are
-// whatever is left in hXq), then one control pair per query (1 = evaluate, 0 = leave for good).  A pair leaves in one 16-byte store and
-// its tag is mixed with the value's bits (mail_mix), so a reader never takes a value that does not belong to its tag.
-static void server_post(pcabo_ctx* ctx, int cap, int nq, int k, unsigned long long tag) {
-  MailPair* m = ctx->dMail;                                    // device memory, through the PCIe BAR
-  const int np = cap * k;
-  for (int i = 0; i < np; ++i) put_mail_pair(m + 1 + i, ctx->hXq[i], tag);
-  for (int q = 0; q < cap; ++q) put_mail_pair(m + 1 + np + q, q < nq ? 1.0 : 0.0, tag);     // control pairs: evaluate / leave
-  _mm_sfence();                                                // flush the write-combining buffers now
-}
-static int server_wait(pcabo_ctx* ctx, int nq, unsigned long long tag) {
-  if (wait_flags(ctx->hm, 0, nq, tag, deadline_in(3)) != FLAGS_SET)
-    return set_err(ctx, PCABO_ERR_TIMEOUT, "resident acquisition kernel did not answer%s", "");
-  return PCABO_OK;
-}
+// The mailbox of a resident kernel of `cap` queries, in device memory, written through the PCIe BAR: cap k coordinate pairs
+// behind the first pair, then one control pair per query (1 = evaluate, 0 = leave for good).  A pair leaves in one 16-byte
+// store and its tag is mixed with the value's bits (mail_mix), so a reader never takes a value that does not belong to its
+// tag.  The kernel answers query q by its results in pinned host memory and then the tag in hm->qflag[q].
+struct BarMailbox {
+  MailPair* m; const HostMirror* hm; int cap, k;
+  void coords(int q0, int nq, const double* x, unsigned long long tag) const {
+    for (int t = 0; t < nq * k; ++t) put_mail_pair(m + 1 + q0 * k + t, x[t], tag);
+  }
+  void controls(int q0, int nq, double what, unsigned long long tag) const {
+    for (int j = 0; j < nq; ++j) put_mail_pair(m + 1 + cap * k + q0 + j, what, tag);
+  }
+  void flush() const { _mm_sfence(); }   // the write-combining buffers leave now
+  // the mailbox of free_pair (host_side.h): a group's own slots
+  void post(int q0, int nq, const double* x, unsigned long long tag) const { coords(q0, nq, x, tag); controls(q0, nq, 1.0, tag); flush(); }
+  unsigned long long tag_of(int q) const { return __atomic_load_n(&hm->qflag[q], __ATOMIC_ACQUIRE); }
+  void leave(int q0, int nq, unsigned long long tag) const { controls(q0, nq, 0.0, tag); flush(); }
+  // one lock-step round: all cap k coordinate pairs get the round's tag (coordinates of queries that are no longer active are
+  // whatever is left in xq), the first nq queries are evaluated, the others leave
+  void post_round(int nq, const double* xq, unsigned long long tag) const {
+    coords(0, cap, xq, tag); controls(0, nq, 1.0, tag); controls(nq, cap - nq, 0.0, tag); flush();
+  }
+};
+
+// The resident kernel of ONE optimise call: a launch of `cap` queries that stays on the chip and takes the evaluations of the call
+// through the mailbox (see k_acq_fast): no launch and no operand refill per round.  Whatever way the call is left, the kernel is
+// told to go and waited for (stop, the destructor).
+struct ResidentSession {
+  pcabo_ctx* ctx; AcqParams& p;
+  int cap = 0;                           // > 0 while a kernel of that many queries is in flight
+  BarMailbox mail() const { return BarMailbox{ctx->dMail, ctx->hm, cap, ctx->k}; }
+  // Does this call, at its first round of nq queries, go to a resident kernel?  Only a process alone on the device, and only
+  // the one context of it: several contexts in ONE process (one run per host thread, or a batch next to a single run) would
+  // each want most of the chip at the same time - one launch per evaluation then, which interleaves well.  A call under a
+  // penalty (the GPU looked shared, see round and free_pair) pays one unit of it and takes plain launches.
+  bool wanted(unsigned round_no, int nq) {
+    if (round_no != 1) return false;
+    if ((ctx->alone_age++ & 7) == 0) ctx->alone = presence_alone(ctx->device);
+    if (ctx->srv_penalty > 0) { --ctx->srv_penalty; return false; }
+    return ctx->opt_resident && ctx->mail_bar && !ctx->opt_group_acq && ctx->alone && presence_local_contexts(ctx->device) == 1 &&
+           !ctx->prof && acq_server_possible(nq, ctx->n, ctx->k, ctx->NP);
+  }
+  int start(int nq) {
+    cap = nq;
+    launch_acq(ctx->stream, nullptr, nullptr, cap, gp_model(ctx), p, ctx->dPartial, ctx->dCounters, ctx->dVal, ctx->dGrad,
+               ctx->hVal, ctx->hGrad, ctx->hm, ctx->seq + 1, ctx->dMail, ctx->dPairs);
+    HIPCHK(hipGetLastError());
+    return PCABO_OK;
+  }
+  // One lock-step round of nq queries staged in ctx->hXq.  No answer within 3 s (e.g. this thread lost the CPU for longer than
+  // the kernel waits): plain launches from here on.  A FIRST answer after more than a millisecond (normal: ~20 us) means the
+  // grid could not become resident at once: another process holds the GPU with its own resident kernel.  Resident kernels of
+  // different processes then run one after the other, whole calls at a time; plain launches interleave much better, so use
+  // them for a while.
+  int round(int nq, bool first) {
+    const auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const unsigned long long tag = ++ctx->seq;
+    const double tp = now();
+    mail().post_round(nq, ctx->hXq, tag);
+    if (wait_flags(ctx->hm, 0, nq, tag, deadline_in(3)) != FLAGS_SET) {
+      (void)set_err(ctx, PCABO_ERR_TIMEOUT, "resident acquisition kernel did not answer%s", "");   // (the tickets may be dirty)
+      stop();
+      ctx->srv_penalty = 1000;
+      return eval_staged(ctx, nq, p);
+    }
+    if (first && now() - tp > 1e-3) ctx->srv_penalty = 40;
+    return PCABO_OK;
+  }
+  // The call's two groups free of each other (free_pair, host_side.h) until both have left the kernel, which ends with them.
+  // A group that was not answered leaves the call to plain launches, and the next calls too.
+  int pair(CrewCall& crew, RunRestarts& run) {
+    const unsigned long long seq0 = ctx->seq;
+    BarMailbox mb = mail();
+    const FreePair fp = free_pair(crew, run, mb, seq0);
+    HIPCHK(hipStreamSynchronize(ctx->stream));        // every group of the grid has been told to leave
+    ctx->seq = seq0 + std::max(fp.used[0], fp.used[1]) + 1;
+    cap = 0;
+    if (fp.got_nan[0] || fp.got_nan[1]) return set_err(ctx, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
+    if (fp.timed_out[0] || fp.timed_out[1]) ctx->srv_penalty = 1000;
+    else if (fp.slow_first[0] || fp.slow_first[1]) ctx->srv_penalty = 40;
+    return PCABO_OK;
+  }
+  void stop() {
+    if (cap <= 0) return;
+    mail().post_round(0, ctx->hXq, ++ctx->seq);
+    (void)hipStreamSynchronize(ctx->stream);
+    cap = 0;
+  }
+  ~ResidentSession() { stop(); }
+};
 
 // ---- multi-start L-BFGS-B over the device acquisition ------------------------------------------
-// All restart groups advance in lock-step: per round every still-active group asks for one joint
-// value+gradient evaluation; the points of all groups go to the device in ONE launch whose results
-// land in pinned host memory (eval_staged above).
+// All restart groups advance in lock-step: per round every still-active group asks for one joint value+gradient evaluation
+// (CrewCall, host_side.h: the groups are stepped by up to seven threads); the points of all groups go to the device together
+// (pack_active) and the results land in pinned host memory.  A round is evaluated by the call's resident kernel when it has one
+// (two groups: free of each other from there on, free_pair), else by one launch: of k_acq_group per restart group
+// (PCABO_OPT_GROUP_ACQ) or of the per-query kernels (eval_staged above).
 int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int batch_limit, const double* bounds,
                         int maxiter, double best_f, int maximize, int acq, double* cand, double* vals, int* info,
                         int* failed) {
@@ -1270,167 +1307,40 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
   const int k = ctx->k;
   RunRestarts run;
   run.init(ics, bounds, num_restarts, batch_limit, k, maxiter);
+  run.bind(ctx->hXq, ctx->hVal, ctx->hGrad);
   std::vector<RestartGroup>& grp = run.grp;
   const int ngroups = (int)grp.size();
   AcqParams p = make_params(ctx, best_f, maximize, acq, 1);
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  // advance one group until it needs f, g at its x (or stops); a group the free-running mode below left waiting for its
-  // evaluation (pending: char, not vector<bool> - groups are touched from two threads) is not stepped again
   std::vector<char> pending(ngroups, 0);
-  auto advance = [&](int gi) {
-    if (pending[gi]) pending[gi] = 0;
-    else grp[gi].advance();
-  };
-  // The groups are independent between evaluations: odd-numbered groups advance on the context's helper thread
-  // while the calling thread advances the even ones (hand-off through two monotonic round counters, spin-waiting).
-  OptHelper& hp = ctx->helper;
-  // With many groups (the stress configuration: 256 restarts = 52 joint problems of up to 5 x 78 variables) two threads
-  // spend longer on the state machines than the device on the evaluations (90-150 us against 100-180 us per round): then up
-  // to five more helpers share the groups (stride T over the group index; the calling thread takes every T-th).
-  const int T = ngroups >= 12 ? std::min(7, 1 + ngroups / 8) : 2;          // threads that step groups, the caller included
-  if (T > 2) while ((int)ctx->more_helpers.size() < T - 2) ctx->more_helpers.emplace_back(new OptHelper());
-  std::vector<OptHelper*> hs;                                               // hs[i] steps the groups gi = i + 1 (mod T)
-  if (ngroups > 1) hs.push_back(&hp);
-  for (int i = 0; i < T - 2; ++i) hs.push_back(ctx->more_helpers[i].get());
-  for (size_t i = 0; i < hs.size(); ++i) {
-    const int first = (int)i + 1;
-    hs[i]->begin([&, first] { for (int gi = first; gi < ngroups; gi += T) advance(gi); });
-  }
-  struct Ender { std::vector<OptHelper*>& h; ~Ender() { for (OptHelper* x : h) x->end(); } } ender{hs};
-  unsigned round_no = 0;
   std::vector<int> qoff(ngroups, -1);
-  int srv_cap = 0;                       // > 0 while a resident kernel of that many queries is in flight
-  struct ServerStop {                    // whatever way the loop is left: tell the kernel to go, wait until it has gone
-    pcabo_ctx* c; int& cap; int k;
-    void stop() {
-      if (cap <= 0) return;
-      server_post(c, cap, 0, k, ++c->seq);
-      (void)hipStreamSynchronize(c->stream);
-      cap = 0;
-    }
-    ~ServerStop() { stop(); }
-  } server_stop{ctx, srv_cap, k};
-  while (true) {
-    ++round_no;
-    unsigned tickets[8] = {0};
-    for (size_t i = 0; i < hs.size(); ++i) {
-      tickets[i] = hs[i]->go.load(std::memory_order_relaxed) + 1;
-      hs[i]->go.store(tickets[i], std::memory_order_release);
-    }
-    for (int gi = 0; gi < ngroups; gi += T) advance(gi);
-    for (size_t i = 0; i < hs.size(); ++i)
-      while (hs[i]->done.load(std::memory_order_acquire) != tickets[i]) __builtin_ia32_pause();
-    int nq = 0;
-    for (int gi = 0; gi < ngroups; ++gi) {
-      qoff[gi] = -1;
-      if (!grp[gi].active) continue;
-      qoff[gi] = nq;
-      memcpy(ctx->hXq + (size_t)nq * k, grp[gi].x.data(), grp[gi].x.size() * sizeof(double));
-      nq += grp[gi].nq;
-    }
+  CrewCall crew(ctx->crew, run, pending);
+  ResidentSession srv{ctx, p};
+  for (unsigned round_no = 1;; ++round_no) {
+    crew.advance_all();
+    const int nq = pack_active(run, qoff);
     if (nq == 0) break;
     int rc;
-    if (round_no == 1 && (ctx->alone_age++ & 7) == 0) ctx->alone = presence_alone(ctx->device);
-    // several contexts in ONE process (one run per host thread, or a batch next to a single run): their resident kernels
-    // would each want most of the chip at the same time - one launch per evaluation then, which interleaves well
-    const bool only_context_here = presence_local_contexts(ctx->device) == 1;
-    if (round_no == 1 && ctx->srv_penalty > 0) --ctx->srv_penalty;
-    else if (round_no == 1 && ctx->opt_resident && ctx->mail_bar && !ctx->opt_group_acq && ctx->alone && only_context_here && !ctx->prof && acq_server_possible(nq, ctx->n, k, ctx->NP)) {
-      // the evaluations of this call go to ONE resident launch (see k_acq_fast): no launch and no operand refill per round
-      srv_cap = nq;
-      launch_acq(ctx->stream, nullptr, nullptr, srv_cap, gp_model(ctx), p, ctx->dPartial, ctx->dCounters, ctx->dVal, ctx->dGrad,
-                 ctx->hVal, ctx->hGrad, ctx->hm, ctx->seq + 1, ctx->dMail, ctx->dPairs);
-      HIPCHK(hipGetLastError());
+    if (srv.wanted(round_no, nq)) {
+      if ((rc = srv.start(nq)) != PCABO_OK) return rc;
       if (ngroups == 2 && grp[0].active && grp[1].active && nq == num_restarts) {
-        // ---- the two restart groups free of each other ------------------------------------------------------------
-        // Each group has its own slots, control pairs and round counter in the mailbox, so each host thread drives its
-        // own group (post - wait - L-BFGS-B step) without meeting the other: a round no longer waits for the slower of
-        // the two steps and there is no hand-off between the threads.  Same evaluations, same order per group.
-        const unsigned long long seq0 = ctx->seq;
-        MailPair* m = ctx->dMail;
-        const int cap = srv_cap;
-        std::atomic<int> abort_flag{0};
-        int timed_out[2] = {0, 0}, got_nan[2] = {0, 0}, left[2] = {0, 0}, slow_first[2] = {0, 0};
-        unsigned long long used[2] = {0, 0};
-        auto free_loop = [&](int gi) {
-          RestartGroup& rg = grp[gi];
-          const int q0 = rg.q0, nqg = rg.nq;
-          unsigned long long r = 0;
-          for (;;) {
-            if (abort_flag.load(std::memory_order_relaxed)) { pending[gi] = 1; break; }
-            const unsigned long long tag = seq0 + (++r);
-            for (int t = 0; t < nqg * k; ++t) put_mail_pair(m + 1 + q0 * k + t, rg.x[t], tag);
-            for (int j = 0; j < nqg; ++j) put_mail_pair(m + 1 + cap * k + q0 + j, 1.0, tag);
-            _mm_sfence();
-            const auto t0 = std::chrono::steady_clock::now();
-            unsigned long spins = 0;
-            bool ok = true;
-            for (int j = 0; j < nqg && ok; ++j) {
-              while (__atomic_load_n(&ctx->hm->qflag[q0 + j], __ATOMIC_ACQUIRE) != tag) {
-                if ((++spins & 0xFFF) == 0) {
-                  if (abort_flag.load(std::memory_order_relaxed)) { ok = false; break; }
-                  if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(3)) {
-                    timed_out[gi] = 1; abort_flag.store(1, std::memory_order_relaxed); ok = false; break;
-                  }
-                }
-              }
-            }
-            if (!ok) { pending[gi] = 1; break; }
-            if (r == 1 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(1)) slow_first[gi] = 1;
-            if (!rg.absorb(ctx->hVal, ctx->hGrad, q0)) { got_nan[gi] = 1; abort_flag.store(1, std::memory_order_relaxed); break; }
-            if (!rg.advance()) break;
-          }
-          // this group's slab and finishing groups may go (they wait for round r + 1 of their own count)
-          const unsigned long long bye = seq0 + r + 1;
-          for (int j = 0; j < nqg; ++j) put_mail_pair(m + 1 + cap * k + q0 + j, 0.0, bye);
-          _mm_sfence();
-          left[gi] = 1;
-          used[gi] = r + 1;
-        };
-        hp.fn = [&] { free_loop(1); };                 // the helper is idle here (its ticket of this round is done)
-        const unsigned fticket = hp.go.load(std::memory_order_relaxed) + 1;
-        hp.go.store(fticket, std::memory_order_release);
-        free_loop(0);
-        while (hp.done.load(std::memory_order_acquire) != fticket) __builtin_ia32_pause();
-        hp.fn = [&] { for (int gi = 1; gi < ngroups; gi += T) advance(gi); };
-        HIPCHK(hipStreamSynchronize(ctx->stream));      // every group of the grid has been told to leave
-        ctx->seq = seq0 + std::max(used[0], used[1]) + 1;
-        srv_cap = 0;
-        if (got_nan[0] || got_nan[1]) return set_err(ctx, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
-        if (timed_out[0] || timed_out[1]) ctx->srv_penalty = 1000;      // plain launches from here on (see below)
-        else if (slow_first[0] || slow_first[1]) ctx->srv_penalty = 40;
+        if ((rc = srv.pair(crew, run)) != PCABO_OK) return rc;
         if (!grp[0].active && !grp[1].active) break;    // the normal end: both groups ran to their stop
-        continue;                                       // a wait failed: the lock-step loop below finishes the call
+        continue;                                       // a wait failed: the lock-step rounds finish the call
       }
     }
-    if (srv_cap > 0) {
-      const unsigned long long tag = ++ctx->seq;
-      const double tp = now();
-      server_post(ctx, srv_cap, nq, k, tag);
-      rc = server_wait(ctx, nq, tag);
-      if (rc == PCABO_ERR_TIMEOUT) {       // e.g. this thread lost the CPU for longer than the kernel waits: plain launches from here on
-        server_stop.stop();
-        ctx->srv_penalty = 1000;
-        rc = eval_staged(ctx, nq, p);
-      } else if (round_no == 1 && now() - tp > 1e-3) {
-        // A first answer after more than a millisecond (normal: ~20 us) means the grid could not become resident at once:
-        // another process holds the GPU with its own resident kernel.  Resident kernels of different processes then run
-        // one after the other, whole calls at a time; plain launches interleave much better, so use them for a while.
-        ctx->srv_penalty = 40;
-      }
+    if (srv.cap > 0) {
+      rc = srv.round(nq, round_no == 1);
     } else if (group_mode(ctx, nq, 1) && batch_limit <= PCABO_GROUP_Q && ngroups <= 8) {
-      int g0[8], gn[8], ng = 0;
-      for (int gi = 0; gi < ngroups; ++gi) if (qoff[gi] >= 0) { g0[ng] = qoff[gi]; gn[ng] = grp[gi].nq; ++ng; }
-      rc = eval_staged_groups(ctx, g0, gn, ng, p);
+      GroupLaunches t;
+      for (int gi = 0; gi < ngroups; ++gi) if (qoff[gi] >= 0) t.add(qoff[gi], grp[gi].nq);
+      rc = eval_staged_groups(ctx, t, p);
     } else {
       rc = eval_staged(ctx, nq, p);
     }
     if (rc != PCABO_OK) return rc;
-    for (int gi = 0; gi < ngroups; ++gi)
-      if (qoff[gi] >= 0 && !grp[gi].absorb(ctx->hVal, ctx->hGrad, qoff[gi]))
-        return set_err(ctx, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
+    if (!absorb_packed(run, qoff)) return set_err(ctx, PCABO_ERR_NAN, "NaN in acquisition gradient%s", "");
   }
-  server_stop.stop();
+  srv.stop();
   // botorch evaluates the acquisition once more at the clamped end points.  An L-BFGS-B run normally ends ON the last point
   // it had evaluated (the accepted trial of its last line search), whose per-restart values are still here - the same
   // kernel arithmetic, so the same bits; only a run that ended elsewhere (abnormal line search) needs the launch.

@@ -1,9 +1,13 @@
 """CPU-side guards (SURVEY.md section 5 "race detection / sanitizers").
 
 1. The host side of the library - csrc/lbfgsb.cpp, csrc/host_entry.cpp, csrc/host_side.h (RestartGroup, RunRestarts, run_rounds,
-   GangPool; FitRun, fit_rounds, mll_assemble) and csrc/lb_plan.h - built with g++ under AddressSanitizer,
-   UndefinedBehaviorSanitizer and ThreadSanitizer (`make asan ubsan tsan`, no GPU, no HIP runtime) and run: a driver whose pool
-   workers run the product's round loop (run_rounds) with a stub evaluator, the GP fit's stepper (FitRun / fit_rounds) over a small
+   GangPool; OptHelper, OptCrew, CrewCall, pack_active, absorb_packed, free_pair; FitRun, fit_rounds, mll_assemble) and
+   csrc/lb_plan.h - built with g++ under AddressSanitizer, UndefinedBehaviorSanitizer and ThreadSanitizer (`make asan ubsan
+   tsan`, no GPU, no HIP runtime) and run: a driver whose pool workers run the product's round loop (run_rounds) with a stub
+   evaluator; the single run's optimise call without its launches - the helper threads of a call for every number of stepping
+   threads (1 to 7), each group against the same group alone, two calls on the same helpers, and the free-running pair of two
+   groups over a mailbox in plain memory that a third thread answers: both groups to their stop, a group that is never answered
+   (time-out, abort, the call finished in lock-step) and a NaN gradient; the GP fit's stepper (FitRun / fit_rounds) over a small
    dense GP on the CPU - lock-step runs against the same runs alone, the NOT_PD and DOMAIN stops, resting and parked runs - and
    the scipy comparison of tests/test_lbfgsb_vs_scipy.py once more through the ASan build of the entry points.
 2. The kernarg segment of every kernel in the built code objects stays below 3 968 bytes: round 2's abort under the tracer came
