@@ -10,10 +10,13 @@
 // the rule gives, two calls on the same helpers) and the free-running pair of two groups (free_pair: test_free_pair) over a
 // mailbox in plain memory that a third thread answers in the resident kernel's place - both groups to their stop, a group that
 // is never answered (the time-out is a parameter: milliseconds here), a NaN gradient.  No check uses more than eight threads.
+// The memory of a context is csrc/ctx_layout.h's arithmetic (test_ctx_layout): no region is allocated, the offsets and every
+// feature's use of a buffer are checked as numbers over a sweep of shapes.
 // Exit code 0 and "host selftest ok" = every check passed; a sanitizer report aborts the process (halt_on_error).
 #include "../../include/pcabo.h"
 #include "host_side.h"
 #include "lb_plan.h"
+#include "ctx_layout.h"
 
 #include <atomic>
 #include <cmath>
@@ -939,6 +942,127 @@ void test_inverse_map_host() {
   CHECK(x == std::ldexp(1.0, -60), "inverse map: the chain is not fused (got %g, an unfused product gives 0)", x);
 }
 
+// The layout of a context's memory (ctx_layout.h), arithmetic only: no region is allocated, no pointer formed.  For every shape of
+// the sweep: the buffers in carving order, apart, 256-byte aligned, the regions multiples of 4096 bytes and two calls alike (what
+// lets a batch address every run with one stride); every secondary use of a buffer inside its landlord at its largest legal
+// arguments, and the uses that are live together apart; the fitting predicates against the inequalities they replaced, written out
+// here once as they stood at the call sites.  For four shapes every offset and both region sizes against a recorded table: the
+// numbers were printed by the hand-written carving code that ctx_layout() replaced, not by ctx_layout() itself, so a change of an
+// offset fails here (the batched kernels' single stride and the bit-pinned tests rest on the layout).
+void test_ctx_layout() {
+  struct Pinned { int shape[3]; size_t dev_bytes, host_bytes, dev[D_COUNT], host[H_COUNT]; };
+  static const Pinned pinned[] = {
+    {{2, 1, 1}, 262144, 12288,
+    {
+     0, 256, 512, 768, 1024, 1792, 2048, 2304, 2560, 4608, 4864, 5120, 5376, 5632, 5888, 6144, 6400, 6656, 7168, 7424, 11520,
+     12544, 14592, 16640, 18688, 19200, 51968, 84736, 117504, 118016, 118528, 184064, 184320, 192768, 193024, 193280, 193536,
+     193792, 194048, 194560, 260096, 260352, 261376},
+    {
+     0, 4608, 8192, 8448, 8704, 9472, 9728, 9984, 10240, 11264}},
+    {{90, 5, 16}, 876544, 24576,
+    {
+     0, 3840, 7680, 8448, 9216, 21248, 22016, 22528, 31232, 33280, 33536, 33792, 34048, 37888, 38144, 38400, 38656, 39424,
+     40448, 40704, 44800, 45824, 47872, 56064, 64256, 65280, 196352, 327424, 458496, 459520, 460544, 526080, 526848, 791040,
+     791296, 792064, 792320, 792576, 792832, 809216, 874752, 875264, 876288},
+    {
+     0, 4608, 8192, 8448, 9216, 10496, 19200, 19456, 19712, 20736}},
+    {{450, 40, 512}, 44011520, 651264,
+    {
+     0, 144128, 288256, 292096, 295936, 470272, 474112, 487936, 783360, 801792, 814592, 827392, 827904, 972032, 972288, 972544,
+     972800, 976640, 980736, 980992, 985088, 986112, 988160, 1152000, 1315840, 1319936, 3417088, 5514240, 7611392, 7615488,
+     7619584, 7685120, 7849216, 41665792, 41669888, 41833728, 41834240, 41834752, 41835008, 43932160, 43997696, 44009984,
+     44011008},
+    {
+     0, 4608, 168704, 172800, 336640, 352512, 647936, 648192, 648704, 649728}},
+    {{513, 128, 64}, 18243584, 1339392,
+    {
+     0, 525312, 1050624, 1054976, 1059328, 1588736, 1593088, 1727232, 2786304, 2917376, 3048448, 3179520, 3180544, 3705856,
+     3706112, 3706368, 3706624, 3710976, 3715584, 3715840, 3719936, 3720960, 3723008, 4312832, 4902656, 4907264, 7561472,
+     10215680, 12869888, 12874496, 12879104, 12944640, 13010432, 17765888, 17766400, 17831936, 17832960, 17833984, 17834240,
+     18129152, 18194688, 18242304, 18243328},
+    {
+     0, 4608, 70400, 70912, 136448, 276224, 1335296, 1335552, 1336832, 1337856}},
+  };
+  for (const Pinned& p : pinned) {
+    const CtxLayout L = ctx_layout(ctx_shape(p.shape[0], p.shape[1], p.shape[2]));
+    CHECK(L.dev_bytes == p.dev_bytes && L.host_bytes == p.host_bytes, "layout (%d, %d, %d): region sizes %zu / %zu", p.shape[0], p.shape[1], p.shape[2], L.dev_bytes, L.host_bytes);
+    for (int i = 0; i < D_COUNT; ++i) CHECK(L.dev[i].off == p.dev[i], "layout (%d, %d, %d): device buffer %d at %zu, recorded %zu", p.shape[0], p.shape[1], p.shape[2], i, L.dev[i].off, p.dev[i]);
+    for (int i = 0; i < H_COUNT; ++i) CHECK(L.host[i].off == p.host[i], "layout (%d, %d, %d): host buffer %d at %zu, recorded %zu", p.shape[0], p.shape[1], p.shape[2], i, L.host[i].off, p.host[i]);
+  }
+  const auto region_ok = [](const Buf* b, int count, size_t bytes) {
+    size_t end = 0;
+    for (int i = 0; i < count; ++i) {
+      if (b[i].off % 256 != 0 || b[i].off < end || b[i].count == 0 || b[i].elem == 0) return false;
+      end = b[i].off + b[i].count * b[i].elem;
+    }
+    return bytes % 4096 == 0 && end <= bytes && bytes - end < 4096;
+  };
+  const int ns[] = {2, 63, 64, 65, 448, 512, 513, 1280, 4096}, ds[] = {1, 3, 4, 5, 16, 17, 40, 41, 128};
+  const int qs[] = {1, 15, 16, 32, 63, 64, 72, 512, PCABO_CNT_DONE - 1};
+  CHECK(!ctx_sizes_ok(1, 1, 1) && !ctx_sizes_ok(2, 0, 1) && !ctx_sizes_ok(2, PCABO_MAXD + 1, 1) && !ctx_sizes_ok(2, 1, 0) &&
+        !ctx_sizes_ok(2, 1, PCABO_CNT_DONE), "ctx_sizes_ok lets a shape beyond the limits through");
+  for (int max_n : ns) for (int max_d : ds) for (int max_q : qs) {
+    CHECK(ctx_sizes_ok(max_n, max_d, max_q), "shape (%d, %d, %d) refused", max_n, max_d, max_q);
+    const CtxShape s = ctx_shape(max_n, max_d, max_q);
+    const CtxLayout L = ctx_layout(s), L2 = ctx_layout(ctx_shape(max_n, max_d, max_q));
+#define LCHECK(c, what) CHECK(c, "layout (%d, %d, %d): %s", max_n, max_d, max_q, what)
+    LCHECK(s.NPcap % PCABO_BS == 0 && s.NPcap >= max_n && s.NPcap - max_n < PCABO_BS && s.DPcap % 16 == 0 && s.DPcap >= max_d &&
+           s.KPcap % 4 == 0 && s.KPcap >= max_d && s.KPcap - max_d < 4 && s.Scap * PCABO_SLAB == s.NPcap, "the padded capacities");
+    LCHECK(region_ok(L.dev, D_COUNT, L.dev_bytes), "device buffers out of order, overlapping or unaligned");
+    LCHECK(region_ok(L.host, H_COUNT, L.host_bytes), "host buffers out of order, overlapping or unaligned");
+    LCHECK(std::memcmp(L.dev, L2.dev, sizeof(L.dev)) == 0 && std::memcmp(L.host, L2.host, sizeof(L.host)) == 0 &&
+           L.dev_bytes == L2.dev_bytes && L.host_bytes == L2.host_bytes, "two calls disagree");
+    const Buf &partial = L.dev[D_PARTIAL], &xq = L.dev[D_XQ], &hxq = L.host[H_XQ], &small = L.host[H_SMALL];
+    // dPartial: the extend scratch, the leave-one-out block, the posterior's records and results
+    LCHECK(fits(partial_ext_scratch(s), partial), "the extend scratch");
+    LCHECK(fits(partial_loo(max_n), partial) && partial_loo_part(max_n, 3) + max_n == partial_loo(max_n).count, "the leave-one-out block");
+    for (int q : {1, max_q}) for (int NP : {64, s.NPcap}) {
+      const Use rec = partial_post_records(q, NP), res = partial_post_result(q, NP);
+      LCHECK(fits(rec, partial) && fits(res, partial) && apart(rec, res), "the posterior's records and results");
+    }
+    // dXq: the extend's rows and values; rows_cap as the call site had it
+    LCHECK(fits(xq_queries(s), xq) && fits(xq_queries(s), hxq) && xq_queries(s).count + PCABO_XQ_TAIL == xq.count, "the query block");
+    for (int k = 1; k <= max_d; ++k) {
+      const int rows_cap = ext_rows_cap(s, k);
+      const Use rows = xq_ext_rows(s, k), vals = xq_ext_vals(s, k);
+      LCHECK(rows_cap >= 1 && rows_cap == (int)(((size_t)max_q * max_d + 8) / ((size_t)k + 1)), "rows_cap");
+      LCHECK((size_t)rows_cap * (k + 1) <= xq.count && fits(rows, xq) && fits(vals, xq) && apart(rows, vals), "the extend's rows and values");
+    }
+    // the device optimiser: opt_fits against `max_q < 64 + 8 ngroups || (num_restarts + 2) kmax > max_q max_d`, and its tenants
+    for (int nr : {1, 5, 10, 32}) for (int bl : {1, 5}) for (int kmax : {1, max_d}) {
+      const int ngroups = opt_groups(nr, bl);
+      const bool was = !(max_q < 64 + 8 * ngroups || (size_t)(nr + 2) * kmax > (size_t)max_q * max_d);
+      LCHECK(ngroups == (nr + bl - 1) / bl && opt_fits(L, nr, ngroups, kmax) == was, "the device optimiser's eligibility");
+      // (its evaluation-only entry point asked `max_q < 64` alone)
+      LCHECK(opt_fits(L, nr, 0, kmax) == !(max_q < 64), "the device evaluation's eligibility");
+      if (!was) continue;
+      const Use pts = xq_opt_points(nr, kmax), cands = grad_opt_cands(nr, kmax), vals = val_opt_values(nr), rec = val_opt_records(ngroups);
+      LCHECK(fits(pts, xq) && fits(pts, hxq), "the device optimiser's points");
+      LCHECK(fits(cands, L.dev[D_GRAD]) && fits(cands, L.host[H_GRAD]), "the device optimiser's candidates");
+      LCHECK(fits(vals, L.dev[D_VAL]) && fits(rec, L.dev[D_VAL]) && fits(rec, L.host[H_VAL]) && apart(vals, rec) &&
+             val_opt_record(0) == 64 && val_opt_record(ngroups - 1) + 8 == rec.start + rec.count, "the device optimiser's values and records");
+    }
+    // the fit's results behind the widest run's tile partials, on both sides
+    for (int M : {1, s.KPcap}) {
+      const Use part = mll_partials(s.NPcap, M), res = mll_result(s.NPcap, M);
+      LCHECK(fits(part, L.dev[D_MLL]) && fits(res, L.dev[D_MLL]) && apart(part, res) && fits(hmll_result(M), L.host[H_MLL]) &&
+             hmll_result(M).count == res.count, "the fit's results");
+    }
+    // hSmall at k = d = max_d: the wPCA results, the inverse map's x, a batch's Normalize bounds
+    const Use w = small_wpca(s), x = small_imap_x(s), nb = small_norm_bounds(s);
+    const PcaParts pp = pca_parts(s);
+    LCHECK(fits(w, small) && fits(x, small) && fits(nb, small) && apart(w, x) && apart(w, nb) && apart(x, nb), "the three tenants of hSmall");
+    LCHECK(x.count >= (size_t)max_d && nb.count >= 2 * (size_t)max_d && pca_copy_count(s, max_d, max_d) == w.count && w.count == L.dev[D_PCAOUT].count &&
+           pp.data_mean + max_d <= pp.pca_mean && pp.pca_mean + max_d <= pp.evr && pp.evr + max_d <= pp.comps, "the wPCA result block");
+    // the packed inputs, the tickets, the transposed root inverse, the kernel vectors' rows
+    LCHECK(in_pack(max_n, max_d, true, true, true).total == L.dev[D_IN].count && L.dev[D_IN].count == L.host[H_IN].count, "the packed inputs");
+    LCHECK(fits(counters_queries(max_q), L.dev[D_COUNTERS]) && fits(counters_group(), L.dev[D_COUNTERS]) &&
+           apart(counters_queries(PCABO_QFLAG_WORDS), counters_group()), "the tickets");
+    LCHECK(fits(gram_rt(s.NPcap, s.NPcap), L.dev[D_GRAM]), "the transposed root inverse");
+#undef LCHECK
+  }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -953,6 +1077,7 @@ int main(int argc, char** argv) {
   test_free_pair();
   test_fit_run();
   test_inverse_map_host();
+  test_ctx_layout();
   test_gang_pool(1, 3);
   test_gang_pool(workers, 11);
   if (g_fail) { std::fprintf(stderr, "host selftest: %d check(s) failed\n", g_fail); return 1; }

@@ -1670,7 +1670,7 @@ __device__ __noinline__ void lb_eval(const LbLds L_, int nq, bool want_grad) {
 // mode 1: optimise from the initial conditions; mode 0: one evaluation at the given points (value and gradient to the run's
 // dVal / dGrad: the host-paced twin of the tests and the end-point values).
 // Per run (stride zs): Xq = [num_restarts x k initial points | lower[k] | upper[k]], out_x = candidates (num_restarts x k),
-// out_v = [values (num_restarts) ... | 64 + 8 gi: niter, nfev, warnflag, task, status, evaluations, ties].
+// out_v = [values (num_restarts) ... | PCABO_OPT_REC_BASE + PCABO_OPT_REC_STRIDE gi: niter, nfev, warnflag, task, status, evaluations, ties].
 // =====================================================================================================================
 __global__ __launch_bounds__(LB_THREADS) void k_lbfgsb_group(
     const unsigned* __restrict__ table, int mode, int num_restarts, int maxiter, int n, int NP, int ld,
@@ -1770,7 +1770,7 @@ __global__ __launch_bounds__(LB_THREADS) void k_lbfgsb_group(
   if (tid == 0) {
     const int task = ISR(I_TASK);
     const int wf = (task == LBFGSB_CONV_PG || task == LBFGSB_CONV_F) ? 0 : ((task == LBFGSB_STOP_ITER || task == LBFGSB_STOP_FUN) ? 1 : 2);
-    double* o = out_v + 64 + 8 * gi;
+    double* o = out_v + PCABO_OPT_REC_BASE + PCABO_OPT_REC_STRIDE * gi;
     o[0] = ISR(I_NITER); o[1] = ISR(I_NFEV); o[2] = wf; o[3] = task; o[4] = status; o[5] = ISR(I_EVALS); o[6] = ISR(I_TIES);
     o[7] = ISR(I_ACTIVE) ? 1.0 : 0.0;                 // 1: stopped by the evaluation cap (cannot happen within the host's limits)
   }

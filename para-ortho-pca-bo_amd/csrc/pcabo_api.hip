@@ -46,7 +46,8 @@ struct pcabo_ctx {
   bool zn_recorded = false;              // evZn belongs to the conditioning in flight
   bool opt_hidden_tail = true;
   int max_n = 0, max_d = 0, max_q = 0;
-  int NPcap = 0, ld = 0, DPcap = 0, KPcap = 0, Scap = 0;
+  CtxLayout lay{};                       // shape (lay.s: the padded capacities) and layout of the two regions (ctx_layout.h)
+  int ld = 0;
   int ptr_mode = PCABO_PTR_HOST;
   // problem state
   int n = 0, d = 0, k = 0, NP = 0, KP = 0;
@@ -82,7 +83,6 @@ struct pcabo_ctx {
                                          // by the first such call, kept until destroy
   char* dSample = nullptr;               // pcabo_gp_posterior_sample: the sample block (SampleBlock), allocated by the first such call
   char *dRegion = nullptr, *hRegion = nullptr;   // the two allocations everything above / below is carved from
-  size_t region_bytes = 0, hregion_bytes = 0;
   bool in_batch = false; int batch_index = 0;
   bool rt_stale = false;                 // pcabo_get_gram has overwritten the transposed root inverse kept in dGram (device-resident L-BFGS-B)
   // pinned host
@@ -326,82 +326,46 @@ int pcabo_device_count(void) {
 }  // extern "C" (helpers with C++ linkage follow)
 
 // ---- memory of a context --------------------------------------------------------------------------------------------
-// All device buffers of a context are carved out of ONE allocation (its "region"), all pinned host buffers out of another.
-// A stand-alone context owns both.  The contexts of a batch (pcabo_batch_create) live side by side in one device slab and
-// one pinned slab with the SAME layout, so that buffer X of run b sits at (X of run 0) + b * region_bytes: the batched
-// launches address a run's operands as `pointer + blockIdx.z * stride` with a single stride for every buffer.
-struct Carver {
-  char* base; size_t off = 0;
-  template <typename T> T* take(size_t count) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += count * sizeof(T);
-    return p;
-  }
-};
-static size_t carve_device(pcabo_ctx* ctx, char* base) {
-  Carver c{base};
-  const size_t N = ctx->NPcap, D = ctx->DPcap, n = ctx->max_n, d = ctx->max_d, Q = ctx->max_q;
-  ctx->dX = c.take<double>(n * d);        ctx->dNoise = c.take<double>(n * d);
-  ctx->dF = c.take<double>(n);            ctx->dWeights = c.take<double>(n);
-  ctx->dWc = c.take<double>((n + 4) * D); ctx->dRanks = c.take<long long>(n);
-  ctx->dPcaOut = c.take<double>(3 * d + d * d);
-  ctx->dDataMean = ctx->dPcaOut; ctx->dPcaMean = ctx->dPcaOut + d; ctx->dEvr = ctx->dPcaOut + 2 * d;
-  ctx->dComps = ctx->dPcaOut + 3 * d;
-  ctx->dIn = c.take<double>(n * (2 * d + 2));
-  ctx->dC = c.take<double>(D * D);        ctx->dGbuf[0] = c.take<double>(d * d); ctx->dGbuf[1] = c.take<double>(d * d);
+// The context's pointers from its layout (ctx_layout.h: the two regions, every buffer's offset, and who else uses a buffer)
+static void ctx_bind(pcabo_ctx* ctx) {
+  const CtxLayout& L = ctx->lay;
+  const auto D = [&](DevBuf b) { return buf_at<double>(ctx->dRegion, L.dev[b]); };
+  const auto I = [&](DevBuf b) { return buf_at<int>(ctx->dRegion, L.dev[b]); };
+  const auto H = [&](HostBuf b) { return buf_at<double>(ctx->hRegion, L.host[b]); };
+  ctx->dX = D(D_X);             ctx->dNoise = D(D_NOISE);   ctx->dF = D(D_F);           ctx->dWeights = D(D_WEIGHTS);
+  ctx->dWc = D(D_WC);           ctx->dRanks = buf_at<long long>(ctx->dRegion, L.dev[D_RANKS]);
+  const PcaParts pp = pca_parts(L.s);
+  ctx->dPcaOut = D(D_PCAOUT);
+  ctx->dDataMean = ctx->dPcaOut + pp.data_mean; ctx->dPcaMean = ctx->dPcaOut + pp.pca_mean; ctx->dEvr = ctx->dPcaOut + pp.evr;
+  ctx->dComps = ctx->dPcaOut + pp.comps;
+  ctx->dIn = D(D_IN);           ctx->dC = D(D_C);           ctx->dGbuf[0] = D(D_G0);    ctx->dGbuf[1] = D(D_G1);
   ctx->dG = ctx->dGbuf[0];
-  ctx->dLam = c.take<double>(d);          ctx->dZ = c.take<double>(n * d);
-  ctx->dK = c.take<int>(1);               ctx->dSweeps = c.take<int>(1);         ctx->dInfo = c.take<int>(1);
-  ctx->dY = c.take<double>(n);            ctx->dYs = c.take<double>(N);
-  ctx->dYstats = c.take<double>(2);       ctx->dBounds4 = c.take<double>(4 * PCABO_MAXD);
-  ctx->dZnMean = c.take<double>(PCABO_MAXD); ctx->dUserNB = c.take<double>(2 * PCABO_MAXD);
-  ctx->dZnT = c.take<double>((size_t)ctx->KPcap * N); ctx->dAT = c.take<double>((size_t)ctx->KPcap * N);
-  ctx->dNrm = c.take<double>(N);
-  ctx->dGram = c.take<double>(N * N);     ctx->dL = c.take<double>(N * N);       ctx->dR = c.take<double>(N * N);
-  ctx->dTmp = c.take<double>(N);          ctx->dAlpha = c.take<double>(N);
-  ctx->dDiag = c.take<double>((size_t)2 * PCABO_BS * PCABO_BS);      // two hand-over tiles (k_chol_step)
-  ctx->dXq = c.take<double>(Q * d + 8);   // (+ the run's best_f behind the query block in batched scoring)
-  ctx->dPartial = c.take<double>(Q * (size_t)ctx->Scap * (2 + 2 * PCABO_MAXD));
-  ctx->dVal = c.take<double>(Q);          ctx->dGrad = c.take<double>(Q * d);
-  ctx->dZq = c.take<double>(d);           ctx->dXout = c.take<double>(d);
-  ctx->dBestF = c.take<double>(2);
-  ctx->dKS = c.take<double>(Q * N);        // kernel vectors of a large value-only batch (GEMM scoring)
-  ctx->dCounters = c.take<unsigned int>(PCABO_CNT_DONE + 1);
-  const size_t nb = N / PCABO_BS;
-  ctx->dMll = c.take<double>(std::max<size_t>(nb * (nb + 1), nb * (nb + 1) / 2 * (1 + (size_t)ctx->KPcap) + ctx->KPcap) + 8);
-  ctx->dArdLs = c.take<double>(PCABO_MAXD);
-  ctx->dHyp = c.take<double>(PCABO_HYP_WORDS);
-  return (c.off + 4095) & ~(size_t)4095;
+  ctx->dLam = D(D_LAM);         ctx->dZ = D(D_Z);
+  ctx->dK = I(D_K);             ctx->dSweeps = I(D_SWEEPS); ctx->dInfo = I(D_INFO);
+  ctx->dY = D(D_Y);             ctx->dYs = D(D_YS);         ctx->dYstats = D(D_YSTATS); ctx->dBounds4 = D(D_BOUNDS4);
+  ctx->dZnMean = D(D_ZNMEAN);   ctx->dUserNB = D(D_USERNB); ctx->dZnT = D(D_ZNT);       ctx->dAT = D(D_AT);
+  ctx->dNrm = D(D_NRM);         ctx->dGram = D(D_GRAM);     ctx->dL = D(D_L);           ctx->dR = D(D_R);
+  ctx->dTmp = D(D_TMP);         ctx->dAlpha = D(D_ALPHA);   ctx->dDiag = D(D_DIAG);
+  ctx->dXq = D(D_XQ);           ctx->dPartial = D(D_PARTIAL); ctx->dVal = D(D_VAL);     ctx->dGrad = D(D_GRAD);
+  ctx->dZq = D(D_ZQ);           ctx->dXout = D(D_XOUT);     ctx->dBestF = D(D_BESTF);   ctx->dKS = D(D_KS);
+  ctx->dCounters = buf_at<unsigned int>(ctx->dRegion, L.dev[D_COUNTERS]);
+  ctx->dMll = D(D_MLL);         ctx->dArdLs = D(D_ARDLS);   ctx->dHyp = D(D_HYP);
+  ctx->hm = buf_at<HostMirror>(ctx->hRegion, L.host[H_MIRROR]);
+  ctx->hXq = H(H_XQ);           ctx->hVal = H(H_VAL);       ctx->hGrad = H(H_GRAD);     ctx->hSmall = H(H_SMALL);
+  ctx->hIn = H(H_IN);           ctx->hBestF = H(H_BESTF);   ctx->hMll = H(H_MLL);       ctx->hArdLs = H(H_ARDLS);
+  ctx->hHyp = H(H_HYP);
 }
-static size_t carve_host(pcabo_ctx* ctx, char* base) {
-  Carver c{base};
-  const size_t n = ctx->max_n, d = ctx->max_d, Q = ctx->max_q;
-  ctx->hm = c.take<HostMirror>(1);
-  // (hXq: at least one QueryArgs block - small batches are handed to the kernel by value from here)
-  ctx->hXq = c.take<double>(std::max<size_t>(Q * d, PCABO_QA_MAX) + 8);
-  ctx->hVal = c.take<double>(Q);
-  ctx->hGrad = c.take<double>(Q * d);
-  ctx->hSmall = c.take<double>(d * d + 8 * d + 64);
-  ctx->hIn = c.take<double>(n * (2 * d + 2));
-  ctx->hBestF = c.take<double>(2);
-  ctx->hMll = c.take<double>(8 + (size_t)ctx->KPcap);
-  ctx->hArdLs = c.take<double>(PCABO_MAXD);
-  ctx->hHyp = c.take<double>(PCABO_HYP_WORDS);
-  return (c.off + 4095) & ~(size_t)4095;
-}
+// a use of hSmall in one run's block; the bytes of a run's ticket array
+static double* small_at(const pcabo_ctx* ctx, Use u) { return ctx->hSmall + u.start; }
+static size_t ticket_bytes(const pcabo_ctx* ctx) { return ctx->lay.dev[D_COUNTERS].count * sizeof(unsigned int); }
 
 // Fill in a context over (optionally) somebody else's memory and stream: `dreg` / `hreg` / `stream` non-null = a member
 // of a batch (no resident-mode buffers, nothing owned).
-static int ctx_setup(pcabo_ctx* ctx, int device, int max_n, int max_d, int max_q, char* dreg, char* hreg,
-                     hipStream_t stream) {
+static int ctx_setup(pcabo_ctx* ctx, int device, const CtxLayout& lay, char* dreg, char* hreg, hipStream_t stream) {
   ctx->device = device;
-  ctx->max_n = max_n; ctx->max_d = max_d; ctx->max_q = max_q;
-  ctx->NPcap = round_up(max_n, PCABO_BS);
-  ctx->ld = ctx->NPcap;
-  ctx->DPcap = round_up(max_d, 16);
-  ctx->KPcap = round_up(max_d, 4);
-  ctx->Scap = ctx->NPcap / PCABO_SLAB;
+  ctx->lay = lay;
+  ctx->max_n = lay.s.max_n; ctx->max_d = lay.s.max_d; ctx->max_q = lay.s.max_q;
+  ctx->ld = lay.s.NPcap;
   ctx->in_batch = dreg != nullptr;
   HIPCHK(hipSetDevice(device));
   if (stream) ctx->stream = stream;
@@ -414,20 +378,17 @@ static int ctx_setup(pcabo_ctx* ctx, int device, int max_n, int max_d, int max_q
     HIPCHK(hipEventCreateWithFlags(&ctx->evZn, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&ctx->evKS, hipEventDisableTiming));
   }
-  ctx->region_bytes = carve_device(ctx, nullptr);
-  ctx->hregion_bytes = carve_host(ctx, nullptr);
   if (dreg) {
     ctx->dRegion = dreg; ctx->hRegion = hreg;        // zeroed by the batch
   } else {
-    HIPCHK(hipMalloc((void**)&ctx->dRegion, ctx->region_bytes));
-    HIPCHK(hipHostMalloc((void**)&ctx->hRegion, ctx->hregion_bytes, hipHostMallocDefault));
-    memset(ctx->hRegion, 0, ctx->hregion_bytes);
+    HIPCHK(hipMalloc((void**)&ctx->dRegion, lay.dev_bytes));
+    HIPCHK(hipHostMalloc((void**)&ctx->hRegion, lay.host_bytes, hipHostMallocDefault));
+    memset(ctx->hRegion, 0, lay.host_bytes);
   }
-  carve_device(ctx, ctx->dRegion);
-  carve_host(ctx, ctx->hRegion);
+  ctx_bind(ctx);
   if (!dreg) {
     // zero: the per-query tickets, the padded tail of y_s, and R (its blocks above the diagonal stay zero for good)
-    HIPCHK(hipMemsetAsync(ctx->dRegion, 0, ctx->region_bytes, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->dRegion, 0, lay.dev_bytes, ctx->stream));
     if (hipExtMallocWithFlags((void**)&ctx->dMail, PCABO_MAIL_PAIRS * sizeof(MailPair), hipDeviceMallocFinegrained) != hipSuccess) {
       (void)hipGetLastError();
       HIPCHK(dalloc(&ctx->dMail, PCABO_MAIL_PAIRS));
@@ -474,10 +435,6 @@ static void ctx_teardown(pcabo_ctx* ctx) {
   if (ctx->registered) presence_unregister(ctx->device);
 }
 
-static bool ctx_sizes_ok(int max_n, int max_d, int max_q) {
-  return max_n >= 2 && max_d >= 1 && max_d <= PCABO_MAXD && max_q >= 1 && max_q < PCABO_CNT_DONE;
-}
-
 // ---- rows D-H: ONE launch sequence for a single context and for the B runs of a batch -----------------------------------
 // ctx = the context, or run 0 of a batch with zb = its strides (blockIdx.z = run).  phase(1..4) is called at the four cuts of the
 // sequence - before k_zstats, before the Cholesky, before the root inverse, behind alpha - and returns PCABO_OK (0) or an error that
@@ -498,7 +455,7 @@ struct RowsDH {
 // pcabo_gp_truncate) they are reset as enqueue_rows_dh resets them.
 static int ext_tickets(pcabo_ctx* ctx, hipStream_t s, int NP, int* cnt_S) {
   if (acq_slabs(NP) == *cnt_S) return PCABO_OK;
-  HIPCHK(hipMemsetAsync(ctx->dCounters, 0, (PCABO_CNT_DONE + 1) * sizeof(unsigned int), s));
+  HIPCHK(hipMemsetAsync(ctx->dCounters, 0, ticket_bytes(ctx), s));
   *cnt_S = acq_slabs(NP);
   return PCABO_OK;
 }
@@ -524,8 +481,8 @@ static int enqueue_rows_dh(pcabo_ctx* ctx, hipStream_t s, const RowsDH& a, Phase
   // the per-query tickets count modulo the number of slab groups: they only need a reset when that number changes
   // (every 64th iteration) or after a launch that did not complete
   if (a.cnt_S && (acq_slabs(NP) != *a.cnt_S || *a.cnt_dirty)) {
-    if (a.zb.zs) HIPCHK(hipMemset2DAsync(ctx->dCounters, a.zb.zs, 0, (PCABO_CNT_DONE + 1) * sizeof(unsigned int), a.zb.B, s));
-    else HIPCHK(hipMemsetAsync(ctx->dCounters, 0, (PCABO_CNT_DONE + 1) * sizeof(unsigned int), s));
+    if (a.zb.zs) HIPCHK(hipMemset2DAsync(ctx->dCounters, a.zb.zs, 0, ticket_bytes(ctx), a.zb.B, s));
+    else HIPCHK(hipMemsetAsync(ctx->dCounters, 0, ticket_bytes(ctx), s));
     *a.cnt_S = acq_slabs(NP); *a.cnt_dirty = false;
   }
   if (const int rc = phase(1)) return rc;
@@ -598,7 +555,7 @@ int pcabo_ctx_create(int device, int max_n, int max_d, int max_q, pcabo_ctx** ou
   pcabo_ctx* ctx = new (std::nothrow) pcabo_ctx();
   if (!ctx) return PCABO_ERR_HIP;
   *out = ctx;                       // handed back even on failure so the caller can read the message
-  return ctx_setup(ctx, device, max_n, max_d, max_q, nullptr, nullptr, nullptr);
+  return ctx_setup(ctx, device, ctx_layout(ctx_shape(max_n, max_d, max_q)), nullptr, nullptr, nullptr);
 }
 
 int pcabo_ctx_destroy(pcabo_ctx* ctx) {
@@ -660,16 +617,15 @@ static int stage_inputs(pcabo_ctx* ctx, const double* X, const double* f, const 
   const size_t nd = (size_t)n * d;
   if (ctx->ptr_mode == PCABO_PTR_HOST) {
     double* h = ctx->hIn;
-    size_t off = 0;
-    memcpy(h, X, nd * sizeof(double));                               in->X = ctx->dIn; off += nd;
-    if (noise) { memcpy(h + off, noise, nd * sizeof(double));        in->noise = ctx->dIn + off; off += nd; }
-    const size_t off_r = off;
-    memcpy(h + off, ranks ? (const void*)ranks : (const void*)f, (size_t)n * 8); off += n;
-    if (y) { memcpy(h + off, y, (size_t)n * sizeof(double));         in->y = ctx->dIn + off; off += n; }
+    const InPack pk = in_pack(n, d, noise != nullptr, true, y != nullptr);
+    memcpy(h, X, nd * sizeof(double));                               in->X = ctx->dIn;
+    if (noise) { memcpy(h + pk.noise, noise, nd * sizeof(double));   in->noise = ctx->dIn + pk.noise; }
+    memcpy(h + pk.ranks, ranks ? (const void*)ranks : (const void*)f, (size_t)n * 8);
+    if (y) { memcpy(h + pk.y, y, (size_t)n * sizeof(double));        in->y = ctx->dIn + pk.y; }
     // (segments are only 8-byte aligned: none of the consumers uses wider loads on them)
-    HIPCHK(hipMemcpyAsync(ctx->dIn, h, off * sizeof(double), hipMemcpyHostToDevice, s));
-    if (ranks) in->ranks = (const long long*)(ctx->dIn + off_r);
-    else { launch_rank(s, ctx->dIn + off_r, n, maximize, ctx->dRanks); in->ranks = ctx->dRanks; }
+    HIPCHK(hipMemcpyAsync(ctx->dIn, h, pk.total * sizeof(double), hipMemcpyHostToDevice, s));
+    if (ranks) in->ranks = (const long long*)(ctx->dIn + pk.ranks);
+    else { launch_rank(s, ctx->dIn + pk.ranks, n, maximize, ctx->dRanks); in->ranks = ctx->dRanks; }
     return PCABO_OK;
   }
   STAGE_IN(ctx->dX, X, nd, double);                                  in->X = ctx->dX;
@@ -699,10 +655,20 @@ static int enqueue_wpca(pcabo_ctx* ctx, const WpcaInputs& in, int n, int d, doub
     launch_project(s, in.X, ctx->dDataMean, ctx->dPcaMean, ctx->dComps, ctx->dK, n, d, ctx->dZ);
   }
   const int rcount = n < d ? n : d;
-  HIPCHK(hipMemcpyAsync(ctx->hSmall, ctx->dPcaOut, ((size_t)3 * ctx->max_d + (size_t)rcount * d) * sizeof(double),
+  HIPCHK(hipMemcpyAsync(small_at(ctx, small_wpca(ctx->lay.s)), ctx->dPcaOut, pca_copy_count(ctx->lay.s, rcount, d) * sizeof(double),
                         hipMemcpyDeviceToHost, s));
   HIPCHK(hipEventRecord(ctx->evPca, s));
   return PCABO_OK;
+}
+
+// a run's wPCA results from its pinned block to the caller's arrays (null: not asked for)
+static void wpca_hand_out(const pcabo_ctx* ctx, int d, int rcount, double* data_mean, double* pca_mean, double* comps, double* evr) {
+  const double* h = small_at(ctx, small_wpca(ctx->lay.s));
+  const PcaParts pp = pca_parts(ctx->lay.s);
+  if (data_mean) memcpy(data_mean, h + pp.data_mean, (size_t)d * sizeof(double));
+  if (pca_mean) memcpy(pca_mean, h + pp.pca_mean, (size_t)d * sizeof(double));
+  if (evr) memcpy(evr, h + pp.evr, (size_t)rcount * sizeof(double));
+  if (comps) memcpy(comps, h + pp.comps, (size_t)rcount * d * sizeof(double));
 }
 
 // wait for the wPCA results only (whatever was enqueued behind them keeps running) and hand them out
@@ -711,12 +677,7 @@ static int collect_wpca(pcabo_ctx* ctx, int n, int d, double* data_mean, double*
   HIPCHK(wait_event(ctx->evPca));
   HIPCHK(hipGetLastError());
   const int rcount = n < d ? n : d;
-  const double* h = ctx->hSmall;
-  const size_t D = ctx->max_d;
-  if (data_mean) memcpy(data_mean, h, (size_t)d * sizeof(double));
-  if (pca_mean) memcpy(pca_mean, h + D, (size_t)d * sizeof(double));
-  if (evr) memcpy(evr, h + 2 * D, (size_t)rcount * sizeof(double));
-  if (comps) memcpy(comps, h + 3 * D, (size_t)rcount * d * sizeof(double));
+  wpca_hand_out(ctx, d, rcount, data_mean, pca_mean, comps, evr);
   ctx->d = d; ctx->k = ctx->hm->k;
   ctx->have_wpca = true;
   if (k) *k = ctx->k;
@@ -888,10 +849,10 @@ static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, bool ard, const dou
 // failed enters at attempt 1.
 static int mll_attempts(pcabo_ctx* ctx, int attempt, bool ard) {
   const int rc = factor_attempts(ctx, attempt, [ctx, ard]() -> int {
-    const int nb = ctx->NP / PCABO_BS, tiles = nb * (nb + 1) / 2, M = ard ? ctx->KP : 1;
-    double* out = ctx->dMll + (size_t)(1 + M) * tiles;
+    const int M = ard ? ctx->KP : 1;
+    double* out = ctx->dMll + mll_result(ctx->NP, M).start;
     launch_mll_grad(ctx->stream, ard, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
-    HOST_OUT(ctx->hMll, out, 5 + M, double);
+    HOST_OUT(ctx->hMll, out, mll_result(ctx->NP, M).count, double);
     return PCABO_OK;
   });
   if (rc == PCABO_OK) ctx->have_gp = true;
@@ -1091,7 +1052,7 @@ static int eval_staged_groups(pcabo_ctx* ctx, const GroupLaunches& t, AcqParams&
     int nq = 0;
     for (int g = 0; g < ng; ++g) nq += gn[g];
     ProfScope ps(ctx, 4, acq_bytes(ctx->n, ctx->k, nq, p.want_grad), acq_flops(ctx->n, ctx->k, nq, p.want_grad));
-    if (launch_acq_group(s, &tab, ng, ctx->hXq, gp_model(ctx), p, ctx->dPartial, ctx->dCounters + PCABO_GROUP_CNT_OFFSET, ctx->dVal,
+    if (launch_acq_group(s, &tab, ng, ctx->hXq, gp_model(ctx), p, ctx->dPartial, ctx->dCounters + counters_group().start, ctx->dVal,
                          ctx->dGrad, ctx->hVal, ctx->hGrad, ctx->hm, seq, AcqBatch()) != 0)
       return set_err(ctx, PCABO_ERR_HIP, "the restart-group acquisition kernel could not be launched%s", "");
   }
@@ -1366,8 +1327,9 @@ int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x) {
     // A single context has [data_mean | pca_mean | evr | comps] in pinned host memory since the wPCA results were collected:
     // the k d multiply-adds run here, with the kernel's bits (inverse_map_host) - no launch, no flag wait, no device copy of x.
     if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
-    const double* h = ctx->hSmall;
-    inverse_map_host(z, h + 3 * (size_t)ctx->max_d, h + ctx->max_d, h, ctx->k, ctx->d, x);
+    const double* h = small_at(ctx, small_wpca(ctx->lay.s));
+    const PcaParts pp = pca_parts(ctx->lay.s);
+    inverse_map_host(z, h + pp.comps, h + pp.pca_mean, h + pp.data_mean, ctx->k, ctx->d, x);
     return PCABO_OK;
   }
   HIPCHK(hipSetDevice(ctx->device));
@@ -1377,7 +1339,7 @@ int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x) {
   // synchronisation (40 -> 15 us per BO iteration on the host clock)
   memcpy(ctx->hXq, z, (size_t)ctx->k * sizeof(double));
   const unsigned long long seq = ++ctx->seq;
-  double* hx = ctx->hSmall + (size_t)ctx->max_d * ctx->max_d + 3 * (size_t)ctx->max_d;      // behind the wPCA results' block
+  double* hx = small_at(ctx, small_imap_x(ctx->lay.s));
   launch_inverse_map(s, ctx->hXq, ctx->dComps, ctx->dDataMean, ctx->dPcaMean, ctx->k, ctx->d, ctx->dXout, nullptr, ZB(),
                      hx, ctx->hm, seq);
   HIPCHK(hipGetLastError());
@@ -1613,14 +1575,8 @@ int pcabo_batch_create(int device, int B, int max_n, int max_d, int max_q, pcabo
   BHIPCHK(hipStreamCreateWithFlags(&batch->stream, hipStreamNonBlocking));
   BHIPCHK(hipEventCreateWithFlags(&batch->evPca, hipEventDisableTiming));
   BHIPCHK(hipEventCreateWithFlags(&batch->evBounds, hipEventDisableTiming));
-  {
-    pcabo_ctx probe;                 // layout only
-    probe.max_n = max_n; probe.max_d = max_d; probe.max_q = max_q;
-    probe.NPcap = round_up(max_n, PCABO_BS); probe.DPcap = round_up(max_d, 16); probe.KPcap = round_up(max_d, 4);
-    probe.Scap = probe.NPcap / PCABO_SLAB;
-    batch->zs = carve_device(&probe, nullptr);
-    batch->hzs = carve_host(&probe, nullptr);
-  }
+  const CtxLayout lay = ctx_layout(ctx_shape(max_n, max_d, max_q));      // of every run: run b's regions lie b strides behind run 0's
+  batch->zs = lay.dev_bytes; batch->hzs = lay.host_bytes;
   BHIPCHK(hipMalloc((void**)&batch->dSlab, batch->zs * (size_t)B));
   BHIPCHK(hipHostMalloc((void**)&batch->hSlab, batch->hzs * (size_t)B, hipHostMallocDefault));
   memset(batch->hSlab, 0, batch->hzs * (size_t)B);
@@ -1634,12 +1590,9 @@ int pcabo_batch_create(int device, int B, int max_n, int max_d, int max_q, pcabo
     pcabo_ctx* c = new (std::nothrow) pcabo_ctx();
     if (!c) return bset_err(batch, PCABO_ERR_HIP, "out of memory%s", "");
     batch->ctx[b] = c;
-    int rc = ctx_setup(c, device, max_n, max_d, max_q, batch->dSlab + batch->zs * (size_t)b,
-                       batch->hSlab + batch->hzs * (size_t)b, batch->stream);
+    int rc = ctx_setup(c, device, lay, batch->dSlab + batch->zs * (size_t)b, batch->hSlab + batch->hzs * (size_t)b, batch->stream);
     c->batch_index = b;
     if (rc != PCABO_OK) return bset_err(batch, rc, "context %s%d of the batch could not be set up", "", b);
-    if (c->region_bytes != batch->zs || c->hregion_bytes != batch->hzs)
-      return bset_err(batch, PCABO_ERR_ARG, "internal: layout mismatch%s", "");
   }
   // worker threads of the L-BFGS-B phase: one gang of runs per thread, a HIP stream per gang
   // (hardware_concurrency reports the host, not this process's share of it: a GPU of a shared node comes with ~16 cores,
@@ -1758,7 +1711,8 @@ int pcabo_batch_wpca_gp_condition_begin(pcabo_batch* batch, const double* X, con
   const int B = batch->B;
   const size_t nd = (size_t)n * d;
   // pack [X | noise | ranks | y] of every run into its pinned block; ONE strided copy carries all runs
-  const size_t off_noise = nd, off_r = noise ? 2 * nd : nd, off_y = off_r + n, total = off_y + n;
+  const InPack pk = in_pack(n, d, noise != nullptr, true, true);
+  const size_t off_noise = pk.noise, off_r = pk.ranks, off_y = pk.y, total = pk.total;
   const size_t sx = batch->in_stride_x ? batch->in_stride_x : nd, sn = batch->in_stride_noise ? batch->in_stride_noise : nd;
   const size_t sy = batch->in_stride_y ? batch->in_stride_y : (size_t)n;
   if (sx < nd || sn < nd || sy < (size_t)n)
@@ -1788,8 +1742,8 @@ int pcabo_batch_wpca_gp_condition_begin(pcabo_batch* batch, const double* X, con
   batch->vprev_d = d;
   launch_project(s, inX, c0->dDataMean, c0->dPcaMean, c0->dComps, c0->dK, n, d, c0->dZ, zb);
   const int rcount = n < d ? n : d;
-  BHIPCHK(hipMemcpy2DAsync(c0->hSmall, batch->hzs, c0->dPcaOut, batch->zs,
-                           ((size_t)3 * batch->max_d + (size_t)rcount * d) * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  BHIPCHK(hipMemcpy2DAsync(small_at(c0, small_wpca(c0->lay.s)), batch->hzs, c0->dPcaOut, batch->zs,
+                           pca_copy_count(c0->lay.s, rcount, d) * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipEventRecord(batch->evPca, s));
   // rows D-H, queued behind the projection (k is read on the device)
   return batch_enqueue_condition(batch, c0->dZ, inY, nullptr, n, d, -1, lengthscale, gp_noise, kernel);
@@ -1809,7 +1763,7 @@ int pcabo_batch_gp_condition_begin(pcabo_batch* batch, const double* Z, const do
   BHIPCHK(hipSetDevice(batch->device));
   hipStream_t s = batch->stream;
   const int B = batch->B;
-  const size_t nk = (size_t)n * k, off_y = nk, total = nk + n;
+  const size_t nk = (size_t)n * k, off_y = in_pack(n, k, false, false, true).y, total = in_pack(n, k, false, false, true).total;
   const size_t sx = batch->in_stride_x ? batch->in_stride_x : nk, sy = batch->in_stride_y ? batch->in_stride_y : (size_t)n;
   if (sx < nk || sy < (size_t)n)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_begin: an input stride is smaller than a run's block%s", "");
@@ -1818,12 +1772,13 @@ int pcabo_batch_gp_condition_begin(pcabo_batch* batch, const double* Z, const do
     memcpy(c->hIn, Z + (size_t)b * sx, nk * sizeof(double));
     memcpy(c->hIn + off_y, y + (size_t)b * sy, (size_t)n * sizeof(double));
     c->hm->k = k;
-    if (norm_bounds) memcpy(c->hSmall, norm_bounds, (size_t)2 * k * sizeof(double));
+    if (norm_bounds) memcpy(small_at(c, small_norm_bounds(c->lay.s)), norm_bounds, (size_t)2 * k * sizeof(double));
   }
   BHIPCHK(hipMemcpy2DAsync(c0->dIn, batch->zs, c0->hIn, batch->hzs, total * sizeof(double), B, hipMemcpyHostToDevice, s));
   BHIPCHK(hipMemcpy2DAsync(c0->dK, batch->zs, &c0->hm->k, batch->hzs, sizeof(int), B, hipMemcpyHostToDevice, s));
   if (norm_bounds)
-    BHIPCHK(hipMemcpy2DAsync(c0->dUserNB, batch->zs, c0->hSmall, batch->hzs, (size_t)2 * k * sizeof(double), B, hipMemcpyHostToDevice, s));
+    BHIPCHK(hipMemcpy2DAsync(c0->dUserNB, batch->zs, small_at(c0, small_norm_bounds(c0->lay.s)), batch->hzs, (size_t)2 * k * sizeof(double), B,
+                             hipMemcpyHostToDevice, s));
   if (batch->prof) (void)hipEventRecord(batch->pev[0], s);
   return batch_enqueue_condition(batch, c0->dIn, c0->dIn + off_y, norm_bounds ? c0->dUserNB : nullptr, n, k, k, lengthscale, gp_noise, kernel);
 }
@@ -1835,14 +1790,10 @@ int pcabo_batch_wpca_results(pcabo_batch* batch, double* data_mean, double* pca_
   BHIPCHK(wait_event(batch->evPca));
   BHIPCHK(hipGetLastError());
   const int n = batch->n, d = batch->d, rcount = n < d ? n : d;
-  const size_t D = batch->max_d;
   for (int b = 0; b < batch->B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
-    const double* h = c->hSmall;
-    if (data_mean) memcpy(data_mean + (size_t)b * d, h, (size_t)d * sizeof(double));
-    if (pca_mean) memcpy(pca_mean + (size_t)b * d, h + D, (size_t)d * sizeof(double));
-    if (evr) memcpy(evr + (size_t)b * d, h + 2 * D, (size_t)rcount * sizeof(double));
-    if (comps) memcpy(comps + (size_t)b * d * d, h + 3 * D, (size_t)rcount * d * sizeof(double));
+    wpca_hand_out(c, d, rcount, data_mean ? data_mean + (size_t)b * d : nullptr, pca_mean ? pca_mean + (size_t)b * d : nullptr,
+                  comps ? comps + (size_t)b * d * d : nullptr, evr ? evr + (size_t)b * d : nullptr);
     c->k = c->hm->k; c->KP = round_up(c->k, 4); c->have_wpca = true;
     if (k) k[b] = c->k;
   }
@@ -1957,10 +1908,9 @@ static int batch_mll_round(pcabo_batch* batch, bool ard, const std::vector<const
   const int rc = enqueue_rows_dh(c0, s, a, [&](int phase) -> int {
     if (phase != 4) return PCABO_OK;     // behind alpha: the likelihood kernels and the strided copy of the runs' results
     pcabo_ctx* ctx = c0;
-    const int nb = NP / PCABO_BS, tiles = nb * (nb + 1) / 2;
-    double* out = c0->dMll + (size_t)(1 + Mmax) * tiles;      // one offset for all runs, behind the widest run's tile partials
+    double* out = c0->dMll + mll_result(NP, Mmax).start;      // one place for all runs, behind the widest run's tile partials
     launch_mll_grad(s, ard, c0->dR, c0->dAT, c0->dNrm, c0->dAlpha, c0->dL, c0->dYs, n, NP, 0, c0->ld, c0->dMll, out, c0->dK, zb);
-    HIPCHK(hipMemcpy2DAsync(c0->hMll, batch->hzs, out, batch->zs, (size_t)(5 + Mmax) * sizeof(double), B, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpy2DAsync(c0->hMll, batch->hzs, out, batch->zs, mll_result(NP, Mmax).count * sizeof(double), B, hipMemcpyDeviceToHost, s));
     return PCABO_OK;
   });
   if (rc != PCABO_OK) return bset_err(batch, rc, "%s", c0->err);
@@ -2253,7 +2203,7 @@ struct PostSite {
   hipMemcpyKind in = hipMemcpyHostToDevice, out = hipMemcpyDeviceToHost;
 
   PostSite(pcabo_ctx* run0, int max_q, char** post, char** sample)      // both views: V (NPcap x max_q), cov (max_q^2) behind it
-      : c0(run0), post_slot(post), post_v((size_t)run0->NPcap * run0->max_q),
+      : c0(run0), post_slot(post), post_v((size_t)run0->lay.s.NPcap * run0->max_q),
         post_bytes(((post_v + (size_t)max_q * max_q) * sizeof(double) + 255) & ~(size_t)255), sample_slot(sample), L(max_q) {}
   explicit PostSite(pcabo_ctx* c) : PostSite(c, c->max_q, &c->dPostV, &c->dSample) {
     ctx = c; s = c->stream; device = c->device; busy = c->gp_pending; have_gp = c->have_gp; xq_cols = c->k; noise = c->noise;
@@ -2272,9 +2222,8 @@ struct PostSite {
   double* V() const { return reinterpret_cast<double*>(*post_slot); }
   double* cov(int b = 0) const { return reinterpret_cast<double*>(*post_slot + (size_t)b * post_bytes) + post_v; }
   char* blk(int b = 0) const { return *sample_slot + (size_t)b * L.bytes; }
-  // mean | variance | unfloored variance of a call with q queries: behind the q S records of the scoring in dPartial, whose
-  // capacity (max_q NPcap / 16 records) is four times what the 64-row blocks of the GEMM route ever use
-  double* post(int q) const { return c0->dPartial + (size_t)q * (m.NP / 64) * PCABO_PSTRIDE; }
+  // mean | variance | unfloored variance of a call with q queries, in dPartial behind the records of the scoring
+  double* post(int q) const { return c0->dPartial + partial_post_result(q, m.NP).start; }
 };
 #define PHIPCHK(call)                                                                                           \
   do {                                                                                                          \
@@ -2464,7 +2413,7 @@ int pcabo_gp_loo(pcabo_ctx* ctx, double* mean, double* var, double* z, double* l
   std::vector<double> own(lpd_sum && !lpd ? n : 0);      // the sum is asked for without its terms
   double* out[4] = {mean, var, z, lpd ? lpd : lpd_sum ? own.data() : nullptr};
   for (int v = 0; v < 4; ++v)
-    if (out[v]) PHIPCHK(hipMemcpyAsync(out[v], w.c0->dPartial + (size_t)v * n, n * sizeof(double), hipMemcpyDeviceToHost, w.s));
+    if (out[v]) PHIPCHK(hipMemcpyAsync(out[v], w.c0->dPartial + partial_loo_part(w.m.n, v), n * sizeof(double), hipMemcpyDeviceToHost, w.s));
   PHIPCHK(wait_stream(w.s));
   PHIPCHK(hipGetLastError());
   if (lpd_sum) *lpd_sum = loo_sum(out[3], n);
@@ -2478,18 +2427,19 @@ int pcabo_batch_gp_loo(pcabo_batch* batch, double* mean, double* var, double* z,
   if (const int rc = loo_enqueue(w, "pcabo_batch_gp_loo", mean || var || z || lpd || lpd_sum)) return rc;
   const int B = w.B;
   const size_t n = (size_t)w.m.n;
-  std::vector<double> all((size_t)B * 4 * n);
-  PHIPCHK(hipMemcpy2DAsync(all.data(), 4 * n * sizeof(double), w.c0->dPartial, w.zs, 4 * n * sizeof(double), B, hipMemcpyDeviceToHost, w.s));
+  const size_t n4 = partial_loo(w.m.n).count;
+  std::vector<double> all((size_t)B * n4);
+  PHIPCHK(hipMemcpy2DAsync(all.data(), n4 * sizeof(double), w.c0->dPartial, w.zs, n4 * sizeof(double), B, hipMemcpyDeviceToHost, w.s));
   PHIPCHK(wait_stream(w.s));
   PHIPCHK(hipGetLastError());
   double* out[4] = {mean, var, z, lpd};
   for (int b = 0; b < B; ++b) {
     if (status) status[b] = w.live(b) ? PCABO_OK : PCABO_ERR_ARG;
     if (!w.live(b)) continue;
-    const double* run = &all[(size_t)b * 4 * n];
+    const double* run = &all[(size_t)b * n4];
     for (int v = 0; v < 4; ++v)
-      if (out[v]) memcpy(out[v] + (size_t)b * n, run + (size_t)v * n, n * sizeof(double));
-    if (lpd_sum) lpd_sum[b] = loo_sum(run + 3 * n, n);
+      if (out[v]) memcpy(out[v] + (size_t)b * n, run + partial_loo_part(w.m.n, v), n * sizeof(double));
+    if (lpd_sum) lpd_sum[b] = loo_sum(run + partial_loo_part(w.m.n, 3), n);
   }
   return PCABO_OK;
 }
@@ -2565,11 +2515,11 @@ int pcabo_gp_extend(pcabo_ctx* ctx, const double* Zp, const double* yp, int p, i
       if (!std::isfinite(yp[i])) return w.fail(PCABO_ERR_ARG, "%s: a value is not finite", name);
   }
   PHIPCHK(hipSetDevice(w.device));
-  const ExtScratch e(ctx->dPartial, (size_t)ctx->NPcap);
+  const ExtScratch e(ctx->dPartial, ctx->lay.s);
   ExtHeader hdr;
   if (const int rc = ext_put_header(w, e, &hdr)) return rc;
-  const int rows_cap = (int)(((size_t)ctx->max_q * ctx->max_d + 8) / ((size_t)k + 1));      // points that fit dXq with their values
-  double* dY = yp ? ctx->dXq + (size_t)rows_cap * k : nullptr;
+  const int rows_cap = ext_rows_cap(ctx->lay.s, k);      // points that fit dXq with their values
+  double* dY = yp ? ctx->dXq + xq_ext_vals(ctx->lay.s, k).start : nullptr;
   int n = n0;
   for (int i0 = 0; i0 < p; i0 += rows_cap) {
     const int rows = std::min(rows_cap, p - i0);
@@ -2606,7 +2556,7 @@ int pcabo_gp_truncate(pcabo_ctx* ctx, int n0) {
   if (n0 < ctx->n_base || n0 > n) return w.fail(PCABO_ERR_ARG, "%s: n0 must lie in n_base .. n", name);
   if (n0 == n) return PCABO_OK;
   PHIPCHK(hipSetDevice(w.device));
-  const ExtScratch e(ctx->dPartial, (size_t)ctx->NPcap);
+  const ExtScratch e(ctx->dPartial, ctx->lay.s);
   ExtHeader hdr;
   if (const int rc = ext_put_header(w, e, &hdr)) return rc;
   if (const int rc = ext_take_back(w, e, n0, n)) return rc;
@@ -2630,13 +2580,13 @@ static int batch_run_status(const pcabo_batch* batch, int b) {
 // (value 1: device_opt_enqueue / device_opt_collect), or the host's L-BFGS-B over the same kernel's evaluation-only mode, one launch
 // per round (value 2, batch_optimize_twin: the twin the device stepping is compared with).
 
-// Does the call qualify (the kernel's size limits, room for its records in the runs' buffers, finite ordered bounds of every run
-// that takes part)?  act: those runs.  A call that does not takes the host-paced path.
+// Does the call qualify (the kernel's size limits, room for its points and records in the runs' buffers - opt_fits, ctx_layout.h -
+// finite ordered bounds of every run that takes part)?  act: those runs.  A call that does not takes the host-paced path.
 static bool device_opt_eligible(const pcabo_batch* batch, int num_restarts, int batch_limit, const double* bounds, int maxiter,
                                 std::vector<int>* act) {
-  const int MD = batch->max_d, kmax = batch_max_k(batch), ngroups = (num_restarts + batch_limit - 1) / batch_limit;
-  if (!lbfgsb_device_possible(batch->NP, kmax, batch_limit) || maxiter < 1 || batch->max_q < 64 + 8 * ngroups ||
-      (size_t)(num_restarts + 2) * kmax > (size_t)batch->max_q * MD)
+  const int MD = batch->max_d, kmax = batch_max_k(batch);
+  if (!lbfgsb_device_possible(batch->NP, kmax, batch_limit) || maxiter < 1 ||
+      !opt_fits(batch->ctx[0]->lay, num_restarts, opt_groups(num_restarts, batch_limit), kmax))
     return false;
   act->clear();
   for (int b = 0; b < batch->B; ++b) {
@@ -2652,10 +2602,10 @@ static bool device_opt_eligible(const pcabo_batch* batch, int num_restarts, int 
 
 // One launch of k_lbfgsb_group over the first nent entries of the pinned table, enqueued on the batch's stream: the transposed root
 // inverse of the table's runs where a later conditioning outdated it, the table, the runs' points ([num_restarts x k | lower k |
-// upper k], strided over the runs), the kernel, and back val_doubles values / records and the num_restarts candidates or gradients
-// of every run.  The caller waits for the stream.
+// upper k], strided over the runs), the kernel, and back the head of dVal up to the end of `back` (the values, or the values and
+// the groups' records) and the num_restarts candidates or gradients of every run.  The caller waits for the stream.
 static int device_opt_launch(pcabo_batch* batch, int nent, int mode, int num_restarts, int batch_limit, int maxiter, int maximize,
-                             int acq, size_t val_doubles) {
+                             int acq, Use back) {
   pcabo_ctx* c0 = batch->ctx[0];
   hipStream_t s = batch->stream;
   const int B = batch->B, kmax = batch_max_k(batch);
@@ -2664,13 +2614,13 @@ static int device_opt_launch(pcabo_batch* batch, int nent, int mode, int num_res
     if (c->rt_stale) { launch_rt_build(s, c->dR, c->n, c->NP, c->ld, c->dGram); c->rt_stale = false; }
   }
   BHIPCHK(hipMemcpyAsync(batch->dOptTab, batch->hOptTab, (size_t)nent * sizeof(unsigned), hipMemcpyHostToDevice, s));
-  BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, c0->hXq, batch->hzs, (size_t)(num_restarts + 2) * kmax * sizeof(double), B, hipMemcpyHostToDevice, s));
+  BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, c0->hXq, batch->hzs, xq_opt_points(num_restarts, kmax).count * sizeof(double), B, hipMemcpyHostToDevice, s));
   if (launch_lbfgsb_group(s, batch->dOptTab, nent, mode, num_restarts, maxiter, gp_model(batch, kmax), c0->dXq, c0->dGram, c0->dBestF,
                           c0->dK, 1.0 / batch->lengthscale, maximize ? 1 : 0, acq, batch->kernel, c0->dGrad, c0->dVal, batch->zs,
                           batch_hyp(batch), batch_limit) != 0)
     return bset_err(batch, PCABO_ERR_HIP, "the device-resident optimiser could not be launched%s", "");
-  BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, val_doubles * sizeof(double), B, hipMemcpyDeviceToHost, s));
-  BHIPCHK(hipMemcpy2DAsync(c0->hGrad, batch->hzs, c0->dGrad, batch->zs, (size_t)num_restarts * kmax * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (back.start + back.count) * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  BHIPCHK(hipMemcpy2DAsync(c0->hGrad, batch->hzs, c0->dGrad, batch->zs, grad_opt_cands(num_restarts, kmax).count * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipGetLastError());
   return PCABO_OK;
 }
@@ -2678,7 +2628,7 @@ static int device_opt_launch(pcabo_batch* batch, int nent, int mode, int num_res
 // Device mode, first half: the launch table, the runs' starts and bounds, the one launch; the call's shape is kept for _collect.
 static int device_opt_enqueue(pcabo_batch* batch, const std::vector<int>& act, const double* ics, int num_restarts, int batch_limit,
                               const double* bounds, int maxiter, int maximize, int acq) {
-  const int MD = batch->max_d, ngroups = (num_restarts + batch_limit - 1) / batch_limit;
+  const int MD = batch->max_d, ngroups = opt_groups(num_restarts, batch_limit);
   int nent = 0;
   for (size_t blk = 0; blk < act.size(); blk += 8)          // both groups of a run on one XCD (work-groups go round the 8 XCDs)
     for (int gi = 0; gi < ngroups; ++gi)
@@ -2693,7 +2643,7 @@ static int device_opt_enqueue(pcabo_batch* batch, const std::vector<int>& act, c
     memcpy(c->hXq + (size_t)num_restarts * k, bounds + (size_t)b * 2 * MD, (size_t)2 * k * sizeof(double));
   }
   if (nent > 0)
-    if (const int rc = device_opt_launch(batch, nent, 1, num_restarts, batch_limit, maxiter, maximize, acq, (size_t)(64 + 8 * ngroups))) return rc;
+    if (const int rc = device_opt_launch(batch, nent, 1, num_restarts, batch_limit, maxiter, maximize, acq, val_opt_records(ngroups))) return rc;
   batch->opt_act = act; batch->opt_restarts = num_restarts; batch->opt_limit = batch_limit; batch->opt_enqueued = true;
   return PCABO_OK;
 }
@@ -2703,7 +2653,7 @@ static int device_opt_collect(pcabo_batch* batch, int num_restarts, int batch_li
                               int* status) {
   if (!batch->opt_enqueued || batch->opt_restarts != num_restarts || batch->opt_limit != batch_limit)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_end: no matching _begin before it%s", "");
-  const int B = batch->B, MD = batch->max_d, ngroups = (num_restarts + batch_limit - 1) / batch_limit;
+  const int B = batch->B, MD = batch->max_d, ngroups = opt_groups(num_restarts, batch_limit);
   std::vector<int> run_status(B);
   for (int b = 0; b < B; ++b) run_status[b] = batch_run_status(batch, b);
   batch->opt_enqueued = false;
@@ -2715,9 +2665,9 @@ static int device_opt_collect(pcabo_batch* batch, int num_restarts, int batch_li
     const pcabo_ctx* c = batch->ctx[b];
     const int k = c->k;
     int any_failed = 0;
-    std::copy(c->hVal + 64, c->hVal + 64 + 8 * ngroups, batch->dbg_group_out.begin() + (size_t)b * ngroups * 8);
+    std::copy(c->hVal + val_opt_record(0), c->hVal + val_opt_record(ngroups), batch->dbg_group_out.begin() + (size_t)b * ngroups * 8);
     for (int gi = 0; gi < ngroups; ++gi) {
-      const double* o = c->hVal + 64 + 8 * gi;
+      const double* o = c->hVal + val_opt_record(gi);
       if (info) { int* io = info + ((size_t)b * ngroups + gi) * 4; io[0] = (int)o[0]; io[1] = (int)o[1]; io[2] = (int)o[2]; io[3] = (int)o[3]; }
       if ((int)o[2] == 2) any_failed = 1;
       if ((int)o[4] != 0) run_status[b] = (int)o[4];
@@ -2739,7 +2689,7 @@ static int device_opt_collect(pcabo_batch* batch, int num_restarts, int batch_li
 static int batch_optimize_twin(pcabo_batch* batch, const std::vector<int>& act, const double* ics, int num_restarts, int batch_limit,
                                const double* bounds, int maxiter, int maximize, int acq, double* cand, double* vals, int* info,
                                int* failed, int* status) {
-  const int B = batch->B, MD = batch->max_d, ngroups = (num_restarts + batch_limit - 1) / batch_limit;
+  const int B = batch->B, MD = batch->max_d, ngroups = opt_groups(num_restarts, batch_limit);
   std::vector<RunRestarts> runs(B);
   for (int b = 0; b < B; ++b) runs[b].status = batch_run_status(batch, b);
   for (int b : act) {
@@ -2752,7 +2702,7 @@ static int batch_optimize_twin(pcabo_batch* batch, const std::vector<int>& act, 
   auto stage = [&](int b, const RestartGroup& rg) { batch->hOptTab[nent++] = group_entry(b, rg.q0, rg.nq); };
   auto eval = [&]() -> int {
     const int n = nent; nent = 0;
-    if (const int rc = device_opt_launch(batch, n, 0, num_restarts, batch_limit, maxiter, maximize, acq, (size_t)(64 + 8 * ngroups))) return rc;
+    if (const int rc = device_opt_launch(batch, n, 0, num_restarts, batch_limit, maxiter, maximize, acq, val_opt_records(ngroups))) return rc;
     BHIPCHK(wait_stream(batch->stream));
     BHIPCHK(hipGetLastError());
     return PCABO_OK;
@@ -2815,7 +2765,7 @@ extern "C" int pcabo_debug_batch_lbfgsb_device_out(pcabo_batch* batch, double* o
 static int batch_optimize_host(pcabo_batch* batch, const double* ics, int num_restarts, int batch_limit, const double* bounds,
                                int maxiter, int maximize, int acq, double* cand, double* vals, int* info, int* failed, int* status) {
   const int B = batch->B, MD = batch->max_d, kmax = batch_max_k(batch), G = batch->G;
-  const int ngroups = (num_restarts + batch_limit - 1) / batch_limit;
+  const int ngroups = opt_groups(num_restarts, batch_limit);
   BHIPCHK(hipStreamSynchronize(batch->stream));
   pcabo_ctx* c0 = batch->ctx[0];
   const GpModel gm = gp_model(batch, kmax);
@@ -2849,7 +2799,7 @@ static int batch_optimize_host(pcabo_batch* batch, const double* ics, int num_re
       const int n = nent;
       nent = 0;
       if (groups) {
-        if (launch_acq_group(st, &tab, n, c0->hXq, gm, p, c0->dPartial, c0->dCounters + PCABO_GROUP_CNT_OFFSET, c0->dVal, c0->dGrad,
+        if (launch_acq_group(st, &tab, n, c0->hXq, gm, p, c0->dPartial, c0->dCounters + counters_group().start, c0->dVal, c0->dGrad,
                              c0->hVal, c0->hGrad, c0->hm, seq, batch_ab(batch, 1, 1)) != 0)
           return false;                              // nothing was launched: no flags to wait for
       } else {
@@ -2967,7 +2917,7 @@ int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, con
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: a _begin call of this batch has not been ended%s", "");
   BHIPCHK(hipSetDevice(batch->device));
   const int MD = batch->max_d;
-  if (!lbfgsb_device_possible(batch->NP, batch_max_k(batch), PCABO_GROUP_Q) || batch->max_q < 64)
+  if (!lbfgsb_device_possible(batch->NP, batch_max_k(batch), PCABO_GROUP_Q) || !opt_fits(batch->ctx[0]->lay, q, 0, batch_max_k(batch)))
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: shape beyond the device optimiser (n <= 512, k <= 40)%s", "");
   if (const int rc = batch_put_best_f(batch, best_f)) return rc;
   std::vector<int> runs;
@@ -2980,7 +2930,7 @@ int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, con
       batch->hOptTab[nent++] = group_entry(b, q0, std::min(PCABO_GROUP_Q, q - q0));
   }
   if (nent == 0) return PCABO_OK;
-  if (const int rc = device_opt_launch(batch, nent, 0, q, PCABO_GROUP_Q, 1, maximize, acq, (size_t)q)) return rc;
+  if (const int rc = device_opt_launch(batch, nent, 0, q, PCABO_GROUP_Q, 1, maximize, acq, val_opt_values(q))) return rc;
   BHIPCHK(wait_stream(batch->stream));
   BHIPCHK(hipGetLastError());
   for (int b : runs) {
@@ -3002,7 +2952,7 @@ static int batch_inverse_map_enqueue(pcabo_batch* batch, const double* z, bool x
   for (int b = 0; b < B; ++b) memcpy(batch->ctx[b]->hXq, z + (size_t)b * MD, (size_t)batch->ctx[b]->k * sizeof(double));
   BHIPCHK(hipMemcpy2DAsync(c0->dZq, batch->zs, c0->hXq, batch->hzs, (size_t)MD * sizeof(double), B, hipMemcpyHostToDevice, s));
   launch_inverse_map(s, c0->dZq, c0->dComps, c0->dDataMean, c0->dPcaMean, 0, d, c0->dXout, c0->dK, batch_zb(batch));
-  BHIPCHK(hipMemcpy2DAsync(c0->hSmall, batch->hzs, c0->dXout, batch->zs, (size_t)d * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  BHIPCHK(hipMemcpy2DAsync(small_at(c0, small_imap_x(c0->lay.s)), batch->hzs, c0->dXout, batch->zs, (size_t)d * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipGetLastError());
   batch->imap_enqueued = true;
   return PCABO_OK;
@@ -3015,7 +2965,7 @@ static int batch_inverse_map_collect(pcabo_batch* batch, double* x) {
   BHIPCHK(wait_stream(batch->stream));
   BHIPCHK(hipGetLastError());
   const int d = batch->d;
-  for (int b = 0; b < batch->B; ++b) memcpy(x + (size_t)b * d, batch->ctx[b]->hSmall, (size_t)d * sizeof(double));
+  for (int b = 0; b < batch->B; ++b) memcpy(x + (size_t)b * d, small_at(batch->ctx[b], small_imap_x(batch->ctx[b]->lay.s)), (size_t)d * sizeof(double));
   return PCABO_OK;
 }
 int pcabo_batch_inverse_map(pcabo_batch* batch, const double* z, double* x) {

@@ -3,17 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "ctx_layout.h"      // the sizes, HostMirror, round_up and where everything lies in a context's memory (no HIP in there)
 
-#define PCABO_BS 64          // tile edge of the Gram / Cholesky / root-inverse kernels
-#define PCABO_SLAB 16        // rows of R handled by one acquisition work-group
-#define PCABO_MAXD 128       // largest ambient / reduced dimension supported
 #define PCABO_TLD 66         // LDS leading dimension (doubles) of a 64x64 tile: conflict-free ds_read_b64
-#define PCABO_PSTRIDE (2 + 2 * PCABO_MAXD)   // doubles per (query, slab) partial record of the acquisition kernels: |v|^2, mu_s, two gradient parts
-
-#define PCABO_QA_MAX 416      // query coordinates that travel as kernel arguments (3.25 KB; 10 restarts x 40 dims = 400 fit).  With 448 the
-                              // kernarg segment of k_acq_fast was exactly HIP's 4096-byte maximum; 416 leaves 256 bytes of head room
-#define PCABO_CNT_DONE 0x3fff // capacity of the per-query ticket array
 #define PCABO_INLAUNCH_MAXQ 32 // largest batch finished inside the launch (results + flags straight to the host)
+static_assert(PCABO_INLAUNCH_MAXQ == PCABO_QFLAG_WORDS, "one sequence word of the host mirror per query finished inside a launch");
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 struct QueryArgs { double x[PCABO_QA_MAX]; };
@@ -49,8 +43,6 @@ __device__ inline double fast_rsq(double x) {
 }
 #endif
 
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 // Model / problem constants handed to the acquisition kernels by value.
 struct AcqParams {
   double best_f;        // already rounded like torch.as_tensor(float) does; PCABO_ACQ_UCB: the slot carries kappa = sqrt(beta)
@@ -76,17 +68,6 @@ struct AcqBatch {
                                    //    (32-bit entries: run << 16 | query of that run); 0: run = blockIdx.z
   int xq_host = 0;                 // 1: Xq is a pinned HOST pointer (stride hzs), read by the kernel over PCIe
   const double* hyp = nullptr;     // run 0's hyperparameter block (PCABO_HYP_*) after a lock-step fit (null: prm.inv_ls)
-};
-
-// Small results the host needs after a device phase; lives in pinned host memory.
-struct HostMirror {
-  int k;                 // reduced dimension chosen by the wPCA
-  int chol_info;         // 0 or 1 + index of the failing pivot
-  int pad0, pad1;
-  double y_mean, y_std;
-  double norm_lo[PCABO_MAXD], norm_hi[PCABO_MAXD];
-  double acq_lo[PCABO_MAXD], acq_hi[PCABO_MAXD];
-  volatile unsigned long long qflag[PCABO_INLAUNCH_MAXQ];   // per query: sequence number written after its results
 };
 
 // ---- launchers (defined in kernels_*.hip); all asynchronous on `s` -------------------
@@ -341,11 +322,7 @@ void launch_rank(hipStream_t s, const double* f, int n, int maximize, long long*
 // hyp: run 0's hyperparameter block, set once the runs of a batch carry their own fitted model (pcabo_batch_gp_fit): k_zstats,
 // k_znorm and k_gram then read the mean constant, 1 / lengthscale and the noise of THEIR run from it instead of the scalar
 // argument.  The host writes the very doubles the single-context path passes by value (1.0 / softplus(rho) is formed there).
-#define PCABO_HYP_INV_LS 0
-#define PCABO_HYP_NOISE 1
-#define PCABO_HYP_MEAN_C 2
-#define PCABO_HYP_ARD_FOLD 3              // != 0: k_zstats folds this run's ARD lengthscales (read only where ard_ls is given)
-#define PCABO_HYP_WORDS 4
+// (the words of a block: PCABO_HYP_* in ctx_layout.h)
 struct ZB { int B = 1; size_t zs = 0, hzs = 0; const double* hyp = nullptr; };
 void launch_wpca_prep(hipStream_t s, const double* X, const long long* ranks, const double* noise, int n, int d,
                       int DP, double* weights, double* data_mean, double* pca_mean, double* Wc, ZB zb = ZB());
@@ -400,7 +377,6 @@ void launch_acq(hipStream_t s, const QueryArgs* qa, const double* Xq, int q, con
 // throughput variant: one work-group per (restart group of <= 5 queries, 64-row slab); `tab` holds `entries` 32-bit words
 // run << 16 | first query << 8 | count (see k_acq_group)
 #define PCABO_GROUP_Q 5
-#define PCABO_GROUP_CNT_OFFSET 8192      // its tickets live in the upper half of the counter array (other slab count)
 bool acq_group_possible(int NP, int k);
 int launch_acq_group(hipStream_t st, const QueryArgs* tab, int entries, const double* Xq, const GpModel& m, AcqParams p,
                      double* partial, unsigned int* counters, double* val, double* grad, double* host_val, double* host_grad,
@@ -437,21 +413,7 @@ void launch_post_sample(hipStream_t st, const double* F, int q, const double* ba
 void launch_loo(hipStream_t st, const double* R, const double* alpha, const double* ys, const double* ystats, int n, int ld,
                 double* out, size_t zs = 0, int B = 1);
 // Appending points to a conditioned GP and taking them back (kernels_ext.hip).  The scratch of a run lies at the head of its
-// dPartial, which every evaluation writes before it reads: ks | v | w (N = NPcap doubles each) | small.  small holds the normalised
-// point, its standardised value, the rung and the info word (the header, written by the host before the first launch with info 0;
-// the kernels set 1 + index of the point whose pivot failed) and the believer mean's partial sums, one per 256 points.
-#define EXT_XN 0
-#define EXT_YS PCABO_MAXD
-#define EXT_HDR_RUNG (PCABO_MAXD + 1)
-#define EXT_HDR_INFO (PCABO_MAXD + 2)
-#define EXT_HDR 2                          // doubles of the header: rung, info word (an int in the second double)
-#define EXT_MU (PCABO_MAXD + 3)
-#define EXT_MU_MAX 64                      // partial sums: n <= 16384
-#define EXT_SMALL (EXT_MU + EXT_MU_MAX)
-struct ExtScratch {
-  double *ks, *v, *w, *small;
-  ExtScratch(double* partial, size_t N) : ks(partial), v(partial + N), w(partial + 2 * N), small(partial + 3 * N) {}
-};
+// dPartial, which every evaluation writes before it reads (ExtScratch and the EXT_* words of its small block: ctx_layout.h).
 // m: the model BEFORE the point (n, NP); X / Y: the staged points and values of the call, row xi / entry yi this one's (Y null:
 // believer mode, the value is the model's mean there).  launch_alpha(R, e.ks, n, NP, ld, e.v, e.w) goes between the two.
 void launch_ext_ks(hipStream_t st, const double* X, int xi, const double* Y, int yi, const GpModel& m, double inv_ls, int kernel,
@@ -472,7 +434,7 @@ void launch_inverse_map(hipStream_t s, const double* z, const double* comps, con
 // Device-resident L-BFGS-B of a batch's restart groups (kernels_lbfgsb.hip): RT = transposed root inverse (zeros above the
 // diagonal and beyond n), then one work-group per table entry (run << 16 | first query << 8 | count).  mode 1: optimise from the
 // initial conditions in Xq ([num_restarts x k | lower k | upper k] per run), candidates to out_x, values / counters to out_v (the
-// eight counters of the group that starts at restart gi batch_limit at out_v + 64 + 8 gi);
+// eight counters of the group that starts at restart gi batch_limit at out_v + PCABO_OPT_REC_BASE + PCABO_OPT_REC_STRIDE gi);
 // mode 0: one value+gradient evaluation at the points in Xq.  Returns 0, or -1 when the launch could not be set up.
 void launch_rt_build(hipStream_t s, const double* R, int n, int NP, int ld, double* RT, ZB zb = ZB());
 bool lbfgsb_device_possible(int NP, int kmax, int batch_limit);

@@ -394,3 +394,32 @@ def test_experiment_runner_batches_vanilla_too(native, tmp_path):
         rel = os.path.join("vanilla-experiment", f"data_f{fid}_{name}", f"IOHprofiler_f{fid}_DIM5.dat")
         a, b = open(os.path.join(outs[0][0], rel)).read(), open(os.path.join(outs[1][0], rel)).read()
         assert a == b
+
+
+def test_wpca_results_are_the_same_after_the_inverse_map(native):
+    """A run's pinned small block holds the wPCA results, the inverse map's x and a batch's Normalize bounds in three slots of
+    their own (csrc/ctx_layout.h): pcabo_batch_wpca_results after pcabo_batch_inverse_map hands out what it handed out before
+    it - the batch's x used to land on data_mean - and x is what the single-context call on the run gives, bit for bit."""
+    rng = np.random.default_rng(33)
+    B, n, d, q = 2, 8, 3, 4
+    X = rng.uniform(-5, 5, (B, n, d))
+    y = rng.normal(size=(B, n)) * 50 + 300
+    ranks = np.argsort(np.argsort(y, axis=1), axis=1) + 1
+    noise = rng.normal(0, 1e-8, (B, n, d))
+    bt = native.Batch(B, max_n=16, max_d=d, max_q=16)
+    bt.wpca_gp_condition_begin(X, ranks, noise, y)
+    first = bt.wpca_results()
+    boxes = bt.acq_bounds()
+    raw = [boxes[b][0] + (boxes[b][1] - boxes[b][0]) * rng.uniform(size=(q, first[b]["k"])) for b in range(B)]
+    _, status = bt.gp_wait_eval(raw, [float(y[b].min()) for b in range(B)])
+    assert not status.any()
+    z = [raw[b][0] for b in range(B)]
+    x = bt.inverse_map(z)
+    again = bt.wpca_results()
+    for b in range(B):
+        assert x[b].tobytes() != first[b]["data_mean"].tobytes()      # (or the call before could not tell the two apart)
+        assert again[b]["k"] == first[b]["k"]
+        for key in ("data_mean", "pca_mean", "components", "evr"):
+            assert again[b][key].tobytes() == first[b][key].tobytes(), (b, key)
+        assert bt.ctx[b].inverse_map(z[b]).tobytes() == x[b].tobytes(), b
+    bt.close()
