@@ -17,6 +17,7 @@
 #include "host_side.h"
 #include "lb_plan.h"
 #include "ctx_layout.h"
+#include "model_state.h"
 
 #include <atomic>
 #include <cmath>
@@ -1063,6 +1064,220 @@ void test_ctx_layout() {
   }
 }
 
+// The call state (model_state.h): a record is driven through the legal call sequences of a BO iteration, for a context and for a
+// batch with three member runs, and after every step EVERY field is compared with values written out here - what the assignment
+// sites of pcabo_api.hip left before the record existed - and every question with a table that restates the call-order rules of
+// include/pcabo.h.  The slab count is the launcher's (acq_slabs: NP / 16 at these sizes), handed in as pcabo_api.hip hands it in.
+struct MS {      // a ModelState written out, in the order of its declaration
+  int n, n_base, d, k, KP, NP; double ls, s2; int kernel; double rung;
+  bool have_wpca, unc; int wn, wd; bool pending, have_gp, zn, rt; int cnt_S; bool dirty; int gcur, vprev_d;
+};
+void expect_state(const ModelState& s, const MS& e, const char* what) {
+  CHECK(s.n == e.n && s.n_base == e.n_base && s.d == e.d && s.k == e.k && s.KP == e.KP && s.NP == e.NP,
+        "%s: shape n %d n_base %d d %d k %d KP %d NP %d", what, s.n, s.n_base, s.d, s.k, s.KP, s.NP);
+  CHECK(s.lengthscale == e.ls && s.noise == e.s2 && s.kernel == e.kernel && s.rung == e.rung,
+        "%s: hyperparameters %g %g %d rung %g", what, s.lengthscale, s.noise, s.kernel, s.rung);
+  CHECK(s.have_wpca == e.have_wpca && s.wpca_uncollected == e.unc && s.wpca_n == e.wn && s.wpca_d == e.wd,
+        "%s: wPCA phase %d %d (%d x %d)", what, s.have_wpca, s.wpca_uncollected, s.wpca_n, s.wpca_d);
+  CHECK(s.gp_pending == e.pending && s.have_gp == e.have_gp && s.zn_recorded == e.zn && s.rt_stale == e.rt,
+        "%s: GP phase pending %d have_gp %d zn %d rt_stale %d", what, s.gp_pending, s.have_gp, s.zn_recorded, s.rt_stale);
+  CHECK(s.cnt_S == e.cnt_S && s.cnt_dirty == e.dirty && s.gcur == e.gcur && s.vprev_d == e.vprev_d,
+        "%s: tickets %d %d, ping-pong %d %d", what, s.cnt_S, s.cnt_dirty, s.gcur, s.vprev_d);
+}
+// the questions of a context's entry points: pcabo_wpca / _begin refuse while in flight, pcabo_gp_condition_end(_eval) need one in
+// flight, the calls on the conditioned model need GP_READY, Z == NULL needs the wPCA of these very (n, k), and the tickets
+struct MQ { bool in_flight; GpReady ready; bool wpca_known, z_null_3_1, z_null_64_5, reset_4, reset_8; };
+void expect_answers(const ModelState& s, const MQ& e, const char* what) {
+  CHECK(s.in_flight() == e.in_flight && s.gp_ready() == e.ready && s.conditioned() == (e.ready == GP_READY) && s.wpca_known() == e.wpca_known, "%s: in flight %d ready %d wPCA known %d",
+        what, s.in_flight(), (int)s.gp_ready(), s.wpca_known());
+  CHECK(s.wpca_matches(3, 1) == e.z_null_3_1 && s.wpca_matches(64, 5) == e.z_null_64_5 && !s.wpca_matches(3, 2) && !s.wpca_matches(65, 1),
+        "%s: Z == NULL allowed for (3, 1): %d, (64, 5): %d", what, s.wpca_matches(3, 1), s.wpca_matches(64, 5));
+  CHECK(s.tickets_need_reset(4) == e.reset_4 && s.tickets_need_reset(8) == e.reset_8, "%s: tickets need a reset for 4 slabs %d, 8 slabs %d",
+        what, s.tickets_need_reset(4), s.tickets_need_reset(8));
+}
+
+void test_model_state() {
+  const auto slabs = [](int NP) { return NP / 16; };
+  const double LS = 0.75, S2 = 1e-3; const int KN = PCABO_KERNEL_MATERN52;
+  const bool T = true, F = false;
+  {  // ---- a context ----
+    ModelState s;
+    expect_state(s, {0, 0, 0, 0, 0, 0, 0.0, 0.0, 0, 0.0, F, F, 0, 0, F, F, F, F, 0, T, 0, 0}, "a new context");
+    expect_answers(s, {F, GP_NONE, F, F, F, T, T}, "a new context");
+    // pcabo_wpca (n = 3, d = 2, k = 1), then pcabo_gp_condition_begin with k known, pcabo_gp_condition_end on rung 0
+    CHECK(!s.warm_start(2), "no eigenvectors to start from yet");
+    s.wpca_enqueued(3, 2); s.points_replaced(3);
+    expect_state(s, {3, 0, 0, 0, 0, 0, 0.0, 0.0, 0, 0.0, F, F, 3, 2, F, F, F, F, 0, T, 1, 2}, "wPCA enqueued");
+    expect_answers(s, {F, GP_NONE, F, F, F, T, T}, "wPCA enqueued");
+    s.wpca_collected(1);
+    expect_state(s, {3, 0, 2, 1, 4, 0, 0.0, 0.0, 0, 0.0, T, F, 3, 2, F, F, F, F, 0, T, 1, 2}, "wPCA collected");
+    expect_answers(s, {F, GP_NONE, T, T, F, T, T}, "wPCA collected");
+    s.condition_enqueued(3, 1, LS, S2, KN, true);
+    CHECK(s.tickets_reset_if_needed(slabs(s.NP)), "the first conditioning resets the tickets");
+    expect_state(s, {3, 3, 2, 1, 4, 64, LS, S2, KN, 0.0, T, F, 3, 2, T, F, T, F, 4, F, 1, 2}, "conditioning enqueued (k known)");
+    expect_answers(s, {T, GP_IN_FLIGHT, T, T, F, F, T}, "conditioning enqueued (k known)");
+    s.condition_ended_ok(0.0);
+    expect_state(s, {3, 3, 2, 1, 4, 64, LS, S2, KN, 0.0, T, F, 3, 2, F, T, T, F, 4, F, 1, 2}, "conditioning ended on rung 0");
+    expect_answers(s, {F, GP_READY, T, T, F, F, T}, "conditioning ended on rung 0");
+    // pcabo_wpca_gp_condition_begin (n = 64, k on the device), pcabo_wpca_results (k = 5), pcabo_gp_condition_end_eval on 1e-7
+    CHECK(s.warm_start(2) && !s.warm_start(3), "the previous eigenvectors serve a wPCA of the same d only");
+    s.wpca_enqueued(64, 2);
+    s.condition_enqueued(64, -1, LS, S2, KN, true);
+    CHECK(!s.tickets_reset_if_needed(slabs(s.NP)), "n = 64 has the slab count of n = 3: no reset");
+    expect_state(s, {64, 64, 2, 1, 4, 64, LS, S2, KN, 0.0, T, T, 64, 2, T, F, T, F, 4, F, 0, 2}, "conditioning enqueued (k on the device)");
+    expect_answers(s, {T, GP_IN_FLIGHT, T, F, F, F, T}, "conditioning enqueued (k on the device)");
+    s.wpca_collected(5);
+    expect_state(s, {64, 64, 2, 5, 8, 64, LS, S2, KN, 0.0, T, F, 64, 2, T, F, T, F, 4, F, 0, 2}, "wPCA results behind the conditioning");
+    expect_answers(s, {T, GP_IN_FLIGHT, T, F, T, F, T}, "wPCA results behind the conditioning");
+    ModelState failed = s, plain = s;
+    CHECK(s.zn_consumed() && !s.zn_consumed(), "the event behind k_znorm is taken once");
+    s.condition_ended_ok(1e-7);                        // (the jitter redo of pcabo_gp_condition_end_eval ends through pcabo_gp_condition_end)
+    expect_state(s, {64, 64, 2, 5, 8, 64, LS, S2, KN, 1e-7, T, F, 64, 2, F, T, F, F, 4, F, 0, 2}, "conditioning ended on rung 1e-7");
+    expect_answers(s, {F, GP_READY, T, F, T, F, T}, "conditioning ended on rung 1e-7");
+    failed.condition_failed();
+    expect_state(failed, {64, 64, 2, 5, 8, 64, LS, S2, KN, 0.0, T, F, 64, 2, F, F, T, F, 4, F, 0, 2}, "conditioning failed");
+    expect_answers(failed, {F, GP_NONE, T, F, T, F, T}, "conditioning failed");
+    (void)plain.zn_consumed(); plain.condition_ended_ok(0.0);      // pcabo_gp_condition_end_eval without a redo
+    expect_state(plain, {64, 64, 2, 5, 8, 64, LS, S2, KN, 0.0, T, F, 64, 2, F, T, F, F, 4, F, 0, 2}, "end_eval without a jitter redo");
+    expect_answers(plain, {F, GP_READY, T, F, T, F, T}, "end_eval without a jitter redo");
+    // one evaluation of a fit (pcabo_gp_mll): the conditioning at theta, ended inside the call
+    s.condition_enqueued(64, 5, 1.0, 0.02, KN, true);
+    CHECK(!s.tickets_reset_if_needed(slabs(s.NP)), "a fit evaluation at the same n: no reset");
+    s.condition_ended_ok(1e-8);
+    expect_state(s, {64, 64, 2, 5, 8, 64, 1.0, 0.02, KN, 1e-8, T, F, 64, 2, F, T, T, F, 4, F, 0, 2}, "fit evaluation");
+    expect_answers(s, {F, GP_READY, T, F, T, F, T}, "fit evaluation");
+    // pcabo_get_gram, then the device optimiser's rebuild; the option switched on behind a conditioning
+    s.gram_fetched();
+    expect_state(s, {64, 64, 2, 5, 8, 64, 1.0, 0.02, KN, 1e-8, T, F, 64, 2, F, T, T, T, 4, F, 0, 2}, "Gram fetched");
+    expect_answers(s, {F, GP_READY, T, F, T, F, T}, "Gram fetched");
+    s.rt_rebuilt(); CHECK(!s.rt_stale, "rebuilt: fresh");
+    s.rt_wanted(); CHECK(s.rt_stale, "the device optimiser switched on behind a conditioning: stale");
+    s.rt_rebuilt(); failed.rt_wanted(); CHECK(!failed.rt_stale, "no GP: nothing to rebuild");
+    // pcabo_gp_extend across NP (64 -> 65) and pcabo_gp_truncate back: n_base held, the tickets follow the slab count
+    s.n_changed(65);
+    CHECK(s.tickets_reset_if_needed(slabs(s.NP)), "65 points: 8 slab groups, the tickets are reset");
+    expect_state(s, {65, 64, 2, 5, 8, 128, 1.0, 0.02, KN, 1e-8, T, F, 64, 2, F, T, T, T, 8, F, 0, 2}, "extended to 65");
+    expect_answers(s, {F, GP_READY, T, F, F, T, F}, "extended to 65");
+    s.n_changed(64);
+    CHECK(s.tickets_reset_if_needed(slabs(s.NP)), "back to 64 points: 4 slab groups again");
+    expect_state(s, {64, 64, 2, 5, 8, 64, 1.0, 0.02, KN, 1e-8, T, F, 64, 2, F, T, T, T, 4, F, 0, 2}, "truncated to 64");
+    expect_answers(s, {F, GP_READY, T, F, T, F, T}, "truncated to 64");
+    // a second conditioning with another n; a launch that may have died
+    s.wpca_enqueued(65, 2);
+    s.condition_enqueued(65, -1, LS, S2, KN, false);
+    CHECK(s.tickets_reset_if_needed(slabs(s.NP)), "conditioning at n = 65: reset");
+    expect_state(s, {65, 65, 2, 5, 8, 128, LS, S2, KN, 0.0, T, T, 65, 2, T, F, F, T, 8, F, 1, 2}, "second conditioning");
+    expect_answers(s, {T, GP_IN_FLIGHT, T, F, F, T, F}, "second conditioning");
+    s.launch_may_have_died();
+    expect_answers(s, {T, GP_IN_FLIGHT, T, F, F, T, T}, "a launch may have died: a reset is due at the same slab count");
+    CHECK(s.tickets_reset_if_needed(8) && !s.tickets_need_reset(8) && !s.cnt_dirty, "the reset clears the mark");
+  }
+  {  // ---- a batch of three runs: k = 1, 5, 5; run 1 fails its factorisation, run 2 ends on a jitter rung ----
+    BatchState b;
+    ModelState r[3];
+    const std::vector<ModelState*> runs = {&r[0], &r[1], &r[2]};
+    const int ks[3] = {1, 5, 5};
+    const auto expect_batch = [&](const MS& e, bool fitted, bool score, bool imap, bool opt, GpReady ready, bool scorable, bool on_host, const char* what) {
+      expect_state(b.m, e, what);
+      CHECK(b.fitted == fitted && b.score_enqueued == score && b.imap_enqueued == imap && b.opt_enqueued == opt, "%s: pending halves", what);
+      CHECK(b.begin_pending() == (score || imap || opt) && b.gp_ready() == ready && b.scorable() == scorable && b.wpca_on_host() == on_host &&
+            b.anything_enqueued() == (e.n != 0 || e.unc), "%s: the batch's answers", what);
+    };
+    expect_batch({0, 0, 0, 0, 0, 0, 0.0, 0.0, 0, 0.0, F, F, 0, 0, F, F, F, F, 0, T, 0, 0}, F, F, F, F, GP_NONE, F, F, "a new batch");
+    // pcabo_batch_wpca_gp_condition_begin, n = 3, d = 2
+    b.m.wpca_enqueued(3, 2);
+    CHECK(b.tickets_reset_if_needed(slabs(64), runs), "the first conditioning resets every run's tickets");
+    b.condition_enqueued(3, 2, -1, LS, S2, KN);
+    for (int i = 0; i < 3; ++i) r[i].follow(b, r[i].own().with_k(r[i].k).started(LS, S2));
+    expect_batch({3, 3, 2, 0, 0, 64, LS, S2, KN, 0.0, F, T, 3, 2, T, F, F, F, 4, F, 1, 2}, F, F, F, F, GP_IN_FLIGHT, T, F, "batch conditioning enqueued");
+    for (int i = 0; i < 3; ++i)      // (a member has nothing in flight of its own: single-context calls on it are refused for want of a GP)
+      expect_state(r[i], {3, 3, 2, 0, 0, 64, LS, S2, KN, 0.0, F, F, 0, 0, F, F, F, F, 4, F, 1, 2}, "a member behind the batch's conditioning");
+    for (int i = 0; i < 3; ++i) expect_answers(r[i], {F, GP_NONE, F, F, F, F, T}, "a member behind the batch's conditioning");
+    // pcabo_batch_wpca_results
+    b.wpca_collected();
+    for (int i = 0; i < 3; ++i) r[i].follow(b, r[i].own().with_k(ks[i]));
+    expect_batch({3, 3, 2, 0, 0, 64, LS, S2, KN, 0.0, T, F, 3, 2, T, F, F, F, 4, F, 1, 2}, F, F, F, F, GP_IN_FLIGHT, T, T, "batch wPCA collected");
+    expect_state(r[0], {3, 3, 2, 1, 4, 64, LS, S2, KN, 0.0, T, F, 0, 0, F, F, F, F, 4, F, 1, 2}, "member 0 behind the wPCA results");
+    expect_state(r[2], {3, 3, 2, 5, 8, 64, LS, S2, KN, 0.0, T, F, 0, 0, F, F, F, F, 4, F, 1, 2}, "member 2 behind the wPCA results");
+    expect_answers(r[0], {F, GP_NONE, T, T, F, F, T}, "member 0 behind the wPCA results");
+    expect_answers(r[2], {F, GP_NONE, T, F, F, F, T}, "member 2 behind the wPCA results");
+    // pcabo_batch_gp_condition_end_eval_begin / _end: run 1's ladder fails, run 2's ends on 1e-7 (their own records are told)
+    b.scoring_begun();
+    expect_batch({3, 3, 2, 0, 0, 64, LS, S2, KN, 0.0, T, F, 3, 2, T, F, F, F, 4, F, 1, 2}, F, T, F, F, GP_IN_FLIGHT, T, T, "scoring enqueued");
+    b.scoring_ended();
+    r[1].condition_failed(); r[2].condition_ended_ok(1e-7);
+    const bool ok[3] = {T, F, T};
+    for (int i = 0; i < 3; ++i) r[i].follow(b, r[i].own().ended(ok[i]));
+    expect_batch({3, 3, 2, 0, 0, 64, LS, S2, KN, 0.0, T, F, 3, 2, F, T, F, F, 4, F, 1, 2}, F, F, F, F, GP_READY, F, T, "scoring collected");
+    expect_state(r[0], {3, 3, 2, 1, 4, 64, LS, S2, KN, 0.0, T, F, 0, 0, F, T, F, F, 4, F, 1, 2}, "member 0 conditioned");
+    expect_state(r[1], {3, 3, 2, 5, 8, 64, LS, S2, KN, 0.0, T, F, 0, 0, F, F, F, F, 4, F, 1, 2}, "member 1 without a GP");
+    expect_state(r[2], {3, 3, 2, 5, 8, 64, LS, S2, KN, 1e-7, T, F, 0, 0, F, T, F, F, 4, F, 1, 2}, "member 2 on rung 1e-7");
+    expect_answers(r[0], {F, GP_READY, T, T, F, F, T}, "member 0 conditioned");
+    expect_answers(r[1], {F, GP_NONE, T, F, F, F, T}, "member 1 without a GP");
+    expect_answers(r[2], {F, GP_READY, T, F, F, F, T}, "member 2 on rung 1e-7");
+    // the other pending halves
+    b.opt_begun(8, 4);
+    CHECK(b.opt_matches(8, 4) && !b.opt_matches(8, 5) && !b.opt_matches(7, 4) && b.gp_ready() == GP_IN_FLIGHT && b.begin_pending(), "optimisation enqueued");
+    b.opt_ended();
+    CHECK(!b.opt_matches(8, 4) && b.gp_ready() == GP_READY, "optimisation collected");
+    b.imap_begun(); CHECK(b.imap_enqueued && b.gp_ready() == GP_IN_FLIGHT, "inverse map enqueued");
+    b.imap_ended(); CHECK(!b.begin_pending() && b.gp_ready() == GP_READY, "inverse map collected");
+    // a second conditioning at n = 64 and a lock-step fit behind it: a round starts every run at its own hyperparameters
+    b.m.wpca_enqueued(64, 2);
+    CHECK(!b.tickets_reset_if_needed(slabs(64), runs), "same slab count, nobody dirty: no reset");
+    b.condition_enqueued(64, 2, -1, LS, S2, KN);
+    for (int i = 0; i < 3; ++i) r[i].follow(b, r[i].own().with_k(r[i].k).started(LS, S2));
+    b.wpca_collected();
+    for (int i = 0; i < 3; ++i) r[i].follow(b, r[i].own().with_k(ks[i]));
+    expect_state(r[2], {64, 64, 2, 5, 8, 64, LS, S2, KN, 0.0, T, F, 0, 0, F, F, F, F, 4, F, 0, 2}, "member 2 behind the second conditioning");
+    expect_answers(r[2], {F, GP_NONE, T, F, T, F, T}, "member 2 behind the second conditioning");
+    const double ls_own[3] = {0.5, LS, 1.0}, s2_own[3] = {0.01, S2, 0.02};      // (run 1 is parked: it rests at the shared model)
+    for (int i = 0; i < 3; ++i) r[i].follow(b, r[i].own().started(ls_own[i], s2_own[i]));
+    expect_state(r[0], {64, 64, 2, 1, 4, 64, 0.5, 0.01, KN, 0.0, T, F, 0, 0, F, F, F, F, 4, F, 0, 2}, "member 0 in a fit round");
+    expect_answers(r[0], {F, GP_NONE, T, F, F, F, T}, "member 0 in a fit round");
+    r[2].condition_ended_ok(1e-8);                     // its round failed: redone alone on its own context
+    r[0].follow(b, r[0].own().ended(true)); r[1].follow(b, r[1].own().ended(true));
+    b.fit_finished();
+    r[1].follow(b, r[1].own().ended(false));           // (pcabo_batch_gp_fit: a run whose fit failed is left without a GP)
+    expect_batch({64, 64, 2, 0, 0, 64, LS, S2, KN, 0.0, T, F, 64, 2, F, T, F, F, 4, F, 0, 2}, T, F, F, F, GP_READY, T, T, "fit finished");
+    expect_state(r[0], {64, 64, 2, 1, 4, 64, 0.5, 0.01, KN, 0.0, T, F, 0, 0, F, T, F, F, 4, F, 0, 2}, "member 0 fitted");
+    expect_state(r[1], {64, 64, 2, 5, 8, 64, LS, S2, KN, 0.0, T, F, 0, 0, F, F, F, F, 4, F, 0, 2}, "member 1 after a failed fit");
+    expect_state(r[2], {64, 64, 2, 5, 8, 64, 1.0, 0.02, KN, 1e-8, T, F, 0, 0, F, T, F, F, 4, F, 0, 2}, "member 2 fitted on rung 1e-8");
+    expect_answers(r[0], {F, GP_READY, T, F, F, F, T}, "member 0 fitted");
+    expect_answers(r[1], {F, GP_NONE, T, F, T, F, T}, "member 1 after a failed fit");
+    expect_answers(r[2], {F, GP_READY, T, F, T, F, T}, "member 2 fitted on rung 1e-8");
+    for (int i = 0; i < 3; ++i) r[i].follow(b, r[i].own().with_k(ks[i]));      // pcabo_batch_wpca_results once more: the fitted models stay
+    expect_state(r[0], {64, 64, 2, 1, 4, 64, 0.5, 0.01, KN, 0.0, T, F, 0, 0, F, T, F, F, 4, F, 0, 2}, "member 0 keeps its fitted model");
+    expect_answers(r[0], {F, GP_READY, T, F, F, F, T}, "member 0 keeps its fitted model");
+    // pcabo_batch_gp_condition_begin (no wPCA: k = d = 5 for every run) at n = 65: the fit is over, the tickets follow NP
+    CHECK(b.tickets_reset_if_needed(slabs(128), runs), "65 points: reset");
+    b.condition_enqueued(65, 5, 5, LS, S2, KN);
+    for (int i = 0; i < 3; ++i) { r[i].rt_rebuilt(); r[i].follow(b, r[i].own().with_k(5).started(LS, S2)); }
+    expect_batch({65, 65, 5, 5, 8, 128, LS, S2, KN, 0.0, F, F, 64, 2, T, F, F, F, 8, F, 0, 2}, F, F, F, F, GP_IN_FLIGHT, T, T, "conditioning without a wPCA");
+    expect_state(r[0], {65, 65, 5, 5, 8, 128, LS, S2, KN, 0.0, F, F, 0, 0, F, F, F, F, 8, F, 0, 2}, "member 0 behind it");
+    expect_answers(r[0], {F, GP_NONE, F, F, F, T, F}, "member 0 behind the conditioning without a wPCA");
+    {  // (a conditioning without a wPCA clears a batch's uncollected mark; one with it sets it)
+      BatchState c2 = b; c2.m.wpca_enqueued(65, 5); c2.condition_enqueued(65, 5, -1, LS, S2, KN);
+      CHECK(c2.m.wpca_uncollected && !c2.wpca_on_host(), "k on the device: the wPCA is uncollected");
+      c2.condition_enqueued(65, 5, 5, LS, S2, KN);
+      CHECK(!c2.m.wpca_uncollected && c2.wpca_on_host(), "k known: no wPCA goes with the conditioning");
+    }
+    // dirty tickets: a single-context call on member 1 timed out
+    r[1].launch_may_have_died();
+    CHECK(b.tickets_need_reset(8, runs) && !b.m.tickets_need_reset(8), "a member's mark makes the batch's reset due at an unchanged NP");
+    r[1].follow(b, r[1].own().ended(true));
+    CHECK(r[1].cnt_dirty && b.tickets_need_reset(8, runs), "following the batch does not clear a member's mark");
+    CHECK(b.tickets_reset_if_needed(8, runs), "the next conditioning resets");
+    CHECK(!b.m.cnt_dirty && !r[0].cnt_dirty && !r[1].cnt_dirty && !r[2].cnt_dirty && r[1].cnt_S == 8, "the reset clears the mark on the batch and on every member");
+    CHECK(!b.tickets_need_reset(8, runs) && b.tickets_need_reset(4, runs), "no mark, same slab count: no reset");
+    // the transposed root inverse: Gram fetched -> stale, the conditioning's rebuild -> fresh, extend -> stale
+    r[0].condition_ended_ok(0.0);
+    r[0].gram_fetched(); CHECK(r[0].rt_stale, "Gram fetched: stale");
+    r[0].rt_rebuilt(); CHECK(!r[0].rt_stale, "the conditioning's rebuild: fresh");
+    r[0].n_changed(66); CHECK(r[0].rt_stale && r[0].n_base == 65, "extend: stale, n_base held");
+  }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -1078,6 +1293,7 @@ int main(int argc, char** argv) {
   test_fit_run();
   test_inverse_map_host();
   test_ctx_layout();
+  test_model_state();
   test_gang_pool(1, 3);
   test_gang_pool(workers, 11);
   if (g_fail) { std::fprintf(stderr, "host selftest: %d check(s) failed\n", g_fail); return 1; }

@@ -4,6 +4,7 @@
 #include "pcabo_internal.h"
 #include "lbfgsb.h"
 #include "host_side.h"
+#include "model_state.h"
 
 #include <algorithm>
 #include <atomic>
@@ -43,26 +44,17 @@ struct pcabo_ctx {
   // behind the kernel vectors, the main stream waits for it in front of the launches that need them.
   hipStream_t stream2 = nullptr;
   hipEvent_t evZn = nullptr, evKS = nullptr;
-  bool zn_recorded = false;              // evZn belongs to the conditioning in flight
   bool opt_hidden_tail = true;
   int max_n = 0, max_d = 0, max_q = 0;
   CtxLayout lay{};                       // shape (lay.s: the padded capacities) and layout of the two regions (ctx_layout.h)
   int ld = 0;
   int ptr_mode = PCABO_PTR_HOST;
-  // problem state
-  int n = 0, d = 0, k = 0, NP = 0, KP = 0;
-  int n_base = 0;                        // the n of the last conditioning or fit: points n_base .. n - 1 were appended by pcabo_gp_extend
-  double rung = 0.0;                     // the jitter the factorisation ended on (0, 1e-8, 1e-7, 1e-6): part of K's diagonal as factored
-  bool have_wpca = false, have_gp = false, gp_pending = false;
-  int wpca_n = 0, wpca_d = 0; bool wpca_uncollected = false;   // a wPCA whose results have not been waited for yet
-  double lengthscale = 0.0, noise = 0.0;
-  int kernel = 0;
+  ModelState st;                         // where the model stands (model_state.h): read here, changed by its transitions only
   // device buffers
   double *dX = nullptr, *dNoise = nullptr, *dF = nullptr, *dWeights = nullptr, *dWc = nullptr;
   long long* dRanks = nullptr;
-  double *dDataMean = nullptr, *dPcaMean = nullptr, *dC = nullptr, *dG = nullptr, *dLam = nullptr;
-  double* dGbuf[2] = {nullptr, nullptr};   // eigenvector ping-pong: the previous result warm-starts the next Jacobi
-  int gcur = 0, vprev_d = 0;
+  double *dDataMean = nullptr, *dPcaMean = nullptr, *dC = nullptr, *dLam = nullptr;
+  double* dGbuf[2] = {nullptr, nullptr};   // eigenvector ping-pong (st.gcur): the previous result warm-starts the next Jacobi
   double *dComps = nullptr, *dEvr = nullptr, *dZ = nullptr;
   double* dPcaOut = nullptr;             // [data_mean | pca_mean | evr | comps]: one allocation, one copy to the host
   double *dIn = nullptr, *hIn = nullptr; // host-pointer mode: X, noise, ranks (or f) and y travel packed in ONE copy
@@ -71,8 +63,7 @@ struct pcabo_ctx {
   double *dZnT = nullptr, *dAT = nullptr, *dNrm = nullptr, *dGram = nullptr, *dL = nullptr, *dR = nullptr;
   double *dTmp = nullptr, *dAlpha = nullptr, *dDiag = nullptr;   // dDiag: 64x64 hand-over tile of the Cholesky panels
   double *dXq = nullptr, *dPartial = nullptr, *dVal = nullptr, *dGrad = nullptr, *dZq = nullptr, *dXout = nullptr;
-  unsigned int* dCounters = nullptr;     // per-query tickets of the in-launch combine
-  int cnt_S = 0; bool cnt_dirty = true;  // slab-group count the tickets are consistent with / a launch may have died
+  unsigned int* dCounters = nullptr;     // per-query tickets of the in-launch combine (st.cnt_S, st.cnt_dirty)
   double* dKS = nullptr;                 // q x ld kernel vectors of the GEMM scoring path
   double* dBestF = nullptr;              // best_f of this run for the batched acquisition launches (set by the batch)
   double* dMll = nullptr;                // GP fit: 1 + M partial sums per lower 64 x 64 tile of K^-1, then the 5 + M results
@@ -84,7 +75,6 @@ struct pcabo_ctx {
   char* dSample = nullptr;               // pcabo_gp_posterior_sample: the sample block (SampleBlock), allocated by the first such call
   char *dRegion = nullptr, *hRegion = nullptr;   // the two allocations everything above / below is carved from
   bool in_batch = false; int batch_index = 0;
-  bool rt_stale = false;                 // pcabo_get_gram has overwritten the transposed root inverse kept in dGram (device-resident L-BFGS-B)
   // pinned host
   HostMirror* hm = nullptr;
   double *hXq = nullptr, *hVal = nullptr, *hGrad = nullptr, *hSmall = nullptr, *hBestF = nullptr;
@@ -166,7 +156,7 @@ static bool presence_alone(int device) {
 
 static int set_err(pcabo_ctx* c, int code, const char* fmt, const char* a = "", int v = 0) {
   if (c) snprintf(c->err, sizeof(c->err), fmt, a, v);
-  if (c && (code == PCABO_ERR_TIMEOUT || code == PCABO_ERR_HIP)) c->cnt_dirty = true;   // a launch may have died half-way
+  if (c && (code == PCABO_ERR_TIMEOUT || code == PCABO_ERR_HIP)) c->st.launch_may_have_died();
   return code;
 }
 #define HIPCHK(call)                                                                         \
@@ -339,7 +329,6 @@ static void ctx_bind(pcabo_ctx* ctx) {
   ctx->dDataMean = ctx->dPcaOut + pp.data_mean; ctx->dPcaMean = ctx->dPcaOut + pp.pca_mean; ctx->dEvr = ctx->dPcaOut + pp.evr;
   ctx->dComps = ctx->dPcaOut + pp.comps;
   ctx->dIn = D(D_IN);           ctx->dC = D(D_C);           ctx->dGbuf[0] = D(D_G0);    ctx->dGbuf[1] = D(D_G1);
-  ctx->dG = ctx->dGbuf[0];
   ctx->dLam = D(D_LAM);         ctx->dZ = D(D_Z);
   ctx->dK = I(D_K);             ctx->dSweeps = I(D_SWEEPS); ctx->dInfo = I(D_INFO);
   ctx->dY = D(D_Y);             ctx->dYs = D(D_YS);         ctx->dYstats = D(D_YSTATS); ctx->dBounds4 = D(D_BOUNDS4);
@@ -446,17 +435,16 @@ struct RowsDH {
   double inv_ls, noise, mean_c; int kernel;   // by value (zero where zb.hyp carries every run's own)
   ZB zb;
   hipEvent_t ev[2];                      // recorded behind k_zstats (null: none): the search box is on its way to the host
-  int* cnt_S; bool* cnt_dirty;           // the owner's ticket state (null: the tickets are left alone)
+  bool reset_tickets;                    // the owner's record asked for it (tickets_need_reset) and has been told (tickets_reset)
   const double* ard_ls = nullptr;        // ARD fit: k lengthscales on the device, folded by k_zstats (inv_ls = 1); a batch: run 0's,
                                          // every run's own where its zb.hyp block has PCABO_HYP_ARD_FOLD set
   hipEvent_t ev_zn = nullptr;            // recorded behind k_znorm (null: none): ZnT and the Normalize bounds are final
 };
 // The per-query tickets are consistent only with acq_slabs(NP): where NP changes outside a conditioning (pcabo_gp_extend /
 // pcabo_gp_truncate) they are reset as enqueue_rows_dh resets them.
-static int ext_tickets(pcabo_ctx* ctx, hipStream_t s, int NP, int* cnt_S) {
-  if (acq_slabs(NP) == *cnt_S) return PCABO_OK;
+static int ext_tickets(pcabo_ctx* ctx, hipStream_t s) {
+  if (!ctx->st.tickets_reset_if_needed(acq_slabs(ctx->st.NP))) return PCABO_OK;
   HIPCHK(hipMemsetAsync(ctx->dCounters, 0, ticket_bytes(ctx), s));
-  *cnt_S = acq_slabs(NP);
   return PCABO_OK;
 }
 template <class Phase>
@@ -478,12 +466,9 @@ static int enqueue_factor(pcabo_ctx* ctx, hipStream_t s, int n, int NP, ZB zb, P
 template <class Phase>
 static int enqueue_rows_dh(pcabo_ctx* ctx, hipStream_t s, const RowsDH& a, Phase&& phase) {
   const int NP = round_up(a.n, PCABO_BS);
-  // the per-query tickets count modulo the number of slab groups: they only need a reset when that number changes
-  // (every 64th iteration) or after a launch that did not complete
-  if (a.cnt_S && (acq_slabs(NP) != *a.cnt_S || *a.cnt_dirty)) {
+  if (a.reset_tickets) {
     if (a.zb.zs) HIPCHK(hipMemset2DAsync(ctx->dCounters, a.zb.zs, 0, ticket_bytes(ctx), a.zb.B, s));
     else HIPCHK(hipMemsetAsync(ctx->dCounters, 0, ticket_bytes(ctx), s));
-    *a.cnt_S = acq_slabs(NP); *a.cnt_dirty = false;
   }
   if (const int rc = phase(1)) return rc;
   launch_zstats(s, a.Z, a.y, a.n, a.k, a.unb, ctx->dBounds4, ctx->dZnMean, ctx->dYstats, ctx->dYs, ctx->hm, a.k_dev, a.zb, a.mean_c, a.ard_ls);
@@ -494,13 +479,39 @@ static int enqueue_rows_dh(pcabo_ctx* ctx, hipStream_t s, const RowsDH& a, Phase
   return enqueue_factor(ctx, s, a.n, NP, a.zb, phase);
 }
 
+// ---- rows A-C: the weighted PCA of one BO iteration, its inputs on the device --------------------------------------------------------
+struct WpcaInputs { const double *X, *noise, *y; const long long* ranks; };
+// ONE launch sequence for a single context and for the B runs of a batch, like enqueue_rows_dh: ctx = the context, or run 0 of a
+// batch with zb = its strides; st = the owner's record (the ping-pong of the eigenvectors); ev = the owner's evPca.  mark(0) is
+// called in front of the launches and mark(1) behind them: the caller's profiling marks at those places in stream order.
+template <class Mark>
+static int enqueue_rows_ac(pcabo_ctx* ctx, hipStream_t s, ModelState& st, const WpcaInputs& in, int n, int d, double var_threshold,
+                           int n_components, ZB zb, hipEvent_t ev, Mark&& mark) {
+  const int DP = round_up(d, 16);
+  mark(0);
+  launch_wpca_prep(s, in.X, in.ranks, in.noise, n, d, DP, ctx->dWeights, ctx->dDataMean, ctx->dPcaMean, ctx->dWc, zb);
+  launch_cov(s, ctx->dWc, n, DP, ctx->dC, zb);
+  const double* v0 = st.warm_start(d) ? ctx->dGbuf[st.gcur] : nullptr;
+  st.wpca_enqueued(n, d);                // (flips the ping-pong: this Jacobi writes the other buffer)
+  launch_jacobi(s, ctx->dC, d, DP, v0, ctx->dGbuf[st.gcur], ctx->dLam, ctx->dSweeps, n, var_threshold, n_components, ctx->dComps,
+                ctx->dEvr, ctx->dK, ctx->hm, zb);
+  launch_project(s, in.X, ctx->dDataMean, ctx->dPcaMean, ctx->dComps, ctx->dK, n, d, ctx->dZ, zb);
+  mark(1);
+  const size_t bytes = pca_copy_count(ctx->lay.s, n < d ? n : d, d) * sizeof(double);
+  double* h = small_at(ctx, small_wpca(ctx->lay.s));
+  if (zb.zs) HIPCHK(hipMemcpy2DAsync(h, zb.hzs, ctx->dPcaOut, zb.zs, bytes, zb.B, hipMemcpyDeviceToHost, s));
+  else HIPCHK(hipMemcpyAsync(h, ctx->dPcaOut, bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(ev, s));
+  return PCABO_OK;
+}
+
 // The single context's profile groups over those phases: 1 Normalize + Gram, 2 Cholesky, 3 root inverse + alpha (kk: the reduced
 // dimension of group 1's work model).  Unprofiled, no event is recorded.
 struct CondProf {
   pcabo_ctx* c; int kk;
   std::optional<ProfScope> ps;
   int operator()(int phase) {
-    const double n = c->n;
+    const double n = c->st.n;
     ps.reset();
     if (phase == 1) ps.emplace(c, 1, 8.0 * n * kk + 4.0 * n * (n + 1.0), 2.0 * n * n * kk + 12.0 * n * n);
     if (phase == 2) ps.emplace(c, 2, 16.0 * n * n, n * n * n / 3.0);
@@ -512,19 +523,20 @@ struct CondProf {
 static int launch_factorisation(pcabo_ctx* ctx, double jitter) {
   hipStream_t s = ctx->stream;
   if (jitter > 0.0) {      // a retry: K is built again (same kernel, same bits, flag cleared), then the jitter goes on its diagonal
-    launch_gram(s, ctx->dAT, ctx->dNrm, ctx->n, ctx->NP, round_up(ctx->k, 4), ctx->ld, ctx->noise, ctx->kernel, nullptr, nullptr,
+    launch_gram(s, ctx->dAT, ctx->dNrm, ctx->st.n, ctx->st.NP, round_up(ctx->st.k, 4), ctx->ld, ctx->st.noise, ctx->st.kernel, nullptr, nullptr,
                 ctx->dL, ctx->dInfo);
-    launch_add_jitter(s, ctx->dL, ctx->n, ctx->ld, jitter);
+    launch_add_jitter(s, ctx->dL, ctx->st.n, ctx->ld, jitter);
   }
-  return enqueue_factor(ctx, s, ctx->n, ctx->NP, ZB(), CondProf{ctx, 0});
+  return enqueue_factor(ctx, s, ctx->st.n, ctx->st.NP, ZB(), CondProf{ctx, 0});
 }
 
 // psd_safe_cholesky's ladder for one context from `attempt` on (jitter 0, 1e-8, 1e-7, 1e-6).  Attempt 0 finds its factorisation
 // already on the stream; a later one redoes it with that attempt's jitter.  Each attempt: extra() (launches the caller wants behind
-// the factorisation; PCABO_OK or an error), one wait, the look at chol_info.  PCABO_OK, PCABO_ERR_NOT_PD or the launch / HIP error.
+// the factorisation; PCABO_OK or an error), one wait, the look at chol_info.  PCABO_OK, PCABO_ERR_NOT_PD or the launch / HIP error;
+// either way the conditioning has ended, and the context's record is told how (ok with *used, the rung it ended on, or failed).
 template <class Extra>
-static int factor_attempts(pcabo_ctx* ctx, int attempt, Extra&& extra) {
-  double jitter = 1e-8, used = 0.0;
+static int factor_ladder(pcabo_ctx* ctx, int attempt, Extra&& extra, double* used_out) {
+  double jitter = 1e-8, &used = *used_out;
   for (int a = 2; a <= attempt; ++a) jitter *= 10.0;
   for (;; ++attempt) {
     if (attempt > 0) {
@@ -537,10 +549,18 @@ static int factor_attempts(pcabo_ctx* ctx, int attempt, Extra&& extra) {
     if (rc != PCABO_OK) return rc;
     HIPCHK(wait_stream(ctx->stream));
     HIPCHK(hipGetLastError());
-    if (ctx->hm->chol_info == 0) { ctx->rung = used; return PCABO_OK; }      // (pcabo_gp_extend borders K as it was factored)
+    if (ctx->hm->chol_info == 0) return PCABO_OK;
     if (attempt == 3)
       return set_err(ctx, PCABO_ERR_NOT_PD, "K + s2 I not positive definite after jitter retries (pivot %s%d)", "", ctx->hm->chol_info);
   }
+}
+template <class Extra>
+static int factor_attempts(pcabo_ctx* ctx, int attempt, Extra&& extra) {
+  double used = 0.0;
+  const int rc = factor_ladder(ctx, attempt, extra, &used);
+  if (rc == PCABO_OK) ctx->st.condition_ended_ok(used);      // (pcabo_gp_extend borders K as it was factored: the rung is kept)
+  else ctx->st.condition_failed();
+  return rc;
 }
 static int factor_attempts(pcabo_ctx* ctx, int attempt) { return factor_attempts(ctx, attempt, [] { return (int)PCABO_OK; }); }
 
@@ -610,7 +630,6 @@ int pcabo_last_error(pcabo_ctx* ctx, char* buf, int buflen) {
 // Inputs of one BO iteration.  Host-pointer mode: X, the noise block, the ranks (or f) and y are packed into one pinned
 // buffer and cross in ONE copy (four pageable copies cost 60-170 us of host time per iteration); device-pointer mode:
 // device-to-device copies into the context's own buffers as before.
-struct WpcaInputs { const double *X, *noise, *y; const long long* ranks; };
 static int stage_inputs(pcabo_ctx* ctx, const double* X, const double* f, const int64_t* ranks, const double* noise,
                         const double* y, int n, int d, int maximize, WpcaInputs* in) {
   hipStream_t s = ctx->stream;
@@ -640,25 +659,11 @@ static int stage_inputs(pcabo_ctx* ctx, const double* X, const double* f, const 
 // wPCA launches, then ONE copy of [data_mean | pca_mean | evr | comps] to pinned memory and the event that says it
 // arrived.  k arrives through the HostMirror (written by the selection step at the end of k_jacobi).
 static int enqueue_wpca(pcabo_ctx* ctx, const WpcaInputs& in, int n, int d, double var_threshold, int n_components) {
-  hipStream_t s = ctx->stream;
-  const int DP = round_up(d, 16);
-  {
-    ProfScope ps(ctx, 0, 8.0 * n * d * 2 + 8.0 * n * d, 2.0 * n * d * d + 9.0 * d * d * d + 2.0 * n * d * d);
-    launch_wpca_prep(s, in.X, in.ranks, in.noise, n, d, DP, ctx->dWeights, ctx->dDataMean, ctx->dPcaMean, ctx->dWc);
-    launch_cov(s, ctx->dWc, n, DP, ctx->dC);
-    const double* v0 = (ctx->vprev_d == d) ? ctx->dGbuf[ctx->gcur] : nullptr;
-    ctx->gcur ^= 1;
-    ctx->dG = ctx->dGbuf[ctx->gcur];
-    launch_jacobi(s, ctx->dC, d, DP, v0, ctx->dG, ctx->dLam, ctx->dSweeps, n, var_threshold, n_components, ctx->dComps,
-                  ctx->dEvr, ctx->dK, ctx->hm);
-    ctx->vprev_d = d;
-    launch_project(s, in.X, ctx->dDataMean, ctx->dPcaMean, ctx->dComps, ctx->dK, n, d, ctx->dZ);
-  }
-  const int rcount = n < d ? n : d;
-  HIPCHK(hipMemcpyAsync(small_at(ctx, small_wpca(ctx->lay.s)), ctx->dPcaOut, pca_copy_count(ctx->lay.s, rcount, d) * sizeof(double),
-                        hipMemcpyDeviceToHost, s));
-  HIPCHK(hipEventRecord(ctx->evPca, s));
-  return PCABO_OK;
+  std::optional<ProfScope> ps;
+  return enqueue_rows_ac(ctx, ctx->stream, ctx->st, in, n, d, var_threshold, n_components, ZB(), ctx->evPca, [&](int behind) {
+    if (behind) ps.reset();
+    else ps.emplace(ctx, 0, 8.0 * n * d * 2 + 8.0 * n * d, 2.0 * n * d * d + 9.0 * d * d * d + 2.0 * n * d * d);
+  });
 }
 
 // a run's wPCA results from its pinned block to the caller's arrays (null: not asked for)
@@ -671,17 +676,19 @@ static void wpca_hand_out(const pcabo_ctx* ctx, int d, int rcount, double* data_
   if (comps) memcpy(comps, h + pp.comps, (size_t)rcount * d * sizeof(double));
 }
 
-// wait for the wPCA results only (whatever was enqueued behind them keeps running) and hand them out
-static int collect_wpca(pcabo_ctx* ctx, int n, int d, double* data_mean, double* pca_mean, double* comps, double* evr,
-                        int* k) {
+// wait for the results of the wPCA last enqueued only (whatever was enqueued behind them keeps running) and hand them out
+static int collect_wpca(pcabo_ctx* ctx, double* data_mean, double* pca_mean, double* comps, double* evr, int* k) {
   HIPCHK(wait_event(ctx->evPca));
   HIPCHK(hipGetLastError());
-  const int rcount = n < d ? n : d;
-  wpca_hand_out(ctx, d, rcount, data_mean, pca_mean, comps, evr);
-  ctx->d = d; ctx->k = ctx->hm->k;
-  ctx->have_wpca = true;
-  if (k) *k = ctx->k;
+  const int n = ctx->st.wpca_n, d = ctx->st.wpca_d;
+  wpca_hand_out(ctx, d, n < d ? n : d, data_mean, pca_mean, comps, evr);
+  ctx->st.wpca_collected(ctx->hm->k);
+  if (k) *k = ctx->st.k;
   return PCABO_OK;
+}
+// ... where a call needs them and nobody has asked for them yet
+static int collect_pending_wpca(pcabo_ctx* ctx) {
+  return ctx->st.wpca_uncollected ? pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr) : PCABO_OK;
 }
 
 int pcabo_wpca(pcabo_ctx* ctx, const double* X, const double* f, const int64_t* ranks, int n, int d, int maximize,
@@ -690,7 +697,7 @@ int pcabo_wpca(pcabo_ctx* ctx, const double* X, const double* f, const int64_t* 
   if (!ctx) return PCABO_ERR_ARG;
   if (!X || (!f && !ranks) || n < 2 || n > ctx->max_n || d < 1 || d > ctx->max_d)
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_wpca: bad argument or size beyond context capacity%s", "");
-  if (ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "pcabo_wpca: a conditioning is in flight, call pcabo_gp_condition_end first%s", "");
+  if (ctx->st.in_flight()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_wpca: a conditioning is in flight, call pcabo_gp_condition_end first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   WpcaInputs in{nullptr, nullptr, nullptr, nullptr};
@@ -698,12 +705,11 @@ int pcabo_wpca(pcabo_ctx* ctx, const double* X, const double* f, const int64_t* 
   if (rc != PCABO_OK) return rc;
   rc = enqueue_wpca(ctx, in, n, d, var_threshold, n_components);
   if (rc != PCABO_OK) return rc;
-  ctx->have_gp = false;
-  rc = collect_wpca(ctx, n, d, data_mean, pca_mean, comps, evr, k);
+  ctx->st.points_replaced(n);
+  rc = collect_wpca(ctx, data_mean, pca_mean, comps, evr, k);
   if (rc != PCABO_OK) return rc;
-  ctx->n = n;
   if (Z) {
-    STAGE_OUT(Z, ctx->dZ, (size_t)n * ctx->k, double);
+    STAGE_OUT(Z, ctx->dZ, (size_t)n * ctx->st.k, double);
     HIPCHK(hipStreamSynchronize(s));
   }
   return PCABO_OK;
@@ -713,17 +719,13 @@ int pcabo_wpca(pcabo_ctx* ctx, const double* X, const double* f, const int64_t* 
 // right behind the wPCA) - the three kernels that need it read it from ctx->dK.
 static int enqueue_condition(pcabo_ctx* ctx, const double* y_dev, int n, int k, const double* unb, double lengthscale,
                              double noise, int kernel, double mean_c = 0.0, const double* ard_ls = nullptr) {
-  ctx->n = ctx->n_base = n;
-  ctx->rung = 0.0;
-  ctx->NP = round_up(n, PCABO_BS);
-  if (k >= 0) { ctx->k = k; ctx->KP = round_up(k, 4); }
-  ctx->lengthscale = lengthscale; ctx->noise = noise; ctx->kernel = kernel;
-  ctx->have_gp = false;
-  ctx->gp_pending = true;
   // (a profiled context keeps everything on one stream: its event pairs time the main stream alone)
-  ctx->zn_recorded = ctx->stream2 && ctx->opt_hidden_tail && !ctx->prof;
-  const RowsDH a{ctx->dZ, y_dev, unb, n, k, ctx->KP, k < 0 ? ctx->dK : nullptr, 1.0 / lengthscale, noise, mean_c, kernel, ZB(),
-                 {ctx->evBounds, nullptr}, &ctx->cnt_S, &ctx->cnt_dirty, ard_ls, ctx->zn_recorded ? ctx->evZn : nullptr};
+  ctx->st.condition_enqueued(n, k, lengthscale, noise, kernel, ctx->stream2 && ctx->opt_hidden_tail && !ctx->prof);
+  // the per-query tickets count modulo the number of slab groups: they only need a reset when that number changes
+  // (every 64th iteration) or after a launch that did not complete
+  const bool reset = ctx->st.tickets_reset_if_needed(acq_slabs(ctx->st.NP));
+  const RowsDH a{ctx->dZ, y_dev, unb, n, k, ctx->st.KP, k < 0 ? ctx->dK : nullptr, 1.0 / lengthscale, noise, mean_c, kernel, ZB(),
+                 {ctx->evBounds, nullptr}, reset, ard_ls, ctx->st.zn_recorded ? ctx->evZn : nullptr};
   return enqueue_rows_dh(ctx, ctx->stream, a, CondProf{ctx, k < 0 ? ctx->max_d : k});   // asynchronous: pcabo_gp_condition_end() waits and checks
 }
 
@@ -751,7 +753,7 @@ int pcabo_gp_condition_begin(pcabo_ctx* ctx, const double* Z, const double* y, i
   if (!ctx) return PCABO_ERR_ARG;
   if (!y || k < 1 || k > ctx->max_d || !gp_args_ok(ctx, n, lengthscale, noise, kernel))
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition: bad argument or size beyond context capacity%s", "");
-  if (!Z && (!ctx->have_wpca || ctx->n != n || ctx->k != k))
+  if (!Z && !ctx->st.wpca_matches(n, k))
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition: Z == NULL needs a matching pcabo_wpca call first%s", "");
   const double* unb = nullptr;
   const int rc = stage_gp_inputs(ctx, Z, y, n, k, norm_bounds, &unb);
@@ -770,22 +772,20 @@ int pcabo_wpca_gp_condition_begin(pcabo_ctx* ctx, const double* X, const double*
   if (!ctx) return PCABO_ERR_ARG;
   if (!X || !y || (!f && !ranks) || d < 1 || d > ctx->max_d || !gp_args_ok(ctx, n, lengthscale, gp_noise, kernel))
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_wpca_gp_condition_begin: bad argument or size beyond context capacity%s", "");
-  if (ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "pcabo_wpca_gp_condition_begin: a conditioning is in flight, call pcabo_gp_condition_end first%s", "");
+  if (ctx->st.in_flight()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_wpca_gp_condition_begin: a conditioning is in flight, call pcabo_gp_condition_end first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
   WpcaInputs in{nullptr, nullptr, nullptr, nullptr};
   int rc = stage_inputs(ctx, X, f, ranks, noise, y, n, d, maximize, &in);
   if (rc != PCABO_OK) return rc;
   rc = enqueue_wpca(ctx, in, n, d, var_threshold, n_components);
   if (rc != PCABO_OK) return rc;
-  ctx->wpca_n = n; ctx->wpca_d = d;
   if (ctx->prof) {                       // profiled runs keep the two phases apart (the work model of group 1 needs k)
-    rc = collect_wpca(ctx, n, d, data_mean, pca_mean, comps, evr, k);
+    rc = collect_wpca(ctx, data_mean, pca_mean, comps, evr, k);
     if (rc != PCABO_OK) return rc;
-    return enqueue_condition(ctx, in.y, n, ctx->k, nullptr, lengthscale, gp_noise, kernel);
+    return enqueue_condition(ctx, in.y, n, ctx->st.k, nullptr, lengthscale, gp_noise, kernel);
   }
-  rc = enqueue_condition(ctx, in.y, n, -1, nullptr, lengthscale, gp_noise, kernel);
+  rc = enqueue_condition(ctx, in.y, n, -1, nullptr, lengthscale, gp_noise, kernel);      // (k on the device: the wPCA is uncollected)
   if (rc != PCABO_OK) return rc;
-  ctx->wpca_n = n; ctx->wpca_d = d; ctx->wpca_uncollected = true;
   if (!data_mean && !pca_mean && !comps && !evr && !k) return PCABO_OK;      // enqueue only: pcabo_wpca_results() waits
   return pcabo_wpca_results(ctx, data_mean, pca_mean, comps, evr, k);
 }
@@ -795,25 +795,17 @@ int pcabo_wpca_gp_condition_begin(pcabo_ctx* ctx, const double* X, const double*
 // scrambled Sobol engine of the initial-condition draw, with last iteration's k) while the eigen-decomposition runs.
 int pcabo_wpca_results(pcabo_ctx* ctx, double* data_mean, double* pca_mean, double* comps, double* evr, int* k) {
   if (!ctx) return PCABO_ERR_ARG;
-  if (!ctx->wpca_uncollected && !ctx->have_wpca)
-    return set_err(ctx, PCABO_ERR_ARG, "pcabo_wpca_results: no weighted PCA enqueued%s", "");
+  if (!ctx->st.wpca_known()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_wpca_results: no weighted PCA enqueued%s", "");
   HIPCHK(hipSetDevice(ctx->device));
-  int rc = collect_wpca(ctx, ctx->wpca_n, ctx->wpca_d, data_mean, pca_mean, comps, evr, k);
-  if (rc != PCABO_OK) return rc;
-  ctx->wpca_uncollected = false;
-  ctx->KP = round_up(ctx->k, 4);
-  return PCABO_OK;
+  return collect_wpca(ctx, data_mean, pca_mean, comps, evr, k);
 }
 
 int pcabo_gp_condition_end(pcabo_ctx* ctx) {
   if (!ctx) return PCABO_ERR_ARG;
-  if (!ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end: no conditioning in flight%s", "");
+  if (!ctx->st.in_flight()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end: no conditioning in flight%s", "");
   HIPCHK(hipSetDevice(ctx->device));
-  if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
-  ctx->gp_pending = false;
-  const int rc = factor_attempts(ctx, 0);
-  if (rc == PCABO_OK) ctx->have_gp = true;
-  return rc;
+  if (const int rc = collect_pending_wpca(ctx)) return rc;
+  return factor_attempts(ctx, 0);
 }
 
 int pcabo_gp_condition(pcabo_ctx* ctx, const double* Z, const double* y, int n, int k, const double* norm_bounds,
@@ -837,9 +829,9 @@ static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, bool ard, const dou
     return set_err(ctx, PCABO_ERR_ARG, "%s: bad argument or size beyond context capacity", who);
   if (kernel != PCABO_KERNEL_MATERN52)
     return set_err(ctx, PCABO_ERR_ARG, "%s: the fit is restated for the Matern-5/2 kernel only", who);
-  if (ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "%s: a conditioning is in flight, call pcabo_gp_condition_end first", who);
-  if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
-  if (!Z && (!ctx->have_wpca || ctx->n != n || ctx->k != k))
+  if (ctx->st.in_flight()) return set_err(ctx, PCABO_ERR_ARG, "%s: a conditioning is in flight, call pcabo_gp_condition_end first", who);
+  if (const int rc = collect_pending_wpca(ctx)) return rc;
+  if (!Z && !ctx->st.wpca_matches(n, k))
     return set_err(ctx, PCABO_ERR_ARG, "%s: Z == NULL needs a matching pcabo_wpca call first", who);
   return stage_gp_inputs(ctx, Z, y, n, k, norm_bounds, unb);
 }
@@ -848,21 +840,19 @@ static int stage_fit_inputs(pcabo_ctx* ctx, const char* who, bool ard, const dou
 // factorisation and copies their 5 + M results (M = 1, ard: M = KP) in front of its wait.  A run of a batch whose lock-step round
 // failed enters at attempt 1.
 static int mll_attempts(pcabo_ctx* ctx, int attempt, bool ard) {
-  const int rc = factor_attempts(ctx, attempt, [ctx, ard]() -> int {
-    const int M = ard ? ctx->KP : 1;
-    double* out = ctx->dMll + mll_result(ctx->NP, M).start;
-    launch_mll_grad(ctx->stream, ard, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->n, ctx->NP, ctx->KP, ctx->ld, ctx->dMll, out);
-    HOST_OUT(ctx->hMll, out, mll_result(ctx->NP, M).count, double);
+  return factor_attempts(ctx, attempt, [ctx, ard]() -> int {
+    const int M = ard ? ctx->st.KP : 1;
+    double* out = ctx->dMll + mll_result(ctx->st.NP, M).start;
+    launch_mll_grad(ctx->stream, ard, ctx->dR, ctx->dAT, ctx->dNrm, ctx->dAlpha, ctx->dL, ctx->dYs, ctx->st.n, ctx->st.NP, ctx->st.KP, ctx->ld, ctx->dMll, out);
+    HOST_OUT(ctx->hMll, out, mll_result(ctx->st.NP, M).count, double);
     return PCABO_OK;
   });
-  if (rc == PCABO_OK) ctx->have_gp = true;
-  return rc;
 }
 
 // One evaluation at a theta inside the model's domain: the conditioning there (k_zstats with the mean constant -> k_znorm -> k_gram
 // -> Cholesky -> root inverse -> alpha), then mll_attempts; the sums are left in ctx->hMll.
 // ard (DESIGN.md "ARD lengthscales"): the lengthscales softplus(rho_c) go to the device and k_zstats folds them into the Normalize
-// ranges, so the evaluation is the scalar one at lengthscale 1 on the folded ranges (ctx->lengthscale = 1: the acquisition kernels
+// ranges, so the evaluation is the scalar one at lengthscale 1 on the folded ranges (the record's lengthscale is 1: the acquisition kernels
 // read the folded bounds4 and need no change); k_mll_grad<true> adds the per-input sums.  The next conditioning call passes no
 // lengthscales and returns to the unfolded model.
 static int mll_launch(pcabo_ctx* ctx, bool ard, int n, int k, const double* unb, const double* theta) {
@@ -873,8 +863,7 @@ static int mll_launch(pcabo_ctx* ctx, bool ard, int n, int k, const double* unb,
   const int rc = enqueue_condition(ctx, ctx->dY, n, k, unb, ard ? 1.0 : softplus_host(theta[2]), theta[0], PCABO_KERNEL_MATERN52,
                                    theta[1], ard ? ctx->dArdLs : nullptr);
   if (rc != PCABO_OK) return rc;
-  ctx->gp_pending = false;
-  return mll_attempts(ctx, 0, ard);
+  return mll_attempts(ctx, 0, ard);      // (waits: the conditioning has ended when this returns)
 }
 // (the shared-lengthscale form names pcabo_gp_mll whichever entry point met the theta: its text since the first fit)
 static int theta_domain_err(pcabo_ctx* ctx, const char* who, bool ard) {
@@ -939,14 +928,14 @@ int pcabo_gp_fit_ard(pcabo_ctx* ctx, const double* Z, const double* y, int n, in
 
 int pcabo_acq_bounds(pcabo_ctx* ctx, double* bounds) {
   if (!ctx || !bounds) return PCABO_ERR_ARG;
-  if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
-  if (ctx->gp_pending) {                   // conditioning in flight: the box only needs k_zstats, wait for that alone
+  if (const int rc = collect_pending_wpca(ctx)) return rc;
+  if (ctx->st.in_flight()) {                   // conditioning in flight: the box only needs k_zstats, wait for that alone
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(wait_event(ctx->evBounds));
-  } else if (!ctx->have_gp) {
+  } else if (!ctx->st.conditioned()) {
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_bounds: call pcabo_gp_condition first%s", "");
   }
-  for (int c = 0; c < ctx->k; ++c) { bounds[c] = ctx->hm->acq_lo[c]; bounds[ctx->k + c] = ctx->hm->acq_hi[c]; }
+  for (int c = 0; c < ctx->st.k; ++c) { bounds[c] = ctx->hm->acq_lo[c]; bounds[ctx->st.k + c] = ctx->hm->acq_hi[c]; }
   return PCABO_OK;
 }
 
@@ -965,16 +954,16 @@ static AcqParams make_params(pcabo_ctx* ctx, double best_f, int maximize, int ac
   // PCABO_ACQ_UCB: the slot carries kappa, which the Python layer passes float32-representable already
   p.best_f = ctx->bestf_f32 ? (double)(float)best_f : best_f;
   p.y_mean = 0.0; p.y_std = 1.0;
-  p.inv_ls = 1.0 / ctx->lengthscale;
+  p.inv_ls = 1.0 / ctx->st.lengthscale;
   p.maximize = maximize ? 1 : 0;
   p.acq = acq;
-  p.kernel = ctx->kernel;
+  p.kernel = ctx->st.kernel;
   p.want_grad = want_grad;
   return p;
 }
 
 // the conditioned model of a context as the acquisition launchers take it
-static GpModel gp_model(const pcabo_ctx* c) { return {c->n, c->k, c->NP, c->ld, c->dZnT, c->dR, c->dAlpha, c->dBounds4, c->dYstats}; }
+static GpModel gp_model(const pcabo_ctx* c) { return {c->st.n, c->st.k, c->st.NP, c->ld, c->dZnT, c->dR, c->dAlpha, c->dBounds4, c->dYstats}; }
 
 // The outcome of waiting for an acquisition launch's flags
 static int acq_published(pcabo_ctx* ctx, FlagWait w) {
@@ -990,7 +979,7 @@ static int acq_published(pcabo_ctx* ctx, FlagWait w) {
 // whose results land in ctx->hVal / ctx->hGrad; the host spins on the sequence flag.
 static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = true) {
   hipStream_t s = ctx->stream;
-  const int k = ctx->k;
+  const int k = ctx->st.k;
   const unsigned long long seq = ++ctx->seq;
   const QueryArgs* qa = nullptr;
   const double* xdev = nullptr;
@@ -1007,10 +996,10 @@ static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = t
       HIPCHK(hipMemcpyAsync(ctx->dXq, ctx->hXq, (size_t)nq * k * sizeof(double), hipMemcpyHostToDevice, s));
       xdev = ctx->dXq;
     }
-    ProfScope ps(ctx, 5, acq_bytes(ctx->n, k, nq, 0), acq_flops(ctx->n, k, nq, 0));
+    ProfScope ps(ctx, 5, acq_bytes(ctx->st.n, k, nq, 0), acq_flops(ctx->st.n, k, nq, 0));
     launch_score(s, xdev, nq, gp_model(ctx), p, ctx->dKS, ctx->dPartial, ctx->dVal);
   } else {
-    ProfScope ps(ctx, small ? 4 : 5, acq_bytes(ctx->n, k, nq, p.want_grad), acq_flops(ctx->n, k, nq, p.want_grad));
+    ProfScope ps(ctx, small ? 4 : 5, acq_bytes(ctx->st.n, k, nq, p.want_grad), acq_flops(ctx->st.n, k, nq, p.want_grad));
     launch_acq(s, qa, xdev, nq, gp_model(ctx), p, ctx->dPartial, ctx->dCounters, ctx->dVal, ctx->dGrad, small ? ctx->hVal : nullptr,
                small ? ctx->hGrad : nullptr, small ? ctx->hm : nullptr, seq);
   }
@@ -1051,7 +1040,7 @@ static int eval_staged_groups(pcabo_ctx* ctx, const GroupLaunches& t, AcqParams&
   {
     int nq = 0;
     for (int g = 0; g < ng; ++g) nq += gn[g];
-    ProfScope ps(ctx, 4, acq_bytes(ctx->n, ctx->k, nq, p.want_grad), acq_flops(ctx->n, ctx->k, nq, p.want_grad));
+    ProfScope ps(ctx, 4, acq_bytes(ctx->st.n, ctx->st.k, nq, p.want_grad), acq_flops(ctx->st.n, ctx->st.k, nq, p.want_grad));
     if (launch_acq_group(s, &tab, ng, ctx->hXq, gp_model(ctx), p, ctx->dPartial, ctx->dCounters + counters_group().start, ctx->dVal,
                          ctx->dGrad, ctx->hVal, ctx->hGrad, ctx->hm, seq, AcqBatch()) != 0)
       return set_err(ctx, PCABO_ERR_HIP, "the restart-group acquisition kernel could not be launched%s", "");
@@ -1063,7 +1052,7 @@ static int eval_staged_groups(pcabo_ctx* ctx, const GroupLaunches& t, AcqParams&
   return acq_published(ctx, w);
 }
 static bool group_mode(const pcabo_ctx* ctx, int q, int want_grad) {
-  return ctx->opt_group_acq && want_grad && q <= PCABO_INLAUNCH_MAXQ && acq_group_possible(ctx->NP, ctx->k);
+  return ctx->opt_group_acq && want_grad && q <= PCABO_INLAUNCH_MAXQ && acq_group_possible(ctx->st.NP, ctx->st.k);
 }
 
 int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq, double* val,
@@ -1072,10 +1061,10 @@ int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int m
   if (!Xq || !val || q < 1 || q > ctx->max_q)
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: bad argument or q beyond context capacity%s", "");
   if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: %s", why);
-  if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: call pcabo_gp_condition first%s", "");
+  if (!ctx->st.conditioned()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: call pcabo_gp_condition first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const int k = ctx->k;
+  const int k = ctx->st.k;
   const size_t nx = (size_t)q * k;
   if (ctx->ptr_mode == PCABO_PTR_HOST) memcpy(ctx->hXq, Xq, nx * sizeof(double));
   else {
@@ -1114,24 +1103,23 @@ int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double 
   if (!Xq || !val || q < 1 || q > ctx->max_q)
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: bad argument or q beyond context capacity%s", "");
   if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: %s", why);
-  if (!ctx->gp_pending) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: no conditioning in flight%s", "");
-  if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
+  if (!ctx->st.in_flight()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: no conditioning in flight%s", "");
+  if (const int rc = collect_pending_wpca(ctx)) return rc;
   if (q <= PCABO_INLAUNCH_MAXQ || ctx->ptr_mode != PCABO_PTR_HOST) {      // nothing to gain: the two calls in a row
     int rc = pcabo_gp_condition_end(ctx);
     if (rc != PCABO_OK) return rc;
     return pcabo_acq_eval(ctx, Xq, q, best_f, maximize, acq, val, nullptr);
   }
   HIPCHK(hipSetDevice(ctx->device));
-  memcpy(ctx->hXq, Xq, (size_t)q * ctx->k * sizeof(double));
+  memcpy(ctx->hXq, Xq, (size_t)q * ctx->st.k * sizeof(double));
   AcqParams p = make_params(ctx, best_f, maximize, acq, 0);
   // The kernel vectors of the samples need the Normalize bounds and ZnT only: they and the samples' copy go to the second stream
   // and run beside the factorisation; what needs alpha and R follows on the main stream (score_tail).
-  const bool hidden = ctx->zn_recorded && ctx->opt_hidden_tail && !ctx->prof && score_gemm_possible(q);
-  ctx->zn_recorded = false;
+  const bool hidden = ctx->st.zn_consumed() && ctx->opt_hidden_tail && !ctx->prof && score_gemm_possible(q);
   int rc;
   if (hidden) {
     HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->evZn, 0));
-    HIPCHK(hipMemcpyAsync(ctx->dXq, ctx->hXq, (size_t)q * ctx->k * sizeof(double), hipMemcpyHostToDevice, ctx->stream2));
+    HIPCHK(hipMemcpyAsync(ctx->dXq, ctx->hXq, (size_t)q * ctx->st.k * sizeof(double), hipMemcpyHostToDevice, ctx->stream2));
     launch_score_ks_only(ctx->stream2, ctx->dXq, q, gp_model(ctx), p, ctx->dKS);
     HIPCHK(hipEventRecord(ctx->evKS, ctx->stream2));
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evKS, 0));
@@ -1139,7 +1127,7 @@ int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double 
   } else {
     rc = eval_staged(ctx, q, p);                    // ends with a stream synchronisation: the conditioning is over too
   }
-  if (rc != PCABO_OK) { ctx->gp_pending = false; return rc; }
+  if (rc != PCABO_OK) { ctx->st.condition_failed(); return rc; }
   if (ctx->hm->chol_info != 0) {                    // rare: jitter retries, then the evaluation again
     rc = pcabo_gp_condition_end(ctx);
     if (rc != PCABO_OK) return rc;
@@ -1147,8 +1135,7 @@ int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double 
     rc = hidden ? score_tail(ctx, q, p) : eval_staged(ctx, q, p);
     if (rc != PCABO_OK) return rc;
   } else {
-    ctx->gp_pending = false;
-    ctx->have_gp = true;
+    ctx->st.condition_ended_ok(0.0);                // (the factorisation as enqueued: no jitter)
   }
   memcpy(val, ctx->hVal, (size_t)q * sizeof(double));
   return PCABO_OK;
@@ -1189,7 +1176,7 @@ struct BarMailbox {
 struct ResidentSession {
   pcabo_ctx* ctx; AcqParams& p;
   int cap = 0;                           // > 0 while a kernel of that many queries is in flight
-  BarMailbox mail() const { return BarMailbox{ctx->dMail, ctx->hm, cap, ctx->k}; }
+  BarMailbox mail() const { return BarMailbox{ctx->dMail, ctx->hm, cap, ctx->st.k}; }
   // Does this call, at its first round of nq queries, go to a resident kernel?  Only a process alone on the device, and only
   // the one context of it: several contexts in ONE process (one run per host thread, or a batch next to a single run) would
   // each want most of the chip at the same time - one launch per evaluation then, which interleaves well.  A call under a
@@ -1199,7 +1186,7 @@ struct ResidentSession {
     if ((ctx->alone_age++ & 7) == 0) ctx->alone = presence_alone(ctx->device);
     if (ctx->srv_penalty > 0) { --ctx->srv_penalty; return false; }
     return ctx->opt_resident && ctx->mail_bar && !ctx->opt_group_acq && ctx->alone && presence_local_contexts(ctx->device) == 1 &&
-           !ctx->prof && acq_server_possible(nq, ctx->n, ctx->k, ctx->NP);
+           !ctx->prof && acq_server_possible(nq, ctx->st.n, ctx->st.k, ctx->st.NP);
   }
   int start(int nq) {
     cap = nq;
@@ -1263,9 +1250,9 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
   if (!ics || !bounds || !cand || !vals || num_restarts < 1 || batch_limit < 1 || num_restarts > ctx->max_q)
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: bad argument%s", "");
   if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: %s", why);
-  if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: call pcabo_gp_condition first%s", "");
+  if (!ctx->st.conditioned()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: call pcabo_gp_condition first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
-  const int k = ctx->k;
+  const int k = ctx->st.k;
   RunRestarts run;
   run.init(ics, bounds, num_restarts, batch_limit, k, maxiter);
   run.bind(ctx->hXq, ctx->hVal, ctx->hGrad);
@@ -1322,14 +1309,14 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
 
 int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x) {
   if (!ctx || !z || !x) return PCABO_ERR_ARG;
-  if (!ctx->have_wpca) return set_err(ctx, PCABO_ERR_ARG, "pcabo_inverse_map: call pcabo_wpca first%s", "");
+  if (!ctx->st.have_wpca) return set_err(ctx, PCABO_ERR_ARG, "pcabo_inverse_map: call pcabo_wpca first%s", "");
   if (!ctx->in_batch && ctx->opt_hidden_tail) {
     // A single context has [data_mean | pca_mean | evr | comps] in pinned host memory since the wPCA results were collected:
     // the k d multiply-adds run here, with the kernel's bits (inverse_map_host) - no launch, no flag wait, no device copy of x.
-    if (ctx->wpca_uncollected) { int rc0 = pcabo_wpca_results(ctx, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc0 != PCABO_OK) return rc0; }
+    if (const int rc = collect_pending_wpca(ctx)) return rc;
     const double* h = small_at(ctx, small_wpca(ctx->lay.s));
     const PcaParts pp = pca_parts(ctx->lay.s);
-    inverse_map_host(z, h + pp.comps, h + pp.pca_mean, h + pp.data_mean, ctx->k, ctx->d, x);
+    inverse_map_host(z, h + pp.comps, h + pp.pca_mean, h + pp.data_mean, ctx->st.k, ctx->st.d, x);
     return PCABO_OK;
   }
   HIPCHK(hipSetDevice(ctx->device));
@@ -1337,10 +1324,10 @@ int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x) {
   // z travels through the pinned query block (the kernel reads it in place over PCIe: 36 doubles), x comes back the way the
   // acquisition results do - stores to pinned host memory followed by a sequence word the host polls: no copy, no stream
   // synchronisation (40 -> 15 us per BO iteration on the host clock)
-  memcpy(ctx->hXq, z, (size_t)ctx->k * sizeof(double));
+  memcpy(ctx->hXq, z, (size_t)ctx->st.k * sizeof(double));
   const unsigned long long seq = ++ctx->seq;
   double* hx = small_at(ctx, small_imap_x(ctx->lay.s));
-  launch_inverse_map(s, ctx->hXq, ctx->dComps, ctx->dDataMean, ctx->dPcaMean, ctx->k, ctx->d, ctx->dXout, nullptr, ZB(),
+  launch_inverse_map(s, ctx->hXq, ctx->dComps, ctx->dDataMean, ctx->dPcaMean, ctx->st.k, ctx->st.d, ctx->dXout, nullptr, ZB(),
                      hx, ctx->hm, seq);
   HIPCHK(hipGetLastError());
   const FlagWait w = wait_flags(ctx->hm, 0, 1, seq, deadline_in(20), &s);
@@ -1349,35 +1336,35 @@ int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x) {
     return set_err(ctx, PCABO_ERR_TIMEOUT, "inverse-map kernel finished without publishing its result%s", "");
   }
   if (w == FLAGS_LATE) return set_err(ctx, PCABO_ERR_TIMEOUT, "device did not publish the inverse map%s", "");
-  memcpy(x, hx, (size_t)ctx->d * sizeof(double));
+  memcpy(x, hx, (size_t)ctx->st.d * sizeof(double));
   return PCABO_OK;
 }
 
 int pcabo_get_gp_state(pcabo_ctx* ctx, double* K_chol, double* Rinv, double* alpha, double* y_mean_std,
                        double* norm_bounds) {
   if (!ctx) return PCABO_ERR_ARG;
-  if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_get_gp_state: call pcabo_gp_condition first%s", "");
+  if (!ctx->st.conditioned()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_get_gp_state: call pcabo_gp_condition first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const size_t n = ctx->n, w = n * sizeof(double), pitch = (size_t)ctx->ld * sizeof(double);
+  const size_t n = ctx->st.n, w = n * sizeof(double), pitch = (size_t)ctx->ld * sizeof(double);
   if (K_chol) HIPCHK(hipMemcpy2DAsync(K_chol, w, ctx->dL, pitch, w, n, hipMemcpyDeviceToHost, s));
   if (Rinv) HIPCHK(hipMemcpy2DAsync(Rinv, w, ctx->dR, pitch, w, n, hipMemcpyDeviceToHost, s));
   if (alpha) HOST_OUT(alpha, ctx->dAlpha, n, double);
   HIPCHK(hipStreamSynchronize(s));
   if (y_mean_std) { y_mean_std[0] = ctx->hm->y_mean; y_mean_std[1] = ctx->hm->y_std; }
   if (norm_bounds)
-    for (int c = 0; c < ctx->k; ++c) { norm_bounds[c] = ctx->hm->norm_lo[c]; norm_bounds[ctx->k + c] = ctx->hm->norm_hi[c]; }
+    for (int c = 0; c < ctx->st.k; ++c) { norm_bounds[c] = ctx->hm->norm_lo[c]; norm_bounds[ctx->st.k + c] = ctx->hm->norm_hi[c]; }
   return PCABO_OK;
 }
 
 int pcabo_get_gram(pcabo_ctx* ctx, double* K) {
   if (!ctx || !K) return PCABO_ERR_ARG;
-  if (!ctx->have_gp) return set_err(ctx, PCABO_ERR_ARG, "pcabo_get_gram: call pcabo_gp_condition first%s", "");
+  if (!ctx->st.conditioned()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_get_gram: call pcabo_gp_condition first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
-  const size_t n = ctx->n, w = n * sizeof(double), pitch = (size_t)ctx->ld * sizeof(double);
+  const size_t n = ctx->st.n, w = n * sizeof(double), pitch = (size_t)ctx->ld * sizeof(double);
   // built on demand: the conditioning itself writes only the copy that the factorisation then overwrites
-  ctx->rt_stale = true;
-  launch_gram(ctx->stream, ctx->dAT, ctx->dNrm, ctx->n, ctx->NP, round_up(ctx->k, 4), ctx->ld, ctx->noise, ctx->kernel, ctx->dGram,
+  ctx->st.gram_fetched();
+  launch_gram(ctx->stream, ctx->dAT, ctx->dNrm, ctx->st.n, ctx->st.NP, round_up(ctx->st.k, 4), ctx->ld, ctx->st.noise, ctx->st.kernel, ctx->dGram,
               nullptr, nullptr, nullptr);
   HIPCHK(hipMemcpy2DAsync(K, w, ctx->dGram, pitch, w, n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1461,23 +1448,16 @@ struct pcabo_batch {
   size_t zs = 0, hzs = 0;
   std::vector<pcabo_ctx*> ctx;
   std::vector<char> active;              // runs that still take part in pcabo_batch_optimize_acqf (pcabo_batch_set_active)
-  int n = 0, d = 0, NP = 0;
-  bool wpca_uncollected = false, gp_pending = false, have_gp = false;
-  double lengthscale = 0.0, noise = 0.0;
-  int kernel = 0;
-  // lock-step fit (pcabo_batch_gp_mll / pcabo_batch_gp_fit): where the last conditioning's inputs lie on the device (run 0), and
-  // whether the runs now carry their own model - then every batched launch reads 1 / lengthscale from the runs' dHyp blocks
+  BatchState st;                         // where the runs stand together, and the pending _begin halves (model_state.h)
+  std::vector<ModelState*> run_st;       // the members' records (ctx[b]->st): written from st by follow() only
+  // lock-step fit (pcabo_batch_gp_mll / pcabo_batch_gp_fit): where the last conditioning's inputs lie on the device (run 0); once
+  // st.fitted, every batched launch reads 1 / lengthscale from the runs' dHyp blocks
   const double *fitZ = nullptr, *fitY = nullptr, *fitUnb = nullptr;
-  bool fitted = false;
   int fit_rounds = 0;
-  int gcur = 0, vprev_d = 0;             // eigenvector ping-pong of ALL runs (they advance together)
-  int cnt_S = 0; bool cnt_dirty = true;
   bool prof = false; hipEvent_t pev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // phase marks of the last conditioning
   bool group_acq = true;                 // L-BFGS-B rounds through k_acq_group (pcabo_batch_set_option(PCABO_OPT_GROUP_ACQ, 0): the per-query kernels)
   size_t in_stride_x = 0, in_stride_noise = 0, in_stride_y = 0;   // pcabo_batch_set_input_strides (doubles between two runs' blocks; 0: dense)
-  bool score_enqueued = false;           // pcabo_batch_gp_condition_end_eval_begin without its _end yet
-  bool imap_enqueued = false;            // pcabo_batch_inverse_map_begin without its _end yet
-  bool opt_enqueued = false; int opt_restarts = 0, opt_limit = 0; std::vector<int> opt_act;   // pcabo_batch_optimize_acqf_begin without its _end yet
+  std::vector<int> opt_act;              // the runs of the pcabo_batch_optimize_acqf_begin that has not been ended yet
   int dev_lbfgsb = 0;                    // PCABO_OPT_DEVICE_LBFGSB: 1 device-resident L-BFGS-B, 2 its host-stepped twin
   // debug record of the last optimise call on the device path (pcabo_debug_batch_lbfgsb_*; tests): the twin's branch counters
   // [B][groups][LBB_COUNT], or the eight doubles per group the kernel wrote [B][groups][8]
@@ -1505,7 +1485,7 @@ static int bset_err(pcabo_batch* b, int code, const char* fmt, const char* a = "
 
 static ZB batch_zb(const pcabo_batch* b) { ZB z; z.B = b->B; z.zs = b->zs; z.hzs = b->hzs; return z; }
 // per-run hyperparameter blocks for the batched acquisition launches: only after a lock-step fit (null: the shared scalar)
-static const double* batch_hyp(const pcabo_batch* b) { return b->fitted ? b->ctx[0]->dHyp : nullptr; }
+static const double* batch_hyp(const pcabo_batch* b) { return b->st.fitted ? b->ctx[0]->dHyp : nullptr; }
 
 static void batch_free(pcabo_batch* batch) {
   (void)hipSetDevice(batch->device);
@@ -1535,8 +1515,11 @@ static int batch_enqueue_condition(pcabo_batch* batch, const double* Z, const do
   hipStream_t s = batch->stream;
   const ZB zb = batch_zb(batch);
   const int NP = round_up(n, PCABO_BS);
+  // the tickets of ALL runs are reset when the batch's record or any member's asks for it (a single-context call on a member may
+  // have timed out)
+  const bool reset = batch->st.tickets_reset_if_needed(acq_slabs(NP), batch->run_st);
   const RowsDH a{Z, y, unb, n, -1, 0, c0->dK, 1.0 / lengthscale, gp_noise, 0.0, kernel, zb,
-                 {batch->evBounds, k < 0 ? nullptr : batch->evPca}, &batch->cnt_S, &batch->cnt_dirty};
+                 {batch->evBounds, k < 0 ? nullptr : batch->evPca}, reset};
   const int rc = enqueue_rows_dh(c0, s, a, [&](int phase) {
     if (batch->prof) (void)hipEventRecord(batch->pev[phase], s);
     // the device-resident optimiser reads the root inverse transposed as well (the Gram buffer is free: K is only kept on demand)
@@ -1545,18 +1528,16 @@ static int batch_enqueue_condition(pcabo_batch* batch, const double* Z, const do
   });
   if (rc != PCABO_OK) return bset_err(batch, rc, "%s", c0->err);
   BHIPCHK(hipGetLastError());
-  batch->n = n; batch->d = d; batch->NP = NP;
-  batch->lengthscale = lengthscale; batch->noise = gp_noise; batch->kernel = kernel;
-  batch->wpca_uncollected = k < 0; batch->gp_pending = true; batch->have_gp = false;
-  batch->fitZ = Z; batch->fitY = y; batch->fitUnb = unb; batch->fitted = false;
+  batch->st.condition_enqueued(n, d, k, lengthscale, gp_noise, kernel);
+  batch->fitZ = Z; batch->fitY = y; batch->fitUnb = unb;
   for (pcabo_ctx* c : batch->ctx) {      // the per-run contexts see the same state (single-context calls keep working)
-    c->n = c->n_base = n; c->rung = 0.0; c->d = d; c->NP = NP; c->lengthscale = lengthscale; c->noise = gp_noise; c->kernel = kernel;
-    c->have_gp = false; c->have_wpca = false; c->gp_pending = false; c->wpca_uncollected = false;
-    if (k >= 0) { c->k = k; c->KP = round_up(k, 4); }
-    else { c->gcur = batch->gcur; c->dG = c->dGbuf[c->gcur]; c->vprev_d = d; }
-    c->cnt_S = batch->cnt_S; c->cnt_dirty = false;
+    if (batch->dev_lbfgsb) c->st.rt_rebuilt();
+    c->st.follow(batch->st, c->st.own().with_k(k >= 0 ? k : c->st.k).started(lengthscale, gp_noise));
   }
   return PCABO_OK;
+}
+static int collect_pending_wpca(pcabo_batch* batch) {
+  return batch->st.m.wpca_uncollected ? pcabo_batch_wpca_results(batch, nullptr, nullptr, nullptr, nullptr, nullptr) : PCABO_OK;
 }
 
 extern "C" {
@@ -1590,6 +1571,7 @@ int pcabo_batch_create(int device, int B, int max_n, int max_d, int max_q, pcabo
     pcabo_ctx* c = new (std::nothrow) pcabo_ctx();
     if (!c) return bset_err(batch, PCABO_ERR_HIP, "out of memory%s", "");
     batch->ctx[b] = c;
+    batch->run_st.push_back(&c->st);
     int rc = ctx_setup(c, device, lay, batch->dSlab + batch->zs * (size_t)b, batch->hSlab + batch->hzs * (size_t)b, batch->stream);
     c->batch_index = b;
     if (rc != PCABO_OK) return bset_err(batch, rc, "context %s%d of the batch could not be set up", "", b);
@@ -1641,7 +1623,7 @@ int pcabo_batch_set_option(pcabo_batch* batch, int option, int value) {
     if (value < 0 || value > 2) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_set_option: PCABO_OPT_DEVICE_LBFGSB takes 0, 1 or 2 (%s%d)", "", value);
     // switched on after a conditioning: dGram holds K (or an older RT), not this GP's transposed root inverse - the next
     // launch of the device optimiser rebuilds it (k_rt_build) instead of reading whatever is there
-    if (value != 0 && batch->dev_lbfgsb == 0) for (pcabo_ctx* c : batch->ctx) if (c->have_gp) c->rt_stale = true;
+    if (value != 0 && batch->dev_lbfgsb == 0) for (pcabo_ctx* c : batch->ctx) c->st.rt_wanted();
     batch->dev_lbfgsb = value;
     return PCABO_OK;
   }
@@ -1705,7 +1687,7 @@ int pcabo_batch_wpca_gp_condition_begin(pcabo_batch* batch, const double* X, con
   pcabo_ctx* c0 = batch->ctx[0];
   if (!X || !ranks || !y || n < 2 || n > batch->max_n || d < 1 || d > batch->max_d || !gp_args_ok(c0, n, lengthscale, gp_noise, kernel))
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_wpca_gp_condition_begin: bad argument or size beyond the batch's capacity%s", "");
-  if (batch->gp_pending) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_wpca_gp_condition_begin: a conditioning is in flight%s", "");
+  if (batch->st.m.in_flight()) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_wpca_gp_condition_begin: a conditioning is in flight%s", "");
   BHIPCHK(hipSetDevice(batch->device));
   hipStream_t s = batch->stream;
   const int B = batch->B;
@@ -1725,28 +1707,14 @@ int pcabo_batch_wpca_gp_condition_begin(pcabo_batch* batch, const double* X, con
     memcpy(h + off_y, y + (size_t)b * sy, (size_t)n * sizeof(double));
   }
   BHIPCHK(hipMemcpy2DAsync(c0->dIn, batch->zs, c0->hIn, batch->hzs, total * sizeof(double), B, hipMemcpyHostToDevice, s));
-  const double* inX = c0->dIn;
-  const double* inNoise = noise ? c0->dIn + off_noise : nullptr;
-  const long long* inRanks = reinterpret_cast<const long long*>(c0->dIn + off_r);
-  const double* inY = c0->dIn + off_y;
-  const ZB zb = batch_zb(batch);
-  const int DP = round_up(d, 16);
-  if (batch->prof) (void)hipEventRecord(batch->pev[0], s);
-  // rows A-C
-  launch_wpca_prep(s, inX, inRanks, inNoise, n, d, DP, c0->dWeights, c0->dDataMean, c0->dPcaMean, c0->dWc, zb);
-  launch_cov(s, c0->dWc, n, DP, c0->dC, zb);
-  const double* v0 = (batch->vprev_d == d) ? c0->dGbuf[batch->gcur] : nullptr;
-  batch->gcur ^= 1;
-  launch_jacobi(s, c0->dC, d, DP, v0, c0->dGbuf[batch->gcur], c0->dLam, c0->dSweeps, n, var_threshold, n_components,
-                c0->dComps, c0->dEvr, c0->dK, c0->hm, zb);
-  batch->vprev_d = d;
-  launch_project(s, inX, c0->dDataMean, c0->dPcaMean, c0->dComps, c0->dK, n, d, c0->dZ, zb);
-  const int rcount = n < d ? n : d;
-  BHIPCHK(hipMemcpy2DAsync(small_at(c0, small_wpca(c0->lay.s)), batch->hzs, c0->dPcaOut, batch->zs,
-                           pca_copy_count(c0->lay.s, rcount, d) * sizeof(double), B, hipMemcpyDeviceToHost, s));
-  BHIPCHK(hipEventRecord(batch->evPca, s));
+  const WpcaInputs in{c0->dIn, noise ? c0->dIn + off_noise : nullptr, c0->dIn + off_y, reinterpret_cast<const long long*>(c0->dIn + off_r)};
+  // rows A-C (the ping-pong of ALL runs is the batch's: they advance together)
+  const int rc = enqueue_rows_ac(c0, s, batch->st.m, in, n, d, var_threshold, n_components, batch_zb(batch), batch->evPca, [&](int behind) {
+    if (!behind && batch->prof) (void)hipEventRecord(batch->pev[0], s);
+  });
+  if (rc != PCABO_OK) return bset_err(batch, rc, "%s", c0->err);
   // rows D-H, queued behind the projection (k is read on the device)
-  return batch_enqueue_condition(batch, c0->dZ, inY, nullptr, n, d, -1, lengthscale, gp_noise, kernel);
+  return batch_enqueue_condition(batch, c0->dZ, in.y, nullptr, n, d, -1, lengthscale, gp_noise, kernel);
 }
 
 // Rows D-H for every run WITHOUT the weighted PCA: the GPs live on the given points (pcabo_gp_condition_begin for B runs; the
@@ -1759,7 +1727,7 @@ int pcabo_batch_gp_condition_begin(pcabo_batch* batch, const double* Z, const do
   pcabo_ctx* c0 = batch->ctx[0];
   if (!Z || !y || n < 2 || n > batch->max_n || k < 1 || k > batch->max_d || !gp_args_ok(c0, n, lengthscale, gp_noise, kernel))
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_begin: bad argument or size beyond the batch's capacity%s", "");
-  if (batch->gp_pending) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_begin: a conditioning is in flight%s", "");
+  if (batch->st.m.in_flight()) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_begin: a conditioning is in flight%s", "");
   BHIPCHK(hipSetDevice(batch->device));
   hipStream_t s = batch->stream;
   const int B = batch->B;
@@ -1785,42 +1753,42 @@ int pcabo_batch_gp_condition_begin(pcabo_batch* batch, const double* Z, const do
 
 int pcabo_batch_wpca_results(pcabo_batch* batch, double* data_mean, double* pca_mean, double* comps, double* evr, int* k) {
   if (!batch) return PCABO_ERR_ARG;
-  if (!batch->wpca_uncollected && batch->n == 0) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_wpca_results: nothing enqueued%s", "");
+  if (!batch->st.anything_enqueued()) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_wpca_results: nothing enqueued%s", "");
   BHIPCHK(hipSetDevice(batch->device));
   BHIPCHK(wait_event(batch->evPca));
   BHIPCHK(hipGetLastError());
-  const int n = batch->n, d = batch->d, rcount = n < d ? n : d;
+  const int n = batch->st.m.n, d = batch->st.m.d, rcount = n < d ? n : d;
+  batch->st.wpca_collected();
   for (int b = 0; b < batch->B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
     wpca_hand_out(c, d, rcount, data_mean ? data_mean + (size_t)b * d : nullptr, pca_mean ? pca_mean + (size_t)b * d : nullptr,
                   comps ? comps + (size_t)b * d * d : nullptr, evr ? evr + (size_t)b * d : nullptr);
-    c->k = c->hm->k; c->KP = round_up(c->k, 4); c->have_wpca = true;
-    if (k) k[b] = c->k;
+    c->st.follow(batch->st, c->st.own().with_k(c->hm->k));
+    if (k) k[b] = c->st.k;
   }
-  batch->wpca_uncollected = false;
   return PCABO_OK;
 }
 
 int pcabo_batch_acq_bounds(pcabo_batch* batch, double* bounds) {
   if (!batch || !bounds) return PCABO_ERR_ARG;
-  if (batch->wpca_uncollected) { int rc = pcabo_batch_wpca_results(batch, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc != PCABO_OK) return rc; }
-  if (batch->gp_pending) {
+  if (const int rc = collect_pending_wpca(batch)) return rc;
+  if (batch->st.m.in_flight()) {
     BHIPCHK(hipSetDevice(batch->device));
     BHIPCHK(wait_event(batch->evBounds));
-  } else if (!batch->have_gp) {
+  } else if (!batch->st.m.conditioned()) {
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_acq_bounds: no conditioning enqueued%s", "");
   }
   for (int b = 0; b < batch->B; ++b) {
     const pcabo_ctx* c = batch->ctx[b];
     double* o = bounds + (size_t)b * 2 * batch->max_d;
-    for (int j = 0; j < c->k; ++j) { o[j] = c->hm->acq_lo[j]; o[c->k + j] = c->hm->acq_hi[j]; }
+    for (int j = 0; j < c->st.k; ++j) { o[j] = c->hm->acq_lo[j]; o[c->st.k + j] = c->hm->acq_hi[j]; }
   }
   return PCABO_OK;
 }
 
 static int batch_max_k(const pcabo_batch* batch) {
   int km = 1;
-  for (const pcabo_ctx* c : batch->ctx) km = std::max(km, c->k);
+  for (const pcabo_ctx* c : batch->ctx) km = std::max(km, c->st.k);
   return km;
 }
 
@@ -1828,13 +1796,13 @@ static int batch_max_k(const pcabo_batch* batch) {
 // batch's n / NP, the largest k of the runs
 static GpModel gp_model(const pcabo_batch* batch, int kmax) {
   GpModel m = gp_model(batch->ctx[0]);
-  m.n = batch->n; m.k = kmax; m.NP = batch->NP;
+  m.n = batch->st.m.n; m.k = kmax; m.NP = batch->st.m.NP;
   return m;
 }
 // the acquisition constants of a batched launch (best_f travels per run: batch_put_best_f)
 static AcqParams batch_params(const pcabo_batch* batch, int maximize, int acq, int want_grad) {
   AcqParams p = make_params(batch->ctx[0], 0.0, maximize, acq, want_grad);
-  p.inv_ls = 1.0 / batch->lengthscale; p.kernel = batch->kernel;
+  p.inv_ls = 1.0 / batch->st.m.lengthscale; p.kernel = batch->st.m.kernel;
   return p;
 }
 
@@ -1878,9 +1846,9 @@ static int batch_put_best_f(pcabo_batch* batch, const double* best_f) {
 // shared lengthscale, no fold.
 // A run whose Cholesky failed in the round is redone alone on its own context (mll_attempts from the first jitter on), as
 // batch_score_collect does; st[b] is PCABO_OK, PCABO_ERR_NOT_PD or a HIP error for every run with a theta, untouched otherwise.
-static int batch_fit_m(const pcabo_batch* batch, bool ard, int b) { return ard ? batch->ctx[b]->k : 1; }
+static int batch_fit_m(const pcabo_batch* batch, bool ard, int b) { return ard ? batch->ctx[b]->st.k : 1; }
 static int batch_mll_round(pcabo_batch* batch, bool ard, const std::vector<const double*>& hyp_theta, int* st) {
-  const int B = batch->B, n = batch->n, NP = batch->NP;
+  const int B = batch->B, n = batch->st.m.n, NP = batch->st.m.NP;
   pcabo_ctx* c0 = batch->ctx[0];
   hipStream_t s = batch->stream;
   const int kmax = batch_max_k(batch), Mmax = ard ? round_up(kmax, 4) : 1;
@@ -1889,21 +1857,20 @@ static int batch_mll_round(pcabo_batch* batch, bool ard, const std::vector<const
     const double* th = hyp_theta[b];
     // the very doubles the single-context path passes by value: 1.0 / softplus(rho) (ard: 1.0 / 1.0), the noise, the mean constant
     const bool fold = ard && th;
-    const double ls = !th ? batch->lengthscale : (ard ? 1.0 : softplus_host(th[2]));
+    const double ls = !th ? batch->st.m.lengthscale : (ard ? 1.0 : softplus_host(th[2]));
     c->hHyp[PCABO_HYP_INV_LS] = 1.0 / ls;
-    c->hHyp[PCABO_HYP_NOISE] = th ? th[0] : batch->noise;
+    c->hHyp[PCABO_HYP_NOISE] = th ? th[0] : batch->st.m.noise;
     c->hHyp[PCABO_HYP_MEAN_C] = th ? th[1] : 0.0;
     c->hHyp[PCABO_HYP_ARD_FOLD] = fold ? 1.0 : 0.0;
     if (fold)                            // the very doubles mll_launch writes for a single context
-      for (int j = 0; j < c->k; ++j) c->hArdLs[j] = softplus_host(th[2 + j]);
-    c->lengthscale = ls; c->noise = c->hHyp[PCABO_HYP_NOISE]; c->kernel = batch->kernel;   // single-context calls on a member see its model
-    c->have_gp = false; c->rung = 0.0;
+      for (int j = 0; j < c->st.k; ++j) c->hArdLs[j] = softplus_host(th[2 + j]);
+    c->st.follow(batch->st, c->st.own().started(ls, c->hHyp[PCABO_HYP_NOISE]));   // single-context calls on a member see its model
   }
   BHIPCHK(hipMemcpy2DAsync(c0->dHyp, batch->zs, c0->hHyp, batch->hzs, PCABO_HYP_WORDS * sizeof(double), B, hipMemcpyHostToDevice, s));
   if (ard) BHIPCHK(hipMemcpy2DAsync(c0->dArdLs, batch->zs, c0->hArdLs, batch->hzs, (size_t)kmax * sizeof(double), B, hipMemcpyHostToDevice, s));
   ZB zb = batch_zb(batch);
   zb.hyp = c0->dHyp;
-  const RowsDH a{batch->fitZ, batch->fitY, batch->fitUnb, n, -1, 0, c0->dK, 0.0, 0.0, 0.0, batch->kernel, zb, {nullptr, nullptr}, nullptr, nullptr,
+  const RowsDH a{batch->fitZ, batch->fitY, batch->fitUnb, n, -1, 0, c0->dK, 0.0, 0.0, 0.0, batch->st.m.kernel, zb, {nullptr, nullptr}, false,
                  ard ? c0->dArdLs : nullptr};
   const int rc = enqueue_rows_dh(c0, s, a, [&](int phase) -> int {
     if (phase != 4) return PCABO_OK;     // behind alpha: the likelihood kernels and the strided copy of the runs' results
@@ -1919,9 +1886,9 @@ static int batch_mll_round(pcabo_batch* batch, bool ard, const std::vector<const
   ++batch->fit_rounds;
   for (int b = 0; b < B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
-    if (c->hm->chol_info == 0) { c->have_gp = true; if (hyp_theta[b]) st[b] = PCABO_OK; continue; }
+    if (c->hm->chol_info == 0) { c->st.follow(batch->st, c->st.own().ended(true)); if (hyp_theta[b]) st[b] = PCABO_OK; continue; }
     if (!hyp_theta[b]) continue;
-    st[b] = mll_attempts(c, 1, ard);     // rare: jitter 1e-8, 1e-7, 1e-6 for this run alone (sets have_gp)
+    st[b] = mll_attempts(c, 1, ard);     // rare: jitter 1e-8, 1e-7, 1e-6 for this run alone (its own record is told how it ended)
   }
   return PCABO_OK;
 }
@@ -1929,14 +1896,14 @@ static int batch_mll_round(pcabo_batch* batch, bool ard, const std::vector<const
 // what both entry points need before the first round; *act = the runs that take part.  ld_theta: doubles between two runs' thetas
 // (the ARD form: at least 2 + the largest k of the runs, known once the wPCA results are in)
 static int batch_fit_prepare(pcabo_batch* batch, const char* who, bool ard, int ld_theta, std::vector<char>* act, int* status) {
-  if (batch->kernel != PCABO_KERNEL_MATERN52 && (batch->gp_pending || batch->have_gp))
+  if (batch->st.m.kernel != PCABO_KERNEL_MATERN52 && (batch->st.m.in_flight() || batch->st.m.conditioned()))
     return bset_err(batch, PCABO_ERR_ARG, "%s: the fit is restated for the Matern-5/2 kernel only", who);
-  if ((!batch->gp_pending && !batch->fitted) || !batch->fitZ)
+  if (!batch->st.scorable() || !batch->fitZ)
     return bset_err(batch, PCABO_ERR_ARG, "%s: call pcabo_batch_wpca_gp_condition_begin or pcabo_batch_gp_condition_begin first", who);
-  if (batch->score_enqueued || batch->opt_enqueued || batch->imap_enqueued)
+  if (batch->st.begin_pending())
     return bset_err(batch, PCABO_ERR_ARG, "%s: a _begin call of this batch has not been ended", who);
   BHIPCHK(hipSetDevice(batch->device));
-  if (batch->wpca_uncollected) { int rc = pcabo_batch_wpca_results(batch, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc != PCABO_OK) return rc; }
+  if (const int rc = collect_pending_wpca(batch)) return rc;
   if (ard && ld_theta < 2 + batch_max_k(batch))
     return bset_err(batch, PCABO_ERR_ARG, "%s: ld_theta is smaller than 2 + the largest reduced dimension of the runs (%d)", who, 2 + batch_max_k(batch));
   act->assign((size_t)batch->B, 0);
@@ -1949,12 +1916,12 @@ static int batch_fit_prepare(pcabo_batch* batch, const char* who, bool ard, int 
 
 // the batch after its last round: conditioned (and waited for), every run at its own model
 static void batch_fit_done(pcabo_batch* batch) {
-  batch->gp_pending = false; batch->have_gp = true; batch->fitted = true;
+  batch->st.fit_finished();
   // the device-resident optimiser reads the transposed root inverse of the FINAL factorisation (stream order: before its launch)
   if (batch->dev_lbfgsb) {
     pcabo_ctx* c0 = batch->ctx[0];
-    launch_rt_build(batch->stream, c0->dR, batch->n, batch->NP, c0->ld, c0->dGram, batch_zb(batch));
-    for (pcabo_ctx* c : batch->ctx) c->rt_stale = false;
+    launch_rt_build(batch->stream, c0->dR, batch->st.m.n, batch->st.m.NP, c0->ld, c0->dGram, batch_zb(batch));
+    for (pcabo_ctx* c : batch->ctx) c->st.rt_rebuilt();
   }
 }
 
@@ -1982,7 +1949,7 @@ static int batch_gp_mll_call(pcabo_batch* batch, const char* who, bool ard, cons
   int worst = PCABO_OK;
   for (int b = 0; b < B; ++b) {
     if (st[b] == PCABO_OK)
-      mll_assemble(batch->ctx[b]->hMll, batch->n, batch_fit_m(batch, ard, b), theta + (size_t)ld * b, loss + b,
+      mll_assemble(batch->ctx[b]->hMll, batch->st.m.n, batch_fit_m(batch, ard, b), theta + (size_t)ld * b, loss + b,
                    grad ? grad + (size_t)ld * b : nullptr);
     else if (act[b]) worst = st[b];
     if (status) status[b] = st[b];
@@ -2007,7 +1974,7 @@ static int batch_gp_fit_call(pcabo_batch* batch, const char* who, bool ard, doub
   }
   batch->fit_rounds = 0;
   const auto round = [&](const std::vector<const double*>& th, int* st) { return batch_mll_round(batch, ard, th, st); };
-  rc = fit_rounds(runs, batch->n, round);
+  rc = fit_rounds(runs, batch->st.m.n, round);
   // (no run wanted an evaluation: one round all the same, the batch is left conditioned at the shared model)
   if (rc == PCABO_OK && batch->fit_rounds == 0) rc = round(std::vector<const double*>((size_t)B, nullptr), nullptr);
   if (rc != PCABO_OK) return rc;
@@ -2018,7 +1985,7 @@ static int batch_gp_fit_call(pcabo_batch* batch, const char* who, bool ard, doub
     if (status) status[b] = r.status;
     if (!act[b]) continue;
     if (r.status == PCABO_ERR_ARG) theta_domain_err(batch->ctx[b], who, ard);
-    if (r.status != PCABO_OK) { worst = r.status; batch->ctx[b]->have_gp = false; continue; }
+    if (r.status != PCABO_OK) { worst = r.status; batch->ctx[b]->st.follow(batch->st, batch->ctx[b]->st.own().ended(false)); continue; }
     memcpy(theta_inout + (size_t)ld * b, r.xr, (size_t)r.nvar * sizeof(double));
     if (loss) loss[b] = r.fr;
     if (info) r.report(info + 4 * b);
@@ -2069,21 +2036,21 @@ static int batch_score_args(pcabo_batch* batch, const double* Xq, int q, const d
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: bad argument%s", "");
   if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: %s", why);
   // (after pcabo_batch_gp_fit the conditioning has been waited for already: the fitted state is scored by the same launches)
-  if (!batch->gp_pending && !batch->fitted) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: no conditioning in flight%s", "");
+  if (!batch->st.scorable()) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: no conditioning in flight%s", "");
   return PCABO_OK;
 }
 
 static int batch_score_enqueue(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq, bool out_ok = true) {
   if (!batch) return PCABO_ERR_ARG;
   if (const int rc = batch_score_args(batch, Xq, q, best_f, acq, out_ok)) return rc;
-  if (batch->score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: a scoring is already enqueued%s", "");
-  if (batch->wpca_uncollected) { int rc = pcabo_batch_wpca_results(batch, nullptr, nullptr, nullptr, nullptr, nullptr); if (rc != PCABO_OK) return rc; }
+  if (batch->st.score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: a scoring is already enqueued%s", "");
+  if (const int rc = collect_pending_wpca(batch)) return rc;
   BHIPCHK(hipSetDevice(batch->device));
   hipStream_t s = batch->stream;
   const int B = batch->B, kmax = batch_max_k(batch);
   pcabo_ctx* c0 = batch->ctx[0];
   for (int b = 0; b < B; ++b)
-    memcpy(batch->ctx[b]->hXq, Xq + (size_t)b * q * batch->max_d, (size_t)q * batch->ctx[b]->k * sizeof(double));
+    memcpy(batch->ctx[b]->hXq, Xq + (size_t)b * q * batch->max_d, (size_t)q * batch->ctx[b]->st.k * sizeof(double));
   BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, c0->hXq, batch->hzs, (size_t)q * kmax * sizeof(double), B, hipMemcpyHostToDevice, s));
   if (const int rc = batch_put_best_f(batch, best_f)) return rc;
   const AcqParams p = batch_params(batch, maximize, acq, 0);
@@ -2094,34 +2061,33 @@ static int batch_score_enqueue(pcabo_batch* batch, const double* Xq, int q, cons
                nullptr, 0, nullptr, nullptr, batch_ab(batch, 0, 0), B, 0);
   BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (size_t)q * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipGetLastError());
-  batch->score_enqueued = true;
+  batch->st.scoring_begun();
   return PCABO_OK;
 }
 
 static int batch_score_collect(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq, double* val,
                                int* status) {
   if (!batch) return PCABO_ERR_ARG;
-  if (!batch->score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval_end: no _begin before it%s", "");
+  if (!batch->st.score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval_end: no _begin before it%s", "");
   if (const int rc = batch_score_args(batch, Xq, q, best_f, acq, val != nullptr)) return rc;
   BHIPCHK(hipSetDevice(batch->device));
   BHIPCHK(wait_stream(batch->stream));
   BHIPCHK(hipGetLastError());
-  batch->score_enqueued = false;
-  batch->gp_pending = false; batch->have_gp = true;
+  batch->st.scoring_ended();
   int worst = PCABO_OK;
   for (int b = 0; b < batch->B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
     int st = PCABO_OK;
     if (c->hm->chol_info != 0) {
-      // rare: this run's K needed jitter (psd_safe_cholesky: 1e-8, 1e-7, 1e-6) - redo it alone, then score again
+      // rare: this run's K needed jitter (psd_safe_cholesky: 1e-8, 1e-7, 1e-6) - redo it alone (its own record is told how that
+      // ended), then score again
       st = factor_attempts(c, 1);
       if (st == PCABO_OK) {
-        c->have_gp = true;
-        if (batch->dev_lbfgsb) launch_rt_build(c->stream, c->dR, c->n, c->NP, c->ld, c->dGram);
+        if (batch->dev_lbfgsb) { launch_rt_build(c->stream, c->dR, c->st.n, c->st.NP, c->ld, c->dGram); c->st.rt_rebuilt(); }
         st = pcabo_acq_eval(c, Xq + (size_t)b * q * batch->max_d, q, best_f[b], maximize, acq, c->hVal, nullptr);
       }
     }
-    c->have_gp = st == PCABO_OK;
+    c->st.follow(batch->st, c->st.own().ended(st == PCABO_OK));
     if (st == PCABO_OK) memcpy(val + (size_t)b * q, c->hVal, (size_t)q * sizeof(double));
     if (status) status[b] = st;
     if (st != PCABO_OK) worst = st;
@@ -2195,7 +2161,7 @@ struct PostSite {
   pcabo_batch* batch = nullptr;      // ... or the batch: whose error text is written
   pcabo_ctx* c0;                     // the context, or run 0: dXq, dKS and dPartial of the launches
   hipStream_t s; int device, B = 1; size_t zs = 0;
-  bool busy, have_gp;
+  GpReady ready;                     // the owner's record on whether a call on the conditioned model can go ahead
   int xq_cols;                       // coordinates per staged query: k, or the largest k of the runs
   GpModel m; AcqParams p; AcqBatch ab; double noise;
   char** post_slot; size_t post_v, post_bytes, vzs = 0;   // the runs' V | cov blocks: V's doubles, a block's bytes, the launches' stride
@@ -2206,19 +2172,19 @@ struct PostSite {
       : c0(run0), post_slot(post), post_v((size_t)run0->lay.s.NPcap * run0->max_q),
         post_bytes(((post_v + (size_t)max_q * max_q) * sizeof(double) + 255) & ~(size_t)255), sample_slot(sample), L(max_q) {}
   explicit PostSite(pcabo_ctx* c) : PostSite(c, c->max_q, &c->dPostV, &c->dSample) {
-    ctx = c; s = c->stream; device = c->device; busy = c->gp_pending; have_gp = c->have_gp; xq_cols = c->k; noise = c->noise;
+    ctx = c; s = c->stream; device = c->device; ready = c->st.gp_ready(); xq_cols = c->st.k; noise = c->st.noise;
     m = gp_model(c); p = make_params(c, 0.0, 1, PCABO_ACQ_UCB, 0);      // (the kernels read 1 / lengthscale and the kernel code)
     if (c->ptr_mode != PCABO_PTR_HOST) in = out = hipMemcpyDeviceToDevice;
   }
   explicit PostSite(pcabo_batch* b) : PostSite(b->ctx[0], b->max_q, &b->dPost, &b->dSample) {
-    batch = b; s = b->stream; device = b->device; B = b->B; zs = b->zs; vzs = post_bytes; szs = L.bytes; noise = b->noise;
-    busy = b->gp_pending || b->score_enqueued || b->opt_enqueued || b->imap_enqueued; have_gp = b->have_gp; xq_cols = batch_max_k(b);
+    batch = b; s = b->stream; device = b->device; B = b->B; zs = b->zs; vzs = post_bytes; szs = L.bytes; noise = b->st.m.noise;
+    ready = b->st.gp_ready(); xq_cols = batch_max_k(b);
     m = gp_model(b, xq_cols); p = batch_params(b, 1, PCABO_ACQ_UCB, 0); ab = batch_ab(b, 0, 0);
   }
   int fail(int code, const char* fmt, const char* a = "", int v = 0) const {
     return batch ? bset_err(batch, code, fmt, a, v) : set_err(ctx, code, fmt, a, v);
   }
-  bool live(int b) const { return !batch || (batch->active[b] && batch->ctx[b]->have_gp); }   // is run b's result handed out?
+  bool live(int b) const { return !batch || (batch->active[b] && batch->ctx[b]->st.conditioned()); }   // is run b's result handed out?
   double* V() const { return reinterpret_cast<double*>(*post_slot); }
   double* cov(int b = 0) const { return reinterpret_cast<double*>(*post_slot + (size_t)b * post_bytes) + post_v; }
   char* blk(int b = 0) const { return *sample_slot + (size_t)b * L.bytes; }
@@ -2233,10 +2199,10 @@ struct PostSite {
 
 // The state every call on a conditioned model needs: nothing of the context or the batch in flight, and a GP to ask.
 static int post_state_check(const PostSite& w, const char* name) {
-  if (w.busy)
+  if (w.ready == GP_IN_FLIGHT)
     return w.fail(PCABO_ERR_ARG, w.batch ? "%s: a conditioning or a _begin call of this batch has not been ended"
                                          : "%s: a conditioning is in flight, call pcabo_gp_condition_end first", name);
-  if (!w.have_gp) return w.fail(PCABO_ERR_ARG, w.batch ? "%s: no conditioned GP" : "%s: no conditioned GP, call pcabo_gp_condition first", name);
+  if (w.ready == GP_NONE) return w.fail(PCABO_ERR_ARG, w.batch ? "%s: no conditioned GP" : "%s: no conditioned GP, call pcabo_gp_condition first", name);
   return PCABO_OK;
 }
 
@@ -2460,16 +2426,15 @@ static GpModel ext_model(const PostSite& w, int n) { GpModel m = w.m; m.n = n; m
 
 // The header: the rung, and the info word cleared.  hdr lives until the caller has waited for the stream.
 static int ext_put_header(const PostSite& w, const ExtScratch& e, ExtHeader* hdr) {
-  *hdr = ExtHeader{w.ctx->rung, 0, 0};
+  *hdr = ExtHeader{w.ctx->st.rung, 0, 0};
   PHIPCHK(hipMemcpyAsync(e.small + EXT_HDR_RUNG, hdr, sizeof(ExtHeader), hipMemcpyHostToDevice, w.s));
   return PCABO_OK;
 }
 
 // The host's side of a changed n: the counts, the tickets where NP changed, the transposed root inverse marked stale.
 static int ext_set_n(const PostSite& w, int n) {
-  pcabo_ctx* ctx = w.ctx;
-  ctx->n = n; ctx->NP = round_up(n, PCABO_BS); ctx->rt_stale = true;
-  return ext_tickets(ctx, w.s, ctx->NP, &ctx->cnt_S);
+  w.ctx->st.n_changed(n);
+  return ext_tickets(w.ctx, w.s);
 }
 
 // alpha = R^T (R y_s) on n points - the conditioning's own launches
@@ -2481,7 +2446,7 @@ static void ext_alpha(const PostSite& w, int n) {
 // Points n0 .. are taken back (the header is on the stream already) and alpha follows; no wait.
 static int ext_take_back(const PostSite& w, const ExtScratch& e, int n0, int n_now) {
   pcabo_ctx* c = w.ctx;
-  launch_ext_truncate(w.s, e, n0, c->k, round_up(n_now, PCABO_BS), c->ld, c->dL, c->dR, c->dZnT, c->dAT, c->dNrm, c->dYs);
+  launch_ext_truncate(w.s, e, n0, c->st.k, round_up(n_now, PCABO_BS), c->ld, c->dL, c->dR, c->dZnT, c->dAT, c->dNrm, c->dYs);
   if (const int rc = ext_set_n(w, n0)) return rc;
   ext_alpha(w, n0);
   return PCABO_OK;
@@ -2505,7 +2470,7 @@ int pcabo_gp_extend(pcabo_ctx* ctx, const double* Zp, const double* yp, int p, i
   if (believer) yp = nullptr;
   if (p < 1) return w.fail(PCABO_ERR_ARG, "%s: p must be at least 1", name);
   if (const int rc = post_state_check(w, name)) return rc;
-  const int n0 = ctx->n, k = ctx->k;
+  const int n0 = ctx->st.n, k = ctx->st.k;
   if (n0 + p > ctx->max_n) return w.fail(PCABO_ERR_ARG, "%s: n + p exceeds max_n (%d)", name, ctx->max_n);
   if ((round_up(n0 + p, PCABO_BS) + 255) / 256 > EXT_MU_MAX) return w.fail(PCABO_ERR_ARG, "%s: n + p beyond what the kernels cover", name);
   if (w.in == hipMemcpyHostToDevice) {                 // host pointers: every coordinate and value
@@ -2552,8 +2517,8 @@ int pcabo_gp_truncate(pcabo_ctx* ctx, int n0) {
   if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch", name);
   const PostSite w(ctx);
   if (const int rc = post_state_check(w, name)) return rc;
-  const int n = ctx->n;
-  if (n0 < ctx->n_base || n0 > n) return w.fail(PCABO_ERR_ARG, "%s: n0 must lie in n_base .. n", name);
+  const int n = ctx->st.n;
+  if (n0 < ctx->st.n_base || n0 > n) return w.fail(PCABO_ERR_ARG, "%s: n0 must lie in n_base .. n", name);
   if (n0 == n) return PCABO_OK;
   PHIPCHK(hipSetDevice(w.device));
   const ExtScratch e(ctx->dPartial, ctx->lay.s);
@@ -2565,15 +2530,15 @@ int pcabo_gp_truncate(pcabo_ctx* ctx, int n0) {
 
 int pcabo_gp_extended(pcabo_ctx* ctx, int* n_base, int* n) {
   if (!ctx) return PCABO_ERR_ARG;
-  if (n_base) *n_base = ctx->n_base;
-  if (n) *n = ctx->n;
+  if (n_base) *n_base = ctx->st.n_base;
+  if (n) *n = ctx->st.n;
   return PCABO_OK;
 }
 #undef PHIPCHK
 
 // a run's status at the start of an optimise call: parked by the caller, without a GP, or taking part
 static int batch_run_status(const pcabo_batch* batch, int b) {
-  return !batch->active[b] ? PCABO_ERR_ARG : !batch->ctx[b]->have_gp ? PCABO_ERR_NOT_PD : PCABO_OK;
+  return !batch->active[b] ? PCABO_ERR_ARG : !batch->ctx[b]->st.conditioned() ? PCABO_ERR_NOT_PD : PCABO_OK;
 }
 
 // ---- pcabo_batch_optimize_acqf with PCABO_OPT_DEVICE_LBFGSB: every restart group's L-BFGS-B inside one launch of k_lbfgsb_group
@@ -2585,13 +2550,13 @@ static int batch_run_status(const pcabo_batch* batch, int b) {
 static bool device_opt_eligible(const pcabo_batch* batch, int num_restarts, int batch_limit, const double* bounds, int maxiter,
                                 std::vector<int>* act) {
   const int MD = batch->max_d, kmax = batch_max_k(batch);
-  if (!lbfgsb_device_possible(batch->NP, kmax, batch_limit) || maxiter < 1 ||
+  if (!lbfgsb_device_possible(batch->st.m.NP, kmax, batch_limit) || maxiter < 1 ||
       !opt_fits(batch->ctx[0]->lay, num_restarts, opt_groups(num_restarts, batch_limit), kmax))
     return false;
   act->clear();
   for (int b = 0; b < batch->B; ++b) {
     if (batch_run_status(batch, b) != PCABO_OK) continue;
-    const int k = batch->ctx[b]->k;
+    const int k = batch->ctx[b]->st.k;
     const double* bd = bounds + (size_t)b * 2 * MD;
     for (int j = 0; j < k; ++j)
       if (!std::isfinite(bd[j]) || !std::isfinite(bd[k + j]) || bd[j] > bd[k + j]) return false;
@@ -2611,12 +2576,12 @@ static int device_opt_launch(pcabo_batch* batch, int nent, int mode, int num_res
   const int B = batch->B, kmax = batch_max_k(batch);
   for (int e = 0; e < nent; ++e) {
     pcabo_ctx* c = batch->ctx[batch->hOptTab[e] >> 16];
-    if (c->rt_stale) { launch_rt_build(s, c->dR, c->n, c->NP, c->ld, c->dGram); c->rt_stale = false; }
+    if (c->st.rt_stale) { launch_rt_build(s, c->dR, c->st.n, c->st.NP, c->ld, c->dGram); c->st.rt_rebuilt(); }
   }
   BHIPCHK(hipMemcpyAsync(batch->dOptTab, batch->hOptTab, (size_t)nent * sizeof(unsigned), hipMemcpyHostToDevice, s));
   BHIPCHK(hipMemcpy2DAsync(c0->dXq, batch->zs, c0->hXq, batch->hzs, xq_opt_points(num_restarts, kmax).count * sizeof(double), B, hipMemcpyHostToDevice, s));
   if (launch_lbfgsb_group(s, batch->dOptTab, nent, mode, num_restarts, maxiter, gp_model(batch, kmax), c0->dXq, c0->dGram, c0->dBestF,
-                          c0->dK, 1.0 / batch->lengthscale, maximize ? 1 : 0, acq, batch->kernel, c0->dGrad, c0->dVal, batch->zs,
+                          c0->dK, 1.0 / batch->st.m.lengthscale, maximize ? 1 : 0, acq, batch->st.m.kernel, c0->dGrad, c0->dVal, batch->zs,
                           batch_hyp(batch), batch_limit) != 0)
     return bset_err(batch, PCABO_ERR_HIP, "the device-resident optimiser could not be launched%s", "");
   BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (back.start + back.count) * sizeof(double), B, hipMemcpyDeviceToHost, s));
@@ -2638,32 +2603,32 @@ static int device_opt_enqueue(pcabo_batch* batch, const std::vector<int>& act, c
       }
   for (int b : act) {
     pcabo_ctx* c = batch->ctx[b];
-    const int k = c->k;
+    const int k = c->st.k;
     memcpy(c->hXq, ics + (size_t)b * num_restarts * MD, (size_t)num_restarts * k * sizeof(double));
     memcpy(c->hXq + (size_t)num_restarts * k, bounds + (size_t)b * 2 * MD, (size_t)2 * k * sizeof(double));
   }
   if (nent > 0)
     if (const int rc = device_opt_launch(batch, nent, 1, num_restarts, batch_limit, maxiter, maximize, acq, val_opt_records(ngroups))) return rc;
-  batch->opt_act = act; batch->opt_restarts = num_restarts; batch->opt_limit = batch_limit; batch->opt_enqueued = true;
+  batch->opt_act = act; batch->st.opt_begun(num_restarts, batch_limit);
   return PCABO_OK;
 }
 
 // Device mode, second half: wait, then candidates, values and the kernel's eight counters per restart group to the caller.
 static int device_opt_collect(pcabo_batch* batch, int num_restarts, int batch_limit, double* cand, double* vals, int* info, int* failed,
                               int* status) {
-  if (!batch->opt_enqueued || batch->opt_restarts != num_restarts || batch->opt_limit != batch_limit)
+  if (!batch->st.opt_matches(num_restarts, batch_limit))
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_end: no matching _begin before it%s", "");
   const int B = batch->B, MD = batch->max_d, ngroups = opt_groups(num_restarts, batch_limit);
   std::vector<int> run_status(B);
   for (int b = 0; b < B; ++b) run_status[b] = batch_run_status(batch, b);
-  batch->opt_enqueued = false;
+  batch->st.opt_ended();
   BHIPCHK(wait_stream(batch->stream));
   BHIPCHK(hipGetLastError());
   batch->dbg_groups = ngroups; batch->dbg_branches.clear();
   batch->dbg_group_out.assign((size_t)B * ngroups * 8, 0.0);
   for (int b : batch->opt_act) {
     const pcabo_ctx* c = batch->ctx[b];
-    const int k = c->k;
+    const int k = c->st.k;
     int any_failed = 0;
     std::copy(c->hVal + val_opt_record(0), c->hVal + val_opt_record(ngroups), batch->dbg_group_out.begin() + (size_t)b * ngroups * 8);
     for (int gi = 0; gi < ngroups; ++gi) {
@@ -2695,7 +2660,7 @@ static int batch_optimize_twin(pcabo_batch* batch, const std::vector<int>& act, 
   for (int b : act) {
     pcabo_ctx* c = batch->ctx[b];
     // (the device steps in the 64-lane tree order of lbfgsb.cpp: so does its twin)
-    runs[b].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, num_restarts, batch_limit, c->k, maxiter, 1);
+    runs[b].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, num_restarts, batch_limit, c->st.k, maxiter, 1);
     runs[b].bind(c->hXq, c->hVal, c->hGrad);
   }
   int nent = 0;
@@ -2714,7 +2679,7 @@ static int batch_optimize_twin(pcabo_batch* batch, const std::vector<int>& act, 
   std::vector<std::pair<int, const RestartGroup*>> redo;
   for (int b : act) {
     if (runs[b].status != PCABO_OK) continue;
-    const int k = batch->ctx[b]->k;
+    const int k = batch->ctx[b]->st.k;
     double* cb = cand + (size_t)b * num_restarts * MD;
     runs[b].end_points(cb, vals + (size_t)b * num_restarts, [&](const RestartGroup& rg) {
       memcpy(runs[b].xq + (size_t)rg.q0 * k, cb + (size_t)rg.q0 * k, (size_t)rg.nq * k * sizeof(double));
@@ -2775,7 +2740,7 @@ static int batch_optimize_host(pcabo_batch* batch, const double* ics, int num_re
     pcabo_ctx* c = batch->ctx[b];
     runs[b].status = batch_run_status(batch, b);
     if (runs[b].status != PCABO_OK) continue;
-    runs[b].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, num_restarts, batch_limit, c->k, maxiter);
+    runs[b].init(ics + (size_t)b * num_restarts * MD, bounds + (size_t)b * 2 * MD, num_restarts, batch_limit, c->st.k, maxiter);
     runs[b].bind(c->hXq, c->hVal, c->hGrad);
   }
   std::atomic<int> hip_failed{0};
@@ -2788,7 +2753,7 @@ static int batch_optimize_host(pcabo_batch* batch, const double* ics, int num_re
     if (hipSetDevice(batch->device) != hipSuccess) { hip_failed.store(1); return; }
     std::vector<int> mine;
     for (int b = g; b < B; b += G) mine.push_back(b);
-    const bool use_group = batch->group_acq && batch_limit <= PCABO_GROUP_Q && acq_group_possible(batch->NP, kmax);
+    const bool use_group = batch->group_acq && batch_limit <= PCABO_GROUP_Q && acq_group_possible(batch->st.m.NP, kmax);
     hipStream_t st = batch->gstream[g];
     QueryArgs tab;                                   // the launch table (travels in the kernel arguments)
     unsigned* ent = reinterpret_cast<unsigned*>(tab.x);
@@ -2830,7 +2795,7 @@ static int batch_optimize_host(pcabo_batch* batch, const double* ics, int num_re
       if (run.status != PCABO_OK) continue;
       double* cb = cand + (size_t)b * num_restarts * MD;
       if (run.end_points(cb, vals + (size_t)b * num_restarts) == 0) continue;
-      memcpy(run.xq, cb, (size_t)num_restarts * batch->ctx[b]->k * sizeof(double));
+      memcpy(run.xq, cb, (size_t)num_restarts * batch->ctx[b]->st.k * sizeof(double));
       for (int j = 0; j < num_restarts; ++j) ent[nent++] = query_entry(b, j);
       redo.push_back(b);
     }
@@ -2841,7 +2806,7 @@ static int batch_optimize_host(pcabo_batch* batch, const double* ics, int num_re
   };
   batch->pool.run(gang);
   if (hip_failed.load()) {
-    batch->cnt_dirty = true;
+    batch->st.m.launch_may_have_died();
     (void)hipDeviceSynchronize();
     return bset_err(batch, PCABO_ERR_HIP, "an acquisition launch of the batch failed or did not answer%s", "");
   }
@@ -2860,9 +2825,9 @@ int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_res
   if (!ics || !bounds || !best_f || !cand || !vals || num_restarts < 1 || batch_limit < 1 || num_restarts > PCABO_INLAUNCH_MAXQ)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: bad argument (num_restarts <= 32)%s", "");
   if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: %s", why);
-  if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: no conditioned GP%s", "");
+  if (!batch->st.m.conditioned()) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: no conditioned GP%s", "");
   // (the pinned point / value buffers and the runs' best_f words belong to an enqueued call until its _end)
-  if (batch->opt_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: an optimisation of this batch is already enqueued%s", "");
+  if (batch->st.opt_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: an optimisation of this batch is already enqueued%s", "");
   BHIPCHK(hipSetDevice(batch->device));
   if (const int rc = batch_put_best_f(batch, best_f)) return rc;
   batch->dbg_branches.clear(); batch->dbg_group_out.clear();      // (a call that takes the host-paced path leaves no debug record)
@@ -2885,8 +2850,8 @@ int pcabo_batch_optimize_acqf_begin(pcabo_batch* batch, const double* ics, int n
   if (!ics || !bounds || !best_f || num_restarts < 1 || batch_limit < 1 || num_restarts > PCABO_INLAUNCH_MAXQ)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: bad argument (num_restarts <= 32)%s", "");
   if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: %s", why);
-  if (!batch->have_gp) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: no conditioned GP%s", "");
-  if (batch->opt_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: an optimisation of this batch is already enqueued%s", "");
+  if (!batch->st.m.conditioned()) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf_begin: no conditioned GP%s", "");
+  if (batch->st.opt_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_optimize_acqf: an optimisation of this batch is already enqueued%s", "");
   if (batch->dev_lbfgsb != 1) return 1;
   BHIPCHK(hipSetDevice(batch->device));
   if (const int rc = batch_put_best_f(batch, best_f)) return rc;
@@ -2910,22 +2875,22 @@ int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, con
   if (!Xq || !best_f || !val || !grad || q < 1 || q > PCABO_INLAUNCH_MAXQ)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: bad argument (q <= 32)%s", "");
   if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: %s", why);
-  if (!batch->have_gp || !batch->dev_lbfgsb)
+  if (!batch->st.m.conditioned() || !batch->dev_lbfgsb)
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: needs a conditioned GP and PCABO_OPT_DEVICE_LBFGSB%s", "");
   // the pinned table / point / value / gradient buffers below belong to an enqueued call until its _end has collected them
-  if (batch->opt_enqueued || batch->score_enqueued || batch->imap_enqueued)
+  if (batch->st.begin_pending())
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: a _begin call of this batch has not been ended%s", "");
   BHIPCHK(hipSetDevice(batch->device));
   const int MD = batch->max_d;
-  if (!lbfgsb_device_possible(batch->NP, batch_max_k(batch), PCABO_GROUP_Q) || !opt_fits(batch->ctx[0]->lay, q, 0, batch_max_k(batch)))
+  if (!lbfgsb_device_possible(batch->st.m.NP, batch_max_k(batch), PCABO_GROUP_Q) || !opt_fits(batch->ctx[0]->lay, q, 0, batch_max_k(batch)))
     return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_device_acq_eval: shape beyond the device optimiser (n <= 512, k <= 40)%s", "");
   if (const int rc = batch_put_best_f(batch, best_f)) return rc;
   std::vector<int> runs;
-  for (int b = 0; b < batch->B; ++b) if (batch->ctx[b]->have_gp) runs.push_back(b);
+  for (int b = 0; b < batch->B; ++b) if (batch->ctx[b]->st.conditioned()) runs.push_back(b);
   int nent = 0;
   for (int b : runs) {
     pcabo_ctx* c = batch->ctx[b];
-    memcpy(c->hXq, Xq + (size_t)b * q * MD, (size_t)q * c->k * sizeof(double));
+    memcpy(c->hXq, Xq + (size_t)b * q * MD, (size_t)q * c->st.k * sizeof(double));
     for (int q0 = 0; q0 < q; q0 += PCABO_GROUP_Q)
       batch->hOptTab[nent++] = group_entry(b, q0, std::min(PCABO_GROUP_Q, q - q0));
   }
@@ -2936,7 +2901,7 @@ int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, con
   for (int b : runs) {
     const pcabo_ctx* c = batch->ctx[b];
     memcpy(val + (size_t)b * q, c->hVal, (size_t)q * sizeof(double));
-    memcpy(grad + (size_t)b * q * MD, c->hGrad, (size_t)q * c->k * sizeof(double));
+    memcpy(grad + (size_t)b * q * MD, c->hGrad, (size_t)q * c->st.k * sizeof(double));
   }
   return PCABO_OK;
 }
@@ -2944,27 +2909,27 @@ int pcabo_batch_device_acq_eval(pcabo_batch* batch, const double* Xq, int q, con
 // the inverse map of every run's candidate in two halves (x_ok: the caller's x is there - asked before anything is written)
 static int batch_inverse_map_enqueue(pcabo_batch* batch, const double* z, bool x_ok = true) {
   if (!batch || !z || !x_ok) return PCABO_ERR_ARG;
-  if (batch->n == 0 || batch->wpca_uncollected) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_inverse_map: no weighted PCA collected%s", "");
+  if (!batch->st.wpca_on_host()) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_inverse_map: no weighted PCA collected%s", "");
   BHIPCHK(hipSetDevice(batch->device));
   hipStream_t s = batch->stream;
   pcabo_ctx* c0 = batch->ctx[0];
-  const int B = batch->B, MD = batch->max_d, d = batch->d;
-  for (int b = 0; b < B; ++b) memcpy(batch->ctx[b]->hXq, z + (size_t)b * MD, (size_t)batch->ctx[b]->k * sizeof(double));
+  const int B = batch->B, MD = batch->max_d, d = batch->st.m.d;
+  for (int b = 0; b < B; ++b) memcpy(batch->ctx[b]->hXq, z + (size_t)b * MD, (size_t)batch->ctx[b]->st.k * sizeof(double));
   BHIPCHK(hipMemcpy2DAsync(c0->dZq, batch->zs, c0->hXq, batch->hzs, (size_t)MD * sizeof(double), B, hipMemcpyHostToDevice, s));
   launch_inverse_map(s, c0->dZq, c0->dComps, c0->dDataMean, c0->dPcaMean, 0, d, c0->dXout, c0->dK, batch_zb(batch));
   BHIPCHK(hipMemcpy2DAsync(small_at(c0, small_imap_x(c0->lay.s)), batch->hzs, c0->dXout, batch->zs, (size_t)d * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipGetLastError());
-  batch->imap_enqueued = true;
+  batch->st.imap_begun();
   return PCABO_OK;
 }
 static int batch_inverse_map_collect(pcabo_batch* batch, double* x) {
   if (!batch || !x) return PCABO_ERR_ARG;
-  if (!batch->imap_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_inverse_map_end: no _begin before it%s", "");
+  if (!batch->st.imap_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_inverse_map_end: no _begin before it%s", "");
   BHIPCHK(hipSetDevice(batch->device));
-  batch->imap_enqueued = false;
+  batch->st.imap_ended();
   BHIPCHK(wait_stream(batch->stream));
   BHIPCHK(hipGetLastError());
-  const int d = batch->d;
+  const int d = batch->st.m.d;
   for (int b = 0; b < batch->B; ++b) memcpy(x + (size_t)b * d, small_at(batch->ctx[b], small_imap_x(batch->ctx[b]->lay.s)), (size_t)d * sizeof(double));
   return PCABO_OK;
 }
