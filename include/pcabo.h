@@ -273,7 +273,8 @@ int pcabo_gp_loo(pcabo_ctx* ctx, double* mean /*n*/, double* var /*n*/, double* 
  * All or nothing: if d2 of a point is not positive and finite the call returns PCABO_ERR_NOT_PD with the context taken back to the n
  * it had on entry.  PCABO_ERR_ARG, nothing launched and nothing written: p < 1; n + p > max_n; Zp NULL; yp NULL without the believer
  * flag; a coordinate or value that is not finite (host-pointer mode); unknown flag bits; no conditioned GP; between
- * pcabo_gp_condition_begin and its _end; a member context of a batch (the lock-step batches have no such call yet).
+ * pcabo_gp_condition_begin and its _end; a member context of a batch (the lock-step form is pcabo_batch_gp_extend / pcabo_batch_gp_truncate;
+ * pcabo_gp_extended on a member reads its batch's counts).
  * pcabo_gp_truncate takes back the points from n0 on, n_base <= n0 <= n (else PCABO_ERR_ARG), n_base the n of the last conditioning
  * or fit: the leading block of a triangular inverse is the inverse of the leading block, so this is bookkeeping plus alpha on n0
  * points.  After pcabo_gp_truncate(ctx, n_base) every later call returns the bytes it would have returned before the first extend.
@@ -302,7 +303,8 @@ int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x);
 
 /* Introspection used by the parity tests (all [host] outputs, row-major n x n / vectors).
  * After pcabo_gp_mll_ard / pcabo_gp_fit_ard norm_bounds are the FOLDED Normalize bounds the model runs on:
- * hi_c = lo_c + (hi_c - lo_c) l_c (the model's lengthscale is then 1). */
+ * hi_c = lo_c + (hi_c - lo_c) l_c (the model's lengthscale is then 1).
+ * On a member context of a batch that is set aside (pcabo_batch_gp_extend) n is the number of points the run holds, not the batch's. */
 int pcabo_get_gp_state(pcabo_ctx* ctx, double* K_chol /*n*n lower*/, double* Rinv /*n*n lower*/,
                        double* alpha /*n*/, double* y_mean_std /*2*/, double* norm_bounds /*2*k*/);
 int pcabo_get_gram(pcabo_ctx* ctx, double* K /*n*n, symmetric, incl. noise*/);
@@ -457,6 +459,36 @@ int pcabo_batch_gp_posterior_sample(pcabo_batch* batch, const double* Xq /*[B][q
  * nothing launched: the refusals of pcabo_gp_loo; a conditioning that has not been waited for or a _begin call without its _end. */
 int pcabo_batch_gp_loo(pcabo_batch* batch, double* mean /*[B][n]*/, double* var, double* z, double* lpd, double* lpd_sum /*[B]*/,
                        int* status /*[B]*/);
+/* pcabo_gp_extend / pcabo_gp_truncate / pcabo_gp_extended for the runs of a batch in lock-step: ONE launch sequence per point for all
+ * runs, one wait per call.  Host pointers.  Zp[B][p*max_d]: run b's block holds a dense p x k_b array (packed like Xq of
+ * pcabo_batch_gp_posterior); yp[B][p], or NULL with PCABO_EXTEND_BELIEVER (it is then not read); flags: 0 or PCABO_EXTEND_BELIEVER.
+ * Per run the semantics are exactly those of pcabo_gp_extend: transforms and hyperparameters held (after pcabo_batch_gp_fit / _ard
+ * every run's own noise, 1 / lengthscale, mean constant and folded ARD ranges), the points appended one after the other, the rung of
+ * the run's own factorisation.  Every run that takes part ends with the bytes (L, R, alpha, y_s, ZnT, AT, nrm) it would have in a
+ * context of its own, conditioned or fitted on the same data and extended with the same points.  All runs share n: on success the
+ * batch's n becomes n + p and n_base is held; a new conditioning, fit or likelihood evaluation of the batch starts over from n_base.
+ * Runs that take no part - parked by pcabo_batch_set_active, without a GP, or set aside (below): status[b] = PCABO_ERR_ARG; their
+ * blocks of Zp / yp are not read and none of their model bytes is written, by the extend or by the truncate that follows.
+ * A pivot that fails in run b (d2 not positive and finite): run b ALONE is taken back to the bytes it had on entry, status[b] =
+ * PCABO_ERR_NOT_PD; the other runs keep their p points and the call returns PCABO_OK, the failure in status and in
+ * pcabo_batch_last_error.
+ * SET ASIDE: a run with a GP that did not go along with an extend (its pivot failed, or it was parked) holds fewer points than its
+ * batch; it is out of step and is skipped like a run without a GP by every batched model call (posterior, sample, loo, optimise,
+ * device_acq_eval, extend) and by the single-context calls on pcabo_batch_ctx(b), until a pcabo_batch_gp_truncate with n0 <= the n
+ * of entry of the extend it missed - in particular n_base.  From then on it is live again with the bytes it had at n0.  A new
+ * conditioning or fit clears the mark as well; a scoring of the extended batch (pcabo_batch_gp_condition_end_eval* after a fit)
+ * does not: it skips the run (status[b] = PCABO_ERR_ARG, its block of val left alone).  The one call that still answers for such a
+ * run is the reader pcabo_get_gp_state on pcabo_batch_ctx(b), which launches nothing: it hands out the factors at the n the run holds.  While n > n_base pcabo_batch_set_active refuses to change a flag (PCABO_ERR_ARG).
+ * PCABO_ERR_ARG, nothing launched and nothing written: p < 1; n + p > max_n; Zp NULL; yp NULL without the believer flag; unknown
+ * flag bits; a coordinate or value of a run that takes part that is not finite; no conditioned batch; a conditioning or a _begin
+ * half of the batch not yet ended; truncate with n0 outside n_base .. n.
+ * pcabo_batch_gp_truncate takes the points from n0 on back for the runs that hold rows beyond n0 (n0 == n: nothing to do); after a
+ * truncate to n_base every later call of every run returns the bytes it would have returned before the first extend.
+ * status[B] may be NULL.  pcabo_batch_gp_extended reads the batch's counts; either pointer may be NULL. */
+int pcabo_batch_gp_extend(pcabo_batch* batch, const double* Zp /*[B][p*max_d]*/, const double* yp /*[B][p] or NULL*/, int p, int flags,
+                          int* status /*[B], may be NULL*/);
+int pcabo_batch_gp_truncate(pcabo_batch* batch, int n0, int* status /*[B], may be NULL*/);
+int pcabo_batch_gp_extended(pcabo_batch* batch, int* n_base, int* n);
 /* Rows M-N for every run (pcabo_optimize_acqf semantics per run).  ics[B][num_restarts*max_d] (dense num_restarts x k_b per
  * block), bounds[B][2*max_d] as pcabo_batch_acq_bounds gives them, best_f[B]; cand[B][num_restarts*max_d] (dense per block),
  * vals[B][num_restarts], info[B][4*ngroups] or NULL, failed[B], status[B]. */
@@ -481,7 +513,8 @@ int pcabo_batch_inverse_map_begin(pcabo_batch* batch, const double* z);
 int pcabo_batch_inverse_map_end(pcabo_batch* batch, double* x);
 /* Park / unpark runs: active[B]; a parked run still goes through the lock-step launches of rows A-K but is skipped by
  * pcabo_batch_optimize_acqf (status PCABO_ERR_ARG).  For runs that failed the way the reference's would (botorch raises on a
- * NaN acquisition gradient, reached once the reference's unclipped out-of-box candidates have blown up the search box). */
+ * NaN acquisition gradient, reached once the reference's unclipped out-of-box candidates have blown up the search box).
+ * PCABO_ERR_ARG for a call that would change a flag while points appended by pcabo_batch_gp_extend have not been taken back. */
 int pcabo_batch_set_active(pcabo_batch* batch, const int* active);
 /* Device time of the phases of the last pcabo_batch_wpca_gp_condition_begin (HIP events on the batch's stream; call once
  * that conditioning has been waited for): ms[0] rows A-C, ms[1] Normalize + Gram, ms[2] Cholesky, ms[3] root inverse + alpha. */

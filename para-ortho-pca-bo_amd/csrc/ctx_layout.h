@@ -41,6 +41,8 @@ static_assert(PCABO_QFLAG_WORDS <= PCABO_OPT_REC_BASE, "the values of a call's r
 #define EXT_HDR_RUNG (PCABO_MAXD + 1)
 #define EXT_HDR_INFO (PCABO_MAXD + 2)
 #define EXT_HDR 2                          // doubles of the header: rung, info word (an int in the second double)
+#define EXT_INFO_SKIP (-1)                 // info word of a run of a batch that takes no part in the call: every kernel leaves it alone
+                                           // (never the 1 + index of a failed point, which is positive)
 #define EXT_MU (PCABO_MAXD + 3)
 #define EXT_MU_MAX 64                      // partial sums: n <= 16384
 #define EXT_SMALL (EXT_MU + EXT_MU_MAX)

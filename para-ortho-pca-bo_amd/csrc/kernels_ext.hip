@@ -17,7 +17,10 @@
 // Every kernel here returns at once where the info word is not 0: the points behind a failed one change nothing.
 // All sums have one order and there are no atomics: the same call on the same state gives the same bytes.
 // The kernels address their operands as the conditioning's do (blockIdx.z = run, zs bytes per run, k from k_dev, 1 / lengthscale
-// and the noise from a run's hyperparameter block); the entry points launch them for a single context: one run, strides 0.
+// and the noise from a run's hyperparameter block).  pcabo_gp_extend launches them for a single context: one run, strides 0;
+// pcabo_batch_gp_extend for all runs of a batch at once, every run with a header of its own.  A run that takes no part in the call
+// has the info word EXT_INFO_SKIP, written by the host: not 0, so the kernels here (and the gated form of launch_alpha between them)
+// leave its bytes alone, and negative, so it is never taken for a failed point.
 #include "pcabo_internal.h"
 #include "acq_math.h"
 

@@ -357,9 +357,11 @@ __global__ __launch_bounds__(256) void k_trinv_cols(const double* __restrict__ L
 
 // ---------------------------------------------------------------------------------------------
 // alpha = K^-1 y_s = R^T (R y_s): two matrix-vector products with the root inverse.
-__global__ __launch_bounds__(256) void k_rmatvec(const double* __restrict__ R, const double* __restrict__ y, int n,
-                                                 int ld, double* __restrict__ t, size_t zs) {
-  ZRUN(R); ZRUN(y); ZRUN(t);
+// Both kernels come in two forms with ONE body each: the plain one, and a gated one for launches over the runs of a batch of which
+// some take no part (pcabo_batch_gp_extend / _truncate): a work-group of a run whose gate word is not 0 returns before it reads or
+// writes anything of that run.  Same loops, same summation order: a live run gets the bits of the plain form.
+__device__ __forceinline__ void rmatvec_run(const double* __restrict__ R, const double* __restrict__ y, int n, int ld,
+                                            double* __restrict__ t) {
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   for (int rr = 0; rr < 4; ++rr) {
     const int i = blockIdx.x * 16 + w * 4 + rr;
@@ -370,14 +372,24 @@ __global__ __launch_bounds__(256) void k_rmatvec(const double* __restrict__ R, c
     if (l == 0) t[i] = (i < n) ? s : 0.0;
   }
 }
+__global__ __launch_bounds__(256) void k_rmatvec(const double* __restrict__ R, const double* __restrict__ y, int n,
+                                                 int ld, double* __restrict__ t, size_t zs) {
+  ZRUN(R); ZRUN(y); ZRUN(t);
+  rmatvec_run(R, y, n, ld, t);
+}
+__global__ __launch_bounds__(256) void k_rmatvec_gated(const double* __restrict__ R, const double* __restrict__ y, int n, int ld,
+                                                       double* __restrict__ t, size_t zs, const int* __restrict__ gate) {
+  if (*zrun(gate, zs, blockIdx.z) != 0) return;
+  ZRUN(R); ZRUN(y); ZRUN(t);
+  rmatvec_run(R, y, n, ld, t);
+}
 
 // out = R^T t, 64 columns per group, 16 waves walking down the rows: every wave reads whole 512-byte row segments
 // (the same row for all its lanes; rows above the group's first column hold only zeros of the lower-triangular R and are
 // skipped group-wise).  Fixed summation order: 4 interleaved accumulators per wave, then the 16 waves in order.
 #define RTM_WAVES 16
-__global__ __launch_bounds__(64 * RTM_WAVES) void k_rtmatvec(const double* __restrict__ R, const double* __restrict__ t,
-                                                             int n, int ld, double* __restrict__ out, size_t zs) {
-  ZRUN(R); ZRUN(t); ZRUN(out);
+__device__ __forceinline__ void rtmatvec_run(const double* __restrict__ R, const double* __restrict__ t, int n, int ld,
+                                             double* __restrict__ out) {
   __shared__ double s_p[RTM_WAVES][64];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int j0 = blockIdx.x * 64, j = j0 + l;
@@ -398,6 +410,18 @@ __global__ __launch_bounds__(64 * RTM_WAVES) void k_rtmatvec(const double* __res
     for (int u = 0; u < RTM_WAVES; ++u) s += s_p[u][l];
     out[j] = (j < n) ? s : 0.0;
   }
+}
+__global__ __launch_bounds__(64 * RTM_WAVES) void k_rtmatvec(const double* __restrict__ R, const double* __restrict__ t,
+                                                             int n, int ld, double* __restrict__ out, size_t zs) {
+  ZRUN(R); ZRUN(t); ZRUN(out);
+  rtmatvec_run(R, t, n, ld, out);
+}
+__global__ __launch_bounds__(64 * RTM_WAVES) void k_rtmatvec_gated(const double* __restrict__ R, const double* __restrict__ t, int n,
+                                                                   int ld, double* __restrict__ out, size_t zs,
+                                                                   const int* __restrict__ gate) {
+  if (*zrun(gate, zs, blockIdx.z) != 0) return;      // (uniform over the work-group: nobody is left waiting at the barrier)
+  ZRUN(R); ZRUN(t); ZRUN(out);
+  rtmatvec_run(R, t, n, ld, out);
 }
 
 // ---- launchers --------------------------------------------------------------------------------
@@ -479,4 +503,9 @@ void launch_alpha(hipStream_t s, const double* R, const double* ys, int n, int N
                   ZB zb) {
   hipLaunchKernelGGL(k_rmatvec, dim3(NP / 16, 1, zb.B), dim3(256), 0, s, R, ys, n, ld, tmp, zb.zs);
   hipLaunchKernelGGL(k_rtmatvec, dim3(NP / 64, 1, zb.B), dim3(64 * RTM_WAVES), 0, s, R, tmp, n, ld, alpha, zb.zs);
+}
+void launch_alpha_gated(hipStream_t s, const double* R, const double* ys, int n, int NP, int ld, double* tmp, double* alpha, ZB zb,
+                        const int* gate) {
+  hipLaunchKernelGGL(k_rmatvec_gated, dim3(NP / 16, 1, zb.B), dim3(256), 0, s, R, ys, n, ld, tmp, zb.zs, gate);
+  hipLaunchKernelGGL(k_rtmatvec_gated, dim3(NP / 64, 1, zb.B), dim3(64 * RTM_WAVES), 0, s, R, tmp, n, ld, alpha, zb.zs, gate);
 }

@@ -13,11 +13,25 @@ enum GpReady { GP_READY, GP_IN_FLIGHT, GP_NONE };      // can a call on the cond
 struct BatchState;
 // what a member run of a batch has of its own: its reduced dimension, how its factorisation ended, and - after a lock-step fit -
 // the hyperparameters it was conditioned at (before a fit: the batch's shared ones)
+// aside_n >= 0: the run is SET ASIDE - it holds a GP of aside_n points while its batch has appended more (pcabo_batch_gp_extend: its
+// pivot failed, or it did not take part).  It counts as a run without a GP until the batch is truncated to n0 <= aside_n.
 struct RunOwn {
-  int k; double rung; bool have_gp; double lengthscale, noise;
-  RunOwn with_k(int k_) const { return {k_, rung, have_gp, lengthscale, noise}; }                   // its wPCA was collected
-  RunOwn started(double ls, double s2) const { return {k, 0.0, false, ls, s2}; }                    // a conditioning of it went out
-  RunOwn ended(bool ok) const { return {k, rung, ok, lengthscale, noise}; }                         // ... and ended
+  int k; double rung; bool have_gp; double lengthscale, noise; int aside_n = -1;
+  RunOwn with_k(int k_) const { return {k_, rung, have_gp, lengthscale, noise, aside_n}; }          // its wPCA was collected
+  RunOwn started(double ls, double s2) const { return {k, 0.0, false, ls, s2, -1}; }                // a conditioning of it went out
+  // ... and ended.  A run set aside had no conditioning: a scoring of its extended, fitted batch ends without a word on it
+  RunOwn ended(bool ok) const { return is_aside() ? *this : RunOwn{k, rung, ok, lengthscale, noise, -1}; }
+  bool is_aside() const { return aside_n >= 0; }
+  bool revives_at(int n0) const { return is_aside() && n0 <= aside_n; }                             // would a truncate to n0 bring it back?
+  // does a truncate of its batch from n to n0 have rows of this run to take back?  A live run holds n, one that the truncate brings
+  // back holds aside_n; a run that stays aside, or has no GP, is left alone
+  bool rows_beyond(int n0, int n) const { return have_gp ? n > n0 : revives_at(n0) && aside_n > n0; }
+  // the batch went on from n_valid points without it: a run with a GP is set aside, one set aside already keeps its smaller n
+  RunOwn set_aside(int n_valid) const {
+    if (!have_gp && !is_aside()) return *this;                                                      // (no GP: nothing to keep)
+    return {k, rung, false, lengthscale, noise, is_aside() && aside_n < n_valid ? aside_n : n_valid};
+  }
+  RunOwn truncated(int n0) const { return revives_at(n0) ? RunOwn{k, rung, true, lengthscale, noise, -1} : *this; }
 };
 
 struct ModelState {
@@ -34,6 +48,8 @@ struct ModelState {
   int cnt_S = 0; bool cnt_dirty = true;
   // eigenvector ping-pong: the buffer the last Jacobi wrote, and the d it was for (the next one of the same d starts from it)
   int gcur = 0, vprev_d = 0;
+  // a member run of a batch only: set aside with a GP of aside_n points (RunOwn), -1: in step with its batch
+  int aside_n = -1;
 
   // ---- questions ----
   bool in_flight() const { return gp_pending; }
@@ -43,7 +59,7 @@ struct ModelState {
   bool wpca_matches(int n_, int k_) const { return have_wpca && n == n_ && k == k_; }      // may a conditioning pass Z == NULL?
   bool warm_start(int d_) const { return vprev_d == d_; }
   bool tickets_need_reset(int slabs) const { return slabs != cnt_S || cnt_dirty; }
-  RunOwn own() const { return {k, rung, have_gp, lengthscale, noise}; }
+  RunOwn own() const { return {k, rung, have_gp, lengthscale, noise, aside_n}; }
 
   // ---- transitions ----
   void wpca_enqueued(int n_, int d_) { gcur ^= 1; vprev_d = d_; wpca_n = n_; wpca_d = d_; }
@@ -63,11 +79,19 @@ struct ModelState {
   void gram_fetched() { rt_stale = true; }                           // K was built where the transposed root inverse lay
   void rt_wanted() { if (have_gp) rt_stale = true; }                 // the device optimiser was switched on behind a conditioning
   void rt_rebuilt() { rt_stale = false; }
+  void root_changed() { rt_stale = true; }                           // a member's L and R grew or shrank with its batch's
   void launch_may_have_died() { cnt_dirty = true; }
   void tickets_reset(int slabs) { cnt_S = slabs; cnt_dirty = false; }
   // question and transition in one: true = the caller enqueues the memset of the tickets now
   bool tickets_reset_if_needed(int slabs) { const bool need = tickets_need_reset(slabs); if (need) tickets_reset(slabs); return need; }
   inline void follow(const BatchState& b, const RunOwn& o);          // a member run after any transition of its batch
+  // a member after its batch's extend (took: it took the points; otherwise it is set aside at n_entry, the batch's n before the
+  // call) and after its batch's truncate to n0 - the ONE statement of these two steps, for pcabo_api.hip and the record's checks
+  inline void follow_extend(const BatchState& b, bool took, int n_entry);
+  inline void follow_truncate(const BatchState& b, int n0);
+  // a member set aside still holds a model: its factors can be READ (pcabo_get_gp_state, which launches nothing), at rows_held()
+  bool holds_factors() const { return have_gp || aside_n >= 0; }
+  int rows_held() const { return aside_n >= 0 ? aside_n : n; }
 };
 
 struct BatchState {
@@ -83,6 +107,8 @@ struct BatchState {
   bool scorable() const { return m.gp_pending || fitted; }           // a conditioning in flight, or a fit (waited for already)
   bool anything_enqueued() const { return m.wpca_uncollected || m.n != 0; }
   bool wpca_on_host() const { return m.n != 0 && !m.wpca_uncollected; }
+  bool extended() const { return m.n > m.n_base; }                   // points appended by pcabo_batch_gp_extend and not taken back
+  bool can_truncate_to(int n0) const { return n0 >= m.n_base && n0 <= m.n; }
   bool opt_matches(int restarts, int limit) const { return opt_enqueued && opt_restarts == restarts && opt_limit == limit; }
   // a reset is due when the batch's record OR any member's says so (set_err marks the member a single-context call ran on)
   template <class Runs> bool tickets_need_reset(int slabs, const Runs& runs) const {
@@ -98,6 +124,10 @@ struct BatchState {
     m.d = d_; m.have_wpca = false; fitted = false;
   }
   void wpca_collected() { m.have_wpca = true; m.wpca_uncollected = false; }
+  // pcabo_batch_gp_extend / pcabo_batch_gp_truncate: all runs share the new n, n_base is held (the members: follow + root_changed)
+  void points_appended(int p) { m.n += p; m.NP = round_up(m.n, PCABO_BS); }
+  void points_taken_back(int n0) { m.n = n0; m.NP = round_up(n0, PCABO_BS); }
+  void extension_forgotten() { points_taken_back(m.n_base); }        // a fit or likelihood evaluation starts over from n_base
   void fit_finished() { m.gp_pending = false; m.have_gp = true; fitted = true; }
   void scoring_begun() { score_enqueued = true; }
   void scoring_ended() { score_enqueued = false; m.gp_pending = false; m.have_gp = true; }
@@ -117,12 +147,22 @@ struct BatchState {
 };
 
 // The ONE way a member's record is written by its batch.  From the batch: the shape but k, the kernel, the wPCA's phase, the
-// ping-pong and the ticket count.  The run's own: RunOwn.  A member never has a conditioning or a wPCA of its own in flight.  Kept:
-// what only calls on the member itself change (rt_stale, zn_recorded, wpca_n / wpca_d) and its dirty mark, which only a reset clears.
+// ping-pong and the ticket count.  The run's own: RunOwn (with its set-aside mark).  A member never has a conditioning or a wPCA of its own in
+// flight.  Kept: what only calls on the member itself change (rt_stale, zn_recorded, wpca_n / wpca_d) and its dirty mark, which only a reset clears.
 inline void ModelState::follow(const BatchState& b, const RunOwn& o) {
   n = b.m.n; n_base = b.m.n_base; d = b.m.d; NP = b.m.NP; kernel = b.m.kernel;
   have_wpca = b.m.have_wpca; gcur = b.m.gcur; vprev_d = b.m.vprev_d;
   cnt_S = b.m.cnt_S; cnt_dirty = cnt_dirty || b.m.cnt_dirty;
   k = o.k; KP = round_up(o.k, 4); rung = o.rung; have_gp = o.have_gp; lengthscale = o.lengthscale; noise = o.noise;
+  aside_n = o.aside_n;
   gp_pending = false; wpca_uncollected = false;
+}
+inline void ModelState::follow_extend(const BatchState& b, bool took, int n_entry) {
+  follow(b, took ? own() : own().set_aside(n_entry));
+  if (took) root_changed();
+}
+inline void ModelState::follow_truncate(const BatchState& b, int n0) {
+  const bool taken_back = own().rows_beyond(n0, n);                  // (n: still the batch's before the call)
+  follow(b, own().truncated(n0));
+  if (taken_back) root_changed();
 }

@@ -1343,10 +1343,11 @@ int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x) {
 int pcabo_get_gp_state(pcabo_ctx* ctx, double* K_chol, double* Rinv, double* alpha, double* y_mean_std,
                        double* norm_bounds) {
   if (!ctx) return PCABO_ERR_ARG;
-  if (!ctx->st.conditioned()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_get_gp_state: call pcabo_gp_condition first%s", "");
+  // (a member of a batch that is set aside - pcabo_batch_gp_extend - still holds factors: they are read at the rows it holds)
+  if (!ctx->st.holds_factors()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_get_gp_state: call pcabo_gp_condition first%s", "");
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const size_t n = ctx->st.n, w = n * sizeof(double), pitch = (size_t)ctx->ld * sizeof(double);
+  const size_t n = ctx->st.rows_held(), w = n * sizeof(double), pitch = (size_t)ctx->ld * sizeof(double);
   if (K_chol) HIPCHK(hipMemcpy2DAsync(K_chol, w, ctx->dL, pitch, w, n, hipMemcpyDeviceToHost, s));
   if (Rinv) HIPCHK(hipMemcpy2DAsync(Rinv, w, ctx->dR, pitch, w, n, hipMemcpyDeviceToHost, s));
   if (alpha) HOST_OUT(alpha, ctx->dAlpha, n, double);
@@ -1655,6 +1656,11 @@ int pcabo_batch_get_profile(pcabo_batch* batch, double* ms) {
 // A-K (on whatever finite data the caller keeps feeding it) but no longer takes part in pcabo_batch_optimize_acqf.
 int pcabo_batch_set_active(pcabo_batch* batch, const int* active) {
   if (!batch || !active) return PCABO_ERR_ARG;
+  // between pcabo_batch_gp_extend and the truncate back to n_base a run that did not take part is out of step: nobody changes sides
+  if (batch->st.extended())
+    for (int b = 0; b < batch->B; ++b)
+      if ((active[b] != 0) != (batch->active[b] != 0))
+        return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_set_active: points are appended (pcabo_batch_gp_extend); truncate to n_base first%s", "");
   for (int b = 0; b < batch->B; ++b) batch->active[b] = active[b] != 0;
   return PCABO_OK;
 }
@@ -1911,6 +1917,13 @@ static int batch_fit_prepare(pcabo_batch* batch, const char* who, bool ard, int 
     (*act)[b] = batch->active[b] ? 1 : 0;
     if (status) status[b] = batch->active[b] ? PCABO_OK : PCABO_ERR_ARG;
   }
+  // behind the last refusal (a refused call changes nothing): points appended by pcabo_batch_gp_extend are forgotten, the fit starts
+  // over from the n_base it was given; the first round's follow() tells the members
+  if (batch->st.extended()) {
+    batch->st.extension_forgotten();
+    if (batch->st.tickets_reset_if_needed(acq_slabs(batch->st.m.NP), batch->run_st))
+      BHIPCHK(hipMemset2DAsync(batch->ctx[0]->dCounters, batch->zs, 0, ticket_bytes(batch->ctx[0]), batch->B, batch->stream));
+  }
   return PCABO_OK;
 }
 
@@ -2078,6 +2091,13 @@ static int batch_score_collect(pcabo_batch* batch, const double* Xq, int q, cons
   for (int b = 0; b < batch->B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
     int st = PCABO_OK;
+    if (c->st.own().is_aside()) {
+      // a scoring of an extended, fitted batch: a run set aside (pcabo_batch_gp_extend) holds fewer points than were scored - it is
+      // skipped like a run without a GP, its block of val left alone, and it stays aside
+      c->st.follow(batch->st, c->st.own().ended(false));
+      if (status) status[b] = PCABO_ERR_ARG;
+      continue;
+    }
     if (c->hm->chol_info != 0) {
       // rare: this run's K needed jitter (psd_safe_cholesky: 1e-8, 1e-7, 1e-6) - redo it alone (its own record is told how that
       // ended), then score again
@@ -2461,7 +2481,7 @@ static int ext_wait(const PostSite& w) {
 int pcabo_gp_extend(pcabo_ctx* ctx, const double* Zp, const double* yp, int p, int flags) {
   if (!ctx) return PCABO_ERR_ARG;
   const char* name = "pcabo_gp_extend";
-  if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch", name);
+  if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch", name);      // (its lock-step form: pcabo_batch_gp_extend)
   const PostSite w(ctx);
   if (!Zp) return w.fail(PCABO_ERR_ARG, "%s: Zp is required", name);
   if (flags & ~PCABO_EXTEND_BELIEVER) return w.fail(PCABO_ERR_ARG, "%s: unknown flag bits", name);
@@ -2514,7 +2534,7 @@ int pcabo_gp_extend(pcabo_ctx* ctx, const double* Zp, const double* yp, int p, i
 int pcabo_gp_truncate(pcabo_ctx* ctx, int n0) {
   if (!ctx) return PCABO_ERR_ARG;
   const char* name = "pcabo_gp_truncate";
-  if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch", name);
+  if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch", name);      // (its lock-step form: pcabo_batch_gp_truncate)
   const PostSite w(ctx);
   if (const int rc = post_state_check(w, name)) return rc;
   const int n = ctx->st.n;
@@ -2532,6 +2552,166 @@ int pcabo_gp_extended(pcabo_ctx* ctx, int* n_base, int* n) {
   if (!ctx) return PCABO_ERR_ARG;
   if (n_base) *n_base = ctx->st.n_base;
   if (n) *n = ctx->st.n;
+  return PCABO_OK;
+}
+
+// ---- the same for the runs of a batch in lock-step (DESIGN.md "Extending the GPs of a batch") -----------------------------------
+// ONE launch sequence per point for all runs (blockIdx.z = run), every run with its own header {rung, info word} in its scratch,
+// written by one strided copy; a run that takes no part (parked, without a GP, set aside) gets the info word EXT_INFO_SKIP and is
+// left alone by the three kernels of kernels_ext.hip and by the gated form of launch_alpha.  One strided copy brings the B info
+// words back, one wait.  A run whose pivot failed has stopped on the device at that point; it alone is taken back to the n of entry
+// with the launches of a single context on its own buffers and is then SET ASIDE (model_state.h) until a truncate reaches that n.
+// The points travel through the runs' pinned hXq to their dXq, as many rows at a time as fit with the widest run's k.
+static bool batch_ext_takes_part(const pcabo_batch* batch, int b) { return batch->active[b] && batch->ctx[b]->st.conditioned(); }
+
+// the headers of all runs: run b's rung, and info 0 where go[b], EXT_INFO_SKIP elsewhere.  hdr lives until the stream was waited for.
+static int batch_ext_put_headers(const PostSite& w, const ExtScratch& e, const std::vector<char>& go, std::vector<ExtHeader>* hdr) {
+  hdr->resize((size_t)w.B);
+  for (int b = 0; b < w.B; ++b) (*hdr)[b] = ExtHeader{w.batch->ctx[b]->st.rung, go[b] ? 0 : EXT_INFO_SKIP, 0};
+  PHIPCHK(hipMemcpy2DAsync(e.small + EXT_HDR_RUNG, w.zs, hdr->data(), sizeof(ExtHeader), sizeof(ExtHeader), w.B, hipMemcpyHostToDevice, w.s));
+  return PCABO_OK;
+}
+// the batch's tickets follow acq_slabs(NP) as a conditioning's do: those of ALL runs, where the batch's record or a member's asks
+static int batch_ext_tickets(const PostSite& w) {
+  pcabo_batch* batch = w.batch;
+  if (!batch->st.tickets_reset_if_needed(acq_slabs(batch->st.m.NP), batch->run_st)) return PCABO_OK;
+  PHIPCHK(hipMemset2DAsync(w.c0->dCounters, w.zs, 0, ticket_bytes(w.c0), w.B, w.s));
+  return PCABO_OK;
+}
+static const int* batch_ext_gate(const ExtScratch& e) { return reinterpret_cast<const int*>(e.small + EXT_HDR_INFO); }
+
+int pcabo_batch_gp_extend(pcabo_batch* batch, const double* Zp, const double* yp, int p, int flags, int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  const char* name = "pcabo_batch_gp_extend";
+  const PostSite w(batch);
+  if (!Zp) return w.fail(PCABO_ERR_ARG, "%s: Zp is required", name);
+  if (flags & ~PCABO_EXTEND_BELIEVER) return w.fail(PCABO_ERR_ARG, "%s: unknown flag bits", name);
+  const bool believer = (flags & PCABO_EXTEND_BELIEVER) != 0;
+  if (!yp && !believer) return w.fail(PCABO_ERR_ARG, "%s: yp is required without PCABO_EXTEND_BELIEVER", name);
+  if (believer) yp = nullptr;
+  if (p < 1) return w.fail(PCABO_ERR_ARG, "%s: p must be at least 1", name);
+  if (const int rc = post_state_check(w, name)) return rc;
+  const int B = w.B, n0 = batch->st.m.n, MD = batch->max_d, kmax = w.xq_cols;
+  if (n0 + p > batch->max_n) return w.fail(PCABO_ERR_ARG, "%s: n + p exceeds max_n (%d)", name, batch->max_n);
+  if ((round_up(n0 + p, PCABO_BS) + 255) / 256 > EXT_MU_MAX) return w.fail(PCABO_ERR_ARG, "%s: n + p beyond what the kernels cover", name);
+  std::vector<char> part((size_t)B, 0);
+  for (int b = 0; b < B; ++b) {                        // every coordinate and value of the runs that take part; the others' are not read
+    if (!(part[b] = batch_ext_takes_part(batch, b))) continue;
+    const double* z = Zp + (size_t)b * p * MD;
+    for (size_t i = 0; i < (size_t)p * batch->ctx[b]->st.k; ++i)
+      if (!std::isfinite(z[i])) return w.fail(PCABO_ERR_ARG, "%s: a coordinate of run %d is not finite", name, b);
+    for (int i = 0; yp && i < p; ++i)
+      if (!std::isfinite(yp[(size_t)b * p + i])) return w.fail(PCABO_ERR_ARG, "%s: a value of run %d is not finite", name, b);
+  }
+  PHIPCHK(hipSetDevice(w.device));
+  pcabo_ctx* c0 = w.c0;
+  const ExtScratch e(c0->dPartial, c0->lay.s);
+  const int* gate = batch_ext_gate(e);
+  const ZB zb = batch_zb(batch);
+  std::vector<ExtHeader> hdr;
+  if (const int rc = batch_ext_put_headers(w, e, part, &hdr)) return rc;
+  const int rows_cap = ext_rows_cap(c0->lay.s, kmax);     // points that fit dXq with their values, at the widest run's k
+  const size_t vals = xq_ext_vals(c0->lay.s, kmax).start;
+  double* dY = yp ? c0->dXq + vals : nullptr;
+  int n = n0;
+  for (int i0 = 0; i0 < p; i0 += rows_cap) {
+    const int rows = std::min(rows_cap, p - i0);
+    if (i0 > 0) PHIPCHK(wait_stream(w.s));               // (the pinned staging goes round again: rare, p beyond rows_cap)
+    for (int b = 0; b < B; ++b) {
+      if (!part[b]) continue;
+      pcabo_ctx* c = batch->ctx[b];
+      const int k = c->st.k;
+      memcpy(c->hXq, Zp + (size_t)b * p * MD + (size_t)i0 * k, (size_t)rows * k * sizeof(double));
+      if (yp) memcpy(c->hXq + vals, yp + (size_t)b * p + i0, (size_t)rows * sizeof(double));
+    }
+    const size_t staged = yp ? vals + (size_t)rows : (size_t)rows * kmax;
+    PHIPCHK(hipMemcpy2DAsync(c0->dXq, w.zs, c0->hXq, batch->hzs, staged * sizeof(double), B, hipMemcpyHostToDevice, w.s));
+    for (int i = 0; i < rows; ++i, ++n) {
+      const GpModel m = ext_model(w, n);
+      launch_ext_ks(w.s, c0->dXq, i, dY, i, m, w.p.inv_ls, w.p.kernel, e, w.ab, B);
+      launch_alpha_gated(w.s, c0->dR, e.ks, m.n, m.NP, m.ld, e.v, e.w, zb, gate);
+      launch_ext_append(w.s, m, e, i0 + i, believer ? 1 : 0, w.noise, w.p.inv_ls, c0->dZnMean, c0->dL, c0->dR, c0->dZnT, c0->dAT,
+                        c0->dNrm, c0->dYs, w.ab, B);
+      if (believer && i0 + i + 1 < p)
+        launch_alpha_gated(w.s, c0->dR, c0->dYs, n + 1, round_up(n + 1, PCABO_BS), c0->ld, c0->dTmp, c0->dAlpha, zb, gate);
+    }
+  }
+  batch->st.points_appended(p);
+  if (const int rc = batch_ext_tickets(w)) return rc;
+  launch_alpha_gated(w.s, c0->dR, c0->dYs, n, round_up(n, PCABO_BS), c0->ld, c0->dTmp, c0->dAlpha, zb, gate);
+  std::vector<int> info((size_t)B, 0);
+  PHIPCHK(hipMemcpy2DAsync(info.data(), sizeof(int), gate, w.zs, sizeof(int), B, hipMemcpyDeviceToHost, w.s));
+  if (const int rc = ext_wait(w)) return rc;
+  // the runs whose pivot failed: each alone back to the bytes of entry (the launches of ext_take_back on the member's own buffers)
+  int failed = 0, first_bad = -1, first_point = 0;
+  for (int b = 0; b < B; ++b) {
+    if (!part[b] || info[b] <= 0) continue;
+    pcabo_ctx* c = batch->ctx[b];
+    const ExtScratch eb(c->dPartial, c->lay.s);
+    hdr[b] = ExtHeader{c->st.rung, 0, 0};
+    PHIPCHK(hipMemcpyAsync(eb.small + EXT_HDR_RUNG, &hdr[b], sizeof(ExtHeader), hipMemcpyHostToDevice, w.s));
+    launch_ext_truncate(w.s, eb, n0, c->st.k, round_up(n, PCABO_BS), c->ld, c->dL, c->dR, c->dZnT, c->dAT, c->dNrm, c->dYs);
+    launch_alpha(w.s, c->dR, c->dYs, n0, round_up(n0, PCABO_BS), c->ld, c->dTmp, c->dAlpha);
+    if (!failed++) { first_bad = b; first_point = info[b] - 1; }
+  }
+  if (failed)
+    if (const int rc = ext_wait(w)) return rc;
+  for (int b = 0; b < B; ++b) {
+    pcabo_ctx* c = batch->ctx[b];
+    const bool ok = part[b] && info[b] == 0;
+    c->st.follow_extend(batch->st, ok, n0);
+    if (status) status[b] = ok ? PCABO_OK : part[b] ? PCABO_ERR_NOT_PD : PCABO_ERR_ARG;
+  }
+  if (failed) {
+    snprintf(batch->err, sizeof(batch->err), "%s: run %d: the bordered matrix is not positive definite at new point %d; %d run(s) "
+             "taken back and set aside until pcabo_batch_gp_truncate", name, first_bad, first_point, failed);
+  }
+  return PCABO_OK;
+}
+
+int pcabo_batch_gp_truncate(pcabo_batch* batch, int n0, int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  const char* name = "pcabo_batch_gp_truncate";
+  const PostSite w(batch);
+  if (const int rc = post_state_check(w, name)) return rc;
+  const int B = w.B, n = batch->st.m.n;
+  if (!batch->st.can_truncate_to(n0)) return w.fail(PCABO_ERR_ARG, "%s: n0 must lie in n_base .. n", name);
+  // who holds rows beyond n0: a live run (n of them), a run set aside that this call brings back (aside_n of them)
+  std::vector<char> go((size_t)B, 0);
+  bool any = false;
+  for (int b = 0; b < B; ++b) {
+    go[b] = batch->ctx[b]->st.own().rows_beyond(n0, n);
+    any = any || go[b];
+  }
+  if (any) {
+    PHIPCHK(hipSetDevice(w.device));
+    pcabo_ctx* c0 = w.c0;
+    const ExtScratch e(c0->dPartial, c0->lay.s);
+    std::vector<ExtHeader> hdr;
+    if (const int rc = batch_ext_put_headers(w, e, go, &hdr)) return rc;
+    launch_ext_truncate(w.s, e, n0, w.xq_cols, round_up(n, PCABO_BS), c0->ld, c0->dL, c0->dR, c0->dZnT, c0->dAT, c0->dNrm, c0->dYs, w.ab, B);
+    batch->st.points_taken_back(n0);
+    if (const int rc = batch_ext_tickets(w)) return rc;
+    launch_alpha_gated(w.s, c0->dR, c0->dYs, n0, round_up(n0, PCABO_BS), c0->ld, c0->dTmp, c0->dAlpha, batch_zb(batch), batch_ext_gate(e));
+    if (const int rc = ext_wait(w)) return rc;
+  } else if (n0 < n) {
+    PHIPCHK(hipSetDevice(w.device));
+    batch->st.points_taken_back(n0);
+    if (const int rc = batch_ext_tickets(w)) return rc;
+    if (const int rc = ext_wait(w)) return rc;
+  }
+  for (int b = 0; b < B; ++b) {
+    pcabo_ctx* c = batch->ctx[b];
+    c->st.follow_truncate(batch->st, n0);
+    if (status) status[b] = batch_ext_takes_part(batch, b) ? PCABO_OK : PCABO_ERR_ARG;
+  }
+  return PCABO_OK;
+}
+
+int pcabo_batch_gp_extended(pcabo_batch* batch, int* n_base, int* n) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (n_base) *n_base = batch->st.m.n_base;
+  if (n) *n = batch->st.m.n;
   return PCABO_OK;
 }
 #undef PHIPCHK

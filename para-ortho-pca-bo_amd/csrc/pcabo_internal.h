@@ -361,6 +361,10 @@ int launch_chol_steps(hipStream_t s, double* L, int NP, int ld, int* info, doubl
 void launch_trinv_diag_w(hipStream_t s, const double* L, int nblk, int ld, double* R, ZB zb = ZB());
 void launch_alpha(hipStream_t s, const double* R, const double* ys, int n, int NP, int ld, double* tmp, double* alpha,
                   ZB zb = ZB());
+// The same two launches for the runs of a batch of which some take no part: gate = run 0's gate word (the others zb.zs bytes apart
+// each); a run whose word is not 0 keeps its tmp and alpha bytes, a run whose word is 0 gets launch_alpha's bits.
+void launch_alpha_gated(hipStream_t s, const double* R, const double* ys, int n, int NP, int ld, double* tmp, double* alpha, ZB zb,
+                        const int* gate);
 // marginal-likelihood pieces of a conditioned state (kernels_fit.hip, Matern-5/2): partial = 1 + M doubles per lower 64 x 64 tile,
 // out[5 + M] = {sum log L_ii, y_s^T alpha, sum alpha, alpha^T alpha, tr K^-1, then M sums}.  The shared lengthscale: M = 1,
 // sum_ij W_ij dK_ij/dlog l.  ard (one lengthscale per input, folded into the Normalize ranges): M = KP, S_c = sum_ij W_ij

@@ -20,6 +20,7 @@ PTR_HOST, PTR_DEVICE = 0, 1
 OPT_RESIDENT, OPT_BESTF_F32, OPT_GROUP_ACQ, OPT_DEVICE_LBFGSB = 0, 1, 2, 3
 OPT_HIDDEN_TAIL = 5
 POST_OBS_NOISE = 1                              # gp_posterior: variance / covariance of an observation (likelihood noise added)
+EXTEND_BELIEVER = 1                             # gp_extend: every point takes the model's own mean there (PCABO_EXTEND_BELIEVER)
 POST_CENTRED = 2                                # gp_posterior_samples: the mean is not added (the centred process)
 POST_MAX_SAMPLES = 1024                         # gp_posterior_samples: most samples of one call
 FIT_THETA0 = (0.006737946999085467, 0.0, 0.0)   # GP fit: (noise, mean constant, raw lengthscale) of a freshly built model
@@ -56,7 +57,8 @@ EXPORTS = [
     "pcabo_gp_mll", "pcabo_gp_fit", "pcabo_gp_mll_ard", "pcabo_gp_fit_ard",
     "pcabo_acq_bounds",
     "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_gp_posterior_sample", "pcabo_batch_gp_posterior_sample", "pcabo_gp_loo", "pcabo_batch_gp_loo",
-    "pcabo_gp_extend", "pcabo_gp_truncate", "pcabo_gp_extended", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
+    "pcabo_gp_extend", "pcabo_gp_truncate", "pcabo_gp_extended",
+    "pcabo_batch_gp_extend", "pcabo_batch_gp_truncate", "pcabo_batch_gp_extended", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
     "pcabo_get_gram", "pcabo_lbfgsb_minimize", "pcabo_lbfgsb_set_vector_kernels", "pcabo_lbfgsb_set_sum_order", "pcabo_sobol_scramble", "pcabo_sobol_draw", "pcabo_sobol_draw_rows", "pcabo_torch_randint2", "pcabo_torch_multinomial_rows", "pcabo_boltzmann_pick_rows", "pcabo_set_profiling",
     "pcabo_get_profile", "pcabo_get_profile_calibration", "pcabo_reset_profile",
     "pcabo_batch_create", "pcabo_batch_destroy", "pcabo_batch_last_error", "pcabo_batch_ctx",
@@ -126,6 +128,9 @@ def _load() -> C.CDLL:
     lib.pcabo_gp_extend.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     lib.pcabo_gp_truncate.argtypes = [vp, C.c_int]
     lib.pcabo_gp_extended.argtypes = [vp, ip, ip]
+    lib.pcabo_batch_gp_extend.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
+    lib.pcabo_batch_gp_truncate.argtypes = [vp, C.c_int, vp]
+    lib.pcabo_batch_gp_extended.argtypes = [vp, ip, ip]
     lib.pcabo_optimize_acqf.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                         vp, vp, vp, ip]
     lib.pcabo_inverse_map.argtypes = [vp, vp, vp]
@@ -516,7 +521,7 @@ class Context:
         Zp = _f64(Zp).reshape(-1, self.k)
         p = Zp.shape[0]
         yv = None if y is None else _f64(y, (p,))
-        self._chk(LIB.pcabo_gp_extend(self._h, _ptr(Zp), _ptr(yv), p, 1 if y is None else 0))      # (PCABO_EXTEND_BELIEVER)
+        self._chk(LIB.pcabo_gp_extend(self._h, _ptr(Zp), _ptr(yv), p, EXTEND_BELIEVER if y is None else 0))
         self.n += p
         return self.n
 
@@ -805,6 +810,63 @@ class Batch:
         return [None if status[b] != 0 else {"samples": samples[b].copy(), "mean": mean[b].copy(), "jitter": float(jitter[b])}
                 for b in range(self.B)]
 
+    # ---- appending points to every run's GP and taking them back (pcabo_batch_gp_extend / pcabo_batch_gp_truncate) -------
+    def _counts(self):
+        nb, n = C.c_int(0), C.c_int(0)
+        self._chk(LIB.pcabo_batch_gp_extended(self._h, C.byref(nb), C.byref(n)))
+        return int(nb.value), int(n.value)
+
+    def _follow_n(self, held=None) -> int:
+        """The batch's n as the library holds it, for this object; the runs' borrowed contexts get the number of points they hold
+        (held[b]; None: the batch's n for all) - a run set aside by gp_extend holds fewer, and its gp_state() reads those."""
+        self.n = self._counts()[1]
+        for b, c in enumerate(self.ctx):
+            c.n = self.n if held is None else int(held[b])
+        return self.n
+
+    def _chk_fit(self, rc: int) -> None:
+        """_chk for a fit or likelihood evaluation: they forget points appended by gp_extend and bring every run back in step, so n
+        follows the library; a refused call changed nothing, and then only the batch's own n is read again."""
+        try:
+            self._chk(rc)
+        except PcaboError:
+            self.n = self._counts()[1]
+            raise
+        self._follow_n()
+
+    def gp_extend(self, Zp_list, y=None):
+        """Context.gp_extend for every run in one launch sequence per point: Zp_list[b] is p x k_b (None for a run the caller knows
+        to be skipped), y is (B, p), or None for believer mode.  Returns (n, status[B]): 0 for a run that took the points, -1 for
+        a run that took no part (parked, without a GP, set aside), -2 for a run whose pivot failed - it alone is taken back and set
+        aside until gp_truncate reaches the n of entry (include/pcabo.h)."""
+        if len(Zp_list) != self.B:
+            raise ValueError(f"Zp_list must have one entry per run ({self.B})")
+        shapes = {np.asarray(z, dtype=np.float64).reshape(-1, int(self.k[b])).shape[0] for b, z in enumerate(Zp_list) if z is not None}
+        if len(shapes) > 1:
+            raise ValueError("every run takes the same number of points")
+        p = shapes.pop() if shapes else (0 if y is None else np.asarray(y).reshape(self.B, -1).shape[1])
+        buf = np.zeros((self.B, max(p, 1) * self.max_d))
+        for b, z in enumerate(Zp_list):
+            if z is not None:
+                buf[b, : p * int(self.k[b])] = np.ascontiguousarray(z, dtype=np.float64).ravel()
+        yv = None if y is None else _f64(y, (self.B, p))
+        status = np.zeros(self.B, dtype=np.int32)
+        self._chk(LIB.pcabo_batch_gp_extend(self._h, _ptr(buf), _ptr(yv), p, EXTEND_BELIEVER if y is None else 0,
+                                            _ptr(status)))
+        new_n = self._counts()[1]
+        return self._follow_n([new_n if status[b] == 0 else c.n for b, c in enumerate(self.ctx)]), status
+
+    def gp_truncate(self, n0=None) -> int:
+        """Take back the appended points of every run from n0 on (None: all of them, back to n_base).  Returns the new n."""
+        n0 = self.n_base if n0 is None else int(n0)
+        self._chk(LIB.pcabo_batch_gp_truncate(self._h, n0, None))
+        return self._follow_n([min(c.n, n0) for c in self.ctx])
+
+    @property
+    def n_base(self) -> int:
+        """The n of the batch's last conditioning or fit: gp_extend appends behind it."""
+        return self._counts()[0]
+
     # ---- opt-in GP hyperparameter fit of all runs in lock-step (pcabo_batch_gp_mll / pcabo_batch_gp_fit) -----------------
     # Both work on the inputs of the last wpca_gp_condition_begin / gp_condition_begin and leave every run conditioned at its
     # own theta; gp_wait_eval / gp_eval_begin + gp_eval_end and optimize_acqf then use the runs' own models.
@@ -814,7 +876,7 @@ class Batch:
         th = _f64(thetas, (self.B, 3))
         loss, grad = np.zeros(self.B), np.zeros((self.B, 3))
         status = np.zeros(self.B, dtype=np.int32)
-        self._chk(LIB.pcabo_batch_gp_mll(self._h, _ptr(th), _ptr(loss), _ptr(grad), _ptr(status)))
+        self._chk_fit(LIB.pcabo_batch_gp_mll(self._h, _ptr(th), _ptr(loss), _ptr(grad), _ptr(status)))
         return [{**Context._fit_result(th[b], loss[b]), "grad": grad[b].copy(), "status": 0} if status[b] == 0
                 else {"status": int(status[b])} for b in range(self.B)]
 
@@ -827,7 +889,7 @@ class Batch:
         th = np.ascontiguousarray(np.broadcast_to(th0, (self.B, 3)), dtype=np.float64).copy()
         loss, info = np.zeros(self.B), np.zeros((self.B, 4), dtype=np.int32)
         status = np.zeros(self.B, dtype=np.int32)
-        self._chk(LIB.pcabo_batch_gp_fit(self._h, _ptr(th), _ptr(loss), _ptr(info), _ptr(status)))
+        self._chk_fit(LIB.pcabo_batch_gp_fit(self._h, _ptr(th), _ptr(loss), _ptr(info), _ptr(status)))
         self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
         return [{**Context._fit_result(th[b], loss[b]), "iterations": int(info[b, 0]), "evaluations": int(info[b, 1]),
                  "warnflag": int(info[b, 2]), "task": int(info[b, 3]), "status": 0} if status[b] == 0
@@ -851,7 +913,7 @@ class Batch:
         th, ks = self._ard_rows(thetas)
         loss, grad = np.zeros(self.B), np.zeros_like(th)
         status = np.zeros(self.B, dtype=np.int32)
-        self._chk(LIB.pcabo_batch_gp_mll_ard(self._h, _ptr(th), th.shape[1], _ptr(loss), _ptr(grad), _ptr(status)))
+        self._chk_fit(LIB.pcabo_batch_gp_mll_ard(self._h, _ptr(th), th.shape[1], _ptr(loss), _ptr(grad), _ptr(status)))
         self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
         return [{**Context._fit_result(th[b, : 2 + k], loss[b], True), "grad": grad[b, : 2 + k].copy(), "status": 0}
                 if status[b] == 0 else {"status": int(status[b])} for b, k in enumerate(ks)]
@@ -863,7 +925,7 @@ class Batch:
         th, ks = self._ard_rows(theta0)
         loss, info = np.zeros(self.B), np.zeros((self.B, 4), dtype=np.int32)
         status = np.zeros(self.B, dtype=np.int32)
-        self._chk(LIB.pcabo_batch_gp_fit_ard(self._h, _ptr(th), th.shape[1], _ptr(loss), _ptr(info), _ptr(status)))
+        self._chk_fit(LIB.pcabo_batch_gp_fit_ard(self._h, _ptr(th), th.shape[1], _ptr(loss), _ptr(info), _ptr(status)))
         self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
         return [{**Context._fit_result(th[b, : 2 + k], loss[b], True), "iterations": int(info[b, 0]),
                  "evaluations": int(info[b, 1]), "warnflag": int(info[b, 2]), "task": int(info[b, 3]), "status": 0}
