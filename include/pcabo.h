@@ -435,6 +435,18 @@ int pcabo_batch_acq_bounds(pcabo_batch* batch, double* bounds);
  * best_f[B]; val[B][q]; status[B] (PCABO_ERR_NOT_PD for a run whose factorisation failed after the jitter retries). */
 int pcabo_batch_gp_condition_end_eval(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize,
                                       int acq, double* val, int* status);
+/* Score q points per run on the batch's model AS IT STANDS - fitted or not, extended by pcabo_batch_gp_extend or not: values only,
+ * the launches of pcabo_batch_gp_condition_end_eval (the GEMM scoring from q = 64, the per-query kernels below), every run's values
+ * bit for bit those of pcabo_acq_eval(values only) on the same run in a context of its own with the same extension.  What the later
+ * proposals of an iteration are scored with: pcabo_batch_gp_condition_end_eval ENDS a conditioning and refuses
+ * an unfitted batch once that has happened.  Arrays as there.  Nothing of the model's phase changes and no run is redone alone.
+ * status[B] (may be NULL): PCABO_ERR_ARG for a run parked by pcabo_batch_set_active, set aside, or without a GP - skipped, its block
+ * of val left alone.  PCABO_ERR_ARG, nothing launched: a bad argument; no conditioned batch; a conditioning that has not been waited
+ * for; a _begin half of the batch (this call's included) not yet ended.  _begin enqueues and returns, _end waits and collects. */
+int pcabo_batch_acq_score(pcabo_batch* batch, const double* Xq /*[B][q*max_d]*/, int q, const double* best_f /*[B]*/, int maximize,
+                          int acq, double* val /*[B][q]*/, int* status /*[B]*/);
+int pcabo_batch_acq_score_begin(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq);
+int pcabo_batch_acq_score_end(pcabo_batch* batch, int q, double* val, int* status);
 /* pcabo_gp_posterior for every run in one launch sequence, each run bit for bit what it takes alone.  Host pointers.
  * Xq[B][q*max_d]: run b's block holds a dense q x k_b array; mean[B][q], var[B][q], cov[B][q*q], each may be NULL (not all three).
  * status[B] (may be NULL): PCABO_ERR_ARG for a run parked by pcabo_batch_set_active and for a run whose factorisation failed - both
@@ -562,12 +574,17 @@ int pcabo_batch_gp_fit_ard(pcabo_batch* batch, double* theta_inout /*B*ld_theta*
  * tables[B][pcabo_bbob_table_doubles(d)]: per run [x_opt(d) | R(d*d) | M(d*d) | aux], generated on the host by the seeded
  * legacy generators (pcabo/bbob.py builds them; layout in pcabo/bbob_device.py).  fid[B] in 15..24.
  * pcabo_bbob_eval: X[B][d] candidates -> raw[B] (value WITHOUT f_opt; `penalty` for a candidate outside [lb, ub]^d, which is
- * not evaluated: PCA_BO.py:248-263) and oob[B] (may be NULL). */
+ * not evaluated: PCA_BO.py:248-263) and oob[B] (may be NULL).
+ * pcabo_bbob_eval_many: m >= 1 candidates per run in ONE launch (grid B x m), X[B][m][d] -> raw[B][m], oob[B][m] (may be NULL):
+ * candidate j of run b gets the bytes pcabo_bbob_eval gives it alone (the same work-group code, one work-group per candidate).
+ * For the q candidates a run proposes per iteration.  The staging buffers grow on the first call that needs
+ * them.  PCABO_ERR_ARG: m < 1 (or > 65535, the grid's second dimension), a NULL obj, X or raw. */
 typedef struct pcabo_objective pcabo_objective;
 int pcabo_bbob_table_doubles(int d);
 int pcabo_bbob_create(int device, int B, int d, const int* fid, const double* tables, pcabo_objective** out);
 int pcabo_bbob_destroy(pcabo_objective* obj);
 int pcabo_bbob_eval(pcabo_objective* obj, const double* X, double lb, double ub, double penalty, double* raw, int* oob);
+int pcabo_bbob_eval_many(pcabo_objective* obj, const double* X, int m, double lb, double ub, double penalty, double* raw, int* oob);
 
 /* ---- Final gather of best-so-far values across the GPUs of a node -------------------------------------
  * Runs are independent (ExperimentRunner.py:137-183: one optimiser object per (function, dimension, instance)), so the

@@ -129,6 +129,11 @@ class DeviceBayesianOptimizer(AbstractBayesianOptimizer):
         # ucb_beta (not in the reference, whose UCB cannot run): with acquisition_function "UCB" every iteration builds
         # UpperConfidenceBound(model, beta=ucb_beta, maximize=...), botorch's own signature.  None keeps the reference's TypeError.
         self._ucb_beta = _acqopt.checked_ucb_beta(kwargs.pop("ucb_beta", None), acquisition_function)
+        # q, q_strategy (not in the reference, whose BATCH_SIZE never reaches optimize_acqf): every iteration proposes q candidates,
+        # one after the other on a model that takes each pending point in - at its own mean ("kriging_believer") or at the min / mean /
+        # max of the values seen ("constant_liar_*") - and evaluates them in that order (pcabo.acqopt.propose).
+        # The last iteration proposes what the budget leaves.  q=1 is the reference's loop.
+        self._q, self._q_strategy = _acqopt.checked_q(kwargs.pop("q", 1), kwargs.pop("q_strategy", "kriging_believer"))
         super().__init__(budget, n_DoE, **kwargs)
         self.random_seed = random_seed
         smoke_test = os.environ.get("SMOKE_TEST")
@@ -210,6 +215,10 @@ class DeviceBayesianOptimizer(AbstractBayesianOptimizer):
             print(self.FINAL_LINE)
         self.restore_random_states()
 
+    def _q_eff(self) -> int:
+        """Candidates of the current iteration: q, or what the budget leaves."""
+        return max(1, min(self._q, self.budget - len(self.f_evals)))
+
     def assign_new_best(self):
         super().assign_new_best()
 
@@ -220,7 +229,7 @@ class DeviceBayesianOptimizer(AbstractBayesianOptimizer):
 
     @abstractmethod
     def optimize_acqf_and_get_observation(self) -> np.ndarray:
-        """The iteration's candidates, one row each, in the space of the model."""
+        """The iteration's candidates (`_q_eff()` of them), one row each, in the space of the model."""
 
     @abstractmethod
     def _observe(self, problem, candidate) -> float:

@@ -189,10 +189,11 @@ class PCA_BO(DeviceBayesianOptimizer):
                 res.put(e)
 
     def _prefetch_noise(self) -> None:
-        """Called once the current iteration's noise is consumed: the next iteration (if there is one) has one more
-        point.  One worker thread per run (creating a thread per iteration cost 0.24 ms of every iteration)."""
-        n = len(self.x_evals)
-        if not self.__prefetch_on or self.__noise_pending or n + 1 >= self.budget:
+        """Called once the current iteration's noise is consumed: the next iteration (if there is one) has as many more
+        points as this one proposes (one, or q).  One worker thread per run (creating a thread per iteration cost 0.24 ms of
+        every iteration)."""
+        n, q_eff = len(self.x_evals), self._q_eff()
+        if not self.__prefetch_on or self.__noise_pending or n + q_eff >= self.budget:
             return
         if self.__noise_thread is None:
             import queue
@@ -202,7 +203,7 @@ class PCA_BO(DeviceBayesianOptimizer):
                                                    daemon=True)
             self.__noise_thread.start()
         self.__noise_pending = True
-        self.__noise_req.put((n + 1, self.dimension))
+        self.__noise_req.put((n + q_eff, self.dimension))
 
     def _stop_noise_worker(self) -> None:
         if self.__noise_thread is None:
@@ -305,14 +306,15 @@ class PCA_BO(DeviceBayesianOptimizer):
         elif self.__gp_pending:
             ctx.gp_wait()
             self.__gp_pending = False
-        new_z, cand, vals, info = _acqopt.optimize_acqf(
+        new_z, infos = _acqopt.propose(
             ctx, bounds, acq.device_scalar, acq.maximize, acq.acq_code, num_restarts, raw_samples, batch_limit, 200,
+            q_eff=self._q_eff(), strategy=self._q_strategy, f_evals=self.f_evals,
             raw=raw, raw_vals=raw_vals, breakdown=self.phase_breakdown,
             trace=self.trace[-1] if self._record_trace else None,
             before_lbfgsb=self._prefetch_noise)   # the draw overlaps with the optimiser's time inside the library; started
         # any earlier it shares the core with the torch ops of the initial pick and doubles their time (0.10 -> 0.21 ms)
         self.timing_logs["optimize_acqf"].append(perf_counter() - start)
-        self.lbfgsb_info.append(info)
+        self.lbfgsb_info.extend(infos)
         return new_z
 
     # ---- row O ------------------------------------------------------------------------------------

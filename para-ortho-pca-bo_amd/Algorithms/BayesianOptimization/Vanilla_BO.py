@@ -66,10 +66,10 @@ class Vanilla_BO(DeviceBayesianOptimizer):
             t0 = perf_counter()            # the raw samples are scored right behind the conditioning: one wait for both
             raw_vals = ctx.gp_wait_eval(raw, acq.device_scalar, acq.maximize, acq.acq_code)
             self.phase_breakdown["raw_eval"] = self.phase_breakdown.get("raw_eval", 0.0) + perf_counter() - t0
-        new_x, cand, vals, info = _acqopt.optimize_acqf(
+        new_x, infos = _acqopt.propose(
             ctx, self.__box, acq.device_scalar, acq.maximize, acq.acq_code, cfg["NUM_RESTARTS"], cfg["RAW_SAMPLES"], 5, 200,
-            raw=raw, raw_vals=raw_vals, breakdown=self.phase_breakdown,
+            q_eff=self._q_eff(), strategy=self._q_strategy, f_evals=self.f_evals, raw=raw, raw_vals=raw_vals, breakdown=self.phase_breakdown,
             trace=self.trace[-1] if self._record_trace else None)
         self.timing_logs["optimize_acqf"].append(perf_counter() - start)
-        self.lbfgsb_info.append(info)
+        self.lbfgsb_info.extend(infos)
         return new_x

@@ -125,7 +125,13 @@ class ExperimentRunner:
                  experiment_name: str = "experiment", acquisition_function: str = "expected_improvement",
                  pca_components: Optional[int] = None, var_threshold: float = 0.95, verbose: bool = False,
                  progress: bool = True, batched: int = 0, side_by_side: int = 2, batch_acq_kernel: str = "group",
-                 fit_gp: bool = False, batched_fit_gp: bool = False, ucb_beta: Optional[float] = None, ard: bool = False, batched_ard: bool = False):
+                 fit_gp: bool = False, batched_fit_gp: bool = False, ucb_beta: Optional[float] = None, ard: bool = False, batched_ard: bool = False,
+                 q: int = 1, q_strategy: str = "kriging_believer"):
+        # q, q_strategy (not in the reference): every run proposes q candidates per iteration, one run after the other (PCA_BO /
+        # Vanilla_BO q=..., pcabo.acqopt.propose) or in the lock-step batches (pcabo.batchrun q=...); q=1 is the reference's loop
+        # and leaves every file as it was
+        from pcabo.acqopt import checked_q
+        self.q, self.q_strategy = checked_q(q, q_strategy)
         # fit_gp (not in the reference): every run fits its GP's hyperparameters by the marginal likelihood each iteration
         # (PCA_BO / Vanilla_BO fit_gp=True), one run after the other.  For the lock-step batches: batched_fit_gp below.
         self.fit_gp = bool(fit_gp)
@@ -294,7 +300,7 @@ class ExperimentRunner:
                                       var_threshold=self.var_threshold, acquisition_function=self.acquisition_function,
                                       device=self.device, workers=workers_for(len(group)) if len(group) > 1 else 0,
                                       host_threads=max(1, 8 // len(group)), acq_kernel=kernel, fit_gp=self.batched_fit_gp,
-                                      ucb_beta=self.ucb_beta, batched_ard=self.batched_ard)
+                                      ucb_beta=self.ucb_beta, batched_ard=self.batched_ard, q=self.q, q_strategy=self.q_strategy)
                 jobs.append((dim, chunk, probs, n_doe, runner))
             kernel = group[0][2]
             start_time = time()
@@ -357,6 +363,9 @@ class ExperimentRunner:
                     provenance["gp_fit"] = "map-ard" if self.ard or self.batched_ard else "map"
                 if self.ucb_beta is not None:            # (only when set: the files of every other configuration stay as they were)
                     provenance["ucb_beta"] = f"{self.ucb_beta}"
+                if self.q > 1:                           # (likewise)
+                    provenance["q"] = f"{self.q}"
+                    provenance["q_strategy"] = self.q_strategy
                 logger.set_experiment_attributes({
                     "budget_factor": f"{self.budget_factor}",
                     "doe_factor": f"{self.doe_factor}",
@@ -410,6 +419,8 @@ class ExperimentRunner:
                             common["ard"] = True
                         if self.ucb_beta is not None:
                             common["ucb_beta"] = self.ucb_beta
+                        if self.q > 1:
+                            common.update(q=self.q, q_strategy=self.q_strategy)
                         if algorithm == "vanilla":
                             optimizer = Vanilla_BO(**common)
                         else:

@@ -67,19 +67,22 @@ __device__ inline void bb_matvec(const double* __restrict__ A, const double* v, 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(BB_THREADS) void k_bbob_eval(const double* __restrict__ tables, const int* __restrict__ fids,
-                                                          BbobLayout L, const double* __restrict__ X, double lb, double ub,
-                                                          double penalty, double* __restrict__ raw, int* __restrict__ oob) {
+// One candidate of run b by one work-group: its d coordinates at X + row * d, its value and flag written to slot `slot` of raw / oob.
+// Both kernels below are this body; the LDS arrays are the work-group's own.
+__device__ __forceinline__ void bb_eval_one(const double* __restrict__ tables, const int* __restrict__ fids, const BbobLayout L,
+                                            const double* __restrict__ X, const int b, const size_t row, const size_t slot,
+                                            const double lb, const double ub, const double penalty, double* __restrict__ raw,
+                                            int* __restrict__ oob) {
   __shared__ double s_red[BB_THREADS];
   __shared__ double s_x[PCABO_MAXD], s_a[PCABO_MAXD], s_b[PCABO_MAXD];
-  const int b = blockIdx.x, tid = threadIdx.x, d = L.d;
+  const int tid = threadIdx.x, d = L.d;
   const double* T = tables + (size_t)b * L.stride;
   const double *xopt = T + L.off_xopt, *R = T + L.off_r, *M = T + L.off_m, *aux = T + L.off_aux;
   const int fid = fids[b];
   const double two_pi = 6.283185307179586;
   double pen_loc = 0.0, out_loc = 0.0;
   for (int i = tid; i < d; i += BB_THREADS) {
-    const double x = X[(size_t)b * d + i];
+    const double x = X[row * d + i];
     s_x[i] = x;
     const double o = fabs(x) - 5.0;
     if (o > 0.0) pen_loc += o * o;
@@ -89,7 +92,7 @@ __global__ __launch_bounds__(BB_THREADS) void k_bbob_eval(const double* __restri
   const double pen = bb_block_sum(pen_loc, s_red);
   const bool outside = bb_block_sum(out_loc, s_red) > 0.0;
   if (outside) {                             // PCA_BO.py:260-261: not evaluated, fixed penalty
-    if (tid == 0) { raw[b] = penalty; oob[b] = 1; }
+    if (tid == 0) { raw[slot] = penalty; oob[slot] = 1; }
     return;
   }
   double f = 0.0;
@@ -194,7 +197,22 @@ __global__ __launch_bounds__(BB_THREADS) void k_bbob_eval(const double* __restri
     const double S1 = bb_block_sum(s1, s_red), S2 = bb_block_sum(s2, s_red), C = bb_block_sum(c, s_red);
     f = fmin(S1, dd * d + sfac * S2) + 10.0 * (d - C) + 1e4 * pen;
   }
-  if (tid == 0) { raw[b] = f; oob[b] = 0; }
+  if (tid == 0) { raw[slot] = f; oob[slot] = 0; }
+}
+
+// grid (B): one candidate per run, X[B][d]
+__global__ __launch_bounds__(BB_THREADS) void k_bbob_eval(const double* __restrict__ tables, const int* __restrict__ fids,
+                                                          BbobLayout L, const double* __restrict__ X, double lb, double ub,
+                                                          double penalty, double* __restrict__ raw, int* __restrict__ oob) {
+  bb_eval_one(tables, fids, L, X, blockIdx.x, blockIdx.x, blockIdx.x, lb, ub, penalty, raw, oob);
+}
+
+// grid (B, m): m candidates per run, X[B][m][d] -> raw[B][m], oob[B][m]; candidate j of run b as k_bbob_eval evaluates it alone
+__global__ __launch_bounds__(BB_THREADS) void k_bbob_eval_many(const double* __restrict__ tables, const int* __restrict__ fids,
+                                                               BbobLayout L, const double* __restrict__ X, int m, double lb, double ub,
+                                                               double penalty, double* __restrict__ raw, int* __restrict__ oob) {
+  const size_t slot = (size_t)blockIdx.x * m + blockIdx.y;
+  bb_eval_one(tables, fids, L, X, blockIdx.x, slot, slot, lb, ub, penalty, raw, oob);
 }
 
 struct pcabo_objective {
@@ -203,7 +221,30 @@ struct pcabo_objective {
   hipStream_t stream = nullptr;
   double *dTables = nullptr, *dX = nullptr, *dRaw = nullptr, *hX = nullptr, *hRaw = nullptr;
   int *dFid = nullptr, *dOob = nullptr, *hOob = nullptr;
+  int cap_m = 1;                                     // candidates per run the staging buffers (dX, dRaw, dOob, hX, hRaw, hOob) hold
 };
+
+// The staging buffers for m candidates per run; they grow on the first call that needs them (the stream is idle between calls).
+static bool bbob_reserve(pcabo_objective* o, int m) {
+  if (m <= o->cap_m) return true;
+  if (hipStreamSynchronize(o->stream) != hipSuccess) return false;
+  void* dev[] = {o->dX, o->dRaw, o->dOob};
+  for (void* p : dev) if (p) (void)hipFree(p);
+  void* host[] = {o->hX, o->hRaw, o->hOob};
+  for (void* p : host) if (p) (void)hipHostFree(p);
+  o->dX = o->dRaw = o->hX = o->hRaw = nullptr;
+  o->dOob = o->hOob = nullptr;
+  o->cap_m = 0;
+  const size_t slots = (size_t)o->B * m;
+  const bool ok = hipMalloc((void**)&o->dX, slots * o->d * sizeof(double)) == hipSuccess &&
+                  hipMalloc((void**)&o->dRaw, slots * sizeof(double)) == hipSuccess &&
+                  hipMalloc((void**)&o->dOob, slots * sizeof(int)) == hipSuccess &&
+                  hipHostMalloc((void**)&o->hX, slots * o->d * sizeof(double), hipHostMallocDefault) == hipSuccess &&
+                  hipHostMalloc((void**)&o->hRaw, slots * sizeof(double), hipHostMallocDefault) == hipSuccess &&
+                  hipHostMalloc((void**)&o->hOob, slots * sizeof(int), hipHostMallocDefault) == hipSuccess;
+  if (ok) o->cap_m = m;
+  return ok;
+}
 
 extern "C" {
 
@@ -247,7 +288,7 @@ int pcabo_bbob_destroy(pcabo_objective* o) {
 
 int pcabo_bbob_eval(pcabo_objective* o, const double* X, double lb, double ub, double penalty, double* raw, int* oob) {
   if (!o || !X || !raw) return PCABO_ERR_ARG;
-  if (hipSetDevice(o->device) != hipSuccess) return PCABO_ERR_HIP;
+  if (hipSetDevice(o->device) != hipSuccess || !bbob_reserve(o, 1)) return PCABO_ERR_HIP;
   const size_t xb = (size_t)o->B * o->d * sizeof(double);
   memcpy(o->hX, X, xb);
   if (hipMemcpyAsync(o->dX, o->hX, xb, hipMemcpyHostToDevice, o->stream) != hipSuccess) return PCABO_ERR_HIP;
@@ -259,6 +300,23 @@ int pcabo_bbob_eval(pcabo_objective* o, const double* X, double lb, double ub, d
     return PCABO_ERR_HIP;
   memcpy(raw, o->hRaw, o->B * sizeof(double));
   if (oob) memcpy(oob, o->hOob, o->B * sizeof(int));
+  return PCABO_OK;
+}
+
+int pcabo_bbob_eval_many(pcabo_objective* o, const double* X, int m, double lb, double ub, double penalty, double* raw, int* oob) {
+  if (!o || !X || !raw || m < 1 || m > 65535) return PCABO_ERR_ARG;
+  if (hipSetDevice(o->device) != hipSuccess || !bbob_reserve(o, m)) return PCABO_ERR_HIP;
+  const size_t slots = (size_t)o->B * m, xb = slots * o->d * sizeof(double);
+  memcpy(o->hX, X, xb);
+  if (hipMemcpyAsync(o->dX, o->hX, xb, hipMemcpyHostToDevice, o->stream) != hipSuccess) return PCABO_ERR_HIP;
+  hipLaunchKernelGGL(k_bbob_eval_many, dim3(o->B, m), dim3(BB_THREADS), 0, o->stream, o->dTables, o->dFid, o->L, o->dX, m, lb, ub,
+                     penalty, o->dRaw, o->dOob);
+  if (hipMemcpyAsync(o->hRaw, o->dRaw, slots * sizeof(double), hipMemcpyDeviceToHost, o->stream) != hipSuccess ||
+      hipMemcpyAsync(o->hOob, o->dOob, slots * sizeof(int), hipMemcpyDeviceToHost, o->stream) != hipSuccess ||
+      hipStreamSynchronize(o->stream) != hipSuccess || hipGetLastError() != hipSuccess)
+    return PCABO_ERR_HIP;
+  memcpy(raw, o->hRaw, slots * sizeof(double));
+  if (oob) memcpy(oob, o->hOob, slots * sizeof(int));
   return PCABO_OK;
 }
 

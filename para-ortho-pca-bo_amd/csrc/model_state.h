@@ -100,11 +100,15 @@ struct BatchState {
   bool score_enqueued = false;           // pcabo_batch_gp_condition_end_eval_begin without its _end yet
   bool imap_enqueued = false;            // pcabo_batch_inverse_map_begin without its _end yet
   bool opt_enqueued = false; int opt_restarts = 0, opt_limit = 0;      // pcabo_batch_optimize_acqf_begin without its _end yet
+  bool value_score_enqueued = false;     // pcabo_batch_acq_score_begin without its _end yet
 
   // ---- questions ----
-  bool begin_pending() const { return score_enqueued || opt_enqueued || imap_enqueued; }
+  bool begin_pending() const { return score_enqueued || opt_enqueued || imap_enqueued || value_score_enqueued; }
   GpReady gp_ready() const { return m.gp_pending || begin_pending() ? GP_IN_FLIGHT : m.have_gp ? GP_READY : GP_NONE; }
   bool scorable() const { return m.gp_pending || fitted; }           // a conditioning in flight, or a fit (waited for already)
+  // pcabo_batch_acq_score: values on the model as it stands - the batch has a GP, its conditioning has been waited for and no
+  // _begin half is open; fitted or not, extended or not.  (scorable() above is the other scoring's question: it ENDS a conditioning.)
+  bool value_scorable() const { return gp_ready() == GP_READY; }
   bool anything_enqueued() const { return m.wpca_uncollected || m.n != 0; }
   bool wpca_on_host() const { return m.n != 0 && !m.wpca_uncollected; }
   bool extended() const { return m.n > m.n_base; }                   // points appended by pcabo_batch_gp_extend and not taken back
@@ -131,6 +135,8 @@ struct BatchState {
   void fit_finished() { m.gp_pending = false; m.have_gp = true; fitted = true; }
   void scoring_begun() { score_enqueued = true; }
   void scoring_ended() { score_enqueued = false; m.gp_pending = false; m.have_gp = true; }
+  void value_scoring_begun() { value_score_enqueued = true; }          // the model's phase is not touched: nothing ends, nothing starts
+  void value_scoring_ended() { value_score_enqueued = false; }
   void imap_begun() { imap_enqueued = true; }
   void imap_ended() { imap_enqueued = false; }
   void opt_begun(int restarts, int limit) { opt_enqueued = true; opt_restarts = restarts; opt_limit = limit; }

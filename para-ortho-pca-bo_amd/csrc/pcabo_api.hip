@@ -2053,10 +2053,9 @@ static int batch_score_args(pcabo_batch* batch, const double* Xq, int q, const d
   return PCABO_OK;
 }
 
-static int batch_score_enqueue(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq, bool out_ok = true) {
-  if (!batch) return PCABO_ERR_ARG;
-  if (const int rc = batch_score_args(batch, Xq, q, best_f, acq, out_ok)) return rc;
-  if (batch->st.score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: a scoring is already enqueued%s", "");
+// The launches of a scoring of all runs' queries on the batch's model as it stands: queries packed and copied, the values' launch
+// (the GEMM route from q = 64, the per-query kernels below), the values on their way back to every run's hVal.
+static int batch_score_launch(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq) {
   if (const int rc = collect_pending_wpca(batch)) return rc;
   BHIPCHK(hipSetDevice(batch->device));
   hipStream_t s = batch->stream;
@@ -2074,6 +2073,16 @@ static int batch_score_enqueue(pcabo_batch* batch, const double* Xq, int q, cons
                nullptr, 0, nullptr, nullptr, batch_ab(batch, 0, 0), B, 0);
   BHIPCHK(hipMemcpy2DAsync(c0->hVal, batch->hzs, c0->dVal, batch->zs, (size_t)q * sizeof(double), B, hipMemcpyDeviceToHost, s));
   BHIPCHK(hipGetLastError());
+  return PCABO_OK;
+}
+
+static int batch_score_enqueue(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq, bool out_ok = true) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (const int rc = batch_score_args(batch, Xq, q, best_f, acq, out_ok)) return rc;
+  if (batch->st.score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: a scoring is already enqueued%s", "");
+  if (batch->st.value_score_enqueued)
+    return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_gp_condition_end_eval: a pcabo_batch_acq_score_begin has not been ended%s", "");
+  if (const int rc = batch_score_launch(batch, Xq, q, best_f, maximize, acq)) return rc;
   batch->st.scoring_begun();
   return PCABO_OK;
 }
@@ -2114,6 +2123,54 @@ static int batch_score_collect(pcabo_batch* batch, const double* Xq, int q, cons
   }
   if (worst != PCABO_OK && !status) return bset_err(batch, worst, "a run of the batch failed in the conditioning (status array not given)%s", "");
   return PCABO_OK;
+}
+
+// pcabo_batch_acq_score: the same launches on a model that is there already (BatchState::value_scorable) - values only, nothing of
+// the model's phase changes, no run is redone alone.  A run that is parked, set aside or without a GP is computed with the others
+// and not handed out.
+static int batch_value_score_args(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int acq, bool out_ok) {
+  if (!Xq || !best_f || !out_ok || q < 1 || q > batch->max_q) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_acq_score: bad argument%s", "");
+  if (const char* why = batch_acq_arg_error(batch, acq, best_f)) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_acq_score: %s", why);
+  return PCABO_OK;
+}
+static int batch_value_score_enqueue(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq, bool out_ok = true) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (const int rc = batch_value_score_args(batch, Xq, q, best_f, acq, out_ok)) return rc;
+  if (!batch->st.value_scorable())
+    return bset_err(batch, PCABO_ERR_ARG, batch->st.gp_ready() == GP_IN_FLIGHT
+                        ? "pcabo_batch_acq_score: a conditioning or a _begin call of this batch has not been ended%s"
+                        : "pcabo_batch_acq_score: no conditioned GP%s", "");
+  if (const int rc = batch_score_launch(batch, Xq, q, best_f, maximize, acq)) return rc;
+  batch->st.value_scoring_begun();
+  return PCABO_OK;
+}
+static int batch_value_score_collect(pcabo_batch* batch, int q, double* val, int* status) {
+  if (!batch) return PCABO_ERR_ARG;
+  if (!batch->st.value_score_enqueued) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_acq_score_end: no _begin before it%s", "");
+  if (!val || q < 1 || q > batch->max_q) return bset_err(batch, PCABO_ERR_ARG, "pcabo_batch_acq_score_end: bad argument%s", "");
+  BHIPCHK(hipSetDevice(batch->device));
+  BHIPCHK(wait_stream(batch->stream));
+  BHIPCHK(hipGetLastError());
+  batch->st.value_scoring_ended();
+  for (int b = 0; b < batch->B; ++b) {
+    pcabo_ctx* c = batch->ctx[b];
+    const bool live = batch->active[b] && c->st.conditioned();
+    if (live) memcpy(val + (size_t)b * q, c->hVal, (size_t)q * sizeof(double));
+    if (status) status[b] = live ? PCABO_OK : PCABO_ERR_ARG;
+  }
+  return PCABO_OK;
+}
+
+int pcabo_batch_acq_score(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq, double* val,
+                          int* status) {
+  const int rc = batch_value_score_enqueue(batch, Xq, q, best_f, maximize, acq, val != nullptr);
+  return rc != PCABO_OK ? rc : batch_value_score_collect(batch, q, val, status);
+}
+int pcabo_batch_acq_score_begin(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize, int acq) {
+  return batch_value_score_enqueue(batch, Xq, q, best_f, maximize, acq);
+}
+int pcabo_batch_acq_score_end(pcabo_batch* batch, int q, double* val, int* status) {
+  return batch_value_score_collect(batch, q, val, status);
 }
 
 int pcabo_batch_gp_condition_end_eval(pcabo_batch* batch, const double* Xq, int q, const double* best_f, int maximize,

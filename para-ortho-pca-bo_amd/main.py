@@ -50,7 +50,16 @@ def parse_arguments(argv=None):
                    help="beta of botorch's UpperConfidenceBound(model, beta): value = -mean + sqrt(beta) * sigma when minimising.  This "
                         "flag is what makes --acquisition upper_confidence_bound runnable (not in the reference, where that choice "
                         "raises TypeError at the first BO iteration - as it still does here without the flag)")
+    p.add_argument("--q", type=int, default=1,
+                   help="candidates proposed and evaluated per iteration (not in the reference, which asks for one): each later one "
+                        "is optimised on the model extended by those before it (also with --batched)")
+    p.add_argument("--q_strategy", default="kriging_believer",
+                   choices=["kriging_believer", "constant_liar_min", "constant_liar_mean", "constant_liar_max"],
+                   help="with --q > 1, the value a pending candidate takes in the model: the model's own mean there, or the min / "
+                        "mean / max of the values seen so far")
     a = p.parse_args(argv)
+    if a.q < 1:
+        p.error("--q must be at least 1")
     if a.batched_ard and not (a.batched > 1 and a.batched_fit_gp):
         p.error("--batched_ard needs --batched N (N > 1) and --batched_fit_gp")
     return a
@@ -66,7 +75,8 @@ def main():
         budget_factor=a.budget_factor, doe_factor=a.doe_factor, root_dir=os.getcwd(), experiment_name=a.experiment_dir,
         acquisition_function=a.acquisition, pca_components=0, var_threshold=a.var_threshold, verbose=a.verbose,
         progress=(rank == 0), batched=a.batched, side_by_side=a.side_by_side, batch_acq_kernel=a.batch_acq_kernel,
-        fit_gp=a.fit_gp, batched_fit_gp=a.batched_fit_gp, ucb_beta=a.ucb_beta, ard=a.ard, batched_ard=a.batched_ard)
+        fit_gp=a.fit_gp, batched_fit_gp=a.batched_fit_gp, ucb_beta=a.ucb_beta, ard=a.ard, batched_ard=a.batched_ard,
+        q=a.q, q_strategy=a.q_strategy)
     t0 = time.time()
     experiment.run_experiment()
     dt = time.time() - t0

@@ -63,6 +63,7 @@ EXPORTS = [
     "pcabo_get_profile", "pcabo_get_profile_calibration", "pcabo_reset_profile",
     "pcabo_batch_create", "pcabo_batch_destroy", "pcabo_batch_last_error", "pcabo_batch_ctx",
     "pcabo_batch_wpca_gp_condition_begin", "pcabo_batch_wpca_results", "pcabo_batch_acq_bounds",
+    "pcabo_batch_acq_score", "pcabo_batch_acq_score_begin", "pcabo_batch_acq_score_end",
     "pcabo_batch_gp_condition_end_eval", "pcabo_batch_optimize_acqf", "pcabo_batch_inverse_map", "pcabo_batch_device_acq_eval",
     "pcabo_batch_busy", "pcabo_batch_gp_condition_end_eval_begin", "pcabo_batch_gp_condition_end_eval_end",
     "pcabo_batch_optimize_acqf_begin", "pcabo_batch_optimize_acqf_end", "pcabo_batch_inverse_map_begin", "pcabo_batch_inverse_map_end",
@@ -70,7 +71,7 @@ EXPORTS = [
     "pcabo_batch_gp_mll", "pcabo_batch_gp_fit", "pcabo_batch_gp_fit_rounds", "pcabo_batch_gp_mll_ard", "pcabo_batch_gp_fit_ard",
     "pcabo_batch_set_profiling", "pcabo_batch_get_profile", "pcabo_batch_set_active", "pcabo_batch_set_workers", "pcabo_batch_set_option",
     "pcabo_device_lbfgsb_limits",
-    "pcabo_bbob_table_doubles", "pcabo_bbob_create", "pcabo_bbob_destroy", "pcabo_bbob_eval",
+    "pcabo_bbob_table_doubles", "pcabo_bbob_create", "pcabo_bbob_destroy", "pcabo_bbob_eval", "pcabo_bbob_eval_many",
     "pcabo_comm_unique_id", "pcabo_comm_create", "pcabo_gather_best", "pcabo_comm_last_error", "pcabo_comm_destroy",
 ]
 
@@ -166,6 +167,9 @@ def _load() -> C.CDLL:
     lib.pcabo_batch_busy.argtypes = [vp]
     lib.pcabo_batch_gp_condition_end_eval_begin.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int]
     lib.pcabo_batch_gp_condition_end_eval_end.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    lib.pcabo_batch_acq_score.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    lib.pcabo_batch_acq_score_begin.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int]
+    lib.pcabo_batch_acq_score_end.argtypes = [vp, C.c_int, vp, vp]
     lib.pcabo_batch_optimize_acqf_begin.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int]
     lib.pcabo_batch_optimize_acqf_end.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.pcabo_batch_inverse_map_begin.argtypes = [vp, vp]
@@ -964,6 +968,29 @@ class Batch:
         status = np.zeros(self.B, dtype=np.int32)
         self._chk(LIB.pcabo_batch_gp_condition_end_eval_end(self._h, _ptr(buf), q, _ptr(bf), mx, acq, _ptr(val), _ptr(status)))
         return val, status
+
+    # ---- values on the model as it stands (pcabo_batch_acq_score: the later proposals of an iteration) ---------------------
+    def acq_score_begin(self, Xq_list, best_f, maximize=False, acq=ACQ_LOG_EI):
+        """Enqueue the scoring of Xq_list[b] (q x k_b, the same q for all runs) on every run's current model - extended or not,
+        fitted or not; the batch's conditioning has been waited for.  Returns the token acq_score_end takes."""
+        q = Xq_list[0].shape[0]
+        buf = self.raw_row_buffer(q)
+        for b, xq in enumerate(Xq_list):
+            if not (isinstance(xq, np.ndarray) and xq.base is buf):
+                buf[b, : xq.size] = np.ascontiguousarray(xq, dtype=np.float64).ravel()
+        bf = _f64(best_f, (self.B,))
+        self._chk(LIB.pcabo_batch_acq_score_begin(self._h, _ptr(buf), q, _ptr(bf), int(bool(maximize)), int(acq)))
+        return q
+
+    def acq_score_end(self, token):
+        """(values[B, q], status[B]): status -1 for a run that was skipped (parked, set aside, without a GP), its row zeros."""
+        q = token
+        val, status = np.zeros((self.B, q)), np.zeros(self.B, dtype=np.int32)
+        self._chk(LIB.pcabo_batch_acq_score_end(self._h, q, _ptr(val), _ptr(status)))
+        return val, status
+
+    def acq_score(self, Xq_list, best_f, maximize=False, acq=ACQ_LOG_EI):
+        return self.acq_score_end(self.acq_score_begin(Xq_list, best_f, maximize, acq))
 
     def _pack_ics(self, ics_list, bounds_list):
         B, MD = self.B, self.max_d

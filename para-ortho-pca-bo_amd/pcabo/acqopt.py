@@ -59,6 +59,33 @@ def checked_ucb_beta(ucb_beta, acquisition_name: str) -> Optional[float]:
     return beta
 
 
+Q_STRATEGIES = ("kriging_believer", "constant_liar_min", "constant_liar_mean", "constant_liar_max")
+
+
+def checked_q(q, q_strategy):
+    """The `q` / `q_strategy` keywords of the optimisers, validated where they are constructed: q an integer >= 1 (a bool is not
+    one), the strategy one of Q_STRATEGIES; ValueError otherwise.  Returns (int(q), q_strategy)."""
+    if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or q < 1:
+        raise ValueError(f"q must be an integer >= 1, got {q!r}")
+    if q_strategy not in Q_STRATEGIES:
+        raise ValueError(f"q_strategy must be one of {', '.join(Q_STRATEGIES)}; got {q_strategy!r}")
+    return int(q), q_strategy
+
+
+def liar_value(strategy: str, f_evals) -> float:
+    """The value a constant-liar strategy gives every pending point: min / mean / max of the objective values seen so far."""
+    f = np.asarray(f_evals, dtype=np.float64)
+    return float({"constant_liar_min": f.min, "constant_liar_mean": f.mean, "constant_liar_max": f.max}[strategy]())
+
+
+def moved_scalar(s, v, maximize: bool, acq_code: int):
+    """The acquisition's scalar after a pending point took the value v: UCB's kappa stays, an incumbent moves to the better of
+    the two (an unmoved best_f lets EI and PI propose the same point again: the variance there is gone, the mean is not)."""
+    if acq_code == _native.ACQ_UCB:
+        return s
+    return max(s, v) if maximize else min(s, v)
+
+
 def optimize_acqf(ctx: "_native.Context", bounds: np.ndarray, best_f: float, maximize: bool, acq_code: int,
                   num_restarts: int, raw_samples: int, batch_limit: int = 5, maxiter: int = 200, engine=None,
                   breakdown: Optional[dict] = None, trace: Optional[dict] = None, raw: Optional[np.ndarray] = None,
@@ -112,3 +139,45 @@ def optimize_acqf(ctx: "_native.Context", bounds: np.ndarray, best_f: float, max
         trace.update(ics=ics.copy(), cands=cand.copy(), vals=vals.copy(), chosen=best, info=info.copy(),
                      k=int(cand.shape[1]))
     return cand[best].reshape(1, -1), cand, vals, info
+
+
+def propose(ctx: "_native.Context", bounds: np.ndarray, best_f: float, maximize: bool, acq_code: int, num_restarts: int,
+            raw_samples: int, batch_limit: int = 5, maxiter: int = 200, q_eff: int = 1, strategy: str = "kriging_believer",
+            f_evals=None, breakdown: Optional[dict] = None, trace: Optional[dict] = None, raw: Optional[np.ndarray] = None,
+            raw_vals: Optional[np.ndarray] = None, before_lbfgsb=None):
+    """q_eff candidates of one iteration, one after the other on a model that takes every pending point in (DESIGN.md section
+    18).  Proposal 0 is `optimize_acqf` with everything the caller prepared (`raw`, `raw_vals`, `before_lbfgsb`, `trace`); each
+    later one is a whole `optimize_acqf` of its own - a fresh scrambled Sobol engine from torch's global generator, scoring by
+    `Context.acq_eval`, pick, L-BFGS-B, botorch's retry - on the context extended by the point before it (`Context.gp_extend`)
+    with the value v: the model's own mean there (kriging_believer) or min / mean / max of `f_evals` (constant_liar_*).  The
+    scalar moves with v (`moved_scalar`).  `bounds` is held.  Whatever was appended is taken back before this returns or raises.
+    A later proposal's trace is a dict of `optimize_acqf`'s keys plus `best_f` and `believed` in trace["proposals"].
+    Returns (candidates[q_eff, k], [L-BFGS-B info per proposal])."""
+    believer = strategy == "kriging_believer"
+    if strategy not in Q_STRATEGIES:
+        raise ValueError(f"q_strategy must be one of {', '.join(Q_STRATEGIES)}; got {strategy!r}")
+    liar = None if believer or q_eff <= 1 else liar_value(strategy, f_evals)
+    s, n0, cands, infos = best_f, None, [], []
+    try:
+        z, _, _, info = optimize_acqf(ctx, bounds, s, maximize, acq_code, num_restarts, raw_samples, batch_limit, maxiter,
+                                      breakdown=breakdown, trace=trace, raw=raw, raw_vals=raw_vals, before_lbfgsb=before_lbfgsb)
+        cands.append(z)
+        infos.append(info)
+        for _ in range(1, q_eff):
+            v = float(ctx.gp_posterior(z)["mean"][0]) if believer else liar
+            n = ctx.n
+            ctx.gp_extend(z, None if believer else [v])
+            n0 = n if n0 is None else n0
+            s = moved_scalar(s, v, maximize, acq_code)
+            tr = None
+            if trace is not None:
+                tr = {"best_f": s, "believed": v}
+                trace.setdefault("proposals", []).append(tr)
+            z, _, _, info = optimize_acqf(ctx, bounds, s, maximize, acq_code, num_restarts, raw_samples, batch_limit, maxiter,
+                                          breakdown=breakdown, trace=tr)
+            cands.append(z)
+            infos.append(info)
+    finally:
+        if n0 is not None:
+            ctx.gp_truncate(n0)
+    return np.concatenate(cands, axis=0), infos

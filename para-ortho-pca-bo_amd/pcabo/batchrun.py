@@ -24,7 +24,7 @@ import torch
 from . import _native
 from .hostrng import HostMT
 from . import initializers as _init
-from .acqopt import acquisition_long_name, checked_ucb_beta, ucb_kappa
+from .acqopt import acquisition_long_name, checked_q, checked_ucb_beta, liar_value, moved_scalar, ucb_kappa
 from .gcguard import RunGuard
 from .lhs import lhs_center
 
@@ -62,7 +62,12 @@ class BatchedPCABO:
                  record_trace: bool = False, host_threads: int = 0, device_objective: bool = False, workers: int = 0,
                  trace_filter=None, acq_kernel: str = "group", torch_threads: Optional[int] = 4,
                  gc_freeze: bool = True, fit_gp: bool = False, ucb_beta: Optional[float] = None, ard: bool = False,
-                 batched_ard: bool = False):
+                 batched_ard: bool = False, q: int = 1, q_strategy: str = "kriging_believer"):
+        # q, q_strategy (not in the reference; PCA_BO / Vanilla_BO have the same keywords): every run proposes q candidates per
+        # iteration, the later ones on its model extended by those before (pcabo.acqopt.propose in lock-step: _later_proposals)
+        self._q, self._q_strategy = checked_q(q, q_strategy)
+        self._extended = False             # between the first gp_extend of an iteration and its gp_truncate
+        self._park_pending = False         # a run was parked meanwhile: the library takes the flag once the points are taken back
         if ard:                            # (the batches' keyword is batched_ard: DESIGN.md "ARD lengthscales", scope)
             raise ValueError("ard=True is a mode of the single-run classes Algorithms.PCA_BO / Vanilla_BO (fit_gp=True, ard=True): "
                              "the lock-step batches take fit_gp=True, batched_ard=True")
@@ -227,7 +232,10 @@ class BatchedPCABO:
         self._X[b] = self._frozen[b][0]
         self._F[b] = self._frozen[b][1]
         self.current_best[b] = float(np.min(fd) if not self.maximization else np.max(fd))
-        self._batch.set_active([self.failed[i] is None for i in range(self.B)])
+        if self._extended:                 # (the library refuses a change of the flags while points are appended: _later_proposals)
+            self._park_pending = True
+        else:
+            self._batch.set_active([self.failed[i] is None for i in range(self.B)])
         warnings.warn(f"run {b} (seed {self.seeds[b]}) stopped at n = {n}: {message}", RuntimeWarning)
 
     def _fit_all(self, n: int) -> float:
@@ -272,21 +280,16 @@ class BatchedPCABO:
         idx = self._pick(vals)
         ics = [raw[b][idx[b]] for b in range(B)]
         t5 = perf_counter()
-        engines_job = None
-        if self._pool is not None and not self.record_trace and n + 1 < self.budget:
-            self._draw_noise_ahead(n)
-            engines_job = self._build_engines_ahead()
-        token = bt.optimize_begin(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200) \
-            if self._device_lbfgsb == 1 else None
-        if token is not None:             # the device-resident optimiser: one launch, collected when it has drained
-            yield "optimize"
-            outs, status = bt.optimize_end(token)
-        else:
-            outs, status = bt.optimize_acqf(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200)
-        self._after_optimiser(engines_job, outs, status, n)
+        # this iteration's candidates per run (q, or what the budget leaves), hence the next iteration's n: what is made ahead is
+        # made for that n, and the engines - a guess for the next iteration's FIRST proposal - beside the last optimiser call
+        q_eff = max(1, min(self._q, self.budget - n))
+        ahead = self._pool is not None and not self.record_trace and n + q_eff < self.budget
+        if ahead:
+            self._draw_noise_ahead(n, q_eff)
+        outs = yield from self._optimise(ics, bounds, best_f, n, ahead and q_eff == 1)
         t6 = perf_counter()
         # per run: the candidate it goes on with (None: parked), its optimiser's counters (a parked run keeps the batch call's)
-        chosen, infos = [None] * B, [out[2] for out in outs]
+        chosen, infos, entries = [None] * B, [out[2] for out in outs], {}
         for b in range(B):
             cand, v, _, failed = outs[b]
             if self.failed[b] is not None:
@@ -296,14 +299,108 @@ class BatchedPCABO:
             best = int(np.argmax(v))
             chosen[b] = cand[best]
             if b in pre:
-                self.trace.append({"b": b, "n": n, "k": int(bt.k[b]), "ic_idx": np.asarray(idx[b]).copy(), "ics": ics[b].copy(),
-                                   "cands": cand.copy(), "vals": v.copy(), "info": infos[b].copy(), "chosen": best,
-                                   "retried": failed, **pre[b]})
+                entries[b] = {"b": b, "n": n, "k": int(bt.k[b]), "ic_idx": np.asarray(idx[b]).copy(), "ics": ics[b].copy(),
+                              "cands": cand.copy(), "vals": v.copy(), "info": infos[b].copy(), "chosen": best,
+                              "retried": failed, **pre[b]}
+                self.trace.append(entries[b])
         self.lbfgsb_info.append(infos)
-        yield from self._new_points(chosen, n)
+        proposals, t_more = [chosen], 0.0
+        if q_eff > 1:
+            t7 = perf_counter()
+            proposals += yield from self._later_proposals(q_eff, n, bounds, best_f, chosen, entries, ahead)
+            t_more = perf_counter() - t7
+        yield from self._new_points(proposals, n)
         for phase, seconds in (("host_prep", t1 - t0), ("pca", t2 - t1), ("wait_score", (t4 - t2) - tfit), ("fit", tfit),
-                               ("init_pick", t5 - t4), ("lbfgsb", t6 - t5), ("tail", perf_counter() - t6)):
+                               ("init_pick", t5 - t4), ("lbfgsb", t6 - t5 + t_more), ("tail", perf_counter() - t6 - t_more)):
             self.timing[phase] += seconds
+
+    def _optimise(self, ics, bounds, best_f, n: int, engines_ahead: bool):
+        """The optimiser of all runs in the batch's mode (a generator: the device-resident one is collected after a yield), with
+        the next iteration's engines built beside it when asked; runs the optimiser gave up are parked.  Returns the runs' results."""
+        bt = self._batch
+        engines_job = self._build_engines_ahead() if engines_ahead else None
+        token = bt.optimize_begin(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200) \
+            if self._device_lbfgsb == 1 else None
+        if token is not None:             # the device-resident optimiser: one launch, collected when it has drained
+            yield "optimize"
+            outs, status = bt.optimize_end(token)
+        else:
+            outs, status = bt.optimize_acqf(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200)
+        self._after_optimiser(engines_job, outs, status, n)
+        return outs
+
+    def _search_boxes_packed(self) -> np.ndarray:
+        """The runs' search boxes as sobol_draw_rows reads them: B x [lo(k_b), hi(k_b)]."""
+        return self._batch.acq_bounds_packed
+
+    def _later_proposals(self, q_eff: int, n: int, bounds, s, z_prev, entries, ahead: bool):
+        """Proposals 1 .. q_eff - 1 of all runs: pcabo.acqopt.propose in lock-step.  Per proposal one posterior
+        launch for the believed values, one extend, every run's fresh engine and raw samples from its own generator, one scoring
+        on the extended models (Batch.acq_score_*), the pick, the optimiser in the batch's mode, botorch's retry per run on its
+        member context.  The search boxes are held.  The points are taken back before this returns or raises.  A run whose extend
+        fails is parked alone.  Returns the later proposals' candidates, one list (per run; None: parked) per proposal."""
+        B, bt = self.B, self._batch
+        believer = self._q_strategy == "kriging_believer"
+        liar = None if believer else [liar_value(self._q_strategy, self.f_evals[b][:n]) if self.failed[b] is None else 0.0
+                                      for b in range(B)]
+        s, more = list(s), []
+        try:
+            for j in range(1, q_eff):
+                Zl = [np.asarray(z_prev[b], dtype=np.float64).reshape(1, -1) if self.failed[b] is None
+                      else np.zeros((1, int(bt.k[b]))) for b in range(B)]
+                if believer:
+                    post = bt.gp_posterior(Zl)
+                    v = [float(post[b]["mean"][0]) if self.failed[b] is None and post[b] is not None else 0.0 for b in range(B)]
+                    self._extended = True
+                    _, status = bt.gp_extend(Zl)
+                else:
+                    v = liar
+                    self._extended = True
+                    _, status = bt.gp_extend(Zl, np.array(v, dtype=np.float64).reshape(B, 1))
+                for b in range(B):
+                    if self.failed[b] is None and status[b] != 0:
+                        self._park(b, n, f"the GP could not take proposal {j - 1} in (not positive definite)" if status[b] == -2
+                                   else f"the GP could not take proposal {j - 1} in (status {int(status[b])})")
+                s = [moved_scalar(s[b], v[b], self.maximization, self.acq_code) for b in range(B)]
+                engines = [_init.scrambled_sobol_engine(int(bt.k[b]), self._tg[b]) for b in range(B)]
+                raw = _native.sobol_draw_rows(engines, self.raw_samples, self._search_boxes_packed(), bt.raw_row_buffer(self.raw_samples))
+                token = bt.acq_score_begin(raw, s, self.maximization, self.acq_code)
+                yield "scoring"
+                vals, status = bt.acq_score_end(token)
+                for b in range(B):
+                    if self.failed[b] is None and (status[b] != 0 or not np.isfinite(vals[b]).all()):
+                        self._park(b, n, f"proposal {j}: the extended model could not be scored" if status[b] != 0
+                                   else f"proposal {j}: non-finite acquisition values on the raw samples")
+                    if self.failed[b] is not None:
+                        vals[b] = np.linspace(0.0, 1.0, vals.shape[1])
+                idx = self._pick(vals)
+                ics = [raw[b][idx[b]] for b in range(B)]
+                outs = yield from self._optimise(ics, bounds, s, n, ahead and j == q_eff - 1)
+                chosen, infos = [None] * B, [out[2] for out in outs]
+                for b in range(B):
+                    cand, val, _, failed = outs[b]
+                    if self.failed[b] is not None:
+                        continue
+                    if failed:
+                        ics[b], cand, val, infos[b] = self._retry(b, bounds[b], s[b])
+                    best = int(np.argmax(val))
+                    chosen[b] = cand[best]
+                    if b in entries:
+                        entries[b].setdefault("proposals", []).append(
+                            {"k": int(bt.k[b]), "ic_idx": np.asarray(idx[b]).copy(), "ics": ics[b].copy(), "cands": cand.copy(),
+                             "vals": val.copy(), "info": infos[b].copy(), "chosen": best, "retried": failed, "best_f": s[b],
+                             "believed": v[b]})
+                self.lbfgsb_info.append(infos)
+                more.append(chosen)
+                z_prev = chosen
+        finally:
+            if self._extended:
+                self._extended = False
+                bt.gp_truncate()
+            if self._park_pending:
+                self._park_pending = False
+                bt.set_active([self.failed[i] is None for i in range(B)])
+        return more
 
     def _condition_and_draw(self, n):
         """From the evaluated points to conditioned GPs and raw samples to score (a generator: it waits for the weighted PCA).  Returns
@@ -388,9 +485,10 @@ class BatchedPCABO:
         return [_init.initialize_q_batch_nonneg(vals[b], self.num_restarts, generator=self._tg[b]) if self.failed[b] is None
                 else np.arange(self.num_restarts) for b in range(self.B)]
 
-    def _draw_noise_ahead(self, n: int) -> None:
-        """The next iteration's noise blocks, on the pool while the optimiser runs (see __init__)."""
+    def _draw_noise_ahead(self, n: int, q_eff: int = 1) -> None:
+        """The next iteration's noise blocks (it has q_eff more points), on the pool while the optimiser runs (see __init__)."""
         B, d = self.B, self.dimension
+        n = n + q_eff - 1
         # one task per pool thread, each drawing the blocks of its share of the runs (a submit per run cost the host thread
         # 0.7 ms per iteration at 30 runs); every run's block comes from its own stream, so the grouping changes nothing
         alive = [b for b in range(B) if self.failed[b] is None]
@@ -443,33 +541,42 @@ class BatchedPCABO:
         cand, v, info, _ = c.optimize_acqf(ics, bounds, best_f, self.maximization, self.acq_code, batch_limit=5, maxiter=200)
         return ics, cand, v, info
 
-    def _new_points(self, chosen, n: int):
-        """From every live run's chosen candidate to its next evaluated point (a generator: it waits for the inverse map)."""
+    def _new_points(self, proposals, n: int):
+        """From every live run's chosen candidates (proposals[j][b]; one proposal, or the q of the iteration) to its next evaluated
+        points, in the order they were proposed (a generator: it waits for the inverse maps)."""
         bt = self._batch
-        bt.inverse_map_begin([np.zeros(int(bt.k[b])) if z is None else z for b, z in enumerate(chosen)])
-        yield "inverse map"
-        X_new = bt.inverse_map_end()
-        f_dev = None
+        X_all = []
+        for chosen in proposals:
+            bt.inverse_map_begin([np.zeros(int(bt.k[b])) if z is None else z for b, z in enumerate(chosen)])
+            yield "inverse map"
+            X_all.append(bt.inverse_map_end())
+        f_all = None
         if self._dev_obj is not None and not self.maximization:
-            f_dev, raw_dev, oob_dev = self._dev_obj.evaluate(X_new)
-        new = []
-        for b in range(self.B):
-            if self.failed[b] is not None:
-                continue
-            new_x = X_new[b].copy()
-            if f_dev is not None:
-                new_f = float(f_dev[b])
-                if not oob_dev[b]:               # keep the problem's own record (what the Analyzer rows are written from)
-                    p = self.problems[b]
-                    p.evaluations += 1
-                    p.best_raw = min(p.best_raw, float(raw_dev[b]))
-                    p.log.append((float(raw_dev[b]), new_x.copy()))
-            else:
-                outside = not np.all(new_x >= self.bounds[b][:, 0]) or not np.all(new_x <= self.bounds[b][:, 1])
-                # out-of-box candidates are not evaluated; they cost budget and a fixed penalty (PCA_BO.py:260-263)
-                new_f = (-OOB_PENALTY if self.maximization else OOB_PENALTY) if outside else self.problems[b](new_x)
-            new.append((b, new_x, new_f))
-        self._append(n, new)
+            if len(X_all) == 1:
+                f_all = [self._dev_obj.evaluate(X_all[0])]
+            else:                                # the q candidates of all runs in one launch
+                f, raw, oob = self._dev_obj.eval_many(np.stack(X_all, axis=1))
+                f_all = [(f[:, j], raw[:, j], oob[:, j]) for j in range(len(X_all))]
+        for j, X_new in enumerate(X_all):
+            new = []
+            for b in range(self.B):
+                if self.failed[b] is not None:
+                    continue
+                new_x = X_new[b].copy()
+                if f_all is not None:
+                    f_dev, raw_dev, oob_dev = f_all[j]
+                    new_f = float(f_dev[b])
+                    if not oob_dev[b]:               # keep the problem's own record (what the Analyzer rows are written from)
+                        p = self.problems[b]
+                        p.evaluations += 1
+                        p.best_raw = min(p.best_raw, float(raw_dev[b]))
+                        p.log.append((float(raw_dev[b]), new_x.copy()))
+                else:
+                    outside = not np.all(new_x >= self.bounds[b][:, 0]) or not np.all(new_x <= self.bounds[b][:, 1])
+                    # out-of-box candidates are not evaluated; they cost budget and a fixed penalty (PCA_BO.py:260-263)
+                    new_f = (-OOB_PENALTY if self.maximization else OOB_PENALTY) if outside else self.problems[b](new_x)
+                new.append((b, new_x, new_f))
+            self._append(n + j, new)
 
     def _append(self, n: int, new) -> None:
         """new: (run, point, objective value) of every run that goes on - its (n + 1)-th evaluated point."""
@@ -536,13 +643,18 @@ class BatchedVanillaBO(BatchedPCABO):
             tfit = self._fit_all(n)
         return self._boxes, raw, best_f, t1, t2, tfit
 
-    def _draw_noise_ahead(self, n: int) -> None:
+    def _search_boxes_packed(self) -> np.ndarray:
+        return self._boxes_packed
+
+    def _draw_noise_ahead(self, n: int, q_eff: int = 1) -> None:
         pass                                       # (no noise in front of a PCA here: the engines are all there is to make ahead)
 
-    def _new_points(self, chosen, n: int):
+    def _new_points(self, proposals, n: int):
         # (Vanilla_BO.py:221-232: the candidate lies in the box and is evaluated)
-        points = [(b, np.asarray(z, dtype=np.float64).ravel().copy()) for b, z in enumerate(chosen) if z is not None]
-        self._append(n, [(b, x, self.problems[b](x)) for b, x in points])
+        for j, chosen in enumerate(proposals):
+            points = [(b, np.asarray(z, dtype=np.float64).ravel().copy()) for b, z in enumerate(chosen)
+                      if z is not None and self.failed[b] is None]
+            self._append(n + j, [(b, x, self.problems[b](x)) for b, x in points])
         return ()                                  # (nothing to wait for: no inverse map, no fourth yield)
 
 

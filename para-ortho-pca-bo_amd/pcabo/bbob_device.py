@@ -59,6 +59,8 @@ class DeviceObjectives:
         lib.pcabo_bbob_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         lib.pcabo_bbob_destroy.argtypes = [C.c_void_p]
         lib.pcabo_bbob_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        lib.pcabo_bbob_eval_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                             C.c_void_p]
         stride = lib.pcabo_bbob_table_doubles(self.d)
         if stride < 0:
             raise _native.PcaboError(stride, "dimension not supported by the device objectives")
@@ -83,6 +85,21 @@ class DeviceObjectives:
         if rc != 0:
             raise _native.PcaboError(rc, "pcabo_bbob_eval failed")
         f = np.where(oob != 0, self.penalty, raw + self.f_opt)
+        return f, raw, oob.astype(bool)
+
+    def eval_many(self, X: np.ndarray):
+        """evaluate() for m candidates per run in one launch: X[B, m, d] -> (f[B, m], raw[B, m], oob[B, m]); candidate j of run b
+        as evaluate() gives it alone (`pcabo_bbob_eval_many`)."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 3 or X.shape[0] != self.B or X.shape[2] != self.d:
+            raise ValueError(f"eval_many takes X[B, m, d] = [{self.B}, m, {self.d}], got {X.shape}")
+        m = X.shape[1]
+        raw, oob = np.empty((self.B, m)), np.zeros((self.B, m), dtype=np.int32)
+        rc = _native.LIB.pcabo_bbob_eval_many(self._h, X.ctypes.data_as(C.c_void_p), m, self.lb, self.ub, self.penalty,
+                                              raw.ctypes.data_as(C.c_void_p), oob.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise _native.PcaboError(rc, "pcabo_bbob_eval_many failed")
+        f = np.where(oob != 0, self.penalty, raw + self.f_opt[:, None])
         return f, raw, oob.astype(bool)
 
     def close(self) -> None:
