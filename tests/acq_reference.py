@@ -1,9 +1,11 @@
-"""Extended-precision reference of log-EI and PI on a conditioned GP and the error units their results are judged in.
+"""Extended-precision reference of log-EI, PI, UCB and the posterior query on a conditioned GP and the error units
+their results are judged in.
 
-No tests here: `test_acq_reference_cpu.py` proves the reference and its units on a plain numpy restatement,
-`test_gpu_acq_edges.py` judges the HIP kernels that evaluate the acquisition (`k_acq_fast`, `k_acq_fused`,
-`k_acq_group`, `k_acq_combine`, the GEMM scoring of kernels_acq.hip and `lb_eval` of kernels_lbfgsb.hip, all on the
-scalar maths of acq_math.h) by them.
+No tests here: `test_acq_reference_cpu.py` and `test_ucb_posterior_reference_cpu.py` prove the reference and its units
+on a plain numpy restatement, `test_gpu_acq_edges.py` and `test_gpu_ucb_edges.py` judge the HIP kernels that evaluate
+the acquisition (`k_acq_fast`, `k_acq_fused`, `k_acq_group`, `k_acq_combine`, the GEMM scoring of kernels_acq.hip and
+`lb_eval` of kernels_lbfgsb.hip, all on the scalar maths of acq_math.h) by them, `test_gpu_posterior_edges.py` the
+posterior query (`k_post_combine`, `k_post_cov` of kernels_post.hip behind the scoring's first two launches).
 
 The reference starts from a CONDITIONED state {R, alpha, y_mean, y_std, norm_bounds}, fp64 arrays taken as exact (the
 conditioning has its own judge: gp_reference.py), so nothing of the conditioning's kappa-type factors enters.  For a
@@ -56,10 +58,37 @@ Underflow: as in gp_reference, an error up to 2^-1022 per element counts as none
 below u ~ -38).  `judge()` returns the worst ratio of values and of gradients; a NaN, or an error where the unit is
 0, is infinite.
 
-The module also holds the states, queries and scalars of the two test files (`make_state`, `cases`), a plain fp64 numpy
-restatement of the chain written as the kernels are (`restate`; keyword switches turn on one wrong variant each), and
-the conditions the device test relies on (`check_conditions`).
+UCB (`scalars_ucb`; acq_math.h's `acq == 2` branch, kappa >= 0 in the best_f slot) and the posterior query
+(`posterior`) are linear in the quantities of `linear()`, so they stay in long double and need no mpmath:
+  value = +-mu + kappa sigma,   c_mu = +-y_std,   c_sg = -kappa y_std^2 / sigma (0 where clamped),   g = c_mu A + c_sg B
+  u_value = dmu + kappa dsigma + eps (|kappa sigma| + |value|)       (the product and the sum, fused or not)
+  dc_mu = eps |c_mu|,   dc_sg = |c_sg| (dsigma / sigma + 3 eps)  (the square, the division, the product),   dg as above
+at a clamped variance sigma is sqrt(1e-10) whatever vv is: dsigma = 0, c_sg = dc_sg = 0, and the kappa term moves no
+gradient bit.
+  mean = y_mean + y_std mus                                     unit dmu
+  raw variance = ((1 - vv) [+ s2]) y_std^2                      unit dvar [+ eps y_std^2 (s2 + |1 - vv + s2|): one more sum]
+  variance = the raw one, or exactly 1e-10 (unit 0) where the raw one is below the floor - no raw variance, latent or
+             noisy, may lie within VAR_MARGIN units of it (`check_posterior_conditions`), so the side is never rounding's
+  cov_ab = y_std^2 (kq_ab [+ s2 delta_ab] - v_a . v_b), not floored; its diagonal is the raw variance with that unit
+  kq_ab = k(xn_a, xn_b) in the direct form; dkq_ab is dks with both points queries:
+          dd_c = 2 eps (|xn_ac| + |xn_bc|) + eps |d_c|,  dsq, dkq as dsq_j, dks_j above
+  d(v_a . v_b) = sum_i (|v_ai| dv_bi + |v_bi| dv_ai) + (n + 2) eps sum_i |v_ai v_bi|
+          (each factor off by its dv, and an n-term sum in any order; zero padding of v adds exact zeros)
+  u_cov_ab = y_std^2 (dkq_ab + d(v_a . v_b) + eps |kq_ab - v_a . v_b|) + 3 eps |cov_ab|
+          (the subtraction; y_std^2 and the product)
+The unit of an off-diagonal entry does not shrink with the entry: where kq - v_a . v_b cancels (a duplicated query,
+queries 1e-9 apart, a query on a training point) the error is held absolutely, at eps times the terms that cancel.
+There the slope of k in sq is largest (5/6, 1/2) and sq itself ~ 1e-18, so a distance formed as |a|^2 + |b|^2 - 2 a.b
+shows: it is off by roundings of |xn|^2 / l^2, not of sq.  That is a few eps at k = 1 - inside the unit, the norm form is
+then as good as the direct one - and 28 units per rounding at k = 128.
+
+The module also holds the states, queries and scalars of the test files (`make_state`, `cases`, `cases_ucb`), plain
+fp64 numpy restatements of the chains written as the kernels are (`restate`, `restate_posterior`; keyword switches
+turn on one wrong variant each), the conditions the device tests rely on (`check_conditions`,
+`check_ucb_conditions`, `check_posterior_conditions`) and the cache of references on a device's own state that the
+device test files share (`cached_linear`, `cached_scalars`, `cached_posterior`).
 """
+import hashlib
 import math
 from types import SimpleNamespace
 
@@ -69,7 +98,7 @@ import numpy as np
 from gp_reference import _ratio, hp_exp
 from wpca_reference import EPS, f64, hp, hp_sqrt
 
-LOG_EI, PI = 0, 1
+LOG_EI, PI, UCB = 0, 1, 2
 LENGTHSCALE, NOISE = 0.6931471805599453, 0.006737946999085467      # the defaults of gp_condition
 FLOOR = 1e-10                        # gpytorch's min_variance
 Q = 130                              # queries per state
@@ -77,6 +106,9 @@ PREFIXES = (5, 6, 32, 40, 130)       # what the evaluation paths take of them
 VAR_MARGIN = 32.0                    # no variance within this many dvar of the floor
 SEAM_QUERY = 4                       # the query whose u the seam incumbents are computed for (its duplicate: 3)
 FIXED_QUERIES = (0, 1, 2, 3, SEAM_QUERY)      # placed by hand in make_state, never redrawn
+NEAR_PAIRS = ((6, 7), (SEAM_QUERY, 129))      # (a, b): query b is query a + 1e-9, in one covariance tile and across two
+KAPPAS = (0.0, 0.5, math.sqrt(2.0), 1e3)      # UCB: the mean alone, two usual values, one where sigma carries everything
+POST_PREFIXES = (1, 15, 16, 17, 63, 64, 65, 130)      # what the posterior queries take of the Q queries
 MP = mpmath.mp.clone()
 MP.dps = 80
 _S5 = math.sqrt(5.0)
@@ -104,6 +136,7 @@ STATES = {
     "T": (64, 3, 1.0, "matern52", {"tail_inputs": True}),     # Z and y of test_log_ei_tail_branches
 }
 SMALL_STATES = [s for s in STATES if STATES[s][0] <= 130]
+POSTERIOR_STATES = SMALL_STATES + ["n257", "n513"]      # + two 256-column blocks of k_score_ks, and NP = 576
 
 
 # ---- states and queries ------------------------------------------------------------------------------------------
@@ -120,7 +153,7 @@ def search_box(Z):
 def make_state(name):
     """Seeded inputs of a state: the training points and values of test_gpu_ucb.py's recipe and Q queries, uniform in
     the search box widened by 20 %, with - inside every prefix the paths take - two training points (sq = 0 exactly),
-    a training point + 1e-9 and a duplicated query."""
+    a training point + 1e-9 and a duplicated query; behind them the followers of NEAR_PAIRS, 1e-9 off their leaders."""
     n, k, yscale, kernel, opt = STATES[name]
     if opt.get("tail_inputs"):
         rng = np.random.default_rng(3)
@@ -141,6 +174,8 @@ def make_state(name):
     X[0], X[1] = Z[0], Z[1]
     X[2] = Z[2 % n] + 1e-9
     X[3] = X[4]
+    for a, b in NEAR_PAIRS:
+        X[b] = X[a] + 1e-9
     st.X = X
     st.redrawn = []
     return st
@@ -161,19 +196,23 @@ _PREPARED = {}
 
 def prepared(name):
     """(state inputs, restated conditioned state, linear reference on it), once per process.  Queries whose variance
-    lies within VAR_MARGIN dvar of the floor are REDRAWN here (never skipped), deterministically, so that both test
-    files see the same queries."""
+    - latent, or with the observation noise - lies within VAR_MARGIN dvar of the floor are REDRAWN here (never
+    skipped), deterministically, so that all test files see the same queries; a follower of NEAR_PAIRS goes with its
+    leader."""
     if name not in _PREPARED:
         st = make_state(name)
         gs = restated_state(st)
         lin = linear(st, gs, st.X)
+        kept = set(FIXED_QUERIES) | {b for _, b in NEAR_PAIRS}
         for _ in range(20):
-            near = [i for i in np.flatnonzero(near_floor(lin)) if i not in FIXED_QUERIES]
+            near = [i for i in np.flatnonzero(near_floor(lin) | near_floor(lin, st.noise)) if i not in kept]
             if not near:
                 break
             for i in near:
                 st.X[i] = st.qrng.uniform(st.wide[0], st.wide[1])
                 st.redrawn.append(int(i))
+            for a, b in NEAR_PAIRS:
+                st.X[b] = st.X[a] + 1e-9
             lin = linear(st, gs, st.X)
         _PREPARED[name] = (st, gs, lin)
     return _PREPARED[name]
@@ -233,22 +272,26 @@ def linear(st, gs, X):
 
     dA = d_sum(np.broadcast_to(aal, (q, n)), np.zeros((q, n)))
     dB = d_sum(W, dw)
-    return SimpleNamespace(q=q, k=k, n=n, vv=vv, mus=mus, A=A, B=B, dvv=dvv, dmus=dmus, dA=dA, dB=dB,
+    return SimpleNamespace(q=q, k=k, n=n, vv=vv, mus=mus, A=A, B=B, dvv=dvv, dmus=dmus, dA=dA, dB=dB, v=v, dv=dv, xn=xn,
                            y_mean=float(gs["y_mean"]), y_std=float(gs["y_std"]), sq_min=f64(sq).min(axis=1))
 
 
-def _posterior(lin):
-    """fp64 views of mean, unfloored variance, its unit and the floored sigma."""
+def _posterior(lin, s2=None):
+    """fp64 views of mean, unfloored variance (with the noise s2 where given), its unit and the floored sigma."""
     ym, ysd = lin.y_mean, lin.y_std
     mu = ym + ysd * f64(lin.mus)
-    var = f64((1 - lin.vv) * (hp(ysd) * hp(ysd)))
-    dvar = ysd * ysd * (lin.dvv + EPS * (1.0 + 3.0 * np.abs(f64(1 - lin.vv))))
+    t = 1 - lin.vv
+    dvar = ysd * ysd * (lin.dvv + EPS * (1.0 + 3.0 * np.abs(f64(t))))
+    if s2 is not None:
+        t = t + hp(s2)
+        dvar = dvar + EPS * ysd * ysd * (s2 + np.abs(f64(t)))
+    var = f64(t * (hp(ysd) * hp(ysd)))
     return mu, var, dvar, np.sqrt(np.maximum(var, FLOOR))
 
 
-def near_floor(lin):
+def near_floor(lin, s2=None):
     """Queries whose variance lies within VAR_MARGIN dvar of the floor: which side they fall on is rounding's choice."""
-    _, var, dvar, _ = _posterior(lin)
+    _, var, dvar, _ = _posterior(lin, s2)
     return np.abs(var - FLOOR) <= VAR_MARGIN * dvar
 
 
@@ -306,7 +349,9 @@ def helper_units(u, du=0.0):
 
 
 def scalars(lin, best_f, maximize, acq):
-    """Values and gradients of the acquisition at the queries of `lin` with their units."""
+    """Values and gradients of the acquisition at the queries of `lin` with their units (acq UCB: `best_f` is kappa)."""
+    if acq == UCB:
+        return scalars_ucb(lin, best_f, maximize)
     q, k = lin.q, lin.k
     ym, ysd, sgn = lin.y_mean, lin.y_std, (1.0 if maximize else -1.0)
     value, u_value = hp(np.zeros(q)), np.zeros(q)
@@ -383,6 +428,114 @@ def agreement(ref, g_a, g_b):
     return _ratio(hp(g_a) - hp(g_b), ref.u_grad[:len(g_a)])
 
 
+# ---- UCB and the posterior query: linear in the quantities of `linear()`, in long double ---------------------------
+def scalars_ucb(lin, kappa, maximize):
+    """`scalars()` for the upper confidence bound (same return shape; u is not defined and left 0)."""
+    ym, ysd, sgn, kappa = lin.y_mean, lin.y_std, (1.0 if maximize else -1.0), float(kappa)
+    mu = hp(ym) + hp(ysd) * lin.mus
+    var = (1 - lin.vv) * (hp(ysd) * hp(ysd))
+    clamped = ~(var >= hp(FLOOR))
+    sigma = hp_sqrt(np.where(clamped, hp(FLOOR), var))
+    sf = f64(sigma)
+    dmu = ysd * lin.dmus + 2.0 * EPS * (abs(ym) + np.abs(ysd * f64(lin.mus)))
+    dvar = ysd * ysd * (lin.dvv + EPS * (1.0 + 3.0 * np.abs(f64(1 - lin.vv))))
+    dsig = np.where(clamped, 0.0, dvar / (2.0 * sf) + EPS * sf)
+    value = hp(sgn) * mu + hp(kappa) * sigma
+    u_value = dmu + kappa * dsig + EPS * (np.abs(kappa * sf) + np.abs(f64(value)))
+    c_mu = hp(sgn) * hp(ysd)
+    dc_mu = EPS * abs(sgn * ysd)
+    c_sg = np.where(clamped, hp(0.0), -hp(kappa) * (hp(ysd) * hp(ysd)) / sigma)
+    acs = np.abs(f64(c_sg))
+    dc_sg = acs * (dsig / sf + 3.0 * EPS)                                     # 0 where clamped: c_sg is 0 there
+    grad = c_mu * lin.A + c_sg[:, None] * lin.B
+    aA, aB, acm = np.abs(f64(lin.A)), np.abs(f64(lin.B)), abs(sgn * ysd)
+    u_grad = acm * lin.dA + aA * dc_mu + acs[:, None] * lin.dB + aB * dc_sg[:, None] \
+        + 2.0 * EPS * (acm * aA + acs[:, None] * aB)
+    return SimpleNamespace(value=value, grad=grad, u_value=u_value, u_grad=u_grad, u=np.zeros(lin.q), clamped=clamped)
+
+
+def posterior(st, lin, noise=False):
+    """Mean, floored variance and joint covariance of the posterior query at the queries of `lin`, with their units.
+    The floored variance is exactly FLOOR (unit 0) where the raw one is below it; `check_posterior_conditions` sees to
+    it that no raw variance is within rounding of the floor."""
+    q, k, n, ls, s2 = lin.q, lin.k, lin.n, float(st.lengthscale), float(st.noise)
+    ym, ysd = lin.y_mean, lin.y_std
+    ys2 = hp(ysd) * hp(ysd)
+    mean = hp(ym) + hp(ysd) * lin.mus
+    u_mean = ysd * lin.dmus + 2.0 * EPS * (abs(ym) + np.abs(ysd * f64(lin.mus)))
+    t = 1 - lin.vv
+    u_raw = ysd * ysd * (lin.dvv + EPS * (1.0 + 3.0 * np.abs(f64(t))))
+    if noise:
+        t = t + hp(s2)
+        u_raw = u_raw + EPS * ysd * ysd * (s2 + np.abs(f64(t)))
+    raw = t * ys2
+    clamped = ~(raw >= hp(FLOOR))
+    var, u_var = np.where(clamped, hp(FLOOR), raw), np.where(clamped, 0.0, u_raw)
+    xn = lin.xn
+    d = xn[:, None, :] - xn[None, :, :]                                         # q x q x k
+    ssq = (d * d).sum(axis=2)
+    sq = ssq / (hp(ls) * hp(ls))
+    kq, _, dkq_dsq, _, arg = _cov(sq, st.kernel, ls)
+    vab = lin.v @ lin.v.T
+    core = kq - vab
+    cov = ys2 * core
+    D, XN, V = np.abs(f64(d)), np.abs(f64(xn)), np.abs(f64(lin.v))
+    dd = 2.0 * EPS * (XN[:, None, :] + XN[None, :, :]) + EPS * D
+    dsq = (2.0 * (D * dd).sum(axis=2) + (k + 2) * EPS * f64(ssq)) / (ls * ls) + 3.0 * EPS * f64(sq)
+    dkq = f64(dkq_dsq) * dsq + EPS * np.abs(f64(kq)) * (4.0 + f64(arg))
+    dvab = V @ lin.dv.T + lin.dv @ V.T + (n + 2) * EPS * (V @ V.T)
+    u_cov = ysd * ysd * (dkq + dvab + EPS * np.abs(f64(core))) + 3.0 * EPS * np.abs(f64(cov))
+    i = np.arange(q)
+    cov[i, i], u_cov[i, i] = raw, u_raw                                         # the diagonal: the raw variance
+    return SimpleNamespace(mean=mean, u_mean=u_mean, variance=var, u_variance=u_var, raw=raw, u_raw=u_raw,
+                           covariance=cov, u_covariance=u_cov, clamped=clamped)
+
+
+def judge_posterior(ref, out):
+    """{mean, variance[, covariance]: worst ratio} of an implementation's posterior at the first len(mean) queries."""
+    q = len(out["mean"])
+    r = {"mean": _ratio(hp(out["mean"]) - ref.mean[:q], ref.u_mean[:q]),
+         "variance": _ratio(hp(out["variance"]) - ref.variance[:q], ref.u_variance[:q])}
+    if out.get("covariance") is not None:
+        r["covariance"] = _ratio(hp(out["covariance"]) - ref.covariance[:q, :q], ref.u_covariance[:q, :q])
+    return r
+
+
+# ---- references on a device's own state, shared by the device test files -----------------------------------------
+_REFS = {}
+
+
+def digest(gs):
+    h = hashlib.sha256()
+    for key in ("R", "alpha", "norm_bounds"):
+        h.update(np.ascontiguousarray(gs[key], dtype=np.float64).tobytes())
+    h.update(np.array([gs["y_mean"], gs["y_std"]], dtype=np.float64).tobytes())
+    return h.hexdigest()
+
+
+def cached_linear(st, gs):
+    """(key, linear part of the reference) on a conditioned state, once per distinct state (objects that hold the
+    same bits share it) and never modified."""
+    key = (st.name, digest(gs))
+    if key not in _REFS:
+        _REFS[key] = {"lin": linear(st, gs, st.X)}
+    return key, _REFS[key]["lin"]
+
+
+def cached_scalars(key, label, acq, mx, best):
+    """Reference of one scalar on one conditioned state, cached per (state, scalar)."""
+    if label not in _REFS[key]:
+        _REFS[key][label] = scalars(_REFS[key]["lin"], best, mx, acq)
+    return _REFS[key][label]
+
+
+def cached_posterior(st, key, noise):
+    label = ("posterior", bool(noise))
+    if label not in _REFS[key]:
+        _REFS[key][label] = posterior(st, _REFS[key]["lin"], noise)
+    return _REFS[key][label]
+
+
 # ---- the scalars of a state --------------------------------------------------------------------------------------
 def cases(lin):
     """[(label, acq, maximize, best_f)]: per direction log-EI at `near`, `mid` (50 s_y away) and `far` (1e9 s_y) as
@@ -410,8 +563,13 @@ def u_of(lin, best_f, maximize):
     return (1.0 if maximize else -1.0) * (mu - best_f) / sigma
 
 
-def check_conditions(name, st, lin):
-    """What the device test relies on, as a list of violations (empty: all hold)."""
+def cases_ucb(lin=None):
+    """[(label, UCB, maximize, kappa)]: every kappa of KAPPAS in both directions."""
+    return [("ucb,%d,%s" % (mx, ("%.3g" % kap)), UCB, mx, kap) for mx in (0, 1) for kap in KAPPAS]
+
+
+def _state_conditions(name, st, lin):
+    """The conditions on the queries and the variances, whatever is evaluated there."""
     bad = []
     X, Z = st.X, st.Z
     if not (np.array_equal(X[0], Z[0]) and np.array_equal(X[1], Z[1]) and np.array_equal(X[3], X[4])):
@@ -428,6 +586,35 @@ def check_conditions(name, st, lin):
         bad.append(("state mixed is not mixed", int(cl.sum())))
     if name not in ("E", "mixed") and cl.any():
         bad.append("a clamped variance outside E and mixed")
+    return bad
+
+
+def check_ucb_conditions(name, st, lin):
+    """What the device test of UCB relies on, as a list of violations (empty: all hold).  UCB has no u and no
+    branches: the conditions are those on the queries and on the floor."""
+    return _state_conditions(name, st, lin)
+
+
+def check_posterior_conditions(name, st, lin):
+    """What the device test of the posterior query relies on: the conditions on the queries and the floor, no variance
+    WITH the observation noise within rounding of the floor either, and the near-coincident pairs in place (1e-9 apart
+    per coordinate: a scaled squared distance above 0 and below 1e-12)."""
+    bad = _state_conditions(name, st, lin)
+    if near_floor(lin, st.noise).any():
+        bad.append(("noisy variance within %g dvar of the floor" % VAR_MARGIN, np.flatnonzero(near_floor(lin, st.noise))))
+    ls2 = float(st.lengthscale) ** 2
+    for a, b in NEAR_PAIRS:
+        sq = float(((lin.xn[a] - lin.xn[b]) ** 2).sum()) / ls2
+        if not (np.array_equal(st.X[b], st.X[a] + 1e-9) and 0.0 < sq < 1e-12):
+            bad.append(("near-coincident pair", a, b, sq))
+    if not float(((lin.xn[3] - lin.xn[4]) ** 2).sum()) == 0.0:
+        bad.append("the duplicate pair is not one")
+    return bad
+
+
+def check_conditions(name, st, lin):
+    """What the device test relies on, as a list of violations (empty: all hold)."""
+    bad = _state_conditions(name, st, lin)
     for label, _, maximize, best_f in cases(lin):
         u, tag = u_of(lin, best_f, maximize)[:32], label.split(",")[2]
         ok = {"near": (u > -0.5).any(), "mid": ((u < -2.0) & (u > -1e5)).all(), "far": (u < -1e7).all(),
@@ -502,6 +689,12 @@ def restate(st, gs, X, best_f, maximize, acq, coef53=5.0 / 3.0, drop_last_v=Fals
     clamped = ~(var >= FLOOR)
     sigma = np.sqrt(np.where(clamped, FLOOR, var))
     sgn = 1.0 if maximize else -1.0
+    if acq == UCB:                       # kappa in the best_f slot; the kernels' one fused multiply-add as two roundings
+        kappa = float(best_f)
+        c_sg = kappa * (-(ysd * ysd) / sigma)
+        if not csg_keep_clamped:
+            c_sg = np.where(clamped, 0.0, c_sg)
+        return kappa * sigma + sgn * mu, ((sgn * ysd) * gm + c_sg[:, None] * gs_) / (hi - lo)
     u = (mu - best_f) / sigma * sgn
     with np.errstate(all="ignore"):
         if acq == LOG_EI:
@@ -546,4 +739,81 @@ WRONG = {
     "tail asymptote in -1.5 < u < -1": (dict(tail_from=-1.5), "value",
                                         lambda st, label, ref: label.startswith("log_ei") and "seam-1-1e-6" in label),
     "PI's gradient with Phi for phi": (dict(pi_grad_Phi=True), "grad", lambda st, label, ref: label.startswith("pi")),
+}
+
+
+# ---- UCB and the posterior query in plain fp64 --------------------------------------------------------------------
+# UCB goes through `restate` (acq = UCB).  variant -> (keyword arguments of restate, what it damages, the kappas it can
+# be seen at, the states on which it must leave the device's limit)
+WRONG_UCB = {
+    "5/3 of the radial factor as a float32": (dict(coef53=np.float32(5.0 / 3.0)), "grad", KAPPAS, ("B", "D", "k128")),
+    "last row of v left out of |v|^2": (dict(drop_last_v=True), "any", KAPPAS[1:], ("A", "B", "B-rbf", "user")),
+    "c_sg kept at a clamped variance": (dict(csg_keep_clamped=True), "grad", KAPPAS[1:], ("E", "mixed")),
+}
+
+
+def _ks64(sq, kernel, coef53=5.0 / 3.0):
+    """The covariance of acq_math.h's `acq_cov` on an fp64 array of scaled squared distances."""
+    if kernel == "rbf":
+        return np.exp(-0.5 * sq)
+    dist = np.sqrt(np.maximum(sq, 1e-30))
+    return ((_S5 * dist + 1.0) + float(coef53) * (dist * dist)) * np.exp(-_S5 * dist)
+
+
+def restate_posterior(st, gs, X, noise=False, coef53=5.0 / 3.0, drop_last_v=False, qq_norms=False, diag_from_tile=False,
+                      floor_diag=False, noise_after=False):
+    """numpy fp64 restatement of the posterior query as kernels_post.hip writes it: direct distances, the 1e-30 guard,
+    V = R KS^T, the variance from the column norms of V, the covariance (k(Xq, Xq) - V^T V) s_y^2 with the raw variance
+    on its diagonal.  Each keyword switches on one wrong variant: the 5/3 of the Matern polynomial as a float32, the
+    last row of V dropped, the query-query distance as |a|^2 + |b|^2 - 2 a.b, the covariance's diagonal from the tile
+    product (whose epilogue knows no noise), the floor applied to that diagonal, the noise added after the
+    multiplication by s_y^2."""
+    X = np.asarray(X, dtype=np.float64)
+    R, alpha = np.tril(gs["R"]), np.asarray(gs["alpha"], dtype=np.float64)
+    lo, hi = gs["norm_bounds"][0], gs["norm_bounds"][1]
+    ym, ysd, ls, s2 = float(gs["y_mean"]), float(gs["y_std"]), float(st.lengthscale), float(st.noise)
+    il2 = (1.0 / ls) * (1.0 / ls)
+    xn, zn = (X - lo) / (hi - lo), (st.Z - lo) / (hi - lo)
+    d = xn[:, None, :] - zn[None, :, :]
+    ks = _ks64((d * d).sum(axis=2) * il2, st.kernel, coef53)
+    V = R @ ks.T                                                               # n x q
+    if drop_last_v:
+        V = V[:-1]
+    vv = (V * V).sum(axis=0)
+    mean = ym + ysd * (ks @ alpha)
+    if noise_after:
+        raw = (1.0 - vv) * (ysd * ysd) + (s2 if noise else 0.0)
+    else:
+        raw = ((1.0 - vv) + s2) * (ysd * ysd) if noise else (1.0 - vv) * (ysd * ysd)
+    var = np.where(raw >= FLOOR, raw, FLOOR)
+    if qq_norms:
+        # elementwise numpy only, so that every machine rounds alike: the norms summed over the coordinates in
+        # ascending order, the dot products as a tile product would chain them, four coordinates per step
+        kk = xn.shape[1]
+        nrm, dot = np.zeros(len(X)), np.zeros((len(X), len(X)))
+        prod = [xn[:, c, None] * xn[None, :, c] for c in range(kk)] + [np.zeros((len(X), len(X)))] * (-kk % 4)
+        for c in range(kk):
+            nrm = nrm + xn[:, c] * xn[:, c]
+        for c in range(0, kk, 4):
+            dot = dot + ((prod[c] + prod[c + 1]) + (prod[c + 2] + prod[c + 3]))
+        sqq = np.maximum((nrm[:, None] + nrm[None, :]) - 2.0 * dot, 0.0) * il2
+    else:
+        dq = xn[:, None, :] - xn[None, :, :]
+        sqq = (dq * dq).sum(axis=2) * il2
+    cov = (_ks64(sqq, st.kernel, coef53) - V.T @ V) * (ysd * ysd)
+    if not diag_from_tile:
+        i = np.arange(len(X))
+        cov[i, i] = var if floor_diag else raw
+    return {"mean": mean, "variance": var, "covariance": cov}
+
+
+# variant -> (keyword arguments of restate_posterior, the noise flags it can be seen under, the states on which it must
+# leave the device's limit)
+WRONG_POSTERIOR = {
+    "5/3 of the Matern polynomial as a float32": (dict(coef53=np.float32(5.0 / 3.0)), (False, True), ("A", "B", "D", "n64")),
+    "last row of v dropped": (dict(drop_last_v=True), (False, True), ("A", "B", "B-rbf", "user")),
+    "query-query distance as norms minus a dot product": (dict(qq_norms=True), (False, True), ("k128",)),
+    "covariance diagonal from the tile product": (dict(diag_from_tile=True), (True,), ("A", "B", "B-rbf", "user", "E")),
+    "floor applied to the covariance diagonal": (dict(floor_diag=True), (False, True), ("E", "mixed")),
+    "noise added after the multiplication by y_std^2": (dict(noise_after=True), (True,), ("A", "B", "user", "mixed")),
 }

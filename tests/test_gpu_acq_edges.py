@@ -14,7 +14,6 @@ and its kappa-type factors stay out of the units here.
 The entry points and their order are those of `test_gpu_ucb.py`; the incumbents are float64 (`PCABO_OPT_BESTF_F32`
 off, as for a numpy float64 incumbent), because the seam incumbents must put u at -1 and -1e6 to rounding.
 """
-import hashlib
 import time
 
 import numpy as np
@@ -38,31 +37,6 @@ DEEP_MIDDLE = ("mid", "seam-1e6")
 FAMILIES_UNITS = 2.0 * LIMIT           # two results within LIMIT units of the reference are this close to each other
 PATHS = ("q5", "q6", "finish32", "combine40", "fast130", "gemm130", "group5", "group6", "group32", "group40",
          "group130", "groupgemm130", "batch130", "device32")
-_REFS = {}
-
-
-def _digest(gs):
-    h = hashlib.sha256()
-    for key in ("R", "alpha", "norm_bounds"):
-        h.update(np.ascontiguousarray(gs[key], dtype=np.float64).tobytes())
-    h.update(np.array([gs["y_mean"], gs["y_std"]], dtype=np.float64).tobytes())
-    return h.hexdigest()
-
-
-def _linear(st, gs):
-    """Linear part of the reference on a conditioned state, once per distinct state (objects that hold the same bits
-    share it) and never modified."""
-    key = (st.name, _digest(gs))
-    if key not in _REFS:
-        _REFS[key] = {"lin": A.linear(st, gs, st.X)}
-    return key, _REFS[key]["lin"]
-
-
-def _scalar_ref(key, label, acq, mx, best):
-    """Reference of one scalar on one conditioned state, cached per (state, scalar)."""
-    if label not in _REFS[key]:
-        _REFS[key][label] = A.scalars(_REFS[key]["lin"], best, mx, acq)
-    return _REFS[key][label]
 
 
 def _verr(v, ov):
@@ -103,14 +77,14 @@ def test_log_ei_and_pi_against_the_reference_on_every_path(native, name, capsys)
                               kernel=kcode)
         _, status = bt.gp_wait_eval([X], [float(y.min())], False, native.ACQ_LOG_EI)
         assert not status.any()
-        keys = {}
+        keys, lins = {}, {}
         for tag, c in (("ctx", ctx), ("grp", grp), ("bt", bt.ctx[0])):
             gs = c.gp_state()
             if st.norm_bounds is not None:
                 assert np.array_equal(gs["norm_bounds"], st.norm_bounds)
-            keys[tag], lin = _linear(st, gs)
-            assert A.check_conditions(name, st, lin) == [], (name, tag)            # on the device's own state, not skipped
-        lin = _REFS[keys["ctx"]]["lin"]
+            keys[tag], lins[tag] = A.cached_linear(st, gs)
+            assert A.check_conditions(name, st, lins[tag]) == [], (name, tag)      # on the device's own state, not skipped
+        lin = lins["ctx"]
         worst, fails = {}, []
 
         def note(path, label, ref, v, g=None):
@@ -122,7 +96,7 @@ def test_log_ei_and_pi_against_the_reference_on_every_path(native, name, capsys)
 
         between_worst, between_units = 0.0, 0.0
         for label, acq, mx, best in A.cases(lin):
-            ref, gref, bref = (_scalar_ref(keys[t], label, acq, mx, best) for t in ("ctx", "grp", "bt"))
+            ref, gref, bref = (A.cached_scalars(keys[t], label, acq, mx, best) for t in ("ctx", "grp", "bt"))
             out = {}
             for q, path in ((5, "q5"), (6, "q6"), (32, "finish32"), (40, "combine40"), (130, "fast130")):
                 out[path] = ctx.acq_eval(X[:q], best, mx, acq)
@@ -162,7 +136,7 @@ def test_log_ei_and_pi_against_the_reference_on_every_path(native, name, capsys)
         if not between_units <= FAMILIES_UNITS:
             fails.append(("families, deep middle branch, in units", between_units))
         for tag, c in (("ctx", ctx), ("grp", grp), ("bt", bt.ctx[0])):        # every re-conditioning gave the bits judged
-            if (st.name, _digest(c.gp_state())) != keys[tag]:
+            if (st.name, A.digest(c.gp_state())) != keys[tag]:
                 fails.append(("the conditioned state changed between conditionings", tag))
     finally:
         ctx.close()

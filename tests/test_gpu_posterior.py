@@ -11,6 +11,7 @@ tests/golden/late_state_d40.npz.
 Error units: mean |d| / max(1, |mean|); variance and covariance |d| / s_y^2 (the prior variance, the scale of the cancellation
 1 - |v|^2).  Tolerances: 10 x the largest error measured against the reference on an MI355X over CASES, the late state and the two
 fitted states (the first test prints the worst ratios; EXPERIMENTS.md "GP posterior queries" has them per shape).
+tests/test_gpu_posterior_edges.py judges the same kernels in derived fp64 error units, every covariance entry in its own.
 """
 import os
 

@@ -5,6 +5,7 @@ acq_math.h, which kernels_acq.hip and `lb_eval` in kernels_lbfgsb.hip share; kap
   * bad kappa / unknown acquisition codes are argument errors that leave the context usable;
   * a run inside a batch equals the same run alone, the device-resident L-BFGS-B equals its host-stepped twin, bit for bit;
   * a free PCA_BO run replayed iteration by iteration from the oracle's public functions.
+The tolerances of the first are measured ones; tests/test_gpu_ucb_edges.py judges the same paths in derived fp64 error units.
 """
 import numpy as np
 import pytest
