@@ -503,7 +503,11 @@ int pcabo_batch_gp_truncate(pcabo_batch* batch, int n0, int* status /*[B], may b
 int pcabo_batch_gp_extended(pcabo_batch* batch, int* n_base, int* n);
 /* Rows M-N for every run (pcabo_optimize_acqf semantics per run).  ics[B][num_restarts*max_d] (dense num_restarts x k_b per
  * block), bounds[B][2*max_d] as pcabo_batch_acq_bounds gives them, best_f[B]; cand[B][num_restarts*max_d] (dense per block),
- * vals[B][num_restarts], info[B][4*ngroups] or NULL, failed[B], status[B]. */
+ * vals[B][num_restarts], info[B][4*ngroups] or NULL, failed[B], status[B].
+ * Runs that are not optimised, in every mode of PCABO_OPT_DEVICE_LBFGSB and for the _begin / _end halves alike: a run parked by
+ * pcabo_batch_set_active gets status[b] = PCABO_ERR_ARG, a run WITHOUT A GP - its conditioning ended on PCABO_ERR_NOT_PD, or it is set
+ * aside by pcabo_batch_gp_extend - gets status[b] = PCABO_ERR_NOT_PD; failed[b] = 0 for both, their blocks of ics and bounds are not
+ * read and their blocks of cand, vals and info are left as they are.  The call itself returns PCABO_OK. */
 int pcabo_batch_optimize_acqf(pcabo_batch* batch, const double* ics, int num_restarts, int batch_limit,
                               const double* bounds, int maxiter, const double* best_f, int maximize, int acq,
                               double* cand, double* vals, int* info, int* failed, int* status);

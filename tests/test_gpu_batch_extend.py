@@ -15,8 +15,8 @@ max_q: the issue sets 32 for the file.  The round-trip and optimiser tests use 1
 applies (its records lie behind 64 values of a run's value buffer) and pcabo_batch_device_acq_eval refuses; those tests assert that
 the device path ran.
 
-Not covered: a run WITHOUT a GP beside extended ones - tests/test_gpu_batch.py has no case whose conditioning fails, so there is no
-established way to make one.
+A run WITHOUT a GP beside extended ones (its batched conditioning failed), and an extend at a non-zero rung of the jitter ladder, are
+in tests/test_gpu_batch_rare_paths.py (test_one_run_ends_without_a_gp, test_downstream_of_a_climbed_run).
 """
 import copy
 
