@@ -17,10 +17,11 @@
 // Every kernel here returns at once where the info word is not 0: the points behind a failed one change nothing.
 // All sums have one order and there are no atomics: the same call on the same state gives the same bytes.
 // The kernels address their operands as the conditioning's do (blockIdx.z = run, zs bytes per run, k from k_dev, 1 / lengthscale
-// and the noise from a run's hyperparameter block).  pcabo_gp_extend launches them for a single context: one run, strides 0;
-// pcabo_batch_gp_extend for all runs of a batch at once, every run with a header of its own.  A run that takes no part in the call
-// has the info word EXT_INFO_SKIP, written by the host: not 0, so the kernels here (and the gated form of launch_alpha between them)
-// leave its bytes alone, and negative, so it is never taken for a failed point.
+// and the noise from a run's hyperparameter block).  ONE host sequence launches them (ext_append / ext_take_back in pcabo_api.hip, on
+// an ExtSite): for a single context - one run, strides 0 - and for all runs of a batch at once, every run with a header of its own.
+// A run that takes no part in the call has the info word EXT_INFO_SKIP, written by the host: not 0, so the kernels here (and the
+// gated form of launch_alpha between them) leave its bytes alone, and negative, so it is never taken for a failed point.
+// The launchers take the arrays a call writes as one record (GpArrays, built by gp_arrays(ctx)), as they take the model as GpModel.
 #include "pcabo_internal.h"
 #include "acq_math.h"
 
@@ -187,14 +188,12 @@ void launch_ext_ks(hipStream_t st, const double* X, int xi, const double* Y, int
                      m.bounds4, m.ystats, inv_ls, kernel, e.ks, e.small, ab.zs, ab.k_dev, ab.hyp);
 }
 void launch_ext_append(hipStream_t st, const GpModel& m, const ExtScratch& e, int idx, int believer, double s2, double inv_ls,
-                       const double* zn_mean, double* L, double* R, double* ZnT, double* AT, double* nrm, double* ys, AcqBatch ab,
-                       int B) {
+                       const GpArrays& a, AcqBatch ab, int B) {
   const int groups = m.n == m.NP ? 1 + (m.NP + 64) / 64 : 1;
   hipLaunchKernelGGL(k_ext_append, dim3(groups, 1, B), dim3(256), 0, st, e.v, e.w, e.small, idx, believer, (m.NP + 255) / 256, m.n, m.k,
-                     m.NP, m.ld, s2, inv_ls, zn_mean, L, R, ZnT, AT, nrm, ys, ab.zs, ab.k_dev, ab.hyp);
+                     m.NP, m.ld, s2, inv_ls, a.zn_mean, a.L, a.R, a.ZnT, a.AT, a.nrm, a.ys, ab.zs, ab.k_dev, ab.hyp);
 }
-void launch_ext_truncate(hipStream_t st, const ExtScratch& e, int n0, int k, int NP, int ld, double* L, double* R, double* ZnT,
-                         double* AT, double* nrm, double* ys, AcqBatch ab, int B) {
-  hipLaunchKernelGGL(k_ext_truncate, dim3(NP / 64, 1, B), dim3(256), 0, st, e.small, n0, k, NP, ld, L, R, ZnT, AT, nrm, ys, ab.zs,
-                     ab.k_dev);
+void launch_ext_truncate(hipStream_t st, const ExtScratch& e, int n0, int k, int NP, int ld, const GpArrays& a, AcqBatch ab, int B) {
+  hipLaunchKernelGGL(k_ext_truncate, dim3(NP / 64, 1, B), dim3(256), 0, st, e.small, n0, k, NP, ld, a.L, a.R, a.ZnT, a.AT, a.nrm, a.ys,
+                     ab.zs, ab.k_dev);
 }

@@ -440,13 +440,6 @@ struct RowsDH {
                                          // every run's own where its zb.hyp block has PCABO_HYP_ARD_FOLD set
   hipEvent_t ev_zn = nullptr;            // recorded behind k_znorm (null: none): ZnT and the Normalize bounds are final
 };
-// The per-query tickets are consistent only with acq_slabs(NP): where NP changes outside a conditioning (pcabo_gp_extend /
-// pcabo_gp_truncate) they are reset as enqueue_rows_dh resets them.
-static int ext_tickets(pcabo_ctx* ctx, hipStream_t s) {
-  if (!ctx->st.tickets_reset_if_needed(acq_slabs(ctx->st.NP))) return PCABO_OK;
-  HIPCHK(hipMemsetAsync(ctx->dCounters, 0, ticket_bytes(ctx), s));
-  return PCABO_OK;
-}
 template <class Phase>
 static int enqueue_factor(pcabo_ctx* ctx, hipStream_t s, int n, int NP, ZB zb, Phase&& phase) {
   if (const int rc = phase(2)) return rc;
@@ -964,6 +957,7 @@ static AcqParams make_params(pcabo_ctx* ctx, double best_f, int maximize, int ac
 
 // the conditioned model of a context as the acquisition launchers take it
 static GpModel gp_model(const pcabo_ctx* c) { return {c->st.n, c->st.k, c->st.NP, c->ld, c->dZnT, c->dR, c->dAlpha, c->dBounds4, c->dYstats}; }
+static GpArrays gp_arrays(const pcabo_ctx* c) { return {c->dZnMean, c->dL, c->dR, c->dZnT, c->dAT, c->dNrm, c->dYs}; }
 
 // The outcome of waiting for an acquisition launch's flags
 static int acq_published(pcabo_ctx* ctx, FlagWait w) {
@@ -2487,47 +2481,85 @@ int pcabo_batch_gp_loo(pcabo_batch* batch, double* mean, double* var, double* z,
   return PCABO_OK;
 }
 
-// ---- appending points to the conditioned GP and taking them back (DESIGN.md "Extending a conditioned GP") -----------------------
+}  // extern "C" (helpers with C++ linkage follow)
+// ---- appending points to the conditioned GP and taking them back (DESIGN.md "Extending a conditioned GP", "Extending the GPs of a
+// batch"): ONE host sequence for a single context and for the B runs of a batch -------------------------------------------------
 // The fantasy model of botorch's condition_on_observations: transforms and hyperparameters held, only the data grow.  Per point
-// k_ext_ks, the two matrix-vector launches of launch_alpha on the kernel vector (v = R ks, w = R^T v) and k_ext_append
-// (kernels_ext.hip); behind the last point (believer mode: behind every point, the next one reads the mean) launch_alpha on the
-// grown y_s, then ONE copy of the info word and one wait.  A pivot that fails stops the writes of everything behind it on the
-// device; the host then takes the call back with truncate's launches.  The scratch is the head of dPartial (ExtScratch); the points
-// travel through dXq, as many rows at a time as fit.  Of the state that later calls read, n, NP, L, R, ZnT, AT, nrm, y_s and alpha
-// change, the tickets are reset where NP changes and the transposed root inverse of the device-resident optimiser is marked stale;
-// the search box, the pinned staging, the sequence numbers, the second stream and chol_info are not touched.
+// k_ext_ks, v = R ks and w = R^T v (launch_alpha's two launches on the kernel vector) and k_ext_append (kernels_ext.hip); behind the
+// last point (believer mode: behind every point, the next one reads the mean) alpha on the grown y_s, then ONE copy of the info
+// word(s) and one wait.  A pivot that fails stops the writes of everything behind it on the device; the host then takes the call
+// back with truncate's launches.  Of the state that later calls read, n, NP, L, R, ZnT, AT, nrm, y_s and alpha change, the tickets
+// are reset where NP changes and the transposed root inverse of the device-resident optimiser is marked stale.
+// A batch: the same launches for all runs at once (blockIdx.z = run), every run with its own header {rung, info word}; a run that
+// takes no part (parked, without a GP, set aside) gets the info word EXT_INFO_SKIP and is left alone by the kernels of
+// kernels_ext.hip and by the gated form of launch_alpha.  A run whose pivot failed is taken back alone, as one run on its own
+// buffers, and is then SET ASIDE (model_state.h) until a truncate reaches the n it holds.
 struct ExtHeader { double rung; int info, pad; };
 static_assert(sizeof(ExtHeader) == EXT_HDR * sizeof(double), "the header the kernels of kernels_ext.hip read");
 
+// What an extension needs beyond the posterior call's site.  A plain or a strided copy, launch_alpha or its gated form: by owner
+// (zs, gate), never by B == 1 - a batch of one run keeps its header with EXT_INFO_SKIP, the gated alpha and its strided copies.
+struct ExtSite {
+  const PostSite& w;                 // the owner: its stream, model and parameters; whose error text is written
+  pcabo_ctx* c;                      // whose buffers the launches name: the context, run 0 of a batch, or a member taken back alone
+  ExtScratch e; GpArrays a;          // the scratch at the head of c's dPartial; the arrays the kernels write
+  int k, B = 1; size_t zs = 0; AcqBatch ab; ZB zb;      // (a batch: the widest run's k, every run reads its own from ab.k_dev)
+  const int* gate = nullptr;         // a batch: run 0's gate word, which is the info word of its header
+  std::vector<char> go;              // who takes part (a context: itself)
+  ExtSite(const PostSite& site, pcabo_ctx* own)      // one run on its own buffers: the launches of a single context
+      : w(site), c(own), e(own->dPartial, own->lay.s), a(gp_arrays(own)), k(own->st.k), go(1, 1) {}
+  explicit ExtSite(const PostSite& site) : ExtSite(site, site.c0) {
+    if (!site.batch) return;
+    k = site.xq_cols; B = site.B; zs = site.zs; ab = site.ab; zb = batch_zb(site.batch); gate = info_word(); go.assign((size_t)B, 0);
+  }
+  int* info_word() const { return reinterpret_cast<int*>(e.small + EXT_HDR_INFO); }
+  pcabo_ctx* run(int b) const { return gate ? w.batch->ctx[b] : c; }
+};
+
 static GpModel ext_model(const PostSite& w, int n) { GpModel m = w.m; m.n = n; m.NP = round_up(n, PCABO_BS); return m; }
+static bool all_finite(const double* v, size_t n) { return std::all_of(v, v + n, [](double t) { return std::isfinite(t); }); }
 
-// The header: the rung, and the info word cleared.  hdr lives until the caller has waited for the stream.
-static int ext_put_header(const PostSite& w, const ExtScratch& e, ExtHeader* hdr) {
-  *hdr = ExtHeader{w.ctx->st.rung, 0, 0};
-  PHIPCHK(hipMemcpyAsync(e.small + EXT_HDR_RUNG, hdr, sizeof(ExtHeader), hipMemcpyHostToDevice, w.s));
+// What an extend refuses whoever owns the model: the text behind the entry point's name (%d: max_n), or null.  The counts mean
+// something only where a GP stands: without one, post_state_check behind this refuses the call.
+static const char* ext_arg_error(const PostSite& w, const double* Zp, const double* yp, int p, int flags, int n, int max_n) {
+  if (!Zp) return "%s: Zp is required";
+  if (flags & ~PCABO_EXTEND_BELIEVER) return "%s: unknown flag bits";
+  if (!yp && !(flags & PCABO_EXTEND_BELIEVER)) return "%s: yp is required without PCABO_EXTEND_BELIEVER";
+  if (p < 1) return "%s: p must be at least 1";
+  if (w.ready != GP_READY) return nullptr;
+  if (n + p > max_n) return "%s: n + p exceeds max_n (%d)";
+  if ((round_up(n + p, PCABO_BS) + 255) / 256 > EXT_MU_MAX) return "%s: n + p beyond what the kernels cover";
+  return nullptr;
+}
+
+// The header(s) on their way: every run's rung, the info word cleared where the run takes part and EXT_INFO_SKIP elsewhere.
+// hdr (x.B of them) lives until the caller has waited for the stream.
+static int ext_put_headers(const ExtSite& x, ExtHeader* hdr) {
+  const PostSite& w = x.w;
+  for (int b = 0; b < x.B; ++b) hdr[b] = ExtHeader{x.run(b)->st.rung, x.go[b] ? 0 : EXT_INFO_SKIP, 0};
+  if (x.zs) PHIPCHK(hipMemcpy2DAsync(x.e.small + EXT_HDR_RUNG, x.zs, hdr, sizeof(ExtHeader), sizeof(ExtHeader), x.B, hipMemcpyHostToDevice, w.s));
+  else PHIPCHK(hipMemcpyAsync(x.e.small + EXT_HDR_RUNG, hdr, sizeof(ExtHeader), hipMemcpyHostToDevice, w.s));
   return PCABO_OK;
 }
 
-// The host's side of a changed n: the counts, the tickets where NP changed, the transposed root inverse marked stale.
-static int ext_set_n(const PostSite& w, int n) {
-  w.ctx->st.n_changed(n);
-  return ext_tickets(w.ctx, w.s);
-}
-
-// alpha = R^T (R y_s) on n points - the conditioning's own launches
-static void ext_alpha(const PostSite& w, int n) {
-  pcabo_ctx* c = w.ctx;
-  launch_alpha(w.s, c->dR, c->dYs, n, round_up(n, PCABO_BS), c->ld, c->dTmp, c->dAlpha);
-}
-
-// Points n0 .. are taken back (the header is on the stream already) and alpha follows; no wait.
-static int ext_take_back(const PostSite& w, const ExtScratch& e, int n0, int n_now) {
-  pcabo_ctx* c = w.ctx;
-  launch_ext_truncate(w.s, e, n0, c->st.k, round_up(n_now, PCABO_BS), c->ld, c->dL, c->dR, c->dZnT, c->dAT, c->dNrm, c->dYs);
-  if (const int rc = ext_set_n(w, n0)) return rc;
-  ext_alpha(w, n0);
+// The per-query tickets are consistent only with acq_slabs(NP): where NP changes outside a conditioning they are reset as
+// enqueue_rows_dh resets them - a batch's those of ALL runs, where its record or a member's asks.
+static int ext_tickets(const ExtSite& x) {
+  const PostSite& w = x.w;
+  const bool reset = w.batch ? w.batch->st.tickets_reset_if_needed(acq_slabs(w.batch->st.m.NP), w.batch->run_st)
+                             : w.ctx->st.tickets_reset_if_needed(acq_slabs(w.ctx->st.NP));
+  if (!reset) return PCABO_OK;
+  if (x.zs) PHIPCHK(hipMemset2DAsync(x.c->dCounters, x.zs, 0, ticket_bytes(x.c), x.B, w.s));
+  else PHIPCHK(hipMemsetAsync(x.c->dCounters, 0, ticket_bytes(x.c), w.s));
   return PCABO_OK;
 }
+
+// out = R^T (R y) on n points - the conditioning's own launches, or their gated form with the site's gate word
+static void ext_rtr(const ExtSite& x, const double* y, int n, double* tmp, double* out) {
+  if (x.gate) launch_alpha_gated(x.w.s, x.c->dR, y, n, round_up(n, PCABO_BS), x.c->ld, tmp, out, x.zb, x.gate);
+  else launch_alpha(x.w.s, x.c->dR, y, n, round_up(n, PCABO_BS), x.c->ld, tmp, out);
+}
+static void ext_alpha(const ExtSite& x, int n) { ext_rtr(x, x.c->dYs, n, x.c->dTmp, x.c->dAlpha); }
 
 static int ext_wait(const PostSite& w) {
   PHIPCHK(wait_stream(w.s));
@@ -2535,55 +2567,76 @@ static int ext_wait(const PostSite& w) {
   return PCABO_OK;
 }
 
+// p points appended behind the n0 there are: the header(s), then at most rows_cap points at a time (those that fit dXq with their
+// values, at the widest k).  stage(i0, rows, vals) puts rows i0 .. of every run at the head of its dXq and, where values are given,
+// their values vals doubles behind - the one step that differs between the owners.  record() is the owner's side of the new n: the
+// counts, then ext_tickets.  Behind it alpha, the info word(s) to info (x.B of them) with one copy, one wait.
+template <class Stage, class Record>
+static int ext_append(const ExtSite& x, ExtHeader* hdr, int n0, int p, bool believer, bool values, int* info, Stage&& stage,
+                      Record&& record) {
+  const PostSite& w = x.w;
+  if (const int rc = ext_put_headers(x, hdr)) return rc;
+  const int rows_cap = ext_rows_cap(x.c->lay.s, w.xq_cols);
+  const size_t vals = xq_ext_vals(x.c->lay.s, w.xq_cols).start;
+  double* dY = values ? x.c->dXq + vals : nullptr;
+  int n = n0;
+  for (int i0 = 0; i0 < p; i0 += rows_cap) {
+    const int rows = std::min(rows_cap, p - i0);
+    if (const int rc = stage(i0, rows, vals)) return rc;
+    for (int i = 0; i < rows; ++i, ++n) {
+      const GpModel m = ext_model(w, n);
+      launch_ext_ks(w.s, x.c->dXq, i, dY, i, m, w.p.inv_ls, w.p.kernel, x.e, x.ab, x.B);
+      ext_rtr(x, x.e.ks, n, x.e.v, x.e.w);
+      launch_ext_append(w.s, m, x.e, i0 + i, believer ? 1 : 0, w.noise, w.p.inv_ls, x.a, x.ab, x.B);
+      if (believer && i0 + i + 1 < p) ext_alpha(x, n + 1);
+    }
+  }
+  if (const int rc = record()) return rc;
+  ext_alpha(x, n);
+  if (x.zs) PHIPCHK(hipMemcpy2DAsync(info, sizeof(int), x.info_word(), x.zs, sizeof(int), x.B, hipMemcpyDeviceToHost, w.s));
+  else PHIPCHK(hipMemcpyAsync(info, x.info_word(), sizeof(int), hipMemcpyDeviceToHost, w.s));
+  return ext_wait(w);
+}
+
+// Points n0 .. of the n_now there are go: the header(s), k_ext_truncate, and alpha on n0 points behind record(), the owner's side
+// of the changed n (a member of a batch taken back alone: none here, its batch follows it up).  The caller waits.
+template <class Record>
+static int ext_take_back(const ExtSite& x, ExtHeader* hdr, int n0, int n_now, Record&& record) {
+  if (const int rc = ext_put_headers(x, hdr)) return rc;
+  launch_ext_truncate(x.w.s, x.e, n0, x.k, round_up(n_now, PCABO_BS), x.c->ld, x.a, x.ab, x.B);
+  if (const int rc = record()) return rc;
+  ext_alpha(x, n0);
+  return PCABO_OK;
+}
+
+extern "C" {
+// A context copies the points straight from the caller's arrays (device pointers in PCABO_PTR_DEVICE mode).
 int pcabo_gp_extend(pcabo_ctx* ctx, const double* Zp, const double* yp, int p, int flags) {
   if (!ctx) return PCABO_ERR_ARG;
   const char* name = "pcabo_gp_extend";
   if (ctx->in_batch) return set_err(ctx, PCABO_ERR_ARG, "%s: the context belongs to a batch", name);      // (its lock-step form: pcabo_batch_gp_extend)
   const PostSite w(ctx);
-  if (!Zp) return w.fail(PCABO_ERR_ARG, "%s: Zp is required", name);
-  if (flags & ~PCABO_EXTEND_BELIEVER) return w.fail(PCABO_ERR_ARG, "%s: unknown flag bits", name);
-  const bool believer = (flags & PCABO_EXTEND_BELIEVER) != 0;
-  if (!yp && !believer) return w.fail(PCABO_ERR_ARG, "%s: yp is required without PCABO_EXTEND_BELIEVER", name);
-  if (believer) yp = nullptr;
-  if (p < 1) return w.fail(PCABO_ERR_ARG, "%s: p must be at least 1", name);
-  if (const int rc = post_state_check(w, name)) return rc;
   const int n0 = ctx->st.n, k = ctx->st.k;
-  if (n0 + p > ctx->max_n) return w.fail(PCABO_ERR_ARG, "%s: n + p exceeds max_n (%d)", name, ctx->max_n);
-  if ((round_up(n0 + p, PCABO_BS) + 255) / 256 > EXT_MU_MAX) return w.fail(PCABO_ERR_ARG, "%s: n + p beyond what the kernels cover", name);
+  if (const char* why = ext_arg_error(w, Zp, yp, p, flags, n0, ctx->max_n)) return w.fail(PCABO_ERR_ARG, why, name, ctx->max_n);
+  if (const int rc = post_state_check(w, name)) return rc;
+  const bool believer = (flags & PCABO_EXTEND_BELIEVER) != 0;
+  if (believer) yp = nullptr;
   if (w.in == hipMemcpyHostToDevice) {                 // host pointers: every coordinate and value
-    for (size_t i = 0; i < (size_t)p * k; ++i)
-      if (!std::isfinite(Zp[i])) return w.fail(PCABO_ERR_ARG, "%s: a coordinate is not finite", name);
-    for (int i = 0; yp && i < p; ++i)
-      if (!std::isfinite(yp[i])) return w.fail(PCABO_ERR_ARG, "%s: a value is not finite", name);
+    if (!all_finite(Zp, (size_t)p * k)) return w.fail(PCABO_ERR_ARG, "%s: a coordinate is not finite", name);
+    if (yp && !all_finite(yp, (size_t)p)) return w.fail(PCABO_ERR_ARG, "%s: a value is not finite", name);
   }
   PHIPCHK(hipSetDevice(w.device));
-  const ExtScratch e(ctx->dPartial, ctx->lay.s);
+  const ExtSite x(w);
+  const auto set_n = [&](int n) { ctx->st.n_changed(n); return ext_tickets(x); };
   ExtHeader hdr;
-  if (const int rc = ext_put_header(w, e, &hdr)) return rc;
-  const int rows_cap = ext_rows_cap(ctx->lay.s, k);      // points that fit dXq with their values
-  double* dY = yp ? ctx->dXq + xq_ext_vals(ctx->lay.s, k).start : nullptr;
-  int n = n0;
-  for (int i0 = 0; i0 < p; i0 += rows_cap) {
-    const int rows = std::min(rows_cap, p - i0);
-    PHIPCHK(hipMemcpyAsync(ctx->dXq, Zp + (size_t)i0 * k, (size_t)rows * k * sizeof(double), w.in, w.s));
-    if (yp) PHIPCHK(hipMemcpyAsync(dY, yp + i0, (size_t)rows * sizeof(double), w.in, w.s));
-    for (int i = 0; i < rows; ++i, ++n) {
-      const GpModel m = ext_model(w, n);
-      launch_ext_ks(w.s, ctx->dXq, i, dY, i, m, w.p.inv_ls, w.p.kernel, e);
-      launch_alpha(w.s, ctx->dR, e.ks, m.n, m.NP, m.ld, e.v, e.w);
-      launch_ext_append(w.s, m, e, i0 + i, believer ? 1 : 0, w.noise, w.p.inv_ls, ctx->dZnMean, ctx->dL, ctx->dR, ctx->dZnT, ctx->dAT,
-                        ctx->dNrm, ctx->dYs);
-      if (believer && i0 + i + 1 < p) ext_alpha(w, n + 1);
-    }
-  }
-  if (const int rc = ext_set_n(w, n)) return rc;
-  ext_alpha(w, n);
   int fail = 0;
-  PHIPCHK(hipMemcpyAsync(&fail, reinterpret_cast<char*>(e.small + EXT_HDR_INFO), sizeof(int), hipMemcpyDeviceToHost, w.s));
-  if (const int rc = ext_wait(w)) return rc;
-  if (fail == 0) return PCABO_OK;
-  if (const int rc = ext_put_header(w, e, &hdr)) return rc;
-  if (const int rc = ext_take_back(w, e, n0, n)) return rc;
+  const int rc = ext_append(x, &hdr, n0, p, believer, yp != nullptr, &fail, [&](int i0, int rows, size_t vals) -> int {
+    PHIPCHK(hipMemcpyAsync(ctx->dXq, Zp + (size_t)i0 * k, (size_t)rows * k * sizeof(double), w.in, w.s));
+    if (yp) PHIPCHK(hipMemcpyAsync(ctx->dXq + vals, yp + i0, (size_t)rows * sizeof(double), w.in, w.s));
+    return PCABO_OK;
+  }, [&] { return set_n(n0 + p); });
+  if (rc || fail == 0) return rc;
+  if (const int rc = ext_take_back(x, &hdr, n0, n0 + p, [&] { return set_n(n0); })) return rc;
   if (const int rc = ext_wait(w)) return rc;
   return w.fail(PCABO_ERR_NOT_PD, "%s: the bordered matrix is not positive definite at new point %d; the call has been taken back", name, fail - 1);
 }
@@ -2598,10 +2651,9 @@ int pcabo_gp_truncate(pcabo_ctx* ctx, int n0) {
   if (n0 < ctx->st.n_base || n0 > n) return w.fail(PCABO_ERR_ARG, "%s: n0 must lie in n_base .. n", name);
   if (n0 == n) return PCABO_OK;
   PHIPCHK(hipSetDevice(w.device));
-  const ExtScratch e(ctx->dPartial, ctx->lay.s);
+  const ExtSite x(w);
   ExtHeader hdr;
-  if (const int rc = ext_put_header(w, e, &hdr)) return rc;
-  if (const int rc = ext_take_back(w, e, n0, n)) return rc;
+  if (const int rc = ext_take_back(x, &hdr, n0, n, [&] { ctx->st.n_changed(n0); return ext_tickets(x); })) return rc;
   return ext_wait(w);
 }
 
@@ -2612,112 +2664,56 @@ int pcabo_gp_extended(pcabo_ctx* ctx, int* n_base, int* n) {
   return PCABO_OK;
 }
 
-// ---- the same for the runs of a batch in lock-step (DESIGN.md "Extending the GPs of a batch") -----------------------------------
-// ONE launch sequence per point for all runs (blockIdx.z = run), every run with its own header {rung, info word} in its scratch,
-// written by one strided copy; a run that takes no part (parked, without a GP, set aside) gets the info word EXT_INFO_SKIP and is
-// left alone by the three kernels of kernels_ext.hip and by the gated form of launch_alpha.  One strided copy brings the B info
-// words back, one wait.  A run whose pivot failed has stopped on the device at that point; it alone is taken back to the n of entry
-// with the launches of a single context on its own buffers and is then SET ASIDE (model_state.h) until a truncate reaches that n.
-// The points travel through the runs' pinned hXq to their dXq, as many rows at a time as fit with the widest run's k.
-static bool batch_ext_takes_part(const pcabo_batch* batch, int b) { return batch->active[b] && batch->ctx[b]->st.conditioned(); }
-
-// the headers of all runs: run b's rung, and info 0 where go[b], EXT_INFO_SKIP elsewhere.  hdr lives until the stream was waited for.
-static int batch_ext_put_headers(const PostSite& w, const ExtScratch& e, const std::vector<char>& go, std::vector<ExtHeader>* hdr) {
-  hdr->resize((size_t)w.B);
-  for (int b = 0; b < w.B; ++b) (*hdr)[b] = ExtHeader{w.batch->ctx[b]->st.rung, go[b] ? 0 : EXT_INFO_SKIP, 0};
-  PHIPCHK(hipMemcpy2DAsync(e.small + EXT_HDR_RUNG, w.zs, hdr->data(), sizeof(ExtHeader), sizeof(ExtHeader), w.B, hipMemcpyHostToDevice, w.s));
-  return PCABO_OK;
-}
-// the batch's tickets follow acq_slabs(NP) as a conditioning's do: those of ALL runs, where the batch's record or a member's asks
-static int batch_ext_tickets(const PostSite& w) {
-  pcabo_batch* batch = w.batch;
-  if (!batch->st.tickets_reset_if_needed(acq_slabs(batch->st.m.NP), batch->run_st)) return PCABO_OK;
-  PHIPCHK(hipMemset2DAsync(w.c0->dCounters, w.zs, 0, ticket_bytes(w.c0), w.B, w.s));
-  return PCABO_OK;
-}
-static const int* batch_ext_gate(const ExtScratch& e) { return reinterpret_cast<const int*>(e.small + EXT_HDR_INFO); }
-
+// A batch packs the points of the runs that take part through their pinned hXq (which is waited for when the staging goes round
+// again: rare, p beyond rows_cap) and sends them with one strided copy.
 int pcabo_batch_gp_extend(pcabo_batch* batch, const double* Zp, const double* yp, int p, int flags, int* status) {
   if (!batch) return PCABO_ERR_ARG;
   const char* name = "pcabo_batch_gp_extend";
   const PostSite w(batch);
-  if (!Zp) return w.fail(PCABO_ERR_ARG, "%s: Zp is required", name);
-  if (flags & ~PCABO_EXTEND_BELIEVER) return w.fail(PCABO_ERR_ARG, "%s: unknown flag bits", name);
-  const bool believer = (flags & PCABO_EXTEND_BELIEVER) != 0;
-  if (!yp && !believer) return w.fail(PCABO_ERR_ARG, "%s: yp is required without PCABO_EXTEND_BELIEVER", name);
-  if (believer) yp = nullptr;
-  if (p < 1) return w.fail(PCABO_ERR_ARG, "%s: p must be at least 1", name);
+  const int B = w.B, n0 = batch->st.m.n, MD = batch->max_d;
+  if (const char* why = ext_arg_error(w, Zp, yp, p, flags, n0, batch->max_n)) return w.fail(PCABO_ERR_ARG, why, name, batch->max_n);
   if (const int rc = post_state_check(w, name)) return rc;
-  const int B = w.B, n0 = batch->st.m.n, MD = batch->max_d, kmax = w.xq_cols;
-  if (n0 + p > batch->max_n) return w.fail(PCABO_ERR_ARG, "%s: n + p exceeds max_n (%d)", name, batch->max_n);
-  if ((round_up(n0 + p, PCABO_BS) + 255) / 256 > EXT_MU_MAX) return w.fail(PCABO_ERR_ARG, "%s: n + p beyond what the kernels cover", name);
-  std::vector<char> part((size_t)B, 0);
+  const bool believer = (flags & PCABO_EXTEND_BELIEVER) != 0;
+  if (believer) yp = nullptr;
+  ExtSite x(w);
   for (int b = 0; b < B; ++b) {                        // every coordinate and value of the runs that take part; the others' are not read
-    if (!(part[b] = batch_ext_takes_part(batch, b))) continue;
-    const double* z = Zp + (size_t)b * p * MD;
-    for (size_t i = 0; i < (size_t)p * batch->ctx[b]->st.k; ++i)
-      if (!std::isfinite(z[i])) return w.fail(PCABO_ERR_ARG, "%s: a coordinate of run %d is not finite", name, b);
-    for (int i = 0; yp && i < p; ++i)
-      if (!std::isfinite(yp[(size_t)b * p + i])) return w.fail(PCABO_ERR_ARG, "%s: a value of run %d is not finite", name, b);
+    if (!(x.go[b] = w.live(b))) continue;                 // (active and conditioned: not parked, without a GP or set aside)
+    if (!all_finite(Zp + (size_t)b * p * MD, (size_t)p * batch->ctx[b]->st.k))
+      return w.fail(PCABO_ERR_ARG, "%s: a coordinate of run %d is not finite", name, b);
+    if (yp && !all_finite(yp + (size_t)b * p, (size_t)p)) return w.fail(PCABO_ERR_ARG, "%s: a value of run %d is not finite", name, b);
   }
   PHIPCHK(hipSetDevice(w.device));
-  pcabo_ctx* c0 = w.c0;
-  const ExtScratch e(c0->dPartial, c0->lay.s);
-  const int* gate = batch_ext_gate(e);
-  const ZB zb = batch_zb(batch);
-  std::vector<ExtHeader> hdr;
-  if (const int rc = batch_ext_put_headers(w, e, part, &hdr)) return rc;
-  const int rows_cap = ext_rows_cap(c0->lay.s, kmax);     // points that fit dXq with their values, at the widest run's k
-  const size_t vals = xq_ext_vals(c0->lay.s, kmax).start;
-  double* dY = yp ? c0->dXq + vals : nullptr;
-  int n = n0;
-  for (int i0 = 0; i0 < p; i0 += rows_cap) {
-    const int rows = std::min(rows_cap, p - i0);
-    if (i0 > 0) PHIPCHK(wait_stream(w.s));               // (the pinned staging goes round again: rare, p beyond rows_cap)
+  const int n = n0 + p;
+  std::vector<ExtHeader> hdr((size_t)B);
+  std::vector<int> info((size_t)B, 0);
+  const int rc = ext_append(x, hdr.data(), n0, p, believer, yp != nullptr, info.data(), [&](int i0, int rows, size_t vals) -> int {
+    if (i0 > 0) PHIPCHK(wait_stream(w.s));
     for (int b = 0; b < B; ++b) {
-      if (!part[b]) continue;
+      if (!x.go[b]) continue;
       pcabo_ctx* c = batch->ctx[b];
       const int k = c->st.k;
       memcpy(c->hXq, Zp + (size_t)b * p * MD + (size_t)i0 * k, (size_t)rows * k * sizeof(double));
       if (yp) memcpy(c->hXq + vals, yp + (size_t)b * p + i0, (size_t)rows * sizeof(double));
     }
-    const size_t staged = yp ? vals + (size_t)rows : (size_t)rows * kmax;
-    PHIPCHK(hipMemcpy2DAsync(c0->dXq, w.zs, c0->hXq, batch->hzs, staged * sizeof(double), B, hipMemcpyHostToDevice, w.s));
-    for (int i = 0; i < rows; ++i, ++n) {
-      const GpModel m = ext_model(w, n);
-      launch_ext_ks(w.s, c0->dXq, i, dY, i, m, w.p.inv_ls, w.p.kernel, e, w.ab, B);
-      launch_alpha_gated(w.s, c0->dR, e.ks, m.n, m.NP, m.ld, e.v, e.w, zb, gate);
-      launch_ext_append(w.s, m, e, i0 + i, believer ? 1 : 0, w.noise, w.p.inv_ls, c0->dZnMean, c0->dL, c0->dR, c0->dZnT, c0->dAT,
-                        c0->dNrm, c0->dYs, w.ab, B);
-      if (believer && i0 + i + 1 < p)
-        launch_alpha_gated(w.s, c0->dR, c0->dYs, n + 1, round_up(n + 1, PCABO_BS), c0->ld, c0->dTmp, c0->dAlpha, zb, gate);
-    }
-  }
-  batch->st.points_appended(p);
-  if (const int rc = batch_ext_tickets(w)) return rc;
-  launch_alpha_gated(w.s, c0->dR, c0->dYs, n, round_up(n, PCABO_BS), c0->ld, c0->dTmp, c0->dAlpha, zb, gate);
-  std::vector<int> info((size_t)B, 0);
-  PHIPCHK(hipMemcpy2DAsync(info.data(), sizeof(int), gate, w.zs, sizeof(int), B, hipMemcpyDeviceToHost, w.s));
-  if (const int rc = ext_wait(w)) return rc;
-  // the runs whose pivot failed: each alone back to the bytes of entry (the launches of ext_take_back on the member's own buffers)
+    const size_t staged = yp ? vals + (size_t)rows : (size_t)rows * w.xq_cols;
+    PHIPCHK(hipMemcpy2DAsync(x.c->dXq, w.zs, x.c->hXq, batch->hzs, staged * sizeof(double), B, hipMemcpyHostToDevice, w.s));
+    return PCABO_OK;
+  }, [&] { batch->st.points_appended(p); return ext_tickets(x); });
+  if (rc) return rc;
+  // the runs whose pivot failed: each alone back to the bytes of entry; its record follows below
   int failed = 0, first_bad = -1, first_point = 0;
   for (int b = 0; b < B; ++b) {
-    if (!part[b] || info[b] <= 0) continue;
-    pcabo_ctx* c = batch->ctx[b];
-    const ExtScratch eb(c->dPartial, c->lay.s);
-    hdr[b] = ExtHeader{c->st.rung, 0, 0};
-    PHIPCHK(hipMemcpyAsync(eb.small + EXT_HDR_RUNG, &hdr[b], sizeof(ExtHeader), hipMemcpyHostToDevice, w.s));
-    launch_ext_truncate(w.s, eb, n0, c->st.k, round_up(n, PCABO_BS), c->ld, c->dL, c->dR, c->dZnT, c->dAT, c->dNrm, c->dYs);
-    launch_alpha(w.s, c->dR, c->dYs, n0, round_up(n0, PCABO_BS), c->ld, c->dTmp, c->dAlpha);
+    if (!x.go[b] || info[b] <= 0) continue;
+    if (const int rc = ext_take_back(ExtSite(w, batch->ctx[b]), &hdr[b], n0, n, [] { return (int)PCABO_OK; })) return rc;
     if (!failed++) { first_bad = b; first_point = info[b] - 1; }
   }
   if (failed)
     if (const int rc = ext_wait(w)) return rc;
   for (int b = 0; b < B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
-    const bool ok = part[b] && info[b] == 0;
+    const bool ok = x.go[b] && info[b] == 0;
     c->st.follow_extend(batch->st, ok, n0);
-    if (status) status[b] = ok ? PCABO_OK : part[b] ? PCABO_ERR_NOT_PD : PCABO_ERR_ARG;
+    if (status) status[b] = ok ? PCABO_OK : x.go[b] ? PCABO_ERR_NOT_PD : PCABO_ERR_ARG;
   }
   if (failed) {
     snprintf(batch->err, sizeof(batch->err), "%s: run %d: the bordered matrix is not positive definite at new point %d; %d run(s) "
@@ -2734,33 +2730,24 @@ int pcabo_batch_gp_truncate(pcabo_batch* batch, int n0, int* status) {
   const int B = w.B, n = batch->st.m.n;
   if (!batch->st.can_truncate_to(n0)) return w.fail(PCABO_ERR_ARG, "%s: n0 must lie in n_base .. n", name);
   // who holds rows beyond n0: a live run (n of them), a run set aside that this call brings back (aside_n of them)
-  std::vector<char> go((size_t)B, 0);
+  ExtSite x(w);
   bool any = false;
-  for (int b = 0; b < B; ++b) {
-    go[b] = batch->ctx[b]->st.own().rows_beyond(n0, n);
-    any = any || go[b];
-  }
+  for (int b = 0; b < B; ++b) any = (x.go[b] = batch->ctx[b]->st.own().rows_beyond(n0, n)) || any;
+  const auto record = [&] { batch->st.points_taken_back(n0); return ext_tickets(x); };
   if (any) {
     PHIPCHK(hipSetDevice(w.device));
-    pcabo_ctx* c0 = w.c0;
-    const ExtScratch e(c0->dPartial, c0->lay.s);
-    std::vector<ExtHeader> hdr;
-    if (const int rc = batch_ext_put_headers(w, e, go, &hdr)) return rc;
-    launch_ext_truncate(w.s, e, n0, w.xq_cols, round_up(n, PCABO_BS), c0->ld, c0->dL, c0->dR, c0->dZnT, c0->dAT, c0->dNrm, c0->dYs, w.ab, B);
-    batch->st.points_taken_back(n0);
-    if (const int rc = batch_ext_tickets(w)) return rc;
-    launch_alpha_gated(w.s, c0->dR, c0->dYs, n0, round_up(n0, PCABO_BS), c0->ld, c0->dTmp, c0->dAlpha, batch_zb(batch), batch_ext_gate(e));
+    std::vector<ExtHeader> hdr((size_t)B);
+    if (const int rc = ext_take_back(x, hdr.data(), n0, n, record)) return rc;
     if (const int rc = ext_wait(w)) return rc;
   } else if (n0 < n) {
     PHIPCHK(hipSetDevice(w.device));
-    batch->st.points_taken_back(n0);
-    if (const int rc = batch_ext_tickets(w)) return rc;
+    if (const int rc = record()) return rc;
     if (const int rc = ext_wait(w)) return rc;
   }
   for (int b = 0; b < B; ++b) {
     pcabo_ctx* c = batch->ctx[b];
     c->st.follow_truncate(batch->st, n0);
-    if (status) status[b] = batch_ext_takes_part(batch, b) ? PCABO_OK : PCABO_ERR_ARG;
+    if (status) status[b] = w.live(b) ? PCABO_OK : PCABO_ERR_ARG;
   }
   return PCABO_OK;
 }

@@ -420,14 +420,15 @@ void launch_loo(hipStream_t st, const double* R, const double* alpha, const doub
 // dPartial, which every evaluation writes before it reads (ExtScratch and the EXT_* words of its small block: ctx_layout.h).
 // m: the model BEFORE the point (n, NP); X / Y: the staged points and values of the call, row xi / entry yi this one's (Y null:
 // believer mode, the value is the model's mean there).  launch_alpha(R, e.ks, n, NP, ld, e.v, e.w) goes between the two.
+// GpArrays: the arrays of a run (run 0 of a batch) that an appended point or a take-back writes, and zn_mean, which the append reads.
+struct GpArrays { const double* zn_mean; double *L, *R, *ZnT, *AT, *nrm, *ys; };
 void launch_ext_ks(hipStream_t st, const double* X, int xi, const double* Y, int yi, const GpModel& m, double inv_ls, int kernel,
                    const ExtScratch& e, AcqBatch ab = AcqBatch(), int B = 1);
 void launch_ext_append(hipStream_t st, const GpModel& m, const ExtScratch& e, int idx, int believer, double s2, double inv_ls,
-                       const double* zn_mean, double* L, double* R, double* ZnT, double* AT, double* nrm, double* ys,
-                       AcqBatch ab = AcqBatch(), int B = 1);
+                       const GpArrays& a, AcqBatch ab = AcqBatch(), int B = 1);
 // NP: the padded size before the call
-void launch_ext_truncate(hipStream_t st, const ExtScratch& e, int n0, int k, int NP, int ld, double* L, double* R, double* ZnT,
-                         double* AT, double* nrm, double* ys, AcqBatch ab = AcqBatch(), int B = 1);
+void launch_ext_truncate(hipStream_t st, const ExtScratch& e, int n0, int k, int NP, int ld, const GpArrays& a,
+                         AcqBatch ab = AcqBatch(), int B = 1);
 void launch_score_tail(hipStream_t st, int q, const GpModel& m, AcqParams p, const double* KS, double* partial, double* val);
 // resident mode available for this shape? (fast path + every group of the grid co-resident)
 bool acq_server_possible(int q, int n, int k, int NP);

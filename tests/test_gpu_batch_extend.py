@@ -503,6 +503,50 @@ def test_a_scoring_of_the_extended_batch_leaves_a_run_aside(native, bt):
     assert all(p is not None for p in bt.gp_posterior(probes))
 
 
+def test_a_batch_of_one_run(native, singles):
+    """B = 1 is still a batch: its run keeps a header with the skip word, the gated matrix-vector launches and the strided copies.
+    With the module's B = 3 nothing would notice a batch of one run taking the single context's branches.  n = 63, p = 2: the second
+    point opens a new 64-block.  The failing input is the far-away finite point of test_a_pivot_that_fails_in_one_run_only."""
+    n, p = 63, 2
+    cases = _cases(n, 5)[:1]
+    Xp, yp = _new_points(cases, p)
+    bt = native.Batch(1, max_n=MAX_N, max_d=MAX_D, max_q=MAX_Q)
+    try:
+        _condition_batch(native, bt, cases)
+        before = _batch_model_bytes(bt, cases)
+        entry = _state_bytes(bt.ctx[0].gp_state())                 # L, R, alpha, the Normalize bounds, the Standardize statistics
+        assert entry == before[0][:6]
+        # (a) the run parked: it takes no part, the extend and the truncate write none of its bytes
+        bt.set_active([0])
+        new_n, status = bt.gp_extend(Xp, yp)
+        assert new_n == n + p and list(status) == [ERR_ARG] and bt.ctx[0].n == n
+        assert _state_bytes(bt.ctx[0].gp_state()) == entry
+        assert bt.gp_truncate() == n
+        assert _state_bytes(bt.ctx[0].gp_state()) == entry
+        bt.set_active([1])
+        assert _batch_model_bytes(bt, cases) == before
+        # (b) the run active, values given; (c) believer mode: the bytes of a single context, and those of before once taken back
+        for values in (yp, None):
+            new_n, status = bt.gp_extend(Xp, values)
+            assert new_n == n + p == bt.ctx[0].n and bt.n_base == n and list(status) == [OK]
+            assert _batch_model_bytes(bt, cases) == _alone(native, singles, cases, Xp, values, (0,)), values is None
+            assert bt.gp_truncate() == n
+            assert _batch_model_bytes(bt, cases) == before, values is None
+        # (d) a pivot that fails (the second point: ks and d2 are NaN): the run is taken back to the bytes of entry and set aside
+        bad = [Xp[0].copy()]
+        bad[0][1] = 1e200
+        new_n, status = bt.gp_extend(bad, yp)
+        assert new_n == n + p and list(status) == [NOT_PD] and bt.ctx[0].n == n
+        assert "run 0" in bt._err() and "new point 1" in bt._err() and "positive definite" in bt._err()
+        assert _state_bytes(bt.ctx[0].gp_state()) == entry
+        _refused(native, lambda: bt.ctx[0].gp_loo())
+        assert bt.gp_posterior([_probes(cases[0], 17, 2)])[0] is None
+        assert bt.gp_truncate(n) == n                               # ... and live again
+        assert _batch_model_bytes(bt, cases) == before
+    finally:
+        bt.close()
+
+
 def test_a_refused_fit_leaves_the_extension_alone(native, bt):
     """pcabo_batch_gp_fit_ard with too small an ld_theta on an extended batch: refused, and n, n_base and every run's bytes stay."""
     n, k = 20, 3
