@@ -87,6 +87,14 @@ fp64 numpy restatements of the chains written as the kernels are (`restate`, `re
 turn on one wrong variant each), the conditions the device tests rely on (`check_conditions`,
 `check_ucb_conditions`, `check_posterior_conditions`) and the cache of references on a device's own state that the
 device test files share (`cached_linear`, `cached_scalars`, `cached_posterior`).
+
+STATES ends with four states of the stress region (d = 100 runs: n = 300 .. 1050, k ~ 85; STRESS_STATES), each with
+the code forms it is the first to reach and the arithmetic that puts them there: `k_acq_fused<32>` with k > 32,
+`k_acq_group<2>` at k > 40 and with more than 64 KB of LDS, `k_acq_group<5>` with five live columns, the group context
+beyond `acq_group_possible`, the second iteration of `grad_partial_sum`'s unrolled loop, `k_acq_combine` and
+`k_post_combine` over more than 18 records, more than three `k_score_ks` blocks, more than nine row blocks of
+`k_score_gemm` and panels of `k_post_cov`.  `test_gpu_optimize_edges.py` judges the optimiser's end points at k > 40
+with the same reference.
 """
 import hashlib
 import math
@@ -134,9 +142,37 @@ STATES = {
     "user": (100, 5, 1.0, "rbf", {"user_bounds": True, "lengthscale": 0.4, "noise": 1e-3}),
     "mixed": (30, 3, 1.2e-6, "matern52", {}),   # like E; clamped and free variances among the first 32 queries
     "T": (64, 3, 1.0, "matern52", {"tail_inputs": True}),     # Z and y of test_log_ei_tail_branches
+    # The stress region (d = 100 runs: n = 300 .. 1050, k ~ 85).  NP = 64 ceil(n / 64); S = NP / 32 slabs of 32 rows;
+    # a group of q queries passes q k coordinates, as kernel arguments up to PCABO_QA_MAX = 416 and through a pointer
+    # beyond; k_acq_group<CPT> holds CPT = ceil(NP / 256) columns per thread and, by launch_acq_group's formula, needs
+    # 65 568 bytes of dynamic LDS at (NP, k) = (512, 83) and 65 488 at k = 82: 83 is the smallest k past 64 KB there.
+    # The two high-k states take a longer lengthscale than ln 2: at ln 2 a query in 65 normalised dimensions sees no
+    # training point (median |v|^2 <= 2e-3), every gradient part through R is rounding-sized and a wrong R-part would
+    # sit inside the unit; test_acq_reference_cpu.py holds their median |v|^2 to >= 0.01.
+    #
+    # n385k65, NP = 448 = ACQ_SLAB32_NP: k_acq_fused<32> with k > 32 - three trips of its gradient contraction
+    # (c0 = 0, 32, 64 < 65), the second trip of acq_tail's and acq_finish_query's `c = l; c < k; c += 64` (c = 64)
+    # and the c != l side of acq_tail's bounds selection; k_acq_group<2> (CPT = ceil(448 / 256)) at k > 40; k_post_cov's
+    # second c0 += 64 trip over 7 panels of V; q k = 5 * 65 = 325 and 6 * 65 = 390 as kernel arguments, 32 * 65 = 2080
+    # through the pointer; optimize_acqf on the host-paced paths at k > 40 (test_gpu_optimize_edges.py).
+    "n385k65": (385, 65, 1.0, "matern52", {"lengthscale": 2.0}),
+    # n449k83, NP = 512: k_acq_group<2> with 65 568 bytes of dynamic LDS, the smallest k past the 64 KB default;
+    # q k = 5 * 83 = 415 of PCABO_QA_MAX = 416 as kernel arguments, 6 * 83 = 498 through the pointer; S = 16.
+    "n449k83": (449, 83, 1.0, "matern52", {"lengthscale": 2.5}),
+    # n1025, NP = 1088: k_acq_group<5> with all five columns per thread live (ceil(1088 / 256) = 5; n513 uses three);
+    # S = 34 slabs, so k_acq_combine over S > 18 records; 17 row blocks of k_score_gemm (> 9), whose 17 records per
+    # query k_post_combine adds; ceil(1088 / 256) = 5 blocks of k_score_ks (> 3); k_post_cov over 17 panels of V (> 9).
+    "n1025": (1025, 5, 1.0, "matern52", {}),
+    # n1473, NP = 1536 > 1280: beyond acq_group_possible, what a PCABO_OPT_GROUP_ACQ context does instead; S = 48 >= 46,
+    # so grad_partial_sum's eight-at-a-time loop (`sl + 21 < S; sl += 24`) runs its second iteration; 6 blocks of
+    # k_score_ks, 24 row blocks of k_score_gemm and so k_post_combine over 24 > 18 records, k_post_cov over 24 panels.
+    "n1473": (1473, 2, 1.0, "matern52", {}),
 }
 SMALL_STATES = [s for s in STATES if STATES[s][0] <= 130]
-POSTERIOR_STATES = SMALL_STATES + ["n257", "n513"]      # + two 256-column blocks of k_score_ks, and NP = 576
+STRESS_STATES = ["n385k65", "n449k83", "n1025", "n1473"]
+HIGH_K_STATES = ["n385k65", "n449k83"]                   # the ones that carry their own lengthscale
+# + two 256-column blocks of k_score_ks, and NP = 576; + the stress states: up to six blocks, 24 row blocks and panels
+POSTERIOR_STATES = SMALL_STATES + ["n257", "n513"] + STRESS_STATES
 
 
 # ---- states and queries ------------------------------------------------------------------------------------------
@@ -746,8 +782,8 @@ WRONG = {
 # UCB goes through `restate` (acq = UCB).  variant -> (keyword arguments of restate, what it damages, the kappas it can
 # be seen at, the states on which it must leave the device's limit)
 WRONG_UCB = {
-    "5/3 of the radial factor as a float32": (dict(coef53=np.float32(5.0 / 3.0)), "grad", KAPPAS, ("B", "D", "k128")),
-    "last row of v left out of |v|^2": (dict(drop_last_v=True), "any", KAPPAS[1:], ("A", "B", "B-rbf", "user")),
+    "5/3 of the radial factor as a float32": (dict(coef53=np.float32(5.0 / 3.0)), "grad", KAPPAS, ("B", "D", "k128", "n385k65")),
+    "last row of v left out of |v|^2": (dict(drop_last_v=True), "any", KAPPAS[1:], ("A", "B", "B-rbf", "user", "n385k65")),
     "c_sg kept at a clamped variance": (dict(csg_keep_clamped=True), "grad", KAPPAS[1:], ("E", "mixed")),
 }
 
@@ -810,10 +846,10 @@ def restate_posterior(st, gs, X, noise=False, coef53=5.0 / 3.0, drop_last_v=Fals
 # variant -> (keyword arguments of restate_posterior, the noise flags it can be seen under, the states on which it must
 # leave the device's limit)
 WRONG_POSTERIOR = {
-    "5/3 of the Matern polynomial as a float32": (dict(coef53=np.float32(5.0 / 3.0)), (False, True), ("A", "B", "D", "n64")),
-    "last row of v dropped": (dict(drop_last_v=True), (False, True), ("A", "B", "B-rbf", "user")),
+    "5/3 of the Matern polynomial as a float32": (dict(coef53=np.float32(5.0 / 3.0)), (False, True), ("A", "B", "D", "n64", "n385k65")),
+    "last row of v dropped": (dict(drop_last_v=True), (False, True), ("A", "B", "B-rbf", "user", "n385k65")),
     "query-query distance as norms minus a dot product": (dict(qq_norms=True), (False, True), ("k128",)),
-    "covariance diagonal from the tile product": (dict(diag_from_tile=True), (True,), ("A", "B", "B-rbf", "user", "E")),
+    "covariance diagonal from the tile product": (dict(diag_from_tile=True), (True,), ("A", "B", "B-rbf", "user", "E", "n385k65")),
     "floor applied to the covariance diagonal": (dict(floor_diag=True), (False, True), ("E", "mixed")),
-    "noise added after the multiplication by y_std^2": (dict(noise_after=True), (True,), ("A", "B", "user", "mixed")),
+    "noise added after the multiplication by y_std^2": (dict(noise_after=True), (True,), ("A", "B", "user", "mixed", "n385k65")),
 }

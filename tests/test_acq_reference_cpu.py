@@ -6,7 +6,8 @@ distance, `R @ ks`, the three branches of `log_ei_helper` through scipy's erfcx 
 (limit 4, the margin of the wPCA and GP proofs) on conditioned states of `gp_reference.restate`, and if wrong variants
 of it leave them (more than 16, on the small states more than 1600).  The same file asserts what the device test
 relies on without checking it itself: the hand-placed queries, the branches the incumbents reach, no variance within
-rounding of the 1e-10 floor.
+rounding of the 1e-10 floor.  The four stress states (n385k65, n449k83, n1025, n1473) are proved like the others; the
+wrong variants must be seen on the first of them, and the arithmetic that puts each code form at its state is asserted.
 """
 import numpy as np
 import pytest
@@ -15,7 +16,8 @@ import acq_reference as A
 
 LIMIT = 4.0
 DEVICE_LIMIT = 16.0
-PROVED = A.SMALL_STATES + ["C"]            # every state with n <= 130, and the n = 449 state
+PROVED = A.SMALL_STATES + ["C"] + A.STRESS_STATES     # every state with n <= 130, n = 449, and the stress states
+WRONG_ON = A.SMALL_STATES + ["C", "n385k65"]          # where the wrong variants must be seen: + the first stress state
 _REFS = {}
 
 
@@ -101,7 +103,7 @@ def test_units_notice_wrong_variant(variant, capsys):
     kw, what, applies = A.WRONG[variant][:3]
     strength = A.WRONG[variant][3] if len(A.WRONG[variant]) > 3 else None
     seen, bad = [], []
-    for name in PROVED:
+    for name in WRONG_ON:
         st, gs, _ = A.prepared(name)
         worst = predicted = None
         for label, (acq, mx, best, ref) in _refs(name).items():
@@ -136,6 +138,43 @@ def test_case_inputs_satisfy_the_conditions_of_the_device_test(name):
     assert len(A.cases(lin)) == 16
     assert A.check_conditions(name, st, lin) == []
     assert len(st.redrawn) <= 8 and not set(st.redrawn) & set(A.FIXED_QUERIES)
+
+
+@pytest.mark.parametrize("name", A.HIGH_K_STATES)
+def test_high_k_stress_states_see_their_training_points(name, capsys):
+    """Why the two high-k states carry a lengthscale of their own: the median |v|^2 over the queries is at least 0.01,
+    so the gradient parts through R (w = R^T v, B_c) stand above rounding and a wrong one leaves the unit.  At the
+    default ln 2 it is 2e-3 or less."""
+    st, _, lin = A.prepared(name)
+    vv = A.f64(lin.vv)
+    with capsys.disabled():
+        print("\n[state %s (n=%d k=%d), lengthscale %g] |v|^2 median %.3g, range %.3g .. %.3g"
+              % (name, st.n, st.k, st.lengthscale, np.median(vv), vv.min(), vv.max()))
+    assert st.lengthscale > A.LENGTHSCALE and np.median(vv) >= 0.01
+
+
+def test_stress_states_reach_the_forms_their_comments_name():
+    """The arithmetic of the comments beside the stress states, from the constants of the library's sources as the
+    comments quote them: ACQ_SLAB32_NP = 448, PCABO_QA_MAX = 416, k_acq_group up to NP = 1280 with ceil(NP / 256)
+    columns per thread and launch_acq_group's LDS formula (GQ = 5, GT_LD = 17)."""
+    shape = {name: (64 * -(-A.STATES[name][0] // 64), A.STATES[name][1]) for name in A.STRESS_STATES}
+    assert shape == {"n385k65": (448, 65), "n449k83": (512, 83), "n1025": (1088, 5), "n1473": (1536, 2)}
+    assert set(A.STRESS_STATES) <= set(A.STATES) and set(A.STRESS_STATES) <= set(A.POSTERIOR_STATES)
+
+    def group_lds(NP, k):
+        ke = (k + 1) & ~1
+        return 8 * (5 * max(NP, 2 * ke) + 4 * 64 * 17 + 64 * 8 + 5 * 64 + 2 * 5 + 4 + 2 * 5 + 5 * ke + 8)
+
+    assert [group_lds(512, 83), group_lds(512, 82)] == [65568, 65488] and group_lds(512, 82) <= 65536 < group_lds(512, 83)
+    assert group_lds(448, 65) <= 65536 and -(-448 // 256) == 2 and -(-1088 // 256) == 5 and 1088 <= 1280 < 1536
+    assert len(range(0, 65, 32)) == 3 and len(range(0, 65, 64)) == 2 and len(range(0, 83, 64)) == 2
+    assert [5 * 65, 6 * 65, 5 * 83, 6 * 83] == [325, 390, 415, 498] and 415 <= 416 < 498 and 32 * 65 > 416
+    assert [1088 // 32, 1536 // 32, 1088 // 64, 1536 // 64] == [34, 48, 17, 24] and 34 > 18
+    assert all(first + 24 + 21 < 48 for first in (0, 1, 2)) and not 0 + 24 + 21 < 45     # grad_partial_sum's second trip
+    for name in A.STRESS_STATES:                                       # make_state's own seeds and recipe
+        n, k = A.STATES[name][:2]
+        rng = np.random.default_rng(1000 + 10 * n + k)
+        assert np.array_equal(A.make_state(name).Z, rng.normal(size=(n, k)))
 
 
 def test_states_reach_every_kernel_form_and_reuse_the_ucb_states():

@@ -11,6 +11,15 @@ The reference starts from each object's OWN conditioned state (`gp_state()` of t
 the batch's run), read once after conditioning and taken as exact: the conditioning is judged by `test_gpu_gp_edges.py`,
 and its kappa-type factors stay out of the units here.
 
+Four of the states lie in the stress region of the d = 100 runs (n = 300 .. 1050, k ~ 85; the arithmetic is beside each
+state in `acq_reference.STATES`): n385k65 - `k_acq_fused<32>` with k > 32 (three trips of its gradient contraction, the
+second trip of `acq_tail`'s and `acq_finish_query`'s component loops, the `c != l` side of `acq_tail`'s bounds) and
+`k_acq_group<2>` at k > 40; n449k83 - `k_acq_group<2>` with more than 64 KB of dynamic LDS and 415 of the 416 argument
+coordinates; n1025 - `k_acq_group<5>` with all five columns per thread live, `k_acq_combine` over 34 records, five
+`k_score_ks` blocks and 17 row blocks of `k_score_gemm`; n1473 - the second iteration of `grad_partial_sum`'s unrolled
+loop (48 slabs), six `k_score_ks` blocks, and the group context beyond `acq_group_possible`, whose results must be the
+plain context's bit for bit (GROUP_TWINS).
+
 The entry points and their order are those of `test_gpu_ucb.py`; the incumbents are float64 (`PCABO_OPT_BESTF_F32`
 off, as for a numpy float64 incumbent), because the seam incumbents must put u at -1 and -1e6 to rounding.
 """
@@ -37,6 +46,19 @@ DEEP_MIDDLE = ("mid", "seam-1e6")
 FAMILIES_UNITS = 2.0 * LIMIT           # two results within LIMIT units of the reference are this close to each other
 PATHS = ("q5", "q6", "finish32", "combine40", "fast130", "gemm130", "group5", "group6", "group32", "group40",
          "group130", "groupgemm130", "batch130", "device32")
+
+
+# Beyond `acq_group_possible` (kernels_acq.hip: NP <= 1280 and k <= 128; state n1473 has NP = 1536) a
+# PCABO_OPT_GROUP_ACQ context cannot take k_acq_group: `group_mode` (pcabo_api.hip) is false and `pcabo_acq_eval` goes
+# through `eval_staged`, the plain context's per-query launches, with the same arguments.  Its results are then the plain
+# context's BIT FOR BIT, path by path - a stronger statement than the families rule, which stays for every other state.
+GROUP_TWINS = (("group5", "q5"), ("group6", "q6"), ("group32", "finish32"), ("group40", "combine40"),
+               ("group130", "fast130"), ("groupgemm130", "gemm130"))
+
+
+def group_kernel_possible(n, k):
+    """`acq_group_possible` of kernels_acq.hip at the padded size of n points."""
+    return 64 * -(-n // 64) <= 1280 and k <= 128
 
 
 def _verr(v, ov):
@@ -67,6 +89,8 @@ def test_log_ei_and_pi_against_the_reference_on_every_path(native, name, capsys)
     grp = native.Context(max_n=n, max_d=k, max_q=512)
     grp.set_option(native.OPT_GROUP_ACQ, 1)
     on_device = k <= 40 and n <= 512                                          # the device optimiser's limits
+    group_kernel = group_kernel_possible(n, k)
+    assert group_kernel == (name != "n1473")
     bt = native.Batch(1, max_n=n, max_d=k, max_q=512, device_lbfgsb=1 if on_device else 0)
     try:
         for c in (ctx, grp, bt.ctx[0]):
@@ -86,6 +110,8 @@ def test_log_ei_and_pi_against_the_reference_on_every_path(native, name, capsys)
             assert A.check_conditions(name, st, lins[tag]) == [], (name, tag)      # on the device's own state, not skipped
         lin = lins["ctx"]
         worst, fails = {}, []
+        if not group_kernel:               # the same launches on the same state: the comparison below is bit for bit
+            assert keys["grp"] == keys["ctx"], "two contexts conditioned alike hold different states"
 
         def note(path, label, ref, v, g=None):
             rv, rg = A.judge(ref, v, g)
@@ -102,12 +128,19 @@ def test_log_ei_and_pi_against_the_reference_on_every_path(native, name, capsys)
                 out[path] = ctx.acq_eval(X[:q], best, mx, acq)
                 note(path, label, ref, *out[path])
             ctx.gp_condition(y, wait=False, **cond)
-            note("gemm130", label, ref, ctx.gp_wait_eval(X, best, mx, acq))
+            out["gemm130"] = (ctx.gp_wait_eval(X, best, mx, acq), None)
+            note("gemm130", label, ref, out["gemm130"][0])
             grp.gp_condition(y, wait=False, **cond)
-            note("groupgemm130", label, gref, grp.gp_wait_eval(X, best, mx, acq))
+            out["groupgemm130"] = (grp.gp_wait_eval(X, best, mx, acq), None)
+            note("groupgemm130", label, gref, out["groupgemm130"][0])
             for q, path in ((5, "group5"), (6, "group6"), (32, "group32"), (40, "group40"), (130, "group130")):
                 out[path] = grp.acq_eval(X[:q], best, mx, acq)
                 note(path, label, gref, *out[path])
+            if not group_kernel:           # the group context on the plain context's launches: the same bits
+                for gpath, path in GROUP_TWINS:
+                    for a, b in zip(out[gpath], out[path]):
+                        if a is not None and not np.array_equal(a, b):
+                            fails.append(("the group context beyond k_acq_group differs from the plain one", gpath, label))
             bt.gp_condition_begin(Z[None], y[None], norm_bounds=st.norm_bounds, lengthscale=st.lengthscale,
                                   gp_noise=st.noise, kernel=kcode)
             vb, status = bt.gp_wait_eval([X], [best], mx, acq)

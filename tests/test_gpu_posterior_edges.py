@@ -10,6 +10,11 @@ across two), queries on training points.  The limit is 16 units, as in the other
 compares with a float64 oracle at tolerances measured on the device.
 
 The reference starts from each object's OWN conditioned state (`gp_state()`), read once and taken as exact.
+
+Beside the small states, n257 and n513, the four stress states of `acq_reference.STATES`: n385k65 and n449k83 - the
+second `c0 += 64` trip of `k_post_cov` (k > 64) over 7 and 8 panels of V; n1025 - `k_post_cov` over 17 panels,
+five `k_score_ks` blocks, 17 row blocks of `k_score_gemm` and as many records per query for `k_post_combine`; n1473 -
+24 panels, six blocks, 24 row blocks and records (more than 18).
 """
 import time
 

@@ -9,6 +9,11 @@ these are; `test_gpu_ucb.py` compares the same paths with a float64 oracle at to
 
 The reference starts from each object's OWN conditioned state (`gp_state()`), read once after conditioning and taken
 as exact.  kappa: 0, 0.5, sqrt 2 and 1e3 (the sigma term carries value and gradient), in both directions.
+
+The states are all of `acq_reference.STATES`, the four of the stress region included (n385k65, n449k83, n1025, n1473:
+`k_acq_fused<32>` at k > 32, `k_acq_group<2>` past 64 KB of LDS, `k_acq_group<5>` with five live columns, the second
+iteration of `grad_partial_sum`'s unrolled loop); at n1473 the group context lies beyond `acq_group_possible` and must
+give the plain context's bits (`test_gpu_acq_edges.GROUP_TWINS`).
 """
 import time
 
@@ -16,7 +21,7 @@ import numpy as np
 import pytest
 
 import acq_reference as A
-from test_gpu_acq_edges import FAMILIES_AGREE, PATHS, _rel, _verr
+from test_gpu_acq_edges import FAMILIES_AGREE, GROUP_TWINS, PATHS, _rel, _verr, group_kernel_possible
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +44,7 @@ def test_ucb_against_the_reference_on_every_path(native, name, capsys):
     grp = native.Context(max_n=n, max_d=k, max_q=512)
     grp.set_option(native.OPT_GROUP_ACQ, 1)
     on_device = k <= 40 and n <= 512                                          # the device optimiser's limits
+    group_kernel = group_kernel_possible(n, k)                                # False at n1473: see GROUP_TWINS
     bt = native.Batch(1, max_n=n, max_d=k, max_q=512, device_lbfgsb=1 if on_device else 0)
     U = native.ACQ_UCB
     try:
@@ -57,6 +63,8 @@ def test_ucb_against_the_reference_on_every_path(native, name, capsys):
             keys[tag], lins[tag] = A.cached_linear(st, gs)
             assert A.check_ucb_conditions(name, st, lins[tag]) == [], (name, tag)  # on the device's own state, not skipped
         worst, fails, between_worst = {}, [], 0.0
+        if not group_kernel:               # the same launches on the same state: the comparison below is bit for bit
+            assert keys["grp"] == keys["ctx"], "two contexts conditioned alike hold different states"
         post_mean = ctx.gp_posterior(X)["mean"]
 
         def note(path, label, ref, v, g=None):
@@ -74,12 +82,19 @@ def test_ucb_against_the_reference_on_every_path(native, name, capsys):
                 out[path] = ctx.acq_eval(X[:q], kap, mx, U)
                 note(path, label, ref, *out[path])
             ctx.gp_condition(y, wait=False, **cond)
-            note("gemm130", label, ref, ctx.gp_wait_eval(X, kap, mx, U))
+            gemm = ctx.gp_wait_eval(X, kap, mx, U)
+            note("gemm130", label, ref, gemm)
             grp.gp_condition(y, wait=False, **cond)
-            note("groupgemm130", label, gref, grp.gp_wait_eval(X, kap, mx, U))
+            groupgemm = grp.gp_wait_eval(X, kap, mx, U)
+            note("groupgemm130", label, gref, groupgemm)
             for q, path in ((5, "group5"), (6, "group6"), (32, "group32"), (40, "group40"), (130, "group130")):
                 out[path] = grp.acq_eval(X[:q], kap, mx, U)
                 note(path, label, gref, *out[path])
+            if not group_kernel:           # the group context on the plain context's launches: the same bits
+                twins = [(gp, p, a, b) for gp, p in GROUP_TWINS[:5] for a, b in zip(out[gp], out[p])]
+                for gpath, path, a, b in twins + [GROUP_TWINS[5] + (groupgemm, gemm)]:
+                    if not np.array_equal(a, b):
+                        fails.append(("the group context beyond k_acq_group differs from the plain one", gpath, label))
             bt.gp_condition_begin(Z[None], y[None], **bcond)
             vb, status = bt.gp_wait_eval([X], [kap], mx, U)
             assert not status.any()

@@ -15,7 +15,7 @@ import acq_reference as A
 
 LIMIT = 4.0
 DEVICE_LIMIT = 16.0
-PROVED_UCB = A.SMALL_STATES + ["C"]        # as test_acq_reference_cpu.py: every state with n <= 130, and n = 449
+PROVED_UCB = A.SMALL_STATES + ["C"] + A.STRESS_STATES      # as test_acq_reference_cpu.py: n <= 130, n = 449, the stress states
 PROVED_POSTERIOR = A.POSTERIOR_STATES      # every state of the device test
 _UCB, _POST = {}, {}
 
@@ -94,7 +94,9 @@ def test_units_notice_wrong_posterior_variant(variant, capsys):
     The query-query distance as norms minus a dot product must do so at the covariance of the duplicate pair (3, 4)
     AND at that of a near-coincident pair, nowhere else: away from them the kernel's slope in sq is small and the unit
     of v_a . v_b wide.  It is seen where |xn|^2 / l^2 is large: one rounding of the norms at k = 128 is 28 units there,
-    at k = 41 (state D) one is 7 and below the limit - the norm form IS nearly as good as the direct one at small k."""
+    at k = 41 (state D) one is 7 and below the limit - the norm form IS nearly as good as the direct one at small k.
+    Every other variant that needs no clamped variance is also held on the stress state n385k65; this one is not named
+    there: at lengthscale 2.0 and with the unit of v_a . v_b summed over 385 rows it stays at 0.014 of the unit."""
     kw, flags, states = A.WRONG_POSTERIOR[variant]
     seen, bad = [], []
     for name in states:
@@ -146,6 +148,9 @@ def test_case_inputs_satisfy_the_conditions_of_the_device_tests(name):
 def test_posterior_states_reach_the_forms_the_device_test_names():
     assert set(A.SMALL_STATES) <= set(A.POSTERIOR_STATES)
     assert {"n257", "n513", "D", "k128", "user", "E", "mixed"} <= set(A.POSTERIOR_STATES)
+    assert set(A.STRESS_STATES) <= set(A.POSTERIOR_STATES) and not set(A.STRESS_STATES) & set(A.SMALL_STATES)
+    for variants in (A.WRONG_UCB, A.WRONG_POSTERIOR):                  # the wrong variants are seen in the stress region too
+        assert any("n385k65" in v[-1] for v in variants.values())
     for name, floor in (("E", "all"), ("mixed", "some")):
         st, _, lin = A.prepared(name)
         for noise in (False, True):
