@@ -298,6 +298,23 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
                         const double* bounds, int maxiter, double best_f, int maximize, int acq,
                         double* cand, double* vals, int* info, int* failed);
 
+/* Rows K-N of a single run in ONE call (host pointers only): score the n_raw raw samples - behind the conditioning when one is in
+ * flight (pcabo_gp_condition_end_eval and its call-order rules), on the conditioned model otherwise (pcabo_acq_eval, values only)
+ * -, pick num_restarts < n_raw of them as botorch's initialize_q_batch(eta) does on the generator whose state `blob` is
+ * (pcabo_boltzmann_pick_rows for one row; the blob is ADVANCED in place), and run pcabo_optimize_acqf from them.  The variates of
+ * the pick are drawn while the host would wait for the scores, and the optimiser's stepping helper is woken before that wait
+ * (flags = PCABO_PROPOSE_NO_WAKE leaves it asleep until the optimiser needs it: the A/B switch of that one step).
+ *   raw[n_raw*k], bounds[2*k] [host]; raw_vals[n_raw], ic_idx[num_restarts], ics[num_restarts*k] [host] out;
+ *   cand, vals, info, failed as pcabo_optimize_acqf; phase_seconds[3] [host] or NULL: wait + score, pick, optimise (steady_clock).
+ *   *picked = 1: everything was written.  *picked = 0: flag 1 of pcabo_boltzmann_pick_rows (no spread, or tied ratios) - raw_vals is written, the
+ *   blob is byte for byte what it was, nothing was optimised: the caller takes botorch's other paths and calls pcabo_optimize_acqf.
+ * PCABO_ACQ_PI, whose pick is botorch's non-negative variant, is refused.  Same bits as the separate calls. */
+enum { PCABO_PROPOSE_NO_WAKE = 1 };
+int pcabo_propose_acqf(pcabo_ctx* ctx, const double* raw, int n_raw, void* blob, double eta, int num_restarts, int batch_limit,
+                       const double* bounds, int maxiter, double best_f, int maximize, int acq, int flags, double* raw_vals,
+                       int64_t* ic_idx, double* ics, double* cand, double* vals, int* info, int* failed, int* picked,
+                       double* phase_seconds);
+
 /* Row O: x = z Ck + pca_mean + data_mean (PCA_BO.py:410-434). z[k] [host] -> x[d] [host]. */
 int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x);
 
@@ -345,7 +362,8 @@ int pcabo_sobol_draw_rows(const int64_t* const* states, const int64_t* const* sh
                           const double* boxes, long long box_stride, double* const* outs);
 /* torch's CPU generator restated for the host's pacing thread (csrc/host_entry.cpp): `blob` = the generator's state exactly as
  * torch.Generator.get_state() exports it (5056 bytes), read and ADVANCED in place - set_state(blob) afterwards leaves torch's
- * generator where torch's own call would have left it.
+ * generator where torch's own call would have left it.  Every entry point that takes a blob refuses (PCABO_ERR_ARG) one that is not
+ * seeded or whose `left` / `next` bookkeeping would read past the 624 state words.
  * pcabo_torch_randint2: torch.randint(2, (count,), generator=g) - the Sobol scramble bits of botorch's draw_sobol_samples.
  * pcabo_torch_multinomial_rows: torch.multinomial(weights[r], n_pick, replacement=False, generator=g_r) for `rows` rows, one
  *   generator each (blobs[r] == NULL: row skipped) - the Boltzmann pick of botorch's initialize_q_batch; out[rows][n_pick].
@@ -353,8 +371,9 @@ int pcabo_sobol_draw_rows(const int64_t* const* states, const int64_t* const* sh
 int pcabo_torch_randint2(void* blob, int64_t count, int64_t* out);
 int pcabo_torch_multinomial_rows(void* const* blobs, const double* weights, int rows, int n, int n_pick, int64_t* out);
 /* botorch's initialize_q_batch (Boltzmann pick of the restarts' initial conditions) for `rows` runs in one call: vals[rows][n] raw-sample
- * scores, eta the temperature; out[rows][n_pick]; flags[rows]: 0 picked, 1 all values equal (nothing drawn: the caller takes the
- * random-permutation path), 2 skipped (blobs[r] == NULL). */
+ * scores, eta the temperature; out[rows][n_pick]; flags[rows]: 0 picked; 1 nothing picked here and the row's
+ * generator is as it was - all values equal or a NaN among them, or the largest ratios of the draw tie (weights that overflowed or
+ * underflowed; not at eta = 1): the caller runs torch's own initialize_q_batch on that generator; 2 skipped (blobs[r] == NULL). */
 int pcabo_boltzmann_pick_rows(void* const* blobs, const double* vals, int rows, int n, int n_pick, double eta, int64_t* out, int* flags);
 
 /* Device-time accounting: accumulated HIP-event time (ms, events recorded on the context's own

@@ -112,6 +112,10 @@ class DeviceBayesianOptimizer(AbstractBayesianOptimizer):
         # resident=False: one launch per acquisition evaluation instead of the resident kernel of pcabo_optimize_acqf
         # (PCABO_OPT_RESIDENT; same arithmetic - the tests compare whole runs bit for bit)
         self._resident = bool(kwargs.pop("resident", True))
+        # one_call=False: scoring of the raw samples, initial pick and optimiser stay three calls with torch's pick between them;
+        # True (default; the environment's PCABO_ONE_CALL=0 turns the default off): one native call (pcabo_propose_acqf), which
+        # also ends the conditioning in flight - same arithmetic, same generator stream (the tests compare whole runs)
+        self._one_call = bool(kwargs.pop("one_call", _acqopt.one_call_default()))
         # fantasy_points: room for that many points behind the budget in the run's context, for fantasy() (0: the context holds the
         # budget and fantasy() fits only while n + its points <= budget)
         self._fantasy_points = int(kwargs.pop("fantasy_points", 0))
@@ -214,6 +218,12 @@ class DeviceBayesianOptimizer(AbstractBayesianOptimizer):
         if self.verbose:
             print(self.FINAL_LINE)
         self.restore_random_states()
+
+    def _scores_in_one_call(self, acq) -> bool:
+        """Does pcabo.acqopt.optimize_acqf score this iteration's raw samples itself (its one native call, which also ends a
+        conditioning in flight)?  Then the optimiser hands it `raw` alone."""
+        cfg = self._torch_config
+        return self._one_call and _acqopt.one_call_applies(self._ctx, acq.acq_code, cfg["NUM_RESTARTS"], cfg["RAW_SAMPLES"])
 
     def _q_eff(self) -> int:
         """Candidates of the current iteration: q, or what the budget leaves."""

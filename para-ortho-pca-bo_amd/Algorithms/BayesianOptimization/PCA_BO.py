@@ -297,7 +297,10 @@ class PCA_BO(DeviceBayesianOptimizer):
         raw = _init.draw_sobol(bounds, raw_samples, engine)
         self.phase_breakdown["sobol"] = self.phase_breakdown.get("sobol", 0.0) + perf_counter() - t0
         raw_vals = None
-        if self.__gp_pending and self.__early_scoring:
+        one_call = self._scores_in_one_call(acq)
+        if self.__gp_pending and self.__early_scoring and one_call:
+            self.__gp_pending = False      # the optimiser's one call waits for the conditioning, scores and picks
+        elif self.__gp_pending and self.__early_scoring:
             # the raw samples are scored right behind the conditioning on the stream: one wait for both
             t0 = perf_counter()
             raw_vals = ctx.gp_wait_eval(raw, acq.device_scalar, acq.maximize, acq.acq_code)
@@ -310,9 +313,11 @@ class PCA_BO(DeviceBayesianOptimizer):
             ctx, bounds, acq.device_scalar, acq.maximize, acq.acq_code, num_restarts, raw_samples, batch_limit, 200,
             q_eff=self._q_eff(), strategy=self._q_strategy, f_evals=self.f_evals,
             raw=raw, raw_vals=raw_vals, breakdown=self.phase_breakdown,
-            trace=self.trace[-1] if self._record_trace else None,
-            before_lbfgsb=self._prefetch_noise)   # the draw overlaps with the optimiser's time inside the library; started
-        # any earlier it shares the core with the torch ops of the initial pick and doubles their time (0.10 -> 0.21 ms)
+            trace=self.trace[-1] if self._record_trace else None, one_call=one_call,
+            before_lbfgsb=self._prefetch_noise)   # the draw overlaps with the time inside the library.  With the one call it
+        # starts just before that call: scoring, pick and optimiser are native and hold no torch op it could crowd.  With the
+        # three calls it starts after the initial pick: any earlier it shares the core with the pick's torch ops and doubles
+        # their time (0.10 -> 0.21 ms)
         self.timing_logs["optimize_acqf"].append(perf_counter() - start)
         self.lbfgsb_info.extend(infos)
         return new_z

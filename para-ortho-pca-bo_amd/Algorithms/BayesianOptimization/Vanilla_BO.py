@@ -62,14 +62,15 @@ class Vanilla_BO(DeviceBayesianOptimizer):
         engine = _init.scrambled_sobol_engine(self.dimension)      # built and drawn while the device conditions the GP
         raw = _init.draw_sobol(self.__box, cfg["RAW_SAMPLES"], engine)
         raw_vals = None                    # (fit_gp: the GP is conditioned already, the optimiser scores the raw samples)
-        if not self._fit_gp:
+        one_call = self._scores_in_one_call(acq)   # (then the optimiser's one call waits for the conditioning and scores)
+        if not self._fit_gp and not one_call:
             t0 = perf_counter()            # the raw samples are scored right behind the conditioning: one wait for both
             raw_vals = ctx.gp_wait_eval(raw, acq.device_scalar, acq.maximize, acq.acq_code)
             self.phase_breakdown["raw_eval"] = self.phase_breakdown.get("raw_eval", 0.0) + perf_counter() - t0
         new_x, infos = _acqopt.propose(
             ctx, self.__box, acq.device_scalar, acq.maximize, acq.acq_code, cfg["NUM_RESTARTS"], cfg["RAW_SAMPLES"], 5, 200,
             q_eff=self._q_eff(), strategy=self._q_strategy, f_evals=self.f_evals, raw=raw, raw_vals=raw_vals, breakdown=self.phase_breakdown,
-            trace=self.trace[-1] if self._record_trace else None)
+            trace=self.trace[-1] if self._record_trace else None, one_call=one_call)
         self.timing_logs["optimize_acqf"].append(perf_counter() - start)
         self.lbfgsb_info.extend(infos)
         return new_x

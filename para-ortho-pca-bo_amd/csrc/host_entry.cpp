@@ -3,6 +3,7 @@
 // botorch's gen_batch_initial_conditions behind /root/reference/Algorithms/BayesianOptimization/PCA_BO.py:607-614).
 // Built by g++ into libpcabo.so and, with -fsanitize=..., into the host-only checker libraries of the Makefile.
 #include "../../include/pcabo.h"
+#include "host_side.h"
 #include "lbfgsb.h"
 
 #include <algorithm>
@@ -186,13 +187,19 @@ __attribute__((optimize("O3"))) inline void mt_temper_bits(const uint64_t* w, in
     out[i] = (int64_t)(y & 1u);
   }
 }
+// The one rule for a state blob of every entry point that draws from it: a seeded generator whose bookkeeping cannot read past
+// state[623] - `left` in [1, 624], and either the next draw refills the state (left == 1) or the left - 1 words still to be
+// served from `next` on lie inside it (`next` is bounded by itself first: it is the caller's 64 bits, and a sum can wrap).
+inline bool mt_blob_ok(const TorchMt* s) {
+  return s->seeded && s->left >= 1 && s->left <= 624 && (s->left == 1 || (s->next <= 624 && s->next + (uint64_t)s->left <= 625));
+}
 }  // namespace
 
 // torch.randint(2, (count,), generator=g): one 32-bit draw per element, value = draw % 2 (int64 out).
 int pcabo_torch_randint2(void* blob, int64_t count, int64_t* out) {
   if (!blob || !out || count < 0) return PCABO_ERR_ARG;
   TorchMt* s = static_cast<TorchMt*>(blob);
-  if (!s->seeded || s->left < 1 || s->left > 624 || s->next > 624) return PCABO_ERR_ARG;
+  if (!mt_blob_ok(s)) return PCABO_ERR_ARG;
   // whole runs of state words at a time (the tempering of a run is a loop without dependencies: the compiler vectorises it);
   // the bookkeeping is mt_draw's: a fresh state serves N draws, `left` stays N after the first of them
   while (count > 0) {
@@ -216,15 +223,19 @@ int pcabo_torch_randint2(void* blob, int64_t count, int64_t* out) {
 }
 
 namespace {
-// the n_pick largest of w_i / q_i, largest first (torch's topk on the ratios), q_i an Exp(1) variate drawn as torch's exponential_ does
-void multinomial_row(TorchMt* s, const double* w, int n, int n_pick, double* ratio, int* best, int64_t* out) {
+// The Exp(1) variates of one multinomial draw over n weights, as torch's exponential_ forms them: two draws per element, in index
+// order, before any weight is looked at.
+void draw_variates(TorchMt* s, int n, double* q) {
   for (int i = 0; i < n; ++i) {
     const uint64_t hi = mt_draw(s), lo = mt_draw(s);
     const uint64_t r64 = (hi << 32) | lo;
     const double u = (double)(r64 & ((1ull << 53) - 1)) * 1.1102230246251565e-16;      // 2^-53
-    const double q = -std::log1p(-u);
-    ratio[i] = w[i] / q;
+    q[i] = -std::log1p(-u);
   }
+}
+// the n_pick largest of w_i / q_i, largest first (torch's topk on the ratios), into best[n_pick] and, if given, out; ratio[n] is scratch
+void top_ratios(const double* w, const double* q, int n, int n_pick, double* ratio, int* best, int64_t* out) {
+  for (int i = 0; i < n; ++i) ratio[i] = w[i] / q[i];
   int have = 0;                        // (n_pick is 10 of 512: selection by insertion)
   for (int i = 0; i < n; ++i) {
     const double v = ratio[i];
@@ -234,9 +245,69 @@ void multinomial_row(TorchMt* s, const double* w, int n, int n_pick, double* rat
     best[pos] = i;
     if (have < n_pick) ++have;
   }
+  if (out) for (int j = 0; j < n_pick; ++j) out[j] = best[j];
+}
+// What of botorch's initialize_q_batch stands behind the scores, given the variates of the row's multinomial draw: z = (v - mean) /
+// std (unbiased, Welford), weights exp(eta z) (halved exponents while one overflows), the n_pick largest w_i / q_i, the arg-max
+// forced into the last place if it was not drawn.  *flag = 0 picked; 1 nothing is picked here - the std is not positive (equal
+// values, or a NaN), or ratios tie where the order matters -: torch's own path decides, out is
+// left alone, and a caller that drew the variates ahead puts its generator back.  w[n], ratio[n] and best[n_pick] are scratch.
+void pick_from_variates(const double* v, const double* q, int n, int n_pick, double eta, double* w, double* ratio, int* best,
+                        int64_t* out, int* flag) {
+  double mean = 0.0, m2 = 0.0;
+  int arg = 0;
+  for (int i = 0; i < n; ++i) {
+    const double d = v[i] - mean;
+    mean += d / (double)(i + 1);
+    m2 += d * (v[i] - mean);
+    if (v[i] > v[arg]) arg = i;
+  }
+  const double sd = std::sqrt(m2 / (double)(n - 1));
+  if (!(sd > 0.0)) { *flag = 1; return; }
+  double scale = eta;
+  for (;;) {
+    bool inf = false;
+    for (int i = 0; i < n; ++i) { w[i] = std::exp(scale * ((v[i] - mean) / sd)); inf = inf || std::isinf(w[i]); }
+    if (!inf) break;
+    scale *= 0.5;
+  }
+  top_ratios(w, q, n, n_pick, ratio, best, nullptr);
+  // Equal ratios among the picks, or at their lower edge (weights near the largest double over a small variate give several
+  // inf; weights that underflowed give several 0): the order torch's topk leaves them in is its own.  Nothing is picked here.
+  for (int j = 0; j + 1 < n_pick; ++j)
+    if (ratio[best[j]] == ratio[best[j + 1]]) { *flag = 1; return; }
+  int at_edge = 0;
+  for (int i = 0; i < n; ++i) at_edge += ratio[i] == ratio[best[n_pick - 1]];
+  if (at_edge > 1) { *flag = 1; return; }
   for (int j = 0; j < n_pick; ++j) out[j] = best[j];
+  bool has = false;
+  for (int j = 0; j < n_pick; ++j) has = has || out[j] == arg;
+  if (!has) out[n_pick - 1] = arg;
+  *flag = 0;
 }
 }  // namespace
+
+}  // extern "C"
+
+// The pick with its variates drawn ahead (declared in host_side.h).  What a draw can change of a blob is the twister's part of it
+// (TorchMt): that much is kept and put back.
+bool torch_blob_ok(const void* blob) { return blob && mt_blob_ok(static_cast<const TorchMt*>(blob)); }
+AheadPick::AheadPick(int n_, int n_pick_)
+    : n(n_), n_pick(n_pick_), before(sizeof(TorchMt)), q((size_t)n_), w((size_t)n_), ratio((size_t)n_), best((size_t)n_pick_) {}
+void AheadPick::draw(void* blob_) {
+  blob = blob_;
+  memcpy(before.data(), blob, sizeof(TorchMt));
+  draw_variates(static_cast<TorchMt*>(blob), n, q.data());
+}
+void AheadPick::put_back() { if (blob) memcpy(blob, before.data(), sizeof(TorchMt)); }
+int AheadPick::pick(const double* vals, double eta, int64_t* out) {
+  int flag = 1;
+  pick_from_variates(vals, q.data(), n, n_pick, eta, w.data(), ratio.data(), best.data(), out, &flag);
+  if (flag == 1) put_back();               // (a row without spread draws nothing: its generator goes back as it was)
+  return flag;
+}
+
+extern "C" {
 
 // botorch's initialize_q_batch for `rows` runs at once (behind PCA_BO.py:607-614): per row z = (v - mean) / std (unbiased), weights
 // exp(eta z) (halved exponents while one overflows), torch.multinomial(weights, n_pick) on the row's generator, the arg-max forced
@@ -247,35 +318,11 @@ void multinomial_row(TorchMt* s, const double* w, int n, int n_pick, double* rat
 namespace {
 // rows [r0, r1) of pcabo_boltzmann_pick_rows
 void boltzmann_rows(void* const* blobs, const double* vals, int r0, int r1, int n, int n_pick, double eta, int64_t* out, int* flags) {
-  std::vector<double> w((size_t)n), ratio((size_t)n);
-  std::vector<int> best((size_t)n_pick);
+  AheadPick ahead(n, n_pick);
   for (int r = r0; r < r1; ++r) {
-    TorchMt* s = static_cast<TorchMt*>(blobs[r]);
-    if (!s) { flags[r] = 2; continue; }
-    const double* v = vals + (size_t)r * n;
-    double mean = 0.0, m2 = 0.0;
-    int arg = 0;
-    for (int i = 0; i < n; ++i) {
-      const double d = v[i] - mean;
-      mean += d / (double)(i + 1);
-      m2 += d * (v[i] - mean);
-      if (v[i] > v[arg]) arg = i;
-    }
-    const double sd = std::sqrt(m2 / (double)(n - 1));
-    if (!(sd > 0.0)) { flags[r] = 1; continue; }
-    double scale = eta;
-    for (;;) {
-      bool inf = false;
-      for (int i = 0; i < n; ++i) { w[i] = std::exp(scale * ((v[i] - mean) / sd)); inf = inf || std::isinf(w[i]); }
-      if (!inf) break;
-      scale *= 0.5;
-    }
-    int64_t* o = out + (size_t)r * n_pick;
-    multinomial_row(s, w.data(), n, n_pick, ratio.data(), best.data(), o);
-    bool has = false;
-    for (int j = 0; j < n_pick; ++j) has = has || o[j] == arg;
-    if (!has) o[n_pick - 1] = arg;
-    flags[r] = 0;
+    if (!blobs[r]) { flags[r] = 2; continue; }
+    ahead.draw(blobs[r]);
+    flags[r] = ahead.pick(vals + (size_t)r * n, eta, out + (size_t)r * n_pick);
   }
 }
 }  // namespace
@@ -284,9 +331,25 @@ int pcabo_boltzmann_pick_rows(void* const* blobs, const double* vals, int rows, 
   if (!blobs || !vals || !out || !flags || rows < 1 || n < 2 || n_pick < 1 || n_pick > n) return PCABO_ERR_ARG;
   for (int r = 0; r < rows; ++r) {
     const TorchMt* s = static_cast<const TorchMt*>(blobs[r]);
-    if (s && (!s->seeded || s->left < 1 || s->left > 624 || s->next > 624)) return PCABO_ERR_ARG;
+    if (s && !mt_blob_ok(s)) return PCABO_ERR_ARG;
   }
   boltzmann_rows(blobs, vals, 0, rows, n, n_pick, eta, out, flags);
+  return PCABO_OK;
+}
+
+// Debug export, not part of the ABI in include/pcabo.h (tests/test_propose_pick_cpu.py): one row picked as pcabo_propose_acqf
+// picks it (AheadPick) - the variates drawn before the scores are handed over, the pick from them, the generator put back when the
+// row has no spread (*flag = 1).  put_back != 0: draw, put back, and draw and pick again - the order of pcabo_propose_acqf when
+// its scoring fails and the caller comes again.
+int pcabo_debug_boltzmann_two_halves(void* blob, const double* vals, int n, int n_pick, double eta, int put_back, int64_t* out, int* flag) {
+  if (!vals || !out || !flag || n < 2 || n_pick < 1 || n_pick > n || !torch_blob_ok(blob)) return PCABO_ERR_ARG;
+  AheadPick ahead(n, n_pick);
+  ahead.draw(blob);
+  if (put_back) {
+    ahead.put_back();
+    ahead.draw(blob);
+  }
+  *flag = ahead.pick(vals, eta, out);
   return PCABO_OK;
 }
 
@@ -295,13 +358,14 @@ int pcabo_boltzmann_pick_rows(void* const* blobs, const double* vals, int rows, 
 // torch's exponential_), picks = the n_pick largest weights[i] / q_i, largest first (torch's topk).  out[rows][n_pick].
 int pcabo_torch_multinomial_rows(void* const* blobs, const double* weights, int rows, int n, int n_pick, int64_t* out) {
   if (!blobs || !weights || !out || rows < 1 || n < 1 || n_pick < 1 || n_pick > n) return PCABO_ERR_ARG;
-  std::vector<double> ratio((size_t)n);
+  std::vector<double> ratio((size_t)n), q((size_t)n);
   std::vector<int> best((size_t)n_pick);
   for (int r = 0; r < rows; ++r) {
     TorchMt* s = static_cast<TorchMt*>(blobs[r]);
     if (!s) continue;
-    if (!s->seeded || s->left < 1 || s->left > 624 || s->next > 624) return PCABO_ERR_ARG;
-    multinomial_row(s, weights + (size_t)r * n, n, n_pick, ratio.data(), best.data(), out + (size_t)r * n_pick);
+    if (!mt_blob_ok(s)) return PCABO_ERR_ARG;
+    draw_variates(s, n, q.data());
+    top_ratios(weights + (size_t)r * n, q.data(), n, n_pick, ratio.data(), best.data(), out + (size_t)r * n_pick);
   }
   return PCABO_OK;
 }

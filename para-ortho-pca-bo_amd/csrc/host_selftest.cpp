@@ -147,6 +147,69 @@ void test_torch_rng() {
   for (int j = 0; j < n_pick; ++j) CHECK(idx[j] >= 0 && idx[j] < n && idx[n_pick + j] == -1 && idx[2 * n_pick + j] >= 0, "multinomial pick %d", j);
   blobs[3].left = 900;
   CHECK(pcabo_torch_randint2(&blobs[3], 4, bits.data()) == PCABO_ERR_ARG, "a broken blob accepted");
+
+  // The pick in two halves (host_side.h) = pcabo_boltzmann_pick_rows: the variates drawn first, the pick from them after; a row
+  // without spread (equal values, a NaN) reports 1 and the caller's copy puts the generator back byte for byte.
+  for (int r : {0, 5, 11, 12}) {
+    std::vector<double> row(vals.begin() + (size_t)r * n, vals.begin() + (size_t)(r + 1) * n);
+    if (r == 12) row[100] = NAN;
+    Blob two = again[r], rows1 = again[r];
+    const Blob before = two;
+    std::vector<int64_t> a(n_pick, -1), b(n_pick, -1);
+    int flag1 = -1;
+    void* p1 = &rows1;
+    CHECK(pcabo_boltzmann_pick_rows(&p1, row.data(), 1, n, n_pick, 1.0, b.data(), &flag1) == PCABO_OK, "pick row %d again", r);
+    CHECK(torch_blob_ok(&two), "blob of row %d refused", r);
+    AheadPick ahead(n, n_pick);
+    ahead.draw(&two);
+    CHECK(memcmp(&two, &before, sizeof(Blob)) != 0, "the draw of row %d left its generator alone", r);
+    ahead.put_back();                                          // the scores never came: as it was, and the same draw again
+    CHECK(memcmp(&two, &before, sizeof(Blob)) == 0, "put_back of row %d", r);
+    ahead.draw(&two);
+    const int flag = ahead.pick(row.data(), 1.0, a.data());
+    CHECK(flag == flag1 && flag == (r == 5 || r == 12 ? 1 : 0), "flag of the two halves on row %d: %d / %d", r, flag, flag1);
+    if (flag == 1) {
+      CHECK(memcmp(&two, &before, sizeof(Blob)) == 0, "the two halves moved the generator of a row without spread (row %d)", r);
+      CHECK(memcmp(&rows1, &before, sizeof(Blob)) == 0, "a row without spread moved its generator (row %d)", r);
+      for (int j = 0; j < n_pick; ++j) CHECK(a[j] == -1, "a row without spread wrote pick %d", j);
+    } else {
+      for (int j = 0; j < n_pick; ++j) CHECK(a[j] == b[j], "row %d pick %d: the two halves differ from the one call", r, j);
+      CHECK(memcmp(&two, &rows1, sizeof(Blob)) == 0, "generator of row %d after the two halves", r);
+    }
+  }
+  // the one blob checker: seeded, left in [1, 624], and left == 1 or next + left <= 625 - at all four doors
+  struct { int left, seeded; uint64_t next; bool ok; } shapes[] = {
+      {1, 1, 0, true}, {1, 1, 9999, true}, {624, 1, 1, true}, {624, 1, 2, false}, {2, 1, 623, true}, {2, 1, 624, false},
+      {0, 1, 0, false}, {625, 1, 0, false}, {300, 0, 10, false}, {300, 1, 325, true}, {300, 1, 326, false},
+      {300, 1, ~0ull - 298, false} /* next + left wraps to 1 */, {2, 1, ~0ull, false}, {624, 1, ~0ull - 622, false}, {1, 1, ~0ull, true}};
+  for (const auto& sh : shapes) {
+    Blob t = again[1];
+    t.left = sh.left; t.seeded = sh.seeded; t.next = sh.next;
+    void* pt = &t;
+    int fl = -1;
+    CHECK(torch_blob_ok(&t) == sh.ok, "checker on left %d next %llu", sh.left, (unsigned long long)sh.next);
+    if (sh.ok) continue;                 // (an accepted shape is drawn from in the cases above)
+    CHECK(pcabo_torch_randint2(&t, 4, bits.data()) == PCABO_ERR_ARG, "randint2 took left %d next %llu", sh.left, (unsigned long long)sh.next);
+    CHECK(pcabo_boltzmann_pick_rows(&pt, vals.data(), 1, n, n_pick, 1.0, out1.data(), &fl) == PCABO_ERR_ARG, "pick rows took left %d", sh.left);
+    CHECK(pcabo_torch_multinomial_rows(&pt, w.data(), 1, n, n_pick, idx.data()) == PCABO_ERR_ARG, "multinomial rows took left %d", sh.left);
+  }
+  CHECK(!torch_blob_ok(nullptr), "a null blob accepted");
+}
+
+// OptHelper::wake / OptCrew::Awake: the helper spins ahead of a call, runs nothing until the call posts, and goes back to sleep
+// with or without a call in between.
+void test_helper_wake() {
+  OptCrew crew;
+  { OptCrew::Awake a(crew); }                                  // no call follows
+  for (int rep = 0; rep < 3; ++rep) {
+    OptCrew::Awake a(crew);
+    std::atomic<int> ran{0};
+    crew.helper.begin([&] { ran.fetch_add(1); });              // what CrewCall's constructor does
+    CHECK(ran.load() == 0, "the helper ran before it was asked");
+    for (int i = 1; i <= 5; ++i) { crew.helper.wait(crew.helper.post()); CHECK(ran.load() == i, "round %d ran %d times", i, ran.load()); }
+    crew.helper.end();
+  }
+  crew.shutdown();
 }
 
 // pcabo_sobol_draw_rows: ragged k, a skipped run, the boxes in pcabo_batch_acq_bounds' packing - equal to the per-run calls
@@ -1286,6 +1349,7 @@ int main(int argc, char** argv) {
   test_sobol();
   test_sobol_rows();
   test_torch_rng();
+  test_helper_wake();
   test_plan();
   test_restart_group();
   test_crew();

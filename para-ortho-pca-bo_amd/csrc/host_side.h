@@ -24,6 +24,28 @@
 #include <utility>
 #include <vector>
 
+// botorch's initialize_q_batch on a state blob of torch's CPU generator, in two halves (host_entry.cpp): the n Exp(1) variates of
+// the multinomial draw need no score and are drawn while the device still works; the pick from them follows the scores.  The one
+// spelling of the sequence - a copy of the generator, the draw, the pick, the copy put back when nothing was picked - for
+// pcabo_boltzmann_pick_rows (the two halves in a row, per row), pcabo_propose_acqf and the debug export the CPU test calls.
+constexpr size_t TORCH_BLOB_BYTES = 5056;            // torch.Generator.get_state() of the CPU generator
+bool torch_blob_ok(const void* blob);                // seeded, and its bookkeeping cannot read past the state words
+struct AheadPick {
+  AheadPick(int n, int n_pick);
+  void draw(void* blob);                             // keeps what of the blob a draw can change, then draws the n variates from it
+  // 0: out[n_pick] picked; 1: nothing is picked here - the std of vals[n] is not positive (equal values, or a NaN), or the largest
+  // ratios tie (overflowed or underflowed weights) and their order would be torch's topk's own -: out is left alone and the blob
+  // is, byte for byte, what draw() found; the caller takes torch's path
+  int pick(const double* vals, double eta, int64_t* out);
+  void put_back();                                   // the blob as draw() found it (the scores never came)
+ private:
+  int n, n_pick;
+  void* blob = nullptr;
+  std::vector<unsigned char> before;
+  std::vector<double> q, w, ratio;
+  std::vector<int> best;
+};
+
 // One restart group of one run: the joint L-BFGS-B problem of restarts q0 .. q0 + nq - 1 (nq k variables) on the negated
 // acquisition, and botorch's end of it (the values at the clamped end points).
 struct RestartGroup : LbfgsbDriver {
@@ -167,6 +189,10 @@ struct OptHelper {
     cv.notify_one();
   }
   void end() { active.store(false, std::memory_order_release); }
+  // Leave the condition variable now and spin, before the call that will need the helper is there: `go` has not moved, so
+  // nothing runs until a later begin() has given it its work and post() has asked for it.  Only while the helper is idle.  Followed
+  // by begin() + end() of a call, or by end() alone when no call came.
+  void wake() { if (!active.load(std::memory_order_acquire)) begin([] {}); }
   void shutdown() {
     if (!th.joinable()) return;
     { std::lock_guard<std::mutex> lk(mu); quit.store(true, std::memory_order_release); active.store(false, std::memory_order_release); }
@@ -186,6 +212,14 @@ struct OptHelper {
 struct OptCrew {
   OptHelper helper;
   std::vector<std::unique_ptr<OptHelper>> more;
+  // The first helper spins from here until the guard goes (OptHelper::wake): its wake-up latency then lies beside the wait that
+  // precedes an optimise call, not in front of the call's first round.  A CrewCall inside the guard's life takes the helper over.
+  struct Awake {
+    OptHelper& h;
+    explicit Awake(OptCrew& c) : h(c.helper) { h.wake(); }
+    Awake(const Awake&) = delete;
+    ~Awake() { h.end(); }
+  };
   void shutdown() {
     helper.shutdown();
     for (auto& h : more) h->shutdown();

@@ -90,6 +90,7 @@ struct pcabo_ctx {
   int srv_penalty = 0;                   // > 0: the next calls use plain launches (the GPU looked shared, see ResidentSession)
   unsigned long long seq = 0;
   OptCrew crew;                          // the helper threads of pcabo_optimize_acqf (host_side.h)
+  double first_advance_s = 0.0;          // the last optimise call's first advance_all, host seconds (pcabo_debug_first_advance_seconds)
   bool registered = false;
   bool alone = true; int alone_age = 0;   // cached answer of presence_alone(), refreshed every few calls
   char err[512] = {0};
@@ -969,9 +970,17 @@ static int acq_published(pcabo_ctx* ctx, FlagWait w) {
   return PCABO_OK;
 }
 
+// Host work that needs no result of the device: done once, where everything of an evaluation is enqueued and its wait has not
+// begun (pcabo_propose_acqf draws the variates of its pick there).  An evaluation that is repeated does not repeat it.
+struct HostWork {
+  std::function<void()> fn;
+  void run() { if (fn) { fn(); fn = nullptr; } }
+};
+static void run_beside(HostWork* w) { if (w) w->run(); }
+
 // One evaluation of the acquisition at the nq points staged in ctx->hXq (pinned): a single fused launch
 // whose results land in ctx->hVal / ctx->hGrad; the host spins on the sequence flag.
-static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = true) {
+static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = true, HostWork* beside = nullptr) {
   hipStream_t s = ctx->stream;
   const int k = ctx->st.k;
   const unsigned long long seq = ++ctx->seq;
@@ -1000,19 +1009,22 @@ static int eval_staged(pcabo_ctx* ctx, int nq, AcqParams& p, bool allow_gemm = t
   if (!small) {
     HIPCHK(hipMemcpyAsync(ctx->hVal, ctx->dVal, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, s));
     if (p.want_grad) HIPCHK(hipMemcpyAsync(ctx->hGrad, ctx->dGrad, (size_t)nq * k * sizeof(double), hipMemcpyDeviceToHost, s));
+    run_beside(beside);
     HIPCHK(wait_stream(s));
     HIPCHK(hipGetLastError());
     return PCABO_OK;
   }
+  run_beside(beside);
   return acq_published(ctx, wait_flags(ctx->hm, 0, nq, seq, deadline_in(20), &s));
 }
 
 // The part of the GEMM scoring that needs alpha and R, for nq samples whose kernel vectors are in ctx->dKS: the mu_s sums, V = R KS^T,
 // the scalar chain per sample, the values' copy and the wait (eval_staged's GEMM branch without its first kernel's KS half).
-static int score_tail(pcabo_ctx* ctx, int nq, AcqParams& p) {
+static int score_tail(pcabo_ctx* ctx, int nq, AcqParams& p, HostWork* beside = nullptr) {
   hipStream_t s = ctx->stream;
   launch_score_tail(s, nq, gp_model(ctx), p, ctx->dKS, ctx->dPartial, ctx->dVal);
   HIPCHK(hipMemcpyAsync(ctx->hVal, ctx->dVal, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, s));
+  run_beside(beside);
   HIPCHK(wait_stream(s));
   HIPCHK(hipGetLastError());
   return PCABO_OK;
@@ -1049,6 +1061,15 @@ static bool group_mode(const pcabo_ctx* ctx, int q, int want_grad) {
   return ctx->opt_group_acq && want_grad && q <= PCABO_INLAUNCH_MAXQ && acq_group_possible(ctx->st.NP, ctx->st.k);
 }
 
+// The values of the acquisition at the q host points Xq on the conditioned model, into ctx->hVal: pcabo_acq_eval without a gradient
+// on host pointers, behind its checks.
+static int values_staged(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq, HostWork* beside = nullptr) {
+  HIPCHK(hipSetDevice(ctx->device));
+  memcpy(ctx->hXq, Xq, (size_t)q * ctx->st.k * sizeof(double));
+  AcqParams p = make_params(ctx, best_f, maximize, acq, 0);
+  return eval_staged(ctx, q, p, true, beside);
+}
+
 int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq, double* val,
                    double* grad) {
   if (!ctx) return PCABO_ERR_ARG;
@@ -1056,6 +1077,11 @@ int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int m
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: bad argument or q beyond context capacity%s", "");
   if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: %s", why);
   if (!ctx->st.conditioned()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_acq_eval: call pcabo_gp_condition first%s", "");
+  if (!grad && ctx->ptr_mode == PCABO_PTR_HOST) {
+    const int rc = values_staged(ctx, Xq, q, best_f, maximize, acq);
+    if (rc == PCABO_OK) memcpy(val, ctx->hVal, (size_t)q * sizeof(double));
+    return rc;
+  }
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int k = ctx->st.k;
@@ -1091,18 +1117,13 @@ int pcabo_acq_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int m
 // samples of the initial-condition draw are known before the factorisation has finished, so their copy and launches
 // need not wait for the host to see it end.  If the factorisation turns out to have needed jitter, the values are
 // computed again after the retries.
-int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq,
-                                double* val) {
-  if (!ctx) return PCABO_ERR_ARG;
-  if (!Xq || !val || q < 1 || q > ctx->max_q)
-    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: bad argument or q beyond context capacity%s", "");
-  if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: %s", why);
-  if (!ctx->st.in_flight()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: no conditioning in flight%s", "");
+// ... behind its checks, on host pointers: the values land in ctx->hVal and the conditioning is over.
+static int end_eval_staged(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq, HostWork* beside = nullptr) {
   if (const int rc = collect_pending_wpca(ctx)) return rc;
-  if (q <= PCABO_INLAUNCH_MAXQ || ctx->ptr_mode != PCABO_PTR_HOST) {      // nothing to gain: the two calls in a row
-    int rc = pcabo_gp_condition_end(ctx);
-    if (rc != PCABO_OK) return rc;
-    return pcabo_acq_eval(ctx, Xq, q, best_f, maximize, acq, val, nullptr);
+  if (q <= PCABO_INLAUNCH_MAXQ) {                    // nothing to gain: the two calls in a row
+    run_beside(beside);
+    const int rc = pcabo_gp_condition_end(ctx);
+    return rc != PCABO_OK ? rc : values_staged(ctx, Xq, q, best_f, maximize, acq);
   }
   HIPCHK(hipSetDevice(ctx->device));
   memcpy(ctx->hXq, Xq, (size_t)q * ctx->st.k * sizeof(double));
@@ -1117,9 +1138,9 @@ int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double 
     launch_score_ks_only(ctx->stream2, ctx->dXq, q, gp_model(ctx), p, ctx->dKS);
     HIPCHK(hipEventRecord(ctx->evKS, ctx->stream2));
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evKS, 0));
-    rc = score_tail(ctx, q, p);
+    rc = score_tail(ctx, q, p, beside);
   } else {
-    rc = eval_staged(ctx, q, p);                    // ends with a stream synchronisation: the conditioning is over too
+    rc = eval_staged(ctx, q, p, true, beside);      // ends with a stream synchronisation: the conditioning is over too
   }
   if (rc != PCABO_OK) { ctx->st.condition_failed(); return rc; }
   if (ctx->hm->chol_info != 0) {                    // rare: jitter retries, then the evaluation again
@@ -1131,8 +1152,25 @@ int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double 
   } else {
     ctx->st.condition_ended_ok(0.0);                // (the factorisation as enqueued: no jitter)
   }
-  memcpy(val, ctx->hVal, (size_t)q * sizeof(double));
   return PCABO_OK;
+}
+
+int pcabo_gp_condition_end_eval(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, int acq,
+                                double* val) {
+  if (!ctx) return PCABO_ERR_ARG;
+  if (!Xq || !val || q < 1 || q > ctx->max_q)
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: bad argument or q beyond context capacity%s", "");
+  if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: %s", why);
+  if (!ctx->st.in_flight()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_gp_condition_end_eval: no conditioning in flight%s", "");
+  if (ctx->ptr_mode != PCABO_PTR_HOST) {             // nothing to gain: the two calls in a row
+    if (const int rc = collect_pending_wpca(ctx)) return rc;
+    int rc = pcabo_gp_condition_end(ctx);
+    if (rc != PCABO_OK) return rc;
+    return pcabo_acq_eval(ctx, Xq, q, best_f, maximize, acq, val, nullptr);
+  }
+  const int rc = end_eval_staged(ctx, Xq, q, best_f, maximize, acq);
+  if (rc == PCABO_OK) memcpy(val, ctx->hVal, (size_t)q * sizeof(double));
+  return rc;
 }
 
 int pcabo_logei(pcabo_ctx* ctx, const double* Xq, int q, double best_f, int maximize, double* val, double* grad) {
@@ -1237,6 +1275,9 @@ struct ResidentSession {
 // (pack_active) and the results land in pinned host memory.  A round is evaluated by the call's resident kernel when it has one
 // (two groups: free of each other from there on, free_pair), else by one launch: of k_acq_group per restart group
 // (PCABO_OPT_GROUP_ACQ) or of the per-query kernels (eval_staged above).
+static int optimize_checked(pcabo_ctx* ctx, const double* ics, int num_restarts, int batch_limit, const double* bounds, int maxiter,
+                            double best_f, int maximize, int acq, double* cand, double* vals, int* info, int* failed);
+
 int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int batch_limit, const double* bounds,
                         int maxiter, double best_f, int maximize, int acq, double* cand, double* vals, int* info,
                         int* failed) {
@@ -1245,6 +1286,12 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
     return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: bad argument%s", "");
   if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: %s", why);
   if (!ctx->st.conditioned()) return set_err(ctx, PCABO_ERR_ARG, "pcabo_optimize_acqf: call pcabo_gp_condition first%s", "");
+  return optimize_checked(ctx, ics, num_restarts, batch_limit, bounds, maxiter, best_f, maximize, acq, cand, vals, info, failed);
+}
+
+// ... behind its checks (pcabo_propose_acqf comes here with the initial conditions it picked itself)
+static int optimize_checked(pcabo_ctx* ctx, const double* ics, int num_restarts, int batch_limit, const double* bounds, int maxiter,
+                            double best_f, int maximize, int acq, double* cand, double* vals, int* info, int* failed) {
   HIPCHK(hipSetDevice(ctx->device));
   const int k = ctx->st.k;
   RunRestarts run;
@@ -1258,7 +1305,13 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
   CrewCall crew(ctx->crew, run, pending);
   ResidentSession srv{ctx, p};
   for (unsigned round_no = 1;; ++round_no) {
-    crew.advance_all();
+    if (round_no == 1) {                 // (clocked: what stands in front of the first round, the helper's wake-up included)
+      const auto t = std::chrono::steady_clock::now();
+      crew.advance_all();
+      ctx->first_advance_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+    } else {
+      crew.advance_all();
+    }
     const int nq = pack_active(run, qoff);
     if (nq == 0) break;
     int rc;
@@ -1300,6 +1353,72 @@ int pcabo_optimize_acqf(pcabo_ctx* ctx, const double* ics, int num_restarts, int
   if (failed) *failed = any_failed;
   return PCABO_OK;
 }
+
+// Rows K-N of a single run in one call: the raw samples are scored (behind the conditioning, if one is in flight), botorch's
+// initialize_q_batch picks the initial conditions on the caller's generator blob, and the optimiser starts from them.  Between
+// the scores and the optimiser's first round the host does only what needs the scores: the variates of the pick are drawn while
+// it would otherwise wait for the device, and the stepping helper has left its condition variable by then.
+int pcabo_propose_acqf(pcabo_ctx* ctx, const double* raw, int n_raw, void* blob, double eta, int num_restarts, int batch_limit,
+                       const double* bounds, int maxiter, double best_f, int maximize, int acq, int flags, double* raw_vals,
+                       int64_t* ic_idx, double* ics, double* cand, double* vals, int* info, int* failed, int* picked,
+                       double* phase_seconds) {
+  using clk = std::chrono::steady_clock;
+  if (!ctx) return PCABO_ERR_ARG;
+  if (!raw || !raw_vals || n_raw < 1 || n_raw > ctx->max_q)
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_propose_acqf: bad argument or q beyond context capacity%s", "");
+  if (!blob || !ic_idx || !ics || !picked || !bounds || !cand || !vals || num_restarts < 1 || batch_limit < 1 ||
+      num_restarts > ctx->max_q || (flags & ~PCABO_PROPOSE_NO_WAKE))
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_propose_acqf: bad argument%s", "");
+  if (n_raw < 2 || num_restarts >= n_raw)
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_propose_acqf: the pick takes fewer restarts than raw samples, of at least two%s", "");
+  if (const char* why = acq_arg_error(acq, best_f)) return set_err(ctx, PCABO_ERR_ARG, "pcabo_propose_acqf: %s", why);
+  if (acq == PCABO_ACQ_PI)
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_propose_acqf: the pick of PCABO_ACQ_PI (botorch's non-negative variant) is the caller's%s", "");
+  if (!torch_blob_ok(blob))
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_propose_acqf: not a state blob of torch's CPU generator%s", "");
+  if (ctx->ptr_mode != PCABO_PTR_HOST) return set_err(ctx, PCABO_ERR_ARG, "pcabo_propose_acqf: host pointers only%s", "");
+  const bool pending = ctx->st.in_flight();
+  if (!pending && !ctx->st.conditioned())
+    return set_err(ctx, PCABO_ERR_ARG, "pcabo_propose_acqf: call pcabo_gp_condition first%s", "");
+  *picked = 0;
+  const auto t0 = clk::now();
+  const auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
+  double clocks[3] = {0.0, 0.0, 0.0};
+  const auto hand_clocks = [&] { if (phase_seconds) std::copy(clocks, clocks + 3, phase_seconds); };
+  std::unique_ptr<OptCrew::Awake> awake;
+  if (!(flags & PCABO_PROPOSE_NO_WAKE) && num_restarts > batch_limit) awake.reset(new OptCrew::Awake(ctx->crew));
+  // the variates of the pick need no score: drawn where the scoring is enqueued and its wait has not begun
+  AheadPick ahead(n_raw, num_restarts);
+  HostWork draw{[&] { ahead.draw(blob); }};
+  int rc = pending ? end_eval_staged(ctx, raw, n_raw, best_f, maximize, acq, &draw)
+                   : values_staged(ctx, raw, n_raw, best_f, maximize, acq, &draw);
+  if (rc != PCABO_OK) {
+    ahead.put_back();
+    return rc;
+  }
+  draw.run();                                       // (a path that had no place for it)
+  memcpy(raw_vals, ctx->hVal, (size_t)n_raw * sizeof(double));
+  clocks[0] = since(t0);
+  const auto t1 = clk::now();
+  if (ahead.pick(raw_vals, eta, ic_idx) != 0) {     // no spread in the scores (the blob is back): botorch's other paths, in the caller
+    clocks[1] = since(t1);
+    hand_clocks();
+    return PCABO_OK;
+  }
+  const int k = ctx->st.k;
+  for (int j = 0; j < num_restarts; ++j) memcpy(ics + (size_t)j * k, raw + (size_t)ic_idx[j] * k, (size_t)k * sizeof(double));
+  *picked = 1;
+  clocks[1] = since(t1);
+  const auto t2 = clk::now();
+  rc = optimize_checked(ctx, ics, num_restarts, batch_limit, bounds, maxiter, best_f, maximize, acq, cand, vals, info, failed);
+  clocks[2] = since(t2);
+  hand_clocks();
+  return rc;
+}
+
+// Debug export, not part of the ABI in include/pcabo.h (tools/gpu_propose_clock.py): the host time of the first advance_all of the
+// context's last pcabo_optimize_acqf / pcabo_propose_acqf - every group's first L-BFGS-B step, behind the helper's wake-up.
+double pcabo_debug_first_advance_seconds(pcabo_ctx* ctx) { return ctx ? ctx->first_advance_s : -1.0; }
 
 int pcabo_inverse_map(pcabo_ctx* ctx, const double* z, double* x) {
   if (!ctx || !z || !x) return PCABO_ERR_ARG;

@@ -21,6 +21,8 @@ OPT_RESIDENT, OPT_BESTF_F32, OPT_GROUP_ACQ, OPT_DEVICE_LBFGSB = 0, 1, 2, 3
 OPT_HIDDEN_TAIL = 5
 POST_OBS_NOISE = 1                              # gp_posterior: variance / covariance of an observation (likelihood noise added)
 EXTEND_BELIEVER = 1                             # gp_extend: every point takes the model's own mean there (PCABO_EXTEND_BELIEVER)
+PROPOSE_NO_WAKE = 1                             # propose_acqf: the stepping helper sleeps until the optimiser needs it
+TORCH_BLOB_BYTES = 5056                         # torch.get_rng_state(): the CPU generator's state, as propose_acqf takes it
 POST_CENTRED = 2                                # gp_posterior_samples: the mean is not added (the centred process)
 POST_MAX_SAMPLES = 1024                         # gp_posterior_samples: most samples of one call
 FIT_THETA0 = (0.006737946999085467, 0.0, 0.0)   # GP fit: (noise, mean constant, raw lengthscale) of a freshly built model
@@ -58,7 +60,7 @@ EXPORTS = [
     "pcabo_acq_bounds",
     "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_gp_posterior_sample", "pcabo_batch_gp_posterior_sample", "pcabo_gp_loo", "pcabo_batch_gp_loo",
     "pcabo_gp_extend", "pcabo_gp_truncate", "pcabo_gp_extended",
-    "pcabo_batch_gp_extend", "pcabo_batch_gp_truncate", "pcabo_batch_gp_extended", "pcabo_optimize_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
+    "pcabo_batch_gp_extend", "pcabo_batch_gp_truncate", "pcabo_batch_gp_extended", "pcabo_optimize_acqf", "pcabo_propose_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
     "pcabo_get_gram", "pcabo_lbfgsb_minimize", "pcabo_lbfgsb_set_vector_kernels", "pcabo_lbfgsb_set_sum_order", "pcabo_sobol_scramble", "pcabo_sobol_draw", "pcabo_sobol_draw_rows", "pcabo_torch_randint2", "pcabo_torch_multinomial_rows", "pcabo_boltzmann_pick_rows", "pcabo_set_profiling",
     "pcabo_get_profile", "pcabo_get_profile_calibration", "pcabo_reset_profile",
     "pcabo_batch_create", "pcabo_batch_destroy", "pcabo_batch_last_error", "pcabo_batch_ctx",
@@ -134,6 +136,8 @@ def _load() -> C.CDLL:
     lib.pcabo_batch_gp_extended.argtypes = [vp, ip, ip]
     lib.pcabo_optimize_acqf.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                         vp, vp, vp, ip]
+    lib.pcabo_propose_acqf.argtypes = [vp, vp, C.c_int, vp, C.c_double, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int,
+                                       C.c_int, vp, vp, vp, vp, vp, vp, ip, ip, vp]
     lib.pcabo_inverse_map.argtypes = [vp, vp, vp]
     lib.pcabo_get_gp_state.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.pcabo_get_gram.argtypes = [vp, vp]
@@ -559,6 +563,36 @@ class Context:
                                           float(best_f), int(bool(maximize)), int(acq), _ptr(cand), _ptr(vals),
                                           _ptr(info), C.byref(failed)))
         return cand, vals, info, bool(failed.value)
+
+    def propose_acqf(self, raw, blob, num_restarts, bounds, best_f, maximize=False, acq=ACQ_LOG_EI, batch_limit=5, maxiter=200,
+                     eta=1.0, wake=True) -> dict:
+        """gp_wait_eval / acq_eval(grad=False) of the raw samples, botorch's initialize_q_batch(eta) and optimize_acqf in one
+        call (pcabo_propose_acqf).  `blob`: the state of torch's CPU generator as a contiguous uint8 array of 5056 bytes
+        (`torch.get_rng_state().numpy()`), advanced in place.  Returns `raw_vals`, `picked` and `phase_seconds` (wait + score,
+        pick, optimise); with picked also `ic_idx`, `ics`, `cand`, `vals`, `info`, `failed`.  Not picked: the scores have no
+        spread, the blob is untouched and nothing was optimised - initialize_q_batch's other paths are the caller's."""
+        raw = _f64(raw).reshape(-1, self.k)
+        n_raw, nr = raw.shape[0], int(num_restarts)
+        if not (isinstance(blob, np.ndarray) and blob.dtype == np.uint8 and blob.ndim == 1 and blob.size == TORCH_BLOB_BYTES
+                and blob.flags.c_contiguous and blob.flags.writeable):
+            raise ValueError(f"blob: a writable contiguous uint8 array of {TORCH_BLOB_BYTES} bytes")
+        bounds = _f64(bounds, (2, self.k))
+        raw_vals, idx = np.empty(n_raw), np.empty(max(nr, 0), dtype=np.int64)
+        ics, cand, vals = np.empty((max(nr, 0), self.k)), np.empty((max(nr, 0), self.k)), np.empty(max(nr, 0))
+        ng = (nr + batch_limit - 1) // batch_limit if nr > 0 and batch_limit > 0 else 0
+        info = np.zeros((ng, 4), dtype=np.int32)
+        failed, picked = C.c_int(0), C.c_int(0)
+        clocks = np.zeros(3)
+        rc = LIB.pcabo_propose_acqf(self._h, _ptr(raw), n_raw, _ptr(blob), float(eta), nr, int(batch_limit), _ptr(bounds),
+                                    int(maxiter), float(best_f), int(bool(maximize)), int(acq), 0 if wake else PROPOSE_NO_WAKE,
+                                    _ptr(raw_vals), _ptr(idx), _ptr(ics), _ptr(cand), _ptr(vals), _ptr(info), C.byref(failed),
+                                    C.byref(picked), _ptr(clocks))
+        self._chk(rc)
+        self._keep = None
+        out = {"raw_vals": raw_vals, "picked": bool(picked.value), "phase_seconds": clocks}
+        if picked.value:
+            out.update(ic_idx=idx, ics=ics, cand=cand, vals=vals, info=info, failed=bool(failed.value))
+        return out
 
     # ---- row O --------------------------------------------------------------------------------
     def inverse_map(self, z) -> np.ndarray:

@@ -4,6 +4,7 @@ the device: raw-sample scoring (`Context.acq_eval`), multi-start L-BFGS-B (`Cont
 steps (Sobol scramble bits, multinomial pick) run on torch's global CPU generator in botorch's order."""
 from __future__ import annotations
 
+import os
 import warnings
 from time import perf_counter
 from typing import Optional
@@ -86,16 +87,37 @@ def moved_scalar(s, v, maximize: bool, acq_code: int):
     return max(s, v) if maximize else min(s, v)
 
 
+ONE_CALL_ENV = "PCABO_ONE_CALL"      # "0": scoring, pick and optimiser of a single run stay three calls (A/B runs of one build)
+ONE_CALL_WAKE_ENV = "PCABO_ONE_CALL_WAKE"      # "0": the one call leaves the stepping helper asleep until the optimiser needs it
+
+
+def one_call_default() -> bool:
+    return os.environ.get(ONE_CALL_ENV, "1") != "0"
+
+
+def one_call_applies(ctx, acq_code: int, num_restarts: int, n_raw: int) -> bool:
+    """Can the first attempt of `optimize_acqf` be `Context.propose_acqf`?  Not for PI (botorch's non-negative pick stays in
+    torch), not with as many restarts as raw samples (no pick at all), not on a context that offers the three calls only (a
+    stand-in for `_native.Context`), and not when the native generator is not this torch build's (`hostrng.native_ok`)."""
+    if acq_code == _native.ACQ_PI or num_restarts >= n_raw or not callable(getattr(ctx, "propose_acqf", None)):
+        return False
+    from . import hostrng
+    return hostrng.native_ok()
+
+
 def optimize_acqf(ctx: "_native.Context", bounds: np.ndarray, best_f: float, maximize: bool, acq_code: int,
                   num_restarts: int, raw_samples: int, batch_limit: int = 5, maxiter: int = 200, engine=None,
                   breakdown: Optional[dict] = None, trace: Optional[dict] = None, raw: Optional[np.ndarray] = None,
-                  raw_vals: Optional[np.ndarray] = None, before_lbfgsb=None):
+                  raw_vals: Optional[np.ndarray] = None, before_lbfgsb=None, one_call: Optional[bool] = None):
     """Returns (candidate[1, k], all restart candidates, their values, L-BFGS-B info).  `best_f`: the acquisition's scalar
     (the incumbent; for ACQ_UCB kappa - it takes the standardised Boltzmann pick like log-EI).  `engine`: a scrambled Sobol
     engine prepared earlier (same RNG consumption, earlier in time); `raw`: the raw samples already drawn from it
     (while the device was still factorising); `raw_vals`: their acquisition values if the caller already has them
     (`Context.gp_wait_eval`).  The retry path draws and scores afresh.  `before_lbfgsb()`: called once, after the
-    initial conditions are picked (where PCA_BO starts the next iteration's noise draw on its worker thread)."""
+    initial conditions are picked (where PCA_BO starts the next iteration's noise draw on its worker thread).
+    `one_call` (None: `one_call_default()`): with `raw` given and `raw_vals` not, scoring, pick and optimiser are ONE native call
+    (`Context.propose_acqf`, which also ends a conditioning in flight) on the state of torch's global generator - where
+    `one_call_applies`.  `before_lbfgsb()` is then called just before that call.  Same results and the same generator state afterwards as the three calls."""
     pb = breakdown if breakdown is not None else {}
     engines = [engine] if engine is not None and raw is None else []
     ready = [raw] if raw is not None else []
@@ -119,13 +141,43 @@ def optimize_acqf(ctx: "_native.Context", bounds: np.ndarray, best_f: float, max
             trace.update(raw_vals=vals.copy(), ic_idx=np.asarray(idx).copy())
         return raw[idx]
 
-    ics = initial_conditions()
-    if before_lbfgsb is not None:
-        before_lbfgsb()
-    t_opt = perf_counter()
-    cand, vals, info, failed = ctx.optimize_acqf(ics, bounds, best_f, maximize, acq_code, batch_limit=batch_limit,
-                                                 maxiter=maxiter)
-    pb["lbfgsb"] = pb.get("lbfgsb", 0.0) + perf_counter() - t_opt
+    def in_one_call():
+        """The first attempt through Context.propose_acqf: (ics, cand, vals, info, failed), or None when the scores have no
+        spread - nothing was drawn or optimised, and the scores wait in ready_vals for botorch's other paths."""
+        import torch
+        blob = torch.get_rng_state().numpy()
+        if before_lbfgsb is not None:
+            before_lbfgsb()
+        r = ctx.propose_acqf(raw, blob, num_restarts, bounds, best_f, maximize, acq_code, batch_limit=batch_limit,
+                             maxiter=maxiter, eta=_init.INIT_ETA, wake=os.environ.get(ONE_CALL_WAKE_ENV, "1") != "0")
+        for key, t in zip(("raw_eval", "init_pick", "lbfgsb"), r["phase_seconds"]):
+            pb[key] = pb.get(key, 0.0) + float(t)
+        pb.setdefault("sobol", 0.0)
+        if not r["picked"]:
+            ready_vals.append(r["raw_vals"])
+            return None
+        ready.pop()
+        torch.set_rng_state(torch.from_numpy(blob))
+        if trace is not None:
+            trace.update(raw_vals=r["raw_vals"].copy(), ic_idx=r["ic_idx"].copy())
+        return r["ics"], r["cand"], r["vals"], r["info"], r["failed"]
+
+    if one_call is None:
+        one_call = one_call_default()
+    first = None
+    if one_call and raw is not None and raw_vals is None and one_call_applies(ctx, acq_code, num_restarts, len(raw)):
+        first = in_one_call()
+        before_lbfgsb = None               # (called already)
+    if first is not None:
+        ics, cand, vals, info, failed = first
+    else:
+        ics = initial_conditions()
+        if before_lbfgsb is not None:
+            before_lbfgsb()
+        t_opt = perf_counter()
+        cand, vals, info, failed = ctx.optimize_acqf(ics, bounds, best_f, maximize, acq_code, batch_limit=batch_limit,
+                                                     maxiter=maxiter)
+        pb["lbfgsb"] = pb.get("lbfgsb", 0.0) + perf_counter() - t_opt
     if failed:   # botorch: OptimizationWarning -> one retry with freshly drawn initial conditions
         warnings.warn("Optimization failed in `gen_candidates_scipy`; trying again with a new set of "
                       "initial conditions.", RuntimeWarning)
@@ -144,7 +196,7 @@ def optimize_acqf(ctx: "_native.Context", bounds: np.ndarray, best_f: float, max
 def propose(ctx: "_native.Context", bounds: np.ndarray, best_f: float, maximize: bool, acq_code: int, num_restarts: int,
             raw_samples: int, batch_limit: int = 5, maxiter: int = 200, q_eff: int = 1, strategy: str = "kriging_believer",
             f_evals=None, breakdown: Optional[dict] = None, trace: Optional[dict] = None, raw: Optional[np.ndarray] = None,
-            raw_vals: Optional[np.ndarray] = None, before_lbfgsb=None):
+            raw_vals: Optional[np.ndarray] = None, before_lbfgsb=None, one_call: Optional[bool] = None):
     """q_eff candidates of one iteration, one after the other on a model that takes every pending point in (DESIGN.md section
     18).  Proposal 0 is `optimize_acqf` with everything the caller prepared (`raw`, `raw_vals`, `before_lbfgsb`, `trace`); each
     later one is a whole `optimize_acqf` of its own - a fresh scrambled Sobol engine from torch's global generator, scoring by
@@ -160,7 +212,8 @@ def propose(ctx: "_native.Context", bounds: np.ndarray, best_f: float, maximize:
     s, n0, cands, infos = best_f, None, [], []
     try:
         z, _, _, info = optimize_acqf(ctx, bounds, s, maximize, acq_code, num_restarts, raw_samples, batch_limit, maxiter,
-                                      breakdown=breakdown, trace=trace, raw=raw, raw_vals=raw_vals, before_lbfgsb=before_lbfgsb)
+                                      breakdown=breakdown, trace=trace, raw=raw, raw_vals=raw_vals, before_lbfgsb=before_lbfgsb,
+                                      one_call=one_call)
         cands.append(z)
         infos.append(info)
         for _ in range(1, q_eff):

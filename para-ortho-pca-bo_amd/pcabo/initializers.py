@@ -144,6 +144,7 @@ def initialize_q_batch_rows(acq_vals: np.ndarray, n: int, generators, eta: float
             if flags[b] == 2:
                 out.append(np.arange(n))
             elif flags[b] == 1:
+                # nothing picked natively: the draw's largest ratios tie (overflowed weights; not at eta = 1), or
                 # all values equal by the library's statistic (Welford: exactly 0).  torch's own reduction decides, as it does
                 # for a single run: the mean of equal values can round, std comes out as ~1e-16 instead of 0, and botorch then
                 # draws its multinomial over equal weights rather than a random permutation (met on the flat posteriors a fitted
