@@ -52,30 +52,55 @@ def hw_queues_advice(streams: int) -> Optional[str]:
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "lib", "libpcabo.so")
 
-EXPORTS = [
-    "pcabo_abi_version", "pcabo_device_count", "pcabo_ctx_create", "pcabo_ctx_destroy",
-    "pcabo_set_pointer_mode", "pcabo_set_option", "pcabo_last_error", "pcabo_wpca", "pcabo_gp_condition", "pcabo_gp_condition_begin",
-    "pcabo_gp_condition_end", "pcabo_gp_condition_end_eval", "pcabo_wpca_gp_condition_begin", "pcabo_wpca_results",
-    "pcabo_gp_mll", "pcabo_gp_fit", "pcabo_gp_mll_ard", "pcabo_gp_fit_ard",
-    "pcabo_acq_bounds",
-    "pcabo_acq_eval", "pcabo_logei", "pcabo_gp_posterior", "pcabo_batch_gp_posterior", "pcabo_gp_posterior_sample", "pcabo_batch_gp_posterior_sample", "pcabo_gp_loo", "pcabo_batch_gp_loo",
-    "pcabo_gp_extend", "pcabo_gp_truncate", "pcabo_gp_extended",
-    "pcabo_batch_gp_extend", "pcabo_batch_gp_truncate", "pcabo_batch_gp_extended", "pcabo_optimize_acqf", "pcabo_propose_acqf", "pcabo_inverse_map", "pcabo_get_gp_state",
-    "pcabo_get_gram", "pcabo_lbfgsb_minimize", "pcabo_lbfgsb_set_vector_kernels", "pcabo_lbfgsb_set_sum_order", "pcabo_sobol_scramble", "pcabo_sobol_draw", "pcabo_sobol_draw_rows", "pcabo_torch_randint2", "pcabo_torch_multinomial_rows", "pcabo_boltzmann_pick_rows", "pcabo_set_profiling",
-    "pcabo_get_profile", "pcabo_get_profile_calibration", "pcabo_reset_profile",
-    "pcabo_batch_create", "pcabo_batch_destroy", "pcabo_batch_last_error", "pcabo_batch_ctx",
-    "pcabo_batch_wpca_gp_condition_begin", "pcabo_batch_wpca_results", "pcabo_batch_acq_bounds",
-    "pcabo_batch_acq_score", "pcabo_batch_acq_score_begin", "pcabo_batch_acq_score_end",
-    "pcabo_batch_gp_condition_end_eval", "pcabo_batch_optimize_acqf", "pcabo_batch_inverse_map", "pcabo_batch_device_acq_eval",
-    "pcabo_batch_busy", "pcabo_batch_gp_condition_end_eval_begin", "pcabo_batch_gp_condition_end_eval_end",
-    "pcabo_batch_optimize_acqf_begin", "pcabo_batch_optimize_acqf_end", "pcabo_batch_inverse_map_begin", "pcabo_batch_inverse_map_end",
-    "pcabo_batch_set_input_strides", "pcabo_batch_gp_condition_begin",
-    "pcabo_batch_gp_mll", "pcabo_batch_gp_fit", "pcabo_batch_gp_fit_rounds", "pcabo_batch_gp_mll_ard", "pcabo_batch_gp_fit_ard",
-    "pcabo_batch_set_profiling", "pcabo_batch_get_profile", "pcabo_batch_set_active", "pcabo_batch_set_workers", "pcabo_batch_set_option",
-    "pcabo_device_lbfgsb_limits",
-    "pcabo_bbob_table_doubles", "pcabo_bbob_create", "pcabo_bbob_destroy", "pcabo_bbob_eval", "pcabo_bbob_eval_many",
-    "pcabo_comm_unique_id", "pcabo_comm_create", "pcabo_gather_best", "pcabo_comm_last_error", "pcabo_comm_destroy",
-]
+# The C ABI, declared once: function -> its parameters, one letter each (ARG_TYPES), and after ">" what it returns where that is
+# no int.  include/pcabo.h is the authority; tests/test_abi_and_host.py parses it and holds every entry here to it, kind by kind.
+# The typed pointers (I, D, L, V) stand where callers pass C.byref(...) or a ctypes array; everything numpy hands over as an
+# address is a plain "v" (_ptr).  A new C function gets its prototype in the header and one entry here.
+FG_CALLBACK = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
+ARG_TYPES = {
+    "i": C.c_int, "d": C.c_double, "z": C.c_size_t, "l": C.c_int64, "q": C.c_longlong, "v": C.c_void_p, "s": C.c_char_p,
+    "I": C.POINTER(C.c_int), "D": C.POINTER(C.c_double), "L": C.POINTER(C.c_int64), "V": C.POINTER(C.c_void_p), "f": FG_CALLBACK,
+}
+SIGNATURES = {
+    "pcabo_abi_version": "", "pcabo_device_count": "", "pcabo_ctx_create": "iiiiV", "pcabo_ctx_destroy": "v",
+    "pcabo_set_pointer_mode": "vi", "pcabo_set_option": "vii", "pcabo_last_error": "vsi", "pcabo_wpca": "vvvviiidivvvvvIv",
+    "pcabo_gp_condition": "vvviivddi", "pcabo_gp_condition_begin": "vvviivddi", "pcabo_gp_condition_end": "v",
+    "pcabo_gp_condition_end_eval": "vvidiiv", "pcabo_wpca_gp_condition_begin": "vvvviiidivvddivvvvI",
+    "pcabo_wpca_results": "vvvvvI", "pcabo_gp_mll": "vvviivivDv", "pcabo_gp_fit": "vvviivivDv",
+    "pcabo_gp_mll_ard": "vvviivivDv", "pcabo_gp_fit_ard": "vvviivivDv", "pcabo_acq_bounds": "vv", "pcabo_acq_eval": "vvidiivv",
+    "pcabo_logei": "vvidivv", "pcabo_gp_posterior": "vviivvv", "pcabo_batch_gp_posterior": "vviivvvv",
+    "pcabo_gp_posterior_sample": "vviivivvD", "pcabo_batch_gp_posterior_sample": "vviivivvvv", "pcabo_gp_loo": "vvvvvD",
+    "pcabo_batch_gp_loo": "vvvvvvv", "pcabo_gp_extend": "vvvii", "pcabo_gp_truncate": "vi", "pcabo_gp_extended": "vII",
+    "pcabo_batch_gp_extend": "vvviiv", "pcabo_batch_gp_truncate": "viv", "pcabo_batch_gp_extended": "vII",
+    "pcabo_optimize_acqf": "vviividiivvvI", "pcabo_propose_acqf": "vvivdiividiiivvvvvvIIv", "pcabo_inverse_map": "vvv",
+    "pcabo_get_gp_state": "vvvvvv", "pcabo_get_gram": "vv", "pcabo_lbfgsb_minimize": "ivvvfviddiiiDIII",
+    "pcabo_lbfgsb_set_vector_kernels": "i", "pcabo_lbfgsb_set_sum_order": "i", "pcabo_sobol_scramble": "vvi",
+    "pcabo_sobol_draw": "vviivvv", "pcabo_sobol_draw_rows": "vvviivlv", "pcabo_torch_randint2": "vlv",
+    "pcabo_torch_multinomial_rows": "vviiiv", "pcabo_boltzmann_pick_rows": "vviiidvv", "pcabo_set_profiling": "vi",
+    "pcabo_get_profile": "viDLDD", "pcabo_get_profile_calibration": "vDD", "pcabo_reset_profile": "v",
+    "pcabo_batch_create": "iiiiiV", "pcabo_batch_destroy": "v", "pcabo_batch_last_error": "vsi", "pcabo_batch_ctx": "vi>v",
+    "pcabo_batch_wpca_gp_condition_begin": "vvvvviiididdi", "pcabo_batch_wpca_results": "vvvvvv",
+    "pcabo_batch_acq_bounds": "vv", "pcabo_batch_acq_score": "vviviivv", "pcabo_batch_acq_score_begin": "vvivii",
+    "pcabo_batch_acq_score_end": "vivv", "pcabo_batch_gp_condition_end_eval": "vviviivv",
+    "pcabo_batch_optimize_acqf": "vviiviviivvvvv", "pcabo_batch_inverse_map": "vvv", "pcabo_batch_device_acq_eval": "vviviivv",
+    "pcabo_batch_busy": "v", "pcabo_batch_gp_condition_end_eval_begin": "vvivii",
+    "pcabo_batch_gp_condition_end_eval_end": "vviviivv", "pcabo_batch_optimize_acqf_begin": "vviivivii",
+    "pcabo_batch_optimize_acqf_end": "viivvvvv", "pcabo_batch_inverse_map_begin": "vv", "pcabo_batch_inverse_map_end": "vv",
+    "pcabo_batch_set_input_strides": "vzzz", "pcabo_batch_gp_condition_begin": "vvviivddi", "pcabo_batch_gp_mll": "vvvvv",
+    "pcabo_batch_gp_fit": "vvvvv", "pcabo_batch_gp_fit_rounds": "v", "pcabo_batch_gp_mll_ard": "vvivvv",
+    "pcabo_batch_gp_fit_ard": "vvivvv", "pcabo_batch_set_profiling": "vi", "pcabo_batch_get_profile": "vv",
+    "pcabo_batch_set_active": "vv", "pcabo_batch_set_workers": "vi", "pcabo_batch_set_option": "vii",
+    "pcabo_device_lbfgsb_limits": "III", "pcabo_bbob_table_doubles": "i", "pcabo_bbob_create": "iiivvV",
+    "pcabo_bbob_destroy": "v", "pcabo_bbob_eval": "vvdddvv", "pcabo_bbob_eval_many": "vvidddvv", "pcabo_comm_unique_id": "s",
+    "pcabo_comm_create": "siiiV", "pcabo_gather_best": "vviv", "pcabo_comm_last_error": "vsi", "pcabo_comm_destroy": "v",
+}
+EXPORTS = list(SIGNATURES)
+# debug exports (not in include/pcabo.h): the branch counters of the host L-BFGS-B and what the device optimiser writes per group.
+# Declared where the library has them (the host-only checker builds of the library have no batch).
+DEBUG_SIGNATURES = {
+    "pcabo_debug_lbfgsb_branch_names": "si", "pcabo_debug_lbfgsb_branches": "vi",
+    "pcabo_debug_batch_lbfgsb_branches": "vvi", "pcabo_debug_batch_lbfgsb_device_out": "vvi",
+}
 
 
 class PcaboError(RuntimeError):
@@ -89,6 +114,16 @@ def lib_path() -> str:
     return os.path.normpath(os.environ.get("PCABO_LIB") or _LIB_PATH)
 
 
+def _declare(lib, table, optional=False) -> None:
+    for name, code in table.items():
+        if optional and not hasattr(lib, name):
+            continue
+        args, _, ret = code.partition(">")
+        fn = getattr(lib, name)
+        fn.argtypes = [ARG_TYPES[c] for c in args]
+        fn.restype = ARG_TYPES[ret or "i"]
+
+
 def _load() -> C.CDLL:
     path = lib_path()
     if not os.path.exists(path):
@@ -99,111 +134,12 @@ def _load() -> C.CDLL:
     lib.pcabo_abi_version.restype = C.c_int
     if lib.pcabo_abi_version() != ABI_VERSION:
         raise ImportError(f"{path}: ABI version mismatch")
-    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p
-    lib.pcabo_device_count.restype = C.c_int
-    lib.pcabo_ctx_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
-    lib.pcabo_ctx_destroy.argtypes = [vp]
-    lib.pcabo_set_pointer_mode.argtypes = [vp, C.c_int]
-    lib.pcabo_set_option.argtypes = [vp, C.c_int, C.c_int]
-    lib.pcabo_last_error.argtypes = [vp, C.c_char_p, C.c_int]
-    lib.pcabo_wpca.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp,
-                               vp, vp, vp, vp, ip, vp]
-    lib.pcabo_gp_condition.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int]
-    lib.pcabo_gp_condition_begin.argtypes = lib.pcabo_gp_condition.argtypes
-    lib.pcabo_gp_condition_end.argtypes = [vp]
-    lib.pcabo_gp_mll.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, dp, vp]
-    lib.pcabo_gp_fit.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, dp, vp]
-    lib.pcabo_gp_mll_ard.argtypes = lib.pcabo_gp_mll.argtypes
-    lib.pcabo_gp_fit_ard.argtypes = lib.pcabo_gp_fit.argtypes
-    lib.pcabo_wpca_results.argtypes = [vp, vp, vp, vp, vp, ip]
-    lib.pcabo_gp_condition_end_eval.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp]
-    lib.pcabo_wpca_gp_condition_begin.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp,
-                                                  vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, ip]
-    lib.pcabo_acq_bounds.argtypes = [vp, vp]
-    lib.pcabo_acq_eval.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp]
-    lib.pcabo_logei.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, vp, vp]
-    lib.pcabo_gp_posterior.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
-    lib.pcabo_batch_gp_posterior.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
-    lib.pcabo_gp_posterior_sample.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, dp]
-    lib.pcabo_batch_gp_posterior_sample.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
-    lib.pcabo_gp_loo.argtypes = [vp, vp, vp, vp, vp, dp]
-    lib.pcabo_batch_gp_loo.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.pcabo_gp_extend.argtypes = [vp, vp, vp, C.c_int, C.c_int]
-    lib.pcabo_gp_truncate.argtypes = [vp, C.c_int]
-    lib.pcabo_gp_extended.argtypes = [vp, ip, ip]
-    lib.pcabo_batch_gp_extend.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
-    lib.pcabo_batch_gp_truncate.argtypes = [vp, C.c_int, vp]
-    lib.pcabo_batch_gp_extended.argtypes = [vp, ip, ip]
-    lib.pcabo_optimize_acqf.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int,
-                                        vp, vp, vp, ip]
-    lib.pcabo_propose_acqf.argtypes = [vp, vp, C.c_int, vp, C.c_double, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int,
-                                       C.c_int, vp, vp, vp, vp, vp, vp, ip, ip, vp]
-    lib.pcabo_inverse_map.argtypes = [vp, vp, vp]
-    lib.pcabo_get_gp_state.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.pcabo_get_gram.argtypes = [vp, vp]
-    lib.pcabo_sobol_scramble.argtypes = [vp, vp, C.c_int]
-    lib.pcabo_sobol_draw.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
-    lib.pcabo_sobol_draw_rows.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_longlong, vp]
-    lib.pcabo_set_profiling.argtypes = [vp, C.c_int]
-    lib.pcabo_get_profile.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_int64), dp, dp]
-    lib.pcabo_reset_profile.argtypes = [vp]
-    lib.pcabo_get_profile_calibration.argtypes = [vp, dp, dp]
-    lib.pcabo_lbfgsb_set_vector_kernels.argtypes = [C.c_int]
-    lib.pcabo_batch_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
-    lib.pcabo_comm_unique_id.argtypes = [C.c_char_p]
-    lib.pcabo_comm_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
-    lib.pcabo_gather_best.argtypes = [vp, vp, C.c_int, vp]
-    lib.pcabo_comm_last_error.argtypes = [vp, C.c_char_p, C.c_int]
-    lib.pcabo_comm_destroy.argtypes = [vp]
-    lib.pcabo_batch_destroy.argtypes = [vp]
-    lib.pcabo_batch_set_workers.argtypes = [vp, C.c_int]
-    lib.pcabo_batch_set_option.argtypes = [vp, C.c_int, C.c_int]
-    lib.pcabo_batch_last_error.argtypes = [vp, C.c_char_p, C.c_int]
-    lib.pcabo_batch_ctx.argtypes = [vp, C.c_int]
-    lib.pcabo_batch_wpca_gp_condition_begin.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
-                                                        C.c_double, C.c_double, C.c_int]
-    lib.pcabo_batch_wpca_results.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.pcabo_batch_acq_bounds.argtypes = [vp, vp]
-    lib.pcabo_batch_gp_condition_end_eval.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
-    lib.pcabo_batch_optimize_acqf.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    lib.pcabo_batch_inverse_map.argtypes = [vp, vp, vp]
-    lib.pcabo_batch_device_acq_eval.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
-    lib.pcabo_batch_busy.argtypes = [vp]
-    lib.pcabo_batch_gp_condition_end_eval_begin.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int]
-    lib.pcabo_batch_gp_condition_end_eval_end.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
-    lib.pcabo_batch_acq_score.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
-    lib.pcabo_batch_acq_score_begin.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int]
-    lib.pcabo_batch_acq_score_end.argtypes = [vp, C.c_int, vp, vp]
-    lib.pcabo_batch_optimize_acqf_begin.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int]
-    lib.pcabo_batch_optimize_acqf_end.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    lib.pcabo_batch_inverse_map_begin.argtypes = [vp, vp]
-    lib.pcabo_batch_set_input_strides.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_size_t]
-    lib.pcabo_batch_gp_condition_begin.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_int]
-    lib.pcabo_batch_inverse_map_end.argtypes = [vp, vp]
-    lib.pcabo_batch_set_profiling.argtypes = [vp, C.c_int]
-    lib.pcabo_batch_set_active.argtypes = [vp, vp]
-    lib.pcabo_batch_get_profile.argtypes = [vp, vp]
-    lib.pcabo_batch_gp_mll.argtypes = [vp, vp, vp, vp, vp]
-    lib.pcabo_batch_gp_fit.argtypes = [vp, vp, vp, vp, vp]
-    lib.pcabo_batch_gp_fit_rounds.argtypes = [vp]
-    lib.pcabo_batch_gp_mll_ard.argtypes = [vp, vp, C.c_int, vp, vp, vp]
-    lib.pcabo_batch_gp_fit_ard.argtypes = [vp, vp, C.c_int, vp, vp, vp]
-    for name in EXPORTS:
-        getattr(lib, name).restype = C.c_int
-    lib.pcabo_batch_ctx.restype = vp
+    _declare(lib, SIGNATURES)
+    _declare(lib, DEBUG_SIGNATURES, optional=True)
     return lib
 
 
 LIB = _load()
-FG_CALLBACK = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
-LIB.pcabo_lbfgsb_minimize.argtypes = [
-    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, FG_CALLBACK, C.c_void_p, C.c_int, C.c_double, C.c_double,
-    C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-
-
-# debug exports (not in include/pcabo.h): the branch counters of the host L-BFGS-B and what the device optimiser writes per group
-LIB.pcabo_debug_lbfgsb_branch_names.argtypes = [C.c_char_p, C.c_int]
-LIB.pcabo_debug_lbfgsb_branches.argtypes = [C.c_void_p, C.c_int]
 
 
 def _branch_names():
@@ -216,9 +152,6 @@ def _branch_names():
 
 LBFGSB_BRANCHES = _branch_names()               # the counters' names, in the order of the enum in csrc/lbfgsb.h
 DEVICE_GROUP_FIELDS = ("niter", "nfev", "warnflag", "task", "status", "evaluations", "ties", "evaluation_cap")
-if hasattr(LIB, "pcabo_debug_batch_lbfgsb_branches"):       # (the host-only checker builds of the library have no batch)
-    LIB.pcabo_debug_batch_lbfgsb_branches.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    LIB.pcabo_debug_batch_lbfgsb_device_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 
 
 def device_count() -> int:
@@ -264,29 +197,87 @@ def sample_base(q: int, n_samples=None, base_samples=None, seed=None) -> np.ndar
     return np.random.default_rng(seed).standard_normal((S, q))
 
 
-class Context:
-    """One per-run device context (a HIP stream + workspaces).  Not thread-safe; use one per thread."""
+def pack_rows(blocks, row: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """The (B, row) buffer the batch calls take one run's points per row in: blocks[b], flattened, at the head of row b.  `out`
+    None: a fresh zeroed buffer of len(blocks) rows; else rows are written in place and whatever lies behind a block stays (the
+    library reads only the head).  A block that is a view of `out` already lies in its row (Batch.raw_row_buffer) and is not
+    copied; a None block's row is left alone.  The blocks are numpy arrays of any layout and dtype."""
+    kept, asarray, f64 = out is not None, np.asarray, np.float64            # (locals: this loop runs B times per call of an iteration)
+    if not kept:
+        out = np.zeros((len(blocks), row))
+    for b, x in enumerate(blocks):
+        if x is None or (kept and x.base is out):
+            continue
+        out[b, : x.size] = asarray(x, f64).ravel()                          # (row by row, whatever x's layout)
+    return out
 
-    def __init__(self, max_n: int, max_d: int, max_q: int = 512, device: int = 0):
+
+def per_run(status, build, status_only: bool = False) -> list:
+    """One entry per run of a batch call: build(b) where status[b] == 0; for a run the call skipped None, or {"status": code}."""
+    return [build(b) if status[b] == 0 else ({"status": int(status[b])} if status_only else None) for b in range(len(status))]
+
+
+def fit_result(theta, loss, ard=False, grad=None, info=None) -> dict:
+    """What a likelihood evaluation (`grad`) or a fit (`info`: iterations, evaluations, warnflag, task) returns for one model at
+    theta = (noise, mean constant, raw lengthscale | rho_1 .. rho_k)."""
+    if ard:                                             # softplus as torch (and the library) compute it
+        rho = theta[2:]
+        out = {"lengthscales": np.where(rho > 20.0, rho, np.log1p(np.exp(np.minimum(rho, 20.0))))}
+    else:
+        rho = float(theta[2])
+        out = {"lengthscale": math.log1p(math.exp(rho)) if rho <= 20.0 else rho}
+    out.update(noise=float(theta[0]), mean_constant=float(theta[1]), loss=float(loss), theta=theta.copy())
+    if grad is not None:
+        out["grad"] = grad
+    if info is not None:
+        out.update(iterations=int(info[0]), evaluations=int(info[1]), warnflag=int(info[2]), task=int(info[3]))
+    return out
+
+
+class _Handle:
+    """An object of the library behind one handle: its error text, the check of a status code, its end, and a failed creation."""
+    _last_error = _destroy = None                       # the library's functions for this kind of handle
+    _NOT_CREATED = "no usable HIP device (the HIP path has no CPU fallback)"
+
+    def _create(self, create, *args) -> None:
         self._h = C.c_void_p()
-        rc = LIB.pcabo_ctx_create(int(device), int(max_n), int(max_d), int(max_q), C.byref(self._h))
-        if rc != 0:
-            msg = self._err() if self._h else "no usable HIP device (the HIP path has no CPU fallback)"
-            if self._h:
-                LIB.pcabo_ctx_destroy(self._h)
-                self._h = C.c_void_p()
+        rc = create(*args, C.byref(self._h))
+        if rc != 0:                                     # (the library may hand back a half-made object that holds the message)
+            msg = self._err() if self._h else self._NOT_CREATED
+            _Handle.close(self)
             raise PcaboError(rc, msg)
-        self.max_n, self.max_d, self.max_q, self.device = max_n, max_d, max_q, device
-        self.n = self.d = self.k = 0
 
     def _err(self) -> str:
+        if self._last_error is None:
+            return self._NOT_CREATED
         buf = C.create_string_buffer(512)
-        LIB.pcabo_last_error(self._h, buf, 512)
+        self._last_error(self._h, buf, 512)
         return buf.value.decode(errors="replace")
 
     def _chk(self, rc: int) -> None:
         if rc != 0:
             raise PcaboError(rc, self._err())
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
+    """One per-run device context (a HIP stream + workspaces).  Not thread-safe; use one per thread."""
+    _last_error, _destroy = LIB.pcabo_last_error, LIB.pcabo_ctx_destroy
+
+    def __init__(self, max_n: int, max_d: int, max_q: int = 512, device: int = 0):
+        self._create(LIB.pcabo_ctx_create, int(device), int(max_n), int(max_d), int(max_q))
+        self.max_n, self.max_d, self.max_q, self.device = max_n, max_d, max_q, device
+        self.n = self.d = self.k = 0
 
     def set_option(self, option: int, value: int) -> None:
         self._chk(LIB.pcabo_set_option(self._h, int(option), int(value)))
@@ -298,17 +289,6 @@ class Context:
         if getattr(self, "_bestf_f32", 1) != f32:
             self.set_option(OPT_BESTF_F32, f32)
             self._bestf_f32 = f32
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            LIB.pcabo_ctx_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- rows A-C -----------------------------------------------------------------------------
     def wpca(self, X, f=None, ranks=None, maximize=False, var_threshold=0.95, n_components=0, noise=None,
@@ -387,16 +367,6 @@ class Context:
         return y, Z, k, nb
 
     @staticmethod
-    def _fit_result(theta, loss, ard=False):
-        if ard:                                         # softplus as torch (and the library) compute it
-            rho = theta[2:]
-            ls = {"lengthscales": np.where(rho > 20.0, rho, np.log1p(np.exp(np.minimum(rho, 20.0))))}
-        else:
-            rho = float(theta[2])
-            ls = {"lengthscale": math.log1p(math.exp(rho)) if rho <= 20.0 else rho}
-        return {**ls, "noise": float(theta[0]), "mean_constant": float(theta[1]), "loss": float(loss), "theta": theta.copy()}
-
-    @staticmethod
     def _theta(theta, k, ard):
         if not ard:
             return _f64(theta, (3,)).copy()
@@ -411,7 +381,7 @@ class Context:
         fn = LIB.pcabo_gp_mll_ard if ard else LIB.pcabo_gp_mll
         self._chk(fn(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th), C.byref(loss), _ptr(g)))
         self.n, self.k = y.shape[0], k
-        return {**self._fit_result(th, loss.value, ard), "grad": g}
+        return fit_result(th, loss.value, ard, grad=g)
 
     def _gp_fit(self, ard, y, theta0, Z, norm_bounds, kernel):
         y, Z, k, nb = self._fit_args(y, Z, norm_bounds)
@@ -420,8 +390,7 @@ class Context:
         fn = LIB.pcabo_gp_fit_ard if ard else LIB.pcabo_gp_fit
         self._chk(fn(self._h, _ptr(Z), _ptr(y), y.shape[0], k, _ptr(nb), int(kernel), _ptr(th), C.byref(loss), _ptr(info)))
         self.n, self.k = y.shape[0], k
-        return {**self._fit_result(th, loss.value, ard), "iterations": int(info[0]), "evaluations": int(info[1]),
-                "warnflag": int(info[2]), "task": int(info[3])}
+        return fit_result(th, loss.value, ard, info=info)
 
     def gp_mll(self, y, theta=FIT_THETA0, Z=None, norm_bounds=None, kernel=KERNEL_MATERN52):
         """Loss of the GP fit and its gradient at theta = (noise, mean constant, raw lengthscale); the context is left
@@ -647,20 +616,14 @@ class _BorrowedContext(Context):
         self._h = C.c_void_p()
 
 
-class Batch:
+class Batch(_Handle):
     """B per-run contexts advancing in lock-step (pcabo_batch_* of include/pcabo.h): one launch sequence for the
     rows A-H of all runs, one scoring launch, shared acquisition launches for the L-BFGS-B rounds of all runs."""
+    _last_error, _destroy = LIB.pcabo_batch_last_error, LIB.pcabo_batch_destroy
 
     def __init__(self, B: int, max_n: int, max_d: int, max_q: int = 512, device: int = 0, workers: int = 0,
                  group_acq: bool = True, device_lbfgsb: int = 0):
-        self._h = C.c_void_p()
-        rc = LIB.pcabo_batch_create(int(device), int(B), int(max_n), int(max_d), int(max_q), C.byref(self._h))
-        if rc != 0:
-            msg = self._err() if self._h else "no usable HIP device (the HIP path has no CPU fallback)"
-            if self._h:
-                LIB.pcabo_batch_destroy(self._h)
-                self._h = C.c_void_p()
-            raise PcaboError(rc, msg)
+        self._create(LIB.pcabo_batch_create, int(device), int(B), int(max_n), int(max_d), int(max_q))
         self.B, self.max_n, self.max_d, self.max_q, self.device = B, max_n, max_d, max_q, device
         self.n = self.d = 0
         self.k = np.zeros(B, dtype=np.int32)
@@ -681,27 +644,11 @@ class Batch:
         """Worker threads of the L-BFGS-B phase (they spin: several batches of one process share the process's cores)."""
         self._chk(LIB.pcabo_batch_set_workers(self._h, int(workers)))
 
-    def _err(self) -> str:
-        buf = C.create_string_buffer(512)
-        LIB.pcabo_batch_last_error(self._h, buf, 512)
-        return buf.value.decode(errors="replace")
-
-    def _chk(self, rc: int) -> None:
-        if rc != 0:
-            raise PcaboError(rc, self._err())
-
     def close(self) -> None:
         if getattr(self, "_h", None):
             for c in self.ctx:
                 c.close()
-            LIB.pcabo_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     @staticmethod
     def _block(a, row):
@@ -716,6 +663,26 @@ class Batch:
             return a, a.strides[0] // item
         return np.ascontiguousarray(a, dtype=np.float64), row
 
+    def _packed(self, blocks, row: int) -> np.ndarray:
+        """pack_rows into a fresh zeroed buffer with a row for every run."""
+        if len(blocks) == self.B:
+            return pack_rows(blocks, row)
+        return pack_rows(blocks, row, np.zeros((self.B, row)))      # (too few leave rows zero, too many are an IndexError)
+
+    def _input_blocks(self, *inputs):
+        """The conditioning calls' (X, noise, y), each given as (array or None, doubles per run), as _block lays them out; the
+        library is told the strides between the runs' blocks (0: dense) when they differ from the last call's."""
+        arrays, strides = [], []
+        for a, row in inputs:
+            a, s = self._block(a, row)
+            arrays.append(a)
+            strides.append(0 if s == row else s)
+        strides = tuple(strides)
+        if strides != getattr(self, "_in_strides", (0, 0, 0)):
+            self._chk(LIB.pcabo_batch_set_input_strides(self._h, *strides))
+            self._in_strides = strides
+        return arrays
+
     def wpca_gp_condition_begin(self, X, ranks, noise, y, maximize=False, var_threshold=0.95, n_components=0,
                                 lengthscale=0.6931471805599453, gp_noise=0.006737946999085467, kernel=KERNEL_MATERN52):
         """X[B,n,d], ranks[B,n] (int64), noise[B,n,d] or None, y[B,n]: enqueue rows A-H of every run."""
@@ -724,13 +691,7 @@ class Batch:
         assert B == self.B
         ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(B, n)
         y = np.asarray(y, dtype=np.float64).reshape(B, n)
-        X, sx = self._block(X, n * d)
-        nz, sn = self._block(noise, n * d)
-        y, sy = self._block(y, n)
-        strides = (0 if sx == n * d else sx, 0 if sn == n * d else sn, 0 if sy == n else sy)
-        if strides != getattr(self, "_in_strides", (0, 0, 0)):
-            self._chk(LIB.pcabo_batch_set_input_strides(self._h, *strides))
-            self._in_strides = strides
+        X, nz, y = self._input_blocks((X, n * d), (noise, n * d), (y, n))
         self._chk(LIB.pcabo_batch_wpca_gp_condition_begin(self._h, _ptr(X), _ptr(ranks), _ptr(nz), _ptr(y), n, d,
                                                           int(bool(maximize)), float(var_threshold), int(n_components),
                                                           float(lengthscale), float(gp_noise), int(kernel)))
@@ -744,12 +705,7 @@ class Batch:
         B, n, k = Z.shape
         assert B == self.B
         y = np.asarray(y, dtype=np.float64).reshape(B, n)
-        Z, sx = self._block(Z, n * k)
-        y, sy = self._block(y, n)
-        strides = (0 if sx == n * k else sx, 0, 0 if sy == n else sy)
-        if strides != getattr(self, "_in_strides", (0, 0, 0)):
-            self._chk(LIB.pcabo_batch_set_input_strides(self._h, *strides))
-            self._in_strides = strides
+        Z, _, y = self._input_blocks((Z, n * k), (None, 0), (y, n))
         nb = None if norm_bounds is None else _f64(norm_bounds, (2, k))
         self._chk(LIB.pcabo_batch_gp_condition_begin(self._h, _ptr(Z), _ptr(y), n, k, _ptr(nb), float(lengthscale), float(gp_noise),
                                                      int(kernel)))
@@ -779,9 +735,7 @@ class Batch:
         """Xq_list[b]: q x k_b points of run b; best_f[B]: every run's scalar (ACQ_UCB: its kappa = sqrt(beta), as in
         Context.acq_eval - the same holds for every `best_f` of this class).  Returns (values[B, q], status[B])."""
         q = Xq_list[0].shape[0]
-        buf = np.zeros((self.B, q * self.max_d))
-        for b, xq in enumerate(Xq_list):
-            buf[b, : xq.size] = np.ascontiguousarray(xq, dtype=np.float64).ravel()
+        buf = self._packed(Xq_list, q * self.max_d)
         bf = _f64(best_f, (self.B,))
         val = np.empty((self.B, q))
         status = np.zeros(self.B, dtype=np.int32)
@@ -793,23 +747,18 @@ class Batch:
         """Context.gp_posterior for every run in one launch sequence (Xq_list[b]: q x k_b, the same q for all runs; the batch's
         conditioning has been waited for).  One dict per run, None for a run that was skipped (parked, or without a GP)."""
         q = Xq_list[0].shape[0]
-        buf = np.zeros((self.B, q * self.max_d))
-        for b, xq in enumerate(Xq_list):
-            buf[b, : xq.size] = np.ascontiguousarray(xq, dtype=np.float64).ravel()
+        buf = self._packed(Xq_list, q * self.max_d)
         mean, var = np.zeros((self.B, q)), np.zeros((self.B, q))
         cov = np.zeros((self.B, q, q)) if covariance else None
         status = np.zeros(self.B, dtype=np.int32)
         self._chk(LIB.pcabo_batch_gp_posterior(self._h, _ptr(buf), q, POST_OBS_NOISE if observation_noise else 0, _ptr(mean),
                                                _ptr(var), _ptr(cov), _ptr(status)))
-        out = []
-        for b in range(self.B):
-            if status[b] != 0:
-                out.append(None)
-                continue
-            out.append({"mean": mean[b].copy(), "variance": var[b].copy()})
+        def one(b):
+            out = {"mean": mean[b].copy(), "variance": var[b].copy()}
             if covariance:
-                out[-1]["covariance"] = cov[b].copy()
-        return out
+                out["covariance"] = cov[b].copy()
+            return out
+        return per_run(status, one)
 
     def gp_loo(self):
         """Context.gp_loo for every run in one launch (the batch's conditioning has been waited for).  One dict per run, None for
@@ -819,8 +768,8 @@ class Batch:
         total = np.zeros(self.B)
         status = np.zeros(self.B, dtype=np.int32)
         self._chk(LIB.pcabo_batch_gp_loo(self._h, _ptr(mean), _ptr(var), _ptr(z), _ptr(lpd), _ptr(total), _ptr(status)))
-        return [None if status[b] != 0 else {"mean": mean[b].copy(), "variance": var[b].copy(), "z": z[b].copy(),
-                                             "lpd": lpd[b].copy(), "lpd_sum": float(total[b])} for b in range(self.B)]
+        return per_run(status, lambda b: {"mean": mean[b].copy(), "variance": var[b].copy(), "z": z[b].copy(),
+                                          "lpd": lpd[b].copy(), "lpd_sum": float(total[b])})
 
     def gp_posterior_samples(self, Xq_list, n_samples=None, base_samples=None, seed=None, observation_noise=False, centred=False):
         """Context.gp_posterior_samples for every run in one launch sequence (Xq_list[b]: q x k_b, the same q for all runs).
@@ -837,16 +786,13 @@ class Batch:
             one = sample_base(q, n_samples, base_samples, seed)
             base = np.ascontiguousarray(np.broadcast_to(one, (self.B,) + one.shape))
         S = base.shape[1]
-        buf = np.zeros((self.B, q * self.max_d))
-        for b, xq in enumerate(Xq_list):
-            buf[b, : xq.size] = np.ascontiguousarray(xq, dtype=np.float64).ravel()
+        buf = self._packed(Xq_list, q * self.max_d)
         samples, mean, jitter = np.zeros((self.B, S, q)), np.zeros((self.B, q)), np.zeros(self.B)
         status = self.sample_status = np.zeros(self.B, dtype=np.int32)
         flags = (POST_OBS_NOISE if observation_noise else 0) | (POST_CENTRED if centred else 0)
         self._chk(LIB.pcabo_batch_gp_posterior_sample(self._h, _ptr(buf), q, flags, _ptr(base), S, _ptr(samples), _ptr(mean),
                                                       _ptr(jitter), _ptr(status)))
-        return [None if status[b] != 0 else {"samples": samples[b].copy(), "mean": mean[b].copy(), "jitter": float(jitter[b])}
-                for b in range(self.B)]
+        return per_run(status, lambda b: {"samples": samples[b].copy(), "mean": mean[b].copy(), "jitter": float(jitter[b])})
 
     # ---- appending points to every run's GP and taking them back (pcabo_batch_gp_extend / pcabo_batch_gp_truncate) -------
     def _counts(self):
@@ -879,14 +825,12 @@ class Batch:
         aside until gp_truncate reaches the n of entry (include/pcabo.h)."""
         if len(Zp_list) != self.B:
             raise ValueError(f"Zp_list must have one entry per run ({self.B})")
-        shapes = {np.asarray(z, dtype=np.float64).reshape(-1, int(self.k[b])).shape[0] for b, z in enumerate(Zp_list) if z is not None}
+        Zp = [None if z is None else np.asarray(z, dtype=np.float64).reshape(-1, int(self.k[b])) for b, z in enumerate(Zp_list)]
+        shapes = {z.shape[0] for z in Zp if z is not None}
         if len(shapes) > 1:
             raise ValueError("every run takes the same number of points")
         p = shapes.pop() if shapes else (0 if y is None else np.asarray(y).reshape(self.B, -1).shape[1])
-        buf = np.zeros((self.B, max(p, 1) * self.max_d))
-        for b, z in enumerate(Zp_list):
-            if z is not None:
-                buf[b, : p * int(self.k[b])] = np.ascontiguousarray(z, dtype=np.float64).ravel()
+        buf = self._packed(Zp, max(p, 1) * self.max_d)
         yv = None if y is None else _f64(y, (self.B, p))
         status = np.zeros(self.B, dtype=np.int32)
         self._chk(LIB.pcabo_batch_gp_extend(self._h, _ptr(buf), _ptr(yv), p, EXTEND_BELIEVER if y is None else 0,
@@ -908,15 +852,27 @@ class Batch:
     # ---- opt-in GP hyperparameter fit of all runs in lock-step (pcabo_batch_gp_mll / pcabo_batch_gp_fit) -----------------
     # Both work on the inputs of the last wpca_gp_condition_begin / gp_condition_begin and leave every run conditioned at its
     # own theta; gp_wait_eval / gp_eval_begin + gp_eval_end and optimize_acqf then use the runs' own models.
+    def _fit_call(self, fn, key, th, ks=None):
+        """One of the four calls on the packed thetas `th`, and its results: per run fit_result with `grad` (key "grad") or with
+        the fit's counters (key "info"), plus `status` 0; only `status` for a run the call skipped.  ks: the runs' k in the
+        per-input form (rows of 2 + max k, whose width the library is told), None in the shared form (rows of 3)."""
+        ard = ks is not None
+        loss, status = np.zeros(self.B), np.zeros(self.B, dtype=np.int32)
+        extra = np.zeros_like(th) if key == "grad" else np.zeros((self.B, 4), dtype=np.int32)
+        width = (th.shape[1],) if ard else ()
+        self._chk_fit(fn(self._h, _ptr(th), *width, _ptr(loss), _ptr(extra), _ptr(status)))
+        if ard or key == "info":                        # (the shared form's likelihood steps no rounds)
+            self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
+
+        def one(b):
+            w = 2 + ks[b] if ard else 3
+            return {**fit_result(th[b, :w], loss[b], ard, **{key: extra[b, :w].copy() if key == "grad" else extra[b]}), "status": 0}
+        return per_run(status, one, status_only=True)
+
     def gp_mll(self, thetas):
         """thetas (B, 3) = (noise, mean constant, raw lengthscale) per run.  One dict per run as Context.gp_mll returns it, plus
         `status` (0; a parked run or one that could not be factored: only `status`)."""
-        th = _f64(thetas, (self.B, 3))
-        loss, grad = np.zeros(self.B), np.zeros((self.B, 3))
-        status = np.zeros(self.B, dtype=np.int32)
-        self._chk_fit(LIB.pcabo_batch_gp_mll(self._h, _ptr(th), _ptr(loss), _ptr(grad), _ptr(status)))
-        return [{**Context._fit_result(th[b], loss[b]), "grad": grad[b].copy(), "status": 0} if status[b] == 0
-                else {"status": int(status[b])} for b in range(self.B)]
+        return self._fit_call(LIB.pcabo_batch_gp_mll, "grad", _f64(thetas, (self.B, 3)))
 
     def gp_fit(self, theta0=None):
         """Fit every run's (noise, mean constant, raw lengthscale) from theta0 ((3,) for all runs, (B, 3), or None: the model's
@@ -925,13 +881,7 @@ class Batch:
         start could not be factored: only `status`).  `fit_rounds`: the launch sequences the call took."""
         th0 = np.asarray(FIT_THETA0 if theta0 is None else theta0, dtype=np.float64)
         th = np.ascontiguousarray(np.broadcast_to(th0, (self.B, 3)), dtype=np.float64).copy()
-        loss, info = np.zeros(self.B), np.zeros((self.B, 4), dtype=np.int32)
-        status = np.zeros(self.B, dtype=np.int32)
-        self._chk_fit(LIB.pcabo_batch_gp_fit(self._h, _ptr(th), _ptr(loss), _ptr(info), _ptr(status)))
-        self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
-        return [{**Context._fit_result(th[b], loss[b]), "iterations": int(info[b, 0]), "evaluations": int(info[b, 1]),
-                 "warnflag": int(info[b, 2]), "task": int(info[b, 3]), "status": 0} if status[b] == 0
-                else {"status": int(status[b])} for b in range(self.B)]
+        return self._fit_call(LIB.pcabo_batch_gp_fit, "info", th)
 
     # ---- the same with one lengthscale per input (pcabo_batch_gp_mll_ard / pcabo_batch_gp_fit_ard) ------------------------
     def _ard_rows(self, thetas):
@@ -948,26 +898,13 @@ class Batch:
         """thetas[b] (2 + k_b,) = (noise, mean constant, rho_1 .. rho_{k_b}) of run b.  One dict per run as Context.gp_mll_ard
         returns it (`theta` and `grad` of length 2 + k_b), plus `status` (0; a parked run or one that could not be factored:
         only `status`)."""
-        th, ks = self._ard_rows(thetas)
-        loss, grad = np.zeros(self.B), np.zeros_like(th)
-        status = np.zeros(self.B, dtype=np.int32)
-        self._chk_fit(LIB.pcabo_batch_gp_mll_ard(self._h, _ptr(th), th.shape[1], _ptr(loss), _ptr(grad), _ptr(status)))
-        self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
-        return [{**Context._fit_result(th[b, : 2 + k], loss[b], True), "grad": grad[b, : 2 + k].copy(), "status": 0}
-                if status[b] == 0 else {"status": int(status[b])} for b, k in enumerate(ks)]
+        return self._fit_call(LIB.pcabo_batch_gp_mll_ard, "grad", *self._ard_rows(thetas))
 
     def gp_fit_ard(self, theta0=None):
         """Batch.gp_fit with one lengthscale per input: theta0[b] (2 + k_b,) per run, or None: the model's initial values (every
         rho_c = 0).  Bit for bit the fits Context.gp_fit_ard finds for the runs one by one; one dict per run as it returns it,
         plus `status`.  `fit_rounds`: the launch sequences the call took."""
-        th, ks = self._ard_rows(theta0)
-        loss, info = np.zeros(self.B), np.zeros((self.B, 4), dtype=np.int32)
-        status = np.zeros(self.B, dtype=np.int32)
-        self._chk_fit(LIB.pcabo_batch_gp_fit_ard(self._h, _ptr(th), th.shape[1], _ptr(loss), _ptr(info), _ptr(status)))
-        self.fit_rounds = int(LIB.pcabo_batch_gp_fit_rounds(self._h))
-        return [{**Context._fit_result(th[b, : 2 + k], loss[b], True), "iterations": int(info[b, 0]),
-                 "evaluations": int(info[b, 1]), "warnflag": int(info[b, 2]), "task": int(info[b, 3]), "status": 0}
-                if status[b] == 0 else {"status": int(status[b])} for b, k in enumerate(ks)]
+        return self._fit_call(LIB.pcabo_batch_gp_fit_ard, "info", *self._ard_rows(theta0))
 
     # ---- the two waiting calls in halves (one thread advancing several batches: pcabo.batchrun.run_interleaved) -------------
     def busy(self) -> bool:
@@ -977,8 +914,9 @@ class Batch:
         return rc == 1
 
     def raw_row_buffer(self, q: int) -> np.ndarray:
-        """The (B, q * max_d) buffer gp_eval_begin packs the runs' points into: a caller that writes run b's q x k_b points into
-        `buf[b, :q*k_b].reshape(q, k_b)` itself (and passes those views) saves the copy."""
+        """The (B, q * max_d) buffer gp_eval_begin and acq_score_begin pack the runs' points into: a caller that writes run b's
+        q x k_b points into `buf[b, :q*k_b].reshape(q, k_b)` itself (and passes those views) saves the copy.  Kept from call to
+        call and never cleared: only the first q * k_b entries of a row are read, no need to clear 5 MB per call."""
         buf = getattr(self, "_raw_buf", None)
         if buf is None or buf.shape != (self.B, q * self.max_d):
             buf = self._raw_buf = np.zeros((self.B, q * self.max_d))
@@ -986,12 +924,7 @@ class Batch:
 
     def gp_eval_begin(self, Xq_list, best_f, maximize=False, acq=ACQ_LOG_EI):
         q = Xq_list[0].shape[0]
-        buf = getattr(self, "_raw_buf", None)        # (only the first q * k_b entries of a row are read: no need to clear 5 MB per call)
-        if buf is None or buf.shape != (self.B, q * self.max_d):
-            buf = self._raw_buf = np.zeros((self.B, q * self.max_d))
-        for b, xq in enumerate(Xq_list):
-            if not (isinstance(xq, np.ndarray) and xq.base is buf):       # (raw_row_buffer: the caller drew straight into the row)
-                buf[b, : xq.size] = np.ascontiguousarray(xq, dtype=np.float64).ravel()
+        buf = pack_rows(Xq_list, q * self.max_d, self.raw_row_buffer(q))
         bf = _f64(best_f, (self.B,))
         self._chk(LIB.pcabo_batch_gp_condition_end_eval_begin(self._h, _ptr(buf), q, _ptr(bf), int(bool(maximize)), int(acq)))
         return (buf, q, bf, int(bool(maximize)), int(acq))
@@ -1008,10 +941,7 @@ class Batch:
         """Enqueue the scoring of Xq_list[b] (q x k_b, the same q for all runs) on every run's current model - extended or not,
         fitted or not; the batch's conditioning has been waited for.  Returns the token acq_score_end takes."""
         q = Xq_list[0].shape[0]
-        buf = self.raw_row_buffer(q)
-        for b, xq in enumerate(Xq_list):
-            if not (isinstance(xq, np.ndarray) and xq.base is buf):
-                buf[b, : xq.size] = np.ascontiguousarray(xq, dtype=np.float64).ravel()
+        buf = pack_rows(Xq_list, q * self.max_d, self.raw_row_buffer(q))
         bf = _f64(best_f, (self.B,))
         self._chk(LIB.pcabo_batch_acq_score_begin(self._h, _ptr(buf), q, _ptr(bf), int(bool(maximize)), int(acq)))
         return q
@@ -1027,13 +957,8 @@ class Batch:
         return self.acq_score_end(self.acq_score_begin(Xq_list, best_f, maximize, acq))
 
     def _pack_ics(self, ics_list, bounds_list):
-        B, MD = self.B, self.max_d
         nr = ics_list[0].shape[0]
-        ics, bnd = np.zeros((B, nr * MD)), np.zeros((B, 2 * MD))
-        for b in range(B):
-            ics[b, : ics_list[b].size] = np.ascontiguousarray(ics_list[b], dtype=np.float64).ravel()
-            bnd[b, : bounds_list[b].size] = np.ascontiguousarray(bounds_list[b], dtype=np.float64).ravel()
-        return nr, ics, bnd
+        return nr, self._packed(ics_list[: self.B], nr * self.max_d), self._packed(bounds_list[: self.B], 2 * self.max_d)
 
     def optimize_begin(self, ics_list, bounds_list, best_f, maximize=False, acq=ACQ_LOG_EI, batch_limit=5, maxiter=200):
         """Enqueue the device-resident optimisation; returns a token for optimize_end, or None when the call does not qualify
@@ -1081,9 +1006,7 @@ class Batch:
         """Value and gradient at xq_list[b] (q x k_b, q <= 32) through the evaluation of the device-resident optimiser."""
         B, MD = self.B, self.max_d
         q = xq_list[0].shape[0]
-        xq = np.zeros((B, q * MD))
-        for b in range(B):
-            xq[b, : xq_list[b].size] = np.ascontiguousarray(xq_list[b], dtype=np.float64).ravel()
+        xq = self._packed(xq_list[:B], q * MD)
         bf = _f64(best_f, (B,))
         val, grad = np.zeros((B, q)), np.zeros((B, q * MD))
         self._chk(LIB.pcabo_batch_device_acq_eval(self._h, _ptr(xq), int(q), _ptr(bf), int(bool(maximize)), int(acq), _ptr(val), _ptr(grad)))
@@ -1124,20 +1047,14 @@ class Batch:
         self._chk(LIB.pcabo_batch_get_profile(self._h, _ptr(ms)))
         return dict(zip(("wpca", "gram", "cholesky", "root_inverse_alpha"), ms.tolist()))
 
-    def _pack_z(self, z_list) -> np.ndarray:
-        z = np.zeros((self.B, self.max_d))
-        for b, zb in enumerate(z_list):
-            z[b, : zb.size] = np.asarray(zb, dtype=np.float64).ravel()
-        return z
-
     def inverse_map(self, z_list):
-        z = self._pack_z(z_list)
+        z = self._packed(z_list, self.max_d)
         x = np.empty((self.B, self.d))
         self._chk(LIB.pcabo_batch_inverse_map(self._h, _ptr(z), _ptr(x)))
         return x
 
     def inverse_map_begin(self, z_list) -> None:
-        z = self._pack_z(z_list)
+        z = self._packed(z_list, self.max_d)
         self._chk(LIB.pcabo_batch_inverse_map_begin(self._h, _ptr(z)))
 
     def inverse_map_end(self):
@@ -1204,43 +1121,20 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
-class Comm:
+class Comm(_Handle):
     """RCCL communicator for the final gather of best-so-far values (pcabo_comm_* / pcabo_gather_best of include/pcabo.h)."""
+    _last_error, _destroy = LIB.pcabo_comm_last_error, LIB.pcabo_comm_destroy
+    _NOT_CREATED = "librccl.so could not be opened"
 
     def __init__(self, unique_id: bytes, world: int, rank: int, device: int = 0):
-        self._h = C.c_void_p()
-        rc = LIB.pcabo_comm_create(C.c_char_p(unique_id), int(world), int(rank), int(device), C.byref(self._h))
-        if rc != 0:
-            msg = self._err() if self._h else "librccl.so could not be opened"
-            if self._h:
-                LIB.pcabo_comm_destroy(self._h)
-                self._h = C.c_void_p()
-            raise PcaboError(rc, msg)
+        self._create(LIB.pcabo_comm_create, C.c_char_p(unique_id), int(world), int(rank), int(device))
         self.world, self.rank = int(world), int(rank)
-
-    def _err(self) -> str:
-        buf = C.create_string_buffer(256)
-        LIB.pcabo_comm_last_error(self._h, buf, 256)
-        return buf.value.decode(errors="replace")
 
     def gather_best(self, local) -> np.ndarray:
         local = _f64(local).reshape(-1)
         out = np.empty((self.world, local.shape[0]))
-        rc = LIB.pcabo_gather_best(self._h, _ptr(local), int(local.shape[0]), _ptr(out))
-        if rc != 0:
-            raise PcaboError(rc, self._err())
+        self._chk(LIB.pcabo_gather_best(self._h, _ptr(local), int(local.shape[0]), _ptr(out)))
         return out
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            LIB.pcabo_comm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 def lbfgsb_set_vector_kernels(enabled: bool) -> bool:

@@ -43,25 +43,19 @@ def _table(p: BBOBProblem, stride: int) -> np.ndarray:
     return t
 
 
-class DeviceObjectives:
+class DeviceObjectives(_native._Handle):
     """`problems`: B `BBOBProblem`s of one dimension.  `evaluate(X[B, d])` -> (f[B] incl. f_opt, or the penalty for a
     candidate outside [lb, ub]^d; raw[B] without f_opt, the penalty likewise; oob[B] bool).  `lb`, `ub` and `penalty` are
     read at every call."""
+    _destroy = _native.LIB.pcabo_bbob_destroy           # (no last-error call: a failed creation has one text)
+    _NOT_CREATED = "pcabo_bbob_create failed (no usable HIP device?)"
 
     def __init__(self, problems, device: int = 0, penalty: float = 1000.0):
         self.problems = list(problems)
         self.B = len(self.problems)
         self.d = int(self.problems[0].meta_data.n_variables)
         assert all(int(p.meta_data.n_variables) == self.d for p in self.problems)
-        lib = _native.LIB
-        lib.pcabo_bbob_table_doubles.argtypes = [C.c_int]
-        lib.pcabo_bbob_table_doubles.restype = C.c_int
-        lib.pcabo_bbob_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-        lib.pcabo_bbob_destroy.argtypes = [C.c_void_p]
-        lib.pcabo_bbob_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
-        lib.pcabo_bbob_eval_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
-                                             C.c_void_p]
-        stride = lib.pcabo_bbob_table_doubles(self.d)
+        stride = _native.LIB.pcabo_bbob_table_doubles(self.d)
         if stride < 0:
             raise _native.PcaboError(stride, "dimension not supported by the device objectives")
         tables = np.stack([_table(p, stride) for p in self.problems])
@@ -69,13 +63,8 @@ class DeviceObjectives:
         self.f_opt = np.array([p.f_opt for p in self.problems])
         self.lb, self.ub = float(self.problems[0].bounds.lb[0]), float(self.problems[0].bounds.ub[0])
         self.penalty = float(penalty)
-        self._h = C.c_void_p()
-        rc = lib.pcabo_bbob_create(int(device), self.B, self.d, fid.ctypes.data_as(C.c_void_p),
-                                   tables.ctypes.data_as(C.c_void_p), C.byref(self._h))
-        if rc != 0:
-            if self._h:
-                lib.pcabo_bbob_destroy(self._h)
-            raise _native.PcaboError(rc, "pcabo_bbob_create failed (no usable HIP device?)")
+        self._create(_native.LIB.pcabo_bbob_create, int(device), self.B, self.d, fid.ctypes.data_as(C.c_void_p),
+                     tables.ctypes.data_as(C.c_void_p))
 
     def evaluate(self, X: np.ndarray):
         X = np.ascontiguousarray(X, dtype=np.float64).reshape(self.B, self.d)
@@ -101,14 +90,3 @@ class DeviceObjectives:
             raise _native.PcaboError(rc, "pcabo_bbob_eval_many failed")
         f = np.where(oob != 0, self.penalty, raw + self.f_opt[:, None])
         return f, raw, oob.astype(bool)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _native.LIB.pcabo_bbob_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

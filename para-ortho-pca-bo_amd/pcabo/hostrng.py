@@ -25,9 +25,6 @@ from . import _native
 
 BLOB_BYTES = 5056
 _LIB = _native.LIB
-_LIB.pcabo_torch_randint2.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-_LIB.pcabo_torch_multinomial_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-_LIB.pcabo_boltzmann_pick_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
 
 _native_ok: Optional[bool] = None
 

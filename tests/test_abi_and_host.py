@@ -10,6 +10,62 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+_SCALAR_KINDS = {"int": ctypes.c_int, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64,
+                 "long long": ctypes.c_longlong}
+_POINTEE = {"int": ctypes.c_int, "double": ctypes.c_double, "int64_t": ctypes.c_int64}
+
+
+def _header_prototypes():
+    """{function: (return declaration, [parameter declarations])} of include/pcabo.h, comments and preprocessor lines stripped."""
+    text = open(os.path.join(ROOT, "include", "pcabo.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#[^\n]*", " ", text, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(pcabo_\w+)\s*\(([^()]*)\)\s*;", text):
+        params = [p.strip() for p in params.split(",")]
+        protos[name] = (ret.strip(), [] if params == ["void"] else params)
+    return protos
+
+
+def _accepted(decl, native, named):
+    """The ctypes types the binding may declare for a C declaration (`named`: a parameter, whose last word is its name);
+    ValueError for a kind this test does not know."""
+    words = re.sub(r"\bconst\b", " ", decl).replace("*", " * ").split()
+    if named and words[-1] != "*" and len(words) > 1:
+        words = words[:-1]
+    stars, base = words.count("*"), " ".join(w for w in words if w != "*")
+    if stars == 0 and base in _SCALAR_KINDS:
+        return {_SCALAR_KINDS[base]}
+    if stars == 0 and base == "pcabo_fg_callback":
+        return {native.FG_CALLBACK}
+    if stars == 1 and base == "char":
+        return {ctypes.c_char_p}
+    if stars == 1 and (base in _POINTEE or base == "void" or base.startswith("pcabo_")):
+        return {ctypes.c_void_p} | ({ctypes.POINTER(_POINTEE[base])} if base in _POINTEE else set())
+    if stars == 2 and (base in _POINTEE or base == "void" or base.startswith("pcabo_")):
+        return {ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)}
+    raise ValueError(f"unknown kind of declaration: {decl!r}")
+
+
+def _abi_mismatches(protos, table, native):
+    """One line per function whose entry in the signature table disagrees with its prototype, the function's name first."""
+    out = [f"{name}: in the header, not in the table" for name in sorted(set(protos) - set(table))]
+    out += [f"{name}: in the table, not in the header" for name in sorted(set(table) - set(protos))]
+    for name in sorted(set(protos) & set(table)):
+        ret, params = protos[name]
+        args, _, r = table[name].partition(">")
+        if len(args) != len(params):
+            out.append(f"{name}: {len(params)} parameters in the header, {len(args)} in the table")
+            continue
+        for i, (decl, letter) in enumerate(zip(params, args)):
+            if native.ARG_TYPES[letter] not in _accepted(decl, native, named=True):
+                out.append(f"{name}: parameter {i} is `{decl}`, the table says {letter!r}")
+        if native.ARG_TYPES[r or "i"] not in _accepted(ret, native, named=False):
+            out.append(f"{name}: returns `{ret}`, the table says {(r or 'i')!r}")
+    return out
+
+
 def test_library_exports_every_declared_symbol(native):
     header = open(os.path.join(ROOT, "include", "pcabo.h")).read()
     declared = set(re.findall(r"\b(pcabo_[a-z_0-9]+)\s*\(", header)) - {"pcabo_fg_callback"}
@@ -18,6 +74,36 @@ def test_library_exports_every_declared_symbol(native):
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.pcabo_abi_version() == native.ABI_VERSION
+    # the declarations' types, not only their names: every prototype against the binding's one signature table ...
+    protos = _header_prototypes()
+    assert set(protos) == declared == set(native.SIGNATURES) and native.EXPORTS == list(native.SIGNATURES)
+    assert _abi_mismatches(protos, native.SIGNATURES, native) == []
+    # ... which is what the loaded library carries, for every function (the debug exports, which no header declares, included)
+    for name, code in {**native.SIGNATURES, **native.DEBUG_SIGNATURES}.items():
+        args, _, r = code.partition(">")
+        fn = getattr(native.LIB, name)
+        assert list(fn.argtypes) == [native.ARG_TYPES[c] for c in args] and fn.restype is native.ARG_TYPES[r or "i"], name
+
+
+def test_abi_comparison_names_the_function_that_disagrees(native):
+    """The comparison of the test above is not vacuous: a parameter dropped, a double declared as an int, a missing and a
+    surplus entry, and a wrong return each come back under the function's name; an unknown kind of parameter is an error."""
+    protos, table = _header_prototypes(), dict(native.SIGNATURES)
+    assert table["pcabo_gp_truncate"] == "vi" and table["pcabo_acq_eval"][3] == "d" and table["pcabo_batch_ctx"] == "vi>v"
+    table["pcabo_gp_truncate"] = "v"                                        # one parameter too few
+    code = table["pcabo_acq_eval"]
+    table["pcabo_acq_eval"] = code[:2] + "d" + "i" + code[4:]                # `int q, double best_f` swapped
+    table["pcabo_batch_ctx"] = "vi"                                         # a pointer returned as an int
+    del table["pcabo_get_gram"]
+    table["pcabo_no_such_call"] = "v"
+    bad = _abi_mismatches(protos, table, native)
+    assert sorted(line.split(":")[0] for line in bad) == ["pcabo_acq_eval", "pcabo_acq_eval", "pcabo_batch_ctx", "pcabo_get_gram",
+                                                          "pcabo_gp_truncate", "pcabo_no_such_call"]
+    assert "2 parameters in the header, 1 in the table" in " ".join(bad)
+    with pytest.raises(ValueError):
+        _abi_mismatches({"pcabo_get_gram": ("int", ["pcabo_ctx* ctx", "float* K"])}, {"pcabo_get_gram": "vv"}, native)
+    with pytest.raises(ValueError):
+        _abi_mismatches({"pcabo_get_gram": ("int", ["pcabo_ctx* ctx", "unsigned n"])}, {"pcabo_get_gram": "vi"}, native)
 
 
 def test_no_cpu_fallback_without_device(native):
